@@ -2,6 +2,18 @@
 """bench.py -- Ape-X hot path throughput on MI355X (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+  python bench.py --gpus 1 --steps K --warmup W --full   (+ the other regions, rooflines, CPU baselines, threaded leg)
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
+
+A plain run sets up, warms up, times EXACTLY K steps once (no profiling events, no clock sampling), optionally writes
+the outputs of the last timed step, and prints the result line (`metric`, `value`, `unit`, `ms_per_step`, `dtype`, ...).
+Everything else -- the repeats, the other precisions / reuse modes, the per-kernel table and rooflines, the threaded
+leg, the CPU baselines, the detail record -- runs only with `--full`, which times `--repeats` (default 5) windows of K
+steps per region and reports the median.  (`--gpus N --layout reference`, N > 1, has no such split: its windows
+and detail record are as they were.)  `--dump-outputs DIR` (Ape-X, replicated layout): after the headline's timed
+steps, rank 0 writes what the last of them computed as DIR/<name>.npy (float32 / float64, ~7 MB): the actors' actions,
+Q-values and TD priorities, the learner's IS weights, loss and priorities, and the online net's updated parameters.
+Inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Workload (BASELINE.json configs[1]): Ape-X DQN, 80 actor threads x 80 games = 6,400 envs,
 one MI355X running actors + learner, replay 2^20 (ring 1,310,720 slots, device resident),
@@ -24,7 +36,7 @@ One STEP = what the reference does per env-step of every actor thread plus one l
       -> clip 40 -> RMSprop -> update_priority, hand-written HIP (csrc/learner.hip; RELA_BENCH_LEARNER=torch
       runs PyTorch autograd instead); actor weights re-published every 20 steps, target net every 2,500.
 
-Arithmetic: three modes, all timed by ONE run as regions of the same K steps (`summary`), `value` = the one `--precision`
+Arithmetic: three modes, all timed by ONE --full run as regions of the same K steps (`summary`), `value` = the one `--precision`
 names.  `f32x3` (the default): f32 results at f32 accuracy from the bf16 matrix cores -- conv2 / conv3 / fc of the
 actors' forwards (and the learner's conv forwards and weight-gradient GEMMs) take every f32 operand as THREE exact bf16
 parts and six products with f32 accumulation (csrc/gemm_f32emu.h); against an f64 evaluation its Q-values are as close
@@ -34,7 +46,7 @@ mode (two bf16 parts per operand = 16-bit significands, conv1 on the int8 matrix
 |dQ| < 2e-5 max|Q| against the f32 path) -- a narrower arithmetic, never `value` unless asked for.
 Regions: f32x3_mode, f32x3_strict (all 4 forwards of the reference), f32_mode, strict, fast_mode, fast_no_reuse.
 
-Output (rank 0): ONE compact JSON line on stdout (<= 1,900 characters: the driver keeps the last 2,000 of stdout) with the
+Output (rank 0, --full): ONE compact JSON line on stdout (<= 1,900 characters: the driver keeps the last 2,000 of stdout) with the
 contract's keys, `roofline` (live HIP events around the dominant forward kernel inside the timed region, both the
 algorithmic and the issued-MFMA fraction where they differ, the sampled shader clock), `cpu_baseline` (the reference's
 own CPU-thread actor path from oracle/_ref, pinned to the cgroup's CPU share) and `summary` (the four regions and the
@@ -143,11 +155,12 @@ class ClockSampler:
     different boxes of the pool, and without the sustained clock two rounds' lines cannot be compared.  Best effort:
     summary() is {} when the files are not readable."""
 
-    def __init__(self, pci_bus_id=None, period=0.02):
+    def __init__(self, pci_bus_id=None, period=0.02, enabled=True):
         import glob
         import threading
 
         self.freq_file = self.dpm_file = self.power_file = None
+        self.enabled = enabled
         cards = sorted(glob.glob("/sys/class/drm/card[0-9]*/device"))
         if pci_bus_id:
             want = [c for c in cards if os.path.basename(os.path.realpath(c)).lower() == pci_bus_id.lower()]
@@ -185,7 +198,7 @@ class ClockSampler:
             self._stop.wait(self.period)
 
     def __enter__(self):
-        if self.freq_file or self.dpm_file:
+        if self.enabled and (self.freq_file or self.dpm_file):
             self._th.start()
         return self
 
@@ -269,6 +282,11 @@ def emit(line, detail, tag):
     except OSError:
         pass
     print(json.dumps(detail), file=sys.stderr, flush=True)
+    return print_line(line)
+
+
+def print_line(line):
+    """Prints the compact JSON result line (<= LINE_BUDGET characters) on stdout."""
     line = rnd(line)
     for k in ("detail", "clock", "grad_steps_per_s", "train_samples_per_s"):  # dropped in this order if it ever gets too long
         if len(json.dumps(line)) <= LINE_BUDGET:
@@ -278,6 +296,25 @@ def emit(line, detail, tag):
     assert len(s) <= LINE_BUDGET, "bench line is %d characters: the driver would cut it" % len(s)
     print(s, flush=True)
     return s
+
+
+DUMP_BUDGET = 64 << 20  # bytes, all files of --dump-outputs together
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: every (name -> tensor) as out_dir/<name>.npy, floating point as float32 (float64 stays),
+    integers and booleans as float64 (exact for the values dumped here).  The caller synchronizes the device first.
+    Nothing is written when the arrays would exceed `budget` bytes together."""
+    out = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        out[name] = a.astype(np.float64 if a.dtype.kind in "iub" or a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > budget:
+        raise ValueError("--dump-outputs would write %d bytes, more than %d" % (total, budget))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # rela_prof label -> substring of the HIP kernel name in the rocprofv3 CSVs
@@ -688,9 +725,9 @@ def bench_r2d2(args, world, rank, device):
         # the roofline's kernel only (the actors' gate GEMM in whichever form the mode runs it; r5: the f32x3 label was missing
         # here, and the line priced the h-only kernel of that mode with the whole gate GEMM's FLOPs)
         capi.lib.rela_prof_set_filter(b"lstm_gates_mfma,lstm_gates_x_bf16,lstm_gates_x_f32x3")
-        capi.lib.rela_prof_enable(1)
+        capi.lib.rela_prof_enable(1 if args.full else 0)
         add0 = replay.num_add()
-        with ClockSampler(pci) as clk:
+        with ClockSampler(pci, enabled=args.full) as clk:
             ms = [bracketed(args.steps) / args.steps * 1e3 for _ in range(args.repeats)]
         capi.lib.rela_prof_enable(0)
         adds = replay.num_add() - add0
@@ -704,6 +741,27 @@ def bench_r2d2(args, world, rank, device):
                 "env_steps_per_s": R2_ROWS * world / (med * 1e-3)}
 
     head = timed_region(args.precision, 1, 0)
+    ms_med = head["ms_per_step"]
+    parallelism = "single" if world == 1 else "actor-shards%d+replay-partitions+grad-allreduce" % world
+    line = {"metric": "env-steps/s (R2D2 Atari 84x84x4, seq 80 / burn-in 40 / n 3, actor tick + learner grad-step)",
+            "value": head["env_steps_per_s"], "unit": "env-steps/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_med, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None,
+            "dtype": {"f32": "f32", "f32x3": "f32 (trunk conv2 / conv3: f32 operands as 3 exact bf16 parts on bf16 MFMA; "
+                      "f32-accurate)"}.get(args.precision, "f32 results from split-bf16 MFMA (16-bit significands)"),
+            "data": "synthetic",
+            "config": {"workload": "R2D2 LSTM 40x80 envs/GPU (C4 shapes), seq 80 / burn-in 40 / n 3, B=64, A=18; "
+                                   "device-resident static frames", "parallelism": parallelism},
+            "grad_steps_per_s": 1e3 / ms_med}
+    if not args.full:
+        assert replay.debug_state()["dev_error"] == 0
+        learner.check()
+        if rank == 0:
+            print_line(line)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     capi.lib.rela_prof_set_filter(None)
     capi.lib.rela_prof_enable(1)
     k_all = max(5, args.steps // 10)
@@ -764,14 +822,13 @@ def bench_r2d2(args, world, rank, device):
                         or k in ("replay_targets", "replay_search", "replay_pop", "replay_is_weights")) / k_all
         sample_bytes = 4 * st["safe_size"] + B_LOCAL * sum(replay.row_bytes)
         learner_ms = sum(v["total_ms"] for k, v in prof_all.items() if k.startswith("learner_")) / k_all
-        ms_med = head["ms_per_step"]
         dtype = {"f32": "f32", "f32x3": "f32 (every trunk forward and the input half of every forward gate GEMM with f32 operands as "
                  "three exact bf16 parts on the bf16 MFMA, csrc/gemm_s3.h: f32 accuracy; recurrences, heads, backward in exact f32)"}.get(
             args.precision,
             "f32 results from split-bf16 MFMA (bf16 hi+lo operands, f32 accumulate): the actors' conv trunks and gate GEMM "
             "(h, c, Q within 4e-6), the learner's trunks, LSTM GEMMs and conv gradients; recurrences, cells, heads in f32")
         detail = {
-            "metric": "env-steps/s (R2D2 Atari 84x84x4, seq 80 / burn-in 40 / n 3, actor tick + learner grad-step)",
+            "metric": line["metric"],
             "value": head["env_steps_per_s"], "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_med, "repeats": args.repeats, "ms_per_step_repeats": head["ms"],
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
@@ -781,8 +838,7 @@ def bench_r2d2(args, world, rank, device):
                                    "job; device-resident static frames, rewards / terminals from the host"
                                    % args.replay_cap,
                        "envs_per_gpu": R2_ROWS, "replay_capacity": args.replay_cap, "learner_batch": R2_BATCH,
-                       "learner_batch_per_gpu": B_LOCAL, "parallelism": "single" if world == 1 else
-                       "actor-shards%d+replay-partitions+grad-allreduce" % world},
+                       "learner_batch_per_gpu": B_LOCAL, "parallelism": parallelism},
             "grad_steps_per_s": 1e3 / ms_med, "train_samples_per_s": R2_BATCH * 1e3 / ms_med,
             "buffer_add_per_s": head["adds_per_s"], "learner": "hip (csrc/learner_r2d2.hip)",
             "learner_kernel_ms_per_step": learner_ms,
@@ -804,18 +860,9 @@ def bench_r2d2(args, world, rank, device):
             replay.close()
             torch.cuda.empty_cache()
             detail["cpu_baseline"] = cpu_baseline_reference_r2d2()
-        line = {"metric": detail["metric"], "value": detail["value"], "unit": "env-steps/s", "n_gpus": world,
-                "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_med, "higher_is_better": True,
-                "scaling": "weak", "vs_baseline": None,
-                "dtype": {"f32": "f32", "f32x3": "f32 (trunk conv2 / conv3: f32 operands as 3 exact bf16 parts on bf16 MFMA; "
-                          "f32-accurate)"}.get(args.precision, "f32 results from split-bf16 MFMA (16-bit significands)"),
-                "data": "synthetic",
-                "config": {"workload": "R2D2 LSTM 40x80 envs/GPU (C4 shapes), seq 80 / burn-in 40 / n 3, B=64, A=18; "
-                                       "device-resident static frames", "parallelism": detail["config"]["parallelism"]},
-                "grad_steps_per_s": 1e3 / ms_med,
-                "roofline": {k: roof.get(k) for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic",
-                                                      "avg_launch_ms", "frac_issued", "sclk_mhz") if roof.get(k) is not None
-                             or k == "traffic"}}
+        line["roofline"] = {k: roof.get(k) for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic",
+                                                     "avg_launch_ms", "frac_issued", "sclk_mhz") if roof.get(k) is not None
+                            or k == "traffic"}
         cb = detail.get("cpu_baseline")
         if cb is not None:
             line["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
@@ -1041,14 +1088,20 @@ def bench_reference_layout(args, world, rank, device, rehearsal):
     dist.destroy_process_group()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # default: 5 repeats x 300 steps of ~1.5 ms = ~2.3 s of timed work per region
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="how many times every K-step timed region is repeated (the line reports the median repeat)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how many times every K-step timed region is repeated (the line reports the median repeat); "
+                         "default 5 with --full and for --layout reference, else 1: a plain run times exactly --steps steps")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other precision / reuse regions, the per-kernel table and rooflines "
+                         "(live HIP events, sampled shader clock), the threaded leg, the CPU baselines and the detail record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (Ape-X, replicated layout)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-threaded", action="store_true", help="skip the threaded leg (rela.Context + C++ actor threads)")
     ap.add_argument("--replay-cap", type=int, default=None)
@@ -1077,7 +1130,19 @@ def main():
                          "(rela_amd/parallel.py, r4); packed = one packed gather / two broadcasts through the collective (r3)")
     ap.add_argument("--algo", default="apex", help="apex (BASELINE.json's metric, the default) | r2d2 (config C4's "
                                                    "sequence shape: seq 80 / burn-in 40 / n 3, 3200 envs, B = 64)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    reference_layout = args.layout == "reference" and args.gpus > 1
+    if args.repeats is None:  # (the reference layout's line has no plain / --full split: its windows stay as they were)
+        args.repeats = 5 if args.full or reference_layout else 1
+    if args.dump_outputs and (args.algo != "apex" or reference_layout):
+        ap.error("--dump-outputs covers the Ape-X step of the replicated layout only")
+    if args.dump_outputs and os.environ.get("RELA_BENCH_ONLY"):
+        ap.error("--dump-outputs needs the whole step: RELA_BENCH_ONLY times one side of it")
+    return args
+
+
+def main():
+    args = parse_args()
     if args.replay_cap is None:
         args.replay_cap = REPLAY_CAP if args.algo == "apex" else R2_REPLAY_CAP
 
@@ -1192,10 +1257,12 @@ def main():
     if os.environ.get("RELA_BENCH_ONE_STREAM", "0") == "1":  # diagnosis: actor tick and learner step strictly one after the
         actor_stream = main_stream                           # other (the replay keeps its own streams)
 
+    last = {}  # the arrays the last step handed back (device buffers the next step overwrites), for --dump-outputs
+
     def actor_tick():
         i = step_idx[0] % n_pool
         with torch.cuda.stream(actor_stream):
-            engine.act(online)
+            last["action"] = engine.act(online)
             engine.post_step(reward_pool[i], term_pool[i], online, target, nonblocking=True)
 
     # The HIP learner's step is software-pipelined with the replay (RELA_BENCH_PIPELINE=0: strictly one after the
@@ -1245,8 +1312,10 @@ def main():
         if hip_learner is not None:
             loss, prio = hip_learner.step(batch, weight, world_size=world)
             replay.update_priority(prio)
+            last.update(weight=weight, loss=loss, priority=prio)
             return
         loss, prio = agent.loss(batch, sync_priority=False)
+        last.update(weight=weight, loss=loss, priority=prio)
         (loss * weight).mean().backward()
         if world > 1:
             allreduce_grads(agent.online_net.parameters(), world)
@@ -1313,6 +1382,7 @@ def main():
                 weight = global_weights(weight, size_at_sample)
                 if PIPE:
                     loss, prio = hip_learner.loss(batch, weight)
+                    last.update(weight=weight, loss=loss, priority=prio)
                     lap("loss")
                     replay.update_priority(prio)
                     lap("update_priority")
@@ -1384,7 +1454,7 @@ def main():
     # of them); timing all ~100 kernels of a step costs 0.37 ms of the step itself, so the full
     # per-kernel table comes from a short untimed pass after the timed region.
     ROOF_FILTER = b"conv12_fused,conv1_bf16x3,conv2_mfma,conv3_mfma,fc_mfma"
-    NOPROF = os.environ.get("RELA_BENCH_NOPROF") == "1"
+    NOPROF = os.environ.get("RELA_BENCH_NOPROF") == "1" or not args.full
     buf = C.create_string_buffer(1 << 16)
 
     def prof_summary():
@@ -1425,7 +1495,7 @@ def main():
         capi.lib.rela_prof_set_filter(b"conv12_fused" if precision in ("f32x3", "bf16x2") else ROOF_FILTER)
         capi.lib.rela_prof_enable(0 if NOPROF else 1)
         add0 = replay.num_add()
-        with ClockSampler(pci) as clk:
+        with ClockSampler(pci, enabled=args.full) as clk:
             ms = [bracketed(args.steps) / args.steps * 1e3 for _ in range(args.repeats)]
         capi.lib.rela_prof_enable(0)
         adds = replay.num_add() - add0
@@ -1441,6 +1511,36 @@ def main():
                 "forwards_per_tick": fwd_cnt / (args.steps * args.repeats) if ONLY != "learner" else 0}
 
     head = timed_region(args.precision, 1, 0)
+    if args.dump_outputs and rank == 0:
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, {
+            "actor_action": last["action"], "actor_q": engine.q[0], "actor_priority": engine.prio,
+            "learner_is_weight": last["weight"], "learner_loss": last["loss"], "learner_priority": last["priority"],
+            "online_params": hip_learner.flat()[0] if hip_learner is not None else
+            torch.cat([p.detach().reshape(-1) for p in agent.online_net.parameters()])})
+    line = {"metric": "env-steps/s (Ape-X Atari 84x84x4, actor tick + learner grad-step)", "value": head["env_steps_per_s"],
+            "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": {"f32": "f32", "f32x3": "f32 (f32 operands as 3 exact bf16 parts on bf16 MFMA; f32-accurate)"}.get(
+                args.precision, "f32 results from split-bf16 MFMA (16-bit significands)"),
+            "data": "synthetic",
+            "config": {"workload": "Ape-X DQN 80x80 envs/GPU, actor+learner on one MI355X, replay 2^20, B=512, A=18, n=3; "
+                                   "device-resident static frames",
+                       "parallelism": ("actor-shards%d+replay-partitions+grad-allreduce" % world) if world > 1 else "single"},
+            "grad_steps_per_s": 1e3 / head["ms_per_step"]}
+    if world > 1:
+        line["comm"] = {"backend": dist.get_backend(),
+                        "rccl_ranks": dist.get_world_size() if dist.get_backend() == "nccl" else 0}
+    if ONLY:
+        line["diagnostic_only"] = ONLY
+    if not args.full:
+        assert replay.debug_state()["dev_error"] == 0, "replay reported device error"
+        if rank == 0:
+            print_line(line)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # untimed: the same step with every kernel timed, for the kernels_ms_per_step table
     capi.lib.rela_prof_set_filter(None)
@@ -1574,7 +1674,7 @@ def main():
                                                                  "(rela_ipc_allreduce_run, no collective)")
                                         + "; IS weights: SUM of the partition size + MAX of the weight maximum"}
         detail = {
-            "metric": "env-steps/s (Ape-X Atari 84x84x4, actor tick + learner grad-step)",
+            "metric": line["metric"],
             "value": head["env_steps_per_s"], "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_med, "repeats": args.repeats, "ms_per_step_repeats": head["ms"],
             "ms_per_step_note": "the K-step region (barrier + synchronize on both sides, MAX over ranks) is timed "
@@ -1657,24 +1757,12 @@ def main():
             for env in ("fresh", "sliding"):
                 e = th.get(env, {})
                 summary["threaded_" + env] = e.get("error", [round(e.get("without_sampler", 0)), round(e.get("with_sampler", 0))])
-        line = {"metric": detail["metric"], "value": detail["value"], "unit": "env-steps/s", "n_gpus": world,
-                "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_med, "higher_is_better": True,
-                "scaling": "weak", "vs_baseline": None,
-                "dtype": {"f32": "f32", "f32x3": "f32 (f32 operands as 3 exact bf16 parts on bf16 MFMA; f32-accurate)"}.get(
-                    args.precision, "f32 results from split-bf16 MFMA (16-bit significands)"),
-                "data": "synthetic",
-                "config": {"workload": "Ape-X DQN 80x80 envs/GPU, actor+learner on one MI355X, replay 2^20, B=512, A=18, n=3; "
-                                       "device-resident static frames", "forwards_per_tick": round(head["forwards_per_tick"], 2),
-                           "parallelism": detail["config"]["parallelism"]},
-                "grad_steps_per_s": 1e3 / ms_med, "roofline": short_roof(roof)}
-        if comm is not None:
-            line["comm"] = {"backend": comm["backend"], "rccl_ranks": comm["rccl_ranks"]}
+        line["config"]["forwards_per_tick"] = round(head["forwards_per_tick"], 2)
+        line["roofline"] = short_roof(roof)
         cb = detail.get("cpu_baseline")
         if cb is not None:
             line["cpu_baseline"] = {"value": cb["value"], "unit": cb["unit"], "cores": cb["cores"], "kind": cb["kind"],
                                     "sample": cb["sample"][:150]}
-        if ONLY:
-            line["diagnostic_only"] = ONLY
         line["summary"] = summary
         emit(line, detail, "apex_n%d" % world)
     if world > 1:

@@ -52,3 +52,47 @@ def test_launch_census_symbols_and_binding():
     with capi.launch_census() as c:
         pass
     assert c.counts == {}
+
+
+def test_plain_run_times_exactly_steps_and_full_keeps_the_repeats():
+    b = _bench()
+    plain = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (plain.full, plain.repeats, plain.steps, plain.warmup, plain.dump_outputs) == (False, 1, 7, 2, None)
+    full = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2", "--full"])
+    assert full.full and full.repeats == 5
+    assert b.parse_args(["--gpus", "1", "--full", "--repeats", "3"]).repeats == 3
+    # the multi-GPU reference layout has no plain / --full split: its windows stay at 5
+    assert b.parse_args(["--gpus", "2", "--layout", "reference"]).repeats == 5
+    assert b.parse_args(["--gpus", "1", "--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_dump_outputs_is_refused_where_it_would_not_cover_the_whole_step(monkeypatch):
+    import pytest
+
+    b = _bench()
+    for argv in (["--algo", "r2d2"], ["--gpus", "2", "--layout", "reference"]):
+        with pytest.raises(SystemExit):
+            b.parse_args(argv + ["--dump-outputs", "d"])
+    monkeypatch.setenv("RELA_BENCH_ONLY", "learner")
+    with pytest.raises(SystemExit):
+        b.parse_args(["--dump-outputs", "d"])
+
+
+def test_dump_outputs_dtypes_and_budget(tmp_path):
+    import numpy as np
+    import pytest
+    import torch
+
+    b = _bench()
+    arrays = {"action": torch.arange(5, dtype=torch.int64), "flag": torch.tensor([True, False]),
+              "q": torch.randn(3, 4), "h": torch.randn(2, dtype=torch.float16), "d": torch.ones(2, dtype=torch.float64)}
+    b.dump_outputs(str(tmp_path / "out"), arrays)
+    got = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in arrays}
+    assert {n: a.dtype for n, a in got.items()} == {"action": np.float64, "flag": np.float64, "q": np.float32,
+                                                    "h": np.float32, "d": np.float64}
+    assert got["action"].tolist() == [0, 1, 2, 3, 4] and got["flag"].tolist() == [1.0, 0.0]
+    np.testing.assert_array_equal(got["q"], arrays["q"].numpy())
+    assert b.DUMP_BUDGET == 64 << 20
+    with pytest.raises(ValueError):  # over budget: nothing is written
+        b.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(1025), "y": torch.zeros(1024)}, budget=8192)
+    assert not (tmp_path / "big").exists()

@@ -10,5 +10,5 @@ for set in "fetch:FETCH_SIZE" "write:WRITE_SIZE" "sq:GRBM_GUI_ACTIVE SQ_WAVE_CYC
 done
 python tools/pmc_table.py $O/pmc_r2d2 $O/traffic_r2d2.json > $O/pmc_table_r2d2.md 2>&1; cat $O/pmc_table_r2d2.md | cut -c1-200
 find $O -name "*kernel_trace.csv" -size +3M -delete; find $O -name "*.db" -delete 2>/dev/null
-python bench.py --algo r2d2 --steps 60 --warmup 10 --repeats 3 > $O/bench_r2d2.json 2> /dev/null; echo "bench r2d2 rc=$?"; tail -c 1700 $O/bench_r2d2.json
+python bench.py --full --algo r2d2 --steps 60 --warmup 10 --repeats 3 > $O/bench_r2d2.json 2> /dev/null; echo "bench r2d2 rc=$?"; tail -c 1700 $O/bench_r2d2.json
 cp gpurun_out/bench_detail_r2d2_n1.json $O/bench_r2d2_detail.json 2>/dev/null
