@@ -94,6 +94,18 @@ int rela_replay_units_write(rela_replay* r, int64_t first_seq, int count, const 
 int rela_replay_set_block_min_unit(rela_replay* r, int first_slot, int n, int64_t min_seq);
 int rela_replay_dedup_info(const rela_replay* r, int* units_per_stack, int64_t* unit_bytes, int64_t* unit_capacity);
 
+/* The sequence-schema counterpart (RNNPrioritizedReplay): field `field` holds steps[field] = T stacks per slot, kept
+ * as [T][units_per_stack] int32 references into the unit ring (units_per_stack 1: whole stacks, any env; 4: planes,
+ * sliding-stack envs only).  The reference -1 stands for an all-zero unit (padLike, rela/types.cc:69-80).  The ring
+ * holds ring * units_per_slot + guard_units units; the unit accounting is that of rela_replay_set_schema_dedup with
+ * `ring` replaced by ring * units_per_slot.  sample() rebuilds the time-major [T][batch] stacks of the plain sequence
+ * schema.  Such a partition is not exported: rela_replay_export_ipc / _chunks refuse it with RELA_EINVAL.         */
+int rela_replay_set_schema_seq_dedup(rela_replay* r, int nfields, const int64_t* row_bytes, const int32_t* steps,
+                                     int field, int64_t unit_bytes, int units_per_stack, int64_t units_per_slot,
+                                     int64_t guard_units);
+/* T of a sequence schema with de-duplicated stacks; 0 for the transition schema or no de-duplication */
+int rela_replay_dedup_steps(const rela_replay* r);
+
 /* blockAppend in its three phases (prioritized_replay.h:43-78), for producers that assemble a
  * block piecewise (the R2D2 actor emits several sequences per pop):
  *   begin  :46-56  reserve n slots (blocks while the ring is full unless nonblocking)
@@ -458,6 +470,13 @@ int64_t rela_r2d2_actor_num_act(const rela_r2d2_actor* a);
  * act() ran on this tick, and online_net(obs, hid) (:89) the step act() ran n ticks ago on the same frames, recurrent
  * state (historyHidden_.front()) and legal mask: with unchanged weights both are reused bit-identically.
  * on = 1 (default): both; 2: only the one of next_obs; 0: recompute */
+/* Frame-stack de-duplication of the sequence windows: the replay must have been given rela_replay_set_schema_seq_dedup
+ * with the same units_per_stack and T = burn_in + seq_len + multi_step.  Every stack the shard acts on enters the unit
+ * ring once (1: whole stack; 4: one new plane per env-step, sliding-stack envs only, as rela_apex_actor_set_dedup) and
+ * the windows hold [T][units_per_stack] references instead of frames.  A tick whose units could not be stored
+ * (nonblocking) drops every sequence that contains it; post_step reports that as a dropped piece.
+ * Call once, before the first act().                                                              */
+int rela_r2d2_actor_set_dedup(rela_r2d2_actor* a, int units_per_stack);
 int rela_r2d2_actor_set_reuse(rela_r2d2_actor* a, int on);
 /* diagnostics: current recurrent state (which = 0: h, 1: c) f32[rows,512]; last step priorities */
 const float* rela_r2d2_actor_hidden_dev(const rela_r2d2_actor* a, int which);

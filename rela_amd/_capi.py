@@ -126,6 +126,8 @@ _sig("rela_replay_units_reserve", i32, [vp, i32, i32, P(i64), P(C.c_int32)])
 _sig("rela_replay_units_write", i32, [vp, i64, i32, vp, i64, vp])
 _sig("rela_replay_set_block_min_unit", i32, [vp, i32, i32, i64])
 _sig("rela_replay_dedup_info", i32, [vp, P(i32), P(i64), P(i64)])
+_sig("rela_replay_set_schema_seq_dedup", i32, [vp, i32, P(i64), P(C.c_int32), i32, i64, i32, i64, i64])
+_sig("rela_replay_dedup_steps", i32, [vp])
 _sig("rela_replay_begin_add", i32, [vp, i32, i32, P(i32)])
 _sig("rela_replay_write_rows", i32, [vp, i32, i32, i32, P(vp), vp])
 _sig("rela_replay_write_rows_gather", i32, [vp, i32, i32, vp, P(vp), P(vp), vp])
@@ -197,6 +199,7 @@ _sig("rela_r2d2_actor_act", i32, [vp, vp, vp, vp, vp, vp, P(vp), vp])
 _sig("rela_r2d2_actor_post_step", i32, [vp, vp, vp, vp, vp, i32, P(i32), vp])
 _sig("rela_r2d2_actor_num_act", i64, [vp])
 _sig("rela_r2d2_actor_set_reuse", i32, [vp, i32])
+_sig("rela_r2d2_actor_set_dedup", i32, [vp, i32])
 _sig("rela_r2d2_actor_hidden_dev", vp, [vp, i32])
 _sig("rela_r2d2_actor_last_priority_dev", vp, [vp])
 _sig("rela_apex_learner_create", i32, [P(vp), i32, i32, i32, f32, i32, f32, f32, f32, i32])

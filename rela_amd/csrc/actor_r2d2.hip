@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.h"
+#include "dedup_refs.h"
 #include "prof.h"
 #include "r2d2_seq_core.h"
 
@@ -31,7 +32,8 @@ constexpr int kHid = 512;
 constexpr int kT = 256;
 
 struct Windows {
-  uint8_t* s;     // [R][T][28224]
+  uint8_t* s;     // [R][T][28224]   (null with de-duplication)
+  int32_t* sref;  // [R][T][ups]     de-duplication (rela_r2d2_actor_set_dedup): references instead of frames, -1 = pad
   float* eps;     // [R][T]
   float* legal;   // [R][T][A]
   int64_t* a;     // [R][T]
@@ -41,6 +43,7 @@ struct Windows {
   float* prio;    // [R][seq+n]   per-step priorities (batchSeqPriority_)
   float *h0, *c0, *nh0, *nc0;  // [R][512]  batchH0_ / batchNextH0_
   int T, A, seq, burn, n;
+  int ups;  // 0: frames in `s`; 1 / 4: references in `sref`
 };
 
 __device__ __forceinline__ void block_copy16(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, int64_t bytes) {
@@ -61,11 +64,16 @@ __global__ __launch_bounds__(kT) void r2d2_write_step(Windows w, const int32_t* 
                                                      const float* __restrict__ reward,
                                                      const uint8_t* __restrict__ term, const float* __restrict__ boot,
                                                      const float* __restrict__ prio_step,
-                                                     const float* __restrict__ hid_h, const float* __restrict__ hid_c) {
+                                                     const float* __restrict__ hid_h, const float* __restrict__ hid_c,
+                                                     const int32_t* __restrict__ refs) {
   const int i = blockIdx.x;
   const int j = slot[i];
-  block_copy16(w.s + ((int64_t)i * w.T + j) * kObs, obs + (int64_t)i * kObs, kObs);
   const int64_t o = (int64_t)i * w.T + j;
+  if (w.ups > 0) {
+    for (int k = threadIdx.x; k < w.ups; k += blockDim.x) w.sref[o * w.ups + k] = refs[(int64_t)i * w.ups + k];
+  } else {
+    block_copy16(w.s + o * kObs, obs + (int64_t)i * kObs, kObs);
+  }
   for (int k = threadIdx.x; k < w.A; k += blockDim.x) w.legal[o * w.A + k] = legal[(int64_t)i * w.A + k];
   if (threadIdx.x == 0) {
     w.eps[o] = eps[i];
@@ -95,7 +103,11 @@ __global__ __launch_bounds__(kT) void r2d2_pad(Windows w, const int32_t* __restr
   const int j = begin + blockIdx.y;
   if (j >= end) return;
   const int64_t o = (int64_t)env * w.T + j;
-  block_zero16(w.s + o * kObs, kObs);
+  if (w.ups > 0) {
+    for (int k = threadIdx.x; k < w.ups; k += blockDim.x) w.sref[o * w.ups + k] = -1;  // the all-zero unit
+  } else {
+    block_zero16(w.s + o * kObs, kObs);
+  }
   for (int k = threadIdx.x; k < w.A; k += blockDim.x) w.legal[o * w.A + k] = 0.f;
   if (threadIdx.x == 0) {
     w.eps[o] = 0.f;
@@ -114,7 +126,11 @@ __global__ __launch_bounds__(kT) void r2d2_carry(Windows w, const int32_t* __res
   const int64_t base = (int64_t)env * w.T;
   for (int j = 0; j < w.burn + w.n; ++j) {
     const int64_t d = base + j, s = base + w.seq + j;
-    block_copy16(w.s + d * kObs, w.s + s * kObs, kObs);
+    if (w.ups > 0) {
+      for (int k = threadIdx.x; k < w.ups; k += blockDim.x) w.sref[d * w.ups + k] = w.sref[s * w.ups + k];
+    } else {
+      block_copy16(w.s + d * kObs, w.s + s * kObs, kObs);
+    }
     for (int k = threadIdx.x; k < w.A; k += blockDim.x) w.legal[d * w.A + k] = w.legal[s * w.A + k];
     if (threadIdx.x == 0) {
       w.eps[d] = w.eps[s];
@@ -177,6 +193,15 @@ __global__ void r2d2_reset_hidden(const uint8_t* __restrict__ term, int R, float
   }
 }
 
+// priorities of the sequences a piece keeps (de-duplication drops those that contain an unstored tick)
+__global__ void r2d2_pick(const float* __restrict__ agg, const int32_t* __restrict__ qs, int m, float* __restrict__ out) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < m) out[k] = agg[qs[k]];
+}
+
+constexpr int64_t kPlane = 84 * 84;
+constexpr int64_t kPadTick = -1, kLostTick = -2;  // de-duplication: window entries that are padding / an unstored tick
+
 }  // namespace
 
 struct rela_r2d2_actor {
@@ -219,6 +244,19 @@ struct rela_r2d2_actor {
   std::vector<uint8_t> h_term;  // [n+1][R] host copy: the bookkeeping needs the flags
   SeqBook* book = nullptr;
   SeqPlan plan;
+  // frame-stack de-duplication (rela_r2d2_actor_set_dedup; replay side: rela_replay_set_schema_seq_dedup).  Every tick the
+  // stack acted on enters the unit ring once, as in the Ape-X shard (actor.hip); ref_hist is the n-step ring of its
+  // references, and the windows (w.sref) receive those of obs_t.
+  int dd_ups = 0;
+  int64_t dd_cap = 0;
+  int32_t* ref_hist = nullptr;       // [n+1][R][ups]
+  std::vector<uint8_t> refs_valid;   // [n+1] the slot's units were stored
+  int tick_win = 0;                  // T + n + 8 ticks: the oldest unit a sequence emitted now can refer to is T + n + 3 back
+  std::vector<int64_t> tick_seq;     // [tick_win] first unit sequence number of a tick (ring by tick); unstored: a lower bound
+  int64_t tick = 0, seq_hint = 0;    // ticks so far; the unit sequence number after this shard's last reservation
+  std::vector<int64_t> win_tick;     // [R][T] host: the tick each window entry holds (kPadTick, kLostTick)
+  float* agg_kept = nullptr;         // [2R] priorities of the kept sequences of one piece
+  int32_t* d_kept = nullptr;         // [2R]
   HostStage stage;  // pinned staging of the per-tick index plans (one segment per post_step)
 };
 
@@ -337,7 +375,7 @@ extern "C" void rela_r2d2_actor_destroy(rela_r2d2_actor* a) {
                 a->tmp_c, a->eps,    a->legal,  a->eps_hist, a->legal_hist, a->q,         a->out_r,  a->out_b,  a->prio_step, a->out_t, a->w.s,
                 a->w.eps, a->w.legal, a->w.a,   a->w.reward,  a->w.term, a->w.boot, a->w.prio, a->w.h0,   a->w.c0,
                 a->w.nh0, a->w.nc0,  a->prow,   a->lens,      a->agg,    a->d_slot, a->d_flags, a->d_ranges, a->d_emits, a->d_gather,
-                a->d_envs, a->ws, a->q_hist, a->restart, a->fresh_planes};
+                a->d_envs, a->ws, a->q_hist, a->restart, a->fresh_planes, a->ref_hist, a->w.sref, a->agg_kept, a->d_kept};
   for (void* p : ps) (void)hipFree(p);
   a->stage.destroy();
   delete a->book;
@@ -374,6 +412,38 @@ extern "C" int rela_r2d2_actor_set_reuse(rela_r2d2_actor* a, int on) {
   RELA_CHECK(a, RELA_EINVAL, "rela_r2d2_actor_set_reuse: bad arguments");
   RELA_CHECK(on >= 0 && on <= 2, RELA_EINVAL, "rela_r2d2_actor_set_reuse: 0 (off), 1 (on) or 2 (next_obs only)");
   a->reuse_mode = on;
+  return RELA_OK;
+}
+extern "C" int rela_r2d2_actor_set_dedup(rela_r2d2_actor* a, int units_per_stack) {
+  RELA_CHECK(a && a->replay && (units_per_stack == 1 || units_per_stack == 4), RELA_EINVAL,
+             "rela_r2d2_actor_set_dedup: needs a replay and 1 (stack units) or 4 (plane units)");
+  RELA_CHECK(a->count == 0 && a->act_calls == 0 && a->dd_ups == 0, RELA_ESTATE,
+             "rela_r2d2_actor_set_dedup: call it once, before the first act()");
+  int ups = 0;
+  int64_t ub = 0, cap = 0;
+  int rc = rela_replay_dedup_info(a->replay, &ups, &ub, &cap);
+  if (rc != RELA_OK) return rc;
+  const int steps = rela_replay_dedup_steps(a->replay);
+  RELA_CHECK(ups == units_per_stack && ub * ups == kObs && steps == a->T, RELA_EINVAL,
+             "rela_r2d2_actor_set_dedup: the replay's schema has %d units of %lld bytes per stack and %d steps per slot "
+             "(this shard: %d steps; needs rela_replay_set_schema_seq_dedup)", ups, (long long)ub, steps, a->T);
+  DeviceGuard g(a->device);
+  const size_t H = (size_t)a->n + 1, R = (size_t)a->R, T = (size_t)a->T;
+  RELA_HIP(hipMalloc(&a->ref_hist, H * R * ups * sizeof(int32_t)));
+  RELA_HIP(hipMemset(a->ref_hist, 0, H * R * ups * sizeof(int32_t)));
+  RELA_HIP(hipMalloc(&a->w.sref, R * T * ups * sizeof(int32_t)));
+  RELA_HIP(hipMemset(a->w.sref, 0xff, R * T * ups * sizeof(int32_t)));  // -1: padding
+  RELA_HIP(hipMalloc(&a->agg_kept, 2 * R * sizeof(float)));
+  RELA_HIP(hipMalloc(&a->d_kept, 2 * R * sizeof(int32_t)));
+  RELA_HIP(hipFree(a->w.s));  // the frame windows ([R][T][28,224] B) are no longer needed
+  a->w.s = nullptr;
+  a->w.ups = ups;
+  a->dd_ups = ups;
+  a->dd_cap = cap;
+  a->refs_valid.assign(H, 0);
+  a->tick_win = a->T + a->n + 8;
+  a->tick_seq.assign((size_t)a->tick_win, 0);
+  a->win_tick.assign(R * T, kPadTick);
   return RELA_OK;
 }
 extern "C" int64_t rela_r2d2_actor_num_act(const rela_r2d2_actor* a) { return a ? a->num_act.load() : 0; }
@@ -442,6 +512,46 @@ int upload_ranges(rela_r2d2_actor* a, const std::vector<SeqRange>& rs, hipStream
   RELA_LAUNCH_CHECK();
   return RELA_OK;  // `flat` may die: the upload reads the pinned copy
 }
+
+// de-duplication: the stack acted on this tick (history slot `cur`) enters the unit ring once -- one new plane, or all
+// four on a keyframe (the first tick, or the first after an unstored one), or the whole stack -- exactly as in the Ape-X
+// shard (actor.hip); ref_hist[cur] receives its references.  Ring full and nonblocking: the tick is not stored.
+int dedup_store(rela_r2d2_actor* a, int nonblocking, hipStream_t s) {
+  const int H = a->n + 1, cur = a->cur, prev = (cur + H - 1) % H;
+  const int ups = a->dd_ups;
+  const bool prev_ok = a->tick > 0 && a->refs_valid[prev];
+  const int keyframe = (ups == 4 && !prev_ok) ? 1 : 0;
+  const int count = keyframe ? 4 * a->R : a->R;
+  int64_t seq = 0;
+  int32_t idx = 0;
+  int rc = rela_replay_units_reserve(a->replay, count, nonblocking, &seq, &idx);
+  const size_t tw = (size_t)(a->tick % a->tick_win);
+  if (rc == RELA_EWOULDBLOCK) {
+    a->refs_valid[cur] = 0;
+    a->tick_seq[tw] = a->seq_hint;  // no unit of a later tick is older
+  } else {
+    if (rc != RELA_OK) return rc;
+    const uint8_t* stack = a->obs + (size_t)cur * a->R * kObs;
+    if (ups == 1) rc = rela_replay_units_write(a->replay, seq, count, stack, kObs, s);
+    else if (keyframe) rc = rela_replay_units_write(a->replay, seq, count, stack, kPlane, s);
+    else rc = rela_replay_units_write(a->replay, seq, count, stack + 3 * kPlane, kObs, s);  // the newest plane
+    if (rc != RELA_OK) return rc;
+    hipLaunchKernelGGL(dedup_make_refs, dim3(ceil_div(a->R, 256)), dim3(256), 0, s,
+                       a->ref_hist + (size_t)cur * a->R * ups, a->ref_hist + (size_t)prev * a->R * ups,
+                       a->term + (size_t)prev * a->R, a->R, ups, keyframe, idx, a->dd_cap);
+    RELA_LAUNCH_CHECK();
+    a->refs_valid[cur] = 1;
+    a->tick_seq[tw] = seq;
+    a->seq_hint = seq + count;
+  }
+  a->tick += 1;
+  return RELA_OK;
+}
+
+void win_mark(rela_r2d2_actor* a, const std::vector<SeqRange>& rs) {
+  for (const auto& r : rs)
+    for (int j = r.begin; j < r.end; ++j) a->win_tick[(size_t)r.env * a->T + j] = kPadTick;
+}
 }  // namespace
 
 extern "C" int rela_r2d2_actor_post_step(rela_r2d2_actor* a, const float* reward_host, const uint8_t* terminal_host,
@@ -467,6 +577,10 @@ extern "C" int rela_r2d2_actor_post_step(rela_r2d2_actor* a, const float* reward
   memcpy(&a->h_term[(size_t)a->cur * R], terminal_host, R);
   hipLaunchKernelGGL(r2d2_reset_hidden, dim3(a->R), dim3(128), 0, s, a->term + (size_t)a->cur * R, a->R, a->hid_h,
                      a->hid_c);
+  if (a->dd_ups > 0) {
+    const int rc = dedup_store(a, nonblocking, s);
+    if (rc != RELA_OK) return rc;
+  }
   a->cur = -1;
   a->count += 1;
   if (a->count < H) return RELA_OK;  // multiStepBuffer_.canPop :276-279
@@ -516,11 +630,21 @@ extern "C" int rela_r2d2_actor_post_step(rela_r2d2_actor* a, const float* reward
   if (rc != RELA_OK) return rc;
   RELA_HIP(a->stage.h2d(a->d_slot, plan.write_slot.data(), R * sizeof(int32_t), s));
   RELA_HIP(a->stage.h2d(a->d_flags, plan.flags.data(), R, s));
+  const bool dd = a->dd_ups > 0;
+  const int32_t* refs_t = dd ? a->ref_hist + (size_t)first * R * a->dd_ups : nullptr;
   hipLaunchKernelGGL(r2d2_write_step, dim3(a->R), dim3(kT), 0, s, a->w, a->d_slot, a->d_flags, obs_t, eps_t, legal_t,
-                     act_t, a->out_r, a->out_t, a->out_b, a->prio_step, h_t, c_t);
+                     act_t, a->out_r, a->out_t, a->out_b, a->prio_step, h_t, c_t, refs_t);
   RELA_LAUNCH_CHECK();
   rc = upload_ranges(a, plan.tail_pad, s);
   if (rc != RELA_OK) return rc;
+  // de-duplication: the host mirror of the windows' ticks (which entries are padding, which hold an unstored tick)
+  const int64_t t_first = a->tick - 1 - a->n;  // the tick obs_t was acted on
+  if (dd) {
+    win_mark(a, plan.front_pad);
+    const int64_t v = a->refs_valid[first] ? t_first : kLostTick;
+    for (int i = 0; i < a->R; ++i) a->win_tick[(size_t)i * a->T + plan.write_slot[i]] = v;
+    win_mark(a, plan.tail_pad);
+  }
 
   if (plan.can_pop) {  // :292-301
     const int nseq = (int)plan.emits.size();
@@ -541,11 +665,40 @@ extern "C" int rela_r2d2_actor_post_step(rela_r2d2_actor* a, const float* reward
     const int max_block = ring - cap > 1 ? ring - cap : 1;
     const Windows& w = a->w;
     int inserted = 0, dropped = 0;
+    // de-duplication: a sequence is kept only if every stack of its window was stored (keep[q]), and its block declares
+    // the oldest unit it may refer to.  For that bound: a window spans at most T consecutive ticks up to t_first, and a
+    // plane-unit stack reaches 3 ticks further back -- never across an unstored tick (a keyframe follows it).  The bound
+    // is the same for every sequence of this tick and grows with the tick, so the slots' bounds stay in FIFO order.
+    std::vector<uint8_t> keep((size_t)nseq, 1);
+    int64_t min_seq = 0;
+    if (dd) {
+      std::vector<uint8_t> carries(R, 0);
+      for (int e : plan.carry_env) carries[(size_t)e] = 1;
+      std::vector<int> pad_of(R, -1);
+      for (size_t k = 0; k < plan.carry_pad.size(); ++k) pad_of[(size_t)plan.carry_pad[k].env] = (int)k;
+      auto stored = [&](int env) {
+        const int64_t* wt = &a->win_tick[(size_t)env * a->T];
+        for (int j = 0; j < a->T; ++j)
+          if (wt[j] == kLostTick) return false;
+        return true;
+      };
+      for (int q = 0; q < nseq; ++q) {  // in emission order, with the carry-over replayed between an env's two sequences
+        const int env = plan.emits[q].env;
+        keep[(size_t)q] = stored(env) ? 1 : 0;
+        if (plan.emits[q].second || !carries[(size_t)env]) continue;
+        int64_t* wt = &a->win_tick[(size_t)env * a->T];
+        for (int j = 0; j < a->burn + a->n; ++j) wt[j] = wt[a->seq + j];
+        if (pad_of[(size_t)env] >= 0) win_mark(a, {plan.carry_pad[(size_t)pad_of[(size_t)env]]});
+      }
+      int64_t oldest = t_first - (a->T - 1) - (a->dd_ups == 4 ? 3 : 0);
+      if (oldest < 0) oldest = 0;
+      min_seq = a->tick_seq[(size_t)(oldest % a->tick_win)];  // (tick - oldest <= T + n + 3 < tick_win)
+    }
     size_t ci = 0, pi = 0;  // cursors into carry_env / carry_pad (both ascending in env)
     for (int q0 = 0; q0 < nseq && rc == RELA_OK;) {
       int q1 = nseq - q0 <= max_block ? nseq : q0 + max_block;
       if (q1 < nseq && plan.emits[q1].second) q1 = (q1 - 1 > q0) ? q1 - 1 : q1 + 1;  // keep a pair together
-      const int cnt = q1 - q0;
+      int cnt = q1 - q0;
       const int env_hi = plan.emits[q1 - 1].env;
       std::vector<int32_t> carry;
       while (ci < plan.carry_env.size() && plan.carry_env[ci] <= env_hi) carry.push_back(plan.carry_env[ci++]);
@@ -558,6 +711,18 @@ extern "C" int rela_r2d2_actor_post_step(rela_r2d2_actor* a, const float* reward
         RELA_LAUNCH_CHECK();
         return upload_ranges(a, pads, s);
       };
+      std::vector<int32_t> kept;  // (de-duplication) the sequences of this piece that are stored
+      if (dd) {
+        for (int q = q0; q < q1; ++q)
+          if (keep[(size_t)q]) kept.push_back(q);
+        if ((int)kept.size() < cnt) dropped = 1;
+        cnt = (int)kept.size();
+        if (cnt == 0) {  // the windows advance as if stored
+          rc = carry_piece();
+          q0 = q1;
+          continue;
+        }
+      }
       int slot0 = 0;
       rc = rela_replay_begin_add(a->replay, cnt, nonblocking, &slot0);
       if (rc == RELA_EWOULDBLOCK) {
@@ -568,16 +733,27 @@ extern "C" int rela_r2d2_actor_post_step(rela_r2d2_actor* a, const float* reward
         continue;
       }
       if (rc != RELA_OK) break;
-      // all sequences of one kind leave in ONE gathered write per field: destination offset q - q0, source
-      // row = the env's window (lens is indexed by q itself)
+      if (dd) {
+        rc = rela_replay_set_block_min_unit(a->replay, slot0, cnt, min_seq);
+        if (rc != RELA_OK) {
+          (void)rela_replay_abort_add(a->replay, slot0, cnt);
+          break;
+        }
+      }
+      // all sequences of one kind leave in ONE gathered write per field: destination offset q - q0 (de-duplication: the
+      // rank among the kept ones), source row = the env's window (lens is indexed by q itself)
       auto emit_batch = [&](bool second) -> int {
         std::vector<int32_t> dst, envs, qs;
-        for (int q = q0; q < q1; ++q)
+        int rank = 0;
+        for (int q = q0; q < q1; ++q) {
+          if (dd && !keep[(size_t)q]) continue;
           if ((plan.emits[q].second != 0) == second) {
-            dst.push_back(q - q0);
+            dst.push_back(dd ? rank : q - q0);
             envs.push_back(plan.emits[q].env);
             qs.push_back(q);
           }
+          ++rank;
+        }
         const int m = (int)dst.size();
         if (m == 0) return RELA_OK;
         int32_t* d_dst = a->d_gather + (second ? 3 * (size_t)a->R : 0);
@@ -587,14 +763,24 @@ extern "C" int rela_r2d2_actor_post_step(rela_r2d2_actor* a, const float* reward
         all.insert(all.end(), envs.begin(), envs.end());
         all.insert(all.end(), qs.begin(), qs.end());
         RELA_HIP(a->stage.h2d(d_dst, all.data(), all.size() * sizeof(int32_t), s));  // pinned copy: `all` may die
-        const void* bases[10] = {w.s, w.eps, w.legal, w.a, w.reward, w.term, w.boot, w.h0, w.c0, a->lens};
+        const void* stacks = dd ? (const void*)w.sref : (const void*)w.s;
+        const void* bases[10] = {stacks, w.eps, w.legal, w.a, w.reward, w.term, w.boot, w.h0, w.c0, a->lens};
         const int32_t* idx[10] = {d_env, d_env, d_env, d_env, d_env, d_env, d_env, d_env, d_env, d_q};
         return rela_replay_write_rows_gather(a->replay, slot0, m, d_dst, bases, idx, s);
       };
       rc = emit_batch(false);
       if (rc == RELA_OK) rc = carry_piece();
       if (rc == RELA_OK) rc = emit_batch(true);
-      if (rc == RELA_OK) rc = rela_replay_commit_add(a->replay, slot0, cnt, a->agg + q0, s);
+      const float* prio = a->agg + q0;
+      if (rc == RELA_OK && dd && cnt < q1 - q0) {  // the priorities of the kept sequences, in slot order
+        rc = a->stage.h2d(a->d_kept, kept.data(), kept.size() * sizeof(int32_t), s) == hipSuccess ? RELA_OK : RELA_ENODEV;
+        if (rc == RELA_OK) {
+          hipLaunchKernelGGL(r2d2_pick, dim3(ceil_div(cnt, 256)), dim3(256), 0, s, (const float*)a->agg, a->d_kept, cnt,
+                             a->agg_kept);
+          prio = a->agg_kept;
+        }
+      }
+      if (rc == RELA_OK) rc = rela_replay_commit_add(a->replay, slot0, cnt, prio, s);
       if (rc == RELA_OK) inserted += cnt;
       else (void)rela_replay_abort_add(a->replay, slot0, cnt);  // never leave a reservation uncommitted
       q0 = q1;

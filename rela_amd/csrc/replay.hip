@@ -381,6 +381,40 @@ __global__ __launch_bounds__(kThreads) void replay_gather_dedup(const int32_t* _
   }
 }
 
+// De-duplicated stack field of a SEQUENCE schema (rela_replay_set_schema_seq_dedup): slot ids[b] holds [T][ups] references
+// (-1 = an all-zero unit, padLike); the output is time-major, stack t of sequence b at out[t * batch + b].  One block per
+// (b, t), the blocks of one sequence adjacent.  Plane units (ups = 4) slide: reference (t, k) usually equals (t - 1, k + 1),
+// so the output planes form diagonal CHAINS (t, k), (t + 1, k - 1), ... of one unit.  The block of (t, k) copies the chain
+// only when (t, k) is its head: every output plane is written once and every sliding plane read once (one 16-byte load,
+// up to four 16-byte stores); an episode's first plane, repeated four times, starts four chains and is read by each.
+__global__ __launch_bounds__(kThreads) void replay_gather_seq_dedup(const int32_t* __restrict__ refs,
+                                                                   const int32_t* __restrict__ ids,
+                                                                   const uint8_t* __restrict__ units, int64_t unit_bytes,
+                                                                   int64_t cap, int ups, int steps,
+                                                                   uint8_t* __restrict__ out, int batch) {
+  const int64_t nv = unit_bytes >> 4;
+  const int64_t stack_bytes = unit_bytes * ups;
+  for (int64_t y = blockIdx.x; y < (int64_t)batch * steps; y += gridDim.x) {
+    const int b = (int)(y / steps), t = (int)(y - (int64_t)b * steps);
+    const int32_t* rs = refs + ((int64_t)ids[b] * steps) * ups;  // [T][ups] of this sequence
+    for (int k = 0; k < ups; ++k) {
+      const int32_t u = rs[t * ups + k];
+      if (t > 0 && k + 1 < ups && rs[(t - 1) * ups + k + 1] == u) continue;  // (t, k) continues an earlier chain
+      int len = 1;  // chain (t + d, k - d), d < len
+      while (len <= k && t + len < steps && rs[(t + len) * ups + k - len] == u) ++len;
+      const bool zero = u < 0 || u >= cap;  // -1: padding (an out-of-range reference never reads outside the ring)
+      const uint4* s4 = reinterpret_cast<const uint4*>(units + (zero ? 0 : (int64_t)u) * unit_bytes);
+      for (int64_t i = threadIdx.x; i < nv; i += kThreads) {
+        const uint4 v = zero ? make_uint4(0, 0, 0, 0) : s4[i];
+        for (int d = 0; d < len; ++d) {
+          uint4* d4 = reinterpret_cast<uint4*>(out + ((int64_t)(t + d) * batch + b) * stack_bytes + (int64_t)(k - d) * unit_bytes);
+          d4[i] = v;
+        }
+      }
+    }
+  }
+}
+
 // copies `count` units from a pitched source into the unit ring at sequence first_seq..
 __global__ __launch_bounds__(kThreads) void replay_units_write(const uint8_t* __restrict__ src, int64_t pitch,
                                                               uint8_t* __restrict__ units, int64_t unit_bytes,
@@ -596,7 +630,9 @@ struct rela_replay {
   int64_t dd_unit_bytes = 0, dd_cap = 0;
   uint8_t* d_units = nullptr;     // [dd_cap][dd_unit_bytes]
   VmmRange* vmm_units = nullptr;  // chunked mode: d_units = vmm_units->base
-  int dd_field[2] = {-1, -1};
+  int dd_field[2] = {-1, -1};     // sequence schema (rela_replay_set_schema_seq_dedup): one stack field, dd_field[1] = -1
+  int dd_steps = 0;               // sequence schema: stacks per slot (0 = transition schema, two stack fields)
+  int64_t dd_units_per_slot = 1;  // units a slot adds to the ring beyond the guard (transition schema: 1)
   int64_t dd_next_seq = 0;        // sequence number of the next unit
   std::vector<int64_t> dd_slot_min;  // [ring] smallest unit sequence a slot refers to (host; guarded by m)
 };
@@ -778,6 +814,43 @@ extern "C" int rela_replay_set_schema_seq(rela_replay* r, int nfields, const int
 }
 
 // ---- frame-stack de-duplication ------------------------------------------------------
+// (both schemas) the unit ring: ring * units_per_slot + guard_units units of unit_bytes, plain or chunked like the fields
+static int dedup_alloc_units(rela_replay* r, int64_t unit_bytes, int units_per_stack, int64_t units_per_slot,
+                             int64_t guard_units, const char* who) {
+  DeviceGuard g(r->device);
+  std::lock_guard<std::mutex> lk(r->m);
+  r->dd_ups = units_per_stack;
+  r->dd_unit_bytes = unit_bytes;
+  r->dd_units_per_slot = units_per_slot;
+  r->dd_cap = (int64_t)r->ring * units_per_slot + guard_units;
+  RELA_CHECK(r->dd_cap < ((int64_t)1 << 31), RELA_EINVAL, "%s: unit ring too large", who);
+  const size_t unit_ring_bytes = (size_t)r->dd_cap * (size_t)unit_bytes;
+  if (r->chunk_bytes > 0) {  // exported like the field arrays (vmm_field.h)
+    r->vmm_units = new VmmRange();
+    hipError_t e = r->vmm_units->create(unit_ring_bytes, (size_t)r->chunk_bytes, r->device);
+    if (e != hipSuccess) {
+      set_last_error("%s: unit ring of %.1f GB in chunks of %.1f GB: %s", who, (double)unit_ring_bytes / 1e9,
+                     (double)r->chunk_bytes / 1e9, hipGetErrorString(e));
+      r->vmm_units->destroy();
+      delete r->vmm_units;
+      r->vmm_units = nullptr;
+      r->dd_ups = 0;
+      return e == hipErrorOutOfMemory ? RELA_ENOMEM : RELA_ENODEV;
+    }
+    r->d_units = r->vmm_units->base;
+  } else {
+    const hipError_t e = hipMalloc(&r->d_units, unit_ring_bytes);
+    if (e != hipSuccess) {
+      set_last_error("%s: unit ring of %.1f GB: %s", who, (double)unit_ring_bytes / 1e9, hipGetErrorString(e));
+      r->d_units = nullptr;
+      r->dd_ups = 0;
+      return e == hipErrorOutOfMemory ? RELA_ENOMEM : RELA_ENODEV;
+    }
+  }
+  r->dd_slot_min.assign((size_t)r->ring, 0);
+  return RELA_OK;
+}
+
 extern "C" int rela_replay_set_schema_dedup(rela_replay* r, int nfields, const int64_t* row_bytes, int field_a,
                                             int field_b, int64_t unit_bytes, int units_per_stack,
                                             int64_t guard_units) {
@@ -791,32 +864,28 @@ extern "C" int rela_replay_set_schema_dedup(rela_replay* r, int nfields, const i
   rb[field_a] = rb[field_b] = (int64_t)sizeof(int32_t) * units_per_stack;  // references instead of frames
   int rc = rela_replay_set_schema_seq(r, nfields, rb.data(), nullptr);
   if (rc != RELA_OK) return rc;
-  DeviceGuard g(r->device);
-  std::lock_guard<std::mutex> lk(r->m);
-  r->dd_ups = units_per_stack;
-  r->dd_unit_bytes = unit_bytes;
-  r->dd_cap = (int64_t)r->ring + guard_units;
-  RELA_CHECK(r->dd_cap < ((int64_t)1 << 31), RELA_EINVAL, "rela_replay_set_schema_dedup: unit ring too large");
   r->dd_field[0] = field_a;
   r->dd_field[1] = field_b;
-  const size_t unit_ring_bytes = (size_t)r->dd_cap * (size_t)unit_bytes;
-  if (r->chunk_bytes > 0) {  // exported like the field arrays (vmm_field.h)
-    r->vmm_units = new VmmRange();
-    hipError_t e = r->vmm_units->create(unit_ring_bytes, (size_t)r->chunk_bytes, r->device);
-    if (e != hipSuccess) {
-      set_last_error("rela_replay_set_schema_dedup: unit ring of %.1f GB in chunks of %.1f GB: %s", (double)unit_ring_bytes / 1e9,
-                     (double)r->chunk_bytes / 1e9, hipGetErrorString(e));
-      r->vmm_units->destroy();
-      delete r->vmm_units;
-      r->vmm_units = nullptr;
-      return e == hipErrorOutOfMemory ? RELA_ENOMEM : RELA_ENODEV;
-    }
-    r->d_units = r->vmm_units->base;
-  } else {
-    RELA_HIP(hipMalloc(&r->d_units, unit_ring_bytes));
-  }
-  r->dd_slot_min.assign((size_t)r->ring, 0);
-  return RELA_OK;
+  return dedup_alloc_units(r, unit_bytes, units_per_stack, 1, guard_units, "rela_replay_set_schema_dedup");
+}
+
+extern "C" int rela_replay_set_schema_seq_dedup(rela_replay* r, int nfields, const int64_t* row_bytes, const int32_t* steps,
+                                                int field, int64_t unit_bytes, int units_per_stack, int64_t units_per_slot,
+                                                int64_t guard_units) {
+  RELA_CHECK(r && nfields >= 1 && row_bytes && steps && field >= 0 && field < nfields && unit_bytes > 0 &&
+                 unit_bytes % 16 == 0 && (units_per_stack == 1 || units_per_stack == 4) && units_per_slot >= 1 &&
+                 guard_units >= 0,
+             RELA_EINVAL, "rela_replay_set_schema_seq_dedup: bad arguments");
+  RELA_CHECK(steps[field] >= 1 && row_bytes[field] == (int64_t)steps[field] * unit_bytes * units_per_stack, RELA_EINVAL,
+             "rela_replay_set_schema_seq_dedup: the stack field must be steps * units_per_stack * unit_bytes long");
+  std::vector<int64_t> rb(row_bytes, row_bytes + nfields);
+  rb[field] = (int64_t)sizeof(int32_t) * units_per_stack * steps[field];  // [T][units_per_stack] references
+  int rc = rela_replay_set_schema_seq(r, nfields, rb.data(), steps);
+  if (rc != RELA_OK) return rc;
+  r->dd_field[0] = field;
+  r->dd_field[1] = -1;
+  r->dd_steps = steps[field];
+  return dedup_alloc_units(r, unit_bytes, units_per_stack, units_per_slot, guard_units, "rela_replay_set_schema_seq_dedup");
 }
 
 extern "C" int rela_replay_units_reserve(rela_replay* r, int count, int nonblocking, int64_t* first_seq,
@@ -876,7 +945,7 @@ extern "C" int rela_replay_set_block_min_unit(rela_replay* r, int first_slot, in
   RELA_CHECK(min_seq >= r->dd_next_seq - r->dd_cap, RELA_ESTATE,
              "rela_replay_set_block_min_unit: block refers to unit %lld but units below %lld were already overwritten "
              "(a producer fell more than the guard window of %lld units behind: raise guard_units)",
-             (long long)min_seq, (long long)(r->dd_next_seq - r->dd_cap), (long long)(r->dd_cap - r->ring));
+             (long long)min_seq, (long long)(r->dd_next_seq - r->dd_cap), (long long)(r->dd_cap - r->ring * r->dd_units_per_slot));
   for (int i = 0; i < n; ++i) r->dd_slot_min[(size_t)((first_slot + i) % r->ring)] = min_seq;
   return RELA_OK;
 }
@@ -889,6 +958,8 @@ extern "C" int rela_replay_dedup_info(const rela_replay* r, int* units_per_stack
   if (unit_capacity) *unit_capacity = r->dd_cap;
   return RELA_OK;
 }
+
+extern "C" int rela_replay_dedup_steps(const rela_replay* r) { return r && r->dd_ups > 0 ? r->dd_steps : 0; }
 
 static inline int vec16_ok(const void* a, const void* b, int64_t row_bytes) {
   return ((row_bytes & 15) == 0) && (((uintptr_t)a & 15) == 0) && (((uintptr_t)b & 15) == 0);
@@ -930,7 +1001,7 @@ extern "C" int rela_replay_begin_add(rela_replay* r, int n, int nonblocking, int
   }
   *first_slot = r->tail;
   if (r->dd_ups > 0) {  // until the producer declares it (set_block_min_unit): nothing older than the guard window
-    const int64_t lo = r->dd_next_seq - (r->dd_cap - r->ring);
+    const int64_t lo = r->dd_next_seq - (r->dd_cap - r->ring * r->dd_units_per_slot);
     for (int i = 0; i < n; ++i) r->dd_slot_min[(size_t)((r->tail + i) % r->ring)] = lo;
   }
   r->tail = (r->tail + n) % r->ring;
@@ -1244,7 +1315,16 @@ extern "C" int rela_replay_sample(rela_replay* r, int batch, void* const* out_ro
                        (float)full_size, r->beta, (const ReplayDevState*)r->d_state, out_weight_dev, small,
                        (const int32_t*)r->d_ids);
   }
-  if (out_rows_dev && r->dd_ups > 0) {
+  if (out_rows_dev && r->dd_ups > 0 && r->dd_steps > 0 && out_rows_dev[r->dd_field[0]]) {  // [T][B] stacks of sequences
+    const int f = r->dd_field[0];
+    RELA_CHECK(((uintptr_t)out_rows_dev[f] & 15) == 0, RELA_EINVAL, "rela_replay_sample: unaligned stack output");
+    const int64_t rows = (int64_t)batch * r->dd_steps;
+    ProfScope prof("replay_gather_rows", r->stream);
+    hipLaunchKernelGGL(replay_gather_seq_dedup, dim3((unsigned)std::min<int64_t>(rows, 1 << 20)), dim3(kThreads), 0, r->stream,
+                       (const int32_t*)r->d_fields[f], (const int32_t*)r->d_ids, (const uint8_t*)r->d_units,
+                       r->dd_unit_bytes, r->dd_cap, r->dd_ups, r->dd_steps, (uint8_t*)out_rows_dev[f], batch);
+  }
+  if (out_rows_dev && r->dd_ups > 0 && r->dd_steps == 0) {
     for (int q = 0; q < 2; ++q) {
       const int f = r->dd_field[q];
       if (!out_rows_dev[f]) continue;
@@ -1496,6 +1576,9 @@ static int export_partition(rela_replay* r, rela_replay_ipc_desc* out, rela_repl
                             int max_fds, const char* who) {
   RELA_CHECK(!r->d_fields.empty() && (int)r->d_fields.size() <= RELA_IPC_MAX_FIELDS, RELA_ESTATE,
              "%s: set the schema first (at most %d fields)", who, RELA_IPC_MAX_FIELDS);
+  RELA_CHECK(r->dd_ups == 0 || r->dd_steps == 0, RELA_EINVAL,
+             "%s: a sequence partition with de-duplicated stacks (rela_replay_set_schema_seq_dedup) cannot be exported: "
+             "its consumers would read references, not frames", who);
   RELA_CHECK(r->dd_ups == 0 || chunks, RELA_EINVAL,
              "%s: a de-duplicated partition needs the unit ring next to its fields; export it with rela_replay_export_chunks", who);
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "handle size");
@@ -1658,6 +1741,7 @@ static int import_partition(rela_replay_remote** out, const rela_replay_ipc_desc
     rr->dd_field[0] = chunks->dd_field[0], rr->dd_field[1] = chunks->dd_field[1];
     const int n = chunks->units_chunks;
     const int64_t need = chunks->dd_cap * chunks->dd_unit_bytes;
+    // (dd_field[1] < 0 would be a sequence partition's single stack field: never exported, refused here as well)
     const bool fields_ok = rr->dd_field[0] >= 0 && rr->dd_field[0] < desc->nfields && rr->dd_field[1] >= 0 &&
                            rr->dd_field[1] < desc->nfields && rr->dd_ups <= 16 && rr->dd_unit_bytes > 0 && rr->dd_unit_bytes % 16 == 0 &&
                            desc->row_bytes[rr->dd_field[0]] == 4 * rr->dd_ups && desc->row_bytes[rr->dd_field[1]] == 4 * rr->dd_ups;

@@ -207,6 +207,9 @@ class R2D2ActorEngine:
                                                    burn_in, float(eta), replay.h if replay is not None else None, seed,
                                                    self.device.index or 0), "rela_r2d2_actor_create")
         self.h = h
+        if replay is not None and getattr(replay, "dedup", None):  # frame-stack de-duplication of the windows
+            capi.check(capi.lib.rela_r2d2_actor_set_dedup(h, {"stack": 1, "plane": 4}[replay.dedup]),
+                       "rela_r2d2_actor_set_dedup")
         self._eps = torch.as_tensor(eps, dtype=torch.float32).reshape(rows).contiguous()
         self._legal = torch.ones((rows, num_action), dtype=torch.float32)
         self._first = True

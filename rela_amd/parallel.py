@@ -403,6 +403,9 @@ def _export_desc(replay_handle):
 
     from . import _capi as capi
 
+    if capi.lib.rela_replay_dedup_steps(replay_handle) > 0:
+        raise ValueError("a sequence replay with de-duplicated stacks (RNNReplay(dedup=...), RELA_REPLAY_DEDUP for "
+                         "RNNPrioritizedReplay) cannot be exchanged between processes: its slots hold references, not frames")
     desc = capi.ReplayChunkDesc()
     fds = (C.c_int * capi.IPC_MAX_FDS)()
     capi.check(capi.lib.rela_replay_export_chunks(replay_handle, C.byref(desc), fds, capi.IPC_MAX_FDS),

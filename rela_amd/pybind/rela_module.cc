@@ -841,7 +841,8 @@ class RNNPrioritizedReplay {
 
   ReplayParts& core() { return core_; }
 
-  rela_replay* handle(const void* lockerKey, int device, int numAction, int T) {
+  // unitsPerSlot (de-duplication only): seq_len + multi_step, the new steps an env adds per sequence (csrc/actor_r2d2.hip)
+  rela_replay* handle(const void* lockerKey, int device, int numAction, int T, int unitsPerSlot) {
     {  // (several cohort leaders call this concurrently on their first act: ADVICE r4)
       int64_t seen = 0;
       const int64_t mine = ((int64_t)numAction << 32) | (uint32_t)T;
@@ -854,7 +855,20 @@ class RNNPrioritizedReplay {
       const int64_t A = numAction, t = T;
       const int64_t rb[10] = {t * kObsBytes, t * 4, t * 4 * A, t * 8, t * 4, t, t * 4, 2048, 2048, 4};
       const int32_t st[10] = {T, T, T, T, T, T, T, 1, 1, 1};
-      check(rela_replay_set_schema_seq(h, 10, rb, st), "rela_replay_set_schema_seq");
+      // RELA_REPLAY_DEDUP=stack|plane as for FFPrioritizedReplay: the T stacks of a sequence become [T][1 or 4] references
+      // into a unit ring of ring * unitsPerSlot + guard units.  The default guard, 655,360 units, covers the
+      // (2 T + multi_step + 10) * envs a partition's producers need at T = 123 for up to 2,400 envs (the reference
+      // scripts: 80 x 20 and 60 x 40); 4.6 GB in plane units, 18.5 GB in stack units.  Batches are identical.
+      const char* dd = std::getenv("RELA_REPLAY_DEDUP");
+      const int ups = dd && std::string(dd) == "stack" ? 1 : (dd && std::string(dd) == "plane" ? 4 : 0);
+      if (ups > 0) {
+        const char* gd = std::getenv("RELA_REPLAY_DEDUP_GUARD");
+        const int64_t guard = gd ? std::atoll(gd) : 655360;
+        check(rela_replay_set_schema_seq_dedup(h, 10, rb, st, 0, kObsBytes / ups, ups, unitsPerSlot, guard),
+              "rela_replay_set_schema_seq_dedup");
+      } else {
+        check(rela_replay_set_schema_seq(h, 10, rb, st), "rela_replay_set_schema_seq");
+      }
     });
   }
 
@@ -1000,6 +1014,12 @@ static void enableDedup(rela_apex_actor* a, rela_replay* rep) {
   int ups = 0;
   check(rela_replay_dedup_info(rep, &ups, nullptr, nullptr), "rela_replay_dedup_info");
   if (ups > 0) check(rela_apex_actor_set_dedup(a, ups), "rela_apex_actor_set_dedup");
+}
+static void enableDedup(rela_r2d2_actor* a, rela_replay* rep) {
+  if (!rep) return;
+  int ups = 0;
+  check(rela_replay_dedup_info(rep, &ups, nullptr, nullptr), "rela_replay_dedup_info");
+  if (ups > 0) check(rela_r2d2_actor_set_dedup(a, ups), "rela_r2d2_actor_set_dedup");
 }
 
 // =====================================================================================
@@ -1209,10 +1229,11 @@ class ActorCohort {
       // one pop of the shard commits the sequences of all members as ONE block, in row (= member)
       // order; the reference would issue one block per thread (only the float block-sum grouping of
       // sum_ differs, far below the fp tolerance of the priorities themselves)
-      rela_replay* rep = rnnReplay_->handle(locker_.get(), dev, A, burnin_ + seqLen_ + n_);
+      rela_replay* rep = rnnReplay_->handle(locker_.get(), dev, A, burnin_ + seqLen_ + n_, seqLen_ + n_);
       check(rela_r2d2_actor_create(&hr_, T_ * K_, K_, A, n_, gamma_, seqLen_, burnin_, locker_->eta(), rep,
                                    0xC2B2AE3D27D4EB4Full * (++counter), dev),
             "rela_r2d2_actor_create");
+      enableDedup(hr_, rep);
     } else {
       rela_replay* rep = replay_->handle(locker_.get(), dev, A);
       check(rela_apex_actor_create(&h_, T_ * K_, K_, A, n_, gamma_, rep, 0xA24BAED4963EE407ull * (++counter), dev),
@@ -1447,11 +1468,12 @@ class R2D2Actor : public Actor {
     if (!h_) {
       static std::atomic<uint64_t> counter{0};
       const int T = burnin_ + seqLen_ + multiStep_;
-      rela_replay* rep = replay_ ? replay_->handle(locker_.get(), locker_->execDevice, A, T) : nullptr;
+      rela_replay* rep = replay_ ? replay_->handle(locker_.get(), locker_->execDevice, A, T, seqLen_ + multiStep_) : nullptr;
       check(rela_stream_create(&stream_, locker_->execDevice), "rela_stream_create");
       check(rela_r2d2_actor_create(&h_, batchsize_, batchsize_, A, multiStep_, gamma_, seqLen_, burnin_,
                                    locker_->eta(), rep, 0xD1B54A32D192ED03ull * (++counter), locker_->execDevice),
             "rela_r2d2_actor_create");
+      enableDedup(h_, rep);
       action_ = torch::zeros({batchsize_}, torch::kInt64);
       if (torch::cuda::is_available()) action_ = action_.pin_memory();
       epsHost_ = torch::zeros({batchsize_}, torch::kFloat32);

@@ -430,6 +430,11 @@ def train_multi(args):
 
     if args.algo not in ("apex", "r2d2"):
         raise SystemExit("--algo must be apex or r2d2")
+    if args.algo == "r2d2" and os.environ.get("RELA_REPLAY_DEDUP"):
+        # the learner process would read the partitions' rows through IPC, and a sequence partition with de-duplicated
+        # stacks holds references, not frames: the library refuses to export it (rela_replay_export_chunks)
+        raise SystemExit("RELA_REPLAY_DEDUP is not supported for --algo r2d2 across processes (--act_device): "
+                         "run on one process, or unset it")
     G = len(args.act_device.split(","))
     s = socket.socket()
     s.bind(("127.0.0.1", 0))

@@ -137,7 +137,14 @@ class RNNReplay:
 
     FIELDS = ("s", "eps", "legal_move", "a", "reward", "terminal", "bootstrap", "h0", "c0", "seq_len")
 
-    def __init__(self, capacity, seed, alpha, beta, prefetch, num_action, steps, device="cuda:0"):
+    def __init__(self, capacity, seed, alpha, beta, prefetch, num_action, steps, device="cuda:0", dedup=None,
+                 guard_units=0, units_per_slot=None):
+        """dedup: None (the T stacks of a sequence stored in full, T x 28,224 B per slot), "stack" (every stack an actor
+        acted on stored once, as a whole) or "plane" (one new 84x84 plane per env-step; sliding-stack envs only), as for
+        FFReplay.  A slot then holds [T][1 or 4] int32 references (-1 = padding) into a unit ring of
+        ring * units_per_slot + guard_units units.  units_per_slot: seq_len + multi_step is enough for the R2D2 actor
+        shard (csrc/actor_r2d2.hip); None = steps, which is always enough.  guard_units: (2 * steps + multi_step + 10)
+        * rows of all producers is always enough."""
         self.device = torch.device(device)
         self.num_action, self.T = num_action, steps
         h = C.c_void_p()
@@ -148,7 +155,14 @@ class RNNReplay:
         self.row_bytes = [T * OBS_BYTES, T * 4, T * 4 * A, T * 8, T * 4, T, T * 4, 2048, 2048, 4]
         rb = (C.c_int64 * 10)(*self.row_bytes)
         st = (C.c_int32 * 10)(T, T, T, T, T, T, T, 1, 1, 1)
-        capi.check(capi.lib.rela_replay_set_schema_seq(h, 10, rb, st), "rela_replay_set_schema_seq")
+        self.dedup = dedup
+        if dedup is None:
+            capi.check(capi.lib.rela_replay_set_schema_seq(h, 10, rb, st), "rela_replay_set_schema_seq")
+        else:
+            ups = {"stack": 1, "plane": 4}[dedup]
+            capi.check(capi.lib.rela_replay_set_schema_seq_dedup(
+                h, 10, rb, st, 0, OBS_BYTES // ups, ups, int(units_per_slot or T), int(guard_units)),
+                "rela_replay_set_schema_seq_dedup")
         self._out = {}
         self._keep = None
 
