@@ -3,3 +3,11 @@ mode: conv1 on the int8 matrix cores fused with conv2 through LDS (csrc/ffnet.hi
 generations were removed in r4)."""
 CONV12 = "conv12_i8"
 CONV12_JOBS = "conv12_i8_jobs"
+
+# every kernel of the split-bf16 arithmetic (bf16x2 mode: two-part operands, int8 conv1) -- none of them may run in an
+# f32x3 step, whose three-part kernels are listed per network
+SPLIT_BF16 = frozenset({CONV12, CONV12_JOBS, "conv_bf16s<Conv3F>", "conv3_bf16s_jobs", "fc_bf16s", "fc_bf16s (split-K)",
+                        "gemm_rec64_nt", "unsplit_records64", "unsplit_trunk_rows", "wgrad_conv1_bf16", "wgrad_conv2_bf16",
+                        "wgrad_conv3_bf16", "dgrad_conv2_bf16", "dgrad_conv3_bf16"})
+X3_FFNET = frozenset({"conv12_s3", "conv3_img_s3", "gemm_s3<fc>"})
+X3_LSTM = frozenset({"conv12_s3", "conv3_img_s3", "gemm_s3<gates_x>"})

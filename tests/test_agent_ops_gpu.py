@@ -137,10 +137,27 @@ def test_eps_greedy_statistics():
     assert hist.min() > 0.5 * hist.mean()
 
 
-@pytest.mark.parametrize("A,R,K,precision", [(6, 16, 8, "f32"), (18, 256, 128, "f32"), (18, 256, 128, "bf16x2")])
+def _reuse_kernels(precision, R):
+    """the kernels an actor shard of R rows must launch in `precision` (every forward runs all R rows): split-bf16 from 128
+    rows, with fc as split-K below kFastMinN = 1,024 rows and as one fc_bf16s launch from there; the three-part kernels of
+    f32x3 from kEmuConvMinN = 512 rows; nothing of either below"""
+    from kernel_names import CONV12, X3_FFNET
+
+    if precision == "bf16x2" and R >= 128:
+        return {CONV12, "conv_bf16s<Conv3F>", "fc_bf16s" if R >= 1024 else "fc_bf16s (split-K)"}
+    if precision == "f32x3" and R >= 512:
+        return set(X3_FFNET)
+    return set()
+
+
+@pytest.mark.parametrize("A,R,K,precision", [(6, 16, 8, "f32"), (18, 256, 128, "f32"), (18, 256, 128, "bf16x2"),
+                                             (18, 512, 128, "f32x3"), (18, 6400, 80, "f32x3"), (18, 6400, 80, "bf16x2")])
 def test_post_step_reuses_act_forward_bit_identically(A, R, K, precision):
     """(r4: also at 256 rows in groups of 128 in BOTH precision modes -- the memoised Q tables of the bf16x2 engine
-    at >= 128 rows are what the bench's fast mode runs; the launch census asserts the split-bf16 kernels ran.)
+    at >= 128 rows are what the bench's fast mode runs; the launch census asserts the split-bf16 kernels ran.  Also in
+    f32x3 -- bench.py's default precision, whose three-part kernels start at 512 rows -- at 512 rows and at bench.py's
+    actor shape (6,400 rows in groups of 80), and in bf16x2 at that shape; the census asserts each shape's kernels, and
+    that no kernel of the other arithmetic ran.)
     post_step skips the online forwards on obs and next_obs when act() already ran them with the same
     weights (dqn_actor.h:84,161 and apex.py:38,41 evaluate the same network on the same batches, n ticks ago
     and this tick).  Twin actors -- one whose weights are re-loaded (same values, new version) before every
@@ -154,13 +171,17 @@ def test_post_step_reuses_act_forward_bit_identically(A, R, K, precision):
     from rela_amd.replay import FFReplay
     from synth import synth_obs, synth_params
 
-    from kernel_names import CONV12
+    from kernel_names import SPLIT_BF16, X3_FFNET
 
     n = 3
     params = {k: torch.from_numpy(v) for k, v in synth_params(A, 5).items()}
     tparams = {k: torch.from_numpy(v) for k, v in synth_params(A, 6).items()}
     params2 = {k: torch.from_numpy(v) for k, v in synth_params(A, 7).items()}
     eps = np.linspace(0.0, 0.4, R).astype(np.float32)
+    frames = [torch.from_numpy(synth_obs(R, 100 + t)).cuda() for t in range(n + 8)]
+    # 8 ticks insert R rows each: a replay of 8 R rows (ring 10 R) takes them without eviction or blocking (3.6 GB at
+    # 6,400 rows, where the 16 R of the small shapes would take 7.2 GB)
+    capacity = 16 * R if R <= 256 else 8 * R
     runs = []
     for reload_between in (False, True, "switch", "next_only"):
         online, target = FFNetHandle(A, "cuda:0"), FFNetHandle(A, "cuda:0")
@@ -168,7 +189,7 @@ def test_post_step_reuses_act_forward_bit_identically(A, R, K, precision):
         target.load_state_dict(tparams)
         online.set_precision(precision)
         target.set_precision(precision)
-        replay = FFReplay(16 * R, 3, 0.6, 0.4, 0, A, "cuda:0")
+        replay = FFReplay(capacity, 3, 0.6, 0.4, 0, A, "cuda:0")
         eng = ApexActorEngine(R, K, A, n, 0.99, replay, eps, "cuda:0", seed=11)
         capi.check(capi.lib.rela_prof_count_enable(1), "census")
         eng.legal.fill_(1.0)
@@ -182,7 +203,7 @@ def test_post_step_reuses_act_forward_bit_identically(A, R, K, precision):
             if t == 4:
                 cur = params2
                 online.load_state_dict(cur)
-            eng.next_obs_slot().copy_(torch.from_numpy(synth_obs(R, 100 + t)).cuda())
+            eng.next_obs_slot().copy_(frames[t])
             acts.append(eng.act(online).cpu().numpy().copy())
             v0 = capi.lib.rela_ffnet_version(online.h)
             if reload_between is True:
@@ -197,8 +218,8 @@ def test_post_step_reuses_act_forward_bit_identically(A, R, K, precision):
         capi.check(capi.lib.rela_prof_counts_json(cbuf, len(cbuf)), "census")
         capi.lib.rela_prof_count_enable(0)
         ran = set(json.loads(cbuf.value.decode()))
-        fast = {CONV12, "conv_bf16s<Conv3F>", "fc_bf16s (split-K)"}
-        assert (fast <= ran) if (precision == "bf16x2" and R >= 128) else not (fast & ran), (precision, sorted(ran))
+        want = _reuse_kernels(precision, R)
+        assert want <= ran and not (((SPLIT_BF16 | X3_FFNET) - want) & ran), (precision, R, sorted(ran))
         ring = replay.debug_state()["ring"]
         w, ev = np.zeros(ring, np.float32), np.zeros(ring, np.uint8)
         capi.check(capi.lib.rela_replay_debug_weights(replay.h, w.ctypes.data_as(C.c_void_p),

@@ -4,7 +4,6 @@ single learner fed the concatenated batch."""
 import os
 
 import pytest
-import socket
 
 import numpy as np
 import torch
@@ -12,18 +11,15 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+def _init(rank, world, store):
+    """gloo rendezvous through a FileStore at `store`, a fresh path of the test's tmp_path.  (It was a TCP port found
+    free by binding and closing a socket: another process can take such a port between that probe and rank 0's bind,
+    and the ranks then meet a stranger's store and fail at a later collective.)"""
+    dist.init_process_group("gloo", init_method="file://" + store, rank=rank, world_size=world)
 
 
-def _worker(rank, world, port, out):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _worker(rank, world, store, out):
+    _init(rank, world, store)
     from rela_amd.learner import allreduce_grads
 
     torch.manual_seed(0)
@@ -46,11 +42,11 @@ def _worker(rank, world, port, out):
     dist.destroy_process_group()
 
 
-def test_two_rank_gradient_allreduce_keeps_replicas_identical():
+def test_two_rank_gradient_allreduce_keeps_replicas_identical(tmp_path):
     ctx = mp.get_context("spawn")
     out = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, out)) for r in range(2)]
+    store = str(tmp_path / "store")
+    procs = [ctx.Process(target=_worker, args=(r, 2, store, out)) for r in range(2)]
     for p in procs:
         p.start()
     res = out.get(timeout=120)
@@ -73,10 +69,8 @@ def test_two_rank_gradient_allreduce_keeps_replicas_identical():
     torch.testing.assert_close(a, ref, rtol=1e-5, atol=1e-6)
 
 
-def _is_worker(rank, world, port, out):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _is_worker(rank, world, store, out):
+    _init(rank, world, store)
     from rela_amd.learner import global_is_weights
 
     g = torch.Generator().manual_seed(5)
@@ -92,7 +86,7 @@ def _is_worker(rank, world, port, out):
     dist.destroy_process_group()
 
 
-def test_two_partition_is_weight_normalisation():
+def test_two_partition_is_weight_normalisation(tmp_path):
     """IS weights over two replay partitions with deliberately UNEQUAL sums (123.5 vs 77.25) and sizes: every
     partition contributes B / G draws, so item i of partition g is drawn with probability raw_i / (G * sum_g) and the
     correction is (N_total * that) ** -beta over the global maximum -- the single-buffer formula of
@@ -100,8 +94,8 @@ def test_two_partition_is_weight_normalisation():
     partition sums it coincides with the reference's formula on the union (second half of the test)."""
     ctx = mp.get_context("spawn")
     out = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_is_worker, args=(r, 2, port, out)) for r in range(2)]
+    store = str(tmp_path / "store")
+    procs = [ctx.Process(target=_is_worker, args=(r, 2, store, out)) for r in range(2)]
     for p in procs:
         p.start()
     res = out.get(timeout=120)
@@ -125,10 +119,8 @@ def test_two_partition_is_weight_normalisation():
     torch.testing.assert_close(eq, single, rtol=0, atol=0)
 
 
-def _publish_worker(rank, world, port, out):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _publish_worker(rank, world, store, out):
+    _init(rank, world, store)
     from rela_amd.learner import broadcast_weights, ffnet_flat_layout
 
     layout, total = ffnet_flat_layout(18)
@@ -143,7 +135,7 @@ def _publish_worker(rank, world, port, out):
     dist.destroy_process_group()
 
 
-def test_flat_weight_publish_layout_and_broadcast():
+def test_flat_weight_publish_layout_and_broadcast(tmp_path):
     """The flat parameter buffer of csrc/learner.hip (rela_ffnet_params order, segments padded to 4
     floats) broadcast from the learner rank to an actor-only rank."""
     from rela_amd.learner import ffnet_flat_layout
@@ -157,8 +149,8 @@ def test_flat_weight_publish_layout_and_broadcast():
     assert offs["net.2.weight"] == 8192 + 32 and offs["fc_a.weight"] == offs["fc_v.bias"] + 4
     ctx = mp.get_context("spawn")
     out = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_publish_worker, args=(r, 2, port, out)) for r in range(2)]
+    store = str(tmp_path / "store")
+    procs = [ctx.Process(target=_publish_worker, args=(r, 2, store, out)) for r in range(2)]
     for p in procs:
         p.start()
     same, key, shape, off, val, tot = out.get(timeout=120)
@@ -212,10 +204,8 @@ class _OraclePartition:
         assert self.o.update(p.numpy()) == 0
 
 
-def _exchange_worker(rank, world, port, out, scheduled=False):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def _exchange_worker(rank, world, store, out, scheduled=False):
+    _init(rank, world, store)
     from rela_amd.learner import ffnet_flat_layout
     from rela_amd.parallel import FieldSpec, PartitionedReplay, PartitionServer
 
@@ -260,7 +250,7 @@ def _exchange_worker(rank, world, port, out, scheduled=False):
 
 
 @pytest.mark.parametrize("scheduled", [False, True], ids=["command-words", "scheduled"])
-def test_partitioned_replay_exchange_over_three_ranks(scheduled):
+def test_partitioned_replay_exchange_over_three_ranks(scheduled, tmp_path):
     """Learner rank + two actor ranks (gloo): B/G sampling per partition, ONE packed row gather per sample, IS weights
     normalised over both partitions, priority scatter and the flat weight publish -- with a command word per call and
     in scheduled mode (command words only at publish / stop, an asynchronous sample in between).  Each partition must behave exactly
@@ -272,8 +262,8 @@ def test_partitioned_replay_exchange_over_three_ranks(scheduled):
 
     ctx = mp.get_context("spawn")
     out = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_exchange_worker, args=(r, 3, port, out, scheduled)) for r in range(3)]
+    store = str(tmp_path / "store")
+    procs = [ctx.Process(target=_exchange_worker, args=(r, 3, store, out, scheduled)) for r in range(3)]
     for p in procs:
         p.start()
     msgs = [out.get(timeout=180) for _ in range(3)]

@@ -124,3 +124,65 @@ def test_lstm_step_fast_trunk_within_stated_tolerance(N):
             assert np.array_equal(a, b), name
     assert float((fast[2].argmax(1) == ref[2].argmax(1)).mean()) >= 0.995
     net.close()
+
+
+# test_lstm_step_f32x3_is_f32_accurate: how much further from f64 than the f32 mode the f32x3 mode may be (mean / max |error|
+# of h, c and Q), and how much further the bf16x2 mode must be than f32x3 (mean |error|) -- so that the test would notice
+# f32x3 running two-part arithmetic anywhere in the step.  Measured on the MI355X (f32x3 / f32: mean 0.34-0.97, max
+# 0.25-1.22; bf16x2 / f32x3, mean: h 5.8-7.1 and c 6.0-7.4 at a fresh initialisation, 30-37 at x 4.6; Q 2.8-3.5 and 30-37:
+# Q's error at a fresh initialisation is half f32 rounding of the heads, which every mode runs in f32)
+X3_MEAN_SLACK, X3_MAX_SLACK = 1.25, 1.5
+BF16X2_SEPARATION = {"h": 4.0, "c": 4.0, "q": 2.0}
+
+
+@pytest.mark.parametrize("scale", [1.0, 4.6])
+@pytest.mark.parametrize("N", [515, 1537, 3200])
+def test_lstm_step_f32x3_is_f32_accurate(N, scale, record_property):
+    """h, c and Q of one step in all three precision modes against a float64 evaluation of the same step on the CPU
+    (tests/f64_ref.py): the f32x3 mode is as close to f64 as the exact f32 mode (mean and max |error|), and the bf16x2
+    mode is several times further away.  N = 515 (ragged, just above kEmuConvMinN), 1,537 (ragged row blocks of the
+    gate GEMM) and 3,200 (the R2D2 actor's rows in bench.py); at a fresh initialisation and with every tensor x 4.6 (the
+    scale of trained weights).  The launch census shows the three-part kernels (conv12_s3, conv3_img_s3,
+    gemm_s3<gates_x>) and no split-bf16 kernel in the f32x3 step.  The measured errors are recorded."""
+    import torch
+
+    from f64_ref import err_stats, lstmnet_step
+    from kernel_names import SPLIT_BF16, X3_LSTM
+    from synth import synth_lstm_params, synth_obs
+
+    A = 18
+    p = {k: (v * scale).astype(np.float32) for k, v in synth_lstm_params(A, 61).items()}
+    rng = np.random.default_rng(N + 17)
+    s = synth_obs(N, 700 + N)
+    legal = (rng.uniform(size=(N, A)) < 0.85).astype(np.float32)
+    legal[:, 0] = 1.0
+    h_in = rng.normal(0, 0.3, (N, 512)).astype(np.float32)
+    c_in = rng.normal(0, 0.5, (N, 512)).astype(np.float32)
+    ref = lstmnet_step(p, s, legal, h_in, c_in, torch.float64)
+    net = GpuLstmNet(p, A)
+    err = {}
+    for mode in ("f32", "f32x3", "bf16x2"):
+        net.capi.check(net.capi.lib.rela_lstmnet_set_precision(net.h, {"f32": 0, "bf16x2": 1, "f32x3": 2}[mode]), mode)
+        with net.capi.launch_census() as census:
+            out = net.step(s, legal, h_in, c_in)
+        ran = set(census.counts)
+        if mode == "f32x3":
+            assert X3_LSTM <= ran and not (SPLIT_BF16 & ran), sorted(ran)
+        elif mode == "bf16x2":
+            assert {CONV12, "conv_bf16s<Conv3F>"} | ({"gemm_rec64_nt"} if N >= 1024 else set()) <= ran, sorted(ran)
+        else:
+            assert not ((X3_LSTM | SPLIT_BF16) & ran), sorted(ran)
+        err[mode] = {name: err_stats(got, r) for name, got, r in zip(("h", "c", "q"), out[:3], ref[:3])}
+    net.close()
+    for mode, e in err.items():
+        for name, (mx, mean) in e.items():
+            record_property("max_abs_err_vs_f64_%s_%s" % (name, mode), mx)
+            record_property("mean_abs_err_vs_f64_%s_%s" % (name, mode), mean)
+    print("N=%d x%.1f |err| vs f64 (max / mean): %s" % (N, scale, "; ".join(
+        "%s %s" % (m, " ".join("%s %.3g/%.3g" % (k, *v) for k, v in e.items())) for m, e in err.items())))
+    for name in ("h", "c", "q"):
+        f32, x3, b2 = err["f32"][name], err["f32x3"][name], err["bf16x2"][name]
+        record_property("bf16x2_over_f32x3_mean_%s" % name, b2[1] / x3[1])
+        assert x3[1] <= X3_MEAN_SLACK * f32[1], (name, err)
+        assert x3[0] <= X3_MAX_SLACK * f32[0], (name, err)
+        assert b2[1] >= BF16X2_SEPARATION[name] * x3[1], (name, err)

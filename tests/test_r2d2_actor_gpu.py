@@ -90,11 +90,14 @@ def _run(mode, R=8, K=4, precision="f32"):
     return np.array(acts), np.array(prios), w, size, nseq_total
 
 
-@pytest.mark.parametrize("R,K,precision", [(8, 4, "f32"), (128, 64, "f32"), (128, 64, "bf16x2")])
+@pytest.mark.parametrize("R,K,precision", [(8, 4, "f32"), (128, 64, "f32"), (128, 64, "bf16x2"), (512, 64, "f32x3"),
+                                         (3200, 80, "f32x3")])
 def test_post_step_reuses_the_act_step_bit_identically(R, K, precision):
     """(r4: also at 128 rows in BOTH precision modes: from 128 rows up the bf16x2 LSTM net runs its conv trunk on the
-    split-bf16 kernels -- asserted through the launch census -- and the memoised step must still be bit-identical)"""
-    from kernel_names import CONV12
+    split-bf16 kernels -- asserted through the launch census -- and the memoised step must still be bit-identical.
+    Also in f32x3, bench.py's R2D2 precision, at 512 rows and at bench.py's R2D2 actor shape of 3,200 rows: the census
+    asserts the three-part trunk and gate GEMM ran, and no split-bf16 kernel.)"""
+    from kernel_names import CONV12, SPLIT_BF16, X3_LSTM
     from rela_amd import _capi as capi
 
     with capi.launch_census() as census:
@@ -102,6 +105,10 @@ def test_post_step_reuses_the_act_step_bit_identically(R, K, precision):
     fast = {CONV12, "conv_bf16s<Conv3F>"}
     ran = set(census.counts)
     assert (fast <= ran) if (precision == "bf16x2" and R >= 128) else not (fast & ran), (precision, sorted(ran))
+    if precision == "f32x3" and R >= 512:
+        assert X3_LSTM <= ran and not (SPLIT_BF16 & ran), sorted(ran)
+    else:
+        assert not (X3_LSTM & ran), (precision, sorted(ran))
     assert base[3] > 0 and base[4] == base[3]
     for mode in ("switch", "reload"):
         other = _run(mode, R, K, precision)

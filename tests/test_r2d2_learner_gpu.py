@@ -206,13 +206,34 @@ def _random_batch(rng, A, B, seq, burn, n, device):
     return batch, tt(rng.uniform(0.2, 1.0, B).astype(np.float32))
 
 
+# the three-part kernels of an f32x3 R2D2 learner step: both trunks and the x part of both gate GEMMs, from
+# kEmuConvMinN = 512 frames (T * B) up; below that the f32 kernels (csrc/ffnet.hip lstm_trunk_launch)
+R2D2_X3_MIN_FRAMES = 512
+
+
+def _assert_r2d2_census(counts, precision, frames):
+    from kernel_names import SPLIT_BF16, X3_LSTM
+
+    ran = set(counts)
+    if precision == "f32x3" and frames >= R2D2_X3_MIN_FRAMES:
+        assert X3_LSTM <= ran and not (SPLIT_BF16 & ran), sorted(ran)
+    elif precision == "bf16x2":
+        assert R2D2_FAST_KERNELS <= ran, sorted(ran)
+    else:
+        assert not ((X3_LSTM | SPLIT_BF16) & ran), sorted(ran)
+
+
+@pytest.mark.parametrize("precision", ["f32", "f32x3"])
 @pytest.mark.parametrize("A,B,seq,burn,n", [(18, 64, 80, 40, 3), (6, 5, 7, 0, 2), (18, 33, 12, 6, 3)])
-def test_hip_r2d2_learner_matches_autograd(A, B, seq, burn, n):
+def test_hip_r2d2_learner_matches_autograd(A, B, seq, burn, n, precision):
     """C4's learner shape (B = 64, seq 80 / burn-in 40 / n 3 -> 7,872 frames, 83 BPTT steps), a batch without
     burn-in and a ragged batch: loss, priorities and every gradient tensor against PyTorch autograd of
-    rela_amd/pyrela/r2d2.py on the same device."""
+    rela_amd/pyrela/r2d2.py on the same device, in the exact f32 mode and in f32x3 (bench.py's R2D2 precision) at the
+    same tolerances.  The launch census shows the f32x3 step's three-part kernels from 512 frames; the 45 frames of
+    (6, 5, 7, 0, 2) run the f32 kernels in either mode."""
     import torch
 
+    from rela_amd import _capi as capi
     from rela_amd.learner import HipR2D2Learner
 
     torch.backends.cudnn.allow_tf32 = False
@@ -221,9 +242,12 @@ def test_hip_r2d2_learner_matches_autograd(A, B, seq, burn, n):
     agent = _agent(A, n, 0.997, 0.9, seq, burn, 71, 72, "cuda:0")
     batch, weight = _random_batch(rng, A, B, seq, burn, n, "cuda:0")
     learner = HipR2D2Learner.from_agent(agent, B, grad_clip=1e9)
-    loss, prio, loss_seq = learner.backward(batch, weight)
+    learner.set_precision(precision)
+    with capi.launch_census() as census:
+        loss, prio, loss_seq = learner.backward(batch, weight)
     learner.check()  # no grid-barrier timeout in the persistent recurrent kernels
     torch.cuda.synchronize()
+    _assert_r2d2_census(census.counts, precision, (burn + seq + n) * B)
     ref_loss, ref_prio = agent.loss(batch, sync_priority=False)
     (ref_loss * weight).mean().backward()
     np.testing.assert_allclose(loss_seq.cpu().numpy(), ref_loss.detach().cpu().numpy(), rtol=2e-4, atol=2e-4)
@@ -351,14 +375,17 @@ def test_hip_r2d2_learner_fast_target_trunk_within_tolerance(B, seq, burn):
     learner.close()
 
 
-def test_hip_r2d2_learner_is_bit_reproducible_under_uneven_load():
+@pytest.mark.parametrize("precision", ["bf16x2", "f32x3"])
+def test_hip_r2d2_learner_is_bit_reproducible_under_uneven_load(precision):
     """The persistent recurrent kernels hand h_t / the gate gradients from CU to CU inside one launch (write-through
     stores, one counter per step, sc1 loads in place of an acquire fence: csrc/learner_r2d2.hip).  A stale read would be
     a race: it would come and go with timing.  The same batch at C4's shape is therefore differentiated twelve times --
     alone, and next to another stream that keeps the chip unevenly busy with GEMMs and copies -- and loss, priorities
-    and every gradient must be bit-identical each time (and match autograd, test_hip_r2d2_learner_matches_autograd)."""
+    and every gradient must be bit-identical each time (and match autograd, test_hip_r2d2_learner_matches_autograd) --
+    in bf16x2 and in f32x3, bench.py's R2D2 precision (the census of the first run shows that mode's kernels)."""
     import torch
 
+    from rela_amd import _capi as capi
     from rela_amd.learner import HipR2D2Learner
 
     A, B, seq, burn, n = 18, 64, 80, 40, 3
@@ -366,7 +393,7 @@ def test_hip_r2d2_learner_is_bit_reproducible_under_uneven_load():
     agent = _agent(A, n, 0.997, 0.9, seq, burn, 71, 72, "cuda:0")
     batch, weight = _random_batch(rng, A, B, seq, burn, n, "cuda:0")
     learner = HipR2D2Learner.from_agent(agent, B, grad_clip=1e9)
-    learner.set_precision("bf16x2")
+    learner.set_precision(precision)
     side = torch.cuda.Stream()
     x = torch.randn(3072, 3072, device="cuda")
     big = torch.empty(64 << 20, dtype=torch.uint8, device="cuda")
@@ -377,7 +404,12 @@ def test_hip_r2d2_learner_is_bit_reproducible_under_uneven_load():
                 for _ in range(1 + rep % 5):
                     x = (x @ x).clamp_(-1, 1)
                     big.fill_(rep)
-        loss, prio, loss_seq = learner.backward(batch, weight)
+        if rep == 0:
+            with capi.launch_census() as census:
+                loss, prio, loss_seq = learner.backward(batch, weight)
+            _assert_r2d2_census(census.counts, precision, (burn + seq + n) * B)
+        else:
+            loss, prio, loss_seq = learner.backward(batch, weight)
         learner.check()
         torch.cuda.synchronize()
         cur = (loss.clone(), prio.clone(), loss_seq.clone(), learner.flat()[1].clone())
@@ -387,3 +419,68 @@ def test_hip_r2d2_learner_is_bit_reproducible_under_uneven_load():
             for a, b, name in zip(cur, ref, ("loss", "priority", "loss_seq", "gradients")):
                 assert torch.equal(a, b), "run %d differs from run 0 in %s" % (rep, name)
     learner.close()
+
+
+# test_hip_r2d2_learner_f32x3_is_f32_accurate: how much further from f64 than the f32 mode the f32x3 mode may be (loss per
+# sequence and priorities: mean / max |error|, gradients: relative Frobenius error per tensor), and how much further the
+# bf16x2 mode must be than f32x3 (priorities: mean |error|).  Measured on the MI355X (f32x3 / f32: loss per sequence mean
+# 0.94-1.22, max 1.00-1.27; priorities mean 1.04-1.09, max 1.00-1.25; gradients 0.002-1.09 -- at B = 33 the f32 mode's
+# conv1 gradient carries a ReLU flip; bf16x2 / f32x3, mean: priorities 1.9-2.5, loss per sequence 1.5-2.1).  The
+# separation is small because only the trunk and the x part of the gates differ between the modes: the recurrence, the
+# heads and the loss run in f32 in all three, and their rounding is most of the error.
+X3_MEAN_SLACK, X3_MAX_SLACK, X3_GRAD_SLACK, BF16X2_SEPARATION = 1.5, 1.6, 1.5, 1.5
+
+
+@pytest.mark.parametrize("B,seq,burn,n", [(16, 80, 40, 3), (33, 12, 6, 3)])
+def test_hip_r2d2_learner_f32x3_is_f32_accurate(B, seq, burn, n, record_property):
+    """Loss per sequence, priorities and every gradient tensor of one learner step in all three precision modes against a
+    float64 evaluation of the same step on the CPU (tests/f64_ref.py: r2d2.py's loss, autograd): the f32x3 mode is as
+    close to f64 as the exact f32 mode, and its priorities are closer than the bf16x2 mode's (the loss per sequence does
+    not separate the two arithmetics reliably -- 1.5 x at B = 16 -- and is held to the f32 bound only).
+    B = 16 at C4's sequence shape (seq 80 / burn-in 40 / n 3: 1,968 frames) and a ragged B = 33 (seq 12 / burn-in 6:
+    693 frames).  The launch census shows the three-part kernels and no split-bf16 kernel in the f32x3 step.  Gradients
+    are compared by their relative Frobenius error per tensor (a unit within rounding of zero may switch its ReLU in any
+    mode, which makes single entries noisy)."""
+    import torch
+
+    from f64_ref import err_stats, r2d2_loss, rel_fro
+    from rela_amd import _capi as capi
+    from rela_amd.learner import HipR2D2Learner
+
+    A, gamma, eta = 18, 0.997, 0.9
+    rng = np.random.default_rng(B * 100 + seq)
+    agent = _agent(A, n, gamma, eta, seq, burn, 91, 92, "cuda:0")
+    batch, weight = _random_batch(rng, A, B, seq, burn, n, "cuda:0")
+    sd = lambda net: {k: v.detach().cpu() for k, v in net.state_dict().items()}
+    _, prio64, ls64, g64 = r2d2_loss(sd(agent.online_net), sd(agent.target_net), batch, weight, gamma, n, eta, seq, burn,
+                                     torch.float64)
+    learner = HipR2D2Learner.from_agent(agent, B, grad_clip=1e9)
+    err, gerr = {}, {}
+    for mode in ("f32", "f32x3", "bf16x2"):
+        learner.set_precision(mode)
+        with capi.launch_census() as census:
+            _, prio, loss_seq = learner.backward(batch, weight)
+        learner.check()
+        torch.cuda.synchronize()
+        _assert_r2d2_census(census.counts, mode, (burn + seq + n) * B)
+        err[mode] = {"loss_seq": err_stats(loss_seq, ls64), "priority": err_stats(prio, prio64)}
+        grads = learner.state_dict("grads")
+        gerr[mode] = {k: rel_fro(grads[k], g64[k]) for k in HipR2D2Learner.KEYS}
+    learner.close()
+    for mode in err:
+        for name, (mx, mean) in err[mode].items():
+            record_property("max_abs_%s_err_vs_f64_%s" % (name, mode), mx)
+            record_property("mean_abs_%s_err_vs_f64_%s" % (name, mode), mean)
+        for k, v in gerr[mode].items():
+            record_property("rel_fro_grad_err_vs_f64_%s_%s" % (k, mode), v)
+        print("B=%d seq=%d %s: %s; grad rel-Frobenius %s" % (B, seq, mode, "; ".join(
+            "%s |err| max %.3g mean %.3g" % (k, *v) for k, v in err[mode].items()),
+            " ".join("%s=%.3g" % (k, v) for k, v in gerr[mode].items())))
+    for name in ("loss_seq", "priority"):
+        f32, x3, b2 = err["f32"][name], err["f32x3"][name], err["bf16x2"][name]
+        record_property("bf16x2_over_f32x3_mean_" + name, b2[1] / x3[1])
+        assert x3[1] <= X3_MEAN_SLACK * f32[1], (name, err)
+        assert x3[0] <= X3_MAX_SLACK * f32[0], (name, err)
+    assert err["bf16x2"]["priority"][1] >= BF16X2_SEPARATION * err["f32x3"]["priority"][1], err
+    for k in HipR2D2Learner.KEYS:
+        assert gerr["f32x3"][k] <= X3_GRAD_SLACK * gerr["f32"][k], (k, gerr["f32x3"][k], gerr["f32"][k])
