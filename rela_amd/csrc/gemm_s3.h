@@ -41,7 +41,6 @@ using f32emu::f32x2;
 using f32emu::f32x4;
 using f32emu::kMaxBlocks;
 using f32emu::kStageU4;
-using f32emu::kT;
 using f32emu::TN;
 using f32emu::u32x4;
 using f32emu::WRegs;
@@ -109,29 +108,39 @@ __device__ __forceinline__ void split3_4(const f32x4& v, uint2& p0, uint2& p1, u
 //     side: lane l fetches (row r = (l & 15) >> 1, 16-byte unit u = 2 (l >> 4) + (l & 1)), which puts unit u of row r at
 //     slot 16 (u >> 1) + 2 r + (u & 1) -- the 16 lanes a ds_read_b128 pass serves (rows 0-7 at unit u0, rows 0-7 at
 //     u0 + 1) then hit the 16 bank groups once each (SQ_LDS_BANK_CONFLICT = 0);
-//   * a block owns a range of 16-row tiles and 128 COLUMNS; it walks the range in passes of up to TMV tiles; the four
-//     waves own 32 columns each and ALL tiles of the pass: an activation fragment is fetched from global memory once
-//     per block and read from LDS by four waves.  (r5, first form: 64 columns and <= 6 tiles per block moved 1.6 GB
-//     through L2 for fc at 6,400 rows and spent more issue slots on its 15 LDS-DMAs per pair -- each with its M0 and
-//     address arithmetic -- than on its 52 MFMAs: 167 us.  Bytes per MFMA go with 1 / rows + 1 / columns.)
-//   * WEIGHTS: a wave's own six fragments per k-step arrive by LDS-DMA too (fragment order = lane order: 1 KB
+//   * a block owns a range of 16-row tiles and 128 COLUMNS; it walks the range in passes of up to TMV tiles; its EIGHT
+//     waves (two per SIMD) own 16 columns each and ALL tiles of the pass: an activation fragment is fetched from global
+//     memory once per block and read from LDS by eight waves.  (r5, first form: 64 columns and <= 6 tiles per block
+//     moved 1.6 GB through L2 for fc at 6,400 rows and spent more issue slots on its 15 LDS-DMAs per pair -- each with
+//     its M0 and address arithmetic -- than on its 52 MFMAs: 167 us.  Bytes per MFMA go with 1 / rows + 1 / columns.
+//     r5, last form: four waves of 32 columns, one per SIMD, 7 x 32 accumulator registers each: 256 VGPRs + 256 AGPRs,
+//     148 registers spilled around the k-loops = 39 MB of scratch writes per launch, and nobody to issue MFMAs while
+//     the SIMD's only wave issued its 23 LDS-DMAs per pair: 139-141 us where this form takes 119, same box.  With
+//     16 columns a wave holds 7 x 2 x 4 = 56 + 56 accumulator registers: ~140 VGPRs, no AGPRs, no scratch, and the
+//     SIMD's other wave issues MFMAs while this one issues loads.  The price is LDS reads: 24 ds_read_b128 per 42
+//     MFMAs where the 32-column wave had 27 per 84.  tests/test_s3_resources_cpu.py guards the register budget.)
+//   * WEIGHTS: a wave's own three fragments per k-step arrive by LDS-DMA too (fragment order = lane order: 1 KB
 //     contiguous reads), into a private two-slot ring -- no register holds data in flight, so nothing the compiler does
 //     to registers can touch an outstanding load;
 //   * two activation buffers: pair P + 1 is issued when pair P starts; ONE raw s_barrier per pair (it publishes pair
 //     P's lines and retires the reads of the buffer pair P + 1 lands in); counted vmcnt, never 0 in the loop; the
 //     pipeline runs on across pass boundaries (next pass's rows, same weights);
 //   * LDS reads are inline asm (the compiler would drain vmcnt before any LDS read it can see while an LDS-DMA is
-//     pending) with counted lgkmcnt: a tile's three fragments are read while the tile before issues its 12 MFMAs.
+//     pending) with counted lgkmcnt: a tile's three fragments are read while the tile before issues its 6 MFMAs.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int TMV = 7;                       // row tiles per pass (7 x 32 accumulator registers per wave: 8 spilled)
-constexpr int CT = 2;                        // column tiles per wave (32 columns; 128 per block)
+constexpr int kGemmT = 512;                  // 8 wavefronts per block: two per SIMD (gemm_f32emu.h's kT stays the convolutions')
+constexpr int kGemmWaves = kGemmT / 64;
+constexpr int kBlockCols = 128;              // columns per block
+constexpr int TMV = 7;                       // row tiles per pass (7 x 2 x 4 = 56 main + 56 small-terms accumulator registers per wave)
+constexpr int CT = 1;                        // column tiles per wave (16 columns; 8 waves x 16 = kBlockCols)
+static_assert(kGemmWaves * CT * 16 == kBlockCols, "the waves of a block tile its columns");
 constexpr int kABuf = TMV * 6144;            // one pair of k-steps: [tile][part][rows 0-7 | 8-15] x 1 KB
 constexpr int kBSlot = CT * 3072;            // one k-step of one wave's weights: [column tile][part] x 1 KB
-constexpr int kLdsB = 2 * kABuf;             // the four waves' weight rings (2 slots each) start here
-constexpr int kLdsSpare = kLdsB + 4 * 2 * kBSlot;  // 1 KB landing zone of the padding loads
+constexpr int kLdsB = 2 * kABuf;             // the eight waves' weight rings (2 slots each) start here
+constexpr int kLdsSpare = kLdsB + kGemmWaves * 2 * kBSlot;  // 1 KB landing zone of the padding loads
 constexpr int kLdsTotal = kLdsSpare + 1024;
 static_assert(kLdsTotal <= 160 * 1024, "LDS budget");
-__host__ __device__ constexpr int glds_per_wave(int nt) { return (6 * nt + 3) / 4; }
+__host__ __device__ constexpr int glds_per_wave(int nt) { return (6 * nt + kGemmWaves - 1) / kGemmWaves; }
 
 typedef __attribute__((address_space(3))) uint8_t* lds_ptr_t;
 typedef const __attribute__((address_space(1))) uint8_t* gbl_ptr_t;
@@ -144,8 +153,8 @@ __device__ __forceinline__ void glds16(const uint8_t* g, uint8_t* l) {
 #define S3_GEMM_ABLATE 0
 #endif
 #ifndef S3_GEMM_AHEAD
-#define S3_GEMM_AHEAD 1  // activation fragments read this many tiles ahead of the MFMAs (1: 125-132 us, 2: 150-160 us for fc
-#endif                   // at 6,400 rows on the boxes of r5 -- the deeper ring costs more in registers than the LDS round trip)
+#define S3_GEMM_AHEAD 1  // activation fragments read this many tiles ahead of the MFMAs (four-wave form of r5: 1: 125-132 us,
+#endif                   // 2: 150-160 us for fc at 6,400 rows -- the deeper ring cost more in registers than the LDS round trip)
 constexpr int kAheadTiles = S3_GEMM_AHEAD;
 template <int OFF>
 __device__ __forceinline__ u32x4 lds_read128(uint32_t addr) {
@@ -186,7 +195,7 @@ __device__ __forceinline__ void issue_weights(const uint8_t* wsrc, uint8_t* lds,
   for (int q = 0; q < CT * 3; ++q) glds16(src + q * 1024, dst + q * 1024);
 }
 
-// One pass: NT row tiles x this wave's 32 columns over all KS k-steps.  J = LDS-DMA instructions per wave and pair for
+// One pass: NT row tiles x this wave's 16 columns over all KS k-steps.  J = LDS-DMA instructions per wave and pair for
 // the activations (the block's larger pass size decides it, so that the counts in flight do not change at a pass
 // boundary).  offc / offn: this wave's J source offsets (row base + part + this lane's unit) for this pass and the next.
 // In flight at the top of pair P (issue order): A(P) | W(2P) | W(2P+1) -- then W(2P+1)... see the waits below.
@@ -295,12 +304,12 @@ __device__ __forceinline__ void k_pass(const uint8_t* __restrict__ Xb, const uin
 // column groups of one row block (they read the same activations) share an L2.
 enum { kEpiRelu = 0, kEpiReluS3 = 1, kEpiRaw = 2, kEpiBias = 3 };  // 3: bias + sum, no ReLU, f32 [M][OC]
 template <class P, int EPI>
-__global__ __launch_bounds__(kT, 1) void gemm_s3(const uint8_t* __restrict__ Xb, const uint4* __restrict__ Wp,
+__global__ __launch_bounds__(kGemmT, 1) void gemm_s3(const uint8_t* __restrict__ Xb, const uint4* __restrict__ Wp,
                                                  const float* __restrict__ bias, void* __restrict__ out_, int M) {
-  constexpr int NCG = P::OC / (64 * CT);
+  constexpr int NCG = P::OC / kBlockCols;
   constexpr bool OUT_S3 = EPI == kEpiReluS3;
   const int kp0 = (int)((P::KS / 2) * blockIdx.y / gridDim.y), kp1 = (int)((P::KS / 2) * (blockIdx.y + 1) / gridDim.y);
-  static_assert(P::OC % (64 * CT) == 0, "a block owns 128 columns");
+  static_assert(P::OC % kBlockCols == 0, "a block owns 128 columns");
   __shared__ __attribute__((aligned(1024))) uint8_t lds[kLdsTotal];
   const uint32_t lds0 = (uint32_t)(size_t)(lds_ptr_t)lds;
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, g = lane >> 4;
@@ -318,10 +327,10 @@ __global__ __launch_bounds__(kT, 1) void gemm_s3(const uint8_t* __restrict__ Xb,
   const int ntmax = base + (rem ? 1 : 0);
   auto first_of = [&](int p) { return p < rem ? (base + 1) * p : (base + 1) * rem + base * (p - rem); };
   auto size_of = [&](int p) { return p < rem ? base + 1 : base; };
-  // this wave's columns: 128 cg + 32 wave .. + 31 = column tiles u = 2 (wave & 1), + 1 of the 64-column pack group
-  const int cg64 = cg * 2 + (wave >> 1), u0 = 2 * (wave & 1);
+  // this wave's columns: 128 cg + 16 wave .. + 15 = column tile u = wave & 3 of the 64-column pack group 2 cg + (wave >> 2)
+  const int cg64 = cg * 2 + (wave >> 2), u0 = wave & 3;
   const uint8_t* wsrc = reinterpret_cast<const uint8_t*>(Wp) + ((size_t)cg64 * P::KS * kStageU4 + (size_t)u0 * 3 * 64) * 16;
-  const int col0 = cg * 128 + 32 * wave + 4 * g;  // this lane's first channel (column tile j: + 16 j)
+  const int col0 = cg * kBlockCols + 16 * CT * wave + 4 * g;  // this lane's first channel (column tile j: + 16 j)
   // fragment read address of (tile 0, part 0, half 0): rows 8-15 are the second 1 KB block of a (tile, part)
   const uint32_t frag_base = (uint32_t)((li >> 3) * 1024 + (16 * (g >> 1) + 2 * (li & 7) + (g & 1)) * 16);
   // LDS-DMA source: this lane's row inside an 8-row block and its 16-byte unit inside the 128-byte line
@@ -341,13 +350,13 @@ __global__ __launch_bounds__(kT, 1) void gemm_s3(const uint8_t* __restrict__ Xb,
   auto run = [&](auto ntm) {
     constexpr int NTM = decltype(ntm)::value, J = glds_per_wave(NTM);  // the block's passes have NTM or NTM - 1 tiles
     uint32_t offc[J], offn[J], ldst[J];
-    // LDS-DMA instruction i = wave + 4 j of a pair: i = (tile * 3 + part) * 2 + row half; an instruction past the pass's
+    // LDS-DMA instruction i = wave + 8 j of a pair: i = (tile * 3 + part) * 2 + row half; an instruction past the pass's
     // tiles fetches instruction 0's line again (into the spare KB, or into a tile slot this pass does not read)
     auto set_off = [&](uint32_t (&off)[J], int p) {
       const int nt = size_of(p), t0 = r0 + first_of(p);
 #pragma unroll
       for (int j = 0; j < J; ++j) {
-        int i = wave + 4 * j;
+        int i = wave + kGemmWaves * j;
         if (i >= 6 * nt) i = 0;
         const int part = (i >> 1) % 3, t = i / 6, b = i & 1;
         const int row = min((t0 + t) * 16 + b * 8 + lr, M - 1);
@@ -356,7 +365,7 @@ __global__ __launch_bounds__(kT, 1) void gemm_s3(const uint8_t* __restrict__ Xb,
     };
 #pragma unroll
     for (int j = 0; j < J; ++j) {
-      const int i = wave + 4 * j;
+      const int i = wave + kGemmWaves * j;
       ldst[j] = i < 6 * ntmax ? (uint32_t)i * 1024u : (uint32_t)kLdsSpare;
     }
     set_off(offc, 0);
@@ -368,7 +377,7 @@ __global__ __launch_bounds__(kT, 1) void gemm_s3(const uint8_t* __restrict__ Xb,
       for (int j = 0; j < J; ++j) glds16(src + offc[j], lds + ldst[j]);
       issue_weights<P>(wsrc, lds, kLdsB + wave * 2 * kBSlot, 2 * kp0, 0, lane);
     }
-    // one pass of NT tiles: accumulators (NT x 2 column tiles x {main, small terms} x 4 registers -- sized by NT, not by
+    // one pass of NT tiles: accumulators (NT x CT column tiles x {main, small terms} x 4 registers -- sized by NT, not by
     // TMV: with all eight tiles' registers live the kernel spilled 1.4 KB per lane and wrote 100 MB of scratch per launch),
     // the k-loop, the epilogue
     auto one_pass = [&](auto ntag, int p) {
@@ -439,7 +448,7 @@ struct Plan {
 };
 template <class P>
 inline Plan plan(int M, bool may_split) {
-  constexpr int NCG = P::OC / (64 * CT);
+  constexpr int NCG = P::OC / kBlockCols;
   const int rt_total = (M + 15) / 16;
   const int full = kMaxBlocks / 2;  // one block per CU
   Plan pl;
@@ -454,8 +463,8 @@ inline Plan plan(int M, bool may_split) {
 // slices > 1 (EPI = kEpiRaw only): out = f32 [slices][M][OC] raw sums
 template <class P, int EPI>
 inline void launch(const void* X, const uint4* Wp, const float* bias, void* out, int M, hipStream_t s, Plan pl) {
-  constexpr int NCG = P::OC / (64 * CT);
-  hipLaunchKernelGGL((gemm_s3<P, EPI>), dim3(pl.nrb * NCG, EPI == kEpiRaw ? pl.slices : 1), dim3(kT), 0, s,
+  constexpr int NCG = P::OC / kBlockCols;
+  hipLaunchKernelGGL((gemm_s3<P, EPI>), dim3(pl.nrb * NCG, EPI == kEpiRaw ? pl.slices : 1), dim3(kGemmT), 0, s,
                      reinterpret_cast<const uint8_t*>(X), Wp, bias, out, M);
 }
 template <class P, int EPI>
