@@ -44,6 +44,15 @@ int rela_stream_wait_stream(void* waiter, void* signaler, int device);
 /* asynchronous host->device copy on `stream` (page-locked sources overlap with compute) */
 int rela_memcpy_h2d_async(void* dst_dev, const void* src_host, int64_t bytes, void* stream, int device);
 
+/* GameState::computeFeature (atari/game_state.h:53-82,122-133) for many envs in one launch.  screens_dev:
+ * [rows][2][height][width][3] u8, screen 0 the current and screen 1 the previous screen, RGB-interleaved as
+ * ALEInterface::getScreenRGB writes them; planes_dev: [rows][84][84] u8.  Per pixel: the element-wise max of the two
+ * screens / 255, bilinear to 84x84 with align_corners, gray 0.21 R + 0.72 G + 0.07 B, x 255 truncated to u8, all in a
+ * fixed float32 order without contraction (csrc/atari_screen.h states it; the host restatement there is bit-identical).
+ * 2 <= height, width <= 512, rows >= 1 (RELA_EINVAL otherwise).  Asynchronous on `stream` (the device of the buffers
+ * must be current).                                                                                                  */
+int rela_atari_features(const uint8_t* screens_dev, int rows, int height, int width, uint8_t* planes_dev, void* stream);
+
 /* ===================================================================================
  * Prioritized replay  --  rela/prioritized_replay.h:173-348 (PrioritizedReplay<T>) over
  * :14-171 (ConcurrentQueue<T>), bound in rela/pybind.cc:37-59.
@@ -393,6 +402,17 @@ void* rela_apex_actor_obs_slot(rela_apex_actor* a);
  * does before VectorEnv::step stacks K observations (rela/env.h:63-82).                                          */
 void* rela_apex_actor_plane_stage(rela_apex_actor* a);
 int rela_apex_actor_slide_stacks(rela_apex_actor* a, const uint8_t* restart_host, void* stream);
+/* Raw screens instead of planes (envs that render ALE screens: rela/screen_env.h).  set_screen_input (once, before the
+ * first act) sizes the screen stage: [rows][2][height][width][3] u8 on the device, screen 0 the current and screen 1
+ * the previous RGB screen of every row (rela_atari_features).  screens_to_stacks computes every row's 84x84 feature
+ * from the staged pair and writes the stacks of rela_apex_actor_obs_slot() with the rule of slide_stacks: a row with
+ * restart_host[row] == 1 gets its feature in all four planes (computeFeature after reset(): the deque is empty), any
+ * other row slides by one plane and takes the feature as plane 3.  restart_host is u8[rows] on the host, each 0 or 1;
+ * valid from the first act(), where every row must be flagged 1.  Stream-ordered after the uploads the caller made
+ * `stream` wait for; the stacks are complete on `stream` when it returns.                                        */
+int rela_apex_actor_set_screen_input(rela_apex_actor* a, int height, int width);
+void* rela_apex_actor_screen_stage(rela_apex_actor* a);
+int rela_apex_actor_screens_to_stacks(rela_apex_actor* a, const uint8_t* restart_host, void* stream);
 /* Device addresses of the CURRENT obs["eps"] f32[rows] and obs["legal_move"] f32[rows][A]; act()
  * snapshots them into the history slot of the step, so a transition's obs side carries the values
  * of time t-n and its next_obs side those of time t (dqn_actor.h:84-90).                      */
@@ -454,6 +474,9 @@ void rela_r2d2_actor_destroy(rela_r2d2_actor* a);
 void* rela_r2d2_actor_obs_slot(rela_r2d2_actor* a);
 void* rela_r2d2_actor_plane_stage(rela_r2d2_actor* a);                                          /* as rela_apex_actor_plane_stage */
 int rela_r2d2_actor_slide_stacks(rela_r2d2_actor* a, const uint8_t* restart_host, void* stream); /* as rela_apex_actor_slide_stacks */
+int rela_r2d2_actor_set_screen_input(rela_r2d2_actor* a, int height, int width);        /* as rela_apex_actor_set_screen_input */
+void* rela_r2d2_actor_screen_stage(rela_r2d2_actor* a);                                 /* as rela_apex_actor_screen_stage */
+int rela_r2d2_actor_screens_to_stacks(rela_r2d2_actor* a, const uint8_t* restart_host, void* stream); /* as rela_apex_... */
 /* R2D2Actor::act  r2d2_actor.h:221-249; arguments as rela_apex_actor_act */
 int rela_r2d2_actor_act(rela_r2d2_actor* a, const rela_lstmnet* online, const uint8_t* obs_host,
                         const float* eps_host, const float* legal_host, int64_t* action_host,

@@ -65,7 +65,8 @@ def build_pybind(verbose=False, force=False):
     flags = ["-std=c++17", "-O2", "-fPIC", "-shared", "-fvisibility=hidden", "-D_GLIBCXX_USE_CXX11_ABI=1", "-w"]
     libs = ["-L" + os.path.join(tdir, "lib"), "-ltorch", "-ltorch_cpu", "-lc10", "-ltorch_python",
             "-Wl,-rpath," + os.path.join(tdir, "lib")]
-    hdrs = glob.glob(os.path.join(PYBIND_DIR, "include", "rela", "*.h")) + [os.path.join(ROOT, "include", "rela_amd.h")]
+    hdrs = glob.glob(os.path.join(PYBIND_DIR, "include", "rela", "*.h")) + [os.path.join(ROOT, "include", "rela_amd.h"),
+                                                                             os.path.join(CSRC, "atari_screen.h")]
     jobs = []
     outs = []
     for name, src, extra in (("rela", "rela_module.cc", ["-L" + PKG, "-lrela_amd", "-Wl,-rpath,$ORIGIN/.."]),

@@ -55,6 +55,9 @@ struct rela_apex_actor {
   int64_t tick = 0, key_tick = -1;   // ticks stored so far; tick of the last keyframe (all planes stored)
   uint8_t* restart = nullptr;
   uint8_t* fresh_planes = nullptr;  // [R][7056] staging of the newest plane of every row (rela_apex_actor_plane_stage)        // [R] rela_apex_actor_slide_stacks: 1 = the row's stack restarts with its new plane
+  uint8_t* screens = nullptr;       // [R][2][scr_h][scr_w][3] screen pairs (rela_apex_actor_set_screen_input)
+  uint8_t* screen_prev = nullptr;   // [R][28224] evaluation shard (no replay): copy of the one slot it acts on
+  int scr_h = 0, scr_w = 0;
 };
 
 namespace {
@@ -124,7 +127,7 @@ extern "C" void rela_apex_actor_destroy(rela_apex_actor* a) {
   DeviceGuard g(a->device);
   (void)hipDeviceSynchronize();
   void* ps[] = {a->obs, a->act, a->rew, a->term, a->eps, a->legal, a->q, a->out_r, a->out_b, a->prio, a->out_t, a->ws,
-                a->eps_hist, a->legal_hist, a->ref_hist, a->q_hist, a->restart, a->fresh_planes};
+                a->eps_hist, a->legal_hist, a->ref_hist, a->q_hist, a->restart, a->fresh_planes, a->screens, a->screen_prev};
   for (void* p : ps) (void)hipFree(p);
   delete a;
 }
@@ -154,6 +157,30 @@ extern "C" int rela_apex_actor_slide_stacks(rela_apex_actor* a, const uint8_t* r
   const int H = a->n + 1, slot = next_slot(a), prev = (slot + H - 1) % H;
   return slide_stacks(a->obs + (size_t)slot * a->R * kObs, a->obs + (size_t)prev * a->R * kObs, a->fresh_planes, a->restart,
                       a->R, s);
+}
+extern "C" int rela_apex_actor_set_screen_input(rela_apex_actor* a, int height, int width) {
+  RELA_CHECK(a && height >= 2 && height <= 512 && width >= 2 && width <= 512, RELA_EINVAL,
+             "rela_apex_actor_set_screen_input: bad arguments (screens must be 2..512 x 2..512)");
+  RELA_CHECK(a->act_calls == 0 && !a->screens, RELA_ESTATE, "rela_apex_actor_set_screen_input: call it once, before the first act()");
+  DeviceGuard g(a->device);
+  const size_t bytes = (size_t)a->R * 2 * height * width * 3;
+  RELA_HIP(hipMalloc(&a->screens, bytes));
+  RELA_HIP(hipMemset(a->screens, 0, bytes));
+  RELA_CHECK(rela_apex_actor_plane_stage(a), RELA_ENOMEM, "rela_apex_actor_set_screen_input: plane stage");
+  if (!a->replay) RELA_HIP(hipMalloc(&a->screen_prev, (size_t)a->R * kObs));
+  a->scr_h = height;
+  a->scr_w = width;
+  return RELA_OK;
+}
+extern "C" void* rela_apex_actor_screen_stage(rela_apex_actor* a) { return a ? a->screens : nullptr; }
+extern "C" int rela_apex_actor_screens_to_stacks(rela_apex_actor* a, const uint8_t* restart_host, void* stream_) {
+  RELA_CHECK(a, RELA_EINVAL, "rela_apex_actor_screens_to_stacks: bad arguments");
+  RELA_CHECK(a->count <= a->n, RELA_ESTATE, "rela_apex_actor_screens_to_stacks: act() twice without post_step()");
+  DeviceGuard g(a->device);
+  const int slot = next_slot(a), prev = a->q_slot >= 0 ? a->q_slot : slot;  // the stacks of the last act()
+  return screens_to_stacks(a->screens, a->scr_h, a->scr_w, a->fresh_planes, &a->restart, restart_host, a->act_calls == 0,
+                           a->obs + (size_t)slot * a->R * kObs, a->obs + (size_t)prev * a->R * kObs, a->screen_prev, a->R,
+                           (hipStream_t)stream_, "rela_apex_actor_screens_to_stacks");
 }
 extern "C" int rela_apex_actor_set_reuse(rela_apex_actor* a, int on) {
   RELA_CHECK(a, RELA_EINVAL, "rela_apex_actor_set_reuse: bad arguments");

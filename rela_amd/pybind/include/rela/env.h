@@ -13,13 +13,16 @@
 // there were six per env-step), envs implementing rela::FrameRowEnv render into their row directly,
 // and when ALL envs declare a sliding stack the batch carries one extra key, "__stack_restart"
 // (u8[K]: 1 = the row's stack was just restarted by reset()), which tells this module's actors
-// that only plane 3 of each row is new.
+// that only plane 3 of each row is new.  When ALL envs implement rela::ScreenEnv the batch carries "__screens"
+// ([K][2][H][W][3] u8: every env's current and previous raw screen) and "__stack_restart" instead, and the actors
+// compute the frame stacks on the device (rela/screen_env.h).
 #pragma once
 #include <memory>
 #include <tuple>
 #include <vector>
 
 #include "rela/frame_row_env.h"
+#include "rela/screen_env.h"
 #include "rela/types.h"
 
 namespace rela {
@@ -63,9 +66,12 @@ class VectorEnv {
   };
   void storeRow(const TensorDict& obs, int row);
   void createBatch(const TensorDict& firstObs);
+  void checkScreenMode();
 
   std::vector<std::shared_ptr<Env>> envs_;
   std::vector<FrameRowEnv*> frameEnvs_;  // envs_[i]'s optional extension (nullptr: copying path)
+  std::vector<ScreenEnv*> screenEnvs_;   // envs_[i]'s raw-screen extension (nullptr: none)
+  bool screen_ = false;                  // every env is a ScreenEnv: the batch carries "__screens"
   TensorDict batch_;                     // persistent, page-locked when a GPU is present
   std::vector<KeyRows> rows_;            // raw row addresses of batch_'s tensors
   bool sliding_ = false;                 // every env declared a sliding stack

@@ -130,7 +130,31 @@ namespace rela {
 void VectorEnv::append(std::shared_ptr<Env> env) {
   if (!batch_.empty()) throw std::runtime_error("VectorEnv.append after the first reset()");
   frameEnvs_.push_back(dynamic_cast<FrameRowEnv*>(env.get()));
+  screenEnvs_.push_back(dynamic_cast<ScreenEnv*>(env.get()));
   envs_.push_back(std::move(env));
+}
+
+// screen mode (rela/screen_env.h) needs every env to be a ScreenEnv of one shape and none to be a FrameRowEnv as well
+void VectorEnv::checkScreenMode() {
+  int n = 0;
+  for (size_t i = 0; i < envs_.size(); ++i) {
+    if (!screenEnvs_[i]) continue;
+    ++n;
+    if (frameEnvs_[i])
+      throw std::runtime_error("VectorEnv: env " + std::to_string(i) +
+                               " is both a ScreenEnv and a FrameRowEnv; an env hands over raw screens or finished planes, not both");
+    if (screenEnvs_[i]->screenHeight() != screenEnvs_[0]->screenHeight() ||
+        screenEnvs_[i]->screenWidth() != screenEnvs_[0]->screenWidth())
+      throw std::runtime_error("VectorEnv: screen envs of different shapes (env 0: " +
+                               std::to_string(screenEnvs_[0]->screenHeight()) + "x" + std::to_string(screenEnvs_[0]->screenWidth()) +
+                               ", env " + std::to_string(i) + ": " + std::to_string(screenEnvs_[i]->screenHeight()) + "x" +
+                               std::to_string(screenEnvs_[i]->screenWidth()) + ")");
+  }
+  if (n > 0 && n != (int)envs_.size())
+    throw std::runtime_error("VectorEnv: " + std::to_string(n) + " of " + std::to_string(envs_.size()) +
+                             " envs are ScreenEnvs; a VectorEnv holds only screen envs or none (their observations are "
+                             "built on the device from raw screens, the others' on the host)");
+  screen_ = n > 0;
 }
 
 // Allocates the persistent batch (one page-locked tensor per observation key, shaped [K, ...] like the first
@@ -149,6 +173,15 @@ void VectorEnv::createBatch(const TensorDict& firstObs) {
     kr.rowBytes = K > 0 ? (int64_t)t.nbytes() / K : 0;
     kr.dtype = t.scalar_type();
     rows_.push_back(kr);
+  }
+  if (screen_) {  // raw screens: "__screens" + "__stack_restart"; the actors build the stacks on the device
+    const int64_t H = screenEnvs_[0]->screenHeight(), W = screenEnvs_[0]->screenWidth();
+    auto scr = pin(torch::zeros({K, 2, H, W, 3}, torch::kUInt8));
+    batch_.emplace("__screens", scr);
+    auto flags = pin(torch::ones({K}, torch::kUInt8));
+    restart_ = flags.data_ptr<uint8_t>();
+    batch_.emplace("__stack_restart", flags);
+    return;
   }
   sliding_ = K > 0;
   for (auto* f : frameEnvs_) sliding_ = sliding_ && f && f->slidingStack();
@@ -172,6 +205,7 @@ void VectorEnv::storeRow(const TensorDict& obs, int row) {
         break;
       }
     if (!kr) throw std::runtime_error("VectorEnv: observation key '" + kv.first + "' was not in the first observation");
+    if (screen_ && kv.first == "s") continue;  // built on the device from the screens (rela/screen_env.h)
     const auto& src = kv.second;
     uint8_t* dst = kr->base + (int64_t)row * kr->rowBytes;
     if (src.data_ptr() == dst) continue;  // rendered in place (FrameRowEnv)
@@ -185,11 +219,17 @@ void VectorEnv::storeRow(const TensorDict& obs, int row) {
 
 TensorDict VectorEnv::reset(const TensorDict& previous) {
   const bool first = previous.empty();
+  if (first && batch_.empty()) checkScreenMode();
   for (size_t i = 0; i < envs_.size(); ++i) {
     if (first || envs_[i]->terminated()) {
       storeRow(envs_[i]->reset(), (int)i);
       if (restart_) restart_[i] = 1;
     }
+  }
+  if (first && screen_) {  // every env copies its first pair into its row and renders there from now on
+    const auto& scr = batch_.at("__screens");
+    const int64_t rb = envs_.empty() ? 0 : (int64_t)scr.nbytes() / (int64_t)envs_.size();
+    for (size_t i = 0; i < envs_.size(); ++i) screenEnvs_[i]->bindScreenRow(static_cast<uint8_t*>(scr.data_ptr()) + (int64_t)i * rb);
   }
   if (first) {  // the rows hold every env's first observation: envs that can, render into them from now on
     for (const auto& r : rows_)
@@ -1070,15 +1110,18 @@ class ActorCohort {
     const int64_t tPrep = gStats.on ? ThreadedStats::now() : 0;
     void* slot = nullptr;
     bool planes = false;
+    const bool screens = obs.count("__screens") != 0;
     {
       std::unique_lock<std::mutex> lk(m_);
       if (draining_) return drained();
-      if (!created_) create(A);
+      if (!created_) create(A, screens ? &obs.at("__screens") : nullptr);
+      if (screens != (screenBytes_ > 0))
+        throw std::runtime_error("ActorCohort: the VectorEnvs of one cohort must all hold screen envs or none");
       // (the slot moves only inside the leader's work, which every member of the round has left by now)
       slot = lstm_ ? rela_r2d2_actor_obs_slot(hr_) : rela_apex_actor_obs_slot(h_);
       // a VectorEnv whose envs all slide their frame stack marks its batch (rela/env.h): only plane 3 of every row is
       // new; the very first observation has no predecessor on the device and goes up whole
-      planes = planeUpload_ && !firstRound_ && obs.count("__stack_restart") != 0;
+      planes = !screens && planeUpload_ && !firstRound_ && obs.count("__stack_restart") != 0;
     }
     // this member's rows: frames go to the HBM history slot on the upload stream -- outside the cohort's lock, the
     // rows of different members are disjoint -- the per-env constants to the host staging under it
@@ -1086,7 +1129,17 @@ class ActorCohort {
     const int dev = locker_->execDevice;
     uint8_t* dst = static_cast<uint8_t*>(slot) + (int64_t)member * K_ * kObsBytes;
     uint8_t* flags = restartAll_.data_ptr<uint8_t>() + (int64_t)member * K_;
-    if (planes) {
+    if (screens) {
+      // raw screens (rela/screen_env.h): ONE copy of this member's screen rows into the shard's screen stage; the leader
+      // computes the features and the stacks on the device (screens_to_stacks), the first round included
+      const auto& scr = obs.at("__screens");
+      if (scr.size(0) != K_ || (int64_t)scr.nbytes() != (int64_t)K_ * screenBytes_ || !scr.is_contiguous())
+        throw std::runtime_error("ActorCohort: obs['__screens'] does not match the screen shape of the cohort");
+      check(rela_memcpy_h2d_async(static_cast<uint8_t*>(screenStage_) + (int64_t)member * K_ * screenBytes_, scr.data_ptr(),
+                                  (int64_t)K_ * screenBytes_, upload_, dev),
+            "rela_memcpy_h2d_async");
+      std::memcpy(flags, obs.at("__stack_restart").data_ptr<uint8_t>(), (size_t)K_);
+    } else if (planes) {
       // the newest plane of each of this member's rows, packed into the cohort's page-locked staging (a strided 2-D
       // DMA of K planes costs the issuing thread 2-3 x a plain copy), then ONE 1-D copy to the shard's plane stage
       constexpr int64_t kPlane = 84 * 84;
@@ -1117,7 +1170,11 @@ class ActorCohort {
     if (gStats.on) gStats.actPrep += ThreadedStats::now() - tPrep;
     rendezvous(lk, [&] {
       check(rela_stream_wait_stream(compute_, upload_, dev), "rela_stream_wait_stream");
-      if (planesThisRound_) {  // complete the stacks on the device (atari/game_state.h:53-82) before the forward
+      if (screenBytes_ > 0) {  // features + stacks from the staged screens (atari/game_state.h:53-82,122-133)
+        const uint8_t* f = restartAll_.data_ptr<uint8_t>();
+        check(lstm_ ? rela_r2d2_actor_screens_to_stacks(hr_, f, compute_) : rela_apex_actor_screens_to_stacks(h_, f, compute_),
+              "screens_to_stacks");
+      } else if (planesThisRound_) {  // complete the stacks on the device (atari/game_state.h:53-82) before the forward
         const uint8_t* f = restartAll_.data_ptr<uint8_t>();
         check(lstm_ ? rela_r2d2_actor_slide_stacks(hr_, f, compute_) : rela_apex_actor_slide_stacks(h_, f, compute_),
               "slide_stacks");
@@ -1217,7 +1274,8 @@ class ActorCohort {
 
   TensorDict drained() { return TensorDict{{"a", torch::zeros({K_}, torch::kInt64)}}; }
 
-  void create(int A) {
+  // screens: the first member's obs["__screens"] ([K][2][H][W][3]) when its VectorEnv holds screen envs
+  void create(int A, const torch::Tensor* screens) {
     if (locker_->kind() != (lstm_ ? ModelLocker::kLSTM : ModelLocker::kFF))
       throw std::runtime_error(lstm_ ? "R2D2Actor needs an AtariLSTMNet-shaped agent in its ModelLocker"
                                      : "DQNActor needs an AtariFFNet-shaped agent in its ModelLocker");
@@ -1252,6 +1310,13 @@ class ActorCohort {
     planeHost_ = pin(torch::zeros({R, 84 * 84}, torch::kUInt8));
     planeStage_ = lstm_ ? rela_r2d2_actor_plane_stage(hr_) : rela_apex_actor_plane_stage(h_);
     if (!planeStage_) throw std::runtime_error("ActorCohort: could not allocate the plane stage");
+    if (screens) {
+      const int H = (int)screens->size(2), W = (int)screens->size(3);
+      check(lstm_ ? rela_r2d2_actor_set_screen_input(hr_, H, W) : rela_apex_actor_set_screen_input(h_, H, W),
+            "set_screen_input");
+      screenStage_ = lstm_ ? rela_r2d2_actor_screen_stage(hr_) : rela_apex_actor_screen_stage(h_);
+      screenBytes_ = (int64_t)2 * H * W * 3;
+    }
     keepObs_.resize(T_);
     // RELA_PLANE_UPLOAD=0: always upload whole frame stacks (A/B switch of the sliding-stack path)
     const char* pu = std::getenv("RELA_PLANE_UPLOAD");
@@ -1272,6 +1337,8 @@ class ActorCohort {
   void *compute_ = nullptr, *upload_ = nullptr;
   torch::Tensor actionAll_, epsAll_, legalAll_, rewardAll_, terminalAll_, restartAll_, planeHost_;
   void* planeStage_ = nullptr;  // device [R][7056]: the newest plane of every row
+  void* screenStage_ = nullptr;  // device [R][2][H][W][3]: every row's screen pair (screen mode)
+  int64_t screenBytes_ = 0;      // 2*H*W*3 in screen mode, 0 otherwise
   std::vector<torch::Tensor> keepObs_;
   std::vector<std::atomic<int64_t>> numAct_;
   bool constsValid_ = false, constsDirty_ = false, draining_ = false;
@@ -1281,6 +1348,27 @@ class ActorCohort {
   int arrived_ = 0;
   uint64_t generation_ = 0;
 };
+
+// The screen path of an actor's private shard (a VectorEnv of screen envs, rela/screen_env.h): on the first act the shard
+// gets its screen stage, then every act makes ONE copy of obs["__screens"] into it and the shard writes the frame stacks
+// of its observation slot on the device.  `restart` is this actor's page-locked copy of the flags.
+template <class Shard>
+void privateScreensToStacks(Shard* h, const TensorDict& obs, int rows, int device, void* stream, torch::Tensor& restart,
+                            int (*setInput)(Shard*, int, int), void* (*stage)(Shard*),
+                            int (*toStacks)(Shard*, const uint8_t*, void*)) {
+  const auto& scr = obs.at("__screens");
+  if (scr.dim() != 5 || scr.size(0) != rows || scr.size(1) != 2 || scr.size(4) != 3 || scr.dtype() != torch::kUInt8 ||
+      !scr.is_contiguous())
+    throw std::runtime_error("act: obs['__screens'] must be contiguous uint8 [batchsize,2,H,W,3]");
+  if (!restart.defined()) {
+    check(setInput(h, (int)scr.size(2), (int)scr.size(3)), "set_screen_input");
+    restart = torch::zeros({rows}, torch::kUInt8);
+    if (torch::cuda::is_available()) restart = restart.pin_memory();
+  }
+  check(rela_memcpy_h2d_async(stage(h), scr.data_ptr(), (int64_t)scr.nbytes(), stream, device), "rela_memcpy_h2d_async");
+  std::memcpy(restart.data_ptr<uint8_t>(), obs.at("__stack_restart").data_ptr<uint8_t>(), (size_t)rows);
+  check(toStacks(h, restart.data_ptr<uint8_t>(), stream), "screens_to_stacks");
+}
 
 // =====================================================================================
 // DQNActor (rela/dqn_actor.h:126-211)
@@ -1363,12 +1451,18 @@ class DQNActor : public Actor {
     }
     constsValid_ = true;
     auto sc = s.contiguous();
+    const uint8_t* obsHost = sc.data_ptr<uint8_t>();
+    if (obs.count("__screens")) {  // the stacks are built on the device from the screens
+      privateScreensToStacks(h_, obs, batchsize_, locker_->execDevice, stream_, screenRestart_, rela_apex_actor_set_screen_input,
+                             rela_apex_actor_screen_stage, rela_apex_actor_screens_to_stacks);
+      obsHost = nullptr;
+    }
     auto lease = locker_->getModel();
     if (lease.kind != ModelLocker::kFF) {
       locker_->releaseModel(lease.id);
       throw std::runtime_error("DQNActor needs an AtariFFNet-shaped agent in its ModelLocker");
     }
-    const int rc = rela_apex_actor_act(h_, static_cast<const rela_ffnet*>(lease.online), sc.data_ptr<uint8_t>(), epsPtr, legalPtr,
+    const int rc = rela_apex_actor_act(h_, static_cast<const rela_ffnet*>(lease.online), obsHost, epsPtr, legalPtr,
                                        action_.data_ptr<int64_t>(), nullptr, stream_);
     locker_->releaseModel(lease.id);
     check(rc, "DQNActor.act");
@@ -1401,7 +1495,7 @@ class DQNActor : public Actor {
   std::shared_ptr<FFPrioritizedReplay> replay_;
   rela_apex_actor* h_ = nullptr;
   void* stream_ = nullptr;  // this actor thread's private HIP stream
-  torch::Tensor action_, epsHost_, legalHost_, reward_, terminal_;
+  torch::Tensor action_, epsHost_, legalHost_, reward_, terminal_, screenRestart_;
   bool constsValid_ = false;
   std::shared_ptr<ActorCohort> cohort_;  // set when this actor is batched with its siblings
   int member_ = -1;
@@ -1493,12 +1587,18 @@ class R2D2Actor : public Actor {
     }
     constsValid_ = true;
     auto sc = s.contiguous();
+    const uint8_t* obsHost = sc.data_ptr<uint8_t>();
+    if (obs.count("__screens")) {  // the stacks are built on the device from the screens
+      privateScreensToStacks(h_, obs, batchsize_, locker_->execDevice, stream_, screenRestart_, rela_r2d2_actor_set_screen_input,
+                             rela_r2d2_actor_screen_stage, rela_r2d2_actor_screens_to_stacks);
+      obsHost = nullptr;
+    }
     auto lease = locker_->getModel();
     if (lease.kind != ModelLocker::kLSTM) {
       locker_->releaseModel(lease.id);
       throw std::runtime_error("R2D2Actor needs an AtariLSTMNet-shaped agent in its ModelLocker");
     }
-    const int rc = rela_r2d2_actor_act(h_, static_cast<const rela_lstmnet*>(lease.online), sc.data_ptr<uint8_t>(),
+    const int rc = rela_r2d2_actor_act(h_, static_cast<const rela_lstmnet*>(lease.online), obsHost,
                                        epsPtr, legalPtr, action_.data_ptr<int64_t>(), nullptr, stream_);
     locker_->releaseModel(lease.id);
     check(rc, "R2D2Actor.act");
@@ -1532,7 +1632,7 @@ class R2D2Actor : public Actor {
   std::shared_ptr<RNNPrioritizedReplay> replay_;
   rela_r2d2_actor* h_ = nullptr;
   void* stream_ = nullptr;
-  torch::Tensor action_, epsHost_, legalHost_, reward_, terminal_;
+  torch::Tensor action_, epsHost_, legalHost_, reward_, terminal_, screenRestart_;
   bool constsValid_ = false;
   std::shared_ptr<ActorCohort> cohort_;  // set when this actor is batched with its siblings
   int member_ = -1;

@@ -8,8 +8,10 @@
 // (seed, actions) alone.
 #include <pybind11/pybind11.h>
 
+#include <algorithm>
 #include <cstring>
 #include <torch/extension.h>
+#include <vector>
 
 #include "rela/env.h"
 // this repo's optional in-place rendering extension; absent when this file is compiled against the REFERENCE's
@@ -21,6 +23,14 @@
 #else
 #define RELA_HAS_FRAME_ROW 0
 #define RELA_FRAME_ROW_BASE
+#endif
+// ... and the raw-screen extension with the feature recipe it shares with the kernel (absent in the oracle's build)
+#if __has_include("rela/screen_env.h") && __has_include("../csrc/atari_screen.h")
+#include "../csrc/atari_screen.h"
+#include "rela/screen_env.h"
+#define RELA_HAS_SCREEN 1
+#else
+#define RELA_HAS_SCREEN 0
 #endif
 
 namespace py = pybind11;
@@ -179,6 +189,149 @@ class NullAtariEnv : public rela::Env RELA_FRAME_ROW_BASE {
   torch::Tensor eps_, legal_, frame_;
 };
 
+#if RELA_HAS_SCREEN
+// Raw-screen env: deterministic 210x160 RGB screens like ALE's (ALEInterface::getScreenRGB) -- a background of 10x10
+// blocks in an 8-colour palette drawn from the seed, six blocks recoloured per frame by the LCG, and a 12x16 sprite that
+// the actions move -- so Q-values and actions depend on the frames.  Every reset() / step() emits a (current, previous)
+// screen pair; the observation is GameState::computeFeature of it (atari/game_state.h:53-82,122-133).  This class
+// computes it on the host with the restatement of csrc/atari_screen.h, four-plane deque included (device_features =
+// False: a plain rela::Env, the reference's method); SyntheticScreenEnvDevice below hands the pair to the VectorEnv
+// instead and the actor shard computes the same stacks on the GPU (rela/screen_env.h).
+class SyntheticScreenEnv : public rela::Env {
+ public:
+  static constexpr int kH = 210, kW = 160, kScreen = kH * kW * 3, kBlock = 10;
+
+  SyntheticScreenEnv(int seed, float eps, int numAction, int episodeLen)
+      : state_((uint32_t)seed * 2246822519u + 374761393u), numAction_(numAction), episodeLen_(episodeLen),
+        own_(2 * (size_t)kScreen), pair_(own_.data()), bg_((size_t)kScreen) {
+    eps_ = torch::full({1}, eps, torch::kFloat32);
+    legal_ = torch::ones({numAction}, torch::kFloat32);
+    frame_ = torch::zeros({4, 84, 84}, torch::kUInt8);
+    for (int k = 0; k < 8; ++k)
+      for (int c = 0; c < 3; ++c) pal_[k][c] = (uint8_t)(next() >> 24);
+    for (int by = 0; by < kH / kBlock; ++by)
+      for (int bx = 0; bx < kW / kBlock; ++bx) fillBlock(bg_.data(), by, bx, (int)(next() >> 29));
+  }
+  ~SyntheticScreenEnv() override = default;
+
+  int numAction() const { return numAction_; }
+  float getEpisodeReward() const { return episodeReward_; }
+
+  rela::TensorDict reset() final {
+    steps_ = 0;
+    terminal_ = false;
+    episodeReward_ = 0.f;
+    sy_ = (int)((next() >> 24) % (kH - 12));
+    sx_ = (int)((next() >> 24) % (kW - 16));
+    render(pair_ + kScreen);  // the screen before the first one
+    render(pair_);
+    pushFeature(true);
+    return observation();
+  }
+
+  std::tuple<rela::TensorDict, float, bool> step(const rela::TensorDict& action) final {
+    const auto& at = action.at("a");
+    const int64_t a = (at.device().is_cpu() && at.scalar_type() == torch::kInt64 && at.numel() == 1)
+                          ? *at.data_ptr<int64_t>()
+                          : at.item<int64_t>();
+    if (a < 0 || a >= numAction_) throw std::out_of_range("SyntheticScreenEnv: action out of range");
+    sx_ = std::min(std::max(sx_ + 4 * ((int)(a % 3) - 1), 0), kW - 16);
+    sy_ = std::min(std::max(sy_ + 4 * ((int)((a / 3) % 3) - 1), 0), kH - 12);
+    std::memcpy(pair_ + kScreen, pair_, kScreen);  // the current screen becomes the previous one
+    render(pair_);
+    pushFeature(false);
+    const uint32_t x = next();
+    float reward = 0.f;
+    if ((a & 1) == 0) reward = (float)((int)((x >> 24) % 3) - 1);
+    episodeReward_ += reward;
+    ++steps_;
+    if (steps_ >= episodeLen_) terminal_ = true;
+    return std::make_tuple(observation(), reward, terminal_);
+  }
+
+  bool terminated() const final { return terminal_; }
+
+  // the current pair, [2][210][160][3] (tests)
+  torch::Tensor screens() const { return torch::from_blob(pair_, {2, kH, kW, 3}, torch::kUInt8).clone(); }
+
+ protected:
+  virtual void pushFeature(bool episodeStart) {  // computeFeature's deque, on the host
+    constexpr int kPlane = 84 * 84;
+    uint8_t* p = frame_.data_ptr<uint8_t>();
+    if (!episodeStart) std::memmove(p, p + kPlane, 3 * kPlane);
+    rela_atari::host_features(pair_, pair_ + kScreen, kH, kW, p + 3 * kPlane);
+    if (episodeStart)
+      for (int k = 0; k < 3; ++k) std::memcpy(p + k * kPlane, p + 3 * kPlane, kPlane);
+  }
+
+  uint32_t state_;
+  const int numAction_, episodeLen_;
+  std::vector<uint8_t> own_;
+  uint8_t* pair_;  // [2][kH][kW][3]: own_, or the VectorEnv's row once bound
+  torch::Tensor eps_, legal_, frame_;
+
+ private:
+  uint32_t next() {
+    state_ = state_ * 1664525u + 1013904223u;
+    return state_;
+  }
+  void fillBlock(uint8_t* scr, int by, int bx, int colour) {
+    for (int y = by * kBlock; y < (by + 1) * kBlock; ++y)
+      for (int x = bx * kBlock; x < (bx + 1) * kBlock; ++x)
+        for (int c = 0; c < 3; ++c) scr[(y * kW + x) * 3 + c] = pal_[colour][c];
+  }
+  void render(uint8_t* scr) {
+    std::memcpy(scr, bg_.data(), kScreen);
+    for (int k = 0; k < 6; ++k) {
+      const uint32_t r = next();
+      fillBlock(scr, (int)((r >> 8) % (kH / kBlock)), (int)((r >> 16) % (kW / kBlock)), (int)(r >> 29));
+    }
+    const uint8_t* col = pal_[(steps_ + 3) & 7];
+    for (int y = sy_; y < sy_ + 12; ++y)
+      for (int x = sx_; x < sx_ + 16; ++x)
+        for (int c = 0; c < 3; ++c) scr[(y * kW + x) * 3 + c] = (uint8_t)(255 - col[c]);
+  }
+  rela::TensorDict observation() const { return {{"s", frame_}, {"eps", eps_}, {"legal_move", legal_}}; }
+
+  std::vector<uint8_t> bg_;
+  uint8_t pal_[8][3];
+  int steps_ = 0, sy_ = 0, sx_ = 0;
+  bool terminal_ = true;
+  float episodeReward_ = 0.f;
+};
+
+// device_features = True: the same env as a rela::ScreenEnv -- obs["s"] stays a constant [4,84,84] tensor that nobody
+// reads, the actor shard builds the stacks from the screen pair in the VectorEnv's row
+class SyntheticScreenEnvDevice : public SyntheticScreenEnv, public rela::ScreenEnv {
+ public:
+  using SyntheticScreenEnv::SyntheticScreenEnv;
+  void bindScreenRow(uint8_t* row) final {
+    std::memcpy(row, pair_, 2 * (size_t)kScreen);
+    pair_ = row;
+  }
+  int screenHeight() const final { return kH; }
+  int screenWidth() const final { return kW; }
+
+ protected:
+  void pushFeature(bool) final {}
+};
+
+// synth_atari.screen_features(a, b): the host restatement of csrc/atari_screen.h -- a, b = u8 [H][W][3] (current,
+// previous screen) -> u8 [84][84]
+torch::Tensor screenFeatures(const torch::Tensor& a, const torch::Tensor& b) {
+  if (a.dim() != 3 || a.size(2) != 3 || a.scalar_type() != torch::kUInt8 || !a.device().is_cpu() || !a.sizes().equals(b.sizes()) ||
+      b.scalar_type() != torch::kUInt8 || !b.device().is_cpu())
+    throw std::invalid_argument("screen_features: a and b must be uint8 CPU tensors of one shape [H, W, 3]");
+  const int H = (int)a.size(0), W = (int)a.size(1);
+  if (H < rela_atari::kMinIn || H > rela_atari::kMaxIn || W < rela_atari::kMinIn || W > rela_atari::kMaxIn)
+    throw std::invalid_argument("screen_features: screens must be 2..512 x 2..512");
+  auto ac = a.contiguous(), bc = b.contiguous();
+  auto out = torch::empty({84, 84}, torch::kUInt8);
+  rela_atari::host_features(ac.data_ptr<uint8_t>(), bc.data_ptr<uint8_t>(), H, W, out.data_ptr<uint8_t>());
+  return out;
+}
+#endif
+
 }  // namespace
 
 PYBIND11_MODULE(synth_atari, m) {
@@ -197,4 +350,24 @@ PYBIND11_MODULE(synth_atari, m) {
       .def("reset", &NullAtariEnv::reset)
       .def("step", &NullAtariEnv::step)
       .def("terminated", &NullAtariEnv::terminated);
+#if RELA_HAS_SCREEN
+  py::class_<SyntheticScreenEnv, rela::Env, std::shared_ptr<SyntheticScreenEnv>>(m, "SyntheticScreenEnvHost")
+      .def("num_action", &SyntheticScreenEnv::numAction)
+      .def("reset", &SyntheticScreenEnv::reset)
+      .def("step", &SyntheticScreenEnv::step)
+      .def("terminated", &SyntheticScreenEnv::terminated)
+      .def("get_episode_reward", &SyntheticScreenEnv::getEpisodeReward)
+      .def("screens", &SyntheticScreenEnv::screens);
+  py::class_<SyntheticScreenEnvDevice, SyntheticScreenEnv, std::shared_ptr<SyntheticScreenEnvDevice>>(m, "SyntheticScreenEnvDevice");
+  m.def("SyntheticScreenEnv",
+        [](int seed, float eps, int numAction, int episodeLen, bool deviceFeatures) -> std::shared_ptr<SyntheticScreenEnv> {
+          if (deviceFeatures) return std::make_shared<SyntheticScreenEnvDevice>(seed, eps, numAction, episodeLen);
+          return std::make_shared<SyntheticScreenEnv>(seed, eps, numAction, episodeLen);
+        },
+        py::arg("seed"), py::arg("eps"), py::arg("num_action"), py::arg("episode_len"), py::arg("device_features") = true,
+        "raw-screen synthetic env: device_features=True -> a rela::ScreenEnv (stacks built on the GPU), False -> a plain "
+        "rela::Env that computes the same stacks on the host");
+  m.def("screen_features", &screenFeatures, py::arg("a"), py::arg("b"),
+        "GameState::computeFeature of one screen pair on the host (csrc/atari_screen.h): u8 [H,W,3] x2 -> u8 [84,84]");
+#endif
 }
