@@ -35,6 +35,7 @@
 #include "conv_img_s3.h"
 #include "conv12_s3.h"
 #include "ffnet_layout.h"
+#include "ffnet_plan.h"
 #include "gemm_lds.h"
 #include "prof.h"
 
@@ -646,13 +647,6 @@ struct ConvFastCfg {
   static constexpr int IT = (V16 + kThreads - 1) / kThreads, IT2 = (IT + 1) / 2;
   static_assert(REC / 16 <= Q, "pixel stride too small");
 };
-constexpr int kFastMinN = 1024;  // below this fc_bf16s has too few blocks and the f32 split-K fc is faster
-constexpr int kFastTrunkMinN = 128;  // from here up the split-bf16 convolutions beat the f32 ones
-// f32-accurate bf16 mode (precision 2: the f32x3 arithmetic of gemm_f32emu.h).  r5: from kEmuConvMinN rows the whole trunk
-// runs on pre-split activations ("split3 records", gemm_s3.h): conv1 -> conv2 fused per frame (conv12_s3.h), conv3 as an
-// image kernel with resident weights (conv_img_s3.h), fc as an LDS-DMA GEMM over records (gemm_s3.h); smaller batches
-// run the exact f32 MFMA kernels (same accuracy, channel-last f32).  Byte offsets inside the records are 32-bit.
-constexpr int kEmuConvMinN = 512, kEmuFcMinN = 512, kEmuMaxN = 80000;
 // conv2: 20x20x32 -> 9x9x64, stride 2: 2*Q = 2, 2*RQ = 18 = 2 (mod 16)
 using Conv2F = ConvFastCfg<32, 20, 20, 4, 4, 2, 9, 9, 1, 9, 185, 20 * 185>;
 // conv3: 9x9x64 -> 7x7x64, stride 1: Q = 2, RQ = 14 (7 positions per row), SQ = 98 = 2 (mod 16)
@@ -1223,6 +1217,8 @@ struct FcFastT {
   static constexpr int TOT = 2 * RT, D = RT;  // fragment pairs per position, pairs in flight
 };
 using FcFast = FcFastT<112>;
+static_assert(FcFast::BM == kFcBf16BlockRows && FcFast::NPOS == kFcPositions && kNumCU == kPlanCUs,
+              "fc_bf16_slices (ffnet_plan.h) counts with the kernel's own block");
 
 // SPLIT (batches of a few hundred rows, where 4 x ceil(N / BM) blocks would leave most CUs idle): blockIdx.z owns the
 // positions [z * per, z * per + per) of the contraction and writes its raw partial sums to out[z][N][512]; fc_reduce adds
@@ -1719,20 +1715,7 @@ __global__ void unsplit_records64(uint8_t* __restrict__ rec, int64_t pixels) {
   reinterpret_cast<float*>(r)[c] = v;
 }
 
-// ---- weight packing (load_state_dict time) ------------------------------------------------
-// ---- fc forward for small batches --------------------------------------------------------------
-// Below kFcSplitBelow rows gemm_mfma<GemmFc> launches fewer than 128 blocks, each walking all 98
-// K-chunks (123 us at N = 512, the same at N = 80).  There the product runs as a split-K instance of
-// gemm_lds (gemm_lds.h) over ~256 blocks; fc_reduce sums the partial tiles in a fixed order and
-// applies bias + ReLU.  The partial tiles live in the caller's workspace behind `ha`.
-constexpr int kFcSplitBelow = 2048;
-constexpr int64_t kFcPartFloats = (int64_t)8192 * 512;  // splits * N <= 8192 rows of partial sums (f32 split-K: <= 4096)
-inline int fc_splits(int N) {
-  const int rb = ceil_div(N, 128);
-  const int sp = 32 / rb;
-  return sp < 1 ? 1 : sp;
-}
-
+// ---- fc forward for small batches (kFcSplitBelow, fc_splits: ffnet_plan.h) ------------------------------------------
 using TileFcSmall = gemm::TileCfg<128, 64, 4, 2, false>;
 struct ProbFcFwd : gemm::ProbBase {
   const float *a3, *wt;  // a3 [N][3136] (k = pos*64+c), wt [3136][512]
@@ -1916,6 +1899,11 @@ __global__ void pack_f32emu(int mode, const float* __restrict__ w, uint16_t* __r
 // Every kernel-layout copy of an AtariFFNet's weights in ONE launch (a learner re-packs after every optimiser step:
 // twelve pack kernels, four device copies and the head bias were seventeen launches).  A block finds its job in a
 // table of first-block indices; the job bodies are the *_at functions of the separate kernels.
+// the segments of the launch, in block order
+enum PackSeg {
+  kSegB1, kSegUnused1, kSegB2, kSegB3, kSegBf, kSegBfT, kSegBh, kSegBhp, kSegB2f, kSegB3f, kSegBff, kSegBiases,
+  kSegHeadBias, kSegW2p, kSegW3p, kSegWfcp, kSegW1d, kSegB2e, kSegB3e, kSegBfe, kPackSegs
+};
 struct PackAllArgs {
   const float* p[12];  // rela_ffnet_params order
   uint16_t *B1, *B2f, *B3f, *Bff;
@@ -1925,7 +1913,7 @@ struct PackAllArgs {
   uint8_t* W1d;             // conv1 for the int8 matrix cores (pack_conv1_i8_block)
   float *s1q, *b1q;
   uint16_t *B2e, *B3e, *Bfe;  // bf16 triples of the f32-accurate mode (f32emu::pack_f32emu_at)
-  int first[21];  // first block of job j; first[20] = total
+  int first[kPackSegs + 1];  // first block of segment j; first[kPackSegs] = total
 };
 __global__ void pack_ffnet_all(PackAllArgs a) {
   const int b = blockIdx.x;
@@ -1933,18 +1921,18 @@ __global__ void pack_ffnet_all(PackAllArgs a) {
   while (b >= a.first[j + 1]) ++j;
   const int64_t idx = (int64_t)(b - a.first[j]) * 256 + threadIdx.x;
   switch (j) {
-    case 0: pack_conv1_bf16x3_at((int)idx, a.p[0], a.B1, 0); break;
-    case 1: break;  // (was: plane-major conv1 fragments of the half-frame bf16 kernels, removed in r4; zero blocks)
-    case 2: pack_frags_at(idx, kPackConv2, a.p[2], nullptr, a.A, a.B2, 4, 128); break;
-    case 3: pack_frags_at(idx, kPackConv3, a.p[4], nullptr, a.A, a.B3, 4, 144); break;
-    case 4: pack_frags_at(idx, kPackFc, a.p[6], nullptr, a.A, a.Bf, 32, 784); break;
-    case 5: pack_fc_t_at((int)idx, a.p[6], a.BfT); break;
-    case 6: pack_frags_at(idx, kPackHeads, a.p[10], a.p[8], a.A, a.Bh, 2, 128); break;
-    case 7: pack_heads_perm_at((int)idx, a.p[10], a.p[8], a.A, a.Bhp); break;
-    case 8: pack_frags_bf16s_at(idx, 1, a.p[2], a.B2f, Conv2F::CT, Conv2F::KS); break;
-    case 9: pack_frags_bf16s_at(idx, 2, a.p[4], a.B3f, Conv3F::CT, Conv3F::KS); break;
-    case 10: pack_frags_bf16s_at(idx, 3, a.p[6], a.Bff, 32, FcFast::KS); break;
-    case 11: {  // biases: conv1 32 | conv2 64 | conv3 64 | fc 512
+    case kSegB1: pack_conv1_bf16x3_at((int)idx, a.p[0], a.B1, 0); break;
+    case kSegUnused1: break;  // (was: plane-major conv1 fragments of the half-frame bf16 kernels, removed in r4; zero blocks)
+    case kSegB2: pack_frags_at(idx, kPackConv2, a.p[2], nullptr, a.A, a.B2, 4, 128); break;
+    case kSegB3: pack_frags_at(idx, kPackConv3, a.p[4], nullptr, a.A, a.B3, 4, 144); break;
+    case kSegBf: pack_frags_at(idx, kPackFc, a.p[6], nullptr, a.A, a.Bf, 32, 784); break;
+    case kSegBfT: pack_fc_t_at((int)idx, a.p[6], a.BfT); break;
+    case kSegBh: pack_frags_at(idx, kPackHeads, a.p[10], a.p[8], a.A, a.Bh, 2, 128); break;
+    case kSegBhp: pack_heads_perm_at((int)idx, a.p[10], a.p[8], a.A, a.Bhp); break;
+    case kSegB2f: pack_frags_bf16s_at(idx, 1, a.p[2], a.B2f, Conv2F::CT, Conv2F::KS); break;
+    case kSegB3f: pack_frags_bf16s_at(idx, 2, a.p[4], a.B3f, Conv3F::CT, Conv3F::KS); break;
+    case kSegBff: pack_frags_bf16s_at(idx, 3, a.p[6], a.Bff, 32, FcFast::KS); break;
+    case kSegBiases: {  // biases: conv1 32 | conv2 64 | conv3 64 | fc 512
       const int i = (int)idx;
       if (i < 32) a.b1[i] = a.p[1][i];
       else if (i < 96) a.b2[i - 32] = a.p[3][i - 32];
@@ -1952,18 +1940,18 @@ __global__ void pack_ffnet_all(PackAllArgs a) {
       else if (i < 672) a.bf[i - 160] = a.p[7][i - 160];
       break;
     }
-    case 12: {  // head bias
+    case kSegHeadBias: {  // head bias
       const int i = (int)idx;
       if (i < 32) a.bh[i] = i < a.A ? a.p[11][i] : (i == 31 ? a.p[9][0] : 0.f);
       break;
     }
-    case 13: if (idx < 64 * 512) permute_weight_at(kPermConv2, (int)idx, a.p[2], a.w2p); break;
-    case 14: if (idx < 64 * 576) permute_weight_at(kPermConv3, (int)idx, a.p[4], a.w3p); break;
-    case 15: if (idx < 512 * 3136) permute_weight_at(kPermFc, (int)idx, a.p[6], a.wfcp); break;
-    case 16: pack_conv1_i8_block(b - a.first[16], a.p[0], a.p[1], a.W1d, a.s1q, a.b1q); break;  // (block-uniform: it synchronises)
-    case 17: f32emu::pack_f32emu_at(idx, 1, a.p[2], a.B2e, f32emu::ProbConv2::NCG, f32emu::ProbConv2::KS); break;
-    case 18: f32emu::pack_f32emu_at(idx, 2, a.p[4], a.B3e, f32emu::ProbConv3::NCG, f32emu::ProbConv3::KS); break;
-    default: f32emu::pack_f32emu_at(idx, 3, a.p[6], a.Bfe, f32emu::ProbFc::NCG, f32emu::ProbFc::KS); break;
+    case kSegW2p: if (idx < 64 * 512) permute_weight_at(kPermConv2, (int)idx, a.p[2], a.w2p); break;
+    case kSegW3p: if (idx < 64 * 576) permute_weight_at(kPermConv3, (int)idx, a.p[4], a.w3p); break;
+    case kSegWfcp: if (idx < 512 * 3136) permute_weight_at(kPermFc, (int)idx, a.p[6], a.wfcp); break;
+    case kSegW1d: pack_conv1_i8_block(b - a.first[kSegW1d], a.p[0], a.p[1], a.W1d, a.s1q, a.b1q); break;  // (block-uniform: it synchronises)
+    case kSegB2e: f32emu::pack_f32emu_at(idx, 1, a.p[2], a.B2e, f32emu::ProbConv2::NCG, f32emu::ProbConv2::KS); break;
+    case kSegB3e: f32emu::pack_f32emu_at(idx, 2, a.p[4], a.B3e, f32emu::ProbConv3::NCG, f32emu::ProbConv3::KS); break;
+    default: f32emu::pack_f32emu_at(idx, 3, a.p[6], a.Bfe, f32emu::ProbFc::NCG, f32emu::ProbFc::KS); break;  // kSegBfe
   }
 }
 
@@ -1976,6 +1964,233 @@ namespace {
 const char* const kProfActor[6] = {"conv1_bf16x3", "conv2_mfma", "conv3_mfma", "fc_mfma", "heads_mfma", "dueling"};
 const char* const kProfLearner[6] = {"learner_fwd_conv1", "learner_fwd_conv2", "learner_fwd_conv3",
                                      "learner_fwd_fc",    "learner_fwd_heads", "learner_fwd_dueling"};
+
+// ---- launch helpers shared by the AtariFFNet, the AtariLSTMNet and the learners' entry points -------------------------
+
+// gemm_mfma with the block height prefer_bm112 picks
+template <class G, class G112>
+void launch_gemm_bm(const float* A, const float* A2, const float* Bfrag, const float* bias, float* out, const float* c_in,
+                    float* c_out, int N, hipStream_t s) {
+  if (prefer_bm112(N, G::CT / G::CTB, G::BM))
+    hipLaunchKernelGGL(gemm_mfma<G112>, dim3(G112::CT / G112::CTB, ceil_div(N, G112::BM)), dim3(kThreads), 0, s, A, A2,
+                       Bfrag, bias, out, c_in, c_out, N);
+  else
+    hipLaunchKernelGGL(gemm_mfma<G>, dim3(G::CT / G::CTB, ceil_div(N, G::BM)), dim3(kThreads), 0, s, A, A2, Bfrag, bias,
+                       out, c_in, c_out, N);
+}
+
+// the split-K fcs' partial tiles: behind ha, 256-byte aligned within the workspace (float4 loads)
+inline float* fc_part_ptr(const void* ws, float* ha, int N) {
+  float* part = ha + kHA * N;
+  return part + ((64 - ((part - static_cast<const float*>(ws)) & 63)) & 63);
+}
+
+// h = relu(bias + the slices of part, added in slice order)
+void launch_fc_reduce(const float* part, int slices, int N, const float* bias, float* h, hipStream_t s) {
+  note_launch("fc_reduce");
+  hipLaunchKernelGGL(fc_reduce, dim3(ceil_div(N * 128, 256)), dim3(256), 0, s, part, slices, N, bias, h);
+}
+
+// fc on split-bf16 MFMA straight from a3's records, the contraction split over slices of positions so that ~256 blocks
+// run (fc_bf16_slices, ffnet_plan.h); a3 STAYS in records
+void launch_fc_bf16_splitk(const FFNetDev& d, const uint8_t* a3_records, float* part, float* h, int N, const char* label,
+                           hipStream_t s) {
+  int per = 0;
+  const int slices = fc_bf16_slices(N, &per);
+  {
+    ProfScope prof(label, s);
+    note_launch("fc_bf16s (split-K)");
+    hipLaunchKernelGGL((fc_bf16s<FcFast, true>), fc_grid_xcd(ceil_div(N, FcFast::BM), slices), dim3(kThreads),
+                       FcFast::LDS_BYTES, s, a3_records, (const uint4*)d.Bff, (const float*)d.bf, part, N, per);
+  }
+  launch_fc_reduce(part, slices, N, d.bf, h, s);
+}
+
+// conv1 -> conv2 of the f32x3 mode, fused per frame: a2 as split3 records; keep_f32: a1 as channel-last f32 too
+void launch_conv12_s3(bool keep_f32, const FFNetDev& d, const uint8_t* s_dev, uint8_t* rec2, float* a1, int N, hipStream_t s) {
+  note_launch("conv12_s3");
+  const auto kernel = keep_f32 ? s3::conv12_s3<true> : s3::conv12_s3<false>;
+  hipLaunchKernelGGL(kernel, dim3(persistent_blocks(N)), dim3(s3::Conv12S::kT), s3::Conv12S::LDS_TOTAL, s, s_dev,
+                     (const uint4*)d.W1d, (const float*)d.s1q, (const float*)d.b1q, (const uint4*)d.B2e, (const float*)d.b2,
+                     rec2, keep_f32 ? a1 : (float*)nullptr, N);
+}
+
+// a2 / a3 of an f32x3 trunk that keeps f32 (TrunkOpts::keep_f32): split3 records -> channel-last f32
+void unsplit_s3_a23(const uint8_t* rec2, const uint8_t* rec3, float* a2, float* a3, int N, hipStream_t s) {
+  note_launch("unsplit_s3");
+  const int64_t p2 = (int64_t)N * 81, p3 = (int64_t)N * 49;
+  hipLaunchKernelGGL(s3::unsplit_s3<64>, dim3((unsigned)ceil_div(p2 * 16, 256)), dim3(256), 0, s, rec2, a2, p2);
+  hipLaunchKernelGGL(s3::unsplit_s3<64>, dim3((unsigned)ceil_div(p3 * 16, 256)), dim3(256), 0, s, rec3, a3, p3);
+}
+
+// ---- the conv trunk: frames u8[N][4][84][84] -> a1 / a2 / a3, in one of three arithmetics (TrunkKind, ffnet_plan.h) ----
+struct TrunkLabels {  // per-kernel timing labels (prof.h); conv12: the launch that runs conv1 -> conv2 fused
+  const char *conv1, *conv2, *conv3, *conv12;
+};
+struct TrunkOpts {
+  bool keep_f32 = false;          // kTrunkS3: a1 is ALSO written as channel-last f32 (a2 / a3: unsplit_s3_a23, the caller's)
+  bool leave_a3_records = false;  // kTrunkBf16: a3 stays in split records instead of going back to f32 in place
+};
+// kTrunkF32:  a1 / a2 / a3 channel-last f32
+// kTrunkBf16: a1 is NOT produced; a2 / a3 hold split-bf16 records in the f32 tensors' places (same bytes)
+// kTrunkS3:   a2 / a3 as split3 records at rec2 [N][kRec2Bytes] / rec3 [N][kRec3Bytes]; a1 / a2 / a3 themselves are
+//             untouched unless keep_f32
+void launch_trunk(const FFNetDev& d, TrunkKind kind, int N, const uint8_t* s_dev, float* a1, float* a2, float* a3,
+                  uint8_t* rec2, uint8_t* rec3, const TrunkOpts& o, const TrunkLabels& l, hipStream_t s) {
+  switch (kind) {
+    case kTrunkS3: {
+      {
+        ProfScope prof(l.conv12, s);
+        launch_conv12_s3(o.keep_f32, d, s_dev, rec2, a1, N, s);
+      }
+      ProfScope prof(l.conv3, s);
+      note_launch("conv3_img_s3");
+      s3::launch_conv3_img(rec2, d.B3e, d.b3, rec3, N, s, persistent_blocks(N));
+      break;
+    }
+    case kTrunkBf16: {
+      uint8_t *r2 = reinterpret_cast<uint8_t*>(a2), *r3 = reinterpret_cast<uint8_t*>(a3);
+      {  // conv1 (int8 matrix cores) -> conv2 (split-bf16), fused per frame through LDS
+        ProfScope prof(l.conv12, s);
+        note_launch("conv12_i8");
+        hipLaunchKernelGGL(conv12_i8, dim3(persistent_blocks(N)), dim3(kThreads), Conv12I::LDS_TOTAL, s, s_dev,
+                           (const uint4*)d.W1d, (const float*)d.s1q, (const float*)d.b1q, (const uint4*)d.B2f,
+                           (const float*)d.b2, r2, N);
+      }
+      ProfScope prof(l.conv3, s);
+      note_launch("conv_bf16s<Conv3F>");
+      hipLaunchKernelGGL(conv_bf16s<Conv3F>, dim3(persistent_blocks(ceil_div(N, Conv3F::S))), dim3(kThreads),
+                         Conv3F::LDS_TOTAL, s, (const uint8_t*)r2, (const uint4*)d.B3f, (const float*)d.b3, r3, N);
+      if (!o.leave_a3_records) {
+        note_launch("unsplit_records64");
+        hipLaunchKernelGGL(unsplit_records64, dim3(ceil_div((int64_t)N * 49, 4)), dim3(256), 0, s, r3, (int64_t)N * 49);
+      }
+      break;
+    }
+    case kTrunkF32: {
+      {
+        ProfScope prof(l.conv1, s);
+        note_launch("conv1_bf16x3");
+        hipLaunchKernelGGL(conv1_bf16x3, dim3(ceil_div(N, Conv1B::S)), dim3(kThreads), Conv1B::LDS_BYTES, s, s_dev, d.B1,
+                           d.b1, a1, N);
+      }
+      {
+        ProfScope prof(l.conv2, s);
+        launch_conv<Conv2>(a1, d.B2, d.b2, a2, N, s);
+      }
+      ProfScope prof(l.conv3, s);
+      launch_conv<Conv3>(a2, d.B3, d.b3, a3, N, s);
+      break;
+    }
+  }
+}
+
+// one pass of the job form of the split-bf16 trunk (conv12_i8_jobs / conv3_bf16s_jobs) with the weights of `d`
+TrunkJob trunk_job(const FFNetDev& d, const uint8_t* in0, const uint8_t* in1, int n_in0, uint8_t* a1_out, int a1_lo, int n_a1,
+                   uint8_t* a2, uint8_t* a3, int N, int block0, int nblocks) {
+  TrunkJob j{};
+  j.in0 = in0, j.in1 = in1, j.n_in0 = n_in0;
+  j.B2 = (const uint4*)d.B2f, j.B3 = (const uint4*)d.B3f;
+  j.b2 = d.b2, j.b3 = d.b3;
+  j.W1d = d.W1d, j.s1q = d.s1q, j.b1q = d.b1q;
+  j.a1_out = a1_out, j.a1_lo = a1_lo, j.n_a1 = n_a1;
+  j.a2 = a2, j.a3 = a3;
+  j.N = N, j.block0 = block0, j.nblocks = nblocks;
+  return j;
+}
+
+// ---- create / load helpers ---------------------------------------------------------------------------------------------
+
+// the weight layouts every net with a conv trunk and dueling heads holds (an AtariFFNet adds its fc's and Bhp)
+int alloc_trunk(FFNetDev& d) {
+  RELA_HIP(hipMalloc(&d.B1, sizeof(uint4) * Conv1B::FRAG_UINT4));
+  RELA_HIP(hipMalloc(&d.b1, sizeof(float) * 32));
+  RELA_HIP(hipMalloc(&d.B2, sizeof(float) * 4 * 128 * 64));
+  RELA_HIP(hipMalloc(&d.b2, sizeof(float) * 64));
+  RELA_HIP(hipMalloc(&d.B3, sizeof(float) * 4 * 144 * 64));
+  RELA_HIP(hipMalloc(&d.b3, sizeof(float) * 64));
+  RELA_HIP(hipMalloc(&d.Bh, sizeof(float) * 2 * 128 * 64));
+  RELA_HIP(hipMalloc(&d.bh, sizeof(float) * 32));
+  RELA_HIP(hipMalloc(&d.W1d, sizeof(uint4) * Conv12I::W1_UINT4));
+  RELA_HIP(hipMalloc(&d.s1q, sizeof(float) * 32));
+  RELA_HIP(hipMalloc(&d.b1q, sizeof(float) * 32));
+  RELA_HIP(hipMalloc(&d.B2f, sizeof(uint4) * Conv2F::CT * Conv2F::KS * 2 * 64));
+  RELA_HIP(hipMalloc(&d.B3f, sizeof(uint4) * Conv3F::CT * Conv3F::KS * 2 * 64));
+  RELA_HIP(hipMalloc(&d.B2e, sizeof(uint4) * f32emu::packed_u4<f32emu::ProbConv2>()));
+  RELA_HIP(hipMalloc(&d.B3e, sizeof(uint4) * f32emu::packed_u4<f32emu::ProbConv3>()));
+  return RELA_OK;
+}
+
+struct LdsOptIn {
+  const void* kernel;
+  int bytes;
+};
+int opt_in(const LdsOptIn* ks, int n) {
+  for (int i = 0; i < n; ++i) RELA_HIP(hipFuncSetAttribute(ks[i].kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ks[i].bytes));
+  return RELA_OK;
+}
+// the trunk kernels' opt-in to > 64 KB of dynamic LDS, once per net (the stamps variants opt in where they are launched)
+int opt_in_dynamic_lds() {
+  const LdsOptIn ks[] = {
+      {reinterpret_cast<const void*>(&conv12_i8), Conv12I::LDS_TOTAL},
+      {reinterpret_cast<const void*>(&conv12_i8_jobs), Conv12I::LDS_TOTAL},
+      {reinterpret_cast<const void*>(&s3::conv12_s3<false>), s3::Conv12S::LDS_TOTAL},
+      {reinterpret_cast<const void*>(&s3::conv12_s3<true>), s3::Conv12S::LDS_TOTAL},
+      {reinterpret_cast<const void*>(&conv1_bf16x3), Conv1B::LDS_BYTES},
+      {reinterpret_cast<const void*>(&conv_bf16s<Conv3F>), Conv3F::LDS_TOTAL},
+      {reinterpret_cast<const void*>(&conv_mfma<Conv2>), Conv2::LDS_BYTES},
+      {reinterpret_cast<const void*>(&conv_mfma<Conv3>), Conv3::LDS_BYTES},
+      {reinterpret_cast<const void*>(&conv_mfma_bstat<Conv2>), 2 * Conv2::LDS_BYTES},
+      {reinterpret_cast<const void*>(&conv_mfma_bstat<Conv3>), 2 * Conv3::LDS_BYTES},
+  };
+  return opt_in(ks, (int)(sizeof(ks) / sizeof(ks[0])));
+}
+
+// The n parameter tensors of a load as device pointers dv[]: the caller's own (on_device), or copies in ONE staging
+// buffer *tmp, which the caller hands to free_staging once its pack kernels are on the stream.
+int stage_params(const float* const* src, const size_t* cnt, int n, int on_device, const char* what, float** tmp,
+                 const float** dv, hipStream_t s) {
+  for (int i = 0; i < n; ++i) RELA_CHECK(src[i], RELA_EINVAL, "%s: parameter %d is NULL", what, i);
+  if (on_device) {
+    for (int i = 0; i < n; ++i) dv[i] = src[i];
+    return RELA_OK;
+  }
+  size_t total = 0;
+  for (int i = 0; i < n; ++i) total += cnt[i];
+  RELA_HIP(hipMalloc(tmp, sizeof(float) * total));
+  size_t off = 0;
+  for (int i = 0; i < n; ++i) {
+    RELA_HIP(hipMemcpyAsync(*tmp + off, src[i], sizeof(float) * cnt[i], hipMemcpyHostToDevice, s));
+    dv[i] = *tmp + off;
+    off += cnt[i];
+  }
+  return RELA_OK;
+}
+int free_staging(float* tmp, hipStream_t s) {
+  if (tmp) {
+    RELA_HIP(hipStreamSynchronize(s));
+    (void)hipFree(tmp);
+  }
+  return RELA_OK;
+}
+
+// A diagnostic kernel with shader-clock stamps: launch(out, stamps) writes its ordinary output to `out_bytes` bytes of
+// scratch and its stamps to [2][kStampFrames][kStampPoints] u64, which come back in out_host.
+template <class Launch>
+int run_stamped(size_t out_bytes, Launch launch, unsigned long long* out_host, hipStream_t s) {
+  uint8_t* out = nullptr;
+  unsigned long long* st = nullptr;
+  const size_t nst = (size_t)2 * kStampFrames * kStampPoints;
+  RELA_HIP(hipMalloc(&out, out_bytes));
+  RELA_HIP(hipMalloc(&st, nst * 8));
+  RELA_HIP(hipMemsetAsync(st, 0, nst * 8, s));
+  launch(out, st);
+  RELA_HIP(hipStreamSynchronize(s));
+  RELA_HIP(hipMemcpy(out_host, st, nst * 8, hipMemcpyDeviceToHost));
+  (void)hipFree(out);
+  (void)hipFree(st);
+  return RELA_OK;
+}
 }  // namespace
 
 struct rela_ffnet {
@@ -1995,7 +2210,6 @@ struct rela_ffnet {
   const float* bft_src = nullptr;
 };
 
-
 extern "C" int rela_ffnet_create(rela_ffnet** out, int num_action, int device) {
   RELA_CHECK(out && num_action >= 1 && num_action <= 31, RELA_EINVAL,
              "rela_ffnet_create: num_action must be in 1..31 (got %d)", num_action);
@@ -2009,52 +2223,17 @@ extern "C" int rela_ffnet_create(rela_ffnet** out, int num_action, int device) {
   n->device = device;
   n->num_action = num_action;
   FFNetDev& d = n->d;
-  RELA_HIP(hipMalloc(&d.B1, sizeof(uint4) * Conv1B::FRAG_UINT4));
-  RELA_HIP(hipMalloc(&d.b1, sizeof(float) * 32));
-  RELA_HIP(hipMalloc(&d.B2, sizeof(float) * 4 * 128 * 64));
-  RELA_HIP(hipMalloc(&d.b2, sizeof(float) * 64));
-  RELA_HIP(hipMalloc(&d.B3, sizeof(float) * 4 * 144 * 64));
-  RELA_HIP(hipMalloc(&d.b3, sizeof(float) * 64));
+  if (int rc = alloc_trunk(d)) return rc;
   RELA_HIP(hipMalloc(&d.Bf, sizeof(float) * 32 * 784 * 64));
   RELA_HIP(hipMalloc(&d.BfT, sizeof(float) * 3136 * 512));
   RELA_HIP(hipMalloc(&d.bf, sizeof(float) * 512));
-  RELA_HIP(hipMalloc(&d.Bh, sizeof(float) * 2 * 128 * 64));
-  RELA_HIP(hipMalloc(&d.bh, sizeof(float) * 32));
-  RELA_HIP(hipMalloc(&d.W1d, sizeof(uint4) * Conv12I::W1_UINT4));
-  RELA_HIP(hipMalloc(&d.s1q, sizeof(float) * 32));
-  RELA_HIP(hipMalloc(&d.b1q, sizeof(float) * 32));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv12_i8), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               Conv12I::LDS_TOTAL));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv12_i8_jobs), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               Conv12I::LDS_TOTAL));
   RELA_HIP(hipMalloc(&d.Bhp, sizeof(float) * 2 * 4 * 32 * 64));
-  RELA_HIP(hipMalloc(&d.B2f, sizeof(uint4) * Conv2F::CT * Conv2F::KS * 2 * 64));
-  RELA_HIP(hipMalloc(&d.B3f, sizeof(uint4) * Conv3F::CT * Conv3F::KS * 2 * 64));
   RELA_HIP(hipMalloc(&d.Bff, sizeof(uint4) * 32 * FcFast::KS * 2 * 64));
-  RELA_HIP(hipMalloc(&d.B2e, sizeof(uint4) * f32emu::packed_u4<f32emu::ProbConv2>()));
-  RELA_HIP(hipMalloc(&d.B3e, sizeof(uint4) * f32emu::packed_u4<f32emu::ProbConv3>()));
   RELA_HIP(hipMalloc(&d.Bfe, sizeof(uint4) * f32emu::packed_u4<f32emu::ProbFc>()));
-  // opt in to > 64 KB of dynamic LDS once per process/device
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&s3::conv12_s3<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               s3::Conv12S::LDS_TOTAL));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&s3::conv12_s3<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               s3::Conv12S::LDS_TOTAL));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1_bf16x3),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, Conv1B::LDS_BYTES));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16s<Conv3F>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, Conv3F::LDS_TOTAL));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fc_bf16s<FcFast, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, FcFast::LDS_BYTES));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&fc_bf16s<FcFast>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, FcFast::LDS_BYTES));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma<Conv2>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, Conv2::LDS_BYTES));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma<Conv3>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, Conv3::LDS_BYTES));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_bstat<Conv2>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * Conv2::LDS_BYTES));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_bstat<Conv3>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * Conv3::LDS_BYTES));
+  if (int rc = opt_in_dynamic_lds()) return rc;
+  const LdsOptIn fc[] = {{reinterpret_cast<const void*>(&fc_bf16s<FcFast, true>), FcFast::LDS_BYTES},
+                         {reinterpret_cast<const void*>(&fc_bf16s<FcFast>), FcFast::LDS_BYTES}};
+  if (int rc = opt_in(fc, 2)) return rc;
   *out = n;
   return RELA_OK;
 }
@@ -2077,23 +2256,15 @@ extern "C" int rela_ffnet_debug_conv12_stamps(const rela_ffnet* n, int N, const 
   RELA_CHECK(n && n->loaded && N >= 1 && s_dev && out_host, RELA_EINVAL, "rela_ffnet_debug_conv12_stamps: bad arguments");
   DeviceGuard g(n->device);
   hipStream_t s = (hipStream_t)stream_;
-  uint8_t* a2 = nullptr;
-  unsigned long long* st = nullptr;
-  const size_t nst = (size_t)2 * kStampFrames * kStampPoints;
-  RELA_HIP(hipMalloc(&a2, (size_t)N * 81 * 256));
-  RELA_HIP(hipMalloc(&st, nst * 8));
-  RELA_HIP(hipMemsetAsync(st, 0, nst * 8, s));
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv12_i8_stamps),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, Conv12I::LDS_TOTAL);
+  RELA_HIP(attr);
   const FFNetDev& d = n->d;
-  static const hipError_t attr8 = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv12_i8_stamps),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, Conv12I::LDS_TOTAL);
-  RELA_HIP(attr8);
-  hipLaunchKernelGGL(conv12_i8_stamps, dim3(std::min(kNumCU, N)), dim3(kThreads), Conv12I::LDS_TOTAL, s, s_dev,
-                     (const uint4*)d.W1d, (const float*)d.s1q, (const float*)d.b1q, (const uint4*)d.B2f, (const float*)d.b2, a2, N, st);
-  RELA_HIP(hipStreamSynchronize(s));
-  RELA_HIP(hipMemcpy(out_host, st, nst * 8, hipMemcpyDeviceToHost));
-  (void)hipFree(a2);
-  (void)hipFree(st);
-  return RELA_OK;
+  return run_stamped((size_t)N * 81 * 256, [&](uint8_t* a2, unsigned long long* st) {
+    hipLaunchKernelGGL(conv12_i8_stamps, dim3(std::min(kNumCU, N)), dim3(kThreads), Conv12I::LDS_TOTAL, s, s_dev,
+                       (const uint4*)d.W1d, (const float*)d.s1q, (const float*)d.b1q, (const uint4*)d.B2f, (const float*)d.b2,
+                       a2, N, st);
+  }, out_host, s);
 }
 
 // Diagnostic: conv3 of the split-bf16 mode with shader-clock stamps (block 0, waves 0 and 7, its first 8 groups of two
@@ -2107,20 +2278,11 @@ extern "C" int rela_ffnet_debug_conv3_stamps(const rela_ffnet* n, int N, const u
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_bf16s_stamps),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, Conv3F::LDS_TOTAL);
   RELA_HIP(attr);
-  uint8_t* a3 = nullptr;
-  unsigned long long* st = nullptr;
-  const size_t nst = (size_t)2 * kStampFrames * kStampPoints;
-  RELA_HIP(hipMalloc(&a3, (size_t)N * 49 * 256));
-  RELA_HIP(hipMalloc(&st, nst * 8));
-  RELA_HIP(hipMemsetAsync(st, 0, nst * 8, s));
   const FFNetDev& d = n->d;
-  hipLaunchKernelGGL(conv3_bf16s_stamps, dim3(std::min(kNumCU, ceil_div(N, Conv3F::S))), dim3(kThreads), Conv3F::LDS_TOTAL, s,
-                     a2_records, (const uint4*)d.B3f, (const float*)d.b3, a3, N, st);
-  RELA_HIP(hipStreamSynchronize(s));
-  RELA_HIP(hipMemcpy(out_host, st, nst * 8, hipMemcpyDeviceToHost));
-  (void)hipFree(a3);
-  (void)hipFree(st);
-  return RELA_OK;
+  return run_stamped((size_t)N * 49 * 256, [&](uint8_t* a3, unsigned long long* st) {
+    hipLaunchKernelGGL(conv3_bf16s_stamps, dim3(std::min(kNumCU, ceil_div(N, Conv3F::S))), dim3(kThreads), Conv3F::LDS_TOTAL, s,
+                       a2_records, (const uint4*)d.B3f, (const float*)d.b3, a3, N, st);
+  }, out_host, s);
 }
 
 // Diagnostic: fc_bf16s with shader-clock stamps (block 0, waves 0 and 7, positions 8..15): out_host [2][8][12] u64, points
@@ -2134,20 +2296,12 @@ extern "C" int rela_ffnet_debug_fc_stamps(const rela_ffnet* n, int N, const uint
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&fc_bf16s<FcFast, false, true>),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, FcFast::LDS_BYTES);
   RELA_HIP(attr);
-  float* h = nullptr;
-  unsigned long long* st = nullptr;
-  const size_t nst = (size_t)2 * kStampFrames * kStampPoints;
-  RELA_HIP(hipMalloc(&h, (size_t)N * 512 * 4));
-  RELA_HIP(hipMalloc(&st, nst * 8));
-  RELA_HIP(hipMemsetAsync(st, 0, nst * 8, s));
   const FFNetDev& d = n->d;
-  hipLaunchKernelGGL((fc_bf16s<FcFast, false, true>), fc_grid_xcd(ceil_div(N, FcFast::BM), 1), dim3(kThreads),
-                     FcFast::LDS_BYTES, s, a3_records, (const uint4*)d.Bff, (const float*)d.bf, h, N, 0, st);
-  RELA_HIP(hipStreamSynchronize(s));
-  RELA_HIP(hipMemcpy(out_host, st, nst * 8, hipMemcpyDeviceToHost));
-  (void)hipFree(h);
-  (void)hipFree(st);
-  return RELA_OK;
+  return run_stamped((size_t)N * 512 * 4, [&](uint8_t* h, unsigned long long* st) {
+    hipLaunchKernelGGL((fc_bf16s<FcFast, false, true>), fc_grid_xcd(ceil_div(N, FcFast::BM), 1), dim3(kThreads),
+                       FcFast::LDS_BYTES, s, a3_records, (const uint4*)d.Bff, (const float*)d.bf, reinterpret_cast<float*>(h),
+                       N, 0, st);
+  }, out_host, s);
 }
 
 // Diagnostic / test hook: conv1 -> conv2 of the split-bf16 mode for n frames through the job form of the kernel, which
@@ -2162,16 +2316,9 @@ extern "C" int rela_ffnet_debug_conv12_records(const rela_ffnet* n, int N, const
   const FFNetDev& d = n->d;
   TrunkJobs jobs{};
   jobs.n = 1;
-  TrunkJob& j0 = jobs.j[0];
-  j0.in0 = s_dev, j0.in1 = s_dev, j0.n_in0 = N;
-  j0.B2 = (const uint4*)d.B2f, j0.B3 = (const uint4*)d.B3f;
-  j0.b2 = d.b2, j0.b3 = d.b3;
-  j0.W1d = d.W1d, j0.s1q = d.s1q, j0.b1q = d.b1q;
-  j0.a1_out = a1_records, j0.a1_lo = 0, j0.n_a1 = N;
-  j0.a2 = a2_records, j0.a3 = nullptr;
-  j0.N = N, j0.block0 = 0, j0.nblocks = std::min(kNumCU, N);
+  jobs.j[0] = trunk_job(d, s_dev, s_dev, N, a1_records, 0, N, a2_records, nullptr, N, 0, std::min(kNumCU, N));
   note_launch("conv12_i8_jobs");
-  hipLaunchKernelGGL(conv12_i8_jobs, dim3(j0.nblocks), dim3(kThreads), Conv12I::LDS_TOTAL, s, jobs);
+  hipLaunchKernelGGL(conv12_i8_jobs, dim3(jobs.j[0].nblocks), dim3(kThreads), Conv12I::LDS_TOTAL, s, jobs);
   RELA_HIP(hipStreamSynchronize(s));
   if (scale_host) RELA_HIP(hipMemcpy(scale_host, d.s1q, 32 * sizeof(float), hipMemcpyDeviceToHost));
   if (bias_host) RELA_HIP(hipMemcpy(bias_host, d.b1q, 32 * sizeof(float), hipMemcpyDeviceToHost));
@@ -2232,68 +2379,52 @@ int rela_amd::ffnet_load_impl(rela_ffnet* n, const rela_ffnet_params* p, int on_
                           p->fc_w,    p->fc_b,    p->v_w,     p->v_b,     p->a_w,     p->a_b};
   const float* dv[12];
   float* tmp = nullptr;
-  if (on_device) {
-    for (int i = 0; i < 12; ++i) {
-      RELA_CHECK(src[i], RELA_EINVAL, "rela_ffnet_load: parameter %d is NULL", i);
-      dv[i] = src[i];
-    }
-  } else {
-    size_t total = 0;
-    for (int i = 0; i < 12; ++i) total += cnt[i];
-    RELA_HIP(hipMalloc(&tmp, sizeof(float) * total));
-    size_t off = 0;
-    for (int i = 0; i < 12; ++i) {
-      RELA_CHECK(src[i], RELA_EINVAL, "rela_ffnet_load: parameter %d is NULL", i);
-      RELA_HIP(hipMemcpyAsync(tmp + off, src[i], sizeof(float) * cnt[i], hipMemcpyHostToDevice, s));
-      dv[i] = tmp + off;
-      off += cnt[i];
-    }
+  if (int rc = stage_params(src, cnt, 12, on_device, "rela_ffnet_load", &tmp, dv, s)) return rc;
+  PackAllArgs a{};
+  for (int i = 0; i < 12; ++i) a.p[i] = dv[i];
+  a.B1 = reinterpret_cast<uint16_t*>(n->d.B1);
+  a.B2f = reinterpret_cast<uint16_t*>(n->d.B2f), a.B3f = reinterpret_cast<uint16_t*>(n->d.B3f);
+  a.Bff = reinterpret_cast<uint16_t*>(n->d.Bff);
+  a.B2 = n->d.B2, a.B3 = n->d.B3, a.Bf = n->d.Bf, a.BfT = n->d.BfT, a.Bh = n->d.Bh, a.Bhp = n->d.Bhp;
+  a.b1 = n->d.b1, a.b2 = n->d.b2, a.b3 = n->d.b3, a.bf = n->d.bf, a.bh = n->d.bh, a.A = A;
+  a.w2p = extra.w2p, a.w3p = extra.w3p, a.wfcp = extra.wfcp;
+  a.W1d = reinterpret_cast<uint8_t*>(n->d.W1d), a.s1q = n->d.s1q, a.b1q = n->d.b1q;
+  a.B2e = reinterpret_cast<uint16_t*>(n->d.B2e), a.B3e = reinterpret_cast<uint16_t*>(n->d.B3e);
+  a.Bfe = reinterpret_cast<uint16_t*>(n->d.Bfe);
+  // elements (threads) per segment of pack_ffnet_all; a segment of zero elements gets no blocks
+  int64_t el[kPackSegs] = {};
+  el[kSegB1] = 2 * 8 * 64 * 8;
+  el[kSegB2] = 4 * 128 * 64, el[kSegB3] = 4 * 144 * 64, el[kSegBf] = (int64_t)32 * 784 * 64;
+  el[kSegBfT] = (int64_t)3136 * 512;
+  el[kSegBh] = 2 * 128 * 64, el[kSegBhp] = 2 * 4 * 32 * 64;
+  el[kSegB2f] = (int64_t)Conv2F::CT * Conv2F::KS * 64 * 8, el[kSegB3f] = (int64_t)Conv3F::CT * Conv3F::KS * 64 * 8;
+  el[kSegBff] = (int64_t)32 * FcFast::KS * 64 * 8;
+  el[kSegBiases] = 672, el[kSegHeadBias] = 32;
+  el[kSegW2p] = extra.w2p ? 64 * 512 : 0, el[kSegW3p] = extra.w3p ? 64 * 576 : 0;
+  el[kSegWfcp] = extra.wfcp ? (int64_t)512 * 3136 : 0;
+  el[kSegW1d] = 32 * 256;
+  // (one thread per bf16 TRIPLE of the f32-accurate layouts: a third of their 2-byte elements)
+  el[kSegB2e] = f32emu::packed_u4<f32emu::ProbConv2>() * 8 / 3, el[kSegB3e] = f32emu::packed_u4<f32emu::ProbConv3>() * 8 / 3;
+  el[kSegBfe] = f32emu::packed_u4<f32emu::ProbFc>() * 8 / 3;
+  // a net whose owner never runs large batches (a learner re-packs after every step) skips the two fc layouts
+  // only large batches read: Bf (f32 fragments, N >= kFcSplitBelow) and Bff (bf16 fragments, N >= kFastMinN)
+  // (... nor the layouts of the f32x3 mode its batches are too small for)
+  const int max_rows = n->max_rows;
+  if (max_rows > 0 && max_rows < kEmuConvMinN) el[kSegB2e] = el[kSegB3e] = 0;
+  if (max_rows > 0 && max_rows < kEmuFcMinN) el[kSegBfe] = 0;
+  if (max_rows > 0 && max_rows < kFcSplitBelow) el[kSegBf] = 0;
+  if (!packs_bf16_fc(max_rows)) el[kSegBff] = 0;  // (the split-K fc_bf16s serves 128 rows and up)
+  n->bft_stale = false;
+  if (max_rows >= kFastTrunkMinN && on_device && n->precision == 1) {  // (the owner's buffer outlives this call)
+    el[kSegBfT] = 0;
+    n->bft_stale = true;
+    n->bft_src = dv[6];
   }
-  {
-    PackAllArgs a{};
-    for (int i = 0; i < 12; ++i) a.p[i] = dv[i];
-    a.B1 = reinterpret_cast<uint16_t*>(n->d.B1);
-    a.B2f = reinterpret_cast<uint16_t*>(n->d.B2f), a.B3f = reinterpret_cast<uint16_t*>(n->d.B3f);
-    a.Bff = reinterpret_cast<uint16_t*>(n->d.Bff);
-    a.B2 = n->d.B2, a.B3 = n->d.B3, a.Bf = n->d.Bf, a.BfT = n->d.BfT, a.Bh = n->d.Bh, a.Bhp = n->d.Bhp;
-    a.b1 = n->d.b1, a.b2 = n->d.b2, a.b3 = n->d.b3, a.bf = n->d.bf, a.bh = n->d.bh, a.A = A;
-    a.w2p = extra.w2p, a.w3p = extra.w3p, a.wfcp = extra.wfcp;
-    a.W1d = reinterpret_cast<uint8_t*>(n->d.W1d), a.s1q = n->d.s1q, a.b1q = n->d.b1q;
-    a.B2e = reinterpret_cast<uint16_t*>(n->d.B2e), a.B3e = reinterpret_cast<uint16_t*>(n->d.B3e);
-    a.Bfe = reinterpret_cast<uint16_t*>(n->d.Bfe);
-    // (one thread per bf16 TRIPLE of the f32-accurate layouts: a third of their 2-byte elements)
-    const int64_t emu2 = f32emu::packed_u4<f32emu::ProbConv2>() * 8 / 3, emu3 = f32emu::packed_u4<f32emu::ProbConv3>() * 8 / 3,
-                  emuf = f32emu::packed_u4<f32emu::ProbFc>() * 8 / 3;
-    const int64_t elems[20] = {2 * 8 * 64 * 8, 0, 4 * 128 * 64, 4 * 144 * 64, (int64_t)32 * 784 * 64,
-                               (int64_t)3136 * 512, 2 * 128 * 64, 2 * 4 * 32 * 64,
-                               (int64_t)Conv2F::CT * Conv2F::KS * 64 * 8, (int64_t)Conv3F::CT * Conv3F::KS * 64 * 8,
-                               (int64_t)32 * FcFast::KS * 64 * 8, 672, 32,
-                               extra.w2p ? 64 * 512 : 0, extra.w3p ? 64 * 576 : 0, extra.wfcp ? (int64_t)512 * 3136 : 0,
-                               32 * 256, emu2, emu3, emuf};
-    // a net whose owner never runs large batches (a learner re-packs after every step) skips the two fc layouts
-    // only large batches read: Bf (f32 fragments, N >= kFcSplitBelow) and Bff (bf16 fragments, N >= kFastMinN)
-    int64_t el[20];
-    for (int jn = 0; jn < 20; ++jn) el[jn] = elems[jn];
-    // (... nor the layouts of the f32x3 mode its batches are too small for)
-    if (n->max_rows > 0 && n->max_rows < kEmuConvMinN) el[17] = el[18] = 0;
-    if (n->max_rows > 0 && n->max_rows < kEmuFcMinN) el[19] = 0;
-    if (n->max_rows > 0 && n->max_rows < kFcSplitBelow) el[4] = 0;
-    if (n->max_rows > 0 && n->max_rows < kFastTrunkMinN) el[10] = 0;  // (the split-K fc_bf16s serves 128 rows and up)
-    n->bft_stale = false;
-    if (n->max_rows >= kFastTrunkMinN && on_device && n->precision == 1) {  // (the owner's buffer outlives this call)
-      el[5] = 0;
-      n->bft_stale = true;
-      n->bft_src = dv[6];
-    }
-    a.first[0] = 0;
-    for (int jn = 0; jn < 20; ++jn) a.first[jn + 1] = a.first[jn] + (int)ceil_div(el[jn], 256);
-    hipLaunchKernelGGL(pack_ffnet_all, dim3(a.first[20]), dim3(256), 0, s, a);
-  }
+  a.first[0] = 0;
+  for (int jn = 0; jn < kPackSegs; ++jn) a.first[jn + 1] = a.first[jn] + (int)ceil_div(el[jn], 256);
+  hipLaunchKernelGGL(pack_ffnet_all, dim3(a.first[kPackSegs]), dim3(256), 0, s, a);
   RELA_LAUNCH_CHECK();
-  if (tmp) {
-    RELA_HIP(hipStreamSynchronize(s));
-    (void)hipFree(tmp);
-  }
+  if (int rc = free_staging(tmp, s)) return rc;
   n->loaded = true;
   n->version += 1;
   return RELA_OK;
@@ -2301,7 +2432,7 @@ int rela_amd::ffnet_load_impl(rela_ffnet* n, const rela_ffnet_params* p, int on_
 
 extern "C" int rela_ffnet_forward(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev,
                                   float* q_dev, void* ws, int64_t ws_bytes, void* stream_) {
-  return rela_amd::ffnet_forward_mode(n, N, s_dev, legal_dev, q_dev, ws, ws_bytes, stream_, -1);
+  return rela_amd::ffnet_forward_mode(n, N, s_dev, legal_dev, q_dev, ws, ws_bytes, stream_, kModeNet);
 }
 
 int rela_amd::ffnet_forward_mode(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev, float* q_dev,
@@ -2312,178 +2443,80 @@ int rela_amd::ffnet_forward_mode(const rela_ffnet* n, int N, const uint8_t* s_de
              "rela_ffnet_forward: workspace of %lld bytes is too small for batch %d", (long long)ws_bytes, N);
   RELA_CHECK(((uintptr_t)s_dev & 15) == 0 && ((uintptr_t)ws & 15) == 0, RELA_EINVAL,
              "rela_ffnet_forward: s_dev and workspace must be 16-byte aligned");
+  RELA_CHECK(n->max_rows <= 0 || N <= n->max_rows, RELA_EINVAL,
+             "rela_ffnet_forward: batch %d on a net whose owner declared at most %d rows", N, n->max_rows);
   hipStream_t s = (hipStream_t)stream_;
-  float* a1 = static_cast<float*>(ws);
-  float* a2 = a1 + kA1 * N;
-  float* a3 = a2 + kA2 * N;
-  float* h = a3 + kA3 * N;
-  float* ha = h + kH * N;
+  const FFNetWs w = ffnet_ws(ws, N);
   const FFNetDev& d = n->d;
   const char* const* names = n->prof_names ? n->prof_names : kProfActor;
   const char* name12 = n->prof_names ? "learner_fwd_conv12" : "conv12_fused";  // conv1 -> conv2 in one launch
-  RELA_CHECK(n->max_rows <= 0 || N <= n->max_rows, RELA_EINVAL,
-             "rela_ffnet_forward: batch %d on a net whose owner declared at most %d rows", N, n->max_rows);
-  // (a net packed for small batches only has no bf16 fc fragments: it keeps the f32 fc whatever the threshold says)
-  const int fast_min_n = (n->max_rows > 0 && n->max_rows < kFastMinN) ? n->max_rows + 1 : kFastMinN;
-  const bool keep_f32 = mode == 3;  // f32x3 that also leaves a1 / a2 / a3 in channel-last f32 (the learner's online(obs) pass)
-  const int precision = mode < 0 ? n->precision : (mode == 3 ? 2 : mode);
-  // Between kFastTrunkMinN and kFastMinN rows the convolutions still win on split-bf16 MFMA (N = 512: 39 us against
-  // 90 us in f32) but fc_bf16s has too few blocks (55 us against the 24 us of the f32 split-K GEMM): the trunk runs
-  // fast, a3 is turned back into f32 in place and fc takes the f32 path.
-  const bool fast_trunk_only = precision == 1 && N < fast_min_n && N >= kFastTrunkMinN;
-  // ... and (r3) fc too, as a split-K launch of fc_bf16s, when this net packs the bf16 fc fragments
-  const bool fc_split_bf16 = fast_trunk_only && !(n->max_rows > 0 && n->max_rows < kFastTrunkMinN);
-  const bool emu_conv = precision == 2 && N >= kEmuConvMinN && N <= kEmuMaxN && !(n->max_rows > 0 && n->max_rows < kEmuConvMinN);
-  if (fast_trunk_only) {
-    uint8_t *r2 = reinterpret_cast<uint8_t*>(a2), *r3 = reinterpret_cast<uint8_t*>(a3);
-    {
-      ProfScope prof(name12, s);
-      note_launch("conv12_i8"); hipLaunchKernelGGL(conv12_i8, dim3(persistent_blocks(N)), dim3(kThreads), Conv12I::LDS_TOTAL, s, s_dev,
-                         (const uint4*)d.W1d, (const float*)d.s1q, (const float*)d.b1q, (const uint4*)d.B2f, (const float*)d.b2, r2, N);
-    }
-    {
-      ProfScope prof(names[2], s);
-      note_launch("conv_bf16s<Conv3F>"); hipLaunchKernelGGL(conv_bf16s<Conv3F>, dim3(persistent_blocks(ceil_div(N, Conv3F::S))), dim3(kThreads),
-                         Conv3F::LDS_TOTAL, s, (const uint8_t*)r2, (const uint4*)d.B3f, (const float*)d.b3, r3, N);
-      if (!fc_split_bf16) {
-        note_launch("unsplit_records64"); hipLaunchKernelGGL(unsplit_records64, dim3(ceil_div((int64_t)N * 49, 4)), dim3(256), 0, s, r3, (int64_t)N * 49);
-      }
-    }
-    if (fc_split_bf16) {
-      // fc on split-bf16 MFMA straight from a3's records, the contraction split over blockIdx.z so that ~256 blocks
-      // run (r3; the f32 split-K GEMM after an unsplit pass took 21 + 6 + 6 us at 512 rows); a3 STAYS in records
-      const int rb = ceil_div(N, FcFast::BM);
-      int slices = std::max(1, std::min(FcFast::NPOS, kNumCU / (4 * rb)));
-      slices = std::min(slices, (int)(8192 / N));
-      const int per = ceil_div(FcFast::NPOS, slices);
-      slices = ceil_div(FcFast::NPOS, per);
-      float* part = ha + kHA * N;
-      part += (64 - ((part - static_cast<float*>(ws)) & 63)) & 63;
-      {
-        ProfScope prof(names[3], s);
-        note_launch("fc_bf16s (split-K)");
-        hipLaunchKernelGGL((fc_bf16s<FcFast, true>), fc_grid_xcd(rb, slices), dim3(kThreads), FcFast::LDS_BYTES, s,
-                           (const uint8_t*)r3, (const uint4*)d.Bff, (const float*)d.bf, part, N, per);
-      }
-      note_launch("fc_reduce"); hipLaunchKernelGGL(fc_reduce, dim3(ceil_div(N * 128, 256)), dim3(256), 0, s, (const float*)part, slices, N,
-                         (const float*)d.bf, h);
-    }
-  }
-  if (precision == 1 && N >= fast_min_n) {
-    // split-bf16 fast path: a1 / a2 / a3 hold split records (same bytes as the f32 tensors they replace)
-    uint8_t *r2 = reinterpret_cast<uint8_t*>(a2), *r3 = reinterpret_cast<uint8_t*>(a3);
-    {  // conv1 (int8 matrix cores) -> conv2 (split-bf16), fused per frame through LDS
-      ProfScope prof(name12, s);
-      note_launch("conv12_i8"); hipLaunchKernelGGL(conv12_i8, dim3(persistent_blocks(N)), dim3(kThreads), Conv12I::LDS_TOTAL, s, s_dev,
-                         (const uint4*)d.W1d, (const float*)d.s1q, (const float*)d.b1q, (const uint4*)d.B2f, (const float*)d.b2, r2, N);
-    }
-    {
-      ProfScope prof(names[2], s);
-      note_launch("conv_bf16s<Conv3F>"); hipLaunchKernelGGL(conv_bf16s<Conv3F>, dim3(persistent_blocks(ceil_div(N, Conv3F::S))), dim3(kThreads),
-                         Conv3F::LDS_TOTAL, s, (const uint8_t*)r2, (const uint4*)d.B3f, (const float*)d.b3, r3, N);
-    }
-    {
+  const FfnetPlan plan = plan_ffnet_forward(mode, n->precision, N, n->max_rows);
+
+  // the trunk: a3 as f32, as split-bf16 records in its own place, or as split3 records at rec3 -- whatever plan.fc reads
+  uint8_t* rec2 = static_cast<uint8_t*>(ws) + ws_records_offset(N);
+  uint8_t* rec3 = rec2 + (int64_t)N * kRec2Bytes;
+  TrunkOpts opts;
+  opts.keep_f32 = plan.keep_f32;
+  opts.leave_a3_records = !plan.unsplit_a3;
+  launch_trunk(d, plan.trunk, N, s_dev, w.a1, w.a2, w.a3, rec2, rec3, opts, {names[0], names[1], names[2], name12}, s);
+
+  const uint8_t* a3_records = reinterpret_cast<const uint8_t*>(w.a3);
+  switch (plan.fc) {
+    case kFcBf16: {
       ProfScope prof(names[3], s);
       note_launch("fc_bf16s");
       hipLaunchKernelGGL(fc_bf16s<FcFast>, fc_grid_xcd(ceil_div(N, FcFast::BM), 1), dim3(kThreads), FcFast::LDS_BYTES, s,
-                           (const uint8_t*)r3, (const uint4*)d.Bff, (const float*)d.bf, h, N, 0);
+                         a3_records, (const uint4*)d.Bff, (const float*)d.bf, w.h, N, 0);
+      break;
     }
-  } else {
-  if (emu_conv) {
-    // f32x3 (precision 2; mode 3 = the learner's pass that also leaves a1 / a2 / a3 in f32 for the backward kernels): the
-    // trunk on split3 records.  conv1 -> conv2 fused per frame; conv3 from LDS images with resident weights; fc below.
-    uint8_t* rec2 = static_cast<uint8_t*>(ws) + ws_records_offset(N);
-    uint8_t* rec3 = rec2 + (int64_t)N * kRec2Bytes;
-    {
-      ProfScope prof(name12, s);
-      note_launch("conv12_s3");
-      if (keep_f32)
-        hipLaunchKernelGGL(s3::conv12_s3<true>, dim3(persistent_blocks(N)), dim3(s3::Conv12S::kT), s3::Conv12S::LDS_TOTAL, s, s_dev,
-                           (const uint4*)d.W1d, (const float*)d.s1q, (const float*)d.b1q, (const uint4*)d.B2e, (const float*)d.b2,
-                           rec2, a1, N);
-      else
-        hipLaunchKernelGGL(s3::conv12_s3<false>, dim3(persistent_blocks(N)), dim3(s3::Conv12S::kT), s3::Conv12S::LDS_TOTAL, s, s_dev,
-                           (const uint4*)d.W1d, (const float*)d.s1q, (const float*)d.b1q, (const uint4*)d.B2e, (const float*)d.b2,
-                           rec2, (float*)nullptr, N);
-    }
-    {
-      ProfScope prof(names[2], s);
-      note_launch("conv3_img_s3");
-      s3::launch_conv3_img(rec2, d.B3e, d.b3, rec3, N, s, persistent_blocks(N));
-    }
-    {
+    case kFcBf16SplitK:
+      launch_fc_bf16_splitk(d, a3_records, fc_part_ptr(ws, w.ha, N), w.h, N, names[3], s);
+      break;
+    case kFcS3:
+    case kFcS3SplitK: {
       ProfScope prof(names[3], s);
       note_launch("gemm_s3<fc>");
-      const s3::Plan pl = s3::plan<s3::ProbFc>(N, N < kFcSplitBelow && (int64_t)8 * N <= 8192);  // (the partial tiles' space)
+      const s3::Plan pl = s3::plan<s3::ProbFc>(N, plan.fc == kFcS3SplitK);
       if (pl.slices > 1) {  // small batches: the contraction split over blocks, fc_reduce adds slices + bias + ReLU
-        float* part = ha + kHA * N;
-        part += (64 - ((part - static_cast<float*>(ws)) & 63)) & 63;
+        float* part = fc_part_ptr(ws, w.ha, N);
         s3::launch<s3::ProbFc, s3::kEpiRaw>(rec3, d.Bfe, d.bf, part, N, s, pl);
-        note_launch("fc_reduce"); hipLaunchKernelGGL(fc_reduce, dim3(ceil_div(N * 128, 256)), dim3(256), 0, s, (const float*)part, pl.slices, N,
-                           (const float*)d.bf, h);
+        launch_fc_reduce(part, pl.slices, N, d.bf, w.h, s);
       } else {
-        s3::launch<s3::ProbFc, s3::kEpiRelu>(rec3, d.Bfe, d.bf, h, N, s);
+        s3::launch<s3::ProbFc, s3::kEpiRelu>(rec3, d.Bfe, d.bf, w.h, N, s);
       }
+      break;
     }
-    if (keep_f32) {
-      note_launch("unsplit_s3");
-      const int64_t p2 = (int64_t)N * 81, p3 = (int64_t)N * 49;
-      hipLaunchKernelGGL(s3::unsplit_s3<64>, dim3((unsigned)ceil_div(p2 * 16, 256)), dim3(256), 0, s, (const uint8_t*)rec2, a2, p2);
-      hipLaunchKernelGGL(s3::unsplit_s3<64>, dim3((unsigned)ceil_div(p3 * 16, 256)), dim3(256), 0, s, (const uint8_t*)rec3, a3, p3);
+    case kFcF32SplitK: {
+      float* part = fc_part_ptr(ws, w.ha, N);
+      if (n->bft_stale) {  // (see rela_ffnet::bft_stale)
+        PackAllArgs a{};
+        a.p[6] = n->bft_src, a.BfT = d.BfT;
+        for (int jn = 0; jn < kPackSegs; ++jn)
+          a.first[jn + 1] = a.first[jn] + (jn == kSegBfT ? (int)ceil_div((int64_t)3136 * 512, 256) : 0);
+        hipLaunchKernelGGL(pack_ffnet_all, dim3(a.first[kPackSegs]), dim3(256), 0, s, a);
+        n->bft_stale = false;
+      }
+      ProbFcFwd p{};
+      p.M = N, p.N = 512, p.K = 3136;
+      p.a3 = w.a3, p.wt = d.BfT, p.part = part;
+      gemm::launch_gemm<TileFcSmall>(p, plan.fc_slices, s, names[3]);
+      launch_fc_reduce(part, plan.fc_slices, N, d.bf, w.h, s);
+      break;
     }
-  } else {
-  if (!fast_trunk_only) {
-  {
-    ProfScope prof(names[0], s);
-    note_launch("conv1_bf16x3"); hipLaunchKernelGGL(conv1_bf16x3, dim3(ceil_div(N, Conv1B::S)), dim3(kThreads), Conv1B::LDS_BYTES, s, s_dev,
-                       d.B1, d.b1, a1, N);
-  }
-  {
-    ProfScope prof(names[1], s);
-    launch_conv<Conv2>(a1, d.B2, d.b2, a2, N, s);
-  }
-  {
-    ProfScope prof(names[2], s);
-    launch_conv<Conv3>(a2, d.B3, d.b3, a3, N, s);
-  }
-  }
-  }
-  if (fc_split_bf16 || emu_conv) {
-    // (h is already there)
-  } else if (N < kFcSplitBelow) {
-    const int splits = fc_splits(N);
-    float* part = ha + kHA * N;
-    part += (64 - ((part - static_cast<float*>(ws)) & 63)) & 63;  // 256-byte aligned (float4 loads)
-    if (n->bft_stale) {  // (see rela_ffnet::bft_stale)
-      PackAllArgs a{};
-      a.p[6] = n->bft_src, a.BfT = d.BfT;
-      for (int jn = 0; jn < 20; ++jn) a.first[jn + 1] = a.first[jn] + (jn == 5 ? (int)ceil_div((int64_t)3136 * 512, 256) : 0);
-      hipLaunchKernelGGL(pack_ffnet_all, dim3(a.first[20]), dim3(256), 0, s, a);
-      n->bft_stale = false;
+    case kFcF32Gemm: {
+      ProfScope prof(names[3], s);
+      note_launch("gemm_mfma<GemmFc> (f32)");
+      launch_gemm_bm<GemmFc, GemmFc112>(w.a3, nullptr, d.Bf, d.bf, w.h, nullptr, nullptr, N, s);
+      break;
     }
-    ProbFcFwd p{};
-    p.M = N, p.N = 512, p.K = 3136;
-    p.a3 = a3, p.wt = d.BfT, p.part = part;
-    gemm::launch_gemm<TileFcSmall>(p, splits, s, names[3]);
-    note_launch("fc_reduce"); hipLaunchKernelGGL(fc_reduce, dim3(ceil_div(N * 128, 256)), dim3(256), 0, s, (const float*)part, splits, N,
-                       (const float*)d.bf, h);
-  } else {
-    ProfScope prof(names[3], s);
-    note_launch("gemm_mfma<GemmFc> (f32)");
-    if (prefer_bm112(N, GemmFc::CT / GemmFc::CTB, GemmFc::BM))
-      hipLaunchKernelGGL(gemm_mfma<GemmFc112>, dim3(GemmFc112::CT / GemmFc112::CTB, ceil_div(N, GemmFc112::BM)),
-                         dim3(kThreads), 0, s, (const float*)a3, (const float*)nullptr, (const float*)d.Bf,
-                         (const float*)d.bf, h, (const float*)nullptr, (float*)nullptr, N);
-    else
-      hipLaunchKernelGGL(gemm_mfma<GemmFc>, dim3(GemmFc::CT / GemmFc::CTB, ceil_div(N, GemmFc::BM)), dim3(kThreads), 0,
-                         s, (const float*)a3, (const float*)nullptr, (const float*)d.Bf, (const float*)d.bf, h,
-                         (const float*)nullptr, (float*)nullptr, N);
   }
-  }
+  // the learner's f32x3 pass: a2 / a3 as f32 too, for the backward kernels (a1: conv12_s3 wrote it)
+  if (plan.trunk == kTrunkS3 && plan.keep_f32) unsplit_s3_a23(rec2, rec3, w.a2, w.a3, N, s);
   {
     ProfScope prof(names[4], s);
-    note_launch("heads_duel"); hipLaunchKernelGGL(heads_duel, dim3(ceil_div(N, kHeadRows)), dim3(256), 0, s, (const float*)h, (const float*)d.Bhp,
-                       (const float*)d.bh, legal_dev, ha, q_dev, N, n->num_action);
+    note_launch("heads_duel");
+    hipLaunchKernelGGL(heads_duel, dim3(ceil_div(N, kHeadRows)), dim3(256), 0, s, (const float*)w.h, (const float*)d.Bhp,
+                       (const float*)d.bh, legal_dev, w.ha, q_dev, N, n->num_action);
   }
   RELA_LAUNCH_CHECK();
   return RELA_OK;
@@ -2528,9 +2561,8 @@ __global__ void unsplit_trunk_rows(uint8_t* __restrict__ a1, uint8_t* __restrict
 }  // namespace
 
 bool ffnet_learner_forward_ok(const rela_ffnet* on, const rela_ffnet* tg, int B) {
-  const auto packs_bf16_fc = [](const rela_ffnet* n) { return !(n->max_rows > 0 && n->max_rows < kFastTrunkMinN); };
-  return on && tg && on->loaded && tg->loaded && B >= kFastTrunkMinN && 2 * B < kFcSplitBelow && packs_bf16_fc(on) &&
-         packs_bf16_fc(tg);
+  return on && tg && on->loaded && tg->loaded && learner_merged_rows(B) && packs_bf16_fc(on->max_rows) &&
+         packs_bf16_fc(tg->max_rows);
 }
 
 // online over [s ; s'] (2 B rows: rows < B are s) and target over s' (B rows): conv1 -> conv2 of both nets in ONE
@@ -2544,26 +2576,13 @@ int ffnet_learner_forward(const rela_ffnet* on, const rela_ffnet* tg, int B, con
   RELA_CHECK(ws_bytes >= rela_ffnet_workspace_bytes(on, 2 * B), RELA_EINVAL, "ffnet_learner_forward: workspace too small");
   RELA_CHECK(((uintptr_t)s_obs & 15) == 0 && ((uintptr_t)s_next & 15) == 0, RELA_EINVAL, "ffnet_learner_forward: frames must be 16-byte aligned");
   const FFNetWs w = ffnet_ws(ws_on, 2 * B), wt = ffnet_ws(ws_tg, B);
+  const auto recs = [](float* p) { return reinterpret_cast<uint8_t*>(p); };
   TrunkJobs jobs{};
   jobs.n = 2;
   const int total = std::min(kNumCU, 3 * B);
   const int nb0 = std::max(1, std::min(total - 1, (int)((int64_t)total * 2 / 3)));
-  TrunkJob& j0 = jobs.j[0];
-  j0.in0 = s_obs, j0.in1 = s_next, j0.n_in0 = B;
-  j0.B2 = (const uint4*)on->d.B2f, j0.B3 = (const uint4*)on->d.B3f;
-  j0.b2 = on->d.b2, j0.b3 = on->d.b3;
-  j0.W1d = on->d.W1d, j0.s1q = on->d.s1q, j0.b1q = on->d.b1q;
-  j0.a1_out = reinterpret_cast<uint8_t*>(w.a1), j0.a1_lo = 0, j0.n_a1 = B;
-  j0.a2 = reinterpret_cast<uint8_t*>(w.a2), j0.a3 = reinterpret_cast<uint8_t*>(w.a3);
-  j0.N = 2 * B, j0.block0 = 0, j0.nblocks = nb0;
-  TrunkJob& j1 = jobs.j[1];
-  j1.in0 = s_next, j1.in1 = s_next, j1.n_in0 = B;
-  j1.B2 = (const uint4*)tg->d.B2f, j1.B3 = (const uint4*)tg->d.B3f;
-  j1.b2 = tg->d.b2, j1.b3 = tg->d.b3;
-  j1.W1d = tg->d.W1d, j1.s1q = tg->d.s1q, j1.b1q = tg->d.b1q;
-  j1.a1_out = nullptr, j1.a1_lo = 0, j1.n_a1 = 0;
-  j1.a2 = reinterpret_cast<uint8_t*>(wt.a2), j1.a3 = reinterpret_cast<uint8_t*>(wt.a3);
-  j1.N = B, j1.block0 = nb0, j1.nblocks = total - nb0;
+  jobs.j[0] = trunk_job(on->d, s_obs, s_next, B, recs(w.a1), 0, B, recs(w.a2), recs(w.a3), 2 * B, 0, nb0);
+  jobs.j[1] = trunk_job(tg->d, s_next, s_next, B, nullptr, 0, 0, recs(wt.a2), recs(wt.a3), B, nb0, total - nb0);
   {
     ProfScope prof("learner_fwd_conv12", s);
     note_launch("conv12_i8_jobs");
@@ -2576,26 +2595,8 @@ int ffnet_learner_forward(const rela_ffnet* on, const rela_ffnet* tg, int B, con
     note_launch("conv3_bf16s_jobs");
     hipLaunchKernelGGL(conv3_bf16s_jobs, dim3(total), dim3(kThreads), Conv3F::LDS_TOTAL, s, jobs);
   }
-  auto fc = [&](const rela_ffnet* n, const FFNetWs& ww, int N, void* wsp) {
-    const int rb = ceil_div(N, FcFast::BM);
-    int slices = std::max(1, std::min(FcFast::NPOS, kNumCU / (4 * rb)));
-    slices = std::min(slices, 8192 / N);
-    const int per = ceil_div(FcFast::NPOS, slices);
-    slices = ceil_div(FcFast::NPOS, per);
-    float* part = ww.ha + kHA * N;
-    part += (64 - ((part - static_cast<float*>(wsp)) & 63)) & 63;
-    {
-      ProfScope prof("learner_fwd_fc", s);
-      note_launch("fc_bf16s (split-K)");
-      hipLaunchKernelGGL((fc_bf16s<FcFast, true>), fc_grid_xcd(rb, slices), dim3(kThreads), FcFast::LDS_BYTES, s,
-                         (const uint8_t*)ww.a3, (const uint4*)n->d.Bff, (const float*)n->d.bf, part, N, per);
-    }
-    note_launch("fc_reduce");
-    hipLaunchKernelGGL(fc_reduce, dim3(ceil_div(N * 128, 256)), dim3(256), 0, s, (const float*)part, slices, N,
-                       (const float*)n->d.bf, ww.h);
-  };
-  fc(on, w, 2 * B, ws_on);
-  fc(tg, wt, B, ws_tg);
+  launch_fc_bf16_splitk(on->d, recs(w.a3), fc_part_ptr(ws_on, w.ha, 2 * B), w.h, 2 * B, "learner_fwd_fc", s);
+  launch_fc_bf16_splitk(tg->d, recs(wt.a3), fc_part_ptr(ws_tg, wt.ha, B), wt.h, B, "learner_fwd_fc", s);
   {
     ProfScope prof("learner_fwd_heads", s);
     const int A = on->num_action, nb = ceil_div(B, kHeadRows);
@@ -2661,7 +2662,10 @@ using ProbGateX3 = s3::ProbFcT<2048>;
 inline int64_t lstm_ws_records_offset(int batch) {
   return (((int64_t)sizeof(float) * kLstmWsFloats * (batch > 0 ? batch : 0) + 256) + 255) & ~(int64_t)255;
 }
-}
+const char* const kLstmActorNames[3] = {"conv1_bf16x3", "conv2_mfma", "conv3_mfma"};
+// the trunk of an AtariLSTMNet: the fused conv1 -> conv2 launches run under conv2's label
+inline TrunkLabels lstm_trunk_labels(const char* const* names) { return {names[0], names[1], names[2], names[1]}; }
+}  // namespace
 
 extern "C" int rela_lstmnet_create(rela_lstmnet** out, int num_action, int device) {
   RELA_CHECK(out && num_action >= 1 && num_action <= 31, RELA_EINVAL,
@@ -2675,46 +2679,12 @@ extern "C" int rela_lstmnet_create(rela_lstmnet** out, int num_action, int devic
   auto* n = new rela_lstmnet();
   n->device = device;
   n->num_action = num_action;
-  FFNetDev& d = n->d;
-  RELA_HIP(hipMalloc(&d.B1, sizeof(uint4) * Conv1B::FRAG_UINT4));
-  RELA_HIP(hipMalloc(&d.b1, sizeof(float) * 32));
-  RELA_HIP(hipMalloc(&d.B2, sizeof(float) * 4 * 128 * 64));
-  RELA_HIP(hipMalloc(&d.b2, sizeof(float) * 64));
-  RELA_HIP(hipMalloc(&d.B3, sizeof(float) * 4 * 144 * 64));
-  RELA_HIP(hipMalloc(&d.b3, sizeof(float) * 64));
-  RELA_HIP(hipMalloc(&d.Bh, sizeof(float) * 2 * 128 * 64));
-  RELA_HIP(hipMalloc(&d.bh, sizeof(float) * 32));
+  if (int rc = alloc_trunk(n->d)) return rc;
   RELA_HIP(hipMalloc(&n->Bl, sizeof(float) * (size_t)GemmLstm::CT * GemmLstm::KS * 64));
+  RELA_HIP(hipMalloc(&n->bl, sizeof(float) * 2048));
   RELA_HIP(hipMalloc(&n->Wrec, (size_t)2048 * 49 * 256));
   RELA_HIP(hipMalloc(&n->Wx3, sizeof(uint4) * f32emu::packed_u4<f32emu::ProbGateX>()));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&s3::conv12_s3<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               s3::Conv12S::LDS_TOTAL));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&s3::conv12_s3<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               s3::Conv12S::LDS_TOTAL));
-  RELA_HIP(hipMalloc(&n->bl, sizeof(float) * 2048));
-  RELA_HIP(hipMalloc(&d.W1d, sizeof(uint4) * Conv12I::W1_UINT4));
-  RELA_HIP(hipMalloc(&d.s1q, sizeof(float) * 32));
-  RELA_HIP(hipMalloc(&d.b1q, sizeof(float) * 32));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv12_i8), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               Conv12I::LDS_TOTAL));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv12_i8_jobs), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               Conv12I::LDS_TOTAL));
-  RELA_HIP(hipMalloc(&d.B2f, sizeof(uint4) * Conv2F::CT * Conv2F::KS * 2 * 64));
-  RELA_HIP(hipMalloc(&d.B3f, sizeof(uint4) * Conv3F::CT * Conv3F::KS * 2 * 64));
-  RELA_HIP(hipMalloc(&d.B2e, sizeof(uint4) * f32emu::packed_u4<f32emu::ProbConv2>()));
-  RELA_HIP(hipMalloc(&d.B3e, sizeof(uint4) * f32emu::packed_u4<f32emu::ProbConv3>()));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16s<Conv3F>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, Conv3F::LDS_TOTAL));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1_bf16x3),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, Conv1B::LDS_BYTES));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma<Conv2>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, Conv2::LDS_BYTES));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma<Conv3>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, Conv3::LDS_BYTES));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_bstat<Conv2>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * Conv2::LDS_BYTES));
-  RELA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_bstat<Conv3>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * Conv3::LDS_BYTES));
+  if (int rc = opt_in_dynamic_lds()) return rc;
   *out = n;
   return RELA_OK;
 }
@@ -2757,23 +2727,7 @@ extern "C" int rela_lstmnet_load(rela_lstmnet* n, const rela_lstmnet_params* p, 
                           p->w_hh,    p->b_ih,    p->b_hh,    p->v_w,     p->v_b,     p->a_w,     p->a_b};
   const float* dv[14];
   float* tmp = nullptr;
-  if (on_device) {
-    for (int i = 0; i < 14; ++i) {
-      RELA_CHECK(src[i], RELA_EINVAL, "rela_lstmnet_load: parameter %d is NULL", i);
-      dv[i] = src[i];
-    }
-  } else {
-    size_t total = 0;
-    for (int i = 0; i < 14; ++i) total += cnt[i];
-    RELA_HIP(hipMalloc(&tmp, sizeof(float) * total));
-    size_t off = 0;
-    for (int i = 0; i < 14; ++i) {
-      RELA_CHECK(src[i], RELA_EINVAL, "rela_lstmnet_load: parameter %d is NULL", i);
-      RELA_HIP(hipMemcpyAsync(tmp + off, src[i], sizeof(float) * cnt[i], hipMemcpyHostToDevice, s));
-      dv[i] = tmp + off;
-      off += cnt[i];
-    }
-  }
+  if (int rc = stage_params(src, cnt, 14, on_device, "rela_lstmnet_load", &tmp, dv, s)) return rc;
   auto pack = [&](int mode, const float* w, const float* w2, float* frag, int CT, int KS) {
     const int64_t total = (int64_t)CT * KS * 64;
     hipLaunchKernelGGL(pack_frags, dim3(ceil_div(total, 256)), dim3(256), 0, s, mode, w, w2, A, frag, CT, KS);
@@ -2803,85 +2757,11 @@ extern "C" int rela_lstmnet_load(rela_lstmnet* n, const rela_lstmnet_params* p, 
   hipLaunchKernelGGL(pack_lstm_bias, dim3(8), dim3(256), 0, s, dv[8], dv[9], n->bl);
   hipLaunchKernelGGL(pack_head_bias, dim3(1), dim3(64), 0, s, dv[13], dv[11], A, n->d.bh);
   RELA_LAUNCH_CHECK();
-  if (tmp) {
-    RELA_HIP(hipStreamSynchronize(s));
-    (void)hipFree(tmp);
-  }
+  if (int rc = free_staging(tmp, s)) return rc;
   n->loaded = true;
   n->version += 1;
   return RELA_OK;
 }
-
-namespace {
-// conv trunk of an AtariLSTMNet: f32 kernels, or (fast && N >= kFastTrunkMinN) conv1 -> conv2 fused and conv3 on
-// split-bf16 MFMA with a3 turned back into f32 in place (a1 is then NOT produced, a2 holds split records)
-// records (with fast): a3 stays in split records (the rec64 operand of the learner's split-bf16 gate GEMM); returns
-// whether it did
-// rec (with emu, N >= kEmuConvMinN): N * (kRec2Bytes + kRec3Bytes) bytes of scratch -- the f32x3 trunk on split3 records
-// (conv12_s3 -> conv3_img_s3); a3's records stay at rec + N * kRec2Bytes for the gate GEMM; keep_f32: a1 / a2 / a3 are
-// ALSO written as channel-last f32 (the learner's online pass); returns whether the records were produced
-bool lstm_trunk_launch(const FFNetDev& d, int N, const uint8_t* s_dev, float* a1, float* a2, float* a3, bool fast,
-                       hipStream_t s, const char* const* names, bool records = false, bool emu = false, uint8_t* rec = nullptr,
-                       bool keep_f32 = true) {
-  if (emu && rec && N >= kEmuConvMinN && N <= kEmuMaxN) {
-    uint8_t *rec2 = rec, *rec3 = rec + (int64_t)N * kRec2Bytes;
-    {
-      ProfScope prof(names[1], s);
-      note_launch("conv12_s3");
-      if (keep_f32)
-        hipLaunchKernelGGL(s3::conv12_s3<true>, dim3(persistent_blocks(N)), dim3(s3::Conv12S::kT), s3::Conv12S::LDS_TOTAL, s, s_dev,
-                           (const uint4*)d.W1d, (const float*)d.s1q, (const float*)d.b1q, (const uint4*)d.B2e, (const float*)d.b2,
-                           rec2, a1, N);
-      else
-        hipLaunchKernelGGL(s3::conv12_s3<false>, dim3(persistent_blocks(N)), dim3(s3::Conv12S::kT), s3::Conv12S::LDS_TOTAL, s, s_dev,
-                           (const uint4*)d.W1d, (const float*)d.s1q, (const float*)d.b1q, (const uint4*)d.B2e, (const float*)d.b2,
-                           rec2, (float*)nullptr, N);
-    }
-    {
-      ProfScope prof(names[2], s);
-      note_launch("conv3_img_s3");
-      s3::launch_conv3_img(rec2, d.B3e, d.b3, rec3, N, s, persistent_blocks(N));
-    }
-    if (keep_f32) {
-      note_launch("unsplit_s3");
-      const int64_t p2 = (int64_t)N * 81, p3 = (int64_t)N * 49;
-      hipLaunchKernelGGL(s3::unsplit_s3<64>, dim3((unsigned)ceil_div(p2 * 16, 256)), dim3(256), 0, s, (const uint8_t*)rec2, a2, p2);
-      hipLaunchKernelGGL(s3::unsplit_s3<64>, dim3((unsigned)ceil_div(p3 * 16, 256)), dim3(256), 0, s, (const uint8_t*)rec3, a3, p3);
-    }
-    return true;
-  }
-  if (fast && N >= kFastTrunkMinN) {
-    uint8_t *r2 = reinterpret_cast<uint8_t*>(a2), *r3 = reinterpret_cast<uint8_t*>(a3);
-    {
-      ProfScope prof(names[1], s);
-      note_launch("conv12_i8"); hipLaunchKernelGGL(conv12_i8, dim3(persistent_blocks(N)), dim3(kThreads), Conv12I::LDS_TOTAL, s, s_dev,
-                         (const uint4*)d.W1d, (const float*)d.s1q, (const float*)d.b1q, (const uint4*)d.B2f, (const float*)d.b2, r2, N);
-    }
-    ProfScope prof(names[2], s);
-    note_launch("conv_bf16s<Conv3F>"); hipLaunchKernelGGL(conv_bf16s<Conv3F>, dim3(persistent_blocks(ceil_div(N, Conv3F::S))), dim3(kThreads),
-                       Conv3F::LDS_TOTAL, s, (const uint8_t*)r2, (const uint4*)d.B3f, (const float*)d.b3, r3, N);
-    if (records) return true;
-    note_launch("unsplit_records64"); hipLaunchKernelGGL(unsplit_records64, dim3(ceil_div((int64_t)N * 49, 4)), dim3(256), 0, s, r3, (int64_t)N * 49);
-    return false;
-  }
-  {
-    ProfScope prof(names[0], s);
-    note_launch("conv1_bf16x3"); hipLaunchKernelGGL(conv1_bf16x3, dim3(ceil_div(N, Conv1B::S)), dim3(kThreads), Conv1B::LDS_BYTES, s, s_dev, d.B1,
-                       d.b1, a1, N);
-  }
-  // (f32x3 without record scratch, or below its batch threshold: the exact f32 kernels -- same accuracy)
-  {
-    ProfScope prof(names[1], s);
-    launch_conv<Conv2>(a1, d.B2, d.b2, a2, N, s);
-  }
-  {
-    ProfScope prof(names[2], s);
-    launch_conv<Conv3>(a2, d.B3, d.b3, a3, N, s);
-  }
-  return false;
-}
-const char* const kLstmActorNames[3] = {"conv1_bf16x3", "conv2_mfma", "conv3_mfma"};
-}  // namespace
 
 extern "C" int rela_lstmnet_step(const rela_lstmnet* n, int N, const uint8_t* s_dev, const float* legal_dev,
                                  const float* h_in, const float* c_in, float* h_out, float* c_out, float* q_dev,
@@ -2904,52 +2784,35 @@ extern "C" int rela_lstmnet_step(const rela_lstmnet* n, int N, const uint8_t* s_
   // bf16x2 mode from kFastMinN rows up: a3 stays in split records, the x part of the gates is one split-bf16 GEMM
   // (gemm_bf16s.h: 41 GFLOP at 3,200 rows) and the f32 MFMA kernel only adds h x W_hh (K = 512) and runs the cell
   const bool fast_gates = n->precision == 1 && N >= kFastMinN;
-  uint8_t* rec = static_cast<uint8_t*>(ws) + lstm_ws_records_offset(N);
-  const bool recs = lstm_trunk_launch(d, N, s_dev, a1, a2, a3, n->precision == 1, s, kLstmActorNames, fast_gates,
-                                      n->precision == 2, rec, /*keep_f32=*/false);
-  if (n->precision == 2 && recs) {
-    // f32x3: the x part of the gates (3136 -> 2048) as a three-part GEMM over a3's records -> gx (raw sums, permuted gate
-    // columns); the f32 MFMA kernel adds h x W_hh (K = 512) and the bias and runs the cell
-    {
-      ProfScope prof("lstm_gates_x_f32x3", s);
-      note_launch("gemm_s3<gates_x>");
-      s3::launch<ProbGateX3, s3::kEpiRaw>(rec + (int64_t)N * kRec2Bytes, n->Wx3, nullptr, gx, N, s);
-    }
-    ProfScope prof("lstm_gates_mfma", s);
-    note_launch("gemm_mfma<GemmLstmH> (f32)");
-    if (prefer_bm112(N, GemmLstmH::CT / GemmLstmH::CTB, GemmLstmH::BM))
-      hipLaunchKernelGGL(gemm_mfma<GemmLstmH112>, dim3(GemmLstmH112::CT / GemmLstmH112::CTB, ceil_div(N, GemmLstmH112::BM)),
-                         dim3(kThreads), 0, s, h_in, (const float*)gx, (const float*)n->Bl, (const float*)n->bl, h_out,
-                         c_in, c_out, N);
-    else
-      hipLaunchKernelGGL(gemm_mfma<GemmLstmH>, dim3(GemmLstmH::CT / GemmLstmH::CTB, ceil_div(N, GemmLstmH::BM)),
-                         dim3(kThreads), 0, s, h_in, (const float*)gx, (const float*)n->Bl, (const float*)n->bl, h_out,
-                         c_in, c_out, N);
-  } else if (fast_gates && recs) {
+  uint8_t* rec2 = static_cast<uint8_t*>(ws) + lstm_ws_records_offset(N);
+  uint8_t* rec3 = rec2 + (int64_t)N * kRec2Bytes;
+  const LstmTrunkPlan tp = plan_lstm_trunk(n->precision == 1, n->precision == 2, /*has_rec_scratch=*/true, N, fast_gates);
+  TrunkOpts opts;
+  opts.leave_a3_records = tp.a3_records;
+  launch_trunk(d, tp.trunk, N, s_dev, a1, a2, a3, rec2, rec3, opts, lstm_trunk_labels(kLstmActorNames), s);
+  // the x part of the gates (3136 -> 2048) over a3's records -> gx (raw sums, permuted gate columns), where the trunk
+  // left records: as a three-part GEMM (f32x3) or a split-bf16 one (bf16x2)
+  bool x_in_gx = false;
+  if (tp.trunk == kTrunkS3) {
+    ProfScope prof("lstm_gates_x_f32x3", s);
+    note_launch("gemm_s3<gates_x>");
+    s3::launch<ProbGateX3, s3::kEpiRaw>(rec3, n->Wx3, nullptr, gx, N, s);
+    x_in_gx = true;
+  } else if (tp.trunk == kTrunkBf16 && tp.a3_records) {
     int rc = gemm16::launch_rec64_nt(reinterpret_cast<const uint8_t*>(a3), n->Wrec, N, 2048, 49, gemm16::EpiPlain{gx, 2048}, s,
                                      "lstm_gates_x_bf16");
     if (rc != RELA_OK) return rc;
+    x_in_gx = true;
+  }
+  {
     ProfScope prof("lstm_gates_mfma", s);
-    note_launch("gemm_mfma<GemmLstmH> (f32)");
-    if (prefer_bm112(N, GemmLstmH::CT / GemmLstmH::CTB, GemmLstmH::BM))
-      hipLaunchKernelGGL(gemm_mfma<GemmLstmH112>, dim3(GemmLstmH112::CT / GemmLstmH112::CTB, ceil_div(N, GemmLstmH112::BM)),
-                         dim3(kThreads), 0, s, h_in, (const float*)gx, (const float*)n->Bl, (const float*)n->bl, h_out,
-                         c_in, c_out, N);
-    else
-      hipLaunchKernelGGL(gemm_mfma<GemmLstmH>, dim3(GemmLstmH::CT / GemmLstmH::CTB, ceil_div(N, GemmLstmH::BM)),
-                         dim3(kThreads), 0, s, h_in, (const float*)gx, (const float*)n->Bl, (const float*)n->bl, h_out,
-                         c_in, c_out, N);
-  } else {
-    ProfScope prof("lstm_gates_mfma", s);
-    note_launch("gemm_mfma<GemmLstm> (f32)");
-    if (prefer_bm112(N, GemmLstm::CT / GemmLstm::CTB, GemmLstm::BM))
-      hipLaunchKernelGGL(gemm_mfma<GemmLstm112>, dim3(GemmLstm112::CT / GemmLstm112::CTB, ceil_div(N, GemmLstm112::BM)),
-                         dim3(kThreads), 0, s, (const float*)a3, h_in, (const float*)n->Bl, (const float*)n->bl, h_out,
-                         c_in, c_out, N);
-    else
-      hipLaunchKernelGGL(gemm_mfma<GemmLstm>, dim3(GemmLstm::CT / GemmLstm::CTB, ceil_div(N, GemmLstm::BM)),
-                         dim3(kThreads), 0, s, (const float*)a3, h_in, (const float*)n->Bl, (const float*)n->bl, h_out,
-                         c_in, c_out, N);
+    if (x_in_gx) {  // the f32 MFMA kernel adds h x W_hh (K = 512) and the bias and runs the cell
+      note_launch("gemm_mfma<GemmLstmH> (f32)");
+      launch_gemm_bm<GemmLstmH, GemmLstmH112>(h_in, gx, n->Bl, n->bl, h_out, c_in, c_out, N, s);
+    } else {
+      note_launch("gemm_mfma<GemmLstm> (f32)");
+      launch_gemm_bm<GemmLstm, GemmLstm112>(a3, h_in, n->Bl, n->bl, h_out, c_in, c_out, N, s);
+    }
   }
   if (q_dev || adv_dev) {
     {
@@ -2969,15 +2832,20 @@ extern "C" int rela_lstmnet_step(const rela_lstmnet* n, int N, const uint8_t* s_
 }
 
 // ---- internal entry points for the R2D2 learner (csrc/learner_r2d2.hip) -------------------------
-// conv trunk only: frames u8[N][4][84][84] -> a1 / a2 / a3 (channel-last, ffnet_layout.h)
 namespace rela_amd {
+// conv trunk only: frames u8[N][4][84][84] -> a1 / a2 / a3 (channel-last, ffnet_layout.h has the contract)
 int lstmnet_trunk(const rela_lstmnet* n, int N, const uint8_t* s_dev, float* a1, float* a2, float* a3, hipStream_t s,
                   const char* const* names, bool fast, bool* a3_records, uint8_t* s3_scratch, bool keep_f32) {
   RELA_CHECK(n && n->loaded, RELA_ESTATE, "lstmnet_trunk: parameters were never loaded");
   RELA_CHECK(N >= 1 && s_dev && a1 && a2 && a3, RELA_EINVAL, "lstmnet_trunk: bad arguments");
-  const bool rec = lstm_trunk_launch(n->d, N, s_dev, a1, a2, a3, fast, s, names, a3_records != nullptr,
-                                     !fast && n->precision == 2, s3_scratch, keep_f32);
-  if (a3_records) *a3_records = rec;
+  const LstmTrunkPlan tp = plan_lstm_trunk(fast, !fast && n->precision == 2, s3_scratch != nullptr, N, a3_records != nullptr);
+  uint8_t* rec3 = s3_scratch ? s3_scratch + (int64_t)N * kRec2Bytes : nullptr;
+  TrunkOpts opts;
+  opts.keep_f32 = keep_f32;
+  opts.leave_a3_records = tp.a3_records;
+  launch_trunk(n->d, tp.trunk, N, s_dev, a1, a2, a3, s3_scratch, rec3, opts, lstm_trunk_labels(names), s);
+  if (tp.trunk == kTrunkS3 && keep_f32) unsplit_s3_a23(s3_scratch, rec3, a2, a3, N, s);
+  if (a3_records) *a3_records = tp.a3_records;
   RELA_LAUNCH_CHECK();
   return RELA_OK;
 }
@@ -3006,26 +2874,20 @@ int lstmnet_trunk_records(const rela_lstmnet* n, int N, const uint8_t* s_dev, fl
                           hipStream_t s, const char* const* names) {
   RELA_CHECK(n && n->loaded, RELA_ESTATE, "lstmnet_trunk_records: parameters were never loaded");
   RELA_CHECK(N >= 1 && s_dev && a1 && a2 && a3 && a1_lo >= 0 && a1_lo <= N, RELA_EINVAL, "lstmnet_trunk_records: bad arguments");
-  const FFNetDev& d = n->d;
   TrunkJobs jobs{};
   jobs.n = 1;
-  TrunkJob& j0 = jobs.j[0];
-  j0.in0 = s_dev, j0.in1 = s_dev, j0.n_in0 = N;
-  j0.B2 = (const uint4*)d.B2f, j0.B3 = (const uint4*)d.B3f;
-  j0.b2 = d.b2, j0.b3 = d.b3;
-  j0.W1d = d.W1d, j0.s1q = d.s1q, j0.b1q = d.b1q;
-  j0.a1_out = reinterpret_cast<uint8_t*>(a1), j0.a1_lo = a1_lo, j0.n_a1 = N - a1_lo;
-  j0.a2 = reinterpret_cast<uint8_t*>(a2), j0.a3 = reinterpret_cast<uint8_t*>(a3);
-  j0.N = N, j0.block0 = 0, j0.nblocks = std::min(kNumCU, N);
+  const int nblocks = std::min(kNumCU, N);
+  jobs.j[0] = trunk_job(n->d, s_dev, s_dev, N, reinterpret_cast<uint8_t*>(a1), a1_lo, N - a1_lo, reinterpret_cast<uint8_t*>(a2),
+                        reinterpret_cast<uint8_t*>(a3), N, 0, nblocks);
   {
     ProfScope prof(names[1], s);
     note_launch("conv12_i8_jobs");
-    hipLaunchKernelGGL(conv12_i8_jobs, dim3(j0.nblocks), dim3(kThreads), Conv12I::LDS_TOTAL, s, jobs);
+    hipLaunchKernelGGL(conv12_i8_jobs, dim3(nblocks), dim3(kThreads), Conv12I::LDS_TOTAL, s, jobs);
   }
   {
     ProfScope prof(names[2], s);
     note_launch("conv3_bf16s_jobs");
-    hipLaunchKernelGGL(conv3_bf16s_jobs, dim3(j0.nblocks), dim3(kThreads), Conv3F::LDS_TOTAL, s, jobs);
+    hipLaunchKernelGGL(conv3_bf16s_jobs, dim3(nblocks), dim3(kThreads), Conv3F::LDS_TOTAL, s, jobs);
   }
   RELA_LAUNCH_CHECK();
   return RELA_OK;

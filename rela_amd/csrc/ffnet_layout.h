@@ -31,9 +31,6 @@ inline FFNetWs ffnet_ws(void* ws, int N) {
   return w;
 }
 
-}  // namespace rela_amd
-
-namespace rela_amd {
 // weight copies in the k order the learner's dgrad GEMMs read (one element per call):
 //   conv2: dst[oc][(kh*4+kw)*32+c], conv3: dst[oc][(kh*3+kw)*64+c], fc: dst[u][pos*64+c] <- src[u][c*49+pos]
 enum { kPermConv2 = 0, kPermConv3 = 1, kPermFc = 2 };
@@ -64,8 +61,9 @@ int ffnet_load_extra(rela_ffnet* n, const rela_ffnet_params* p, void* stream, co
 void ffnet_label_as_learner(rela_ffnet* n);
 // the owner never runs more than `rows` rows through this net: rela_ffnet_load skips the layouts only larger batches read
 void ffnet_set_max_rows(rela_ffnet* n, int rows);
-// rela_ffnet_forward with the precision chosen by the caller: mode -1 = the net's own (rela_ffnet_set_precision),
-// 0 = exact f32 whatever the net says -- the learner's pass that keeps a1 / a2 / a3 / h for the backward kernels
+// rela_ffnet_forward with the precision chosen by the caller: mode is an FfnetMode (ffnet_plan.h, which also says what
+// runs in each): kModeNet (-1) = the net's own (rela_ffnet_set_precision), kModeF32 (0) = exact f32 whatever the net says
+// -- the learner's pass that keeps a1 / a2 / a3 / h for the backward kernels
 int ffnet_forward_mode(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev, float* q_dev, void* ws,
                        int64_t ws_bytes, void* stream, int mode);
 // The Ape-X learner's three forwards of td_err (apex.py:30-45) in split-bf16 with one launch per layer: online over
@@ -76,13 +74,11 @@ int ffnet_learner_forward(const rela_ffnet* on, const rela_ffnet* tg, int B, con
                           const float* legal, const float* nlegal, float* q_on, float* q_no, float* q_nt, void* ws_on,
                           void* ws_tg, int64_t ws_bytes, hipStream_t s);
 int ffnet_learner_unsplit(int B, void* ws_on, hipStream_t s);
-}  // namespace rela_amd
 
-struct rela_lstmnet;
-namespace rela_amd {
 // internal (not part of the C ABI): the conv trunk and the dueling heads of an AtariLSTMNet on their own,
 // for the R2D2 learner, which batches the trunk over all T*B frames of a sequence batch and runs the
 // recurrent part itself.  names: three per-kernel timing labels.
+// Which of the three trunks runs is plan_lstm_trunk's decision (ffnet_plan.h); launch_trunk (ffnet.hip) runs it.
 // fast: conv1 -> conv2 fused and conv3 on split-bf16 MFMA (a3 comes out in f32 as always; a1 is NOT produced and a2 holds
 // split records, so only for passes whose activations nobody reads back)
 // a3_records != NULL (with fast): a3 may stay in split records [rows][49][64 hi | 64 lo] (*a3_records says whether)

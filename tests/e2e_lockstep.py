@@ -29,7 +29,7 @@ CFG_SLIDING = dict(CFG, sliding=True, env_seed=950, rounds=8)
 
 
 # r4: ONE actor thread with K = 128 envs -- the smallest shard whose forwards reach the split-bf16 kernels (from 128 rows
-# up, csrc/ffnet.hip kFastTrunkMinN) -- at the headline's replay exponents (alpha 0.6 / beta 0.4, pyrela/main.py:60-65).
+# up, csrc/ffnet_plan.h kFastTrunkMinN) -- at the headline's replay exponents (alpha 0.6 / beta 0.4, pyrela/main.py:60-65).
 # Ring 640 = five blocks of 128.  The golden also records the smallest gap between the two best legal Q-values over
 # every frame the run can see (tests/golden/make_golden.py e2e_big), so "greedy actions equal" is a checked expectation.
 # The synthetic frames are noise, so the online net's two best actions (14 and 9 with these parameters) differ by

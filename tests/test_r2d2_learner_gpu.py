@@ -207,7 +207,7 @@ def _random_batch(rng, A, B, seq, burn, n, device):
 
 
 # the three-part kernels of an f32x3 R2D2 learner step: both trunks and the x part of both gate GEMMs, from
-# kEmuConvMinN = 512 frames (T * B) up; below that the f32 kernels (csrc/ffnet.hip lstm_trunk_launch)
+# kEmuConvMinN = 512 frames (T * B) up; below that the f32 kernels (csrc/ffnet_plan.h plan_lstm_trunk)
 R2D2_X3_MIN_FRAMES = 512
 
 
