@@ -52,6 +52,14 @@ int rela_memcpy_h2d_async(void* dst_dev, const void* src_host, int64_t bytes, vo
  * 2 <= height, width <= 512, rows >= 1 (RELA_EINVAL otherwise).  Asynchronous on `stream` (the device of the buffers
  * must be current).                                                                                                  */
 int rela_atari_features(const uint8_t* screens_dev, int rows, int height, int width, uint8_t* planes_dev, void* stream);
+/* The same features from indexed-colour screens, as ALEInterface::getScreen delivers them (atari/atari_env.h:66-67; the
+ * env's getScreenRGB, atari_env.h:102,147,183, expands them on the host through a 256-entry table).  screens_dev:
+ * [rows][2][height][width] u8 palette indices, screen 0 the current and screen 1 the previous screen; palettes_dev:
+ * [rows][256][3] u8 RGB, one table per row, in device memory.  The frame is max(pal[ia][c], pal[ib][c]) per channel --
+ * the lookup comes first -- and everything after it is rela_atari_features' recipe, so the planes equal those of the
+ * expanded screens bit for bit.  Every index 0..255 is valid.  Shape limits, errors and stream as above.            */
+int rela_atari_features_indexed(const uint8_t* screens_dev, const uint8_t* palettes_dev, int rows, int height, int width,
+                                uint8_t* planes_dev, void* stream);
 
 /* ===================================================================================
  * Prioritized replay  --  rela/prioritized_replay.h:173-348 (PrioritizedReplay<T>) over
@@ -413,6 +421,14 @@ int rela_apex_actor_slide_stacks(rela_apex_actor* a, const uint8_t* restart_host
 int rela_apex_actor_set_screen_input(rela_apex_actor* a, int height, int width);
 void* rela_apex_actor_screen_stage(rela_apex_actor* a);
 int rela_apex_actor_screens_to_stacks(rela_apex_actor* a, const uint8_t* restart_host, void* stream);
+/* Indexed-colour screens (ALEInterface::getScreen, atari/atari_env.h:66-67) instead of RGB ones.
+ * set_screen_input_indexed follows set_screen_input's rule -- once, before the first act -- and excludes it: a shard
+ * takes one format (RELA_ESTATE for the second call of either).  The screen stage is then [rows][2][height][width] u8
+ * palette indices, and palette_stage returns a zero-initialised [rows][256][3] u8 RGB table per row on the device (NULL
+ * with RGB screens or no screen input); the caller fills it once.  screens_to_stacks works as above on whichever format
+ * the shard was set up with (rela_atari_features_indexed).                                                        */
+int rela_apex_actor_set_screen_input_indexed(rela_apex_actor* a, int height, int width);
+void* rela_apex_actor_palette_stage(rela_apex_actor* a);
 /* Device addresses of the CURRENT obs["eps"] f32[rows] and obs["legal_move"] f32[rows][A]; act()
  * snapshots them into the history slot of the step, so a transition's obs side carries the values
  * of time t-n and its next_obs side those of time t (dqn_actor.h:84-90).                      */
@@ -477,6 +493,8 @@ int rela_r2d2_actor_slide_stacks(rela_r2d2_actor* a, const uint8_t* restart_host
 int rela_r2d2_actor_set_screen_input(rela_r2d2_actor* a, int height, int width);        /* as rela_apex_actor_set_screen_input */
 void* rela_r2d2_actor_screen_stage(rela_r2d2_actor* a);                                 /* as rela_apex_actor_screen_stage */
 int rela_r2d2_actor_screens_to_stacks(rela_r2d2_actor* a, const uint8_t* restart_host, void* stream); /* as rela_apex_... */
+int rela_r2d2_actor_set_screen_input_indexed(rela_r2d2_actor* a, int height, int width); /* as rela_apex_actor_set_screen_input_indexed */
+void* rela_r2d2_actor_palette_stage(rela_r2d2_actor* a);                                /* as rela_apex_actor_palette_stage */
 /* R2D2Actor::act  r2d2_actor.h:221-249; arguments as rela_apex_actor_act */
 int rela_r2d2_actor_act(rela_r2d2_actor* a, const rela_lstmnet* online, const uint8_t* obs_host,
                         const float* eps_host, const float* legal_host, int64_t* action_host,

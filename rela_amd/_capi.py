@@ -87,6 +87,7 @@ _sig("rela_stream_synchronize", i32, [vp, i32])
 _sig("rela_stream_wait_stream", i32, [vp, vp, i32])
 _sig("rela_memcpy_h2d_async", i32, [vp, vp, i64, vp, i32])
 _sig("rela_atari_features", i32, [vp, i32, i32, i32, vp, vp])
+_sig("rela_atari_features_indexed", i32, [vp, vp, i32, i32, i32, vp, vp])
 _sig("rela_replay_set_decoupled_insert", i32, [vp, i32])
 _sig("rela_replay_export_ipc", i32, [vp, vp])
 _sig("rela_replay_import_ipc", i32, [P(vp), vp, i32])
@@ -185,6 +186,8 @@ _sig("rela_apex_actor_slide_stacks", i32, [vp, vp, vp])
 _sig("rela_apex_actor_set_screen_input", i32, [vp, i32, i32])
 _sig("rela_apex_actor_screen_stage", vp, [vp])
 _sig("rela_apex_actor_screens_to_stacks", i32, [vp, vp, vp])
+_sig("rela_apex_actor_set_screen_input_indexed", i32, [vp, i32, i32])
+_sig("rela_apex_actor_palette_stage", vp, [vp])
 _sig("rela_apex_actor_eps_dev", vp, [vp])
 _sig("rela_apex_actor_legal_dev", vp, [vp])
 _sig("rela_apex_actor_act", i32, [vp, vp, vp, vp, vp, vp, P(vp), vp])
@@ -202,6 +205,8 @@ _sig("rela_r2d2_actor_slide_stacks", i32, [vp, vp, vp])
 _sig("rela_r2d2_actor_set_screen_input", i32, [vp, i32, i32])
 _sig("rela_r2d2_actor_screen_stage", vp, [vp])
 _sig("rela_r2d2_actor_screens_to_stacks", i32, [vp, vp, vp])
+_sig("rela_r2d2_actor_set_screen_input_indexed", i32, [vp, i32, i32])
+_sig("rela_r2d2_actor_palette_stage", vp, [vp])
 _sig("rela_r2d2_actor_act", i32, [vp, vp, vp, vp, vp, vp, P(vp), vp])
 _sig("rela_r2d2_actor_post_step", i32, [vp, vp, vp, vp, vp, i32, P(i32), vp])
 _sig("rela_r2d2_actor_num_act", i64, [vp])

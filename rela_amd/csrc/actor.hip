@@ -55,7 +55,9 @@ struct rela_apex_actor {
   int64_t tick = 0, key_tick = -1;   // ticks stored so far; tick of the last keyframe (all planes stored)
   uint8_t* restart = nullptr;
   uint8_t* fresh_planes = nullptr;  // [R][7056] staging of the newest plane of every row (rela_apex_actor_plane_stage)        // [R] rela_apex_actor_slide_stacks: 1 = the row's stack restarts with its new plane
-  uint8_t* screens = nullptr;       // [R][2][scr_h][scr_w][3] screen pairs (rela_apex_actor_set_screen_input)
+  uint8_t* screens = nullptr;       // [R][2][scr_h][scr_w][3] screen pairs (rela_apex_actor_set_screen_input), or
+                                    // [R][2][scr_h][scr_w] palette indices (..._set_screen_input_indexed)
+  uint8_t* palettes = nullptr;      // [R][256][3] RGB table of every row: indexed screens only
   uint8_t* screen_prev = nullptr;   // [R][28224] evaluation shard (no replay): copy of the one slot it acts on
   int scr_h = 0, scr_w = 0;
 };
@@ -127,7 +129,7 @@ extern "C" void rela_apex_actor_destroy(rela_apex_actor* a) {
   DeviceGuard g(a->device);
   (void)hipDeviceSynchronize();
   void* ps[] = {a->obs, a->act, a->rew, a->term, a->eps, a->legal, a->q, a->out_r, a->out_b, a->prio, a->out_t, a->ws,
-                a->eps_hist, a->legal_hist, a->ref_hist, a->q_hist, a->restart, a->fresh_planes, a->screens, a->screen_prev};
+                a->eps_hist, a->legal_hist, a->ref_hist, a->q_hist, a->restart, a->fresh_planes, a->screens, a->screen_prev, a->palettes};
   for (void* p : ps) (void)hipFree(p);
   delete a;
 }
@@ -158,27 +160,40 @@ extern "C" int rela_apex_actor_slide_stacks(rela_apex_actor* a, const uint8_t* r
   return slide_stacks(a->obs + (size_t)slot * a->R * kObs, a->obs + (size_t)prev * a->R * kObs, a->fresh_planes, a->restart,
                       a->R, s);
 }
-extern "C" int rela_apex_actor_set_screen_input(rela_apex_actor* a, int height, int width) {
+// channels: 3 = RGB screens, 1 = palette indices (a zeroed palette stage comes with them)
+static int set_screen_input(rela_apex_actor* a, int height, int width, int channels, const char* who) {
   RELA_CHECK(a && height >= 2 && height <= 512 && width >= 2 && width <= 512, RELA_EINVAL,
-             "rela_apex_actor_set_screen_input: bad arguments (screens must be 2..512 x 2..512)");
-  RELA_CHECK(a->act_calls == 0 && !a->screens, RELA_ESTATE, "rela_apex_actor_set_screen_input: call it once, before the first act()");
+             "%s: bad arguments (screens must be 2..512 x 2..512)", who);
+  RELA_CHECK(a->act_calls == 0 && !a->screens, RELA_ESTATE,
+             "%s: call it once, before the first act() (a shard takes RGB or indexed screens, not both)", who);
   DeviceGuard g(a->device);
-  const size_t bytes = (size_t)a->R * 2 * height * width * 3;
+  const size_t bytes = (size_t)a->R * 2 * height * width * channels;
   RELA_HIP(hipMalloc(&a->screens, bytes));
   RELA_HIP(hipMemset(a->screens, 0, bytes));
-  RELA_CHECK(rela_apex_actor_plane_stage(a), RELA_ENOMEM, "rela_apex_actor_set_screen_input: plane stage");
+  if (channels == 1) {
+    RELA_HIP(hipMalloc(&a->palettes, (size_t)a->R * 768));
+    RELA_HIP(hipMemset(a->palettes, 0, (size_t)a->R * 768));
+  }
+  RELA_CHECK(rela_apex_actor_plane_stage(a), RELA_ENOMEM, "%s: plane stage", who);
   if (!a->replay) RELA_HIP(hipMalloc(&a->screen_prev, (size_t)a->R * kObs));
   a->scr_h = height;
   a->scr_w = width;
   return RELA_OK;
 }
+extern "C" int rela_apex_actor_set_screen_input(rela_apex_actor* a, int height, int width) {
+  return set_screen_input(a, height, width, 3, "rela_apex_actor_set_screen_input");
+}
+extern "C" int rela_apex_actor_set_screen_input_indexed(rela_apex_actor* a, int height, int width) {
+  return set_screen_input(a, height, width, 1, "rela_apex_actor_set_screen_input_indexed");
+}
+extern "C" void* rela_apex_actor_palette_stage(rela_apex_actor* a) { return a ? a->palettes : nullptr; }
 extern "C" void* rela_apex_actor_screen_stage(rela_apex_actor* a) { return a ? a->screens : nullptr; }
 extern "C" int rela_apex_actor_screens_to_stacks(rela_apex_actor* a, const uint8_t* restart_host, void* stream_) {
   RELA_CHECK(a, RELA_EINVAL, "rela_apex_actor_screens_to_stacks: bad arguments");
   RELA_CHECK(a->count <= a->n, RELA_ESTATE, "rela_apex_actor_screens_to_stacks: act() twice without post_step()");
   DeviceGuard g(a->device);
   const int slot = next_slot(a), prev = a->q_slot >= 0 ? a->q_slot : slot;  // the stacks of the last act()
-  return screens_to_stacks(a->screens, a->scr_h, a->scr_w, a->fresh_planes, &a->restart, restart_host, a->act_calls == 0,
+  return screens_to_stacks(a->screens, a->palettes, a->scr_h, a->scr_w, a->fresh_planes, &a->restart, restart_host, a->act_calls == 0,
                            a->obs + (size_t)slot * a->R * kObs, a->obs + (size_t)prev * a->R * kObs, a->screen_prev, a->R,
                            (hipStream_t)stream_, "rela_apex_actor_screens_to_stacks");
 }

@@ -239,7 +239,9 @@ struct rela_r2d2_actor {
   uint8_t* d_flags = nullptr;
   uint8_t* restart = nullptr;
   uint8_t* fresh_planes = nullptr;  // [R][7056] staging of the newest plane of every row (rela_r2d2_actor_plane_stage)  // [R] rela_r2d2_actor_slide_stacks
-  uint8_t* screens = nullptr;       // [R][2][scr_h][scr_w][3] screen pairs (rela_r2d2_actor_set_screen_input)
+  uint8_t* screens = nullptr;       // [R][2][scr_h][scr_w][3] screen pairs (rela_r2d2_actor_set_screen_input), or
+                                    // [R][2][scr_h][scr_w] palette indices (..._set_screen_input_indexed)
+  uint8_t* palettes = nullptr;      // [R][256][3] RGB table of every row: indexed screens only
   uint8_t* screen_prev = nullptr;   // [R][28224] evaluation shard (no replay): copy of the one slot it acts on
   int scr_h = 0, scr_w = 0;
   void* ws = nullptr;
@@ -379,7 +381,7 @@ extern "C" void rela_r2d2_actor_destroy(rela_r2d2_actor* a) {
                 a->w.eps, a->w.legal, a->w.a,   a->w.reward,  a->w.term, a->w.boot, a->w.prio, a->w.h0,   a->w.c0,
                 a->w.nh0, a->w.nc0,  a->prow,   a->lens,      a->agg,    a->d_slot, a->d_flags, a->d_ranges, a->d_emits, a->d_gather,
                 a->d_envs, a->ws, a->q_hist, a->restart, a->fresh_planes, a->ref_hist, a->w.sref, a->agg_kept, a->d_kept,
-                a->screens, a->screen_prev};
+                a->screens, a->screen_prev, a->palettes};
   for (void* p : ps) (void)hipFree(p);
   a->stage.destroy();
   delete a->book;
@@ -412,27 +414,40 @@ extern "C" int rela_r2d2_actor_slide_stacks(rela_r2d2_actor* a, const uint8_t* r
   return slide_stacks(a->obs + (size_t)slot * a->R * kObs, a->obs + (size_t)prev * a->R * kObs, a->fresh_planes, a->restart,
                       a->R, s);
 }
-extern "C" int rela_r2d2_actor_set_screen_input(rela_r2d2_actor* a, int height, int width) {
+// channels: 3 = RGB screens, 1 = palette indices (a zeroed palette stage comes with them)
+static int set_screen_input(rela_r2d2_actor* a, int height, int width, int channels, const char* who) {
   RELA_CHECK(a && height >= 2 && height <= 512 && width >= 2 && width <= 512, RELA_EINVAL,
-             "rela_r2d2_actor_set_screen_input: bad arguments (screens must be 2..512 x 2..512)");
-  RELA_CHECK(a->act_calls == 0 && !a->screens, RELA_ESTATE, "rela_r2d2_actor_set_screen_input: call it once, before the first act()");
+             "%s: bad arguments (screens must be 2..512 x 2..512)", who);
+  RELA_CHECK(a->act_calls == 0 && !a->screens, RELA_ESTATE,
+             "%s: call it once, before the first act() (a shard takes RGB or indexed screens, not both)", who);
   DeviceGuard g(a->device);
-  const size_t bytes = (size_t)a->R * 2 * height * width * 3;
+  const size_t bytes = (size_t)a->R * 2 * height * width * channels;
   RELA_HIP(hipMalloc(&a->screens, bytes));
   RELA_HIP(hipMemset(a->screens, 0, bytes));
-  RELA_CHECK(rela_r2d2_actor_plane_stage(a), RELA_ENOMEM, "rela_r2d2_actor_set_screen_input: plane stage");
+  if (channels == 1) {
+    RELA_HIP(hipMalloc(&a->palettes, (size_t)a->R * 768));
+    RELA_HIP(hipMemset(a->palettes, 0, (size_t)a->R * 768));
+  }
+  RELA_CHECK(rela_r2d2_actor_plane_stage(a), RELA_ENOMEM, "%s: plane stage", who);
   if (!a->replay) RELA_HIP(hipMalloc(&a->screen_prev, (size_t)a->R * kObs));
   a->scr_h = height;
   a->scr_w = width;
   return RELA_OK;
 }
+extern "C" int rela_r2d2_actor_set_screen_input(rela_r2d2_actor* a, int height, int width) {
+  return set_screen_input(a, height, width, 3, "rela_r2d2_actor_set_screen_input");
+}
+extern "C" int rela_r2d2_actor_set_screen_input_indexed(rela_r2d2_actor* a, int height, int width) {
+  return set_screen_input(a, height, width, 1, "rela_r2d2_actor_set_screen_input_indexed");
+}
+extern "C" void* rela_r2d2_actor_palette_stage(rela_r2d2_actor* a) { return a ? a->palettes : nullptr; }
 extern "C" void* rela_r2d2_actor_screen_stage(rela_r2d2_actor* a) { return a ? a->screens : nullptr; }
 extern "C" int rela_r2d2_actor_screens_to_stacks(rela_r2d2_actor* a, const uint8_t* restart_host, void* stream_) {
   RELA_CHECK(a, RELA_EINVAL, "rela_r2d2_actor_screens_to_stacks: bad arguments");
   RELA_CHECK(a->count <= a->n, RELA_ESTATE, "rela_r2d2_actor_screens_to_stacks: act() twice without post_step()");
   DeviceGuard g(a->device);
   const int slot = next_slot(a), prev = a->q_slot >= 0 ? a->q_slot : slot;  // the stacks of the last act()
-  return screens_to_stacks(a->screens, a->scr_h, a->scr_w, a->fresh_planes, &a->restart, restart_host, a->act_calls == 0,
+  return screens_to_stacks(a->screens, a->palettes, a->scr_h, a->scr_w, a->fresh_planes, &a->restart, restart_host, a->act_calls == 0,
                            a->obs + (size_t)slot * a->R * kObs, a->obs + (size_t)prev * a->R * kObs, a->screen_prev, a->R,
                            (hipStream_t)stream_, "rela_r2d2_actor_screens_to_stacks");
 }

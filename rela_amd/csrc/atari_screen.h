@@ -7,6 +7,7 @@
 //   g      = (0.21 R + 0.72 G) + 0.07 B;  out = (uint8_t)(g * 255)    (truncated)
 // This is ATen's CPU upsample_bilinear2d formula; the reference's torch ops may order or contract differently per
 // build, so against torch the result is within 1 per pixel, not bit-identical.  No FMA contraction anywhere.
+// Indexed-colour screens (one palette index per pixel) enter the same recipe after the lookup: see indexed_max_pixel.
 // Plain C++ apart from the HIP qualifiers: g++ compiles it for the host restatement.
 #pragma once
 #include <stdint.h>
@@ -91,6 +92,40 @@ inline void host_features(const uint8_t* a, const uint8_t* b, int height, int wi
       const uint8_t* pa = a + (int64_t)src[k] * rb;
       const uint8_t* pb = b + (int64_t)src[k] * rb;
       for (int i = 0; i < rb; ++i) m[k][i] = pa[i] > pb[i] ? pa[i] : pb[i];
+    }
+    for (int x = 0; x < kOut; ++x)
+      out[y * kOut + x] = feature_pixel(t.v, m[0], m[1], t.w.i0[x], t.w.i1[x], t.w.l0[x], t.w.l1[x], t.h.l0[y], t.h.l1[y]);
+  }
+}
+
+// Indexed-colour screens (ALEInterface::getScreen: one palette index per pixel): the frame computeFeature sees is, per
+// channel, max(pal[ia][c], pal[ib][c]) -- the max is taken AFTER the lookup, as getScreenRGB followed by the recipe above
+// does, so the features equal those of the expanded screens bit for bit.  All 256 indices are valid.
+// One pixel of the max image: three bytes at dst from the indices ia / ib and pal = [256][3] u8 RGB.
+RELA_ATARI_HD inline void indexed_max_pixel(const uint8_t* pal, uint8_t ia, uint8_t ib, uint8_t* dst) {
+  for (int c = 0; c < 3; ++c) {
+    const uint8_t a = pal[3 * ia + c], b = pal[3 * ib + c];
+    dst[c] = a > b ? a : b;
+  }
+}
+
+// Host restatement: ia, ib = [height][width] u8 indices (current, previous screen); pal = [256][3] u8; out = [84][84] u8.
+inline void host_features_indexed(const uint8_t* ia, const uint8_t* ib, const uint8_t* pal, int height, int width,
+                                  uint8_t* out) {
+  static thread_local Tables t;
+  static thread_local int th = 0, tw = 0;
+  if (th != height || tw != width) {
+    make_tables(t, height, width);
+    th = height;
+    tw = width;
+  }
+  static thread_local uint8_t m[2][kMaxIn * 3];
+  for (int y = 0; y < kOut; ++y) {
+    const int src[2] = {t.h.i0[y], t.h.i1[y]};
+    for (int k = 0; k < 2; ++k) {
+      const uint8_t* pa = ia + (int64_t)src[k] * width;
+      const uint8_t* pb = ib + (int64_t)src[k] * width;
+      for (int i = 0; i < width; ++i) indexed_max_pixel(pal, pa[i], pb[i], &m[k][3 * i]);
     }
     for (int x = 0; x < kOut; ++x)
       out[y * kOut + x] = feature_pixel(t.v, m[0], m[1], t.w.i0[x], t.w.i1[x], t.w.l0[x], t.w.l1[x], t.h.l0[y], t.h.l1[y]);

@@ -140,9 +140,12 @@ int slide_stacks(uint8_t* cur_slot, const uint8_t* prev_slot, const uint8_t* fre
 
 // atari_screen.hip: 84x84 features of staged screen pairs, and the shards' screens_to_stacks (features into
 // fresh_planes, then slide_stacks with the host restart flags; `first`: the shard's first act, every row must restart;
-// prev_slot: the slot of the last act -- the same as cur_slot for an evaluation shard, which then slides from prev_copy)
+// prev_slot: the slot of the last act -- the same as cur_slot for an evaluation shard, which then slides from prev_copy;
+// palettes: null = RGB screens [rows][2][H][W][3], else [rows][256][3] and the screens are indices [rows][2][H][W])
 int atari_features(const uint8_t* screens, int rows, int height, int width, uint8_t* planes, hipStream_t s);
-int screens_to_stacks(const uint8_t* screens, int height, int width, uint8_t* fresh_planes, uint8_t** restart_dev,
+int atari_features_indexed(const uint8_t* screens, const uint8_t* palettes, int rows, int height, int width, uint8_t* planes,
+                           hipStream_t s);
+int screens_to_stacks(const uint8_t* screens, const uint8_t* palettes, int height, int width, uint8_t* fresh_planes, uint8_t** restart_dev,
                       const uint8_t* restart_host, bool first, uint8_t* cur_slot, const uint8_t* prev_slot,
                       uint8_t* prev_copy, int rows, hipStream_t s, const char* who);
 

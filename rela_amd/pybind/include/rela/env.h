@@ -72,6 +72,7 @@ class VectorEnv {
   std::vector<FrameRowEnv*> frameEnvs_;  // envs_[i]'s optional extension (nullptr: copying path)
   std::vector<ScreenEnv*> screenEnvs_;   // envs_[i]'s raw-screen extension (nullptr: none)
   bool screen_ = false;                  // every env is a ScreenEnv: the batch carries "__screens"
+  bool screenIndexed_ = false;           // ... of palette indices: the batch carries "__palette" too
   TensorDict batch_;                     // persistent, page-locked when a GPU is present
   std::vector<KeyRows> rows_;            // raw row addresses of batch_'s tensors
   bool sliding_ = false;                 // every env declared a sliding stack

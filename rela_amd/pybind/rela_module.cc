@@ -60,6 +60,7 @@ void* torchCurrentStream(int device) {
 }
 
 constexpr int64_t kObsBytes = 4 * 84 * 84;
+constexpr int64_t kPaletteBytes = 256 * 3;  // one row's RGB table (indexed screens, rela/screen_env.h)
 
 // RELA_THREADED_STATS=1: where the actor threads' wall time goes (summed over threads, printed when the Context dies):
 // the drop-in's throughput is bound by host work per env-step, which no GPU profiler sees.
@@ -134,12 +135,14 @@ void VectorEnv::append(std::shared_ptr<Env> env) {
   envs_.push_back(std::move(env));
 }
 
-// screen mode (rela/screen_env.h) needs every env to be a ScreenEnv of one shape and none to be a FrameRowEnv as well
+// screen mode (rela/screen_env.h) needs every env to be a ScreenEnv of one shape and one format (RGB or palette indices)
+// and none to be a FrameRowEnv as well
 void VectorEnv::checkScreenMode() {
   int n = 0;
+  size_t first = 0;  // the first screen env
   for (size_t i = 0; i < envs_.size(); ++i) {
     if (!screenEnvs_[i]) continue;
-    ++n;
+    if (n++ == 0) first = i;
     if (frameEnvs_[i])
       throw std::runtime_error("VectorEnv: env " + std::to_string(i) +
                                " is both a ScreenEnv and a FrameRowEnv; an env hands over raw screens or finished planes, not both");
@@ -149,12 +152,21 @@ void VectorEnv::checkScreenMode() {
                                std::to_string(screenEnvs_[0]->screenHeight()) + "x" + std::to_string(screenEnvs_[0]->screenWidth()) +
                                ", env " + std::to_string(i) + ": " + std::to_string(screenEnvs_[i]->screenHeight()) + "x" +
                                std::to_string(screenEnvs_[i]->screenWidth()) + ")");
+    const int ch = screenEnvs_[i]->screenChannels();
+    if (ch != 1 && ch != 3)
+      throw std::runtime_error("VectorEnv: env " + std::to_string(i) + " has screens of " + std::to_string(ch) +
+                               " channels; a ScreenEnv renders 3 (RGB) or 1 (palette indices)");
+    if (ch != screenEnvs_[first]->screenChannels())
+      throw std::runtime_error("VectorEnv: screen envs of different formats (env " + std::to_string(first) + ": " +
+                               std::to_string(screenEnvs_[first]->screenChannels()) + " channels, env " + std::to_string(i) + ": " +
+                               std::to_string(ch) + "); a VectorEnv holds RGB screen envs or indexed ones, not both");
   }
   if (n > 0 && n != (int)envs_.size())
     throw std::runtime_error("VectorEnv: " + std::to_string(n) + " of " + std::to_string(envs_.size()) +
                              " envs are ScreenEnvs; a VectorEnv holds only screen envs or none (their observations are "
                              "built on the device from raw screens, the others' on the host)");
   screen_ = n > 0;
+  screenIndexed_ = screen_ && screenEnvs_[first]->screenChannels() == 1;
 }
 
 // Allocates the persistent batch (one page-locked tensor per observation key, shaped [K, ...] like the first
@@ -176,8 +188,9 @@ void VectorEnv::createBatch(const TensorDict& firstObs) {
   }
   if (screen_) {  // raw screens: "__screens" + "__stack_restart"; the actors build the stacks on the device
     const int64_t H = screenEnvs_[0]->screenHeight(), W = screenEnvs_[0]->screenWidth();
-    auto scr = pin(torch::zeros({K, 2, H, W, 3}, torch::kUInt8));
+    auto scr = pin(screenIndexed_ ? torch::zeros({K, 2, H, W}, torch::kUInt8) : torch::zeros({K, 2, H, W, 3}, torch::kUInt8));
     batch_.emplace("__screens", scr);
+    if (screenIndexed_) batch_.emplace("__palette", pin(torch::zeros({K, 256, 3}, torch::kUInt8)));  // filled at bind time
     auto flags = pin(torch::ones({K}, torch::kUInt8));
     restart_ = flags.data_ptr<uint8_t>();
     batch_.emplace("__stack_restart", flags);
@@ -230,6 +243,16 @@ TensorDict VectorEnv::reset(const TensorDict& previous) {
     const auto& scr = batch_.at("__screens");
     const int64_t rb = envs_.empty() ? 0 : (int64_t)scr.nbytes() / (int64_t)envs_.size();
     for (size_t i = 0; i < envs_.size(); ++i) screenEnvs_[i]->bindScreenRow(static_cast<uint8_t*>(scr.data_ptr()) + (int64_t)i * rb);
+    if (screenIndexed_) {  // the rows' RGB tables, read once: they are fixed from the env's first reset() on
+      uint8_t* pal = static_cast<uint8_t*>(batch_.at("__palette").data_ptr());
+      for (size_t i = 0; i < envs_.size(); ++i) {
+        const uint8_t* p = screenEnvs_[i]->screenPalette();
+        if (!p)
+          throw std::runtime_error("VectorEnv: env " + std::to_string(i) +
+                                   " renders palette indices (screenChannels() == 1) but has no palette (screenPalette() is null)");
+        std::memcpy(pal + (int64_t)i * kPaletteBytes, p, (size_t)kPaletteBytes);
+      }
+    }
   }
   if (first) {  // the rows hold every env's first observation: envs that can, render into them from now on
     for (const auto& r : rows_)
@@ -1114,9 +1137,12 @@ class ActorCohort {
     {
       std::unique_lock<std::mutex> lk(m_);
       if (draining_) return drained();
-      if (!created_) create(A, screens ? &obs.at("__screens") : nullptr);
+      const bool indexed = screens && obs.count("__palette") != 0;  // palette indices, not RGB (rela/screen_env.h)
+      if (!created_) create(A, screens ? &obs.at("__screens") : nullptr, indexed);
       if (screens != (screenBytes_ > 0))
         throw std::runtime_error("ActorCohort: the VectorEnvs of one cohort must all hold screen envs or none");
+      if (indexed != (paletteStage_ != nullptr))
+        throw std::runtime_error("ActorCohort: the VectorEnvs of one cohort must all hold RGB screen envs or all indexed ones");
       // (the slot moves only inside the leader's work, which every member of the round has left by now)
       slot = lstm_ ? rela_r2d2_actor_obs_slot(hr_) : rela_apex_actor_obs_slot(h_);
       // a VectorEnv whose envs all slide their frame stack marks its batch (rela/env.h): only plane 3 of every row is
@@ -1135,6 +1161,15 @@ class ActorCohort {
       const auto& scr = obs.at("__screens");
       if (scr.size(0) != K_ || (int64_t)scr.nbytes() != (int64_t)K_ * screenBytes_ || !scr.is_contiguous())
         throw std::runtime_error("ActorCohort: obs['__screens'] does not match the screen shape of the cohort");
+      if (paletteStage_ && !paletteSent_[member]) {  // this member's rows' tables: once, they do not change
+        const auto& pal = obs.at("__palette");
+        if ((int64_t)pal.nbytes() != (int64_t)K_ * kPaletteBytes || pal.dtype() != torch::kUInt8 || !pal.is_contiguous())
+          throw std::runtime_error("ActorCohort: obs['__palette'] must be contiguous uint8 [batchsize,256,3]");
+        check(rela_memcpy_h2d_async(static_cast<uint8_t*>(paletteStage_) + (int64_t)member * K_ * kPaletteBytes, pal.data_ptr(),
+                                    (int64_t)K_ * kPaletteBytes, upload_, dev),
+              "rela_memcpy_h2d_async");
+        paletteSent_[member] = 1;
+      }
       check(rela_memcpy_h2d_async(static_cast<uint8_t*>(screenStage_) + (int64_t)member * K_ * screenBytes_, scr.data_ptr(),
                                   (int64_t)K_ * screenBytes_, upload_, dev),
             "rela_memcpy_h2d_async");
@@ -1274,8 +1309,9 @@ class ActorCohort {
 
   TensorDict drained() { return TensorDict{{"a", torch::zeros({K_}, torch::kInt64)}}; }
 
-  // screens: the first member's obs["__screens"] ([K][2][H][W][3]) when its VectorEnv holds screen envs
-  void create(int A, const torch::Tensor* screens) {
+  // screens: the first member's obs["__screens"] ([K][2][H][W][3], indexed: [K][2][H][W]) when its VectorEnv holds
+  // screen envs
+  void create(int A, const torch::Tensor* screens, bool indexed) {
     if (locker_->kind() != (lstm_ ? ModelLocker::kLSTM : ModelLocker::kFF))
       throw std::runtime_error(lstm_ ? "R2D2Actor needs an AtariLSTMNet-shaped agent in its ModelLocker"
                                      : "DQNActor needs an AtariFFNet-shaped agent in its ModelLocker");
@@ -1312,10 +1348,18 @@ class ActorCohort {
     if (!planeStage_) throw std::runtime_error("ActorCohort: could not allocate the plane stage");
     if (screens) {
       const int H = (int)screens->size(2), W = (int)screens->size(3);
-      check(lstm_ ? rela_r2d2_actor_set_screen_input(hr_, H, W) : rela_apex_actor_set_screen_input(h_, H, W),
-            "set_screen_input");
+      if (indexed)
+        check(lstm_ ? rela_r2d2_actor_set_screen_input_indexed(hr_, H, W) : rela_apex_actor_set_screen_input_indexed(h_, H, W),
+              "set_screen_input_indexed");
+      else
+        check(lstm_ ? rela_r2d2_actor_set_screen_input(hr_, H, W) : rela_apex_actor_set_screen_input(h_, H, W),
+              "set_screen_input");
       screenStage_ = lstm_ ? rela_r2d2_actor_screen_stage(hr_) : rela_apex_actor_screen_stage(h_);
-      screenBytes_ = (int64_t)2 * H * W * 3;
+      screenBytes_ = (int64_t)2 * H * W * (indexed ? 1 : 3);
+      if (indexed) {
+        paletteStage_ = lstm_ ? rela_r2d2_actor_palette_stage(hr_) : rela_apex_actor_palette_stage(h_);
+        paletteSent_.assign(T_, 0);
+      }
     }
     keepObs_.resize(T_);
     // RELA_PLANE_UPLOAD=0: always upload whole frame stacks (A/B switch of the sliding-stack path)
@@ -1337,8 +1381,10 @@ class ActorCohort {
   void *compute_ = nullptr, *upload_ = nullptr;
   torch::Tensor actionAll_, epsAll_, legalAll_, rewardAll_, terminalAll_, restartAll_, planeHost_;
   void* planeStage_ = nullptr;  // device [R][7056]: the newest plane of every row
-  void* screenStage_ = nullptr;  // device [R][2][H][W][3]: every row's screen pair (screen mode)
-  int64_t screenBytes_ = 0;      // 2*H*W*3 in screen mode, 0 otherwise
+  void* screenStage_ = nullptr;  // device [R][2][H][W][3]: every row's screen pair (screen mode; indexed: [R][2][H][W])
+  int64_t screenBytes_ = 0;      // 2*H*W*3 (indexed: 2*H*W) in screen mode, 0 otherwise
+  void* paletteStage_ = nullptr;      // device [R][256][3]: every row's RGB table (indexed screens only)
+  std::vector<uint8_t> paletteSent_;  // [T] the member's tables are on the device (each member writes its own entry)
   std::vector<torch::Tensor> keepObs_;
   std::vector<std::atomic<int64_t>> numAct_;
   bool constsValid_ = false, constsDirty_ = false, draining_ = false;
@@ -1352,18 +1398,35 @@ class ActorCohort {
 // The screen path of an actor's private shard (a VectorEnv of screen envs, rela/screen_env.h): on the first act the shard
 // gets its screen stage, then every act makes ONE copy of obs["__screens"] into it and the shard writes the frame stacks
 // of its observation slot on the device.  `restart` is this actor's page-locked copy of the flags.
+// With obs["__palette"] the screens are palette indices: the indexed set-up, and the rows' tables go up with the first act.
 template <class Shard>
 void privateScreensToStacks(Shard* h, const TensorDict& obs, int rows, int device, void* stream, torch::Tensor& restart,
-                            int (*setInput)(Shard*, int, int), void* (*stage)(Shard*),
+                            int (*setInput)(Shard*, int, int), int (*setInputIndexed)(Shard*, int, int),
+                            void* (*stage)(Shard*), void* (*paletteStage)(Shard*),
                             int (*toStacks)(Shard*, const uint8_t*, void*)) {
   const auto& scr = obs.at("__screens");
-  if (scr.dim() != 5 || scr.size(0) != rows || scr.size(1) != 2 || scr.size(4) != 3 || scr.dtype() != torch::kUInt8 ||
-      !scr.is_contiguous())
+  const auto pal = obs.find("__palette");
+  const bool indexed = pal != obs.end();
+  if (indexed) {
+    if (scr.dim() != 4 || scr.size(0) != rows || scr.size(1) != 2 || scr.dtype() != torch::kUInt8 || !scr.is_contiguous())
+      throw std::runtime_error("act: obs['__screens'] must be contiguous uint8 [batchsize,2,H,W] next to obs['__palette']");
+    if ((int64_t)pal->second.nbytes() != (int64_t)rows * kPaletteBytes || pal->second.dtype() != torch::kUInt8 ||
+        !pal->second.is_contiguous())
+      throw std::runtime_error("act: obs['__palette'] must be contiguous uint8 [batchsize,256,3]");
+  } else if (scr.dim() != 5 || scr.size(0) != rows || scr.size(1) != 2 || scr.size(4) != 3 || scr.dtype() != torch::kUInt8 ||
+             !scr.is_contiguous()) {
     throw std::runtime_error("act: obs['__screens'] must be contiguous uint8 [batchsize,2,H,W,3]");
+  }
   if (!restart.defined()) {
-    check(setInput(h, (int)scr.size(2), (int)scr.size(3)), "set_screen_input");
+    check((indexed ? setInputIndexed : setInput)(h, (int)scr.size(2), (int)scr.size(3)),
+          indexed ? "set_screen_input_indexed" : "set_screen_input");
+    if (indexed)
+      check(rela_memcpy_h2d_async(paletteStage(h), pal->second.data_ptr(), (int64_t)rows * kPaletteBytes, stream, device),
+            "rela_memcpy_h2d_async");
     restart = torch::zeros({rows}, torch::kUInt8);
     if (torch::cuda::is_available()) restart = restart.pin_memory();
+  } else if (indexed != (paletteStage(h) != nullptr)) {
+    throw std::runtime_error("act: the screen format (RGB or indexed) changed after the first act");
   }
   check(rela_memcpy_h2d_async(stage(h), scr.data_ptr(), (int64_t)scr.nbytes(), stream, device), "rela_memcpy_h2d_async");
   std::memcpy(restart.data_ptr<uint8_t>(), obs.at("__stack_restart").data_ptr<uint8_t>(), (size_t)rows);
@@ -1454,7 +1517,8 @@ class DQNActor : public Actor {
     const uint8_t* obsHost = sc.data_ptr<uint8_t>();
     if (obs.count("__screens")) {  // the stacks are built on the device from the screens
       privateScreensToStacks(h_, obs, batchsize_, locker_->execDevice, stream_, screenRestart_, rela_apex_actor_set_screen_input,
-                             rela_apex_actor_screen_stage, rela_apex_actor_screens_to_stacks);
+                             rela_apex_actor_set_screen_input_indexed, rela_apex_actor_screen_stage, rela_apex_actor_palette_stage,
+                             rela_apex_actor_screens_to_stacks);
       obsHost = nullptr;
     }
     auto lease = locker_->getModel();
@@ -1590,7 +1654,8 @@ class R2D2Actor : public Actor {
     const uint8_t* obsHost = sc.data_ptr<uint8_t>();
     if (obs.count("__screens")) {  // the stacks are built on the device from the screens
       privateScreensToStacks(h_, obs, batchsize_, locker_->execDevice, stream_, screenRestart_, rela_r2d2_actor_set_screen_input,
-                             rela_r2d2_actor_screen_stage, rela_r2d2_actor_screens_to_stacks);
+                             rela_r2d2_actor_set_screen_input_indexed, rela_r2d2_actor_screen_stage, rela_r2d2_actor_palette_stage,
+                             rela_r2d2_actor_screens_to_stacks);
       obsHost = nullptr;
     }
     auto lease = locker_->getModel();

@@ -197,18 +197,28 @@ class NullAtariEnv : public rela::Env RELA_FRAME_ROW_BASE {
 // computes it on the host with the restatement of csrc/atari_screen.h, four-plane deque included (device_features =
 // False: a plain rela::Env, the reference's method); SyntheticScreenEnvDevice below hands the pair to the VectorEnv
 // instead and the actor shard computes the same stacks on the GPU (rela/screen_env.h).
+// indexed = true: the same picture as ALE's own screen format (ALEInterface::getScreen), one palette index per pixel --
+// index k < 8 is pal_[k], index 8 + k the sprite colour 255 - pal_[k], every other entry of the 256-entry table is 0 -- so
+// the expanded screens equal the RGB env's byte for byte, and rewards, terminals and the LCG stream are the same.
 class SyntheticScreenEnv : public rela::Env {
  public:
-  static constexpr int kH = 210, kW = 160, kScreen = kH * kW * 3, kBlock = 10;
+  static constexpr int kH = 210, kW = 160, kBlock = 10;
 
-  SyntheticScreenEnv(int seed, float eps, int numAction, int episodeLen)
-      : state_((uint32_t)seed * 2246822519u + 374761393u), numAction_(numAction), episodeLen_(episodeLen),
-        own_(2 * (size_t)kScreen), pair_(own_.data()), bg_((size_t)kScreen) {
+  SyntheticScreenEnv(int seed, float eps, int numAction, int episodeLen, bool indexed = false)
+      : state_((uint32_t)seed * 2246822519u + 374761393u), numAction_(numAction), episodeLen_(episodeLen), indexed_(indexed),
+        ch_(indexed ? 1 : 3), screenBytes_(kH * kW * (indexed ? 1 : 3)), own_(2 * (size_t)screenBytes_), pair_(own_.data()),
+        bg_((size_t)screenBytes_) {
     eps_ = torch::full({1}, eps, torch::kFloat32);
     legal_ = torch::ones({numAction}, torch::kFloat32);
     frame_ = torch::zeros({4, 84, 84}, torch::kUInt8);
     for (int k = 0; k < 8; ++k)
       for (int c = 0; c < 3; ++c) pal_[k][c] = (uint8_t)(next() >> 24);
+    std::memset(table_, 0, sizeof(table_));
+    for (int k = 0; k < 8; ++k)
+      for (int c = 0; c < 3; ++c) {
+        table_[k][c] = pal_[k][c];
+        table_[8 + k][c] = (uint8_t)(255 - pal_[k][c]);
+      }
     for (int by = 0; by < kH / kBlock; ++by)
       for (int bx = 0; bx < kW / kBlock; ++bx) fillBlock(bg_.data(), by, bx, (int)(next() >> 29));
   }
@@ -223,7 +233,7 @@ class SyntheticScreenEnv : public rela::Env {
     episodeReward_ = 0.f;
     sy_ = (int)((next() >> 24) % (kH - 12));
     sx_ = (int)((next() >> 24) % (kW - 16));
-    render(pair_ + kScreen);  // the screen before the first one
+    render(pair_ + screenBytes_);  // the screen before the first one
     render(pair_);
     pushFeature(true);
     return observation();
@@ -237,7 +247,7 @@ class SyntheticScreenEnv : public rela::Env {
     if (a < 0 || a >= numAction_) throw std::out_of_range("SyntheticScreenEnv: action out of range");
     sx_ = std::min(std::max(sx_ + 4 * ((int)(a % 3) - 1), 0), kW - 16);
     sy_ = std::min(std::max(sy_ + 4 * ((int)((a / 3) % 3) - 1), 0), kH - 12);
-    std::memcpy(pair_ + kScreen, pair_, kScreen);  // the current screen becomes the previous one
+    std::memcpy(pair_ + screenBytes_, pair_, screenBytes_);  // the current screen becomes the previous one
     render(pair_);
     pushFeature(false);
     const uint32_t x = next();
@@ -251,49 +261,70 @@ class SyntheticScreenEnv : public rela::Env {
 
   bool terminated() const final { return terminal_; }
 
-  // the current pair, [2][210][160][3] (tests)
-  torch::Tensor screens() const { return torch::from_blob(pair_, {2, kH, kW, 3}, torch::kUInt8).clone(); }
+  // the current pair in the env's own format, [2][210][160][3] or, indexed, [2][210][160] (tests)
+  torch::Tensor screens() const {
+    if (indexed_) return torch::from_blob(pair_, {2, kH, kW}, torch::kUInt8).clone();
+    return torch::from_blob(pair_, {2, kH, kW, 3}, torch::kUInt8).clone();
+  }
+  // the 256-entry RGB table of the indexed format, [256][3] (all the colours the RGB format draws with, too)
+  torch::Tensor palette() const { return torch::from_blob((void*)&table_[0][0], {256, 3}, torch::kUInt8).clone(); }
 
  protected:
   virtual void pushFeature(bool episodeStart) {  // computeFeature's deque, on the host
     constexpr int kPlane = 84 * 84;
     uint8_t* p = frame_.data_ptr<uint8_t>();
     if (!episodeStart) std::memmove(p, p + kPlane, 3 * kPlane);
-    rela_atari::host_features(pair_, pair_ + kScreen, kH, kW, p + 3 * kPlane);
+    if (indexed_) {  // what getScreenRGB does: expand through the table, then the RGB recipe
+      rgb_.resize(2 * (size_t)kH * kW * 3);
+      for (size_t i = 0; i < 2 * (size_t)screenBytes_; ++i) std::memcpy(&rgb_[3 * i], table_[pair_[i]], 3);
+      rela_atari::host_features(rgb_.data(), rgb_.data() + (size_t)kH * kW * 3, kH, kW, p + 3 * kPlane);
+    } else {
+      rela_atari::host_features(pair_, pair_ + screenBytes_, kH, kW, p + 3 * kPlane);
+    }
     if (episodeStart)
       for (int k = 0; k < 3; ++k) std::memcpy(p + k * kPlane, p + 3 * kPlane, kPlane);
   }
 
   uint32_t state_;
   const int numAction_, episodeLen_;
+  const bool indexed_;
+  const int ch_;      // bytes per pixel: 3 (RGB) or 1 (palette index)
+  const int screenBytes_;  // bytes per screen
   std::vector<uint8_t> own_;
-  uint8_t* pair_;  // [2][kH][kW][3]: own_, or the VectorEnv's row once bound
+  uint8_t* pair_;  // [2][kH][kW][ch_]: own_, or the VectorEnv's row once bound
   torch::Tensor eps_, legal_, frame_;
+  uint8_t table_[256][3];  // the indexed format's RGB table
 
  private:
   uint32_t next() {
     state_ = state_ * 1664525u + 1013904223u;
     return state_;
   }
+  // one pixel in table colour `index` (0..15), as RGB or as the index
+  void put(uint8_t* scr, int y, int x, int index) {
+    if (indexed_) {
+      scr[y * kW + x] = (uint8_t)index;
+      return;
+    }
+    for (int c = 0; c < 3; ++c) scr[(y * kW + x) * 3 + c] = table_[index][c];
+  }
   void fillBlock(uint8_t* scr, int by, int bx, int colour) {
     for (int y = by * kBlock; y < (by + 1) * kBlock; ++y)
-      for (int x = bx * kBlock; x < (bx + 1) * kBlock; ++x)
-        for (int c = 0; c < 3; ++c) scr[(y * kW + x) * 3 + c] = pal_[colour][c];
+      for (int x = bx * kBlock; x < (bx + 1) * kBlock; ++x) put(scr, y, x, colour);
   }
   void render(uint8_t* scr) {
-    std::memcpy(scr, bg_.data(), kScreen);
+    std::memcpy(scr, bg_.data(), screenBytes_);
     for (int k = 0; k < 6; ++k) {
       const uint32_t r = next();
       fillBlock(scr, (int)((r >> 8) % (kH / kBlock)), (int)((r >> 16) % (kW / kBlock)), (int)(r >> 29));
     }
-    const uint8_t* col = pal_[(steps_ + 3) & 7];
+    const int col = 8 + ((steps_ + 3) & 7);  // the sprite: 255 - pal_[...]
     for (int y = sy_; y < sy_ + 12; ++y)
-      for (int x = sx_; x < sx_ + 16; ++x)
-        for (int c = 0; c < 3; ++c) scr[(y * kW + x) * 3 + c] = (uint8_t)(255 - col[c]);
+      for (int x = sx_; x < sx_ + 16; ++x) put(scr, y, x, col);
   }
   rela::TensorDict observation() const { return {{"s", frame_}, {"eps", eps_}, {"legal_move", legal_}}; }
 
-  std::vector<uint8_t> bg_;
+  std::vector<uint8_t> bg_, rgb_;
   uint8_t pal_[8][3];
   int steps_ = 0, sy_ = 0, sx_ = 0;
   bool terminal_ = true;
@@ -306,11 +337,13 @@ class SyntheticScreenEnvDevice : public SyntheticScreenEnv, public rela::ScreenE
  public:
   using SyntheticScreenEnv::SyntheticScreenEnv;
   void bindScreenRow(uint8_t* row) final {
-    std::memcpy(row, pair_, 2 * (size_t)kScreen);
+    std::memcpy(row, pair_, 2 * (size_t)screenBytes_);
     pair_ = row;
   }
   int screenHeight() const final { return kH; }
   int screenWidth() const final { return kW; }
+  int screenChannels() const final { return ch_; }
+  const uint8_t* screenPalette() const final { return indexed_ ? &table_[0][0] : nullptr; }
 
  protected:
   void pushFeature(bool) final {}
@@ -318,6 +351,24 @@ class SyntheticScreenEnvDevice : public SyntheticScreenEnv, public rela::ScreenE
 
 // synth_atari.screen_features(a, b): the host restatement of csrc/atari_screen.h -- a, b = u8 [H][W][3] (current,
 // previous screen) -> u8 [84][84]
+// synth_atari.screen_features_indexed(ia, ib, pal): the host restatement for indexed screens -- ia, ib = u8 [H][W]
+// palette indices (current, previous screen), pal = u8 [256][3] RGB -> u8 [84][84]
+torch::Tensor screenFeaturesIndexed(const torch::Tensor& ia, const torch::Tensor& ib, const torch::Tensor& pal) {
+  auto ok = [](const torch::Tensor& t) { return t.scalar_type() == torch::kUInt8 && t.device().is_cpu(); };
+  if (ia.dim() != 2 || !ok(ia) || !ok(ib) || !ia.sizes().equals(ib.sizes()))
+    throw std::invalid_argument("screen_features_indexed: ia and ib must be uint8 CPU tensors of one shape [H, W]");
+  if (!ok(pal) || pal.dim() != 2 || pal.size(0) != 256 || pal.size(1) != 3)
+    throw std::invalid_argument("screen_features_indexed: pal must be a uint8 CPU tensor [256, 3]");
+  const int H = (int)ia.size(0), W = (int)ia.size(1);
+  if (H < rela_atari::kMinIn || H > rela_atari::kMaxIn || W < rela_atari::kMinIn || W > rela_atari::kMaxIn)
+    throw std::invalid_argument("screen_features_indexed: screens must be 2..512 x 2..512");
+  auto ac = ia.contiguous(), bc = ib.contiguous(), pc = pal.contiguous();
+  auto out = torch::empty({84, 84}, torch::kUInt8);
+  rela_atari::host_features_indexed(ac.data_ptr<uint8_t>(), bc.data_ptr<uint8_t>(), pc.data_ptr<uint8_t>(), H, W,
+                                    out.data_ptr<uint8_t>());
+  return out;
+}
+
 torch::Tensor screenFeatures(const torch::Tensor& a, const torch::Tensor& b) {
   if (a.dim() != 3 || a.size(2) != 3 || a.scalar_type() != torch::kUInt8 || !a.device().is_cpu() || !a.sizes().equals(b.sizes()) ||
       b.scalar_type() != torch::kUInt8 || !b.device().is_cpu())
@@ -357,17 +408,23 @@ PYBIND11_MODULE(synth_atari, m) {
       .def("step", &SyntheticScreenEnv::step)
       .def("terminated", &SyntheticScreenEnv::terminated)
       .def("get_episode_reward", &SyntheticScreenEnv::getEpisodeReward)
-      .def("screens", &SyntheticScreenEnv::screens);
+      .def("screens", &SyntheticScreenEnv::screens)
+      .def("palette", &SyntheticScreenEnv::palette);
   py::class_<SyntheticScreenEnvDevice, SyntheticScreenEnv, std::shared_ptr<SyntheticScreenEnvDevice>>(m, "SyntheticScreenEnvDevice");
   m.def("SyntheticScreenEnv",
-        [](int seed, float eps, int numAction, int episodeLen, bool deviceFeatures) -> std::shared_ptr<SyntheticScreenEnv> {
-          if (deviceFeatures) return std::make_shared<SyntheticScreenEnvDevice>(seed, eps, numAction, episodeLen);
-          return std::make_shared<SyntheticScreenEnv>(seed, eps, numAction, episodeLen);
+        [](int seed, float eps, int numAction, int episodeLen, bool deviceFeatures,
+           bool indexed) -> std::shared_ptr<SyntheticScreenEnv> {
+          if (deviceFeatures) return std::make_shared<SyntheticScreenEnvDevice>(seed, eps, numAction, episodeLen, indexed);
+          return std::make_shared<SyntheticScreenEnv>(seed, eps, numAction, episodeLen, indexed);
         },
         py::arg("seed"), py::arg("eps"), py::arg("num_action"), py::arg("episode_len"), py::arg("device_features") = true,
+        py::arg("indexed") = false,
         "raw-screen synthetic env: device_features=True -> a rela::ScreenEnv (stacks built on the GPU), False -> a plain "
-        "rela::Env that computes the same stacks on the host");
+        "rela::Env that computes the same stacks on the host; indexed=True -> the same picture as palette indices plus a "
+        "256-entry table (palette()), False -> RGB screens");
   m.def("screen_features", &screenFeatures, py::arg("a"), py::arg("b"),
         "GameState::computeFeature of one screen pair on the host (csrc/atari_screen.h): u8 [H,W,3] x2 -> u8 [84,84]");
+  m.def("screen_features_indexed", &screenFeaturesIndexed, py::arg("ia"), py::arg("ib"), py::arg("pal"),
+        "the same from indexed screens (csrc/atari_screen.h: host_features_indexed): u8 [H,W] x2, u8 [256,3] -> u8 [84,84]");
 #endif
 }

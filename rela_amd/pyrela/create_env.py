@@ -28,11 +28,15 @@ def create_game(seed, eps, episode_len):
         return synth_atari.NullAtariEnv(eps, NUM_ACTION, episode_len, seed)
     # RELA_SYNTH_SCREEN=1: raw 210x160 RGB screens, the observation built from them as GameState::computeFeature does
     # (atari/game_state.h:53-82,122-133) -- on the GPU by the actor shard (rela/screen_env.h); RELA_SYNTH_SCREEN=host:
-    # the same env computing the same stacks on the host, the reference's method.  Their stacks slide by construction,
-    # so RELA_REPLAY_DEDUP=plane accepts them.
+    # the same env computing the same stacks on the host, the reference's method; RELA_SYNTH_SCREEN=indexed: the device
+    # env handing over ALE's own screen format, one palette index per pixel and a 256-entry table (a third of the
+    # bytes, the lookup in the feature kernel).  Their stacks slide by construction, so RELA_REPLAY_DEDUP=plane accepts
+    # them.
     screen = os.environ.get("RELA_SYNTH_SCREEN", "0")
     if screen in ("1", "host"):
         return synth_atari.SyntheticScreenEnv(seed, eps, NUM_ACTION, episode_len, screen == "1")
+    if screen == "indexed":
+        return synth_atari.SyntheticScreenEnv(seed, eps, NUM_ACTION, episode_len, True, indexed=True)
     # RELA_SYNTH_SLIDING=1: Atari-like frame stacks (ONE new 84x84 plane per step, the first plane of an episode
     # repeated four times: atari/game_state.h:53-82) instead of four fresh planes per step -- a quarter of the host
     # work per env-step, and the stacks a de-duplicating replay (RELA_REPLAY_DEDUP=plane) expects
