@@ -13,13 +13,10 @@
 // The integer bookkeeping of the sequence windows is r2d2_seq_core.h (host); this file owns the HBM
 // side: per env one window of T = burn_in + seq_len + multi_step slots PER FIELD, laid out so a whole
 // window is exactly one replay row of that field -- emitting a sequence is a plain row copy.
-#include <atomic>
 #include <cmath>
 #include <cstring>
-#include <vector>
 
-#include "common.h"
-#include "dedup_refs.h"
+#include "actor_shard.h"
 #include "prof.h"
 #include "r2d2_seq_core.h"
 
@@ -27,7 +24,6 @@ using namespace rela_amd;
 
 namespace {
 
-constexpr int64_t kObs = 4 * 84 * 84;
 constexpr int kHid = 512;
 constexpr int kT = 256;
 
@@ -199,66 +195,35 @@ __global__ void r2d2_pick(const float* __restrict__ agg, const int32_t* __restri
   if (k < m) out[k] = agg[qs[k]];
 }
 
-constexpr int64_t kPlane = 84 * 84;
 constexpr int64_t kPadTick = -1, kLostTick = -2;  // de-duplication: window entries that are padding / an unstored tick
 
 }  // namespace
 
-struct rela_r2d2_actor {
-  int device = 0;
-  int R = 0, K = 0, A = 0, n = 0, seq = 0, burn = 0, T = 0;
+struct rela_r2d2_actor : ActorShardBase {
+  int seq = 0, burn = 0, T = 0;
   float gamma = 0.f, gamma_n = 0.f, eta = 0.f, one_minus_eta = 0.f;
-  rela_replay* replay = nullptr;
-  uint64_t seed = 0, act_calls = 0;
-  std::atomic<int64_t> num_act{0};
-  int head = 0, count = 0, cur = -1;
-  // n-step ring (dqn_actor.h:120-123) + hidden history (r2d2_actor.h:345)
-  uint8_t* obs = nullptr;
-  int64_t* act = nullptr;
-  float* rew = nullptr;
-  uint8_t* term = nullptr;
+  uint64_t seed = 0;
+  // hidden history (r2d2_actor.h:345) next to the n-step ring
   float *hist_h = nullptr, *hist_c = nullptr;  // [n+1][R][512]
   float *hid_h = nullptr, *hid_c = nullptr, *tmp_h = nullptr, *tmp_c = nullptr;  // [R][512]
-  float *eps = nullptr, *legal = nullptr;          // current values (uploaded / written by the caller)
-  float *eps_hist = nullptr, *legal_hist = nullptr;  // [n+1][R], [n+1][R][A]: snapshots per history slot
-  float* q = nullptr;  // [4][R][A]: adv(act), q_online, adv_next, q_target
-  float* q_hist = nullptr;  // [n+1][R][A]: act()'s own Q table of every history slot
-  // weights and history slot the advantages in q[0] (written by act) belong to
+  // q: adv(act), q_online, adv_next, q_target; weights the advantages in q[0] (written by act, slot q_slot) belong to
   const rela_lstmnet* q_net = nullptr;
   uint64_t q_version = 0;
-  int q_slot = -1;
-  int reuse_mode = 1;  // 0: recompute everything, 1: reuse both act() steps, 2: only the one of next_obs
-  std::vector<const rela_lstmnet*> qh_net;  // net / weight version act() evaluated every history slot with
-  std::vector<uint64_t> qh_version;
-  float *out_r = nullptr, *out_b = nullptr, *prio_step = nullptr;
-  uint8_t* out_t = nullptr;
+  float* prio_step = nullptr;  // [R]
   Windows w{};
   float *prow = nullptr, *lens = nullptr, *agg = nullptr;  // [2R][seq], [2R], [2R]
   int32_t *d_slot = nullptr, *d_ranges = nullptr, *d_emits = nullptr, *d_envs = nullptr;
   int32_t* d_gather = nullptr;  // [2][3R]: destination offsets, source envs and emit indices of one batch
   uint8_t* d_flags = nullptr;
-  uint8_t* restart = nullptr;
-  uint8_t* fresh_planes = nullptr;  // [R][7056] staging of the newest plane of every row (rela_r2d2_actor_plane_stage)  // [R] rela_r2d2_actor_slide_stacks
-  uint8_t* screens = nullptr;       // [R][2][scr_h][scr_w][3] screen pairs (rela_r2d2_actor_set_screen_input), or
-                                    // [R][2][scr_h][scr_w] palette indices (..._set_screen_input_indexed)
-  uint8_t* palettes = nullptr;      // [R][256][3] RGB table of every row: indexed screens only
-  uint8_t* screen_prev = nullptr;   // [R][28224] evaluation shard (no replay): copy of the one slot it acts on
-  int scr_h = 0, scr_w = 0;
   void* ws = nullptr;
   int64_t ws_bytes = 0;
   std::vector<uint8_t> h_term;  // [n+1][R] host copy: the bookkeeping needs the flags
   SeqBook* book = nullptr;
   SeqPlan plan;
-  // frame-stack de-duplication (rela_r2d2_actor_set_dedup; replay side: rela_replay_set_schema_seq_dedup).  Every tick the
-  // stack acted on enters the unit ring once, as in the Ape-X shard (actor.hip); ref_hist is the n-step ring of its
-  // references, and the windows (w.sref) receive those of obs_t.
-  int dd_ups = 0;
-  int64_t dd_cap = 0;
-  int32_t* ref_hist = nullptr;       // [n+1][R][ups]
-  std::vector<uint8_t> refs_valid;   // [n+1] the slot's units were stored
+  // frame-stack de-duplication: ref_hist is the n-step ring of the stacks' references, and the windows (w.sref) receive
+  // those of obs_t.  tick_seq has tick_win entries; for an unstored tick it holds a lower bound.
   int tick_win = 0;                  // T + n + 8 ticks: the oldest unit a sequence emitted now can refer to is T + n + 3 back
-  std::vector<int64_t> tick_seq;     // [tick_win] first unit sequence number of a tick (ring by tick); unstored: a lower bound
-  int64_t tick = 0, seq_hint = 0;    // ticks so far; the unit sequence number after this shard's last reservation
+  int64_t seq_hint = 0;              // the unit sequence number after this shard's last reservation
   std::vector<int64_t> win_tick;     // [R][T] host: the tick each window entry holds (kPadTick, kLostTick)
   float* agg_kept = nullptr;         // [2R] priorities of the kept sequences of one piece
   int32_t* d_kept = nullptr;         // [2R]
@@ -273,12 +238,8 @@ extern "C" int rela_r2d2_actor_create(rela_r2d2_actor** out, int rows, int group
              RELA_EINVAL, "rela_r2d2_actor_create: bad arguments");
   RELA_CHECK(burn_in <= seq_len && multi_step <= seq_len, RELA_EINVAL,
              "rela_r2d2_actor_create: needs burn_in <= seq_len and multi_step <= seq_len");  // r2d2_actor.h:25-26
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_last_error("rela_r2d2_actor_create: HIP device %d not available (%d visible); there is no CPU path", device,
-                   ndev);
-    return RELA_ENODEV;
-  }
+  int rc = shard_check_device(device, "rela_r2d2_actor_create");
+  if (rc != RELA_OK) return rc;
   DeviceGuard g(device);
   auto* a = new rela_r2d2_actor();
   a->device = device;
@@ -296,38 +257,15 @@ extern "C" int rela_r2d2_actor_create(rela_r2d2_actor** out, int rows, int group
   a->replay = replay;
   a->seed = seed;
   const size_t H = (size_t)multi_step + 1, R = (size_t)rows, A = (size_t)num_action, T = (size_t)a->T;
-  auto alloc = [&](void** p, size_t bytes) -> int {
-    RELA_HIP(hipMalloc(p, bytes));
-    RELA_HIP(hipMemset(*p, 0, bytes));
-    return RELA_OK;
-  };
-#define RELA_ALLOC(ptr, bytes)                                  \
-  do {                                                          \
-    int _rc = alloc(reinterpret_cast<void**>(&(ptr)), (bytes)); \
-    if (_rc != RELA_OK) return _rc;                             \
-  } while (0)
-  RELA_ALLOC(a->obs, H * R * kObs);
-  RELA_ALLOC(a->act, H * R * sizeof(int64_t));
-  RELA_ALLOC(a->rew, H * R * sizeof(float));
-  RELA_ALLOC(a->term, H * R);
+  rc = shard_alloc_ring(a);
+  if (rc != RELA_OK) return rc;
   RELA_ALLOC(a->hist_h, H * R * kHid * sizeof(float));
   RELA_ALLOC(a->hist_c, H * R * kHid * sizeof(float));
   RELA_ALLOC(a->hid_h, R * kHid * sizeof(float));
   RELA_ALLOC(a->hid_c, R * kHid * sizeof(float));
   RELA_ALLOC(a->tmp_h, R * kHid * sizeof(float));
   RELA_ALLOC(a->tmp_c, R * kHid * sizeof(float));
-  RELA_ALLOC(a->eps, R * sizeof(float));
-  RELA_ALLOC(a->legal, R * A * sizeof(float));
-  RELA_ALLOC(a->eps_hist, H * R * sizeof(float));
-  RELA_ALLOC(a->legal_hist, H * R * A * sizeof(float));
-  RELA_ALLOC(a->q, 4 * R * A * sizeof(float));
-  RELA_ALLOC(a->q_hist, (size_t)(multi_step + 1) * R * A * sizeof(float));
-  a->qh_net.assign((size_t)multi_step + 1, nullptr);
-  a->qh_version.assign((size_t)multi_step + 1, 0);
-  RELA_ALLOC(a->out_r, R * sizeof(float));
-  RELA_ALLOC(a->out_b, R * sizeof(float));
   RELA_ALLOC(a->prio_step, R * sizeof(float));
-  RELA_ALLOC(a->out_t, R);
   Windows& w = a->w;
   w.T = a->T;
   w.A = num_action;
@@ -355,18 +293,11 @@ extern "C" int rela_r2d2_actor_create(rela_r2d2_actor** out, int rows, int group
   RELA_ALLOC(a->d_emits, 2 * R * 3 * sizeof(int32_t));
   RELA_ALLOC(a->d_gather, 2 * R * 3 * sizeof(int32_t));
   RELA_ALLOC(a->d_envs, R * sizeof(int32_t));
-#undef RELA_ALLOC
   a->ws_bytes = rela_lstmnet_workspace_bytes(nullptr, rows);
   RELA_HIP(hipMalloc(&a->ws, (size_t)a->ws_bytes));
-  {
-    std::vector<float> ones(R * A, 1.0f);
-    RELA_HIP(hipMemcpy(a->legal, ones.data(), R * A * sizeof(float), hipMemcpyHostToDevice));
-  }
   a->h_term.assign(H * R, 0);
-  {
-    const int rc = a->stage.init(R * 320 + 4096);
-    RELA_CHECK(rc == RELA_OK, rc, "rela_r2d2_actor_create: pinned staging buffer");
-  }
+  rc = a->stage.init(R * 320 + 4096);
+  RELA_CHECK(rc == RELA_OK, rc, "rela_r2d2_actor_create: pinned staging buffer");
   a->book = new SeqBook(rows, multi_step, seq_len, burn_in);
   *out = a;
   return RELA_OK;
@@ -376,114 +307,48 @@ extern "C" void rela_r2d2_actor_destroy(rela_r2d2_actor* a) {
   if (!a) return;
   DeviceGuard g(a->device);
   (void)hipDeviceSynchronize();
-  void* ps[] = {a->obs,   a->act,    a->rew,    a->term,      a->hist_h, a->hist_c, a->hid_h,  a->hid_c,  a->tmp_h,
-                a->tmp_c, a->eps,    a->legal,  a->eps_hist, a->legal_hist, a->q,         a->out_r,  a->out_b,  a->prio_step, a->out_t, a->w.s,
-                a->w.eps, a->w.legal, a->w.a,   a->w.reward,  a->w.term, a->w.boot, a->w.prio, a->w.h0,   a->w.c0,
-                a->w.nh0, a->w.nc0,  a->prow,   a->lens,      a->agg,    a->d_slot, a->d_flags, a->d_ranges, a->d_emits, a->d_gather,
-                a->d_envs, a->ws, a->q_hist, a->restart, a->fresh_planes, a->ref_hist, a->w.sref, a->agg_kept, a->d_kept,
-                a->screens, a->screen_prev, a->palettes};
+  shard_free(a);
+  void* ps[] = {a->hist_h, a->hist_c, a->hid_h,  a->hid_c,  a->tmp_h,  a->tmp_c,    a->prio_step, a->w.s,     a->w.sref,
+                a->w.eps,  a->w.legal, a->w.a,   a->w.reward, a->w.term, a->w.boot, a->w.prio,    a->w.h0,    a->w.c0,
+                a->w.nh0,  a->w.nc0,  a->prow,   a->lens,   a->agg,    a->d_slot,   a->d_flags,   a->d_ranges, a->d_emits,
+                a->d_gather, a->d_envs, a->ws,   a->agg_kept, a->d_kept};
   for (void* p : ps) (void)hipFree(p);
   a->stage.destroy();
   delete a->book;
   delete a;
 }
 
-static inline int next_slot(const rela_r2d2_actor* a) { return (a->head + a->count) % (a->n + 1); }
-
-extern "C" void* rela_r2d2_actor_obs_slot(rela_r2d2_actor* a) {
-  return a ? a->obs + (size_t)next_slot(a) * a->R * kObs : nullptr;
-}
-extern "C" void* rela_r2d2_actor_plane_stage(rela_r2d2_actor* a) {
-  if (!a) return nullptr;
-  if (!a->fresh_planes) {
-    DeviceGuard g(a->device);
-    if (hipMalloc(&a->fresh_planes, (size_t)a->R * 84 * 84) != hipSuccess) a->fresh_planes = nullptr;
-  }
-  return a->fresh_planes;
-}
+extern "C" void* rela_r2d2_actor_obs_slot(rela_r2d2_actor* a) { return shard_obs_slot(a); }
+extern "C" void* rela_r2d2_actor_plane_stage(rela_r2d2_actor* a) { return shard_plane_stage(a); }
 extern "C" int rela_r2d2_actor_slide_stacks(rela_r2d2_actor* a, const uint8_t* restart_host, void* stream_) {
-  RELA_CHECK(a && restart_host, RELA_EINVAL, "rela_r2d2_actor_slide_stacks: bad arguments");
-  RELA_CHECK(a->fresh_planes, RELA_ESTATE, "rela_r2d2_actor_slide_stacks: no plane was staged (rela_r2d2_actor_plane_stage)");
-  RELA_CHECK(a->act_calls > 0, RELA_ESTATE, "rela_r2d2_actor_slide_stacks: the first observation must be uploaded whole");
-  RELA_CHECK(a->count <= a->n, RELA_ESTATE, "rela_r2d2_actor_slide_stacks: act() twice without post_step()");
-  hipStream_t s = (hipStream_t)stream_;
-  DeviceGuard g(a->device);
-  if (!a->restart) RELA_HIP(hipMalloc(&a->restart, (size_t)a->R));
-  RELA_HIP(hipMemcpyAsync(a->restart, restart_host, (size_t)a->R, hipMemcpyHostToDevice, s));
-  const int H = a->n + 1, slot = next_slot(a), prev = (slot + H - 1) % H;
-  return slide_stacks(a->obs + (size_t)slot * a->R * kObs, a->obs + (size_t)prev * a->R * kObs, a->fresh_planes, a->restart,
-                      a->R, s);
-}
-// channels: 3 = RGB screens, 1 = palette indices (a zeroed palette stage comes with them)
-static int set_screen_input(rela_r2d2_actor* a, int height, int width, int channels, const char* who) {
-  RELA_CHECK(a && height >= 2 && height <= 512 && width >= 2 && width <= 512, RELA_EINVAL,
-             "%s: bad arguments (screens must be 2..512 x 2..512)", who);
-  RELA_CHECK(a->act_calls == 0 && !a->screens, RELA_ESTATE,
-             "%s: call it once, before the first act() (a shard takes RGB or indexed screens, not both)", who);
-  DeviceGuard g(a->device);
-  const size_t bytes = (size_t)a->R * 2 * height * width * channels;
-  RELA_HIP(hipMalloc(&a->screens, bytes));
-  RELA_HIP(hipMemset(a->screens, 0, bytes));
-  if (channels == 1) {
-    RELA_HIP(hipMalloc(&a->palettes, (size_t)a->R * 768));
-    RELA_HIP(hipMemset(a->palettes, 0, (size_t)a->R * 768));
-  }
-  RELA_CHECK(rela_r2d2_actor_plane_stage(a), RELA_ENOMEM, "%s: plane stage", who);
-  if (!a->replay) RELA_HIP(hipMalloc(&a->screen_prev, (size_t)a->R * kObs));
-  a->scr_h = height;
-  a->scr_w = width;
-  return RELA_OK;
+  return shard_slide_stacks(a, restart_host, (hipStream_t)stream_, "rela_r2d2_actor_slide_stacks", "rela_r2d2_actor_plane_stage");
 }
 extern "C" int rela_r2d2_actor_set_screen_input(rela_r2d2_actor* a, int height, int width) {
-  return set_screen_input(a, height, width, 3, "rela_r2d2_actor_set_screen_input");
+  return shard_set_screen_input(a, height, width, 3, "rela_r2d2_actor_set_screen_input");
 }
 extern "C" int rela_r2d2_actor_set_screen_input_indexed(rela_r2d2_actor* a, int height, int width) {
-  return set_screen_input(a, height, width, 1, "rela_r2d2_actor_set_screen_input_indexed");
+  return shard_set_screen_input(a, height, width, 1, "rela_r2d2_actor_set_screen_input_indexed");
 }
 extern "C" void* rela_r2d2_actor_palette_stage(rela_r2d2_actor* a) { return a ? a->palettes : nullptr; }
 extern "C" void* rela_r2d2_actor_screen_stage(rela_r2d2_actor* a) { return a ? a->screens : nullptr; }
 extern "C" int rela_r2d2_actor_screens_to_stacks(rela_r2d2_actor* a, const uint8_t* restart_host, void* stream_) {
-  RELA_CHECK(a, RELA_EINVAL, "rela_r2d2_actor_screens_to_stacks: bad arguments");
-  RELA_CHECK(a->count <= a->n, RELA_ESTATE, "rela_r2d2_actor_screens_to_stacks: act() twice without post_step()");
-  DeviceGuard g(a->device);
-  const int slot = next_slot(a), prev = a->q_slot >= 0 ? a->q_slot : slot;  // the stacks of the last act()
-  return screens_to_stacks(a->screens, a->palettes, a->scr_h, a->scr_w, a->fresh_planes, &a->restart, restart_host, a->act_calls == 0,
-                           a->obs + (size_t)slot * a->R * kObs, a->obs + (size_t)prev * a->R * kObs, a->screen_prev, a->R,
-                           (hipStream_t)stream_, "rela_r2d2_actor_screens_to_stacks");
+  return shard_screens_to_stacks(a, restart_host, (hipStream_t)stream_, "rela_r2d2_actor_screens_to_stacks");
 }
 extern "C" int rela_r2d2_actor_set_reuse(rela_r2d2_actor* a, int on) {
-  RELA_CHECK(a, RELA_EINVAL, "rela_r2d2_actor_set_reuse: bad arguments");
-  RELA_CHECK(on >= 0 && on <= 2, RELA_EINVAL, "rela_r2d2_actor_set_reuse: 0 (off), 1 (on) or 2 (next_obs only)");
-  a->reuse_mode = on;
-  return RELA_OK;
+  return shard_set_reuse(a, on, "rela_r2d2_actor_set_reuse");
 }
 extern "C" int rela_r2d2_actor_set_dedup(rela_r2d2_actor* a, int units_per_stack) {
-  RELA_CHECK(a && a->replay && (units_per_stack == 1 || units_per_stack == 4), RELA_EINVAL,
-             "rela_r2d2_actor_set_dedup: needs a replay and 1 (stack units) or 4 (plane units)");
-  RELA_CHECK(a->count == 0 && a->act_calls == 0 && a->dd_ups == 0, RELA_ESTATE,
-             "rela_r2d2_actor_set_dedup: call it once, before the first act()");
-  int ups = 0;
-  int64_t ub = 0, cap = 0;
-  int rc = rela_replay_dedup_info(a->replay, &ups, &ub, &cap);
+  const int rc = shard_set_dedup_common(a, units_per_stack, a ? a->T : 1, "rela_r2d2_actor_set_dedup");
   if (rc != RELA_OK) return rc;
-  const int steps = rela_replay_dedup_steps(a->replay);
-  RELA_CHECK(ups == units_per_stack && ub * ups == kObs && steps == a->T, RELA_EINVAL,
-             "rela_r2d2_actor_set_dedup: the replay's schema has %d units of %lld bytes per stack and %d steps per slot "
-             "(this shard: %d steps; needs rela_replay_set_schema_seq_dedup)", ups, (long long)ub, steps, a->T);
   DeviceGuard g(a->device);
-  const size_t H = (size_t)a->n + 1, R = (size_t)a->R, T = (size_t)a->T;
-  RELA_HIP(hipMalloc(&a->ref_hist, H * R * ups * sizeof(int32_t)));
-  RELA_HIP(hipMemset(a->ref_hist, 0, H * R * ups * sizeof(int32_t)));
+  const size_t R = (size_t)a->R, T = (size_t)a->T, ups = (size_t)a->dd_ups;
   RELA_HIP(hipMalloc(&a->w.sref, R * T * ups * sizeof(int32_t)));
   RELA_HIP(hipMemset(a->w.sref, 0xff, R * T * ups * sizeof(int32_t)));  // -1: padding
   RELA_HIP(hipMalloc(&a->agg_kept, 2 * R * sizeof(float)));
   RELA_HIP(hipMalloc(&a->d_kept, 2 * R * sizeof(int32_t)));
   RELA_HIP(hipFree(a->w.s));  // the frame windows ([R][T][28,224] B) are no longer needed
   a->w.s = nullptr;
-  a->w.ups = ups;
-  a->dd_ups = ups;
-  a->dd_cap = cap;
-  a->refs_valid.assign(H, 0);
+  a->w.ups = a->dd_ups;
   a->tick_win = a->T + a->n + 8;
   a->tick_seq.assign((size_t)a->tick_win, 0);
   a->win_tick.assign(R * T, kPadTick);
@@ -504,41 +369,28 @@ extern "C" int rela_r2d2_actor_act(rela_r2d2_actor* a, const rela_lstmnet* onlin
   RELA_CHECK(a->count <= a->n, RELA_ESTATE, "rela_r2d2_actor_act: act() twice without post_step()");
   hipStream_t s = (hipStream_t)stream_;
   DeviceGuard g(a->device);
-  const int slot = next_slot(a);
-  const size_t R = (size_t)a->R, HB = R * kHid * sizeof(float);
-  uint8_t* obs = a->obs + (size_t)slot * R * kObs;
-  if (obs_host) RELA_HIP(hipMemcpyAsync(obs, obs_host, R * kObs, hipMemcpyHostToDevice, s));
-  if (eps_host) RELA_HIP(hipMemcpyAsync(a->eps, eps_host, R * sizeof(float), hipMemcpyHostToDevice, s));
-  if (legal_host) RELA_HIP(hipMemcpyAsync(a->legal, legal_host, R * a->A * sizeof(float), hipMemcpyHostToDevice, s));
-  // historyHidden_.push_back(hidden_) :226-228
-  RELA_HIP(dev_copy2(a->hist_h + (size_t)slot * R * kHid, a->hid_h, HB, a->hist_c + (size_t)slot * R * kHid, a->hid_c, HB, s));
-  float* eps_s = a->eps_hist + (size_t)slot * R;
-  float* legal_s = a->legal_hist + (size_t)slot * R * a->A;
-  RELA_HIP(dev_copy2(eps_s, a->eps, R * sizeof(float), legal_s, a->legal, R * a->A * sizeof(float), s));
-  // (the dueling Q of this step goes to the slot's table: compute_priority's online_net(obs, hid) n ticks from now)
-  a->qh_net[slot] = nullptr;
-  int rc = rela_lstmnet_step(online, a->R, obs, legal_s, a->hid_h, a->hid_c, a->tmp_h, a->tmp_c,
-                             a->q_hist + (size_t)slot * R * a->A, a->q, a->ws, a->ws_bytes, s);
+  ActSlot sl;
+  int rc = shard_begin_act(a, obs_host, eps_host, legal_host, s, &sl);
   if (rc != RELA_OK) return rc;
-  a->qh_net[slot] = online;
-  a->qh_version[slot] = rela_lstmnet_version(online);
+  const size_t R = (size_t)a->R, HB = R * kHid * sizeof(float);
+  // historyHidden_.push_back(hidden_) :226-228
+  RELA_HIP(dev_copy2(a->hist_h + (size_t)sl.slot * R * kHid, a->hid_h, HB, a->hist_c + (size_t)sl.slot * R * kHid, a->hid_c, HB, s));
+  rc = shard_snapshot_consts(a, sl, s);
+  if (rc != RELA_OK) return rc;
+  // (the dueling Q of this step goes to the slot's table: compute_priority's online_net(obs, hid) n ticks from now)
+  a->qh_net[sl.slot] = nullptr;
+  rc = rela_lstmnet_step(online, a->R, sl.obs, sl.legal, a->hid_h, a->hid_c, a->tmp_h, a->tmp_c, sl.q, a->q, a->ws,
+                         a->ws_bytes, s);
+  if (rc != RELA_OK) return rc;
+  a->qh_net[sl.slot] = online;
+  a->qh_version[sl.slot] = rela_lstmnet_version(online);
   std::swap(a->hid_h, a->tmp_h);  // hidden_ <- new state :241
   std::swap(a->hid_c, a->tmp_c);
-  int64_t* act = a->act + (size_t)slot * R;
-  rc = rela_apex_act_from_q(a->R, a->A, a->K, a->q, legal_s, eps_s, a->seed, a->act_calls * (uint64_t)a->R, act, s);
+  rc = rela_apex_act_from_q(a->R, a->A, a->K, a->q, sl.legal, sl.eps, a->seed, a->act_calls * (uint64_t)a->R, sl.act, s);
   if (rc != RELA_OK) return rc;
   a->q_net = online;
   a->q_version = rela_lstmnet_version(online);
-  a->q_slot = slot;
-  a->act_calls += 1;
-  a->cur = slot;
-  a->num_act += a->R;
-  if (action_dev_out) *action_dev_out = act;
-  if (action_host) {
-    RELA_HIP(hipMemcpyAsync(action_host, act, R * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    RELA_HIP(hipStreamSynchronize(s));
-  }
-  return RELA_OK;
+  return shard_finish_act(a, sl, action_host, action_dev_out, s);
 }
 
 namespace {
@@ -556,38 +408,14 @@ int upload_ranges(rela_r2d2_actor* a, const std::vector<SeqRange>& rs, hipStream
   return RELA_OK;  // `flat` may die: the upload reads the pinned copy
 }
 
-// de-duplication: the stack acted on this tick (history slot `cur`) enters the unit ring once -- one new plane, or all
-// four on a keyframe (the first tick, or the first after an unstored one), or the whole stack -- exactly as in the Ape-X
-// shard (actor.hip); ref_hist[cur] receives its references.  Ring full and nonblocking: the tick is not stored.
+// de-duplication: store this tick's stack (shard_dedup_store), then this shard's window of unit sequence numbers: a
+// stored tick's first unit, an unstored tick's lower bound (no unit of a later tick is older than seq_hint)
 int dedup_store(rela_r2d2_actor* a, int nonblocking, hipStream_t s) {
-  const int H = a->n + 1, cur = a->cur, prev = (cur + H - 1) % H;
-  const int ups = a->dd_ups;
-  const bool prev_ok = a->tick > 0 && a->refs_valid[prev];
-  const int keyframe = (ups == 4 && !prev_ok) ? 1 : 0;
-  const int count = keyframe ? 4 * a->R : a->R;
-  int64_t seq = 0;
-  int32_t idx = 0;
-  int rc = rela_replay_units_reserve(a->replay, count, nonblocking, &seq, &idx);
-  const size_t tw = (size_t)(a->tick % a->tick_win);
-  if (rc == RELA_EWOULDBLOCK) {
-    a->refs_valid[cur] = 0;
-    a->tick_seq[tw] = a->seq_hint;  // no unit of a later tick is older
-  } else {
-    if (rc != RELA_OK) return rc;
-    const uint8_t* stack = a->obs + (size_t)cur * a->R * kObs;
-    if (ups == 1) rc = rela_replay_units_write(a->replay, seq, count, stack, kObs, s);
-    else if (keyframe) rc = rela_replay_units_write(a->replay, seq, count, stack, kPlane, s);
-    else rc = rela_replay_units_write(a->replay, seq, count, stack + 3 * kPlane, kObs, s);  // the newest plane
-    if (rc != RELA_OK) return rc;
-    hipLaunchKernelGGL(dedup_make_refs, dim3(ceil_div(a->R, 256)), dim3(256), 0, s,
-                       a->ref_hist + (size_t)cur * a->R * ups, a->ref_hist + (size_t)prev * a->R * ups,
-                       a->term + (size_t)prev * a->R, a->R, ups, keyframe, idx, a->dd_cap);
-    RELA_LAUNCH_CHECK();
-    a->refs_valid[cur] = 1;
-    a->tick_seq[tw] = seq;
-    a->seq_hint = seq + count;
-  }
-  a->tick += 1;
+  DedupStored st;
+  const int rc = shard_dedup_store(a, nonblocking, s, &st);
+  if (rc != RELA_OK) return rc;
+  if (st.stored) a->seq_hint = st.seq + st.count;
+  a->tick_seq[(size_t)(st.tick % a->tick_win)] = st.stored ? st.seq : a->seq_hint;
   return RELA_OK;
 }
 

@@ -1,6 +1,6 @@
-// dedup_refs.h -- the references of a de-duplicated frame stack, shared by the Ape-X and the R2D2 actor
-// shards (csrc/actor.hip, csrc/actor_r2d2.hip): per env-step each shard stores the stack it acted on in the replay's unit
-// ring once and keeps [rows][ups] int32 references to it.
+// dedup_refs.h -- the references of a de-duplicated frame stack.  Per env-step an actor shard stores the
+// stack it acted on in the replay's unit ring once and keeps [rows][ups] int32 references to it; the one caller is
+// shard_dedup_store (csrc/actor_shard.h), which serves the Ape-X and the R2D2 shard.
 #pragma once
 #include <hip/hip_runtime.h>
 

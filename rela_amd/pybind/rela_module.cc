@@ -29,6 +29,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 
 #include "rela/env.h"
 #include "rela/types.h"
@@ -1071,18 +1072,97 @@ class RNNPrioritizedReplay {
   std::string prefetchedDevice_;
 };
 
+// One actor shard of either algorithm behind one handle: the entry points the module calls, in the spelling of the
+// Ape-X shard (rela_apex_actor_*, nets are rela_ffnet) and of the R2D2 shard (rela_r2d2_actor_*, nets are rela_lstmnet).
+// Only `create` differs in its arguments and stays with the callers.
+struct ShardApi {
+  void (*destroy)(void*);
+  void* (*obs_slot)(void*);
+  void* (*plane_stage)(void*);
+  int (*slide_stacks)(void*, const uint8_t*, void*);
+  int (*set_screen_input)(void*, int, int);
+  int (*set_screen_input_indexed)(void*, int, int);
+  void* (*screen_stage)(void*);
+  void* (*palette_stage)(void*);
+  int (*screens_to_stacks)(void*, const uint8_t*, void*);
+  int64_t (*num_act)(const void*);
+  int (*set_dedup)(void*, int);
+  int (*act)(void* h, const void* online, const uint8_t* obs, const float* eps, const float* legal, int64_t* action,
+             void* stream);
+  int (*post_step)(void* h, const float* reward, const uint8_t* terminal, const void* online, const void* target,
+                   void* stream);  // host reward / terminal, blocking insert
+};
+// F with its first parameter, the typed shard pointer, taken as void*
+template <auto F>
+struct Erased;
+template <class R, class S, class... A, R (*F)(S*, A...)>
+struct Erased<F> {
+  static R call(std::conditional_t<std::is_const_v<S>, const void*, void*> h, A... a) { return F(static_cast<S*>(h), a...); }
+};
+const ShardApi kApexShard = {
+    Erased<rela_apex_actor_destroy>::call,
+    Erased<rela_apex_actor_obs_slot>::call,
+    Erased<rela_apex_actor_plane_stage>::call,
+    Erased<rela_apex_actor_slide_stacks>::call,
+    Erased<rela_apex_actor_set_screen_input>::call,
+    Erased<rela_apex_actor_set_screen_input_indexed>::call,
+    Erased<rela_apex_actor_screen_stage>::call,
+    Erased<rela_apex_actor_palette_stage>::call,
+    Erased<rela_apex_actor_screens_to_stacks>::call,
+    Erased<rela_apex_actor_num_act>::call,
+    Erased<rela_apex_actor_set_dedup>::call,
+    [](void* h, const void* online, const uint8_t* obs, const float* eps, const float* legal, int64_t* action, void* stream) {
+      return rela_apex_actor_act(static_cast<rela_apex_actor*>(h), static_cast<const rela_ffnet*>(online), obs, eps, legal,
+                                 action, nullptr, stream);
+    },
+    [](void* h, const float* reward, const uint8_t* terminal, const void* online, const void* target, void* stream) {
+      return rela_apex_actor_post_step(static_cast<rela_apex_actor*>(h), reward, terminal, /*on_device=*/0,
+                                       static_cast<const rela_ffnet*>(online), static_cast<const rela_ffnet*>(target), 0,
+                                       nullptr, stream);
+    }};
+const ShardApi kR2D2Shard = {
+    Erased<rela_r2d2_actor_destroy>::call,
+    Erased<rela_r2d2_actor_obs_slot>::call,
+    Erased<rela_r2d2_actor_plane_stage>::call,
+    Erased<rela_r2d2_actor_slide_stacks>::call,
+    Erased<rela_r2d2_actor_set_screen_input>::call,
+    Erased<rela_r2d2_actor_set_screen_input_indexed>::call,
+    Erased<rela_r2d2_actor_screen_stage>::call,
+    Erased<rela_r2d2_actor_palette_stage>::call,
+    Erased<rela_r2d2_actor_screens_to_stacks>::call,
+    Erased<rela_r2d2_actor_num_act>::call,
+    Erased<rela_r2d2_actor_set_dedup>::call,
+    [](void* h, const void* online, const uint8_t* obs, const float* eps, const float* legal, int64_t* action, void* stream) {
+      return rela_r2d2_actor_act(static_cast<rela_r2d2_actor*>(h), static_cast<const rela_lstmnet*>(online), obs, eps,
+                                 legal, action, nullptr, stream);
+    },
+    [](void* h, const float* reward, const uint8_t* terminal, const void* online, const void* target, void* stream) {
+      return rela_r2d2_actor_post_step(static_cast<rela_r2d2_actor*>(h), reward, terminal,
+                                       static_cast<const rela_lstmnet*>(online), static_cast<const rela_lstmnet*>(target),
+                                       0, nullptr, stream);
+    }};
+
+struct Shard {
+  void* h = nullptr;
+  const ShardApi* api = nullptr;
+  Shard() = default;
+  Shard(const Shard&) = delete;
+  Shard& operator=(const Shard&) = delete;
+  ~Shard() { reset(); }
+  void reset() {
+    if (h) api->destroy(h);
+    h = nullptr;
+  }
+  explicit operator bool() const { return h != nullptr; }
+  const ShardApi* operator->() const { return api; }
+};
+
 // the actor side of a de-duplicating replay (RELA_REPLAY_DEDUP, see FFPrioritizedReplay::handle)
-static void enableDedup(rela_apex_actor* a, rela_replay* rep) {
+static void enableDedup(Shard& sh, rela_replay* rep) {
   if (!rep) return;
   int ups = 0;
   check(rela_replay_dedup_info(rep, &ups, nullptr, nullptr), "rela_replay_dedup_info");
-  if (ups > 0) check(rela_apex_actor_set_dedup(a, ups), "rela_apex_actor_set_dedup");
-}
-static void enableDedup(rela_r2d2_actor* a, rela_replay* rep) {
-  if (!rep) return;
-  int ups = 0;
-  check(rela_replay_dedup_info(rep, &ups, nullptr, nullptr), "rela_replay_dedup_info");
-  if (ups > 0) check(rela_r2d2_actor_set_dedup(a, ups), "rela_r2d2_actor_set_dedup");
+  if (ups > 0) check(sh->set_dedup(sh.h, ups), "set_dedup");
 }
 
 // =====================================================================================
@@ -1114,8 +1194,7 @@ class ActorCohort {
   }
 
   ~ActorCohort() {
-    rela_apex_actor_destroy(h_);
-    rela_r2d2_actor_destroy(hr_);
+    shard_.reset();  // before its streams
     const int dev = locker_->execDevice;
     if (compute_) rela_stream_destroy(compute_, dev);
     if (upload_) rela_stream_destroy(upload_, dev);
@@ -1128,7 +1207,7 @@ class ActorCohort {
     const auto& legal = obs.at("legal_move");
     const auto& eps = obs.at("eps");
     if (s.size(0) != K_ || s.numel() != (int64_t)K_ * kObsBytes || s.dtype() != torch::kUInt8)
-      throw std::runtime_error("DQNActor.act: obs['s'] must be uint8 [batchsize,4,84,84]");
+      throw std::runtime_error(name_ + ".act: obs['s'] must be uint8 [batchsize,4,84,84]");
     const int A = (int)legal.size(1);
     const int64_t tPrep = gStats.on ? ThreadedStats::now() : 0;
     void* slot = nullptr;
@@ -1144,7 +1223,7 @@ class ActorCohort {
       if (indexed != (paletteStage_ != nullptr))
         throw std::runtime_error("ActorCohort: the VectorEnvs of one cohort must all hold RGB screen envs or all indexed ones");
       // (the slot moves only inside the leader's work, which every member of the round has left by now)
-      slot = lstm_ ? rela_r2d2_actor_obs_slot(hr_) : rela_apex_actor_obs_slot(h_);
+      slot = shard_->obs_slot(shard_.h);
       // a VectorEnv whose envs all slide their frame stack marks its batch (rela/env.h): only plane 3 of every row is
       // new; the very first observation has no predecessor on the device and goes up whole
       planes = !screens && planeUpload_ && !firstRound_ && obs.count("__stack_restart") != 0;
@@ -1207,22 +1286,17 @@ class ActorCohort {
       check(rela_stream_wait_stream(compute_, upload_, dev), "rela_stream_wait_stream");
       if (screenBytes_ > 0) {  // features + stacks from the staged screens (atari/game_state.h:53-82,122-133)
         const uint8_t* f = restartAll_.data_ptr<uint8_t>();
-        check(lstm_ ? rela_r2d2_actor_screens_to_stacks(hr_, f, compute_) : rela_apex_actor_screens_to_stacks(h_, f, compute_),
-              "screens_to_stacks");
+        check(shard_->screens_to_stacks(shard_.h, f, compute_), "screens_to_stacks");
       } else if (planesThisRound_) {  // complete the stacks on the device (atari/game_state.h:53-82) before the forward
         const uint8_t* f = restartAll_.data_ptr<uint8_t>();
-        check(lstm_ ? rela_r2d2_actor_slide_stacks(hr_, f, compute_) : rela_apex_actor_slide_stacks(h_, f, compute_),
-              "slide_stacks");
+        check(shard_->slide_stacks(shard_.h, f, compute_), "slide_stacks");
       }
       auto lease = locker_->getModel();
       const float* e = constsDirty_ ? epsAll_.data_ptr<float>() : nullptr;
       const float* l = constsDirty_ ? legalAll_.data_ptr<float>() : nullptr;
-      const int rc = lstm_ ? rela_r2d2_actor_act(hr_, static_cast<const rela_lstmnet*>(lease.online), nullptr, e, l,
-                                                 actionAll_.data_ptr<int64_t>(), nullptr, compute_)
-                           : rela_apex_actor_act(h_, static_cast<const rela_ffnet*>(lease.online), nullptr, e, l,
-                                                 actionAll_.data_ptr<int64_t>(), nullptr, compute_);
+      const int rc = shard_->act(shard_.h, lease.online, nullptr, e, l, actionAll_.data_ptr<int64_t>(), compute_);
       locker_->releaseModel(lease.id);
-      check(rc, lstm_ ? "R2D2Actor.act (batched)" : "DQNActor.act (batched)");
+      if (rc != RELA_OK) fail(name_ + ".act (batched)", rc);
       constsDirty_ = false;
       constsValid_ = true;
       planesThisRound_ = false;
@@ -1250,13 +1324,7 @@ class ActorCohort {
     rendezvous(lk, [&] {
       auto lease = locker_->getModel();
       const uint8_t* term = reinterpret_cast<const uint8_t*>(terminalAll_.data_ptr<bool>());
-      const int rc =
-          lstm_ ? rela_r2d2_actor_post_step(hr_, rewardAll_.data_ptr<float>(), term,
-                                            static_cast<const rela_lstmnet*>(lease.online),
-                                            static_cast<const rela_lstmnet*>(lease.target), 0, nullptr, compute_)
-                : rela_apex_actor_post_step(h_, rewardAll_.data_ptr<float>(), term, 0,
-                                            static_cast<const rela_ffnet*>(lease.online),
-                                            static_cast<const rela_ffnet*>(lease.target), 0, nullptr, compute_);
+      const int rc = shard_->post_step(shard_.h, rewardAll_.data_ptr<float>(), term, lease.online, lease.target, compute_);
       locker_->releaseModel(lease.id);
       if (rc != RELA_EWOULDBLOCK) check(rc, "postStep (batched)");  // dropped block after shutdown
       // The next round's frames land in the history slot this tick just read (the ring reuses
@@ -1324,15 +1392,21 @@ class ActorCohort {
       // order; the reference would issue one block per thread (only the float block-sum grouping of
       // sum_ differs, far below the fp tolerance of the priorities themselves)
       rela_replay* rep = rnnReplay_->handle(locker_.get(), dev, A, burnin_ + seqLen_ + n_, seqLen_ + n_);
-      check(rela_r2d2_actor_create(&hr_, T_ * K_, K_, A, n_, gamma_, seqLen_, burnin_, locker_->eta(), rep,
+      rela_r2d2_actor* h = nullptr;
+      check(rela_r2d2_actor_create(&h, T_ * K_, K_, A, n_, gamma_, seqLen_, burnin_, locker_->eta(), rep,
                                    0xC2B2AE3D27D4EB4Full * (++counter), dev),
             "rela_r2d2_actor_create");
-      enableDedup(hr_, rep);
+      shard_.h = h;
+      shard_.api = &kR2D2Shard;
+      enableDedup(shard_, rep);
     } else {
       rela_replay* rep = replay_->handle(locker_.get(), dev, A);
-      check(rela_apex_actor_create(&h_, T_ * K_, K_, A, n_, gamma_, rep, 0xA24BAED4963EE407ull * (++counter), dev),
+      rela_apex_actor* h = nullptr;
+      check(rela_apex_actor_create(&h, T_ * K_, K_, A, n_, gamma_, rep, 0xA24BAED4963EE407ull * (++counter), dev),
             "rela_apex_actor_create");
-      enableDedup(h_, rep);
+      shard_.h = h;
+      shard_.api = &kApexShard;
+      enableDedup(shard_, rep);
     }
     created_ = true;
     auto pin = [](torch::Tensor t) { return torch::cuda::is_available() ? t.pin_memory() : t; };
@@ -1344,20 +1418,18 @@ class ActorCohort {
     terminalAll_ = pin(torch::zeros({R}, torch::kBool));
     restartAll_ = pin(torch::full({R}, 2, torch::kUInt8));
     planeHost_ = pin(torch::zeros({R, 84 * 84}, torch::kUInt8));
-    planeStage_ = lstm_ ? rela_r2d2_actor_plane_stage(hr_) : rela_apex_actor_plane_stage(h_);
+    planeStage_ = shard_->plane_stage(shard_.h);
     if (!planeStage_) throw std::runtime_error("ActorCohort: could not allocate the plane stage");
     if (screens) {
       const int H = (int)screens->size(2), W = (int)screens->size(3);
       if (indexed)
-        check(lstm_ ? rela_r2d2_actor_set_screen_input_indexed(hr_, H, W) : rela_apex_actor_set_screen_input_indexed(h_, H, W),
-              "set_screen_input_indexed");
+        check(shard_->set_screen_input_indexed(shard_.h, H, W), "set_screen_input_indexed");
       else
-        check(lstm_ ? rela_r2d2_actor_set_screen_input(hr_, H, W) : rela_apex_actor_set_screen_input(h_, H, W),
-              "set_screen_input");
-      screenStage_ = lstm_ ? rela_r2d2_actor_screen_stage(hr_) : rela_apex_actor_screen_stage(h_);
+        check(shard_->set_screen_input(shard_.h, H, W), "set_screen_input");
+      screenStage_ = shard_->screen_stage(shard_.h);
       screenBytes_ = (int64_t)2 * H * W * (indexed ? 1 : 3);
       if (indexed) {
-        paletteStage_ = lstm_ ? rela_r2d2_actor_palette_stage(hr_) : rela_apex_actor_palette_stage(h_);
+        paletteStage_ = shard_->palette_stage(shard_.h);
         paletteSent_.assign(T_, 0);
       }
     }
@@ -1371,12 +1443,12 @@ class ActorCohort {
   std::shared_ptr<FFPrioritizedReplay> replay_;
   std::shared_ptr<RNNPrioritizedReplay> rnnReplay_;
   const bool lstm_ = false;
+  const std::string name_ = lstm_ ? "R2D2Actor" : "DQNActor";  // the members' class, for messages
   const int seqLen_ = 0, burnin_ = 0;
   const int n_, K_;
   const float gamma_;
   const int T_;
-  rela_apex_actor* h_ = nullptr;
-  rela_r2d2_actor* hr_ = nullptr;
+  Shard shard_;
   bool created_ = false;
   void *compute_ = nullptr, *upload_ = nullptr;
   torch::Tensor actionAll_, epsAll_, legalAll_, rewardAll_, terminalAll_, restartAll_, planeHost_;
@@ -1399,11 +1471,7 @@ class ActorCohort {
 // gets its screen stage, then every act makes ONE copy of obs["__screens"] into it and the shard writes the frame stacks
 // of its observation slot on the device.  `restart` is this actor's page-locked copy of the flags.
 // With obs["__palette"] the screens are palette indices: the indexed set-up, and the rows' tables go up with the first act.
-template <class Shard>
-void privateScreensToStacks(Shard* h, const TensorDict& obs, int rows, int device, void* stream, torch::Tensor& restart,
-                            int (*setInput)(Shard*, int, int), int (*setInputIndexed)(Shard*, int, int),
-                            void* (*stage)(Shard*), void* (*paletteStage)(Shard*),
-                            int (*toStacks)(Shard*, const uint8_t*, void*)) {
+void privateScreensToStacks(Shard& sh, const TensorDict& obs, int rows, int device, void* stream, torch::Tensor& restart) {
   const auto& scr = obs.at("__screens");
   const auto pal = obs.find("__palette");
   const bool indexed = pal != obs.end();
@@ -1418,43 +1486,36 @@ void privateScreensToStacks(Shard* h, const TensorDict& obs, int rows, int devic
     throw std::runtime_error("act: obs['__screens'] must be contiguous uint8 [batchsize,2,H,W,3]");
   }
   if (!restart.defined()) {
-    check((indexed ? setInputIndexed : setInput)(h, (int)scr.size(2), (int)scr.size(3)),
+    check((indexed ? sh->set_screen_input_indexed : sh->set_screen_input)(sh.h, (int)scr.size(2), (int)scr.size(3)),
           indexed ? "set_screen_input_indexed" : "set_screen_input");
     if (indexed)
-      check(rela_memcpy_h2d_async(paletteStage(h), pal->second.data_ptr(), (int64_t)rows * kPaletteBytes, stream, device),
+      check(rela_memcpy_h2d_async(sh->palette_stage(sh.h), pal->second.data_ptr(), (int64_t)rows * kPaletteBytes, stream, device),
             "rela_memcpy_h2d_async");
     restart = torch::zeros({rows}, torch::kUInt8);
     if (torch::cuda::is_available()) restart = restart.pin_memory();
-  } else if (indexed != (paletteStage(h) != nullptr)) {
+  } else if (indexed != (sh->palette_stage(sh.h) != nullptr)) {
     throw std::runtime_error("act: the screen format (RGB or indexed) changed after the first act");
   }
-  check(rela_memcpy_h2d_async(stage(h), scr.data_ptr(), (int64_t)scr.nbytes(), stream, device), "rela_memcpy_h2d_async");
+  check(rela_memcpy_h2d_async(sh->screen_stage(sh.h), scr.data_ptr(), (int64_t)scr.nbytes(), stream, device), "rela_memcpy_h2d_async");
   std::memcpy(restart.data_ptr<uint8_t>(), obs.at("__stack_restart").data_ptr<uint8_t>(), (size_t)rows);
-  check(toStacks(h, restart.data_ptr<uint8_t>(), stream), "screens_to_stacks");
+  check(sh->screens_to_stacks(sh.h, restart.data_ptr<uint8_t>(), stream), "screens_to_stacks");
 }
 
 // =====================================================================================
-// DQNActor (rela/dqn_actor.h:126-211)
+// DQNActor (rela/dqn_actor.h:126-211) and R2D2Actor (rela/r2d2_actor.h:189-353): one implementation over a private
+// shard (or a seat in an ActorCohort).  The two classes add their constructors, their shard's create call and their names.
 // =====================================================================================
-class DQNActor : public Actor {
+template <class ReplayT>
+class ShardActor : public Actor {
  public:
-  DQNActor(std::shared_ptr<ModelLocker> locker, int multiStep, int batchsize, float gamma,
-           std::shared_ptr<FFPrioritizedReplay> replay)
-      : batchsize_(batchsize), multiStep_(multiStep), gamma_(gamma), locker_(std::move(locker)),
-        replay_(std::move(replay)) {}
-
-  // evaluation mode: one env, no replay (dqn_actor.h:141-147)
-  explicit DQNActor(std::shared_ptr<ModelLocker> locker)
-      : batchsize_(1), multiStep_(1), gamma_(1.f), locker_(std::move(locker)), replay_(nullptr) {}
-
-  ~DQNActor() override {
-    rela_apex_actor_destroy(h_);
+  ~ShardActor() override {
+    shard_.reset();  // before its stream
     if (stream_) rela_stream_destroy(stream_, locker_->execDevice);
   }
 
   int numAct() const {
     if (cohort_) return cohort_->numAct(member_);
-    return h_ ? (int)rela_apex_actor_num_act(h_) : 0;
+    return shard_ ? (int)shard_->num_act(shard_.h) : 0;
   }
 
   // batching key: actors that agree on all of these may share one device shard
@@ -1465,7 +1526,7 @@ class DQNActor : public Actor {
   int multiStep() const { return multiStep_; }
   float gamma() const { return gamma_; }
   std::shared_ptr<ModelLocker> locker() const { return locker_; }
-  std::shared_ptr<FFPrioritizedReplay> replay() const { return replay_; }
+  std::shared_ptr<ReplayT> replay() const { return replay_; }
   void joinCohort(std::shared_ptr<ActorCohort> c, int member) {
     cohort_ = std::move(c);
     member_ = member;
@@ -1484,16 +1545,11 @@ class DQNActor : public Actor {
     const auto& legal = obs.at("legal_move");
     const auto& eps = obs.at("eps");
     if (s.size(0) != batchsize_ || s.numel() != (int64_t)batchsize_ * kObsBytes || s.dtype() != torch::kUInt8)
-      throw std::runtime_error("DQNActor.act: obs['s'] must be uint8 [batchsize,4,84,84]");
+      throw std::runtime_error(name_ + ".act: obs['s'] must be uint8 [batchsize,4,84,84]");
     const int A = (int)legal.size(1);
-    if (!h_) {
-      static std::atomic<uint64_t> counter{0};
-      rela_replay* rep = replay_ ? replay_->handle(locker_.get(), locker_->execDevice, A) : nullptr;
+    if (!shard_) {
       check(rela_stream_create(&stream_, locker_->execDevice), "rela_stream_create");
-      check(rela_apex_actor_create(&h_, batchsize_, batchsize_, A, multiStep_, gamma_, rep,
-                                   0x9E3779B97F4A7C15ull * (++counter), locker_->execDevice),
-            "rela_apex_actor_create");
-      enableDedup(h_, rep);
+      createShard(A);
       action_ = torch::zeros({batchsize_}, torch::kInt64);
       if (torch::cuda::is_available()) action_ = action_.pin_memory();
       epsHost_ = torch::zeros({batchsize_}, torch::kFloat32);
@@ -1516,48 +1572,56 @@ class DQNActor : public Actor {
     auto sc = s.contiguous();
     const uint8_t* obsHost = sc.data_ptr<uint8_t>();
     if (obs.count("__screens")) {  // the stacks are built on the device from the screens
-      privateScreensToStacks(h_, obs, batchsize_, locker_->execDevice, stream_, screenRestart_, rela_apex_actor_set_screen_input,
-                             rela_apex_actor_set_screen_input_indexed, rela_apex_actor_screen_stage, rela_apex_actor_palette_stage,
-                             rela_apex_actor_screens_to_stacks);
+      privateScreensToStacks(shard_, obs, batchsize_, locker_->execDevice, stream_, screenRestart_);
       obsHost = nullptr;
     }
     auto lease = locker_->getModel();
-    if (lease.kind != ModelLocker::kFF) {
+    if (lease.kind != netKind_) {
       locker_->releaseModel(lease.id);
-      throw std::runtime_error("DQNActor needs an AtariFFNet-shaped agent in its ModelLocker");
+      throw std::runtime_error(name_ + " needs an " + netName_ + "-shaped agent in its ModelLocker");
     }
-    const int rc = rela_apex_actor_act(h_, static_cast<const rela_ffnet*>(lease.online), obsHost, epsPtr, legalPtr,
-                                       action_.data_ptr<int64_t>(), nullptr, stream_);
+    const int rc = shard_->act(shard_.h, lease.online, obsHost, epsPtr, legalPtr, action_.data_ptr<int64_t>(), stream_);
     locker_->releaseModel(lease.id);
-    check(rc, "DQNActor.act");
+    if (rc != RELA_OK) fail(name_ + ".act", rc);
     return TensorDict{{"a", action_}};
   }
 
   void setRewardAndTerminal(torch::Tensor& r, torch::Tensor& t) override {
-    if (!replay_) throw std::runtime_error("DQNActor: evaluation actor has no replay");  // :175
+    if (!replay_) throw std::runtime_error(name_ + ": evaluation actor has no replay");  // dqn_actor.h:175
     if (cohort_) return cohort_->setRewardAndTerminal(member_, r, t);
     reward_ = r.to(torch::kFloat32).contiguous();
     terminal_ = t.to(torch::kBool).contiguous();
   }
 
   void postStep() override {
-    if (!replay_) throw std::runtime_error("DQNActor: evaluation actor has no replay");  // :182
+    if (!replay_) throw std::runtime_error(name_ + ": evaluation actor has no replay");  // dqn_actor.h:182
     if (cohort_) return cohort_->postStep(member_);
     auto lease = locker_->getModel();
-    const int rc = rela_apex_actor_post_step(h_, reward_.data_ptr<float>(),
-                                             reinterpret_cast<const uint8_t*>(terminal_.data_ptr<bool>()), 0,
-                                             static_cast<const rela_ffnet*>(lease.online),
-                                             static_cast<const rela_ffnet*>(lease.target), 0, nullptr, stream_);
+    const int rc = shard_->post_step(shard_.h, reward_.data_ptr<float>(),
+                                     reinterpret_cast<const uint8_t*>(terminal_.data_ptr<bool>()), lease.online, lease.target,
+                                     stream_);
     locker_->releaseModel(lease.id);
-    if (rc != RELA_EWOULDBLOCK) check(rc, "DQNActor.postStep");  // dropped block after replay shutdown
+    if (rc != RELA_OK && rc != RELA_EWOULDBLOCK) fail(name_ + ".postStep", rc);  // dropped block after replay shutdown
   }
 
- private:
+ protected:
+  ShardActor(const char* name, int netKind, const char* netName, std::shared_ptr<ModelLocker> locker, int multiStep,
+             int batchsize, float gamma, std::shared_ptr<ReplayT> replay)
+      : name_(name), netName_(netName), netKind_(netKind), batchsize_(batchsize), multiStep_(multiStep), gamma_(gamma),
+        locker_(std::move(locker)), replay_(std::move(replay)) {}
+
+  // this actor's private shard of batchsize_ rows in one group, with de-duplication as its replay has it
+  virtual void createShard(int A) = 0;
+
+  const std::string name_, netName_;
+  const int netKind_;
   const int batchsize_, multiStep_;
   const float gamma_;
   std::shared_ptr<ModelLocker> locker_;
-  std::shared_ptr<FFPrioritizedReplay> replay_;
-  rela_apex_actor* h_ = nullptr;
+  std::shared_ptr<ReplayT> replay_;
+  Shard shard_;
+
+ private:
   void* stream_ = nullptr;  // this actor thread's private HIP stream
   torch::Tensor action_, epsHost_, legalHost_, reward_, terminal_, screenRestart_;
   bool constsValid_ = false;
@@ -1565,142 +1629,63 @@ class DQNActor : public Actor {
   int member_ = -1;
 };
 
-// =====================================================================================
-// R2D2Actor (rela/r2d2_actor.h:189-353)
-// =====================================================================================
-class R2D2Actor : public Actor {
+class DQNActor : public ShardActor<FFPrioritizedReplay> {
+ public:
+  DQNActor(std::shared_ptr<ModelLocker> locker, int multiStep, int batchsize, float gamma,
+           std::shared_ptr<FFPrioritizedReplay> replay)
+      : ShardActor("DQNActor", ModelLocker::kFF, "AtariFFNet", std::move(locker), multiStep, batchsize, gamma,
+                   std::move(replay)) {}
+
+  // evaluation mode: one env, no replay (dqn_actor.h:141-147)
+  explicit DQNActor(std::shared_ptr<ModelLocker> locker) : DQNActor(std::move(locker), 1, 1, 1.f, nullptr) {}
+
+ private:
+  void createShard(int A) override {
+    static std::atomic<uint64_t> counter{0};
+    const int dev = locker_->execDevice;
+    rela_replay* rep = replay_ ? replay_->handle(locker_.get(), dev, A) : nullptr;
+    rela_apex_actor* h = nullptr;
+    check(rela_apex_actor_create(&h, batchsize_, batchsize_, A, multiStep_, gamma_, rep, 0x9E3779B97F4A7C15ull * (++counter),
+                                 dev),
+          "rela_apex_actor_create");
+    shard_.h = h;
+    shard_.api = &kApexShard;
+    enableDedup(shard_, rep);
+  }
+};
+
+class R2D2Actor : public ShardActor<RNNPrioritizedReplay> {
  public:
   R2D2Actor(std::shared_ptr<ModelLocker> locker, int multiStep, int batchsize, float gamma, int seqLen, int burnin,
             std::shared_ptr<RNNPrioritizedReplay> replay)
-      : batchsize_(batchsize), multiStep_(multiStep), gamma_(gamma), seqLen_(seqLen), burnin_(burnin),
-        locker_(std::move(locker)), replay_(std::move(replay)) {
+      : ShardActor("R2D2Actor", ModelLocker::kLSTM, "AtariLSTMNet", std::move(locker), multiStep, batchsize, gamma,
+                   std::move(replay)),
+        seqLen_(seqLen), burnin_(burnin) {
     if (burnin_ > seqLen_ || multiStep_ > seqLen_)  // r2d2_actor.h:25-26
       throw std::invalid_argument("R2D2Actor needs burn_in <= seq_len and multi_step <= seq_len");
   }
 
   // evaluation mode (r2d2_actor.h:208-215)
-  explicit R2D2Actor(std::shared_ptr<ModelLocker> locker)
-      : batchsize_(1), multiStep_(1), gamma_(1.f), seqLen_(1), burnin_(0), locker_(std::move(locker)),
-        replay_(nullptr) {}
+  explicit R2D2Actor(std::shared_ptr<ModelLocker> locker) : R2D2Actor(std::move(locker), 1, 1, 1.f, 1, 0, nullptr) {}
 
-  ~R2D2Actor() override {
-    rela_r2d2_actor_destroy(h_);
-    if (stream_) rela_stream_destroy(stream_, locker_->execDevice);
-  }
-
-  int numAct() const {
-    if (cohort_) return cohort_->numAct(member_);
-    return h_ ? (int)rela_r2d2_actor_num_act(h_) : 0;
-  }
-  // batching key: actors that agree on all of these may share one device shard
-  bool trainable() const { return replay_ != nullptr; }
-  const void* lockerKey() const { return locker_.get(); }
-  const void* replayKey() const { return replay_.get(); }
-  int batchsize() const { return batchsize_; }
-  int multiStep() const { return multiStep_; }
-  float gamma() const { return gamma_; }
   int seqLen() const { return seqLen_; }
   int burnin() const { return burnin_; }
-  std::shared_ptr<ModelLocker> locker() const { return locker_; }
-  std::shared_ptr<RNNPrioritizedReplay> replay() const { return replay_; }
-  void joinCohort(std::shared_ptr<ActorCohort> c, int member) {
-    cohort_ = std::move(c);
-    member_ = member;
-  }
-  void onLoopExit() override {
-    if (cohort_) cohort_->leave(member_);
-  }
-  void onShutdown() override {
-    if (cohort_) cohort_->shutdown();
-    if (replay_) replay_->shutdown();
-  }
-
-  TensorDict act(TensorDict& obs) override {
-    if (cohort_) return cohort_->act(member_, obs);
-    const auto& s = obs.at("s");
-    const auto& legal = obs.at("legal_move");
-    const auto& eps = obs.at("eps");
-    if (s.size(0) != batchsize_ || s.numel() != (int64_t)batchsize_ * kObsBytes || s.dtype() != torch::kUInt8)
-      throw std::runtime_error("R2D2Actor.act: obs['s'] must be uint8 [batchsize,4,84,84]");
-    const int A = (int)legal.size(1);
-    if (!h_) {
-      static std::atomic<uint64_t> counter{0};
-      const int T = burnin_ + seqLen_ + multiStep_;
-      rela_replay* rep = replay_ ? replay_->handle(locker_.get(), locker_->execDevice, A, T, seqLen_ + multiStep_) : nullptr;
-      check(rela_stream_create(&stream_, locker_->execDevice), "rela_stream_create");
-      check(rela_r2d2_actor_create(&h_, batchsize_, batchsize_, A, multiStep_, gamma_, seqLen_, burnin_,
-                                   locker_->eta(), rep, 0xD1B54A32D192ED03ull * (++counter), locker_->execDevice),
-            "rela_r2d2_actor_create");
-      enableDedup(h_, rep);
-      action_ = torch::zeros({batchsize_}, torch::kInt64);
-      if (torch::cuda::is_available()) action_ = action_.pin_memory();
-      epsHost_ = torch::zeros({batchsize_}, torch::kFloat32);
-      legalHost_ = torch::zeros({batchsize_, A}, torch::kFloat32);
-    }
-    const float* epsPtr = nullptr;
-    const float* legalPtr = nullptr;
-    auto e = eps.reshape({batchsize_}).to(torch::kFloat32).contiguous();
-    if (!constsValid_ || std::memcmp(e.data_ptr(), epsHost_.data_ptr(), e.nbytes()) != 0) {
-      epsHost_.copy_(e);
-      epsPtr = epsHost_.data_ptr<float>();
-    }
-    auto l = legal.to(torch::kFloat32).contiguous();
-    if (!constsValid_ || std::memcmp(l.data_ptr(), legalHost_.data_ptr(), l.nbytes()) != 0) {
-      legalHost_.copy_(l);
-      legalPtr = legalHost_.data_ptr<float>();
-    }
-    constsValid_ = true;
-    auto sc = s.contiguous();
-    const uint8_t* obsHost = sc.data_ptr<uint8_t>();
-    if (obs.count("__screens")) {  // the stacks are built on the device from the screens
-      privateScreensToStacks(h_, obs, batchsize_, locker_->execDevice, stream_, screenRestart_, rela_r2d2_actor_set_screen_input,
-                             rela_r2d2_actor_set_screen_input_indexed, rela_r2d2_actor_screen_stage, rela_r2d2_actor_palette_stage,
-                             rela_r2d2_actor_screens_to_stacks);
-      obsHost = nullptr;
-    }
-    auto lease = locker_->getModel();
-    if (lease.kind != ModelLocker::kLSTM) {
-      locker_->releaseModel(lease.id);
-      throw std::runtime_error("R2D2Actor needs an AtariLSTMNet-shaped agent in its ModelLocker");
-    }
-    const int rc = rela_r2d2_actor_act(h_, static_cast<const rela_lstmnet*>(lease.online), obsHost,
-                                       epsPtr, legalPtr, action_.data_ptr<int64_t>(), nullptr, stream_);
-    locker_->releaseModel(lease.id);
-    check(rc, "R2D2Actor.act");
-    return TensorDict{{"a", action_}};
-  }
-
-  void setRewardAndTerminal(torch::Tensor& r, torch::Tensor& t) override {
-    if (!replay_) throw std::runtime_error("R2D2Actor: evaluation actor has no replay");
-    if (cohort_) return cohort_->setRewardAndTerminal(member_, r, t);
-    reward_ = r.to(torch::kFloat32).contiguous();
-    terminal_ = t.to(torch::kBool).contiguous();
-  }
-
-  void postStep() override {
-    if (!replay_) throw std::runtime_error("R2D2Actor: evaluation actor has no replay");
-    if (cohort_) return cohort_->postStep(member_);
-    auto lease = locker_->getModel();
-    const int rc = rela_r2d2_actor_post_step(h_, reward_.data_ptr<float>(),
-                                             reinterpret_cast<const uint8_t*>(terminal_.data_ptr<bool>()),
-                                             static_cast<const rela_lstmnet*>(lease.online),
-                                             static_cast<const rela_lstmnet*>(lease.target), 0, nullptr, stream_);
-    locker_->releaseModel(lease.id);
-    if (rc != RELA_EWOULDBLOCK) check(rc, "R2D2Actor.postStep");  // dropped block after replay shutdown
-  }
 
  private:
-  const int batchsize_, multiStep_;
-  const float gamma_;
+  void createShard(int A) override {
+    static std::atomic<uint64_t> counter{0};
+    const int dev = locker_->execDevice, T = burnin_ + seqLen_ + multiStep_;
+    rela_replay* rep = replay_ ? replay_->handle(locker_.get(), dev, A, T, seqLen_ + multiStep_) : nullptr;
+    rela_r2d2_actor* h = nullptr;
+    check(rela_r2d2_actor_create(&h, batchsize_, batchsize_, A, multiStep_, gamma_, seqLen_, burnin_, locker_->eta(), rep,
+                                 0xD1B54A32D192ED03ull * (++counter), dev),
+          "rela_r2d2_actor_create");
+    shard_.h = h;
+    shard_.api = &kR2D2Shard;
+    enableDedup(shard_, rep);
+  }
+
   const int seqLen_, burnin_;
-  std::shared_ptr<ModelLocker> locker_;
-  std::shared_ptr<RNNPrioritizedReplay> replay_;
-  rela_r2d2_actor* h_ = nullptr;
-  void* stream_ = nullptr;
-  torch::Tensor action_, epsHost_, legalHost_, reward_, terminal_, screenRestart_;
-  bool constsValid_ = false;
-  std::shared_ptr<ActorCohort> cohort_;  // set when this actor is batched with its siblings
-  int member_ = -1;
 };
 
 // =====================================================================================
