@@ -14,8 +14,13 @@
 //   a2     ReLU, split, staged in LDS as records and copied out whole (coalesced 16-byte stores) under the next frame's
 //          conv1.
 // One block of FOUR waves per CU (512 registers each: 240 hold weights), persistent over the frames b, b + grid, ...;
-// two barriers per frame.  A1OUT (the learner's online(obs) pass): a1 is also written to HBM as f32 channel-last, what
-// the backward kernels read.
+// two barriers per frame.  Registers by construction: conv2's 192 weight registers are pinned into the accumulator half
+// of the file (MFMA A operands only) beside the sums; conv1's digits, every address and every staged byte live in the 256
+// VGPRs: no scratch in either instantiation.  Per frame a thread stages two units of four cells by 16-byte row loads
+// (uniform frame base + 32-bit offset + immediate row offset); the offsets that do not depend on the frame (T1 / T2 / O
+// places of conv1's tiles, conv2's tiles and the copy-out chunks) are computed once before the frame loop.
+// A1OUT (the learner's online(obs) pass): a1 is also written to HBM as f32 channel-last, what the backward kernels
+// read.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,6 +30,7 @@ namespace rela_amd {
 namespace s3 {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));  // a frame's rows are 4-byte aligned only
 // probe builds only (tools/ubench/s3_probe.hip): leave one part of the kernel out to see what it costs
 #ifndef C12_ABLATE
 #define C12_ABLATE 0
@@ -45,8 +51,10 @@ struct Conv12S {
   static constexpr int SPARE = T1_BYTES + T2_BYTES + O_BYTES;  // 256 B: rows past the last pixel land here
   static constexpr int LDS_TOTAL = SPARE + 256;
   static_assert(LDS_TOTAL <= 160 * 1024, "LDS budget");
-  static constexpr int CELLS = 4 * NPIX, IT = (CELLS + kT - 1) / kT;  // 7 cells per thread
   static constexpr int OV16 = 81 * 24, OIT = (OV16 + kT - 1) / kT;    // 16-byte chunks of an output tile: 8 per thread
+  // staging by 16-byte row loads: a unit = four cells side by side (X0 .. X0 + 3) of one plane, six units per cell row
+  // (X0 = 0, 4, 8, 12, 16 and 17: the sixth unit, cells 17 .. 20, re-writes the cells 17 .. 19 with the same bytes)
+  static constexpr int UNITS = 4 * GW * 6, UIT = (UNITS + kT - 1) / kT;  // 504: two units per thread
   static constexpr int KS2 = 16;
   // k-step -> tap in pack_f32emu_at's mode-1 order (f32emu::ProbConv2::tap), as byte offset inside the a1 image
   static constexpr int tap2(int ks) {
@@ -69,7 +77,6 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
   uint8_t* t1 = smem_c12;
   uint8_t* t2 = t1 + F::T1_BYTES;
   uint8_t* otile = t2 + F::T2_BYTES;
-  uint8_t* spare = smem_c12 + F::SPARE;
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int bid = blockIdx.x, nblk = gridDim.x;
@@ -91,29 +98,48 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
   for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
     for (int d = 0; d < 3; ++d) wd[ks][d] = __builtin_bit_cast(i32x4, W1d[((d * 2 + ct1) * 4 + ks) * 64 + lane]);
+  // registers by construction (the pins are empty statements: they only say where a value lives at that point).  conv2's
+  // 192 weight registers are MFMA A operands only: they sit in the accumulator half of the register file, whose other 64
+  // registers hold the sums (60 in conv1's five-tile pass, 8 in conv2).  conv1's 48 digit registers and everything VALU,
+  // LDS and VMEM touch share the 256 architectural VGPRs: no spills, no copies between the halves but the sums' read-out.
+  // (All 240 in the accumulator half leaves 16 for the sums: in the compiled loop conv1 then moves every sum
+  // in and out around its MFMA.)
+  auto pin_weights = [&]() __attribute__((always_inline)) {
+#pragma unroll
+    for (int ks = 0; ks < F::KS2; ++ks)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) asm volatile("" : "+a"(w2[ks][p]));
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+      for (int d = 0; d < 3; ++d) asm volatile("" : "+v"(wd[ks][d]));
+  };
+  pin_weights();
   const int ch1 = ct1 * 16 + 4 * g, ch2 = wave * 16 + 4 * g;
   const f32x4 sc1 = *reinterpret_cast<const f32x4*>(scale1 + ch1), bv1 = *reinterpret_cast<const f32x4*>(bias1q + ch1);
   const f32x4 bv2 = *reinterpret_cast<const f32x4*>(bias2 + ch2);
 
-  // ---- staging of a frame's cells (clamped cell index; a cell = rows 4Y .. 4Y + 3 x 4 bytes of one plane)
-  uint32_t st[F::IT][4];
-  int cgoff[F::IT], cloff[F::IT];  // (frame-invariant: this thread's cells in the frame and in T1)
+  // ---- staging of a frame by 16-byte row loads: unit u = rows 4Y .. 4Y + 3 x 16 bytes from cell X0 of one plane, i.e.
+  // four cells side by side; which dword of which row goes to which cell is only a choice of registers (clamped unit index)
+  u32x4_a4 sq[F::UIT][4];
+  uint32_t ugoff[F::UIT], uloff[F::UIT];  // (frame-invariant: this thread's units in the frame and in T1)
 #pragma unroll
-  for (int j = 0; j < F::IT; ++j) {
-    const int c = min(tid + j * F::kT, F::CELLS - 1);
-    const int pl = c / F::NPIX, P = c - pl * F::NPIX;
-    const int Y = P / F::GW, X = P - Y * F::GW;
-    cgoff[j] = pl * F::PLANE_ELEMS + 4 * Y * 84 + 4 * X;
-    cloff[j] = pl * F::PLANE1 + P * 16;
+  for (int j = 0; j < F::UIT; ++j) {
+    const int u = min(tid + j * F::kT, F::UNITS - 1);
+    const int pl = u / (F::GW * 6), rem = u - pl * (F::GW * 6);
+    const int Y = rem / 6, qi = rem - Y * 6;
+    const int X0 = qi < 5 ? 4 * qi : 17;
+    ugoff[j] = (uint32_t)(pl * F::PLANE_ELEMS + 4 * Y * 84 + 4 * X0);
+    uloff[j] = (uint32_t)(pl * F::PLANE1 + (Y * F::GW + X0) * 16);
   }
-  auto g_load1 = [&](int fr, int j) __attribute__((always_inline)) {
-    const uint8_t* src = in + (size_t)fr * F::IN_ELEMS + cgoff[j];
+  auto g_load4 = [&](int fr, int j) __attribute__((always_inline)) {
+    const uint8_t* fb = in + (size_t)fr * F::IN_ELEMS;  // uniform frame base + 32-bit offset + the row as immediate
 #pragma unroll
-    for (int r = 0; r < 4; ++r) st[j][r] = *reinterpret_cast<const uint32_t*>(src + r * 84);
+    for (int r = 0; r < 4; ++r) sq[j][r] = *reinterpret_cast<const u32x4_a4*>(fb + (size_t)ugoff[j] + r * 84);
   };
-  auto s_store = [&](int j) __attribute__((always_inline)) {  // x -> x - 128 as int8: flip the sign bits
-    *reinterpret_cast<uint4*>(t1 + cloff[j]) = make_uint4(st[j][0] ^ 0x80808080u, st[j][1] ^ 0x80808080u, st[j][2] ^ 0x80808080u,
-                                                          st[j][3] ^ 0x80808080u);
+  auto s_store4 = [&](int j, int k) __attribute__((always_inline)) {  // cell X0 + k of unit j; x -> x - 128: flip the sign bits
+    *reinterpret_cast<uint4*>(t1 + uloff[j] + k * 16) = make_uint4(sq[j][0][k] ^ 0x80808080u, sq[j][1][k] ^ 0x80808080u,
+                                                                   sq[j][2][k] ^ 0x80808080u, sq[j][3][k] ^ 0x80808080u);
   };
 
   // ---- the output tile of the previous frame -> HBM, in slices behind conv1's MFMAs
@@ -131,19 +157,38 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
     else if constexpr (j == 6) return oc6;
     else return oc7;
   };
-  auto o_read = [&](auto jt) __attribute__((always_inline)) {
-    constexpr int j = decltype(jt)::value;
+  // (frame-invariant: chunk j of this thread inside O.  Its place in the frame's records, i * 16, is recomputed at each
+  // store -- two VALU instructions; eight more live registers across the frame loop bring 20 / 28 B of scratch back)
+  uint32_t oloff[F::OIT];
+#pragma unroll
+  for (int j = 0; j < F::OIT; ++j) {
     const int i = min(tid + j * F::kT, F::OV16 - 1);
     const int px = i / 24, u = i - px * 24;
-    oc_at(jt) = *reinterpret_cast<const uint4*>(otile + px * F::OROW + u * 16);
+    oloff[j] = (uint32_t)(px * F::OROW + u * 16);
+  }
+  auto o_read = [&](auto jt) __attribute__((always_inline)) {
+    constexpr int j = decltype(jt)::value;
+    oc_at(jt) = *reinterpret_cast<const uint4*>(otile + oloff[j]);
   };
   auto o_write = [&](auto jt) __attribute__((always_inline)) {
     constexpr int j = decltype(jt)::value;
     const int i = min(tid + j * F::kT, F::OV16 - 1);
     // (first frame: O holds nothing yet -- the bytes go to frame n's own rows, which its real tile overwrites later from
     // the same thread; no branch in conv1's instruction stream)
-    reinterpret_cast<uint4*>(out + (size_t)(prev >= 0 ? prev : n) * (81 * 384))[i] = oc_at(jt);
+    uint8_t* ob = out + (size_t)(prev >= 0 ? prev : n) * (81 * 384);  // (uniform base + 32-bit offset)
+    *reinterpret_cast<uint4*>(ob + (size_t)(uint32_t)(i * 16)) = oc_at(jt);
   };
+  // conv1's per-tile offsets (frame-invariant): tile rt of this wave -> its pixels' cells in T1 and records in T2
+  uint32_t c1src[13], c1dst[13];
+#pragma unroll
+  for (int t = 0; t < 13; ++t) {
+    const int rt = min(rg1 + 2 * t, 24);
+    const int m = rt * 16 + li;
+    const int oy = m / 20, ox = m - oy * 20;
+    c1src[t] = (uint32_t)(g * F::PLANE1 + (oy * F::GW + ox) * 16);
+    c1dst[t] = (uint32_t)((oy * F::RQ + ox * F::Q) * 16 + ch1 * 2);
+  }
+  const uint32_t a1lane = (uint32_t)((li * 32 + ch1) * 4);
 
   // ---- conv1 over this wave's tiles [T0, T0 + NT): T1 -> split3 records in T2
   auto conv1_pass = [&](auto t0_tag, auto nt_tag, auto&& hook) {
@@ -153,10 +198,7 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       s_hi[t] = s_mid[t] = s_lo[t] = i32x4{0, 0, 0, 0};
-      const int rt = min(rg1 + 2 * (T0 + t), 24);
-      const int m = rt * 16 + li;
-      const int oy = m / 20, ox = m - oy * 20;
-      a1base[t] = g * F::PLANE1 + (oy * F::GW + ox) * 16;
+      a1base[t] = (int)c1src[T0 + t];
     }
     constexpr int TOT = 4 * NT, D = 4;
     uint4 x[D];
@@ -180,12 +222,15 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
       hook(IC<T0 * 4 + IDX>{});
       __builtin_amdgcn_sched_barrier(0);
     });
+    // every sum of the pass stays in its own accumulator registers until the pass's last MFMA has issued: no MFMA is
+    // followed by a read of its own result (the compiler otherwise sends each final MFMA through ONE register tuple and
+    // waits out its latency 3 NT times)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) asm volatile("" : "+a"(s_hi[t]), "+a"(s_mid[t]), "+a"(s_lo[t]));
 #pragma unroll
     for (int t = 0; t < (kNoEpi1 ? 0 : NT); ++t) {
       // (the odd group's thirteenth tile is tile 24 again: the same values to the same addresses as the even group's)
       const int rt = min(rg1 + 2 * (T0 + t), 24);
-      const int m = rt * 16 + li;
-      const int y = m / 20, xx = m - y * 20;
       // the exact integer sum S_hi * 2^16 + S_mid * 2^8 + S_lo enters f32 in two halves (|S_mid * 256 + S_lo| < 2^31; the
       // product with 65536 is exact, so the fused form rounds once where mul + add rounded once too), then ONE rounding
       // for scale and bias (fused: the file is compiled -ffp-contract=off, so the fusion is spelled out)
@@ -200,20 +245,25 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
       }
       uint2 p0, p1, p2;
       split3_4(v, p0, p1, p2);
-      uint8_t* rec = t2 + (size_t)(y * F::RQ + xx * F::Q) * 16 + ch1 * 2;
+      uint8_t* rec = t2 + c1dst[T0 + t];
       *reinterpret_cast<uint2*>(rec) = p0;
       *reinterpret_cast<uint2*>(rec + 64) = p1;
       *reinterpret_cast<uint2*>(rec + 128) = p2;
-      if constexpr (A1OUT)  // the learner's copy: f32 channel-last
-        *reinterpret_cast<f32x4*>(a1_out + ((size_t)n * 400 + m) * 32 + ch1) = v;
+      if constexpr (A1OUT) {  // the learner's copy: f32 channel-last
+        // uniform base (frame and tile) + this lane's pixel and channels
+        uint8_t* ab = reinterpret_cast<uint8_t*>(a1_out + ((size_t)n * 400 + rt * 16) * 32);
+        *reinterpret_cast<f32x4*>(ab + (size_t)a1lane) = v;
+      }
     }
   };
 
   // first frame into T1
 #pragma unroll
-  for (int j = 0; j < F::IT; ++j) g_load1(n, j);
+  for (int j = 0; j < F::UIT; ++j) g_load4(n, j);
 #pragma unroll
-  for (int j = 0; j < F::IT; ++j) s_store(j);
+  for (int j = 0; j < F::UIT; ++j)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s_store4(j, k);
   __syncthreads();
 
   auto copy_hook = [&](auto idx_tag) {
@@ -229,8 +279,22 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
   auto no_hook = [](auto) {};
   static_assert(2 * F::OIT <= 20, "copy-out slots inside conv1's first pass");
 
+  uint32_t xbh[6];  // conv2's per-tile offsets into the a1 image (frame-invariant)
+#pragma unroll
+  for (int t = 0; t < 6; ++t) {
+    const int m = t * 16 + li, mm = m < 81 ? m : 80;
+    const int oy = mm / 9, ox = mm - oy * 9;
+    xbh[t] = (uint32_t)((2 * oy * F::RQ + 2 * ox * F::Q + g) * 16);
+  }
+  uint32_t o2dst[6];  // ... and into O (tile rows past the last pixel: the spare row)
+#pragma unroll
+  for (int t = 0; t < 6; ++t) {
+    const int m = t * 16 + li;
+    o2dst[t] = (uint32_t)((m < 81 ? F::T1_BYTES + F::T2_BYTES + m * F::OROW : F::SPARE) + ch2 * 2);
+  }
   for (; n < N; n += nblk) {
     const int nn = (n + nblk < N) ? n + nblk : n;  // (the last round re-stages its own frame)
+    pin_weights();
     conv1_pass(IC<0>{}, IC<5>{}, copy_hook);
     conv1_pass(IC<5>{}, IC<4>{}, no_hook);
     conv1_pass(IC<9>{}, IC<4>{}, no_hook);
@@ -239,17 +303,11 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
     // ---- conv2 from T2, tile by tile; the next frame's cells go into T1 in the second half
     {
       constexpr int NTILE = 6, TOT = NTILE * F::KS2, D = 3;
-      uint32_t xb[NTILE];
-#pragma unroll
-      for (int t = 0; t < NTILE; ++t) {
-        const int m = t * 16 + li, mm = m < 81 ? m : 80;
-        const int oy = mm / 9, ox = mm - oy * 9;
-        xb[t] = (uint32_t)((2 * oy * F::RQ + 2 * ox * F::Q + g) * 16);
-      }
+      static_assert(NTILE == 6, "xbh / o2dst");
       uint4 xr[D][3];
       auto a_issue = [&](auto idx_tag, int slot) {
         constexpr int IDX = decltype(idx_tag)::value, T = IDX / F::KS2, KS = IDX - T * F::KS2;
-        const uint8_t* ap = t2 + xb[T] + F::koff2(KS);
+        const uint8_t* ap = t2 + xbh[T] + F::koff2(KS);
         xr[slot][0] = *reinterpret_cast<const uint4*>(ap);
         xr[slot][1] = *reinterpret_cast<const uint4*>(ap + 64);
         xr[slot][2] = *reinterpret_cast<const uint4*>(ap + 128);
@@ -272,11 +330,12 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
           asm volatile("" ::"v"(x0), "v"(x1), "v"(x2));
         }
         if constexpr (IDX + D < TOT) a_issue(IC<IDX + D>{}, SLOT);
-        // the next frame's cells: loaded behind items 1, 5, 9, ..., stored (sign bits flipped) in the second half
-        static_for<F::IT>([&](auto jj) {
+        // the next frame's two units: loaded behind items 1 and 13, their eight cells stored (sign bits flipped) behind
+        // items 48, 52, ..., 76
+        static_for<4 * F::UIT>([&](auto jj) {
           constexpr int JJ = decltype(jj)::value;
-          if constexpr (IDX == 1 + 4 * JJ && !kNoStage) g_load1(nn, JJ);
-          if constexpr (IDX == TOT / 2 + 4 * JJ && !kNoStage) s_store(JJ);
+          if constexpr (JJ < F::UIT && IDX == 1 + 12 * JJ && !kNoStage) g_load4(nn, JJ);
+          if constexpr (IDX == TOT / 2 + 4 * JJ && !kNoStage) s_store4(JJ >> 2, JJ & 3);
         });
         if constexpr (KS == F::KS2 - 1 && kNoEpi2) asm volatile("" ::"v"(acc), "v"(accs));
         if constexpr (KS == F::KS2 - 1 && !kNoEpi2) {  // tile T complete: ReLU, split, its record slice into O
@@ -285,8 +344,7 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
           for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
           uint2 p0, p1, p2;
           split3_4(v, p0, p1, p2);
-          const int m = T * 16 + li;
-          uint8_t* rec = (m < 81 ? otile + m * F::OROW : spare) + ch2 * 2;
+          uint8_t* rec = smem_c12 + o2dst[T];
           *reinterpret_cast<uint2*>(rec) = p0;
           *reinterpret_cast<uint2*>(rec + 128) = p1;
           *reinterpret_cast<uint2*>(rec + 256) = p2;
