@@ -242,6 +242,11 @@ int rela_seqscan_search(const float* ring_dev, int64_t ring, int64_t head, int64
  * rela/prioritized_replay.h:188,239,321 (SLEEF powf for the 32-wide vector part, double pow for the n % 32 tail) */
 int rela_debug_pow(const float* x_dev, int n, float exponent, float* out_dev, void* stream);
 
+/* Test tap: h_out[i] = h(x[i]) and hinv_out[i] = h_inv(x[i]) (either may be NULL) of the invertible value rescaling
+ * h(x) = sign(x) (sqrt(|x| + 1) - 1) + eps x, exactly as the TD-target kernels evaluate it (csrc/value_rescale.h; eps > 0).
+ * No reference counterpart: see rela_apex_actor_set_value_rescale.                                        */
+int rela_debug_value_rescale(int n, const float* x_dev, float eps, float* h_out_dev, float* hinv_out_dev, void* stream);
+
 /* Test hook of the scan index (csrc/seqsum.hip): 0 = normal; 1 = binade guesses perturbed, 2 = every guess
  * invalid, 3 = crossing records split one element late.  The guesses only decide how much work the exact
  * evaluation skips, so every result must be bit-identical in all modes (tests/test_replay_gpu.py).      */
@@ -466,6 +471,12 @@ int64_t rela_apex_actor_num_act(const rela_apex_actor* a); /* numAct()  dqn_acto
  * on = 1 (default): reuse both; 2: only the one of next_obs; 0: always recompute, i.e. the reference's
  * 4 forwards per step */
 int rela_apex_actor_set_reuse(rela_apex_actor* a, int on);
+/* Invertible value rescaling of the priority's TD target (R2D2 as published, Kapturowski et al. 2019; the reference
+ * leaves it out and clips rewards in its env instead, so ApexAgent.td_err apex.py:30-45 has no such step):
+ * target = h(reward + bootstrap * gamma ** n * h_inv(target_q)), h(x) = sign(x) (sqrt(|x| + 1) - 1) + eps x, in the
+ * fixed float32 recipe of csrc/value_rescale.h.  eps <= 0 (default): off, bit-identical to the reference arithmetic;
+ * 1e-3 is the paper's value.  Before the first act() only (later: RELA_ESTATE).                          */
+int rela_apex_actor_set_value_rescale(rela_apex_actor* a, float eps);
 /* diagnostic: device pointers of the last Q table of act() (it lives in the history slot that act() wrote: look the
  * pointer up after every act()) and of the last priorities */
 const float* rela_apex_actor_last_q_dev(const rela_apex_actor* a);
@@ -519,6 +530,9 @@ int64_t rela_r2d2_actor_num_act(const rela_r2d2_actor* a);
  * Call once, before the first act().                                                              */
 int rela_r2d2_actor_set_dedup(rela_r2d2_actor* a, int units_per_stack);
 int rela_r2d2_actor_set_reuse(rela_r2d2_actor* a, int on);
+/* as rela_apex_actor_set_value_rescale, for the per-step priority of compute_priority (r2d2.py:76-100, whose target
+ * :98 the reference leaves unscaled).  Before the first act() only (later: RELA_ESTATE). */
+int rela_r2d2_actor_set_value_rescale(rela_r2d2_actor* a, float eps);
 /* diagnostics: current recurrent state (which = 0: h, 1: c) f32[rows,512]; last step priorities */
 const float* rela_r2d2_actor_hidden_dev(const rela_r2d2_actor* a, int which);
 const float* rela_r2d2_actor_last_priority_dev(const rela_r2d2_actor* a);
@@ -554,6 +568,10 @@ int rela_apex_learner_sync_target(rela_apex_learner* l, void* stream);
  * f32 accuracy, mode 0's tolerances (tests/test_learner_gpu.py); conv1, the conv data gradients, loss, clip and
  * optimiser exactly as in mode 0. */
 int rela_apex_learner_set_precision(rela_apex_learner* l, int mode);
+/* as rela_apex_actor_set_value_rescale, for the target of td_err (apex.py:43-44).  The target carries no gradient, so the
+ * backward pass keeps its formula with the new error.  Before the first rela_apex_learner_loss / _backward only (later:
+ * RELA_ESTATE); eps <= 0 (default): off. */
+int rela_apex_learner_set_value_rescale(rela_apex_learner* l, float eps);
 /* loss + backward on one sampled batch.  rows_dev: the ten FFTransition fields in the order
  * rela_replay_sample fills them; weight_dev f32[batch] = the IS weights.  Leaves the gradient of
  * mean(smooth_l1(td_err) * weight) in the flat gradient buffer, |td_err| in priority_dev
@@ -636,6 +654,10 @@ int rela_r2d2_learner_check(rela_r2d2_learner* l, void* stream);
  * 2e-4 of their largest entry of mode 0.  0 (default): everything f32.  2 ("f32x3"): conv2 / conv3 of BOTH nets' trunk
  * forwards on the three-part bf16 kernels (f32 accuracy, mode 0's tolerances); everything else as in mode 0. */
 int rela_r2d2_learner_set_precision(rela_r2d2_learner* l, int mode);
+/* as rela_apex_learner_set_value_rescale, for the per-timestep target of td_err (r2d2.py:172-176):
+ * h(reward[i] + bootstrap[i] * gamma ** n * h_inv(target_qa[i + n])).  Padding, the eta-mixed priority and the gradient
+ * keep their logic.  Before the first rela_r2d2_learner_loss / _backward only (later: RELA_ESTATE). */
+int rela_r2d2_learner_set_value_rescale(rela_r2d2_learner* l, float eps);
 
 /* ===================================================================================
  * Live per-kernel timing (HIP events on the launch stream) for bench.py's roofline line.

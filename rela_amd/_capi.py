@@ -152,6 +152,7 @@ _sig("rela_replay_debug_weights", i32, [vp, vp, vp])
 _sig("rela_replay_debug_read_rows", i32, [vp, i32, i32, i32, vp])
 _sig("rela_seqscan_search", i32, [vp, i64, i64, i64, vp, i32, vp, vp, vp, P(f64), vp])
 _sig("rela_debug_pow", i32, [vp, i32, f32, vp, vp])
+_sig("rela_debug_value_rescale", i32, [i32, vp, f32, vp, vp, vp])
 _sig("rela_seqscan_debug_perturb", i32, [i32])
 _sig("rela_nstep_return", i32, [i32, i32, f32, i32, vp, vp, vp, vp, vp, vp])
 _sig("rela_ffnet_create", i32, [P(vp), i32, i32])
@@ -195,6 +196,7 @@ _sig("rela_apex_actor_post_step", i32, [vp, vp, vp, i32, vp, vp, i32, P(i32), vp
 _sig("rela_apex_actor_set_dedup", i32, [vp, i32])
 _sig("rela_apex_actor_num_act", i64, [vp])
 _sig("rela_apex_actor_set_reuse", i32, [vp, i32])
+_sig("rela_apex_actor_set_value_rescale", i32, [vp, f32])
 _sig("rela_apex_actor_last_q_dev", vp, [vp])
 _sig("rela_apex_actor_last_priority_dev", vp, [vp])
 _sig("rela_r2d2_actor_create", i32, [P(vp), i32, i32, i32, i32, f32, i32, i32, f64, vp, u64, i32])
@@ -212,6 +214,7 @@ _sig("rela_r2d2_actor_post_step", i32, [vp, vp, vp, vp, vp, i32, P(i32), vp])
 _sig("rela_r2d2_actor_num_act", i64, [vp])
 _sig("rela_r2d2_actor_set_reuse", i32, [vp, i32])
 _sig("rela_r2d2_actor_set_dedup", i32, [vp, i32])
+_sig("rela_r2d2_actor_set_value_rescale", i32, [vp, f32])
 _sig("rela_r2d2_actor_hidden_dev", vp, [vp, i32])
 _sig("rela_r2d2_actor_last_priority_dev", vp, [vp])
 _sig("rela_apex_learner_create", i32, [P(vp), i32, i32, i32, f32, i32, f32, f32, f32, i32])
@@ -219,6 +222,7 @@ _sig("rela_apex_learner_destroy", None, [vp])
 _sig("rela_apex_learner_load", i32, [vp, P(FFNetParams), P(FFNetParams), i32, vp])
 _sig("rela_apex_learner_sync_target", i32, [vp, vp])
 _sig("rela_apex_learner_set_precision", i32, [vp, i32])
+_sig("rela_apex_learner_set_value_rescale", i32, [vp, f32])
 _sig("rela_apex_learner_backward", i32, [vp, i32, P(vp), vp, vp, vp, vp])
 _sig("rela_apex_learner_loss", i32, [vp, i32, P(vp), vp, vp, vp, vp])
 _sig("rela_apex_learner_grad", i32, [vp, vp])
@@ -242,6 +246,7 @@ _sig("rela_r2d2_learner_flat", i32, [vp, P(vp), P(vp), P(i64)])
 _sig("rela_r2d2_learner_stats_dev", vp, [vp])
 _sig("rela_r2d2_learner_check", i32, [vp, vp])
 _sig("rela_r2d2_learner_set_precision", i32, [vp, i32])
+_sig("rela_r2d2_learner_set_value_rescale", i32, [vp, f32])
 _sig("rela_prof_enable", i32, [i32])
 _sig("rela_prof_set_filter", i32, [C.c_char_p])
 _sig("rela_prof_summary_json", i32, [C.c_char_p, i64])

@@ -85,6 +85,9 @@ extern "C" int rela_apex_actor_screens_to_stacks(rela_apex_actor* a, const uint8
 extern "C" int rela_apex_actor_set_reuse(rela_apex_actor* a, int on) {
   return shard_set_reuse(a, on, "rela_apex_actor_set_reuse");
 }
+extern "C" int rela_apex_actor_set_value_rescale(rela_apex_actor* a, float eps) {
+  return shard_set_value_rescale(a, eps, "rela_apex_actor_set_value_rescale");
+}
 extern "C" int rela_apex_actor_set_dedup(rela_apex_actor* a, int units_per_stack) {
   const int rc = shard_set_dedup_common(a, units_per_stack, 0, "rela_apex_actor_set_dedup");
   if (rc == RELA_OK) a->tick_seq.assign(kTickWin, 0);
@@ -195,8 +198,8 @@ extern "C" int rela_apex_actor_post_step(rela_apex_actor* a, const float* reward
   rc = rela_ffnet_forward(target, a->R, obs_n, legal_n, a->q + 3 * QA, a->ws, a->ws_bytes, s);  // :42
   if (rc != RELA_OK) return rc;
   const int64_t* act_t = a->act + (size_t)first * a->R;
-  rc = rela_apex_td_from_q(a->R, a->A, a->K, q_online_t, q_online_n, a->q + 3 * QA, legal_n, act_t, a->out_r,
-                           a->out_b, a->gamma_n, nullptr, a->prio, s);
+  rc = td_from_q(a->R, a->A, a->K, q_online_t, q_online_n, a->q + 3 * QA, legal_n, act_t, a->out_r, a->out_b, a->gamma_n,
+                 a->vr_eps, nullptr, a->prio, s);
   if (rc != RELA_OK) return rc;
   // FFTransition rows (types.h:18-51): obs{s,eps,legal_move}, next_obs{...}, action{a}, reward, terminal, bootstrap
   const void* rows[10] = {obs_t, obs_n, eps_t, eps_n, legal_t, legal_n, act_t, a->out_r, a->out_t, a->out_b};

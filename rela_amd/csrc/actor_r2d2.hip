@@ -334,6 +334,9 @@ extern "C" void* rela_r2d2_actor_screen_stage(rela_r2d2_actor* a) { return a ? a
 extern "C" int rela_r2d2_actor_screens_to_stacks(rela_r2d2_actor* a, const uint8_t* restart_host, void* stream_) {
   return shard_screens_to_stacks(a, restart_host, (hipStream_t)stream_, "rela_r2d2_actor_screens_to_stacks");
 }
+extern "C" int rela_r2d2_actor_set_value_rescale(rela_r2d2_actor* a, float eps) {
+  return shard_set_value_rescale(a, eps, "rela_r2d2_actor_set_value_rescale");
+}
 extern "C" int rela_r2d2_actor_set_reuse(rela_r2d2_actor* a, int on) {
   return shard_set_reuse(a, on, "rela_r2d2_actor_set_reuse");
 }
@@ -490,8 +493,8 @@ extern "C" int rela_r2d2_actor_post_step(rela_r2d2_actor* a, const float* reward
                          a->ws_bytes, s);  // target_net(next_obs, next_hid, next_action) :93
   if (rc != RELA_OK) return rc;
   const int64_t* act_t = a->act + (size_t)first * R;
-  rc = rela_apex_td_from_q(a->R, a->A, a->K, q_online_t, adv_next, a->q + 3 * QA, legal_n, act_t, a->out_r, a->out_b,
-                           a->gamma_n, nullptr, a->prio_step, s);
+  rc = td_from_q(a->R, a->A, a->K, q_online_t, adv_next, a->q + 3 * QA, legal_n, act_t, a->out_r, a->out_b, a->gamma_n,
+                 a->vr_eps, nullptr, a->prio_step, s);
   if (rc != RELA_OK) return rc;
 
   // r2d2Buffer_.push(transition, priority, hid) :289

@@ -40,6 +40,7 @@ struct ActorShardBase {
   std::vector<uint64_t> qh_version;
   int q_slot = -1;     // slot of the last act()
   int reuse_mode = 1;  // 0: recompute everything, 1: reuse both act() forwards, 2: only the one of s_t+n
+  float vr_eps = 0.f;  // value rescaling of the priority's TD target (*_set_value_rescale; value_rescale.h), 0 = off
   // sliding-stack and screen input of the observation slot
   uint8_t* restart = nullptr;       // [R] *_slide_stacks / *_screens_to_stacks: 1 = the row's stack restarts with its new plane
   uint8_t* fresh_planes = nullptr;  // [R][7056] staging of the newest plane of every row (*_plane_stage)
@@ -168,6 +169,13 @@ inline int shard_set_reuse(ActorShardBase* a, int on, const char* who) {
   RELA_CHECK(a, RELA_EINVAL, "%s: bad arguments", who);
   RELA_CHECK(on >= 0 && on <= 2, RELA_EINVAL, "%s: 0 (off), 1 (on) or 2 (next_obs only)", who);
   a->reuse_mode = on;
+  return RELA_OK;
+}
+
+inline int shard_set_value_rescale(ActorShardBase* a, float eps, const char* who) {
+  RELA_CHECK(a && eps == eps, RELA_EINVAL, "%s: bad arguments", who);
+  RELA_CHECK(a->act_calls == 0, RELA_ESTATE, "%s: call it before the first act()", who);
+  a->vr_eps = eps > 0.f ? eps : 0.f;
   return RELA_OK;
 }
 

@@ -3,12 +3,14 @@
 //   rela_nstep_return     MultiStepTransitionBuffer::popTransition  rela/dqn_actor.h:58-106
 //   rela_apex_act_from_q  ApexAgent.greedy_act + act                pyrela/apex.py:48-65
 //   rela_apex_td_from_q   ApexAgent.td_err + compute_priority       pyrela/apex.py:30-45,68-78
+//                         (+ the optional value rescaling of the target, value_rescale.h: no reference counterpart)
 //
 // All three are tiny (K <= a few thousand rows of <= 18 floats): one workgroup each, so the
 // batch-global q.min() of greedy_act (apex.py:51) needs no second launch.
 // HBM-bound in principle, launch-latency-bound in practice.
 #include "common.h"
 #include "prof.h"
+#include "value_rescale.h"
 
 namespace rela_amd {
 namespace {
@@ -143,7 +145,8 @@ __global__ __launch_bounds__(kT) void td_kernel(int n, int A, int group, const f
                                                 const float* __restrict__ qno, const float* __restrict__ qnt,
                                                 const float* __restrict__ nlegal, const int64_t* __restrict__ action,
                                                 const float* __restrict__ reward, const float* __restrict__ bootstrap,
-                                                float gamma_n, float* __restrict__ td, float* __restrict__ prio) {
+                                                float gamma_n, float vr_eps, float* __restrict__ td,
+                                                float* __restrict__ prio) {
   __shared__ float red[kT];
   const int r0 = blockIdx.x * group;
   const int r1 = min(n, r0 + group);
@@ -153,7 +156,11 @@ __global__ __launch_bounds__(kT) void td_kernel(int n, int A, int group, const f
     const float qa = q[(size_t)i * A + (int)action[i]];   // :39
     const float bq = qnt[(size_t)i * A + na];              // :43
     const float g = __fmul_rn(bootstrap[i], gamma_n);      // bootstrap * (gamma ** n) * q, left to right :44
-    const float tgt = __fadd_rn(reward[i], __fmul_rn(g, bq));
+    float tgt;
+    if (vr_eps > 0.0f)  // value rescaling (value_rescale.h): h(r + bootstrap * gamma ** n * h_inv(q))
+      tgt = rela_vr::h(__fadd_rn(reward[i], __fmul_rn(g, rela_vr::h_inv(bq, vr_eps))), vr_eps);
+    else
+      tgt = __fadd_rn(reward[i], __fmul_rn(g, bq));
     const float e = __fsub_rn(tgt, qa);                    // :45
     if (td) td[i] = e;
     if (prio) prio[i] = fabsf(e);                          // :78
@@ -192,21 +199,54 @@ extern "C" int rela_apex_act_from_q(int n, int num_action, int group_rows, const
   return RELA_OK;
 }
 
-extern "C" int rela_apex_td_from_q(int n, int num_action, int group_rows, const float* q_dev,
-                                   const float* q_next_online_dev, const float* q_next_target_dev,
-                                   const float* next_legal_dev,
-                                   const int64_t* action_dev, const float* reward_dev, const float* bootstrap_dev,
-                                   float gamma_n, float* td_err_dev, float* priority_dev, void* stream) {
+// rela_apex_td_from_q with the value-rescaling switch of the object that calls it (vr_eps <= 0: off); the actors and
+// the Ape-X learner's large-batch path come through here, the C ABI entry below passes 0
+int rela_amd::td_from_q(int n, int num_action, int group_rows, const float* q_dev, const float* q_next_online_dev,
+                        const float* q_next_target_dev, const float* next_legal_dev, const int64_t* action_dev,
+                        const float* reward_dev, const float* bootstrap_dev, float gamma_n, float vr_eps,
+                        float* td_err_dev, float* priority_dev, hipStream_t stream) {
   RELA_CHECK(n >= 1 && num_action >= 1 && group_rows >= 0 && q_dev && q_next_online_dev && q_next_target_dev &&
                  next_legal_dev && action_dev && reward_dev && bootstrap_dev,
              RELA_EINVAL, "rela_apex_td_from_q: bad arguments");
   const int group = group_rows > 0 ? group_rows : n;
   const int threads = group >= 512 ? kT : 256;
-  ProfScope prof("td_kernel", (hipStream_t)stream);
-  hipLaunchKernelGGL(td_kernel, dim3(ceil_div(n, group)), dim3(threads), 0, (hipStream_t)stream, n, num_action, group,
+  ProfScope prof("td_kernel", stream);
+  hipLaunchKernelGGL(td_kernel, dim3(ceil_div(n, group)), dim3(threads), 0, stream, n, num_action, group,
                      q_dev, q_next_online_dev,
-                     q_next_target_dev, next_legal_dev, action_dev, reward_dev, bootstrap_dev, gamma_n, td_err_dev,
+                     q_next_target_dev, next_legal_dev, action_dev, reward_dev, bootstrap_dev, gamma_n, vr_eps, td_err_dev,
                      priority_dev);
+  RELA_LAUNCH_CHECK();
+  return RELA_OK;
+}
+
+extern "C" int rela_apex_td_from_q(int n, int num_action, int group_rows, const float* q_dev,
+                                   const float* q_next_online_dev, const float* q_next_target_dev,
+                                   const float* next_legal_dev,
+                                   const int64_t* action_dev, const float* reward_dev, const float* bootstrap_dev,
+                                   float gamma_n, float* td_err_dev, float* priority_dev, void* stream) {
+  return td_from_q(n, num_action, group_rows, q_dev, q_next_online_dev, q_next_target_dev, next_legal_dev, action_dev,
+                   reward_dev, bootstrap_dev, gamma_n, 0.0f, td_err_dev, priority_dev, (hipStream_t)stream);
+}
+
+// Test tap: h_out[i] = h(x[i]), hinv_out[i] = h_inv(x[i]) of value_rescale.h as the kernels evaluate them.
+namespace rela_amd {
+namespace {
+__global__ void debug_value_rescale_kernel(int n, const float* __restrict__ x, float eps, float* __restrict__ h_out,
+                                           float* __restrict__ hinv_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (h_out) h_out[i] = rela_vr::h(x[i], eps);
+  if (hinv_out) hinv_out[i] = rela_vr::h_inv(x[i], eps);
+}
+}  // namespace
+}  // namespace rela_amd
+extern "C" int rela_debug_value_rescale(int n, const float* x_dev, float eps, float* h_out_dev, float* hinv_out_dev,
+                                        void* stream) {
+  RELA_CHECK(n >= 0 && x_dev && eps > 0.0f && (h_out_dev || hinv_out_dev), RELA_EINVAL,
+             "rela_debug_value_rescale: bad arguments (eps must be > 0)");
+  if (n > 0)
+    hipLaunchKernelGGL(debug_value_rescale_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, n, x_dev,
+                       eps, h_out_dev, hinv_out_dev);
   RELA_LAUNCH_CHECK();
   return RELA_OK;
 }

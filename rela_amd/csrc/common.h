@@ -138,6 +138,13 @@ inline hipError_t dev_copy2(void* d0, const void* s0, size_t n0, void* d1, const
 int slide_stacks(uint8_t* cur_slot, const uint8_t* prev_slot, const uint8_t* fresh_planes, const uint8_t* restart_dev, int rows,
                  hipStream_t s);
 
+// agent_ops.hip: rela_apex_td_from_q with the caller's value-rescaling switch (vr_eps <= 0: off, today's arithmetic;
+// > 0: the target is h(r + bootstrap * gamma_n * h_inv(q)), value_rescale.h)
+int td_from_q(int n, int num_action, int group_rows, const float* q_dev, const float* q_next_online_dev,
+              const float* q_next_target_dev, const float* next_legal_dev, const int64_t* action_dev,
+              const float* reward_dev, const float* bootstrap_dev, float gamma_n, float vr_eps, float* td_err_dev,
+              float* priority_dev, hipStream_t stream);
+
 // atari_screen.hip: 84x84 features of staged screen pairs, and the shards' screens_to_stacks (features into
 // fresh_planes, then slide_stacks with the host restart flags; `first`: the shard's first act, every row must restart;
 // prev_slot: the slot of the last act -- the same as cur_slot for an evaluation shard, which then slides from prev_copy;

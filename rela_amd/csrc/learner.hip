@@ -33,6 +33,8 @@ struct rela_apex_learner {
   int device = 0;
   int A = 0, Bmax = 0;
   float gamma_n = 0.f;
+  float vr_eps = 0.f;        // value rescaling of the TD target (rela_apex_learner_set_value_rescale), 0 = off
+  bool loss_called = false;  // ... which is fixed from the first rela_apex_learner_loss on
   int optimizer = 0;  // 0 RMSprop, 1 Adam
   float lr = 0.f, opt_eps = 0.f, clip = 0.f;
   int64_t adam_t = 0;
@@ -213,6 +215,13 @@ extern "C" int rela_apex_learner_load(rela_apex_learner* l, const rela_ffnet_par
   return RELA_OK;
 }
 
+extern "C" int rela_apex_learner_set_value_rescale(rela_apex_learner* l, float eps) {
+  RELA_CHECK(l && eps == eps, RELA_EINVAL, "rela_apex_learner_set_value_rescale: bad arguments");
+  RELA_CHECK(!l->loss_called, RELA_ESTATE, "rela_apex_learner_set_value_rescale: call it before the first loss");
+  l->vr_eps = eps > 0.f ? eps : 0.f;
+  return RELA_OK;
+}
+
 extern "C" int rela_apex_learner_set_precision(rela_apex_learner* l, int mode) {
   RELA_CHECK(l && mode >= 0 && mode <= 2, RELA_EINVAL, "rela_apex_learner_set_precision: mode must be 0, 1 or 2");
   int rc = rela_ffnet_set_precision(l->online, mode);
@@ -291,6 +300,7 @@ extern "C" int rela_apex_learner_loss(rela_apex_learner* l, int batch, const voi
   RELA_CHECK(batch >= 1 && batch <= l->Bmax && rows_dev && weight_dev && priority_dev, RELA_EINVAL,
              "rela_apex_learner_loss: bad arguments (batch %d, max %d)", batch, l->Bmax);
   l->pend_B = 0;
+  l->loss_called = true;
   hipStream_t s = (hipStream_t)stream_;
   DeviceGuard g(l->device);
   const int Bn = batch, A = l->A;
@@ -351,10 +361,10 @@ extern "C" int rela_apex_learner_loss(rela_apex_learner* l, int batch, const voi
   if (Bn <= 1024) {
     ProfScope prof("learner_loss_grad", s);
     hipLaunchKernelGGL(learner_td_loss_grad, dim3(1), dim3(1024), 0, s, Bn, A, (const float*)q_on, (const float*)q_no,
-                       (const float*)q_nt, nlegal, act, reward, boot, l->gamma_n, weight_dev, legal, l->td, priority_dev,
-                       l->d_ha, l->loss);
+                       (const float*)q_nt, nlegal, act, reward, boot, l->gamma_n, l->vr_eps, weight_dev, legal, l->td,
+                       priority_dev, l->d_ha, l->loss);
   } else {
-    rc = rela_apex_td_from_q(Bn, A, 0, q_on, q_no, q_nt, nlegal, act, reward, boot, l->gamma_n, l->td, priority_dev, s);
+    rc = td_from_q(Bn, A, 0, q_on, q_no, q_nt, nlegal, act, reward, boot, l->gamma_n, l->vr_eps, l->td, priority_dev, s);
     if (rc != RELA_OK) return rc;
     ProfScope prof("learner_loss_grad", s);
     hipLaunchKernelGGL(learner_loss_grad, dim3(1), dim3(kLT), 0, s, (const float*)l->td, weight_dev, act, legal, Bn,

@@ -12,6 +12,7 @@
 #include "gemm_lds.h"
 #include "gemm_bf16x3.h"
 #include "prof.h"
+#include "value_rescale.h"
 #include "dgrad_conv_bf16.h"
 #include "wgrad_conv1_bf16.h"
 #include "wgrad_conv2_bf16.h"
@@ -389,7 +390,8 @@ __global__ __launch_bounds__(1024) void learner_td_loss_grad(int Bn, int A, cons
                                                              const int64_t* __restrict__ act,
                                                              const float* __restrict__ reward,
                                                              const float* __restrict__ bootstrap, float gamma_n,
-                                                             const float* __restrict__ w, const float* __restrict__ legal,
+                                                             float vr_eps, const float* __restrict__ w,
+                                                             const float* __restrict__ legal,
                                                              float* __restrict__ td, float* __restrict__ prio,
                                                              float* __restrict__ d_ha, float* __restrict__ loss_out) {
   __shared__ float red[1024];
@@ -416,7 +418,11 @@ __global__ __launch_bounds__(1024) void learner_td_loss_grad(int Bn, int A, cons
     const int a = (int)act[i];
     const float qa = q[(size_t)i * A + a];
     const float bq = qnt[(size_t)i * A + na];
-    const float tgt = __fadd_rn(reward[i], __fmul_rn(__fmul_rn(bootstrap[i], gamma_n), bq));
+    float tgt;  // detached: with value rescaling (value_rescale.h) only the target changes, the Huber seed below keeps its formula
+    if (vr_eps > 0.0f)
+      tgt = rela_vr::h(__fadd_rn(reward[i], __fmul_rn(__fmul_rn(bootstrap[i], gamma_n), rela_vr::h_inv(bq, vr_eps))), vr_eps);
+    else
+      tgt = __fadd_rn(reward[i], __fmul_rn(__fmul_rn(bootstrap[i], gamma_n), bq));
     const float e = __fsub_rn(tgt, qa), ae = fabsf(e);
     td[i] = e;
     prio[i] = ae;

@@ -538,8 +538,8 @@ __global__ void seq_select(const float* __restrict__ q_on, const float* __restri
 __global__ __launch_bounds__(1024) void seq_td_loss(const float* __restrict__ qa_on, const float* __restrict__ qa_tg,
                                                     const float* __restrict__ reward, const float* __restrict__ boot,
                                                     const float* __restrict__ seq_len, const float* __restrict__ w,
-                                                    int Bn, int seq, int burn, int nstep, float gamma_n, float eta,
-                                                    float one_minus_eta, float* __restrict__ dqa,
+                                                    int Bn, int seq, int burn, int nstep, float gamma_n, float vr_eps,
+                                                    float eta, float one_minus_eta, float* __restrict__ dqa,
                                                     float* __restrict__ prio, float* __restrict__ loss_seq,
                                                     float* __restrict__ loss_out) {
   __shared__ float red[1024];
@@ -553,7 +553,11 @@ __global__ __launch_bounds__(1024) void seq_td_loss(const float* __restrict__ qa
       const size_t r = (size_t)i * Bn + b;  // training rows are time-major
       float g = 0.f;
       if (i < seq) {
-        const float target = reward[r] + boot[r] * (gamma_n * qa_tg[(size_t)(i + nstep) * Bn + b]);
+        float target;  // detached: with value rescaling (value_rescale.h) only the target changes
+        if (vr_eps > 0.0f)
+          target = rela_vr::h(reward[r] + boot[r] * (gamma_n * rela_vr::h_inv(qa_tg[(size_t)(i + nstep) * Bn + b], vr_eps)), vr_eps);
+        else
+          target = reward[r] + boot[r] * (gamma_n * qa_tg[(size_t)(i + nstep) * Bn + b]);
         const bool pad = (float)i >= len - (float)burn;  // should_padding :175
         const float e = pad ? 0.f : target - qa_on[r];
         const float ae = fabsf(e);
@@ -600,6 +604,8 @@ struct rela_r2d2_learner {
   int device = 0;
   int A = 0, Bmax = 0, seq = 0, burn = 0, n = 0, T = 0;
   float gamma_n = 0.f, eta = 0.f, one_minus_eta = 0.f;
+  float vr_eps = 0.f;        // value rescaling of the TD target (rela_r2d2_learner_set_value_rescale), 0 = off
+  bool loss_called = false;  // ... which is fixed from the first rela_r2d2_learner_loss on
   OptimState opt;
   int64_t off[15] = {0};  // segment offsets, off[14] = total
   float *P = nullptr, *PT = nullptr, *G = nullptr, *S1 = nullptr, *S2 = nullptr;
@@ -1062,6 +1068,13 @@ extern "C" int rela_r2d2_learner_flat(rela_r2d2_learner* l, float** params_dev, 
 
 extern "C" const float* rela_r2d2_learner_stats_dev(const rela_r2d2_learner* l) { return l ? l->norm : nullptr; }
 
+extern "C" int rela_r2d2_learner_set_value_rescale(rela_r2d2_learner* l, float eps) {
+  RELA_CHECK(l && eps == eps, RELA_EINVAL, "rela_r2d2_learner_set_value_rescale: bad arguments");
+  RELA_CHECK(!l->loss_called, RELA_ESTATE, "rela_r2d2_learner_set_value_rescale: call it before the first loss");
+  l->vr_eps = eps > 0.f ? eps : 0.f;
+  return RELA_OK;
+}
+
 extern "C" int rela_r2d2_learner_set_precision(rela_r2d2_learner* l, int mode) {
   RELA_CHECK(l && mode >= 0 && mode <= 2, RELA_EINVAL, "rela_r2d2_learner_set_precision: mode must be 0, 1 or 2");
   l->precision = mode;
@@ -1112,6 +1125,7 @@ extern "C" int rela_r2d2_learner_loss(rela_r2d2_learner* l, int batch, const voi
   hipStream_t s = (hipStream_t)stream_;
   DeviceGuard g(l->device);
   l->pend_B = 0;
+  l->loss_called = true;
   const int Bn = batch, A = l->A, T = l->T, burn = l->burn, Tt = T - burn, rowsTr = Tt * Bn;
   // RNNTransition batch, time-major (types.cc:140-182), in the order of the 10-field sequence schema
   const uint8_t* obs = static_cast<const uint8_t*>(rows_dev[0]);     // [T][B][4][84][84]
@@ -1137,7 +1151,7 @@ extern "C" int rela_r2d2_learner_loss(rela_r2d2_learner* l, int batch, const voi
     hipLaunchKernelGGL(seq_select, dim3(ceil_div(rowsTr, 256)), dim3(256), 0, s, (const float*)l->q_on,
                        (const float*)l->q_tg, legal_tr, act_tr, (const float*)l->qmin, rowsTr, A, l->qa_on, l->qa_tg);
     hipLaunchKernelGGL(seq_td_loss, dim3(1), dim3(1024), 0, s, (const float*)l->qa_on, (const float*)l->qa_tg,
-                       reward + tr0, boot + tr0, seq_len, weight_dev, Bn, l->seq, burn, l->n, l->gamma_n, l->eta,
+                       reward + tr0, boot + tr0, seq_len, weight_dev, Bn, l->seq, burn, l->n, l->gamma_n, l->vr_eps, l->eta,
                        l->one_minus_eta, l->dqa, priority_dev, l->loss_seq, l->loss);
     hipLaunchKernelGGL(seq_head_grad, dim3(ceil_div((int64_t)rowsTr * 32, 256)), dim3(256), 0, s, (const float*)l->dqa,
                        act_tr, legal_tr, rowsTr, A, l->d_ha);

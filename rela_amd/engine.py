@@ -123,6 +123,11 @@ class ApexActorEngine:
         history slot act() wrote, so the pointer is looked up per call)."""
         return dev_view(capi.lib.rela_apex_actor_last_q_dev(self.h), (1, self._rows, self._A), torch.float32, self.device)
 
+    def set_value_rescale(self, eps):
+        """eps of the invertible value rescaling of the priority's TD target (csrc/value_rescale.h); <= 0: off.
+        Before the first act() only."""
+        capi.check(capi.lib.rela_apex_actor_set_value_rescale(self.h, float(eps)), "rela_apex_actor_set_value_rescale")
+
     def set_reuse(self, on):
         """on=0 / False: post_step always recomputes (the reference's 4 forwards per step); 1 / True: reuses act()'s
         forwards of this tick and of n ticks ago; 2: only the one of this tick."""
@@ -229,6 +234,10 @@ class R2D2ActorEngine:
     @property
     def num_act(self):
         return capi.lib.rela_r2d2_actor_num_act(self.h)
+
+    def set_value_rescale(self, eps):
+        """as ApexActorEngine.set_value_rescale, for the per-step priority"""
+        capi.check(capi.lib.rela_r2d2_actor_set_value_rescale(self.h, float(eps)), "rela_r2d2_actor_set_value_rescale")
 
     def set_reuse(self, on):
         capi.check(capi.lib.rela_r2d2_actor_set_reuse(self.h, int(on)), "rela_r2d2_actor_set_reuse")

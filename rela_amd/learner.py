@@ -103,8 +103,14 @@ class HipApexLearner:
         dev = next(agent.online_net.parameters()).device
         num_action = agent.online_net.fc_a.weight.shape[0]
         self = cls(num_action, max_batch, agent.multi_step, agent.gamma, device=str(dev), **kw)
+        self.set_value_rescale(getattr(agent, "value_rescale", 0.0))
         self.load_state_dicts(agent.online_net.state_dict(), agent.target_net.state_dict())
         return self
+
+    def set_value_rescale(self, eps):
+        """eps of the invertible value rescaling of the TD target (csrc/value_rescale.h); <= 0: off.  Before the first
+        loss only."""
+        self._capi.check(self._capi.lib.rela_apex_learner_set_value_rescale(self.h, float(eps)), "rela_apex_learner_set_value_rescale")
 
     def _stream(self):
         return self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -298,8 +304,14 @@ class HipR2D2Learner:
         num_action = agent.online_net.fc_a.weight.shape[0]
         self = cls(num_action, max_batch, agent.multi_step, agent.gamma, agent.seq_len, agent.burn_in, agent.eta,
                    device=str(dev), **kw)
+        self.set_value_rescale(getattr(agent, "value_rescale", 0.0))
         self.load_state_dicts(agent.online_net.state_dict(), agent.target_net.state_dict())
         return self
+
+    def set_value_rescale(self, eps):
+        """eps of the invertible value rescaling of the TD target (csrc/value_rescale.h); <= 0: off.  Before the first
+        loss only."""
+        self._capi.check(self._capi.lib.rela_r2d2_learner_set_value_rescale(self.h, float(eps)), "rela_r2d2_learner_set_value_rescale")
 
     def _stream(self):
         return self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)

@@ -358,6 +358,9 @@ class ModelLocker {
     target_.assign(n, nullptr);
     inFlight_.assign(n, 0);
     if (py::hasattr(pyModels_[0], "eta")) eta_ = pyModels_[0].attr("eta").cast<double>();
+    // value rescaling of the TD targets: an attribute of this engine's agents (pyrela/apex.py, r2d2.py), absent from
+    // the reference's -- the actors' constructor signatures stay the reference's
+    if (py::hasattr(pyModels_[0], "value_rescale")) valueRescale_ = pyModels_[0].attr("value_rescale").cast<float>();
     if (deviceIndex >= 0 || torch::cuda::is_available()) loadSlot(0, pyModels_[0]);
   }
 
@@ -396,6 +399,7 @@ class ModelLocker {
   int numAction() const { return numAction_; }
   Kind kind() const { return kind_; }
   double eta() const { return eta_; }
+  float valueRescale() const { return valueRescale_; }
 
   const std::string device;  // what the caller asked for (public member of the reference class, model_locker.h:54)
   const int deviceIndex;     // -1 for "cpu"
@@ -499,6 +503,7 @@ class ModelLocker {
   Kind kind_ = kFF;
   bool kindKnown_ = false;
   double eta_ = 0.9;
+  float valueRescale_ = 0.f;  // eps of the agent's value rescaling, 0 = off
   std::mutex m_;
   std::condition_variable cv_;
 };
@@ -1087,6 +1092,7 @@ struct ShardApi {
   int (*screens_to_stacks)(void*, const uint8_t*, void*);
   int64_t (*num_act)(const void*);
   int (*set_dedup)(void*, int);
+  int (*set_value_rescale)(void*, float);
   int (*act)(void* h, const void* online, const uint8_t* obs, const float* eps, const float* legal, int64_t* action,
              void* stream);
   int (*post_step)(void* h, const float* reward, const uint8_t* terminal, const void* online, const void* target,
@@ -1111,6 +1117,7 @@ const ShardApi kApexShard = {
     Erased<rela_apex_actor_screens_to_stacks>::call,
     Erased<rela_apex_actor_num_act>::call,
     Erased<rela_apex_actor_set_dedup>::call,
+    Erased<rela_apex_actor_set_value_rescale>::call,
     [](void* h, const void* online, const uint8_t* obs, const float* eps, const float* legal, int64_t* action, void* stream) {
       return rela_apex_actor_act(static_cast<rela_apex_actor*>(h), static_cast<const rela_ffnet*>(online), obs, eps, legal,
                                  action, nullptr, stream);
@@ -1132,6 +1139,7 @@ const ShardApi kR2D2Shard = {
     Erased<rela_r2d2_actor_screens_to_stacks>::call,
     Erased<rela_r2d2_actor_num_act>::call,
     Erased<rela_r2d2_actor_set_dedup>::call,
+    Erased<rela_r2d2_actor_set_value_rescale>::call,
     [](void* h, const void* online, const uint8_t* obs, const float* eps, const float* legal, int64_t* action, void* stream) {
       return rela_r2d2_actor_act(static_cast<rela_r2d2_actor*>(h), static_cast<const rela_lstmnet*>(online), obs, eps,
                                  legal, action, nullptr, stream);
@@ -1163,6 +1171,11 @@ static void enableDedup(Shard& sh, rela_replay* rep) {
   int ups = 0;
   check(rela_replay_dedup_info(rep, &ups, nullptr, nullptr), "rela_replay_dedup_info");
   if (ups > 0) check(sh->set_dedup(sh.h, ups), "set_dedup");
+}
+
+// the agent's value_rescale (ModelLocker::valueRescale) on a fresh shard; 0 leaves the shard as created
+static void enableValueRescale(Shard& sh, float eps) {
+  if (eps > 0.f) check(sh->set_value_rescale(sh.h, eps), "set_value_rescale");
 }
 
 // =====================================================================================
@@ -1399,6 +1412,7 @@ class ActorCohort {
       shard_.h = h;
       shard_.api = &kR2D2Shard;
       enableDedup(shard_, rep);
+      enableValueRescale(shard_, locker_->valueRescale());
     } else {
       rela_replay* rep = replay_->handle(locker_.get(), dev, A);
       rela_apex_actor* h = nullptr;
@@ -1407,6 +1421,7 @@ class ActorCohort {
       shard_.h = h;
       shard_.api = &kApexShard;
       enableDedup(shard_, rep);
+      enableValueRescale(shard_, locker_->valueRescale());
     }
     created_ = true;
     auto pin = [](torch::Tensor t) { return torch::cuda::is_available() ? t.pin_memory() : t; };
@@ -1525,6 +1540,7 @@ class ShardActor : public Actor {
   int batchsize() const { return batchsize_; }
   int multiStep() const { return multiStep_; }
   float gamma() const { return gamma_; }
+  float valueRescale() const { return locker_->valueRescale(); }
   std::shared_ptr<ModelLocker> locker() const { return locker_; }
   std::shared_ptr<ReplayT> replay() const { return replay_; }
   void joinCohort(std::shared_ptr<ActorCohort> c, int member) {
@@ -1651,6 +1667,7 @@ class DQNActor : public ShardActor<FFPrioritizedReplay> {
     shard_.h = h;
     shard_.api = &kApexShard;
     enableDedup(shard_, rep);
+    enableValueRescale(shard_, locker_->valueRescale());
   }
 };
 
@@ -1683,6 +1700,7 @@ class R2D2Actor : public ShardActor<RNNPrioritizedReplay> {
     shard_.h = h;
     shard_.api = &kR2D2Shard;
     enableDedup(shard_, rep);
+    enableValueRescale(shard_, locker_->valueRescale());
   }
 
   const int seqLen_, burnin_;
@@ -1841,7 +1859,7 @@ class Context {
   }
 
  private:
-  // Training DQNActors (R2D2Actors) of this context that share (locker, replay, K, n, gamma[, seq_len,
+  // Training DQNActors (R2D2Actors) of this context that share (locker, replay, K, n, gamma, value_rescale[, seq_len,
   // burn_in]) are batched into one device shard (ActorCohort); a lone actor keeps its private shard.
   // RELA_COHORT_SPLIT=0 opts out.
   template <class ActorT, class Same, class Make>
@@ -1903,7 +1921,7 @@ class Context {
     formCohortsOf<DQNActor>(
         [](const DQNActor& f, const DQNActor& a) {
           return f.lockerKey() == a.lockerKey() && f.replayKey() == a.replayKey() && f.batchsize() == a.batchsize() &&
-                 f.multiStep() == a.multiStep() && f.gamma() == a.gamma();
+                 f.multiStep() == a.multiStep() && f.gamma() == a.gamma() && f.valueRescale() == a.valueRescale();
         },
         [](const DQNActor& f, int members) {
           return std::make_shared<ActorCohort>(f.locker(), f.replay(), f.multiStep(), f.batchsize(), f.gamma(), members);
@@ -1912,7 +1930,7 @@ class Context {
         [](const R2D2Actor& f, const R2D2Actor& a) {
           return f.lockerKey() == a.lockerKey() && f.replayKey() == a.replayKey() && f.batchsize() == a.batchsize() &&
                  f.multiStep() == a.multiStep() && f.gamma() == a.gamma() && f.seqLen() == a.seqLen() &&
-                 f.burnin() == a.burnin();
+                 f.burnin() == a.burnin() && f.valueRescale() == a.valueRescale();
         },
         [](const R2D2Actor& f, int members) {
           return std::make_shared<ActorCohort>(f.locker(), f.replay(), f.multiStep(), f.batchsize(), f.gamma(),

@@ -12,6 +12,18 @@ from torch import nn
 from torch.nn import functional as F
 
 
+def value_rescale_h(x: torch.Tensor, eps: float) -> torch.Tensor:
+    """Invertible value rescaling h(x) = sign(x) (sqrt(|x| + 1) - 1) + eps x (R2D2 as published; the reference
+    leaves it out).  The textbook form in plain torch ops: this module is the parity reference of the kernels'
+    cancellation-free recipe (rela_amd/csrc/value_rescale.h)."""
+    return x.sign() * ((x.abs() + 1).sqrt() - 1) + eps * x
+
+
+def value_rescale_h_inv(x: torch.Tensor, eps: float) -> torch.Tensor:
+    """h^-1(x) = sign(x) (((sqrt(1 + 4 eps (|x| + 1 + eps)) - 1) / (2 eps))^2 - 1), textbook form."""
+    return x.sign() * ((((1 + 4 * eps * (x.abs() + 1 + eps)).sqrt() - 1) / (2 * eps)) ** 2 - 1)
+
+
 def masked_greedy(q: torch.Tensor, legal: torch.Tensor) -> torch.Tensor:
     """argmax over legal moves; the shift uses the minimum of the WHOLE batch (apex.py:48-54)."""
     shifted = (1 + q - q.min()) * legal
@@ -19,17 +31,18 @@ def masked_greedy(q: torch.Tensor, legal: torch.Tensor) -> torch.Tensor:
 
 
 class ApexAgent(nn.Module):
-    def __init__(self, net_cons, multi_step: int, gamma: float):
+    def __init__(self, net_cons, multi_step: int, gamma: float, value_rescale: float = 0.0):
         super().__init__()
         self.net_cons = net_cons
         self.multi_step = multi_step
         self.gamma = gamma
+        self.value_rescale = float(value_rescale)  # eps of h; <= 0: off (the reference's arithmetic)
         self.online_net = net_cons()
         self.target_net = net_cons()
 
     @classmethod
     def clone(cls, model, device):
-        twin = cls(model.net_cons, model.multi_step, model.gamma)
+        twin = cls(model.net_cons, model.multi_step, model.gamma, model.value_rescale)
         twin.load_state_dict(model.state_dict())
         return twin.to(device)
 
@@ -45,7 +58,12 @@ class ApexAgent(nn.Module):
         with torch.no_grad():
             next_a = masked_greedy(self.online_net(next_obs), next_obs["legal_move"])
             next_q = self.target_net(next_obs).gather(1, next_a.unsqueeze(1)).squeeze(1)
-            target = reward + bootstrap * (self.gamma ** self.multi_step) * next_q
+            if self.value_rescale > 0:
+                eps = self.value_rescale
+                target = value_rescale_h(
+                    reward + bootstrap * (self.gamma ** self.multi_step) * value_rescale_h_inv(next_q, eps), eps)
+            else:
+                target = reward + bootstrap * (self.gamma ** self.multi_step) * next_q
         return target - q_taken
 
     @torch.no_grad()

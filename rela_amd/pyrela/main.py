@@ -39,6 +39,9 @@ def parse_args(argv=None):
     p.add_argument("--seq_len", type=int, default=80)
     p.add_argument("--eta", type=float, default=0.9)
     p.add_argument("--same_hid", type=int, default=0)
+    p.add_argument("--value_rescale", type=float, default=0.0,
+                   help="eps of the invertible value rescaling h(x) = sign(x)(sqrt(|x|+1)-1) + eps x of the TD targets "
+                        "(R2D2 as published: 1e-3; no reference counterpart); 0 = off, the reference's targets")
     p.add_argument("--game", type=str, default="synthetic")
     p.add_argument("--seed", type=int, default=10002)
     p.add_argument("--max_frame", type=int, default=108000)
@@ -86,11 +89,13 @@ def train(args, on_epoch=None):
     num_action = create_env.get_num_action(args.game)
     if args.algo == "r2d2":  # pyrela/main.py:98-109,123-126
         agent = R2D2Agent(lambda dev: AtariLSTMNet(dev, num_action), args.train_device, args.multi_step, args.gamma,
-                          args.eta, args.seq_len, args.seq_burn_in, args.same_hid).to(args.train_device)
+                          args.eta, args.seq_len, args.seq_burn_in, args.same_hid,
+                          getattr(args, "value_rescale", 0.0)).to(args.train_device)
         optim = torch.optim.Adam(agent.online_net.parameters(), lr=args.lr, eps=args.eps)
         replay_class = rela.RNNPrioritizedReplay
     else:  # :110-122
-        agent = ApexAgent(lambda: AtariFFNet(num_action), args.multi_step, args.gamma).to(args.train_device)
+        agent = ApexAgent(lambda: AtariFFNet(num_action), args.multi_step, args.gamma,
+                          getattr(args, "value_rescale", 0.0)).to(args.train_device)
         optim = torch.optim.RMSprop(agent.online_net.parameters(), lr=args.lr, eps=args.eps)
         replay_class = rela.FFPrioritizedReplay
     learner = None
@@ -264,12 +269,13 @@ def _multi_worker(rank, world, args, port, results):
     r2d2 = args.algo == "r2d2"
     if r2d2:  # BASELINE C4: sequence replay partitions, LSTM nets (pyrela/main.py:98-109)
         agent = R2D2Agent(lambda dev: AtariLSTMNet(dev, num_action), my_device, args.multi_step, args.gamma, args.eta,
-                          args.seq_len, args.seq_burn_in, args.same_hid).to(my_device)
+                          args.seq_len, args.seq_burn_in, args.same_hid, getattr(args, "value_rescale", 0.0)).to(my_device)
         specs = rnn_field_specs(num_action, args.seq_burn_in + args.seq_len + args.multi_step)
         layout, total = lstmnet_flat_layout(num_action)
         to_namespace, learner_cls = rnn_batch_namespace, HipR2D2Learner
     else:
-        agent = ApexAgent(lambda: AtariFFNet(num_action), args.multi_step, args.gamma).to(my_device)
+        agent = ApexAgent(lambda: AtariFFNet(num_action), args.multi_step, args.gamma,
+                          getattr(args, "value_rescale", 0.0)).to(my_device)
         specs = ff_field_specs(num_action)
         layout, total = ffnet_flat_layout(num_action)
         to_namespace, learner_cls = ff_batch_namespace, HipApexLearner

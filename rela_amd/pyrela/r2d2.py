@@ -9,11 +9,15 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
+from .apex import value_rescale_h, value_rescale_h_inv
+
 
 class R2D2Agent(nn.Module):
-    def __init__(self, net_cons, device, multi_step, gamma, eta, seq_len, burn_in, same_hid=0):
+    def __init__(self, net_cons, device, multi_step, gamma, eta, seq_len, burn_in, same_hid=0,
+                 value_rescale: float = 0.0):
         super().__init__()
         self.net_cons = net_cons
+        self.value_rescale = float(value_rescale)  # eps of h (apex.value_rescale_h); <= 0: off
         self.multi_step, self.gamma, self.eta = multi_step, gamma, eta
         self.seq_len, self.burn_in, self.same_hid = seq_len, burn_in, same_hid
         self.online_net = net_cons(device)
@@ -25,7 +29,7 @@ class R2D2Agent(nn.Module):
     @classmethod
     def clone(cls, model, device):
         twin = cls(model.net_cons, device, model.multi_step, model.gamma, model.eta, model.seq_len, model.burn_in,
-                   model.same_hid)
+                   model.same_hid, model.value_rescale)
         twin.load_state_dict(model.state_dict())
         return twin.to(device)
 
@@ -47,7 +51,12 @@ class R2D2Agent(nn.Module):
         online_q = self.online_net(lift(obs), hid, action["a"].unsqueeze(0))[0].squeeze(0)
         next_a = self.online_net.act(next_obs, next_hid)[0].unsqueeze(0)
         boot_q = self.target_net(lift(next_obs), next_hid, next_a)[0].squeeze(0)
-        target = reward + bootstrap * (self.gamma ** self.multi_step) * boot_q
+        if self.value_rescale > 0:
+            eps = self.value_rescale
+            target = value_rescale_h(
+                reward + bootstrap * (self.gamma ** self.multi_step) * value_rescale_h_inv(boot_q, eps), eps)
+        else:
+            target = reward + bootstrap * (self.gamma ** self.multi_step) * boot_q
         return (target - online_q).abs().cpu()
 
     @torch.no_grad()
@@ -81,7 +90,12 @@ class R2D2Agent(nn.Module):
         gamma_n = self.gamma ** self.multi_step
         cols = []
         for i in range(self.seq_len):
-            target = reward[i] + bootstrap[i] * (gamma_n * target_qa[i + self.multi_step])
+            if self.value_rescale > 0:
+                eps = self.value_rescale
+                target = value_rescale_h(
+                    reward[i] + bootstrap[i] * (gamma_n * value_rescale_h_inv(target_qa[i + self.multi_step], eps)), eps)
+            else:
+                target = reward[i] + bootstrap[i] * (gamma_n * target_qa[i + self.multi_step])
             pad = (i >= (seq_len - b)).float()
             cols.append((target.detach() - online_qa[i]) * (1 - pad))
         return torch.stack(cols, 1)
