@@ -603,6 +603,25 @@ const float* rela_apex_learner_stats_dev(const rela_apex_learner* l);
  * gradients were computed with).  Valid until the next rela_apex_learner_loss.                  */
 int rela_apex_learner_debug_activations(rela_apex_learner* l, float** a1, float** a2, float** a3, float** h, int* batch);
 
+/* Test tap: the backward pass of the conv trunk (csrc/learner_common.h: trunk_backward, shared by both learners) as one
+ * call whose inputs are the forward's activations, so their > 0 patterns -- the ReLU masks -- are data of the call.
+ * All pointers are device pointers; the call allocates its own scratch, synchronises and frees it.
+ *   obs      u8  [frames][4][84][84]
+ *   a1, a2   f32 [frames][400][32], [frames][81][64]   relu(conv1), relu(conv2), channel-last (csrc/ffnet_layout.h)
+ *   d_a3     f32 [frames][49][64]   gradient w.r.t. relu(conv3), channel-last, ALREADY masked by a3 > 0
+ *   conv2_w, conv3_w   [64][32][4][4], [64][64][3][3]   (state_dict layout)
+ *   g_c1w .. g_c3b     out: the six gradients in state_dict layout ([32][4][8][8], [32], [64][32][4][4], [64], [64][64][3][3], [64])
+ *   d_a2, d_a1         out: [frames][81][64], [frames][400][32], channel-last, masked by a2 > 0 / a1 > 0
+ * mode: 0 f32, 1 bf16x2, 2 f32x3 (the learners' precision modes).  lanes: 1 = two lanes with the weight fragments packed
+ * ahead, as rela_apex_learner_grad runs it; 0 = one lane, as the R2D2 learner runs it in f32 and bf16x2 (its f32x3 mode keeps
+ * the trunk's backward in f32) and the Ape-X learner under RELA_LEARNER_LANES=1 in all three.  fast_wgrad_min_frames: the frame
+ * count from which the bf16x2 mode runs conv2's / conv3's weight gradients on their bf16 kernels; <= 0 = the learners'
+ * threshold (2,048).  1 <= frames <= 65,536.                                                                     */
+int rela_debug_trunk_backward(int frames, int mode, int lanes, int fast_wgrad_min_frames, const uint8_t* obs,
+                              const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
+                              const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b, float* g_c3w,
+                              float* g_c3b, float* d_a2, float* d_a1, void* stream);
+
 /* ===================================================================================
  * R2D2 learner step  --  pyrela/main.py:206-251 with R2D2Agent.loss (pyrela/r2d2.py:189-206):
  * td_err (:122-187: burn-in unroll without gradient, state zeroed where terminal[burn_in-1], training

@@ -456,6 +456,81 @@ extern "C" int rela_apex_learner_grad(rela_apex_learner* l, void* stream_) {
   return RELA_OK;
 }
 
+// Test tap: trunk_backward (learner_common.h) on its own, with the activations and the masked d_a3 as inputs of the call.
+// Everything the learners keep across steps (scratch, the permuted weight copies, the side lane) lives for this one call.
+namespace {
+struct TrunkTapScratch {
+  std::vector<void*> bufs;
+  hipStream_t side = nullptr;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  ~TrunkTapScratch() {
+    for (void* p : bufs) (void)hipFree(p);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (side) (void)hipStreamDestroy(side);
+  }
+  template <class T>
+  hipError_t alloc(T** p, size_t bytes) {
+    void* v = nullptr;
+    const hipError_t e = hipMalloc(&v, bytes);
+    if (e == hipSuccess) bufs.push_back(v);
+    *p = static_cast<T*>(v);
+    return e;
+  }
+};
+}  // namespace
+
+extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fast_wgrad_min_frames, const uint8_t* obs,
+                                         const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
+                                         const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b,
+                                         float* g_c3w, float* g_c3b, float* d_a2, float* d_a1, void* stream_) {
+  RELA_CHECK(frames >= 1 && frames <= 65536 && mode >= 0 && mode <= 2 && (lanes == 0 || lanes == 1), RELA_EINVAL,
+             "rela_debug_trunk_backward: bad arguments (frames %d, mode %d, lanes %d)", frames, mode, lanes);
+  RELA_CHECK(obs && a1 && a2 && d_a3 && conv2_w && conv3_w && g_c1w && g_c1b && g_c2w && g_c2b && g_c3w && g_c3b && d_a2 &&
+                 d_a1,
+             RELA_EINVAL, "rela_debug_trunk_backward: a pointer is NULL");
+  hipStream_t s = (hipStream_t)stream_;
+  TrunkTapScratch sc;
+  const size_t cpart_bytes = sizeof(float) * kColsumBlocks * (32 + 512 + 64 + 64 + 32);  // as the learners size it
+  float *w2p = nullptr, *w3p = nullptr;
+  RELA_HIP(sc.alloc(&w2p, sizeof(float) * 64 * 512));
+  RELA_HIP(sc.alloc(&w3p, sizeof(float) * 64 * 576));
+  hipLaunchKernelGGL(permute_weights, dim3(ceil_div(64 * 512, 256)), dim3(256), 0, s, kPermConv2, conv2_w, w2p, 64 * 512);
+  hipLaunchKernelGGL(permute_weights, dim3(ceil_div(64 * 576, 256)), dim3(256), 0, s, kPermConv3, conv3_w, w3p, 64 * 576);
+  TrunkBwd t{};
+  t.Bn = frames, t.obs = obs, t.a1 = a1, t.a2 = a2, t.d_a3 = d_a3, t.d_a2 = d_a2, t.d_a1 = d_a1;
+  t.w2p = w2p, t.w3p = w3p;
+  t.g_c1w = g_c1w, t.g_c1b = g_c1b, t.g_c2w = g_c2w, t.g_c2b = g_c2b, t.g_c3w = g_c3w, t.g_c3b = g_c3b;
+  t.fast = mode == 1;
+  if (fast_wgrad_min_frames > 0) t.fast_wgrad_min_frames = fast_wgrad_min_frames;
+  RELA_HIP(sc.alloc(&t.col, sizeof(float) * trunk_col_floats((size_t)frames)));
+  RELA_HIP(sc.alloc(&t.part, sizeof(float) * kTrunkPartFloats));
+  RELA_HIP(sc.alloc(&t.cpart, cpart_bytes));
+  t.emu = mode == 2;
+  if (lanes) {  // as rela_apex_learner_grad fills it; else one lane, as the R2D2 learner (and RELA_LEARNER_LANES=1)
+    RELA_HIP(hipStreamCreateWithFlags(&sc.side, hipStreamNonBlocking));
+    for (hipEvent_t& e : sc.ev) RELA_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    t.side = sc.side, t.ev_da3 = sc.ev[0], t.ev_da2 = sc.ev[1], t.ev_side = sc.ev[2];
+    RELA_HIP(sc.alloc(&t.part_side, sizeof(float) * kTrunkPartFloats));
+    RELA_HIP(sc.alloc(&t.cpart_side, cpart_bytes));
+    if (t.fast) {  // the data-gradient weight fragments packed ahead, as repack() does
+      void *frag2 = nullptr, *frag3 = nullptr;
+      RELA_HIP(sc.alloc(&frag2, dgfast::kFrag2Bytes));
+      RELA_HIP(sc.alloc(&frag3, dgfast::kFrag3Bytes));
+      dgfast::pack_frags(w2p, w3p, frag2, frag3, s);
+      t.frag2 = frag2, t.frag3 = frag3;
+    }
+  }
+  trunk_backward(t, s);
+  const hipError_t launched = hipGetLastError();
+  // (the scratch goes away with `sc`: both lanes must be done with it whatever happened)
+  const hipError_t done = hipStreamSynchronize(s);
+  if (sc.side) (void)hipStreamSynchronize(sc.side);
+  RELA_HIP(launched);
+  RELA_HIP(done);
+  return RELA_OK;
+}
+
 extern "C" int rela_apex_learner_apply(rela_apex_learner* l, void* stream_) {
   RELA_CHECK(l && l->loaded, RELA_ESTATE, "rela_apex_learner_apply: parameters were never loaded");
   hipStream_t s = (hipStream_t)stream_;

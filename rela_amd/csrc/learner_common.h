@@ -578,6 +578,9 @@ struct TrunkBwd {
   // the f32x3 mode: the weight-gradient GEMMs below (contraction over batch x positions) on the bf16 MFMA with three-part
   // operands, f32 accuracy (r4 at 512 frames, us f32 -> three-part: conv3 49 -> 35, conv2 63 -> 52, conv1 110 -> 102)
   bool emu = false;
+  // frames from which `fast` runs conv2's / conv3's weight gradients on wgrad_conv{2,3}_bf16 (both learners keep the
+  // default; rela_debug_trunk_backward lowers it so that small ragged frame counts reach those kernels)
+  int fast_wgrad_min_frames = kFastWgradMinFrames;
   // Two-lane form (the Ape-X learner): conv3's and conv2's weight gradients, and the column sums of every tensor that
   // exists by then (the caller's pending jobs, d_a3, d_a2), run on `side` next to the data-gradient chain on the
   // caller's stream; the caller's stream waits for the side lane before trunk_backward returns.  Every kernel computes
@@ -629,7 +632,7 @@ inline void trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending
   if (lanes) lane_dep(t.ev_da3, s, sw);  // d_a3 (and everything the pending jobs read) is ready
   // conv2 / conv3 on bf16 MFMA only for many frames (R2D2: T * B): at 512 frames their per-block fixed costs (LDS
   // zero fill, 256 partial tiles of 128 / 144 KB for reduce_splits) cancel the gain (Ape-X: step 0.83 -> 0.91 ms)
-  const bool fast23 = t.fast && Bn >= kFastWgradMinFrames;
+  const bool fast23 = t.fast && Bn >= t.fast_wgrad_min_frames;
   if (fast23) {  // conv3's weight gradient on bf16 MFMA (wgrad_conv3_bf16.h)
     int blocks = 0;
     {

@@ -187,13 +187,17 @@ def test_learner_fast_mode_within_stated_tolerance(B):
     learner.close()
 
 
-@pytest.mark.parametrize("B", [512, 200])
+FAST_WGRAD_MIN_FRAMES = 2048  # csrc/learner_common.h: from here conv2's / conv3's weight gradients run on bf16 MFMA too
+
+
+@pytest.mark.parametrize("B", [512, 200, 2051])
 def test_fast_mode_gradients_match_autograd_on_the_forwards_own_relu_pattern(B):
     """The bf16x2 step's gradients against PyTorch autograd of the SAME network with the ReLUs replaced by the 0/1
     pattern the HIP forward actually produced (rela_apex_learner_debug_activations): where a pre-activation sits
     within rounding of zero the two forwards may disagree about a unit, and the gradient of the network is
     discontinuous there -- with the pattern fixed the comparison is as tight as the f32 mode's own bound against
-    autograd (2e-3 of each tensor's largest entry; RTOL / ATOL above)."""
+    autograd (2e-3 of each tensor's largest entry; RTOL / ATOL above).  B = 2,051: the Ape-X wiring of the path that
+    tests/test_trunk_backward_gpu.py pins call by call -- wgrad_conv2_bf16 and wgrad_conv3_bf16 on the side lane."""
     import torch
     import torch.nn.functional as F
 
@@ -206,7 +210,12 @@ def test_fast_mode_gradients_match_autograd_on_the_forwards_own_relu_pattern(B):
     batch, w = make_batch(B, A, 31)
     learner = HipApexLearner.from_agent(agent, B)
     learner.set_precision("bf16x2")
-    loss, prio = learner.backward(batch, w)
+    from rela_amd import _capi as capi
+
+    with capi.launch_census() as census:
+        loss, prio = learner.backward(batch, w)
+    _assert_fast_learner_kernels(census.counts, B)
+    assert ({"wgrad_conv2_bf16", "wgrad_conv3_bf16"} <= set(census.counts)) == (B >= FAST_WGRAD_MIN_FRAMES), census.counts
     a1, a2, a3, h = learner.debug_activations()
     m1 = (a1 > 0).float().reshape(B, 20, 20, 32).permute(0, 3, 1, 2)
     m2 = (a2 > 0).float().reshape(B, 9, 9, 64).permute(0, 3, 1, 2)
