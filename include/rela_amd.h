@@ -616,7 +616,7 @@ int rela_apex_learner_debug_activations(rela_apex_learner* l, float** a1, float*
  * ahead, as rela_apex_learner_grad runs it; 0 = one lane, as the R2D2 learner runs it in f32 and bf16x2 (its f32x3 mode keeps
  * the trunk's backward in f32) and the Ape-X learner under RELA_LEARNER_LANES=1 in all three.  fast_wgrad_min_frames: the frame
  * count from which the bf16x2 mode runs conv2's / conv3's weight gradients on their bf16 kernels; <= 0 = the learners'
- * threshold (2,048).  1 <= frames <= 65,536.                                                                     */
+ * threshold (2,048).  1 <= frames <= 32,768.                                                                     */
 int rela_debug_trunk_backward(int frames, int mode, int lanes, int fast_wgrad_min_frames, const uint8_t* obs,
                               const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
                               const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b, float* g_c3w,

@@ -76,6 +76,7 @@ __device__ __forceinline__ void split4x3(float4 v, uint2& hi, uint2& mid, uint2&
 template <int BM_, int BN_, int WM_, int WN_, bool AMC_, int PARTS_ = 2>
 struct TileCfg {
   static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, PARTS = PARTS_;
+  static constexpr int BPARTS = PARTS;  // parts of the B operand (SinglePartB below: 1)
   static constexpr bool AMC = AMC_;
   static_assert(PARTS == 2 || PARTS == 3, "two or three bf16 parts per operand");
   static_assert(WM * WN == 8, "8 wavefronts per block");
@@ -90,6 +91,16 @@ struct TileCfg {
   static constexpr int LDS_BYTES = 2 * BUF;
   static constexpr int A_V4 = BM * BK / 4, B_V4 = BN * BK / 4;
   static constexpr int A_IT = (A_V4 + kT - 1) / kT, B_IT = (B_V4 + kT - 1) / kT;
+};
+// A three-part tile whose B operand is exact in ONE bf16 (conv1's weight gradient: B = the u8 frames, 8 significant bits):
+// B is converted to bf16 directly, stored and read as one image, and only the three products with b's hi part are
+// multiplied.  The mid and lo parts would be zeros and their MFMAs would add +-0: the same values as the full form.
+template <class Base>
+struct SinglePartB : Base {
+  static_assert(Base::PARTS == 3, "the one-part B operand goes with a three-part A");
+  static constexpr int BPARTS = 1;
+  static constexpr int BUF = Base::PARTS * Base::A_HALF + Base::B_HALF;
+  static constexpr int LDS_BYTES = 2 * BUF;
 };
 
 // Block -> (N tile, M tile, K split).  Workgroups are dealt round-robin over the 8 XCDs by linear id, so on the plain 3-D
@@ -190,8 +201,8 @@ __global__ __launch_bounds__(kT) void gemm_bf16x3(const P p, const GridMap gm) {
       else split4(rb[S][j], hi, lo);
       const int off = krow(kr) * T::LDB + q * 8;
       *reinterpret_cast<uint2*>(bb + off) = hi;
-      if constexpr (T::PARTS == 3) *reinterpret_cast<uint2*>(bb + T::B_HALF + off) = mid;
-      *reinterpret_cast<uint2*>(bb + (T::PARTS - 1) * T::B_HALF + off) = lo;
+      if constexpr (T::BPARTS == 3) *reinterpret_cast<uint2*>(bb + T::B_HALF + off) = mid;
+      if constexpr (T::BPARTS > 1) *reinterpret_cast<uint2*>(bb + (T::BPARTS - 1) * T::B_HALF + off) = lo;
     }
   };
 
@@ -237,12 +248,12 @@ __global__ __launch_bounds__(kT) void gemm_bf16x3(const P p, const GridMap gm) {
     if (cur + D < c1) gload(cur + D, cs);
     const uint8_t* base = smem + buf * T::BUF;
     const uint8_t* bb = base + T::PARTS * T::A_HALF;
-    bf16x8 bp[T::TN][T::PARTS];  // [..][0] = hi ... [..][PARTS - 1] = lo
+    bf16x8 bp[T::TN][T::BPARTS];  // [..][0] = hi ... [..][BPARTS - 1] = lo
 #pragma unroll
     for (int u = 0; u < T::TN; ++u) {
       const int col0 = (wn * T::TN + u) * 16;
 #pragma unroll
-      for (int q = 0; q < T::PARTS; ++q) bp[u][q] = frag_tr(bb + q * T::B_HALF, T::LDB, col0);
+      for (int q = 0; q < T::BPARTS; ++q) bp[u][q] = frag_tr(bb + q * T::B_HALF, T::LDB, col0);
     }
 #pragma unroll
     for (int t = 0; t < T::TM; ++t) {
@@ -258,6 +269,10 @@ __global__ __launch_bounds__(kT) void gemm_bf16x3(const P p, const GridMap gm) {
         if constexpr (T::PARTS == 2) {
           acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[1], bp[u][0], acc[t][u], 0, 0, 0);
           acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][1], acc[t][u], 0, 0, 0);
+          acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][0], acc[t][u], 0, 0, 0);
+        } else if constexpr (T::BPARTS == 1) {  // b = its hi part: the three products of the six below that are not zero
+          accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[2], bp[u][0], accs[t][u], 0, 0, 0);
+          accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[1], bp[u][0], accs[t][u], 0, 0, 0);
           acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][0], acc[t][u], 0, 0, 0);
         } else {  // (a part, b part) with i + j <= 2, smallest first; hi * hi alone in the main accumulator
           accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[2], bp[u][0], accs[t][u], 0, 0, 0);

@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "common.h"
 #include "prof.h"
 
@@ -36,6 +38,19 @@ struct TileCfg {
   static constexpr int B_FLOATS = BK * LDB;
   static constexpr int A_V4 = BM * BK / 4, B_V4 = BN * BK / 4;
   static constexpr int A_IT = (A_V4 + kLT - 1) / kLT, B_IT = (B_V4 + kLT - 1) / kLT;
+};
+
+// Optional (compile time): a Problem with a member `static constexpr int kFoldChunks = F` gets its sum in GROUPS of F
+// chunks -- after every F chunks the accumulator is added to a running total and cleared, so an element is
+// ((0 + g0) + g1) + ... with each group summed from zero in k order: bit for bit what F-chunk GEMMs per group followed by
+// a sum over the groups in order give.  For launches without split-K whose chunk count is a multiple of F.
+template <class P, class = void>
+struct fold_chunks {
+  static constexpr int value = 0;
+};
+template <class P>
+struct fold_chunks<P, std::void_t<decltype(P::kFoldChunks)>> {
+  static constexpr int value = P::kFoldChunks;
 };
 
 template <class T, class P>
@@ -107,6 +122,14 @@ __global__ __launch_bounds__(kLT) void gemm_lds(const P p) {
   for (int t = 0; t < T::TM; ++t)
 #pragma unroll
     for (int u = 0; u < T::TN; ++u) acc[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+  constexpr int FOLD = fold_chunks<P>::value;
+  f32x4 tot[FOLD ? T::TM : 1][FOLD ? T::TN : 1];
+  if constexpr (FOLD > 0) {
+#pragma unroll
+    for (int t = 0; t < T::TM; ++t)
+#pragma unroll
+      for (int u = 0; u < T::TN; ++u) tot[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
 
   if (c0 < c1) {
     gload(c0);
@@ -131,6 +154,17 @@ __global__ __launch_bounds__(kLT) void gemm_lds(const P p) {
 #pragma unroll
         for (int u = 0; u < T::TN; ++u) acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], b[u], acc[t][u], 0, 0, 0);
     }
+    if constexpr (FOLD > 0) {
+      if ((ch - c0 + 1) % FOLD == 0) {  // (block-uniform) a group is complete
+#pragma unroll
+        for (int t = 0; t < T::TM; ++t)
+#pragma unroll
+          for (int u = 0; u < T::TN; ++u) {
+            tot[t][u] += acc[t][u];
+            acc[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+          }
+      }
+    }
     if (ch + 1 < c1) sstore(buf ^ 1);
     __syncthreads();
   }
@@ -143,7 +177,10 @@ __global__ __launch_bounds__(kLT) void gemm_lds(const P p) {
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + (wm * T::TM + t) * 16 + kk * 4 + r;
         const int n = n0 + (wn * T::TN + u) * 16 + li;
-        if (m < p.M && n < p.N) p.store(blockIdx.z, m, n, acc[t][u][r]);
+        if (m < p.M && n < p.N) {
+          if constexpr (FOLD > 0) p.store(blockIdx.z, m, n, tot[t][u][r]);
+          else p.store(blockIdx.z, m, n, acc[t][u][r]);
+        }
       }
 }
 

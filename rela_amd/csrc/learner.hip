@@ -11,8 +11,8 @@
 //             v_mfma_f32_16x16x4_f32, f32 throughout):
 //               dgrad  d_h   = d_ha  x Wh            (relu mask in the epilogue)
 //                      d_a3  = d_h   x Wfc'          (Wfc' = fc weight in channel-last k order)
-//                      col3  = d_a3' x W3'  -> col2im3 -> d_a2     (d_a3' = rows (b,pos), 64 channels)
-//                      col2  = d_a2' x W2'  -> col2im2 -> d_a1
+//                      d_a2  = convT(d_a3, W3'), d_a1 = convT_stride2(d_a2, W2'): rows = the layer's input pixels,
+//                              k = (tap, output channel), the gather of the output pixels in the A loader
 //               wgrad  dWh   = d_ha^T x h,  dWfc = d_h^T x a3,
 //                      dW3 = d_a3'^T x im2col(a2), dW2 = d_a2'^T x im2col(a1), dW1 = d_a1'^T x im2col(s)
 //                      (im2col is index arithmetic in the B loader; the long reductions over
@@ -46,7 +46,6 @@ struct rela_apex_learner {
   int64_t ws_bytes = 0;
   float *q = nullptr;  // [3][B][A]
   float *td = nullptr, *d_ha = nullptr, *d_h = nullptr, *d_a3 = nullptr, *d_a2 = nullptr, *d_a1 = nullptr;
-  float *col = nullptr;    // max(B*81*512, B*49*576)
   float *part = nullptr;   // split-K partial tiles
   float *cpart = nullptr;  // colsum partials [64][512]
   float *s32 = nullptr;
@@ -96,7 +95,7 @@ int repack(rela_apex_learner* l, bool online, bool target, hipStream_t s) {
 extern "C" int rela_apex_learner_create(rela_apex_learner** out, int num_action, int max_batch, int multi_step,
                                         float gamma, int optimizer, float lr, float eps, float grad_clip,
                                         int device) {
-  RELA_CHECK(out && num_action >= 1 && num_action <= 31 && max_batch >= 1 && multi_step >= 1 &&
+  RELA_CHECK(out && num_action >= 1 && num_action <= 31 && max_batch >= 1 && max_batch <= kTrunkMaxFrames && multi_step >= 1 &&
                  (optimizer == 0 || optimizer == 1),
              RELA_EINVAL, "rela_apex_learner_create: bad arguments (A=%d batch=%d n=%d optimizer=%d)", num_action,
              max_batch, multi_step, optimizer);
@@ -153,7 +152,6 @@ extern "C" int rela_apex_learner_create(rela_apex_learner** out, int num_action,
   RELA_HIP(hipMalloc(&l->d_a3, sizeof(float) * B * kA3));
   RELA_HIP(hipMalloc(&l->d_a2, sizeof(float) * B * kA2));
   RELA_HIP(hipMalloc(&l->d_a1, sizeof(float) * B * kA1));
-  RELA_HIP(hipMalloc(&l->col, sizeof(float) * trunk_col_floats(B)));
   RELA_HIP(hipMalloc(&l->part, sizeof(float) * kTrunkPartFloats));
   RELA_HIP(hipMalloc(&l->cpart, sizeof(float) * kColsumBlocks * (32 + 512 + 64 + 64 + 32)));  // all five jobs
   RELA_HIP(hipMalloc(&l->s32, sizeof(float) * 32));
@@ -178,7 +176,7 @@ extern "C" void rela_apex_learner_destroy(rela_apex_learner* l) {
   DeviceGuard g(l->device);
   (void)hipDeviceSynchronize();
   void* ps[] = {l->P,  l->PT,   l->G,    l->S1,   l->S2,   l->w2p, l->w3p,  l->wfcp,  l->ws_on, l->ws_tmp, l->q,
-                l->td, l->d_ha, l->d_h,  l->d_a3, l->d_a2, l->d_a1, l->col, l->part,  l->cpart, l->s32,    l->npart,
+                l->td, l->d_ha, l->d_h,  l->d_a3, l->d_a2, l->d_a1, l->part,  l->cpart, l->s32,    l->npart,
                 l->norm, l->loss, l->part_side, l->cpart_side, l->frag2, l->frag3};
   for (void* p : ps) (void)hipFree(p);
   for (hipEvent_t e : l->ev)
@@ -439,7 +437,7 @@ extern "C" int rela_apex_learner_grad(rela_apex_learner* l, void* stream_) {
   {
     TrunkBwd t{};
     t.Bn = Bn, t.obs = obs, t.a1 = w.a1, t.a2 = w.a2, t.d_a3 = l->d_a3, t.d_a2 = l->d_a2, t.d_a1 = l->d_a1;
-    t.col = l->col, t.part = l->part, t.cpart = l->cpart, t.w2p = l->w2p, t.w3p = l->w3p;
+    t.part = l->part, t.cpart = l->cpart, t.w2p = l->w2p, t.w3p = l->w3p;
     t.g_c1w = Gm[0], t.g_c1b = Gm[1], t.g_c2w = Gm[2], t.g_c2b = Gm[3], t.g_c3w = Gm[4], t.g_c3b = Gm[5];
     t.fast = rela_ffnet_precision(l->online) == 1;
     t.emu = g6;
@@ -484,7 +482,7 @@ extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fa
                                          const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
                                          const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b,
                                          float* g_c3w, float* g_c3b, float* d_a2, float* d_a1, void* stream_) {
-  RELA_CHECK(frames >= 1 && frames <= 65536 && mode >= 0 && mode <= 2 && (lanes == 0 || lanes == 1), RELA_EINVAL,
+  RELA_CHECK(frames >= 1 && frames <= kTrunkMaxFrames && mode >= 0 && mode <= 2 && (lanes == 0 || lanes == 1), RELA_EINVAL,
              "rela_debug_trunk_backward: bad arguments (frames %d, mode %d, lanes %d)", frames, mode, lanes);
   RELA_CHECK(obs && a1 && a2 && d_a3 && conv2_w && conv3_w && g_c1w && g_c1b && g_c2w && g_c2b && g_c3w && g_c3b && d_a2 &&
                  d_a1,
@@ -503,7 +501,6 @@ extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fa
   t.g_c1w = g_c1w, t.g_c1b = g_c1b, t.g_c2w = g_c2w, t.g_c2b = g_c2b, t.g_c3w = g_c3w, t.g_c3b = g_c3b;
   t.fast = mode == 1;
   if (fast_wgrad_min_frames > 0) t.fast_wgrad_min_frames = fast_wgrad_min_frames;
-  RELA_HIP(sc.alloc(&t.col, sizeof(float) * trunk_col_floats((size_t)frames)));
   RELA_HIP(sc.alloc(&t.part, sizeof(float) * kTrunkPartFloats));
   RELA_HIP(sc.alloc(&t.cpart, cpart_bytes));
   t.emu = mode == 2;

@@ -1,6 +1,6 @@
 // learner_common.h -- pieces shared by the two hand-written learner steps (learner.hip: Ape-X /
 // AtariFFNet; learner_r2d2.hip: R2D2 / AtariLSTMNet): the gemm_lds problem descriptions of the conv trunk's
-// backward pass, col2im, split-K reduction, column sums, global-norm clipping and the optimisers.
+// backward pass, split-K reduction, column sums, global-norm clipping and the optimisers.
 // Everything sits in an anonymous namespace: each translation unit gets its own copy of the kernels.
 #pragma once
 #include <cmath>
@@ -27,6 +27,10 @@ using TileDgrad = TileCfg<128, 64, 4, 2, false>;  // M = batch rows, A k-contigu
 using TileWfc = TileCfg<128, 64, 4, 2, true>;     // fc weight gradient (M = 512 units)
 using TileW64 = TileCfg<64, 64, 2, 4, true>;      // conv2 / conv3 weight gradients (M = 64 channels)
 using TileW32 = TileCfg<32, 64, 2, 4, true>;      // conv1 / head weight gradients (M = 32)
+// conv3's / conv2's data gradients (N = 64 / 32 input channels): 64 rows per block measured ahead of 128 (and of 256 for
+// conv2) at 512 frames -- K is only 576 / 256, so more and smaller blocks hide more of each block's fixed costs
+using TileDgrad3 = TileCfg<64, 64, 2, 4, false>;
+using TileDgrad2 = TileCfg<64, 32, 4, 2, false>;
 // the same shapes on the bf16 matrix cores (gemm_bf16x3.h: operands split into bf16 hi + lo on the way into LDS, three
 // MFMAs per product): the learners' bf16x2 mode.
 using Tile3Dgrad = gemm3::TileCfg<128, 64, 4, 2, false>;
@@ -40,6 +44,8 @@ using Tile6Dgrad = gemm3::TileCfg<128, 64, 4, 2, false, 3>;
 using Tile6Wfc = gemm3::TileCfg<128, 64, 4, 2, true, 3>;
 using Tile6W64 = gemm3::TileCfg<64, 64, 2, 4, true, 3>;
 using Tile6W32 = gemm3::TileCfg<32, 64, 2, 4, true, 3>;
+// conv1's weight gradient: the B operand is the u8 frame, exact in ONE bf16 part -- its mid and lo parts would be zeros
+using Tile6W32U8 = gemm3::SinglePartB<Tile6W32>;
 
 
 // d_h[b][u] = relu'(h) * sum_k d_ha[b][k] * Wh[k][u]      Wh rows: 0..A-1 = fc_a.weight, 31 = fc_v.weight
@@ -118,13 +124,68 @@ struct ProbFcWgrad : ProbBase {
   }
 };
 
-// col[(b,pos)][j] = sum_oc d_out[(b,pos)][oc] * Wp[oc][j]     j = (kh,kw,c)   (64 output channels)
-struct ProbConvDgrad : ProbBase {
-  const float *d_out, *wp;
-  float* col;
-  __device__ float4 loadA(int m, int k) const { return m < M ? ld4(d_out + (size_t)m * 64 + k) : zero4(); }
-  __device__ float4 loadB(int k, int n) const { return ld4(wp + (size_t)k * N + n); }
-  __device__ void store(int, int m, int n, float v) const { col[(size_t)m * N + n] = v; }
+// ---- conv3 / conv2 data gradients: the transposed convolution as ONE GEMM over the pixels of the layer's INPUT ----------
+// Rows are the pixels whose gradient is wanted, k runs over (tap, output channel), and the A loader gathers the output
+// pixel that the tap connects to the row's pixel (zeros outside the output image) -- index arithmetic, as im2col is in
+// ProbConvWgrad::loadB.  The ReLU mask of the layer below is applied in the epilogue: no column buffer, no col2im pass.
+// A tap is two chunks of 32 k (64 output channels), and the sum is folded tap by tap (gemm_lds.h: kFoldChunks): each
+// tap's 64 terms from zero in channel order, the taps added in (kh, kw) order -- the association of the column form
+// this replaces (a 64-term GEMM per tap, then col2im's sum over the taps), so every element has the same bits as before.
+// A tap outside the image contributes an exact zero where col2im skipped it.
+// d_a2[b][y][x][c] = relu'(a2) * sum_{kh,kw,oc} d_a3[b][y-kh][x-kw][oc] * W3p[oc][(kh*3+kw)*64 + c]
+//   M = frames * 81, N = 64, K = 9 * 64, k = (kh*3+kw)*64 + oc
+struct ProbDgrad3 : ProbBase {
+  static constexpr int kFoldChunks = 2;
+  const float *d_out, *wp, *a2;  // d_out [b][49][64]; wp = w3p (permute_weights); a2 [b][81][64]
+  float* d_a2;
+  __device__ float4 loadA(int m, int k) const {
+    if (m >= M) return zero4();
+    const int b = m / 81, pix = m - b * 81;
+    const int y = pix / 9, x = pix - y * 9;
+    const int tap = k >> 6, oc = k & 63;
+    const int kh = tap / 3, kw = tap - kh * 3;
+    const int oy = y - kh, ox = x - kw;
+    if ((unsigned)oy >= 7u || (unsigned)ox >= 7u) return zero4();
+    return ld4(d_out + ((size_t)b * 49 + oy * 7 + ox) * 64 + oc);
+  }
+  __device__ float4 loadB(int k, int n) const { return ld4(wp + (size_t)(k & 63) * 576 + (k >> 6) * 64 + n); }
+  __device__ void store(int, int m, int n, float v) const {
+    const size_t i = (size_t)m * 64 + n;
+    d_a2[i] = a2[i] > 0.f ? v : 0.f;
+  }
+};
+
+// conv2 has stride 2: a pixel (y, x) of a1 meets only the taps kh = 2p + s, kw = 2q + r with (s, r) = (y & 1, x & 1), from
+// the output pixel (y/2 - p, x/2 - q).  The four parity classes are four GEMMs with the SAME A operand and different
+// weights, in one launch: the class is the N tile (N = 4 x 32 with BN = 32, so blockIdx.x of gemm_lds IS the class and no
+// tile holds two classes); rows are the 100 pixels (yh, xh) of a class per frame.
+// d_a1[b][2yh+s][2xh+r][c] = relu'(a1) * sum_{p,q,oc} d_a2[b][yh-p][xh-q][oc] * W2p[oc][((2p+s)*4 + 2q+r)*32 + c]
+//   M = frames * 100, N = 4 * 32 (n = (2s+r)*32 + c), K = 4 * 64, k = (2p+q)*64 + oc
+struct ProbDgrad2 : ProbBase {
+  static constexpr int kFoldChunks = 2;
+  const float *d_out, *wp, *a1;  // d_out [b][81][64]; wp = w2p (permute_weights); a1 [b][400][32]
+  float* d_a1;
+  __device__ float4 loadA(int m, int k) const {
+    if (m >= M) return zero4();
+    const int b = m / 100, pix = m - b * 100;
+    const int yh = pix / 10, xh = pix - yh * 10;
+    const int t = k >> 6, oc = k & 63;
+    const int oy = yh - (t >> 1), ox = xh - (t & 1);
+    if ((unsigned)oy >= 9u || (unsigned)ox >= 9u) return zero4();
+    return ld4(d_out + ((size_t)b * 81 + oy * 9 + ox) * 64 + oc);
+  }
+  __device__ float4 loadB(int k, int n) const {
+    const int cls = n >> 5, t = k >> 6;
+    const int kh = (t & 2) + (cls >> 1), kw = 2 * (t & 1) + (cls & 1);
+    return ld4(wp + (size_t)(k & 63) * 512 + (kh * 4 + kw) * 32 + (n & 31));
+  }
+  __device__ void store(int, int m, int n, float v) const {
+    const int cls = n >> 5;
+    const int b = m / 100, pix = m - b * 100;
+    const int yh = pix / 10, xh = pix - yh * 10;
+    const size_t i = ((size_t)b * 400 + (2 * yh + (cls >> 1)) * 20 + 2 * xh + (cls & 1)) * 32 + (n & 31);
+    d_a1[i] = a1[i] > 0.f ? v : 0.f;
+  }
 };
 
 // partial[z][oc][j] = sum_{(b,pos) in slice z} d_out[(b,pos)][oc] * patch(in)[(b,pos)][j]
@@ -166,53 +227,6 @@ struct ProbW1 : ProbBase {
   __device__ void store(int z, int m, int n, float v) const { part[((size_t)z * M + m) * N + n] = v; }
 };
 
-
-// ---- col2im (gather form) with the ReLU mask of the layer below ------------------------------
-// d_a2[b][y][x][c] = relu'(a2) * sum_{kh,kw} col3[(b, (y-kh)*7 + x-kw)][(kh*3+kw)*64 + c]
-__global__ void col2im3(const float* __restrict__ col, const float* __restrict__ a2, float* __restrict__ d_a2,
-                        int Bn) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= Bn * 81 * 16) return;
-  const int c4 = idx & 15, pix = idx >> 4;
-  const int x = pix % 9, y = (pix / 9) % 9, b = pix / 81;
-  float4 s = zero4();
-  for (int kh = 0; kh < 3; ++kh) {
-    const int oy = y - kh;
-    if (oy < 0 || oy >= 7) continue;
-    for (int kw = 0; kw < 3; ++kw) {
-      const int ox = x - kw;
-      if (ox < 0 || ox >= 7) continue;
-      const float4 v = ld4(col + ((size_t)b * 49 + oy * 7 + ox) * 576 + (kh * 3 + kw) * 64 + c4 * 4);
-      s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
-    }
-  }
-  const float4 a = ld4(a2 + (size_t)pix * 64 + c4 * 4);
-  *reinterpret_cast<float4*>(d_a2 + (size_t)pix * 64 + c4 * 4) =
-      make_float4(a.x > 0.f ? s.x : 0.f, a.y > 0.f ? s.y : 0.f, a.z > 0.f ? s.z : 0.f, a.w > 0.f ? s.w : 0.f);
-}
-
-// d_a1[b][y][x][c] = relu'(a1) * sum_{kh,kw: y-kh = 2*oy, x-kw = 2*ox} col2[(b, oy*9+ox)][(kh*4+kw)*32 + c]
-__global__ void col2im2(const float* __restrict__ col, const float* __restrict__ a1, float* __restrict__ d_a1,
-                        int Bn) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= Bn * 400 * 8) return;
-  const int c4 = idx & 7, pix = idx >> 3;
-  const int x = pix % 20, y = (pix / 20) % 20, b = pix / 400;
-  float4 s = zero4();
-  for (int kh = 0; kh < 4; ++kh) {
-    const int ty = y - kh;
-    if (ty < 0 || (ty & 1) || ty > 16) continue;
-    for (int kw = 0; kw < 4; ++kw) {
-      const int tx = x - kw;
-      if (tx < 0 || (tx & 1) || tx > 16) continue;
-      const float4 v = ld4(col + ((size_t)b * 81 + (ty >> 1) * 9 + (tx >> 1)) * 512 + (kh * 4 + kw) * 32 + c4 * 4);
-      s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
-    }
-  }
-  const float4 a = ld4(a1 + (size_t)pix * 32 + c4 * 4);
-  *reinterpret_cast<float4*>(d_a1 + (size_t)pix * 32 + c4 * 4) =
-      make_float4(a.x > 0.f ? s.x : 0.f, a.y > 0.f ? s.y : 0.f, a.z > 0.f ? s.z : 0.f, a.w > 0.f ? s.w : 0.f);
-}
 
 // ---- split-K reduction, written in state_dict order -----------------------------------------
 enum { kRedConv1 = 0, kRedConv2 = 1, kRedConv3 = 2 };
@@ -560,16 +574,19 @@ static_assert(kTrunkPartFloats >= (size_t)kSplitW3 * 64 * 576 && kTrunkPartFloat
                   kTrunkPartFloats >= (size_t)w2fast::kMaxBlocks * 64 * 512,
               "part size");
 static_assert(kSplitW3 * 64 * 576 >= kSplitW2 * 64 * 512 && kSplitW3 * 64 * 576 >= kSplitW1 * 32 * 256, "part size");
-inline size_t trunk_col_floats(size_t frames) { return frames * (size_t)(81 * 512 > 49 * 576 ? 81 * 512 : 49 * 576); }
 
 constexpr int kFastWgradMinFrames = 2048;
+// the most frames of one trunk_backward call: the data gradients put frames * 100 / 64 (conv2) and frames * 81 / 64
+// (conv3) tiles on the grid's y axis
+constexpr int kTrunkMaxFrames = 32768;
+static_assert(((size_t)kTrunkMaxFrames * 100 + TileDgrad2::BM - 1) / TileDgrad2::BM <= 65535 &&
+                  ((size_t)kTrunkMaxFrames * 81 + TileDgrad3::BM - 1) / TileDgrad3::BM <= 65535, "grid y extent of the data gradients");
 struct TrunkBwd {
   int Bn;              // frames
   const uint8_t* obs;  // [Bn][4][84][84] u8
   const float *a1, *a2;  // relu(conv1), relu(conv2), channel-last (ffnet_layout.h)
   const float* d_a3;   // [Bn][49][64] gradient w.r.t. relu(conv3), ALREADY masked by a3 > 0
   float *d_a2, *d_a1;  // scratch [Bn][81][64], [Bn][400][32]
-  float* col;          // scratch, trunk_col_floats(Bn)
   float* part;         // scratch, kTrunkPartFloats
   float* cpart;        // scratch, kColsumBlocks * 512
   const float *w2p, *w3p;  // conv2 / conv3 weights in dgrad k order (permute_weights)
@@ -660,13 +677,10 @@ inline void trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending
     ProfScope prof("learner_dgrad_conv3", s);
     (void)dgfast::launch_conv3(t.d_a3, t.w3p, t.a2, t.d_a2, Bn, t.part, s, t.frag3);
   } else {
-    ProbConvDgrad p{};
-    p.M = Bn * 49, p.N = 576, p.K = 64;
-    p.d_out = t.d_a3, p.wp = t.w3p, p.col = t.col;
-    launch_gemm<TileDgrad>(p, 1, s, "learner_dgrad_conv3");  // (f32x3: K = 64 -- the three-part GEMM measured 89 against 62 us)
-    ProfScope prof("learner_col2im", s);
-    hipLaunchKernelGGL(col2im3, dim3(ceil_div((int64_t)Bn * 81 * 16, 256)), dim3(256), 0, s, (const float*)t.col, t.a2,
-                       t.d_a2, Bn);
+    ProbDgrad3 p{};  // (f32x3 too: exact f32, one launch, no column buffer)
+    p.M = Bn * 81, p.N = 64, p.K = 576;
+    p.d_out = t.d_a3, p.wp = t.w3p, p.a2 = t.a2, p.d_a2 = t.d_a2;
+    launch_gemm<TileDgrad3>(p, 1, s, "learner_dgrad_conv3");
   }
   if (lanes) lane_dep(t.ev_da2, s, sw);  // d_a2 is ready
   if (fast23) {  // conv2's weight gradient on bf16 MFMA (wgrad_conv2_bf16.h)
@@ -699,13 +713,10 @@ inline void trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending
     ProfScope prof("learner_dgrad_conv2", s);
     (void)dgfast::launch_conv2(t.d_a2, t.w2p, t.a1, t.d_a1, Bn, t.part, s, t.frag2);
   } else {
-    ProbConvDgrad p{};
-    p.M = Bn * 81, p.N = 512, p.K = 64;
-    p.d_out = t.d_a2, p.wp = t.w2p, p.col = t.col;
-    launch_gemm<TileDgrad>(p, 1, s, "learner_dgrad_conv2");  // (f32x3: 88 against 77 us, as above)
-    ProfScope prof("learner_col2im", s);
-    hipLaunchKernelGGL(col2im2, dim3(ceil_div((int64_t)Bn * 400 * 8, 256)), dim3(256), 0, s, (const float*)t.col, t.a1,
-                       t.d_a1, Bn);
+    ProbDgrad2 p{};  // the four parity classes in one launch
+    p.M = Bn * 100, p.N = 4 * 32, p.K = 256;
+    p.d_out = t.d_a2, p.wp = t.w2p, p.a1 = t.a1, p.d_a1 = t.d_a1;
+    launch_gemm<TileDgrad2>(p, 1, s, "learner_dgrad_conv2");
   }
   if (t.fast) {  // conv1 on bf16 MFMA (wgrad_conv1_bf16.h): exact u8 frames x (hi + lo) gradients
     int blocks = 0;
@@ -719,9 +730,12 @@ inline void trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending
     ProbW1 p{};
     p.M = 32, p.N = 256, p.K = Bn * 400;
     p.d_out = t.d_a1, p.obs = t.obs, p.part = t.part;
-    if (t.emu) (void)gemm3::launch_gemm<Tile6W32>(p, kSplitW1, s, "learner_wgrad_conv1");
-    else launch_gemm<TileW32>(p, kSplitW1, s, "learner_wgrad_conv1");
-    hipLaunchKernelGGL(reduce_splits, dim3(ceil_div(32 * 256, 256)), dim3(256), 0, s, (const float*)t.part, kSplitW1, 32,
+    // (kSplitW1 splits at every frame count: 3-4 x the splits at <= 1,024 frames, as conv3 / conv2 above, measured 105 ->
+    // 69-75 us at 512 frames, but another split changes the association of g_c1w and with it the bits of a step)
+    const int split1 = kSplitW1;
+    if (t.emu) (void)gemm3::launch_gemm<Tile6W32U8>(p, split1, s, "learner_wgrad_conv1");
+    else launch_gemm<TileW32>(p, split1, s, "learner_wgrad_conv1");
+    hipLaunchKernelGGL(reduce_splits, dim3(ceil_div(32 * 256, 256)), dim3(256), 0, s, (const float*)t.part, split1, 32,
                        256, kRedConv1, t.g_c1w);
   }
   jobs.add(t.d_a1, (int64_t)Bn * 400, 32, t.g_c1b);

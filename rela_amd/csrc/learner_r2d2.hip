@@ -637,7 +637,7 @@ struct rela_r2d2_learner {
   float *ha = nullptr, *q_on = nullptr, *q_tg = nullptr;              // heads of the training rows
   float *qmin = nullptr, *qa_on = nullptr, *qa_tg = nullptr, *dqa = nullptr, *d_ha = nullptr, *d_o = nullptr;
   float *dc_rec = nullptr;
-  float *d_a3 = nullptr, *d_a2 = nullptr, *d_a1 = nullptr, *col = nullptr, *part = nullptr, *cpart = nullptr,
+  float *d_a3 = nullptr, *d_a2 = nullptr, *d_a1 = nullptr, *part = nullptr, *cpart = nullptr,
         *s32 = nullptr;
   double* npart = nullptr;
   float *norm = nullptr, *loss = nullptr, *loss_seq = nullptr;
@@ -872,6 +872,12 @@ extern "C" int rela_r2d2_learner_create(rela_r2d2_learner** out, int num_action,
   const size_t nb = sizeof(float) * (size_t)l->off[14];
   const size_t B = (size_t)max_batch, A = (size_t)num_action, T = (size_t)l->T, Tt = T - burn_in;
   const size_t rowsAll = T * B, rowsTr = Tt * B;
+  if (rowsTr > (size_t)kTrunkMaxFrames) {
+    delete l;
+    set_last_error("rela_r2d2_learner_create: %zu training frames per step, the trunk's backward pass takes %d", rowsTr,
+                   kTrunkMaxFrames);
+    return RELA_EINVAL;
+  }
   auto alloc = [&](float** p, size_t floats, bool zero) -> int {
     RELA_HIP(hipMalloc(p, sizeof(float) * floats));
     if (zero) RELA_HIP(hipMemset(*p, 0, sizeof(float) * floats));
@@ -971,7 +977,6 @@ extern "C" int rela_r2d2_learner_create(rela_r2d2_learner** out, int num_action,
   R2_ALLOC(l->d_a3, rowsTr * kA3, false);
   R2_ALLOC(l->d_a2, rowsTr * kA2, false);
   R2_ALLOC(l->d_a1, rowsTr * kA1, false);
-  R2_ALLOC(l->col, trunk_col_floats(rowsTr), false);
   R2_ALLOC(l->part, kTrunkPartFloats, false);
   R2_ALLOC(l->cpart, (size_t)kColsumBlocks * kGates, false);
   R2_ALLOC(l->s32, 32, false);
@@ -992,7 +997,7 @@ extern "C" void rela_r2d2_learner_destroy(rela_r2d2_learner* l) {
                 l->whhT[0], l->whhT[1], l->bsum[0], l->bsum[1], l->Hs[0],   l->Hs[1],   l->Cs[0], l->Cs[1],   l->wihp,
                 l->a1,    l->a2,      l->a3,      l->gx,      l->rec_part, l->ha,   l->q_on,    l->q_tg,
                 l->qmin,   l->qa_on,  l->qa_tg,   l->dqa,     l->d_ha,    l->d_o,     l->dc_rec, l->d_a3,   l->d_a2,
-                l->d_a1,   l->col,    l->part,    l->cpart,   l->s32,     l->npart,   l->norm,  l->loss,    l->loss_seq};
+                l->d_a1,   l->part,    l->cpart,   l->s32,     l->npart,   l->norm,  l->loss,    l->loss_seq};
   for (void* p : ps) (void)hipFree(p);
   (void)hipFree(l->rec_bar);
   (void)hipFree(l->rec_chain_bar);
@@ -1291,7 +1296,7 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
   {
     TrunkBwd t{};
     t.Bn = rowsTr, t.obs = obs + tr0 * 28224, t.a1 = l->a1 + tr0 * kA1, t.a2 = l->a2 + tr0 * kA2, t.d_a3 = l->d_a3;
-    t.d_a2 = l->d_a2, t.d_a1 = l->d_a1, t.col = l->col, t.part = l->part, t.cpart = l->cpart;
+    t.d_a2 = l->d_a2, t.d_a1 = l->d_a1, t.part = l->part, t.cpart = l->cpart;
     t.w2p = l->w2p, t.w3p = l->w3p;
     t.g_c1w = Gm[0], t.g_c1b = Gm[1], t.g_c2w = Gm[2], t.g_c2b = Gm[3], t.g_c3w = Gm[4], t.g_c3b = Gm[5];
     t.fast = l->precision == 1;
