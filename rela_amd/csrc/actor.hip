@@ -34,7 +34,7 @@ extern "C" int rela_apex_actor_create(rela_apex_actor** out, int rows, int group
                  multi_step >= 1,
              RELA_EINVAL, "rela_apex_actor_create: bad arguments (rows=%d group=%d A=%d n=%d)", rows, group_rows,
              num_action, multi_step);
-  int rc = shard_check_device(device, "rela_apex_actor_create");
+  int rc = check_device(device, "rela_apex_actor_create");
   if (rc != RELA_OK) return rc;
   DeviceGuard g(device);
   auto* a = new rela_apex_actor();

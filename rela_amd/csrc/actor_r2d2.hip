@@ -238,7 +238,7 @@ extern "C" int rela_r2d2_actor_create(rela_r2d2_actor** out, int rows, int group
              RELA_EINVAL, "rela_r2d2_actor_create: bad arguments");
   RELA_CHECK(burn_in <= seq_len && multi_step <= seq_len, RELA_EINVAL,
              "rela_r2d2_actor_create: needs burn_in <= seq_len and multi_step <= seq_len");  // r2d2_actor.h:25-26
-  int rc = shard_check_device(device, "rela_r2d2_actor_create");
+  int rc = check_device(device, "rela_r2d2_actor_create");
   if (rc != RELA_OK) return rc;
   DeviceGuard g(device);
   auto* a = new rela_r2d2_actor();

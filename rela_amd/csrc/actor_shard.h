@@ -61,15 +61,6 @@ struct ActorShardBase {
 
 namespace {
 
-inline int shard_check_device(int device, const char* who) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_last_error("%s: HIP device %d not available (%d visible); there is no CPU path", who, device, ndev);
-    return RELA_ENODEV;
-  }
-  return RELA_OK;
-}
-
 template <class P>
 inline int shard_alloc(P** p, size_t bytes) {  // a zero-filled device buffer
   RELA_HIP(hipMalloc(reinterpret_cast<void**>(p), bytes));

@@ -46,6 +46,15 @@ struct DeviceGuard {
   }
 };
 
+// every create's device check; `who`, the entry point's own name, leads the message
+inline int check_device(int device, const char* who) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+    set_last_error("%s: HIP device %d not available (%d visible); there is no CPU path", who, device, ndev);
+    return RELA_ENODEV;
+  }
+  return RELA_OK;
+}
 
 // Page-locked staging for the small host->device uploads of the hot path (index plans, RNG draws,
 // host-side priorities).  hipMemcpyAsync from pageable memory is only lifetime-safe because the

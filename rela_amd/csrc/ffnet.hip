@@ -37,6 +37,7 @@
 #include "ffnet_layout.h"
 #include "ffnet_plan.h"
 #include "gemm_lds.h"
+#include "param_layout.h"
 #include "prof.h"
 
 namespace rela_amd {
@@ -2148,7 +2149,7 @@ int opt_in_dynamic_lds() {
 
 // The n parameter tensors of a load as device pointers dv[]: the caller's own (on_device), or copies in ONE staging
 // buffer *tmp, which the caller hands to free_staging once its pack kernels are on the stream.
-int stage_params(const float* const* src, const size_t* cnt, int n, int on_device, const char* what, float** tmp,
+int stage_params(const float* const* src, const int64_t* cnt, int n, int on_device, const char* what, float** tmp,
                  const float** dv, hipStream_t s) {
   for (int i = 0; i < n; ++i) RELA_CHECK(src[i], RELA_EINVAL, "%s: parameter %d is NULL", what, i);
   if (on_device) {
@@ -2213,11 +2214,7 @@ struct rela_ffnet {
 extern "C" int rela_ffnet_create(rela_ffnet** out, int num_action, int device) {
   RELA_CHECK(out && num_action >= 1 && num_action <= 31, RELA_EINVAL,
              "rela_ffnet_create: num_action must be in 1..31 (got %d)", num_action);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_last_error("rela_ffnet_create: HIP device %d not available (%d visible); there is no CPU path", device, ndev);
-    return RELA_ENODEV;
-  }
+  if (int rc = check_device(device, "rela_ffnet_create")) return rc;
   DeviceGuard g(device);
   auto* n = new rela_ffnet();
   n->device = device;
@@ -2373,8 +2370,8 @@ int rela_amd::ffnet_load_impl(rela_ffnet* n, const rela_ffnet_params* p, int on_
   hipStream_t s = (hipStream_t)stream_;
   DeviceGuard g(n->device);
   const int A = n->num_action;
-  const size_t cnt[12] = {32 * 256, 32, 64 * 512, 64, 64 * 576, 64, (size_t)512 * 3136, 512, 512, 1, (size_t)A * 512,
-                          (size_t)A};
+  int64_t cnt[kFFNetSegs];
+  ffnet_param_counts(A, cnt);
   const float* src[12] = {p->conv1_w, p->conv1_b, p->conv2_w, p->conv2_b, p->conv3_w, p->conv3_b,
                           p->fc_w,    p->fc_b,    p->v_w,     p->v_b,     p->a_w,     p->a_b};
   const float* dv[12];
@@ -2670,11 +2667,7 @@ inline TrunkLabels lstm_trunk_labels(const char* const* names) { return {names[0
 extern "C" int rela_lstmnet_create(rela_lstmnet** out, int num_action, int device) {
   RELA_CHECK(out && num_action >= 1 && num_action <= 31, RELA_EINVAL,
              "rela_lstmnet_create: num_action must be in 1..31 (got %d)", num_action);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_last_error("rela_lstmnet_create: HIP device %d not available (%d visible); there is no CPU path", device, ndev);
-    return RELA_ENODEV;
-  }
+  if (int rc = check_device(device, "rela_lstmnet_create")) return rc;
   DeviceGuard g(device);
   auto* n = new rela_lstmnet();
   n->device = device;
@@ -2721,8 +2714,8 @@ extern "C" int rela_lstmnet_load(rela_lstmnet* n, const rela_lstmnet_params* p, 
   hipStream_t s = (hipStream_t)stream_;
   DeviceGuard g(n->device);
   const int A = n->num_action;
-  const size_t cnt[14] = {32 * 256, 32, 64 * 512, 64, 64 * 576, 64, (size_t)2048 * 3136, (size_t)2048 * 512, 2048, 2048,
-                          512, 1, (size_t)A * 512, (size_t)A};
+  int64_t cnt[kLstmNetSegs];
+  lstmnet_param_counts(A, cnt);
   const float* src[14] = {p->conv1_w, p->conv1_b, p->conv2_w, p->conv2_b, p->conv3_w, p->conv3_b, p->w_ih,
                           p->w_hh,    p->b_ih,    p->b_hh,    p->v_w,     p->v_b,     p->a_w,     p->a_b};
   const float* dv[14];

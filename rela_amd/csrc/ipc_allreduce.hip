@@ -145,11 +145,7 @@ extern "C" int rela_ipc_allreduce_create(rela_ipc_allreduce** out, int rank, int
   RELA_CHECK(out && desc_out && world >= 1 && world <= kMaxRanks && rank >= 0 && rank < world && bucket_dev && count > 0 &&
                  ((uintptr_t)bucket_dev & 15) == 0,
              RELA_EINVAL, "rela_ipc_allreduce_create: bad arguments (at most %d ranks, a 16-byte aligned bucket)", kMaxRanks);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_last_error("rela_ipc_allreduce_create: HIP device %d not available (%d visible); there is no CPU path", device, ndev);
-    return RELA_ENODEV;
-  }
+  if (int rc = check_device(device, "rela_ipc_allreduce_create")) return rc;
   DeviceGuard g(device);
   auto* a = new rela_ipc_allreduce();
   a->rank = rank, a->world = world, a->device = device, a->device_flags = device_flags ? 1 : 0;

@@ -28,31 +28,18 @@
 
 using namespace rela_amd;
 
-// flat parameter layout: rela_ffnet_params order, every segment padded to 4 floats
-struct rela_apex_learner {
-  int device = 0;
-  int A = 0, Bmax = 0;
-  float gamma_n = 0.f;
-  float vr_eps = 0.f;        // value rescaling of the TD target (rela_apex_learner_set_value_rescale), 0 = off
-  bool loss_called = false;  // ... which is fixed from the first rela_apex_learner_loss on
-  int optimizer = 0;  // 0 RMSprop, 1 Adam
-  float lr = 0.f, opt_eps = 0.f, clip = 0.f;
-  int64_t adam_t = 0;
-  int64_t off[13] = {0};  // segment offsets, off[12] = total
-  float *P = nullptr, *PT = nullptr, *G = nullptr, *S1 = nullptr, *S2 = nullptr;
+// flat parameter layout: rela_ffnet_params order (LearnerCore, learner_common.h)
+static_assert(sizeof(rela_ffnet_params) == kFFNetSegs * sizeof(float*), "rela_ffnet_params is kFFNetSegs pointers");
+struct rela_apex_learner : LearnerCore {
   rela_ffnet *online = nullptr, *target = nullptr;
   float *w2p = nullptr, *w3p = nullptr, *wfcp = nullptr;  // dgrad operand copies
-  void *ws_on = nullptr, *ws_tmp = nullptr;
+  uint8_t *ws_on = nullptr, *ws_tmp = nullptr;
   int64_t ws_bytes = 0;
   float *q = nullptr;  // [3][B][A]
   float *td = nullptr, *d_ha = nullptr, *d_h = nullptr, *d_a3 = nullptr, *d_a2 = nullptr, *d_a1 = nullptr;
   float *part = nullptr;   // split-K partial tiles
   float *cpart = nullptr;  // colsum partials [64][512]
   float *s32 = nullptr;
-  double* npart = nullptr;
-  float* norm = nullptr;  // [0] grad norm, [1] clip coefficient
-  float* loss = nullptr;
-  bool loaded = false;
   // batch of the last rela_apex_learner_loss, until rela_apex_learner_grad consumes it
   int pend_B = 0, last_B = 0;
   int pend_rows = 0;  // rows of the ffnet_ws layout the last forward used for ws_on (B, or 2 B for the merged forward)
@@ -63,14 +50,13 @@ struct rela_apex_learner {
   hipStream_t side = nullptr;
   hipEvent_t ev[8] = {nullptr};  // 0 forward done | 1 unsplit done | 2 d_ha | 3 d_h | 4 d_a3 | 5 d_a2 | 6 side lane done
   float *part_side = nullptr, *cpart_side = nullptr;
-  void *frag2 = nullptr, *frag3 = nullptr;  // conv2 / conv3 data-gradient weight fragments, re-packed with the weights
+  uint8_t *frag2 = nullptr, *frag3 = nullptr;  // conv2 / conv3 data-gradient weight fragments, re-packed with the weights
 };
 
 namespace {
-rela_ffnet_params params_at(const rela_apex_learner* l, float* base) {
+rela_ffnet_params params_at(const rela_apex_learner* l, const float* base) {
   rela_ffnet_params p;
-  const float** f = reinterpret_cast<const float**>(&p);
-  for (int i = 0; i < 12; ++i) f[i] = base + l->off[i];
+  l->params_at(base, &p);
   return p;
 }
 
@@ -92,6 +78,55 @@ int repack(rela_apex_learner* l, bool online, bool target, hipStream_t s) {
 }
 }  // namespace
 
+namespace {
+// everything rela_apex_learner_create allocates; a failure leaves a half-built learner for rela_apex_learner_destroy
+int build_learner(rela_apex_learner* l, int num_action, int max_batch, int multi_step, float gamma, int optimizer, float lr,
+                  float eps, float grad_clip, int device) {
+  l->device = device;
+  l->A = num_action;
+  l->Bmax = max_batch;
+  l->gamma_n = (float)pow((double)gamma, (double)multi_step);  // apex.py:44
+  l->opt.optimizer = optimizer, l->opt.lr = lr, l->opt.eps = eps, l->opt.clip = grad_clip;
+  if (int rc = l->alloc_flat(kFFNetSegs, ffnet_param_counts, num_action)) return rc;
+  const size_t B = (size_t)max_batch, A = (size_t)num_action;
+  if (int rc = rela_ffnet_create(&l->online, num_action, device)) return rc;
+  if (int rc = rela_ffnet_create(&l->target, num_action, device)) return rc;
+  ffnet_label_as_learner(l->online);
+  ffnet_label_as_learner(l->target);
+  ffnet_set_max_rows(l->online, max_batch);
+  ffnet_set_max_rows(l->target, max_batch);
+  DevBuffers& m = l->mem;
+  if (int rc = m.alloc(&l->w2p, 64 * 512, false)) return rc;
+  if (int rc = m.alloc(&l->w3p, 64 * 576, false)) return rc;
+  if (int rc = m.alloc(&l->wfcp, 512 * 3136, false)) return rc;
+  // (the merged split-bf16 forward runs the online net over 2 x batch rows: [s ; s'])
+  l->ws_bytes = std::max(rela_ffnet_workspace_bytes(nullptr, max_batch), rela_ffnet_workspace_bytes(nullptr, 2 * max_batch));
+  if (int rc = m.alloc(&l->ws_on, (size_t)l->ws_bytes, false)) return rc;
+  if (int rc = m.alloc(&l->ws_tmp, (size_t)l->ws_bytes, false)) return rc;
+  if (int rc = m.alloc(&l->q, 3 * B * A, false)) return rc;
+  if (int rc = m.alloc(&l->td, B, false)) return rc;
+  if (int rc = m.alloc(&l->d_ha, B * 32, false)) return rc;
+  if (int rc = m.alloc(&l->d_h, B * 512, false)) return rc;
+  if (int rc = m.alloc(&l->d_a3, B * kA3, false)) return rc;
+  if (int rc = m.alloc(&l->d_a2, B * kA2, false)) return rc;
+  if (int rc = m.alloc(&l->d_a1, B * kA1, false)) return rc;
+  const size_t cpart_floats = (size_t)kColsumBlocks * (32 + 512 + 64 + 64 + 32);  // all five jobs
+  if (int rc = m.alloc(&l->part, kTrunkPartFloats, false)) return rc;
+  if (int rc = m.alloc(&l->cpart, cpart_floats, false)) return rc;
+  if (int rc = m.alloc(&l->s32, 32, false)) return rc;
+  static const bool lanes = !(getenv("RELA_LEARNER_LANES") && atoi(getenv("RELA_LEARNER_LANES")) == 1);
+  if (lanes) {
+    RELA_HIP(hipStreamCreateWithFlags(&l->side, hipStreamNonBlocking));
+    for (hipEvent_t& e : l->ev) RELA_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (int rc = m.alloc(&l->part_side, kTrunkPartFloats, false)) return rc;
+    if (int rc = m.alloc(&l->cpart_side, cpart_floats, false)) return rc;
+    if (int rc = m.alloc(&l->frag2, dgfast::kFrag2Bytes, false)) return rc;
+    if (int rc = m.alloc(&l->frag3, dgfast::kFrag3Bytes, false)) return rc;
+  }
+  return RELA_OK;
+}
+}  // namespace
+
 extern "C" int rela_apex_learner_create(rela_apex_learner** out, int num_action, int max_batch, int multi_step,
                                         float gamma, int optimizer, float lr, float eps, float grad_clip,
                                         int device) {
@@ -99,86 +134,24 @@ extern "C" int rela_apex_learner_create(rela_apex_learner** out, int num_action,
                  (optimizer == 0 || optimizer == 1),
              RELA_EINVAL, "rela_apex_learner_create: bad arguments (A=%d batch=%d n=%d optimizer=%d)", num_action,
              max_batch, multi_step, optimizer);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_last_error("rela_apex_learner_create: HIP device %d not available (%d visible); there is no CPU path",
-                   device, ndev);
-    return RELA_ENODEV;
-  }
+  if (int rc = check_device(device, "rela_apex_learner_create")) return rc;
   DeviceGuard g(device);
   auto* l = new rela_apex_learner();
-  l->device = device;
-  l->A = num_action;
-  l->Bmax = max_batch;
-  l->gamma_n = (float)pow((double)gamma, (double)multi_step);  // apex.py:44
-  l->optimizer = optimizer;
-  l->lr = lr;
-  l->opt_eps = eps;
-  l->clip = grad_clip;
-  const int64_t cnt[12] = {32 * 256, 32, 64 * 512, 64, 64 * 576, 64, (int64_t)512 * 3136, 512, 512, 1,
-                           (int64_t)num_action * 512, num_action};
-  for (int i = 0; i < 12; ++i) l->off[i + 1] = l->off[i] + (cnt[i] + 3) / 4 * 4;
-  const size_t nb = sizeof(float) * (size_t)l->off[12];
-  const size_t B = (size_t)max_batch, A = (size_t)num_action;
-  RELA_HIP(hipMalloc(&l->P, nb));
-  RELA_HIP(hipMalloc(&l->PT, nb));
-  RELA_HIP(hipMalloc(&l->G, nb));
-  RELA_HIP(hipMalloc(&l->S1, nb));
-  RELA_HIP(hipMalloc(&l->S2, nb));
-  RELA_HIP(hipMemset(l->P, 0, nb));
-  RELA_HIP(hipMemset(l->PT, 0, nb));
-  RELA_HIP(hipMemset(l->G, 0, nb));
-  RELA_HIP(hipMemset(l->S1, 0, nb));
-  RELA_HIP(hipMemset(l->S2, 0, nb));
-  int rc = rela_ffnet_create(&l->online, num_action, device);
-  if (rc != RELA_OK) return rc;
-  rc = rela_ffnet_create(&l->target, num_action, device);
-  if (rc != RELA_OK) return rc;
-  ffnet_label_as_learner(l->online);
-  ffnet_label_as_learner(l->target);
-  ffnet_set_max_rows(l->online, max_batch);
-  ffnet_set_max_rows(l->target, max_batch);
-  RELA_HIP(hipMalloc(&l->w2p, sizeof(float) * 64 * 512));
-  RELA_HIP(hipMalloc(&l->w3p, sizeof(float) * 64 * 576));
-  RELA_HIP(hipMalloc(&l->wfcp, sizeof(float) * 512 * 3136));
-  // (the merged split-bf16 forward runs the online net over 2 x batch rows: [s ; s'])
-  l->ws_bytes = std::max(rela_ffnet_workspace_bytes(nullptr, max_batch), rela_ffnet_workspace_bytes(nullptr, 2 * max_batch));
-  RELA_HIP(hipMalloc(&l->ws_on, (size_t)l->ws_bytes));
-  RELA_HIP(hipMalloc(&l->ws_tmp, (size_t)l->ws_bytes));
-  RELA_HIP(hipMalloc(&l->q, sizeof(float) * 3 * B * A));
-  RELA_HIP(hipMalloc(&l->td, sizeof(float) * B));
-  RELA_HIP(hipMalloc(&l->d_ha, sizeof(float) * B * 32));
-  RELA_HIP(hipMalloc(&l->d_h, sizeof(float) * B * 512));
-  RELA_HIP(hipMalloc(&l->d_a3, sizeof(float) * B * kA3));
-  RELA_HIP(hipMalloc(&l->d_a2, sizeof(float) * B * kA2));
-  RELA_HIP(hipMalloc(&l->d_a1, sizeof(float) * B * kA1));
-  RELA_HIP(hipMalloc(&l->part, sizeof(float) * kTrunkPartFloats));
-  RELA_HIP(hipMalloc(&l->cpart, sizeof(float) * kColsumBlocks * (32 + 512 + 64 + 64 + 32)));  // all five jobs
-  RELA_HIP(hipMalloc(&l->s32, sizeof(float) * 32));
-  RELA_HIP(hipMalloc(&l->npart, sizeof(double) * kNormBlocks));
-  RELA_HIP(hipMalloc(&l->norm, sizeof(float) * 2));
-  RELA_HIP(hipMalloc(&l->loss, sizeof(float)));
-  static const bool lanes = !(getenv("RELA_LEARNER_LANES") && atoi(getenv("RELA_LEARNER_LANES")) == 1);
-  if (lanes) {
-    RELA_HIP(hipStreamCreateWithFlags(&l->side, hipStreamNonBlocking));
-    for (hipEvent_t& e : l->ev) RELA_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    RELA_HIP(hipMalloc(&l->part_side, sizeof(float) * kTrunkPartFloats));
-    RELA_HIP(hipMalloc(&l->cpart_side, sizeof(float) * kColsumBlocks * (32 + 512 + 64 + 64 + 32)));
-    RELA_HIP(hipMalloc(&l->frag2, dgfast::kFrag2Bytes));
-    RELA_HIP(hipMalloc(&l->frag3, dgfast::kFrag3Bytes));
+  const int rc = build_learner(l, num_action, max_batch, multi_step, gamma, optimizer, lr, eps, grad_clip, device);
+  if (rc != RELA_OK) {
+    rela_apex_learner_destroy(l);  // the one exit of a failed create: *out stays untouched
+    return rc;
   }
   *out = l;
   return RELA_OK;
 }
 
+// (also the end of a half-built learner: null nets, stream and events are skipped, l->mem holds what was allocated)
 extern "C" void rela_apex_learner_destroy(rela_apex_learner* l) {
   if (!l) return;
   DeviceGuard g(l->device);
   (void)hipDeviceSynchronize();
-  void* ps[] = {l->P,  l->PT,   l->G,    l->S1,   l->S2,   l->w2p, l->w3p,  l->wfcp,  l->ws_on, l->ws_tmp, l->q,
-                l->td, l->d_ha, l->d_h,  l->d_a3, l->d_a2, l->d_a1, l->part,  l->cpart, l->s32,    l->npart,
-                l->norm, l->loss, l->part_side, l->cpart_side, l->frag2, l->frag3};
-  for (void* p : ps) (void)hipFree(p);
+  l->mem.free_all();
   for (hipEvent_t e : l->ev)
     if (e) (void)hipEventDestroy(e);
   if (l->side) (void)hipStreamDestroy(l->side);
@@ -192,32 +165,15 @@ extern "C" int rela_apex_learner_load(rela_apex_learner* l, const rela_ffnet_par
   RELA_CHECK(l && online, RELA_EINVAL, "rela_apex_learner_load: bad arguments");
   hipStream_t s = (hipStream_t)stream_;
   DeviceGuard g(l->device);
-  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const float* const* fo = reinterpret_cast<const float* const*>(online);
-  const float* const* ft = reinterpret_cast<const float* const*>(target ? target : online);
-  const int64_t cnt[12] = {32 * 256, 32, 64 * 512, 64, 64 * 576, 64, (int64_t)512 * 3136, 512, 512, 1,
-                           (int64_t)l->A * 512, l->A};
-  for (int i = 0; i < 12; ++i) {
-    RELA_CHECK(fo[i] && ft[i], RELA_EINVAL, "rela_apex_learner_load: parameter %d is NULL", i);
-    RELA_HIP(hipMemcpyAsync(l->P + l->off[i], fo[i], sizeof(float) * cnt[i], kind, s));
-    RELA_HIP(hipMemcpyAsync(l->PT + l->off[i], ft[i], sizeof(float) * cnt[i], kind, s));
-  }
-  if (!on_device) RELA_HIP(hipStreamSynchronize(s));  // the host buffers may go away
-  const size_t nb = sizeof(float) * (size_t)l->off[12];
-  RELA_HIP(hipMemsetAsync(l->S1, 0, nb, s));
-  RELA_HIP(hipMemsetAsync(l->S2, 0, nb, s));
-  l->adam_t = 0;
-  int rc = repack(l, true, true, s);
-  if (rc != RELA_OK) return rc;
+  if (int rc = l->load("rela_apex_learner_load", online, target, on_device, s)) return rc;
+  if (int rc = repack(l, true, true, s)) return rc;
   l->loaded = true;
   return RELA_OK;
 }
 
 extern "C" int rela_apex_learner_set_value_rescale(rela_apex_learner* l, float eps) {
-  RELA_CHECK(l && eps == eps, RELA_EINVAL, "rela_apex_learner_set_value_rescale: bad arguments");
-  RELA_CHECK(!l->loss_called, RELA_ESTATE, "rela_apex_learner_set_value_rescale: call it before the first loss");
-  l->vr_eps = eps > 0.f ? eps : 0.f;
-  return RELA_OK;
+  RELA_CHECK(l, RELA_EINVAL, "rela_apex_learner_set_value_rescale: bad arguments");
+  return l->set_value_rescale("rela_apex_learner_set_value_rescale", eps);
 }
 
 extern "C" int rela_apex_learner_set_precision(rela_apex_learner* l, int mode) {
@@ -231,30 +187,27 @@ extern "C" int rela_apex_learner_sync_target(rela_apex_learner* l, void* stream_
   RELA_CHECK(l && l->loaded, RELA_ESTATE, "rela_apex_learner_sync_target: parameters were never loaded");
   hipStream_t s = (hipStream_t)stream_;
   DeviceGuard g(l->device);
-  RELA_HIP(hipMemcpyAsync(l->PT, l->P, sizeof(float) * (size_t)l->off[12], hipMemcpyDeviceToDevice, s));  // apex.py:27
+  if (int rc = l->copy_online_to_target(s)) return rc;
   return repack(l, false, true, s);
 }
 
 extern "C" int rela_apex_learner_params(rela_apex_learner* l, rela_ffnet_params* online_out,
                                         rela_ffnet_params* target_out) {
   RELA_CHECK(l, RELA_EINVAL, "rela_apex_learner_params: bad arguments");
-  if (online_out) *online_out = params_at(l, l->P);
-  if (target_out) *target_out = params_at(l, l->PT);
+  if (online_out) l->params_at(l->P, online_out);
+  if (target_out) l->params_at(l->PT, target_out);
   return RELA_OK;
 }
 
 extern "C" int rela_apex_learner_grads(rela_apex_learner* l, rela_ffnet_params* grads_out) {
   RELA_CHECK(l && grads_out, RELA_EINVAL, "rela_apex_learner_grads: bad arguments");
-  *grads_out = params_at(l, l->G);
+  l->params_at(l->G, grads_out);
   return RELA_OK;
 }
 
 extern "C" int rela_apex_learner_flat(rela_apex_learner* l, float** params_dev, float** grads_dev, int64_t* count) {
   RELA_CHECK(l, RELA_EINVAL, "rela_apex_learner_flat: bad arguments");
-  if (params_dev) *params_dev = l->P;
-  if (grads_dev) *grads_dev = l->G;
-  if (count) *count = l->off[12];
-  return RELA_OK;
+  return l->flat(params_dev, grads_dev, count);
 }
 
 extern "C" const float* rela_apex_learner_stats_dev(const rela_apex_learner* l) { return l ? l->norm : nullptr; }
@@ -387,8 +340,8 @@ extern "C" int rela_apex_learner_grad(rela_apex_learner* l, void* stream_) {
 
   const FFNetWs w = ffnet_ws(l->ws_on, l->pend_rows);
   const rela_ffnet_params P = params_at(l, l->P);
-  float* Gm[12];  // gradient tensors in rela_ffnet_params order
-  for (int i = 0; i < 12; ++i) Gm[i] = l->G + l->off[i];
+  float* Gm[kFFNetSegs];  // gradient tensors in rela_ffnet_params order
+  for (int i = 0; i < kFFNetSegs; ++i) Gm[i] = l->G + l->off[i];
 
   ColsumJobs sums;  // the five bias gradients: queued here, one launch pair at the end of trunk_backward
   const bool g3 = rela_ffnet_precision(l->online) == 1 && gemm_bf16x3_on();  // bf16x2: the GEMMs on bf16 MFMA too
@@ -458,22 +411,14 @@ extern "C" int rela_apex_learner_grad(rela_apex_learner* l, void* stream_) {
 // Everything the learners keep across steps (scratch, the permuted weight copies, the side lane) lives for this one call.
 namespace {
 struct TrunkTapScratch {
-  std::vector<void*> bufs;
+  DevBuffers mem;
   hipStream_t side = nullptr;
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   ~TrunkTapScratch() {
-    for (void* p : bufs) (void)hipFree(p);
+    mem.free_all();
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
     if (side) (void)hipStreamDestroy(side);
-  }
-  template <class T>
-  hipError_t alloc(T** p, size_t bytes) {
-    void* v = nullptr;
-    const hipError_t e = hipMalloc(&v, bytes);
-    if (e == hipSuccess) bufs.push_back(v);
-    *p = static_cast<T*>(v);
-    return e;
   }
 };
 }  // namespace
@@ -489,10 +434,10 @@ extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fa
              RELA_EINVAL, "rela_debug_trunk_backward: a pointer is NULL");
   hipStream_t s = (hipStream_t)stream_;
   TrunkTapScratch sc;
-  const size_t cpart_bytes = sizeof(float) * kColsumBlocks * (32 + 512 + 64 + 64 + 32);  // as the learners size it
+  const size_t cpart_floats = (size_t)kColsumBlocks * (32 + 512 + 64 + 64 + 32);  // as the learners size it
   float *w2p = nullptr, *w3p = nullptr;
-  RELA_HIP(sc.alloc(&w2p, sizeof(float) * 64 * 512));
-  RELA_HIP(sc.alloc(&w3p, sizeof(float) * 64 * 576));
+  if (int rc = sc.mem.alloc(&w2p, 64 * 512, false)) return rc;
+  if (int rc = sc.mem.alloc(&w3p, 64 * 576, false)) return rc;
   hipLaunchKernelGGL(permute_weights, dim3(ceil_div(64 * 512, 256)), dim3(256), 0, s, kPermConv2, conv2_w, w2p, 64 * 512);
   hipLaunchKernelGGL(permute_weights, dim3(ceil_div(64 * 576, 256)), dim3(256), 0, s, kPermConv3, conv3_w, w3p, 64 * 576);
   TrunkBwd t{};
@@ -501,19 +446,19 @@ extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fa
   t.g_c1w = g_c1w, t.g_c1b = g_c1b, t.g_c2w = g_c2w, t.g_c2b = g_c2b, t.g_c3w = g_c3w, t.g_c3b = g_c3b;
   t.fast = mode == 1;
   if (fast_wgrad_min_frames > 0) t.fast_wgrad_min_frames = fast_wgrad_min_frames;
-  RELA_HIP(sc.alloc(&t.part, sizeof(float) * kTrunkPartFloats));
-  RELA_HIP(sc.alloc(&t.cpart, cpart_bytes));
+  if (int rc = sc.mem.alloc(&t.part, kTrunkPartFloats, false)) return rc;
+  if (int rc = sc.mem.alloc(&t.cpart, cpart_floats, false)) return rc;
   t.emu = mode == 2;
   if (lanes) {  // as rela_apex_learner_grad fills it; else one lane, as the R2D2 learner (and RELA_LEARNER_LANES=1)
     RELA_HIP(hipStreamCreateWithFlags(&sc.side, hipStreamNonBlocking));
     for (hipEvent_t& e : sc.ev) RELA_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     t.side = sc.side, t.ev_da3 = sc.ev[0], t.ev_da2 = sc.ev[1], t.ev_side = sc.ev[2];
-    RELA_HIP(sc.alloc(&t.part_side, sizeof(float) * kTrunkPartFloats));
-    RELA_HIP(sc.alloc(&t.cpart_side, cpart_bytes));
+    if (int rc = sc.mem.alloc(&t.part_side, kTrunkPartFloats, false)) return rc;
+    if (int rc = sc.mem.alloc(&t.cpart_side, cpart_floats, false)) return rc;
     if (t.fast) {  // the data-gradient weight fragments packed ahead, as repack() does
-      void *frag2 = nullptr, *frag3 = nullptr;
-      RELA_HIP(sc.alloc(&frag2, dgfast::kFrag2Bytes));
-      RELA_HIP(sc.alloc(&frag3, dgfast::kFrag3Bytes));
+      uint8_t *frag2 = nullptr, *frag3 = nullptr;
+      if (int rc = sc.mem.alloc(&frag2, dgfast::kFrag2Bytes, false)) return rc;
+      if (int rc = sc.mem.alloc(&frag3, dgfast::kFrag3Bytes, false)) return rc;
       dgfast::pack_frags(w2p, w3p, frag2, frag3, s);
       t.frag2 = frag2, t.frag3 = frag3;
     }
@@ -532,10 +477,7 @@ extern "C" int rela_apex_learner_apply(rela_apex_learner* l, void* stream_) {
   RELA_CHECK(l && l->loaded, RELA_ESTATE, "rela_apex_learner_apply: parameters were never loaded");
   hipStream_t s = (hipStream_t)stream_;
   DeviceGuard g(l->device);
-  OptimState o;
-  o.optimizer = l->optimizer, o.lr = l->lr, o.eps = l->opt_eps, o.clip = l->clip, o.adam_t = l->adam_t;
-  optimizer_apply(o, l->P, l->G, l->S1, l->S2, l->off[12], l->npart, l->norm, s);
-  l->adam_t = o.adam_t;
+  l->apply(s);
   RELA_LAUNCH_CHECK();
   return repack(l, true, false, s);
 }

@@ -1,6 +1,8 @@
 // learner_common.h -- pieces shared by the two hand-written learner steps (learner.hip: Ape-X /
 // AtariFFNet; learner_r2d2.hip: R2D2 / AtariLSTMNet): the gemm_lds problem descriptions of the conv trunk's
-// backward pass, split-K reduction, column sums, global-norm clipping and the optimisers.
+// backward pass, split-K reduction, column sums, global-norm clipping and the optimisers, and -- host side, at the
+// end -- DevBuffers (the owner of a learner's device buffers) and LearnerCore, the base of rela_apex_learner and
+// rela_r2d2_learner: the flat parameter / gradient / optimiser-state store and what the entry points do with it.
 // Everything sits in an anonymous namespace: each translation unit gets its own copy of the kernels.
 #pragma once
 #include <cmath>
@@ -11,6 +13,7 @@
 #include "ffnet_layout.h"
 #include "gemm_lds.h"
 #include "gemm_bf16x3.h"
+#include "param_layout.h"
 #include "prof.h"
 #include "value_rescale.h"
 #include "dgrad_conv_bf16.h"
@@ -766,6 +769,100 @@ inline void optimizer_apply(OptimState& o, float* P, const float* G, float* S1, 
                        bc1, bc2s, (const float*)norm);
   }
 }
+
+// ---- the device buffers of one owner: every pointer handed out is recorded, free_all releases them -----------------
+struct DevBuffers {
+  std::vector<void*> ptrs;
+  template <class T>
+  int alloc(T** p, size_t count, bool zero) {
+    void* v = nullptr;
+    RELA_HIP(hipMalloc(&v, sizeof(T) * count));
+    ptrs.push_back(v);
+    *p = static_cast<T*>(v);
+    if (zero) RELA_HIP(hipMemset(v, 0, sizeof(T) * count));
+    return RELA_OK;
+  }
+  void free_all() {
+    for (void* p : ptrs) (void)hipFree(p);
+    ptrs.clear();
+  }
+};
+
+// ---- what the two learners share on the host ------------------------------------------------------------------------
+// The flat store: P (online), PT (target), G (gradients), S1 / S2 (optimiser state), each off[nseg] floats with the
+// net's tensors at off[i] (param_layout.h).  The functions are the bodies of the rela_*_learner_* entry points, which
+// check their handle, select the device, pass their own name (`who` leads every message) and re-pack the
+// kernel-layout weight copies afterwards (each learner's own repack).
+struct LearnerCore {
+  int device = 0;
+  int A = 0, Bmax = 0;
+  float gamma_n = 0.f;
+  float vr_eps = 0.f;        // value rescaling of the TD target (set_value_rescale), 0 = off
+  bool loss_called = false;  // ... which is fixed from the first loss on
+  OptimState opt;
+  int nseg = 0;
+  int64_t cnt[kLstmNetSegs] = {0};      // elements per tensor
+  int64_t off[kLstmNetSegs + 1] = {0};  // segment offsets, off[nseg] = total
+  float *P = nullptr, *PT = nullptr, *G = nullptr, *S1 = nullptr, *S2 = nullptr;
+  double* npart = nullptr;
+  float* norm = nullptr;  // [0] grad norm, [1] clip coefficient
+  float* loss = nullptr;
+  bool loaded = false;
+  DevBuffers mem;  // every device buffer of the learner
+
+  // counts: ffnet_param_counts / lstmnet_param_counts (param_layout.h) with their kFFNetSegs / kLstmNetSegs
+  int alloc_flat(int nseg_, void (*counts)(int, int64_t*), int num_action) {
+    nseg = nseg_;
+    counts(num_action, cnt);
+    flat_offsets(cnt, nseg, off);
+    for (float** p : {&P, &PT, &G, &S1, &S2})
+      if (int rc = mem.alloc(p, (size_t)off[nseg], true)) return rc;
+    if (int rc = mem.alloc(&npart, kNormBlocks, false)) return rc;
+    if (int rc = mem.alloc(&norm, 2, true)) return rc;  // (zeroed: stats before the first apply reads zeros)
+    return mem.alloc(&loss, 1, true);
+  }
+  // online / target: the net's params struct, nseg pointers (target may be null: the online tensors twice)
+  int load(const char* who, const void* online, const void* target, int on_device, hipStream_t s) {
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const float* const* fo = static_cast<const float* const*>(online);
+    const float* const* ft = static_cast<const float* const*>(target ? target : online);
+    for (int i = 0; i < nseg; ++i) {
+      RELA_CHECK(fo[i] && ft[i], RELA_EINVAL, "%s: parameter %d is NULL", who, i);
+      RELA_HIP(hipMemcpyAsync(P + off[i], fo[i], sizeof(float) * cnt[i], kind, s));
+      RELA_HIP(hipMemcpyAsync(PT + off[i], ft[i], sizeof(float) * cnt[i], kind, s));
+    }
+    if (!on_device) RELA_HIP(hipStreamSynchronize(s));  // the host buffers may go away
+    const size_t nb = sizeof(float) * (size_t)off[nseg];
+    RELA_HIP(hipMemsetAsync(S1, 0, nb, s));
+    RELA_HIP(hipMemsetAsync(S2, 0, nb, s));
+    opt.adam_t = 0;
+    return RELA_OK;
+  }
+  int copy_online_to_target(hipStream_t s) {  // apex.py:27
+    RELA_HIP(hipMemcpyAsync(PT, P, sizeof(float) * (size_t)off[nseg], hipMemcpyDeviceToDevice, s));
+    return RELA_OK;
+  }
+  // params_out: the net's params struct; its nseg pointers into the flat buffer at `base`
+  void params_at(const float* base, void* params_out) const {
+    const float** f = static_cast<const float**>(params_out);
+    for (int i = 0; i < nseg; ++i) f[i] = base + off[i];
+  }
+  int flat(float** params_dev, float** grads_dev, int64_t* count) const {
+    if (params_dev) *params_dev = P;
+    if (grads_dev) *grads_dev = G;
+    if (count) *count = off[nseg];
+    return RELA_OK;
+  }
+  int set_value_rescale(const char* who, float eps) {
+    RELA_CHECK(eps == eps, RELA_EINVAL, "%s: bad arguments", who);
+    RELA_CHECK(!loss_called, RELA_ESTATE, "%s: call it before the first loss", who);
+    vr_eps = eps > 0.f ? eps : 0.f;
+    return RELA_OK;
+  }
+  void apply(hipStream_t s, const unsigned* abort_word = nullptr) {
+    optimizer_apply(opt, P, G, S1, S2, off[nseg], npart, norm, s, abort_word);
+  }
+};
 
 }  // namespace
 }  // namespace rela_amd

@@ -599,23 +599,17 @@ __global__ void seq_head_grad(const float* __restrict__ dqa, const int64_t* __re
 }  // namespace
 }  // namespace rela_amd
 
-// flat parameter layout: rela_lstmnet_params order, every segment padded to 4 floats
-struct rela_r2d2_learner {
-  int device = 0;
-  int A = 0, Bmax = 0, seq = 0, burn = 0, n = 0, T = 0;
-  float gamma_n = 0.f, eta = 0.f, one_minus_eta = 0.f;
-  float vr_eps = 0.f;        // value rescaling of the TD target (rela_r2d2_learner_set_value_rescale), 0 = off
-  bool loss_called = false;  // ... which is fixed from the first rela_r2d2_learner_loss on
-  OptimState opt;
-  int64_t off[15] = {0};  // segment offsets, off[14] = total
-  float *P = nullptr, *PT = nullptr, *G = nullptr, *S1 = nullptr, *S2 = nullptr;
+// flat parameter layout: rela_lstmnet_params order (LearnerCore, learner_common.h)
+static_assert(sizeof(rela_lstmnet_params) == kLstmNetSegs * sizeof(float*), "rela_lstmnet_params is kLstmNetSegs pointers");
+struct rela_r2d2_learner : LearnerCore {
+  int seq = 0, burn = 0, n = 0, T = 0;
+  float eta = 0.f, one_minus_eta = 0.f;
   rela_lstmnet *online = nullptr, *target = nullptr;
   float *w2p = nullptr, *w3p = nullptr;                               // conv dgrad operand copies (online)
   float *wihT[2] = {nullptr, nullptr}, *whhT[2] = {nullptr, nullptr}, *bsum[2] = {nullptr, nullptr};  // [online, target]
   float* wihp = nullptr;                                              // online W_ih in k order (dgrad)
   float *a1 = nullptr, *a2 = nullptr, *a3 = nullptr;                  // trunk activations of T*B frames
   float* gxs[2] = {nullptr, nullptr};  // per net [T*B][2048]: GX; the online one -> activated gates -> dgates
-  float*& gx = gxs[0];
   float *Hs[2] = {nullptr, nullptr}, *Cs[2] = {nullptr, nullptr};     // [(T+1)*B][512] per net
   float* rec_part = nullptr;                                          // split-K partials of the recurrent GEMMs
   unsigned* rec_bar = nullptr;                                        // [0] timeout word, [4 ..] per-step arrival counters
@@ -632,33 +626,23 @@ struct rela_r2d2_learner {
   uint64_t wver[2] = {1, 1}, rec_ver[2] = {0, 0};  // weight version (repack) / version the records were made from
   // f32x3 (r5): the trunks on split3 records and the x part of the gates as a three-part GEMM (csrc/gemm_s3.h)
   uint8_t* s3rec = nullptr;          // rowsAll x (a2 + a3 records)
-  void* wx3[2] = {nullptr, nullptr};  // W_ih of either net as three-part fragments (gate columns as stored)
+  uint8_t* wx3[2] = {nullptr, nullptr};  // W_ih of either net as three-part fragments (gate columns as stored)
   uint64_t x3_ver[2] = {0, 0};
   float *ha = nullptr, *q_on = nullptr, *q_tg = nullptr;              // heads of the training rows
   float *qmin = nullptr, *qa_on = nullptr, *qa_tg = nullptr, *dqa = nullptr, *d_ha = nullptr, *d_o = nullptr;
   float *dc_rec = nullptr;
   float *d_a3 = nullptr, *d_a2 = nullptr, *d_a1 = nullptr, *part = nullptr, *cpart = nullptr,
         *s32 = nullptr;
-  double* npart = nullptr;
-  float *norm = nullptr, *loss = nullptr, *loss_seq = nullptr;
-  bool loaded = false;
+  float* loss_seq = nullptr;
   // batch of the last rela_r2d2_learner_loss, until rela_r2d2_learner_grad consumes it
   int pend_B = 0;
   const uint8_t* pend_obs = nullptr;
 };
 
 namespace {
-const int64_t* seg_counts(int A, int64_t cnt[14]) {
-  const int64_t c[14] = {32 * 256, 32, 64 * 512, 64, 64 * 576, 64, (int64_t)kGates * kFeat, (int64_t)kGates * kHid,
-                         kGates, kGates, 512, 1, (int64_t)A * 512, A};
-  for (int i = 0; i < 14; ++i) cnt[i] = c[i];
-  return cnt;
-}
-
-rela_lstmnet_params lparams_at(const rela_r2d2_learner* l, float* base) {
+rela_lstmnet_params lparams_at(const rela_r2d2_learner* l, const float* base) {
   rela_lstmnet_params p;
-  const float** f = reinterpret_cast<const float**>(&p);
-  for (int i = 0; i < 14; ++i) f[i] = base + l->off[i];
+  l->params_at(base, &p);
   return p;
 }
 
@@ -844,21 +828,12 @@ int forward_both(rela_r2d2_learner* l, int Bn, const uint8_t* obs, const float* 
 }
 }  // namespace
 
-extern "C" int rela_r2d2_learner_create(rela_r2d2_learner** out, int num_action, int max_batch, int multi_step,
-                                        float gamma, int seq_len, int burn_in, double eta, int optimizer, float lr,
-                                        float eps, float grad_clip, int device) {
-  RELA_CHECK(out && num_action >= 1 && num_action <= 31 && max_batch >= 1 && max_batch <= 1024 && multi_step >= 1 &&
-                 seq_len >= 1 && burn_in >= 0 && (optimizer == 0 || optimizer == 1),
-             RELA_EINVAL, "rela_r2d2_learner_create: bad arguments (A=%d batch=%d n=%d seq=%d burn=%d optimizer=%d)",
-             num_action, max_batch, multi_step, seq_len, burn_in, optimizer);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_last_error("rela_r2d2_learner_create: HIP device %d not available (%d visible); there is no CPU path", device,
-                   ndev);
-    return RELA_ENODEV;
-  }
-  DeviceGuard g(device);
-  auto* l = new rela_r2d2_learner();
+namespace {
+// everything rela_r2d2_learner_create allocates; a failure leaves a half-built learner for rela_r2d2_learner_destroy.
+// rowsTr: the training frames of a full batch, (seq_len + multi_step) * max_batch, which create has checked
+int build_learner(rela_r2d2_learner* l, int num_action, int max_batch, int multi_step, float gamma, int seq_len,
+                  int burn_in, double eta, int optimizer, float lr, float eps, float grad_clip, int device,
+                  size_t rowsTr) {
   l->device = device;
   l->A = num_action, l->Bmax = max_batch, l->seq = seq_len, l->burn = burn_in, l->n = multi_step;
   l->T = burn_in + seq_len + multi_step;
@@ -866,83 +841,38 @@ extern "C" int rela_r2d2_learner_create(rela_r2d2_learner** out, int num_action,
   l->eta = (float)eta;
   l->one_minus_eta = (float)(1.0 - eta);  // TorchScript folds (1.0 - self.eta) in double, r2d2.py:119
   l->opt.optimizer = optimizer, l->opt.lr = lr, l->opt.eps = eps, l->opt.clip = grad_clip;
-  int64_t cnt[14];
-  seg_counts(num_action, cnt);
-  for (int i = 0; i < 14; ++i) l->off[i + 1] = l->off[i] + (cnt[i] + 3) / 4 * 4;
-  const size_t nb = sizeof(float) * (size_t)l->off[14];
-  const size_t B = (size_t)max_batch, A = (size_t)num_action, T = (size_t)l->T, Tt = T - burn_in;
-  const size_t rowsAll = T * B, rowsTr = Tt * B;
-  if (rowsTr > (size_t)kTrunkMaxFrames) {
-    delete l;
-    set_last_error("rela_r2d2_learner_create: %zu training frames per step, the trunk's backward pass takes %d", rowsTr,
-                   kTrunkMaxFrames);
-    return RELA_EINVAL;
-  }
-  auto alloc = [&](float** p, size_t floats, bool zero) -> int {
-    RELA_HIP(hipMalloc(p, sizeof(float) * floats));
-    if (zero) RELA_HIP(hipMemset(*p, 0, sizeof(float) * floats));
-    return RELA_OK;
-  };
-#define R2_ALLOC(ptr, floats, zero)               \
-  do {                                            \
-    int _rc = alloc(&(ptr), (floats), (zero));    \
-    if (_rc != RELA_OK) return _rc;               \
-  } while (0)
-  R2_ALLOC(l->P, l->off[14], true);
-  R2_ALLOC(l->PT, l->off[14], true);
-  R2_ALLOC(l->G, l->off[14], true);
-  R2_ALLOC(l->S1, l->off[14], true);
-  R2_ALLOC(l->S2, l->off[14], true);
-  (void)nb;
-  int rc = rela_lstmnet_create(&l->online, num_action, device);
-  if (rc != RELA_OK) return rc;
-  rc = rela_lstmnet_create(&l->target, num_action, device);
-  if (rc != RELA_OK) return rc;
-  R2_ALLOC(l->w2p, 64 * 512, false);
-  R2_ALLOC(l->w3p, 64 * 576, false);
+  if (int rc = l->alloc_flat(kLstmNetSegs, lstmnet_param_counts, num_action)) return rc;
+  const size_t B = (size_t)max_batch, A = (size_t)num_action, T = (size_t)l->T;
+  const size_t rowsAll = T * B;
+  if (int rc = rela_lstmnet_create(&l->online, num_action, device)) return rc;
+  if (int rc = rela_lstmnet_create(&l->target, num_action, device)) return rc;
+  DevBuffers& m = l->mem;
+  if (int rc = m.alloc(&l->w2p, 64 * 512, false)) return rc;
+  if (int rc = m.alloc(&l->w3p, 64 * 576, false)) return rc;
   for (int w = 0; w < 2; ++w) {
-    R2_ALLOC(l->wihT[w], (size_t)kGates * kFeat, false);
-    R2_ALLOC(l->whhT[w], (size_t)kGates * kHid, false);
-    R2_ALLOC(l->bsum[w], kGates, false);
-    R2_ALLOC(l->Hs[w], (T + 1) * B * kHid, true);
-    R2_ALLOC(l->Cs[w], (T + 1) * B * kHid, true);
+    if (int rc = m.alloc(&l->wihT[w], (size_t)kGates * kFeat, false)) return rc;
+    if (int rc = m.alloc(&l->whhT[w], (size_t)kGates * kHid, false)) return rc;
+    if (int rc = m.alloc(&l->bsum[w], kGates, false)) return rc;
+    if (int rc = m.alloc(&l->Hs[w], (T + 1) * B * kHid, true)) return rc;
+    if (int rc = m.alloc(&l->Cs[w], (T + 1) * B * kHid, true)) return rc;
+    // bf16x2: rec64 records, 4 bytes per element; f32x3: W_ih as three-part fragments
+    if (int rc = m.alloc(&l->wrec[w], (size_t)4 * kGates * kFeat, false)) return rc;
+    if (int rc = m.alloc(&l->wx3[w], (size_t)gate_x3_packed_bytes(), false)) return rc;
+    if (int rc = m.alloc(&l->gxs[w], rowsAll * kGates, false)) return rc;
   }
-  R2_ALLOC(l->wihp, (size_t)kGates * kFeat, false);
-  {
-    const size_t chunks = (rowsAll + 63) / 64;
-    float* tmp = nullptr;
-    for (int w = 0; w < 2; ++w) {
-      R2_ALLOC(tmp, (size_t)kGates * kFeat, false);
-      l->wrec[w] = reinterpret_cast<uint8_t*>(tmp);
-    }
-    R2_ALLOC(tmp, (size_t)kGates * kFeat, false);
-    l->wTrec = reinterpret_cast<uint8_t*>(tmp);
-    R2_ALLOC(tmp, rowsAll * kFeat, false);
-    l->arec = reinterpret_cast<uint8_t*>(tmp);
-    R2_ALLOC(tmp, (size_t)(kGates + kFeat) * chunks * 64, false);  // [2048][chunks] followed by [3136][chunks]
-    l->trec = reinterpret_cast<uint8_t*>(tmp);
-  }
-  {
-    float* tmp = nullptr;
-    R2_ALLOC(tmp, (rowsAll * (size_t)(kRec2Bytes + kRec3Bytes) + 3) / 4, false);
-    l->s3rec = reinterpret_cast<uint8_t*>(tmp);
-    for (int w = 0; w < 2; ++w) {
-      R2_ALLOC(tmp, ((size_t)gate_x3_packed_bytes() + 3) / 4, false);
-      l->wx3[w] = tmp;
-    }
-  }
-  R2_ALLOC(l->a1, rowsAll * kA1, false);
-  R2_ALLOC(l->a2, rowsAll * kA2, false);
-  R2_ALLOC(l->a3, rowsAll * kA3, false);
-  R2_ALLOC(l->gxs[0], rowsAll * kGates, false);
-  R2_ALLOC(l->gxs[1], rowsAll * kGates, false);
-  {
-    const size_t f = (size_t)kRecSplitF * B * kGates, b = (size_t)kRecSplitB * B * kHid;
-    R2_ALLOC(l->rec_part, f > b ? f : b, false);
-  }
-  RELA_HIP(hipMalloc(&l->rec_bar, sizeof(unsigned) * (size_t)(8 + 2 * ((T + 3) / 4 * 4))));
-  RELA_HIP(hipMemset(l->rec_bar, 0, sizeof(unsigned) * (size_t)(8 + 2 * ((T + 3) / 4 * 4))));
-  RELA_HIP(hipMalloc(&l->rec_chain_bar, sizeof(unsigned) * (size_t)(8 * ((T + 3) / 4 * 4))));
+  if (int rc = m.alloc(&l->wihp, (size_t)kGates * kFeat, false)) return rc;
+  if (int rc = m.alloc(&l->wTrec, (size_t)4 * kGates * kFeat, false)) return rc;
+  if (int rc = m.alloc(&l->arec, 4 * rowsAll * kFeat, false)) return rc;
+  const size_t chunks = (rowsAll + 63) / 64;  // trec: [2048][chunks] followed by [3136][chunks] records of 64 rows
+  if (int rc = m.alloc(&l->trec, (size_t)(kGates + kFeat) * chunks * 64 * 4, false)) return rc;
+  if (int rc = m.alloc(&l->s3rec, rowsAll * (size_t)(kRec2Bytes + kRec3Bytes), false)) return rc;
+  if (int rc = m.alloc(&l->a1, rowsAll * kA1, false)) return rc;
+  if (int rc = m.alloc(&l->a2, rowsAll * kA2, false)) return rc;
+  if (int rc = m.alloc(&l->a3, rowsAll * kA3, false)) return rc;
+  if (int rc = m.alloc(&l->rec_part, std::max((size_t)kRecSplitF * B * kGates, (size_t)kRecSplitB * B * kHid), false)) return rc;
+  const size_t Tpad = (T + 3) / 4 * 4;
+  if (int rc = m.alloc(&l->rec_bar, 8 + 2 * Tpad, true)) return rc;
+  if (int rc = m.alloc(&l->rec_chain_bar, 8 * Tpad, false)) return rc;
   l->rec_persist = !(getenv("RELA_R2D2_REC") && strcmp(getenv("RELA_R2D2_REC"), "steps") == 0);
   if (l->rec_persist) {
     // The persistent kernels spin on a grid barrier: every block must be resident at once.  A plain launch checks
@@ -964,52 +894,56 @@ extern "C" int rela_r2d2_learner_create(rela_r2d2_learner** out, int num_action,
       l->rec_chains_fit = false;
     }
   }
-  R2_ALLOC(l->ha, rowsTr * 32, false);
-  R2_ALLOC(l->q_on, rowsTr * A, false);
-  R2_ALLOC(l->q_tg, rowsTr * A, false);
-  R2_ALLOC(l->qmin, 4, false);
-  R2_ALLOC(l->qa_on, rowsTr, false);
-  R2_ALLOC(l->qa_tg, rowsTr, false);
-  R2_ALLOC(l->dqa, rowsTr, false);
-  R2_ALLOC(l->d_ha, rowsTr * 32, false);
-  R2_ALLOC(l->d_o, rowsTr * kHid, false);
-  R2_ALLOC(l->dc_rec, B * kHid, false);
-  R2_ALLOC(l->d_a3, rowsTr * kA3, false);
-  R2_ALLOC(l->d_a2, rowsTr * kA2, false);
-  R2_ALLOC(l->d_a1, rowsTr * kA1, false);
-  R2_ALLOC(l->part, kTrunkPartFloats, false);
-  R2_ALLOC(l->cpart, (size_t)kColsumBlocks * kGates, false);
-  R2_ALLOC(l->s32, 32, false);
-  R2_ALLOC(l->norm, 2, true);
-  R2_ALLOC(l->loss, 1, true);
-  R2_ALLOC(l->loss_seq, B, true);
-#undef R2_ALLOC
-  RELA_HIP(hipMalloc(&l->npart, sizeof(double) * kNormBlocks));
+  if (int rc = m.alloc(&l->ha, rowsTr * 32, false)) return rc;
+  if (int rc = m.alloc(&l->q_on, rowsTr * A, false)) return rc;
+  if (int rc = m.alloc(&l->q_tg, rowsTr * A, false)) return rc;
+  if (int rc = m.alloc(&l->qmin, 4, false)) return rc;
+  if (int rc = m.alloc(&l->qa_on, rowsTr, false)) return rc;
+  if (int rc = m.alloc(&l->qa_tg, rowsTr, false)) return rc;
+  if (int rc = m.alloc(&l->dqa, rowsTr, false)) return rc;
+  if (int rc = m.alloc(&l->d_ha, rowsTr * 32, false)) return rc;
+  if (int rc = m.alloc(&l->d_o, rowsTr * kHid, false)) return rc;
+  if (int rc = m.alloc(&l->dc_rec, B * kHid, false)) return rc;
+  if (int rc = m.alloc(&l->d_a3, rowsTr * kA3, false)) return rc;
+  if (int rc = m.alloc(&l->d_a2, rowsTr * kA2, false)) return rc;
+  if (int rc = m.alloc(&l->d_a1, rowsTr * kA1, false)) return rc;
+  if (int rc = m.alloc(&l->part, kTrunkPartFloats, false)) return rc;
+  if (int rc = m.alloc(&l->cpart, (size_t)kColsumBlocks * kGates, false)) return rc;
+  if (int rc = m.alloc(&l->s32, 32, false)) return rc;
+  return m.alloc(&l->loss_seq, B, true);
+}
+}  // namespace
+
+extern "C" int rela_r2d2_learner_create(rela_r2d2_learner** out, int num_action, int max_batch, int multi_step,
+                                        float gamma, int seq_len, int burn_in, double eta, int optimizer, float lr,
+                                        float eps, float grad_clip, int device) {
+  RELA_CHECK(out && num_action >= 1 && num_action <= 31 && max_batch >= 1 && max_batch <= 1024 && multi_step >= 1 &&
+                 seq_len >= 1 && burn_in >= 0 && (optimizer == 0 || optimizer == 1),
+             RELA_EINVAL, "rela_r2d2_learner_create: bad arguments (A=%d batch=%d n=%d seq=%d burn=%d optimizer=%d)",
+             num_action, max_batch, multi_step, seq_len, burn_in, optimizer);
+  if (int rc = check_device(device, "rela_r2d2_learner_create")) return rc;
+  const size_t rowsTr = ((size_t)seq_len + multi_step) * max_batch;
+  RELA_CHECK(rowsTr <= (size_t)kTrunkMaxFrames, RELA_EINVAL,
+             "rela_r2d2_learner_create: %zu training frames per step, the trunk's backward pass takes %d", rowsTr,
+             kTrunkMaxFrames);
+  DeviceGuard g(device);
+  auto* l = new rela_r2d2_learner();
+  const int rc = build_learner(l, num_action, max_batch, multi_step, gamma, seq_len, burn_in, eta, optimizer, lr, eps,
+                               grad_clip, device, rowsTr);
+  if (rc != RELA_OK) {
+    rela_r2d2_learner_destroy(l);  // the one exit of a failed create: *out stays untouched
+    return rc;
+  }
   *out = l;
   return RELA_OK;
 }
 
+// (also the end of a half-built learner: null nets are skipped, l->mem holds what was allocated)
 extern "C" void rela_r2d2_learner_destroy(rela_r2d2_learner* l) {
   if (!l) return;
   DeviceGuard g(l->device);
   (void)hipDeviceSynchronize();
-  void* ps[] = {l->P,      l->PT,     l->G,       l->S1,      l->S2,      l->w2p,     l->w3p,   l->wihT[0], l->wihT[1],
-                l->whhT[0], l->whhT[1], l->bsum[0], l->bsum[1], l->Hs[0],   l->Hs[1],   l->Cs[0], l->Cs[1],   l->wihp,
-                l->a1,    l->a2,      l->a3,      l->gx,      l->rec_part, l->ha,   l->q_on,    l->q_tg,
-                l->qmin,   l->qa_on,  l->qa_tg,   l->dqa,     l->d_ha,    l->d_o,     l->dc_rec, l->d_a3,   l->d_a2,
-                l->d_a1,   l->part,    l->cpart,   l->s32,     l->npart,   l->norm,  l->loss,    l->loss_seq};
-  for (void* p : ps) (void)hipFree(p);
-  (void)hipFree(l->rec_bar);
-  (void)hipFree(l->rec_chain_bar);
-  (void)hipFree(l->gxs[1]);
-  (void)hipFree(l->wrec[0]);
-  (void)hipFree(l->wrec[1]);
-  (void)hipFree(l->wTrec);
-  (void)hipFree(l->arec);
-  (void)hipFree(l->s3rec);
-  (void)hipFree(l->wx3[0]);
-  (void)hipFree(l->wx3[1]);
-  (void)hipFree(l->trec);
+  l->mem.free_all();
   rela_lstmnet_destroy(l->online);
   rela_lstmnet_destroy(l->target);
   delete l;
@@ -1020,23 +954,8 @@ extern "C" int rela_r2d2_learner_load(rela_r2d2_learner* l, const rela_lstmnet_p
   RELA_CHECK(l && online, RELA_EINVAL, "rela_r2d2_learner_load: bad arguments");
   hipStream_t s = (hipStream_t)stream_;
   DeviceGuard g(l->device);
-  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  const float* const* fo = reinterpret_cast<const float* const*>(online);
-  const float* const* ft = reinterpret_cast<const float* const*>(target ? target : online);
-  int64_t cnt[14];
-  seg_counts(l->A, cnt);
-  for (int i = 0; i < 14; ++i) {
-    RELA_CHECK(fo[i] && ft[i], RELA_EINVAL, "rela_r2d2_learner_load: parameter %d is NULL", i);
-    RELA_HIP(hipMemcpyAsync(l->P + l->off[i], fo[i], sizeof(float) * cnt[i], kind, s));
-    RELA_HIP(hipMemcpyAsync(l->PT + l->off[i], ft[i], sizeof(float) * cnt[i], kind, s));
-  }
-  if (!on_device) RELA_HIP(hipStreamSynchronize(s));  // the host buffers may go away
-  const size_t nb = sizeof(float) * (size_t)l->off[14];
-  RELA_HIP(hipMemsetAsync(l->S1, 0, nb, s));
-  RELA_HIP(hipMemsetAsync(l->S2, 0, nb, s));
-  l->opt.adam_t = 0;
-  int rc = repack_r2d2(l, true, true, s);
-  if (rc != RELA_OK) return rc;
+  if (int rc = l->load("rela_r2d2_learner_load", online, target, on_device, s)) return rc;
+  if (int rc = repack_r2d2(l, true, true, s)) return rc;
   l->loaded = true;
   return RELA_OK;
 }
@@ -1045,39 +964,34 @@ extern "C" int rela_r2d2_learner_sync_target(rela_r2d2_learner* l, void* stream_
   RELA_CHECK(l && l->loaded, RELA_ESTATE, "rela_r2d2_learner_sync_target: parameters were never loaded");
   hipStream_t s = (hipStream_t)stream_;
   DeviceGuard g(l->device);
-  RELA_HIP(hipMemcpyAsync(l->PT, l->P, sizeof(float) * (size_t)l->off[14], hipMemcpyDeviceToDevice, s));
+  if (int rc = l->copy_online_to_target(s)) return rc;
   return repack_r2d2(l, false, true, s);
 }
 
 extern "C" int rela_r2d2_learner_params(rela_r2d2_learner* l, rela_lstmnet_params* online_out,
                                         rela_lstmnet_params* target_out) {
   RELA_CHECK(l, RELA_EINVAL, "rela_r2d2_learner_params: bad arguments");
-  if (online_out) *online_out = lparams_at(l, l->P);
-  if (target_out) *target_out = lparams_at(l, l->PT);
+  if (online_out) l->params_at(l->P, online_out);
+  if (target_out) l->params_at(l->PT, target_out);
   return RELA_OK;
 }
 
 extern "C" int rela_r2d2_learner_grads(rela_r2d2_learner* l, rela_lstmnet_params* grads_out) {
   RELA_CHECK(l && grads_out, RELA_EINVAL, "rela_r2d2_learner_grads: bad arguments");
-  *grads_out = lparams_at(l, l->G);
+  l->params_at(l->G, grads_out);
   return RELA_OK;
 }
 
 extern "C" int rela_r2d2_learner_flat(rela_r2d2_learner* l, float** params_dev, float** grads_dev, int64_t* count) {
   RELA_CHECK(l, RELA_EINVAL, "rela_r2d2_learner_flat: bad arguments");
-  if (params_dev) *params_dev = l->P;
-  if (grads_dev) *grads_dev = l->G;
-  if (count) *count = l->off[14];
-  return RELA_OK;
+  return l->flat(params_dev, grads_dev, count);
 }
 
 extern "C" const float* rela_r2d2_learner_stats_dev(const rela_r2d2_learner* l) { return l ? l->norm : nullptr; }
 
 extern "C" int rela_r2d2_learner_set_value_rescale(rela_r2d2_learner* l, float eps) {
-  RELA_CHECK(l && eps == eps, RELA_EINVAL, "rela_r2d2_learner_set_value_rescale: bad arguments");
-  RELA_CHECK(!l->loss_called, RELA_ESTATE, "rela_r2d2_learner_set_value_rescale: call it before the first loss");
-  l->vr_eps = eps > 0.f ? eps : 0.f;
-  return RELA_OK;
+  RELA_CHECK(l, RELA_EINVAL, "rela_r2d2_learner_set_value_rescale: bad arguments");
+  return l->set_value_rescale("rela_r2d2_learner_set_value_rescale", eps);
 }
 
 extern "C" int rela_r2d2_learner_set_precision(rela_r2d2_learner* l, int mode) {
@@ -1180,8 +1094,8 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
   l->pend_B = 0;
 
   const rela_lstmnet_params P = lparams_at(l, l->P);
-  float* Gm[14];  // gradient tensors in rela_lstmnet_params order
-  for (int i = 0; i < 14; ++i) Gm[i] = l->G + l->off[i];
+  float* Gm[kLstmNetSegs];  // gradient tensors in rela_lstmnet_params order
+  for (int i = 0; i < kLstmNetSegs; ++i) Gm[i] = l->G + l->off[i];
   const size_t blk = (size_t)Bn * kHid;
   float *H = l->Hs[0], *Cc = l->Cs[0];
   const float* o_tr = H + (size_t)(burn + 1) * blk;  // LSTM outputs of the training steps
@@ -1212,7 +1126,7 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
   // BPTT over the training steps, newest first; the activated gates in gx become the gate gradients in place
   RELA_HIP(hipMemsetAsync(l->dc_rec, 0, blk * sizeof(float), s));
   const int cell_grid = ceil_div((int64_t)Bn * kHid, 256);
-  float* ga_tr = l->gx + tr0 * kGates;
+  float* ga_tr = l->gxs[0] + tr0 * kGates;
   if (l->rec_persist && l->rec_chains_fit && Bn <= 128 && Tt <= l->T) {
     const int Tpad_c = (l->T + 3) / 4 * 4;
     RELA_HIP(hipMemsetAsync(l->rec_chain_bar, 0, sizeof(unsigned) * (size_t)(8 * Tpad_c), s));
@@ -1312,7 +1226,7 @@ extern "C" int rela_r2d2_learner_apply(rela_r2d2_learner* l, void* stream_) {
   DeviceGuard g(l->device);
   // (a grid-barrier timeout of this step's persistent kernels leaves stale gradients: the update is skipped on the
   // device, rela_r2d2_learner_check reports it and switches to the per-step launches)
-  optimizer_apply(l->opt, l->P, l->G, l->S1, l->S2, l->off[14], l->npart, l->norm, s, l->rec_bar);
+  l->apply(s, l->rec_bar);
   RELA_LAUNCH_CHECK();
   return repack_r2d2(l, true, false, s);
 }

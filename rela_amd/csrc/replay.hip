@@ -650,12 +650,7 @@ extern "C" int rela_abi_version(void) { return 1; }
 extern "C" int rela_replay_create(rela_replay** out, int capacity, int seed, float alpha, float beta,
                                   int prefetch, int device) {
   RELA_CHECK(out && capacity > 0, RELA_EINVAL, "rela_replay_create: bad arguments");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_last_error("rela_replay_create: HIP device %d not available (%d visible); there is no CPU path", device,
-                   ndev);
-    return RELA_ENODEV;
-  }
+  if (int rc = check_device(device, "rela_replay_create")) return rc;
   DeviceGuard g(device);
   auto* r = new rela_replay();
   r->device = device;
@@ -1692,11 +1687,7 @@ extern "C" int rela_replay_export_chunks(rela_replay* r, rela_replay_chunk_desc*
 
 static int import_partition(rela_replay_remote** out, const rela_replay_ipc_desc* desc, const rela_replay_chunk_desc* chunks,
                             const int* fds, int nfds, int device, const char* who) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-    set_last_error("%s: HIP device %d not available (%d visible); there is no CPU path", who, device, ndev);
-    return RELA_ENODEV;
-  }
+  if (int rc = check_device(device, who)) return rc;
   DeviceGuard g(device);
   auto* rr = new rela_replay_remote();
   rr->device = device;

@@ -61,7 +61,136 @@ def global_is_weights(raw_w, partition_sum, partition_size, beta, group=None):
     return w / top
 
 
-class HipApexLearner:
+class _HipLearner:
+    """What HipApexLearner and HipR2D2Learner share: the rela_<algo>_learner_* entry points that differ only in their
+    prefix and in the net's params struct.  Subclasses set _PREFIX, _PARAMS (the struct's name in _capi), _NET_LOAD
+    (the actor-side net's load), KEYS (state_dict order) and SHAPES(A)."""
+
+    def _create(self, device, num_action, max_batch, *args):
+        """<prefix>create(&h, num_action, max_batch, *args, device index) and the output buffers of a step."""
+        import ctypes as C
+
+        from . import _capi as capi  # (here, not at the module's top: importing _capi loads the library)
+        from .engine import dev_view
+
+        self._C, self._capi, self._dev_view = C, capi, dev_view
+        self._struct_cls = getattr(capi, self._PARAMS)
+        self._fields = tuple(field for field, _ in self._struct_cls._fields_)
+        self.device = torch.device(device)
+        self.num_action, self.max_batch = num_action, max_batch
+        h = C.c_void_p()
+        name = self._PREFIX + "create"
+        capi.check(getattr(capi.lib, name)(C.byref(h), num_action, max_batch, *args, self.device.index or 0), name)
+        self.h = h
+        self._prio = torch.empty(max_batch, dtype=torch.float32, device=self.device)
+        self._loss = torch.empty(1, dtype=torch.float32, device=self.device)
+
+    def _call(self, name, *args):
+        name = self._PREFIX + name
+        self._capi.check(getattr(self._capi.lib, name)(self.h, *args), name)
+
+    def _stream(self):
+        return self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _view(self, ptr, shape):
+        return self._dev_view(ptr, shape, torch.float32, self.device)
+
+    def _params(self, sd, keep):
+        p = self._struct_cls()
+        for field, key in zip(self._fields, self.KEYS):
+            t = sd[key].detach().to(self.device, torch.float32).contiguous()
+            keep.append(t)
+            setattr(p, field, t.data_ptr())
+        return p
+
+    def _struct(self, which):
+        """The params struct of pointers into the flat buffer of "online" | "target" | "grads"."""
+        C = self._C
+        p = self._struct_cls()
+        if which == "grads":
+            self._call("grads", C.byref(p))
+        elif which == "online":
+            self._call("params", C.byref(p), None)
+        else:
+            self._call("params", None, C.byref(p))
+        return p
+
+    def set_value_rescale(self, eps):
+        """eps of the invertible value rescaling of the TD target (csrc/value_rescale.h); <= 0: off.  Before the first
+        loss only."""
+        self._call("set_value_rescale", float(eps))
+
+    def load_state_dicts(self, online_sd, target_sd=None):
+        C = self._C
+        keep = []
+        po = self._params(online_sd, keep)
+        pt = self._params(target_sd, keep) if target_sd is not None else None
+        self._call("load", C.byref(po), C.byref(pt) if pt is not None else None, 1, self._stream())
+        torch.cuda.current_stream(self.device).synchronize()  # sources may be temporaries
+
+    def sync_target_with_online(self):
+        self._call("sync_target", self._stream())
+
+    def state_dict(self, which="online"):
+        """Zero-copy views of the flat parameter buffer as a state_dict ("online" | "target" | "grads")."""
+        p = self._struct(which)
+        return {key: self._view(getattr(p, field), shape)
+                for field, key, shape in zip(self._fields, self.KEYS, type(self).SHAPES(self.num_action))}
+
+    def flat(self):
+        """(params, grads) as flat f32 views -- the all-reduce bucket of data-parallel learners."""
+        C = self._C
+        pp, gp, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._call("flat", C.byref(pp), C.byref(gp), C.byref(n))
+        return self._view(pp.value, (n.value,)), self._view(gp.value, (n.value,))
+
+    def flat_target(self):
+        """The target net's flat parameter buffer (same layout as flat()[0]) -- what a publish sends along."""
+        p, n = self._struct("target"), self._C.c_int64()
+        self._call("flat", None, None, self._C.byref(n))
+        return self._view(getattr(p, self._fields[0]), (n.value,))  # the first tensor sits at offset 0
+
+    def stats(self):
+        """cuda f32[2]: gradient norm before clipping, clip coefficient of the last apply()."""
+        return self._view(getattr(self._capi.lib, self._PREFIX + "stats_dev")(self.h), (2,))
+
+    def _set_precision(self, mode):
+        self._call("set_precision", {"f32": 0, "bf16x2": 1, "f32x3": 2}[mode])
+
+    def grad(self):
+        self._call("grad", self._stream())
+
+    def apply(self):
+        self._call("apply", self._stream())
+
+    def step(self, batch, weight, world_size=1, group=None):
+        out = self.backward(batch, weight)
+        if world_size > 1:  # replicated learners: one flat SUM all-reduce, then the mean
+            sum_grads(self, world_size, group)
+        self.apply()
+        return out[0], out[1]  # (loss, priority)
+
+    def publish(self, online_handle, target_handle=None):
+        """ModelLocker.update_model for device nets: repack the current weights into actor-side FFNetHandle /
+        LSTMNetHandle objects (rela_ffnet_load / rela_lstmnet_load from device pointers, no host copy)."""
+        C, capi = self._C, self._capi
+        for handle, which in ((online_handle, "online"), (target_handle, "target")):
+            if handle is not None:
+                p = self._struct(which)
+                capi.check(getattr(capi.lib, self._NET_LOAD)(handle.h, C.byref(p), 1, self._stream()), self._NET_LOAD)
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self._capi.lib, self._PREFIX + "destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        capi = getattr(self, "_capi", None)
+        if capi is not None and getattr(capi, "lib", None) is not None:
+            self.close()
+
+
+class HipApexLearner(_HipLearner):
     """The Ape-X learner step in HIP (rela_apex_learner_*, csrc/learner.hip): the counterpart of
     `loss, priority = agent.loss(batch); (loss * weight).mean().backward(); clip_grad_norm_;
     optim.step()` of pyrela/main.py:226-239 for ApexAgent + AtariFFNet, without PyTorch autograd.
@@ -73,6 +202,7 @@ class HipApexLearner:
         learner.publish(actor_net)                  # every actor_sync_freq steps (ModelLocker.update_model)
     """
 
+    _PREFIX, _PARAMS, _NET_LOAD = "rela_apex_learner_", "FFNetParams", "rela_ffnet_load"
     KEYS = ("net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.weight", "net.4.bias",
             "linear.0.weight", "linear.0.bias", "fc_v.weight", "fc_v.bias", "fc_a.weight", "fc_a.bias")
     SHAPES = lambda A: ((32, 4, 8, 8), (32,), (64, 32, 4, 4), (64,), (64, 64, 3, 3), (64,), (512, 3136), (512,),  # noqa: E731
@@ -82,20 +212,8 @@ class HipApexLearner:
 
     def __init__(self, num_action, max_batch, multi_step, gamma, optimizer="rmsprop", lr=6.25e-5, eps=1.5e-4,
                  grad_clip=40.0, device="cuda:0"):
-        import ctypes as C
-
-        from . import _capi as capi
-
-        self._C, self._capi = C, capi
-        self.device = torch.device(device)
-        self.num_action, self.max_batch = num_action, max_batch
-        h = C.c_void_p()
-        capi.check(capi.lib.rela_apex_learner_create(C.byref(h), num_action, max_batch, multi_step, gamma,
-                                                     {"rmsprop": 0, "adam": 1}[optimizer], lr, eps, grad_clip,
-                                                     self.device.index or 0), "rela_apex_learner_create")
-        self.h = h
-        self._prio = torch.empty(max_batch, dtype=torch.float32, device=self.device)
-        self._loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        self._create(device, num_action, max_batch, multi_step, gamma, {"rmsprop": 0, "adam": 1}[optimizer], lr, eps,
+                     grad_clip)
 
     @classmethod
     def from_agent(cls, agent, max_batch, **kw):
@@ -107,114 +225,35 @@ class HipApexLearner:
         self.load_state_dicts(agent.online_net.state_dict(), agent.target_net.state_dict())
         return self
 
-    def set_value_rescale(self, eps):
-        """eps of the invertible value rescaling of the TD target (csrc/value_rescale.h); <= 0: off.  Before the first
-        loss only."""
-        self._capi.check(self._capi.lib.rela_apex_learner_set_value_rescale(self.h, float(eps)), "rela_apex_learner_set_value_rescale")
-
-    def _stream(self):
-        return self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _params(self, sd, keep):
-        p = self._capi.FFNetParams()
-        for (field, _), key in zip(self._capi.FFNetParams._fields_, self.KEYS):
-            t = sd[key].detach().to(self.device, torch.float32).contiguous()
-            keep.append(t)
-            setattr(p, field, t.data_ptr())
-        return p
-
-    def load_state_dicts(self, online_sd, target_sd=None):
-        C, capi = self._C, self._capi
-        keep = []
-        po = self._params(online_sd, keep)
-        pt = self._params(target_sd, keep) if target_sd is not None else None
-        capi.check(capi.lib.rela_apex_learner_load(self.h, C.byref(po), C.byref(pt) if pt is not None else None, 1,
-                                                   self._stream()), "rela_apex_learner_load")
-        torch.cuda.current_stream(self.device).synchronize()  # sources may be temporaries
-
-    def sync_target_with_online(self):
-        self._capi.check(self._capi.lib.rela_apex_learner_sync_target(self.h, self._stream()), "sync_target")
-
-    def _views(self, which):
-        from .engine import dev_view
-
-        C, capi = self._C, self._capi
-        p = capi.FFNetParams()
-        if which == "grads":
-            capi.check(capi.lib.rela_apex_learner_grads(self.h, C.byref(p)), "rela_apex_learner_grads")
-        elif which == "online":
-            capi.check(capi.lib.rela_apex_learner_params(self.h, C.byref(p), None), "rela_apex_learner_params")
-        else:
-            capi.check(capi.lib.rela_apex_learner_params(self.h, None, C.byref(p)), "rela_apex_learner_params")
-        shapes = HipApexLearner.SHAPES(self.num_action)
-        return {key: dev_view(getattr(p, field), shape, torch.float32, self.device)
-                for (field, _), key, shape in zip(capi.FFNetParams._fields_, self.KEYS, shapes)}, p
-
-    def state_dict(self, which="online"):
-        """Zero-copy views of the flat parameter buffer as a state_dict ("online" | "target" | "grads")."""
-        return self._views(which)[0]
-
-    def flat(self):
-        """(params, grads) as flat f32 views -- the all-reduce bucket of data-parallel learners."""
-        from .engine import dev_view
-
-        C, capi = self._C, self._capi
-        pp, gp, n = C.c_void_p(), C.c_void_p(), C.c_int64()
-        capi.check(capi.lib.rela_apex_learner_flat(self.h, C.byref(pp), C.byref(gp), C.byref(n)), "flat")
-        return (dev_view(pp.value, (n.value,), torch.float32, self.device),
-                dev_view(gp.value, (n.value,), torch.float32, self.device))
-
     def set_precision(self, mode):
         """"f32" (default) or "bf16x2": the arithmetic of the two gradient-free forwards of td_err (the pass whose
         activations feed the backward kernels stays f32).  "f32x3": conv2 / conv3 of all three forwards on the f32-accurate
         bf16 kernels (csrc/gemm_f32emu.h, from 512 rows); fc, heads, loss, backward and optimiser in exact f32."""
-        self._capi.check(self._capi.lib.rela_apex_learner_set_precision(self.h, {"f32": 0, "bf16x2": 1, "f32x3": 2}[mode]),
-                         "rela_apex_learner_set_precision")
-
-    def flat_target(self):
-        """The target net's flat parameter buffer (same layout as flat()[0]) -- what a publish sends along."""
-        from .engine import dev_view
-
-        C, capi = self._C, self._capi
-        p, n = capi.FFNetParams(), C.c_int64()
-        capi.check(capi.lib.rela_apex_learner_params(self.h, None, C.byref(p)), "rela_apex_learner_params")
-        capi.check(capi.lib.rela_apex_learner_flat(self.h, None, None, C.byref(n)), "flat")
-        return dev_view(p.conv1_w, (n.value,), torch.float32, self.device)  # conv1_w sits at offset 0
-
-    def stats(self):
-        """cuda f32[2]: gradient norm before clipping, clip coefficient of the last apply()."""
-        from .engine import dev_view
-
-        return dev_view(self._capi.lib.rela_apex_learner_stats_dev(self.h), (2,), torch.float32, self.device)
+        self._set_precision(mode)
 
     def debug_activations(self):
         """f32 views of online(obs)'s activations the last loss() left for the backward pass (channel-last):
         a1 [B,400,32], a2 [B,81,64], a3 [B,49,64], h [B,512]; their > 0 pattern is the ReLU mask of the gradients."""
-        from .engine import dev_view
-
-        C, capi = self._C, self._capi
+        C = self._C
         p = [C.c_void_p() for _ in range(4)]
         b = C.c_int()
-        capi.check(capi.lib.rela_apex_learner_debug_activations(self.h, *[C.byref(x) for x in p], C.byref(b)), "debug_activations")
+        self._call("debug_activations", *[C.byref(x) for x in p], C.byref(b))
         shapes = [(b.value, 400, 32), (b.value, 81, 64), (b.value, 49, 64), (b.value, 512)]
-        return [dev_view(x.value, sh, torch.float32, self.device) for x, sh in zip(p, shapes)]
+        return [self._view(x.value, sh) for x, sh in zip(p, shapes)]
 
     def backward(self, batch, weight):
         """batch: the namespace FFReplay.sample returns (or any object with obs / next_obs / action /
         reward / terminal / bootstrap of cuda tensors); weight: cuda f32[B].  -> (loss[1], priority[B])."""
-        return self._forward_half(batch, weight, "rela_apex_learner_backward")
+        return self._forward_half(batch, weight, "backward")
 
     def loss(self, batch, weight):
         """The forward half of `backward` (forwards, priorities, loss); `grad()` runs the backward pass of it.  In
         between the caller may update_priority and sample the next batch into OTHER buffers (FFReplay.sample(...,
         slot=1 - slot)): the replay's sample path then runs next to the gradient kernels."""
-        return self._forward_half(batch, weight, "rela_apex_learner_loss")
-
-    def grad(self):
-        self._capi.check(self._capi.lib.rela_apex_learner_grad(self.h, self._stream()), "rela_apex_learner_grad")
+        return self._forward_half(batch, weight, "loss")
 
     def _forward_half(self, batch, weight, entry):
-        C, capi = self._C, self._capi
+        C = self._C
         B = weight.numel()
         t = {"s": batch.obs["s"], "next_s": batch.next_obs["s"], "eps": batch.obs["eps"],
              "next_eps": batch.next_obs["eps"], "legal_move": batch.obs["legal_move"],
@@ -224,43 +263,12 @@ class HipApexLearner:
         w = weight.detach().float().contiguous()
         rows = (C.c_void_p * 10)(*[x.data_ptr() for x in keep])
         self._keep = (keep, w)
-        capi.check(getattr(capi.lib, entry)(self.h, B, rows, C.c_void_p(w.data_ptr()),
-                                            C.c_void_p(self._prio.data_ptr()),
-                                            C.c_void_p(self._loss.data_ptr()), self._stream()), entry)
+        self._call(entry, B, rows, C.c_void_p(w.data_ptr()), C.c_void_p(self._prio.data_ptr()),
+                   C.c_void_p(self._loss.data_ptr()), self._stream())
         return self._loss, self._prio[:B]
 
-    def apply(self):
-        self._capi.check(self._capi.lib.rela_apex_learner_apply(self.h, self._stream()), "rela_apex_learner_apply")
 
-    def step(self, batch, weight, world_size=1, group=None):
-        loss, prio = self.backward(batch, weight)
-        if world_size > 1:  # replicated learners: one flat SUM all-reduce, then the mean
-            sum_grads(self, world_size, group)
-        self.apply()
-        return loss, prio
-
-    def publish(self, online_handle, target_handle=None):
-        """ModelLocker.update_model for device nets: repack the current weights into actor-side
-        FFNetHandle objects (rela_ffnet_load from device pointers, no host copy)."""
-        C, capi = self._C, self._capi
-        _, po = self._views("online")
-        capi.check(capi.lib.rela_ffnet_load(online_handle.h, C.byref(po), 1, self._stream()), "rela_ffnet_load")
-        if target_handle is not None:
-            _, pt = self._views("target")
-            capi.check(capi.lib.rela_ffnet_load(target_handle.h, C.byref(pt), 1, self._stream()), "rela_ffnet_load")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._capi.lib.rela_apex_learner_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        capi = getattr(self, "_capi", None)
-        if capi is not None and getattr(capi, "lib", None) is not None:
-            self.close()
-
-
-class HipR2D2Learner:
+class HipR2D2Learner(_HipLearner):
     """The R2D2 learner step in HIP (rela_r2d2_learner_*, csrc/learner_r2d2.hip): the counterpart of
     `loss, priority = agent.loss(batch); (loss * weight).mean().backward(); clip_grad_norm_; optim.step()`
     of pyrela/main.py:226-239 for R2D2Agent + AtariLSTMNet (pyrela/r2d2.py:122-206, net.py:127-163), without
@@ -272,6 +280,7 @@ class HipR2D2Learner:
         replay.update_priority(priority)
     """
 
+    _PREFIX, _PARAMS, _NET_LOAD = "rela_r2d2_learner_", "LSTMNetParams", "rela_lstmnet_load"
     KEYS = ("net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.weight", "net.4.bias",
             "lstm.weight_ih_l0", "lstm.weight_hh_l0", "lstm.bias_ih_l0", "lstm.bias_hh_l0", "fc_v.weight", "fc_v.bias",
             "fc_a.weight", "fc_a.bias")
@@ -280,21 +289,9 @@ class HipR2D2Learner:
 
     def __init__(self, num_action, max_batch, multi_step, gamma, seq_len, burn_in, eta, optimizer="adam", lr=6.25e-5,
                  eps=1.5e-4, grad_clip=40.0, device="cuda:0"):
-        import ctypes as C
-
-        from . import _capi as capi
-
-        self._C, self._capi = C, capi
-        self.device = torch.device(device)
-        self.num_action, self.max_batch = num_action, max_batch
         self.seq_len, self.burn_in, self.multi_step = seq_len, burn_in, multi_step
-        h = C.c_void_p()
-        capi.check(capi.lib.rela_r2d2_learner_create(C.byref(h), num_action, max_batch, multi_step, gamma, seq_len,
-                                                     burn_in, float(eta), {"rmsprop": 0, "adam": 1}[optimizer], lr, eps,
-                                                     grad_clip, self.device.index or 0), "rela_r2d2_learner_create")
-        self.h = h
-        self._prio = torch.empty(max_batch, dtype=torch.float32, device=self.device)
-        self._loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        self._create(device, num_action, max_batch, multi_step, gamma, seq_len, burn_in, float(eta),
+                     {"rmsprop": 0, "adam": 1}[optimizer], lr, eps, grad_clip)
         self._loss_seq = torch.empty(max_batch, dtype=torch.float32, device=self.device)
 
     @classmethod
@@ -308,103 +305,29 @@ class HipR2D2Learner:
         self.load_state_dicts(agent.online_net.state_dict(), agent.target_net.state_dict())
         return self
 
-    def set_value_rescale(self, eps):
-        """eps of the invertible value rescaling of the TD target (csrc/value_rescale.h); <= 0: off.  Before the first
-        loss only."""
-        self._capi.check(self._capi.lib.rela_r2d2_learner_set_value_rescale(self.h, float(eps)), "rela_r2d2_learner_set_value_rescale")
-
-    def _stream(self):
-        return self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _params(self, sd, keep):
-        p = self._capi.LSTMNetParams()
-        for (field, _), key in zip(self._capi.LSTMNetParams._fields_, self.KEYS):
-            t = sd[key].detach().to(self.device, torch.float32).contiguous()
-            keep.append(t)
-            setattr(p, field, t.data_ptr())
-        return p
-
-    def load_state_dicts(self, online_sd, target_sd=None):
-        C, capi = self._C, self._capi
-        keep = []
-        po = self._params(online_sd, keep)
-        pt = self._params(target_sd, keep) if target_sd is not None else None
-        capi.check(capi.lib.rela_r2d2_learner_load(self.h, C.byref(po), C.byref(pt) if pt is not None else None, 1,
-                                                   self._stream()), "rela_r2d2_learner_load")
-        torch.cuda.current_stream(self.device).synchronize()  # sources may be temporaries
-
-    def sync_target_with_online(self):
-        self._capi.check(self._capi.lib.rela_r2d2_learner_sync_target(self.h, self._stream()), "sync_target")
-
-    def state_dict(self, which="online"):
-        """Zero-copy views of the flat buffers as a state_dict ("online" | "target" | "grads")."""
-        from .engine import dev_view
-
-        C, capi = self._C, self._capi
-        p = capi.LSTMNetParams()
-        if which == "grads":
-            capi.check(capi.lib.rela_r2d2_learner_grads(self.h, C.byref(p)), "rela_r2d2_learner_grads")
-        elif which == "online":
-            capi.check(capi.lib.rela_r2d2_learner_params(self.h, C.byref(p), None), "rela_r2d2_learner_params")
-        else:
-            capi.check(capi.lib.rela_r2d2_learner_params(self.h, None, C.byref(p)), "rela_r2d2_learner_params")
-        shapes = HipR2D2Learner.SHAPES(self.num_action)
-        return {key: dev_view(getattr(p, field), shape, torch.float32, self.device)
-                for (field, _), key, shape in zip(capi.LSTMNetParams._fields_, self.KEYS, shapes)}
-
-    def flat(self):
-        """(params, grads) as flat f32 views -- the all-reduce bucket of data-parallel learners (30 MB)."""
-        from .engine import dev_view
-
-        C, capi = self._C, self._capi
-        pp, gp, n = C.c_void_p(), C.c_void_p(), C.c_int64()
-        capi.check(capi.lib.rela_r2d2_learner_flat(self.h, C.byref(pp), C.byref(gp), C.byref(n)), "flat")
-        return (dev_view(pp.value, (n.value,), torch.float32, self.device),
-                dev_view(gp.value, (n.value,), torch.float32, self.device))
-
-    def stats(self):
-        from .engine import dev_view
-
-        return dev_view(self._capi.lib.rela_r2d2_learner_stats_dev(self.h), (2,), torch.float32, self.device)
-
-    def flat_target(self):
-        """The target net's flat parameter buffer (same layout as flat()[0]) -- what a publish sends along."""
-        from .engine import dev_view
-
-        C, capi = self._C, self._capi
-        p, n = capi.LSTMNetParams(), C.c_int64()
-        capi.check(capi.lib.rela_r2d2_learner_params(self.h, None, C.byref(p)), "rela_r2d2_learner_params")
-        capi.check(capi.lib.rela_r2d2_learner_flat(self.h, None, None, C.byref(n)), "flat")
-        return dev_view(getattr(p, capi.LSTMNetParams._fields_[0][0]), (n.value,), torch.float32, self.device)
-
     def set_precision(self, mode):
         """"f32" (default); "bf16x2": the target net's conv trunk on split-bf16 MFMA (no gradient flows through it);
         "f32x3": conv2 / conv3 of both trunks on the f32-accurate three-part bf16 kernels (csrc/gemm_f32emu.h)."""
-        self._capi.check(self._capi.lib.rela_r2d2_learner_set_precision(self.h, {"f32": 0, "bf16x2": 1, "f32x3": 2}[mode]),
-                         "rela_r2d2_learner_set_precision")
+        self._set_precision(mode)
 
     def check(self):
         """Synchronises and raises if a grid barrier of the persistent recurrent kernels gave up since the last check."""
-        stream = self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._capi.check(self._capi.lib.rela_r2d2_learner_check(self.h, stream), "rela_r2d2_learner_check")
+        self._call("check", self._stream())
 
     def backward(self, batch, weight):
         """batch: RNNTransition-shaped (time-major [T, B, ...] cuda tensors: obs{s, eps, legal_move}, h0{h0, c0},
         action{a}, reward, terminal, bootstrap, seq_len); weight: cuda f32[B].
         -> (mean(loss * weight)[1], aggregated priority[B], per-sequence loss[B])."""
-        return self._forward_half(batch, weight, "rela_r2d2_learner_backward")
+        return self._forward_half(batch, weight, "backward")
 
     def loss(self, batch, weight):
         """The forward half of `backward` (unrolls, TD errors, priorities, loss); `grad()` runs the backward pass of
         it.  In between the caller may update_priority and sample the next batch into OTHER buffers
         (RNNReplay.sample(..., slot=1 - slot))."""
-        return self._forward_half(batch, weight, "rela_r2d2_learner_loss")
-
-    def grad(self):
-        self._capi.check(self._capi.lib.rela_r2d2_learner_grad(self.h, self._stream()), "rela_r2d2_learner_grad")
+        return self._forward_half(batch, weight, "loss")
 
     def _forward_half(self, batch, weight, entry):
-        C, capi = self._C, self._capi
+        C = self._C
         B = weight.numel()
         dev = self.device
         fields = [batch.obs["s"], batch.obs["eps"].float(), batch.obs["legal_move"].float(), batch.action["a"],
@@ -417,69 +340,36 @@ class HipR2D2Learner:
         w = weight.detach().to(dev).float().contiguous()
         rows = (C.c_void_p * 10)(*[x.data_ptr() for x in keep])
         self._keep = (keep, w)
-        capi.check(getattr(capi.lib, entry)(self.h, B, rows, C.c_void_p(w.data_ptr()),
-                                            C.c_void_p(self._prio.data_ptr()), C.c_void_p(self._loss.data_ptr()),
-                                            C.c_void_p(self._loss_seq.data_ptr()), self._stream()), entry)
+        self._call(entry, B, rows, C.c_void_p(w.data_ptr()), C.c_void_p(self._prio.data_ptr()),
+                   C.c_void_p(self._loss.data_ptr()), C.c_void_p(self._loss_seq.data_ptr()), self._stream())
         return self._loss, self._prio[:B], self._loss_seq[:B]
-
-    def apply(self):
-        self._capi.check(self._capi.lib.rela_r2d2_learner_apply(self.h, self._stream()), "rela_r2d2_learner_apply")
-
-    def step(self, batch, weight, world_size=1, group=None):
-        loss, prio, _ = self.backward(batch, weight)
-        if world_size > 1:
-            sum_grads(self, world_size, group)
-        self.apply()
-        return loss, prio
-
-    def publish(self, online_handle, target_handle=None):
-        """ModelLocker.update_model for device nets: repack the current weights into actor-side LSTMNetHandle
-        objects (rela_lstmnet_load from device pointers, no host copy)."""
-        C, capi = self._C, self._capi
-        po, pt = capi.LSTMNetParams(), capi.LSTMNetParams()
-        capi.check(capi.lib.rela_r2d2_learner_params(self.h, C.byref(po), C.byref(pt)), "rela_r2d2_learner_params")
-        capi.check(capi.lib.rela_lstmnet_load(online_handle.h, C.byref(po), 1, self._stream()), "rela_lstmnet_load")
-        if target_handle is not None:
-            capi.check(capi.lib.rela_lstmnet_load(target_handle.h, C.byref(pt), 1, self._stream()), "rela_lstmnet_load")
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._capi.lib.rela_r2d2_learner_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        capi = getattr(self, "_capi", None)
-        if capi is not None and getattr(capi, "lib", None) is not None:
-            self.close()
 
 
 # ---- weight publish to actor-only ranks (SURVEY 8e: C3 / C4 layouts) ------------------------------
 FFNET_KEYS = HipApexLearner.KEYS
 
 
-def ffnet_flat_layout(num_action):
-    """[(state_dict key, shape, offset)] and the total length of the flat f32 parameter buffer of
-    csrc/learner.hip: rela_ffnet_params order, every segment padded to a multiple of 4 floats."""
+def _flat_layout(cls, num_action):
     out, off = [], 0
-    for key, shape in zip(FFNET_KEYS, HipApexLearner.SHAPES(num_action)):
+    for key, shape in zip(cls.KEYS, cls.SHAPES(num_action)):
         n = 1
         for d in shape:
             n *= d
         out.append((key, shape, off))
         off += (n + 3) // 4 * 4
     return out, off
+
+
+def ffnet_flat_layout(num_action):
+    """[(state_dict key, shape, offset)] and the total length of the flat f32 parameter buffer of
+    csrc/learner.hip: rela_ffnet_params order, every segment padded to a multiple of 4 floats (csrc/param_layout.h;
+    tests/test_param_layout_host.py holds the two together)."""
+    return _flat_layout(HipApexLearner, num_action)
 
 
 def lstmnet_flat_layout(num_action):
     """As ffnet_flat_layout for the flat buffer of csrc/learner_r2d2.hip (rela_lstmnet_params order)."""
-    out, off = [], 0
-    for key, shape in zip(HipR2D2Learner.KEYS, HipR2D2Learner.SHAPES(num_action)):
-        n = 1
-        for d in shape:
-            n *= d
-        out.append((key, shape, off))
-        off += (n + 3) // 4 * 4
-    return out, off
+    return _flat_layout(HipR2D2Learner, num_action)
 
 
 def broadcast_weights(flat, src=0, group=None):

@@ -484,3 +484,31 @@ def test_hip_r2d2_learner_f32x3_is_f32_accurate(B, seq, burn, n, record_property
     assert err["bf16x2"]["priority"][1] >= BF16X2_SEPARATION * err["f32x3"]["priority"][1], err
     for k in HipR2D2Learner.KEYS:
         assert gerr["f32x3"][k] <= X3_GRAD_SLACK * gerr["f32"][k], (k, gerr["f32x3"][k], gerr["f32"][k])
+
+
+@pytest.mark.parametrize("algo", ["r2d2", "apex"])
+def test_learner_state_dict_views_sit_at_the_flat_layout_offsets(algo):
+    """The learners' flat store (csrc/learner_common.h: LearnerCore, offsets from csrc/param_layout.h) against the Python
+    layout actor-only ranks cut the published buffer up with: every tensor of state_dict("online" | "target" |
+    "grads") is the view at base + 4 * offset of lstmnet_flat_layout / ffnet_flat_layout, the bases being flat()[0],
+    flat_target() and flat()[1], and the buffers are as long as the layout says.  Nothing is loaded and no forward runs."""
+    from rela_amd.learner import HipApexLearner, HipR2D2Learner, ffnet_flat_layout, lstmnet_flat_layout
+
+    A = 6
+    if algo == "r2d2":
+        learner = HipR2D2Learner(A, 2, 1, 0.997, 2, 1, 0.9)  # max_batch 2, multi_step 1, seq_len 2, burn_in 1
+        layout, total = lstmnet_flat_layout(A)
+    else:
+        learner = HipApexLearner(A, 4, 3, 0.99)  # max_batch 4
+        layout, total = ffnet_flat_layout(A)
+    params, grads = learner.flat()
+    assert params.numel() == total and grads.numel() == total and learner.flat_target().numel() == total
+    bases = {"online": params.data_ptr(), "target": learner.flat_target().data_ptr(), "grads": grads.data_ptr()}
+    assert len(set(bases.values())) == 3
+    for which, base in bases.items():
+        sd = learner.state_dict(which)
+        assert list(sd) == [key for key, _, _ in layout]
+        for key, shape, off in layout:
+            assert sd[key].data_ptr() == base + 4 * off, (which, key)
+            assert tuple(sd[key].shape) == tuple(shape), (which, key)
+    learner.close()
