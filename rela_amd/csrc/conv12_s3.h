@@ -10,9 +10,13 @@
 //          consecutive OUTPUT pixels of a conv2 tile (stride 2) advance by 10 units mod 16: conflict-free ds_read_b128.
 //   conv2  six products per operand pair on v_mfma_f32_16x16x32_bf16 (gemm_f32emu.h's arithmetic, small terms in their own
 //          accumulator); a wave owns 16 output channels, its 16 k-steps x 3 parts of weights are RESIDENT (192 registers);
-//          tile by tile (16 pixels), fragments three k-steps ahead in a register ring.
+//          tile by tile (16 pixels), fragments three k-steps ahead in a register ring.  A frame runs FIVE tiles (pixels
+//          0 .. 79); pixel 80's 16 input records go into an LDS ring of RING_S slots, and one more tile over the ring's
+//          slots, when it is full and after the block's last frame, computes pixel 80 of up to RING_S frames at once.
+//          Every output is one MFMA column fed by its own pixel's fragments in the same k order: the same bits as a
+//          sixth tile per frame that held pixel 80 and fifteen copies of it.
 //   a2     ReLU, split, staged in LDS as records and copied out whole (coalesced 16-byte stores) under the next frame's
-//          conv1.
+//          conv1 (pixels 0 .. 79; pixel 80's three parts go from the ring's tile straight to HBM).
 // One block of FOUR waves per CU (512 registers each: 240 hold weights), persistent over the frames b, b + grid, ...;
 // two barriers per frame.  Registers by construction: conv2's 192 weight registers are pinned into the accumulator half
 // of the file (MFMA A operands only) beside the sums; conv1's digits, every address and every staged byte live in the 256
@@ -47,11 +51,19 @@ struct Conv12S {
   static constexpr int Q = 13, RQ = 261;              // a1 image: pixel / row stride in 16-byte units
   static constexpr int T2_BYTES = 20 * RQ * 16;       // 83,520
   static constexpr int OROW = 400;                    // a2 record (384 B) + 16: the 16 pixels of a store spread over the banks
-  static constexpr int O_BYTES = 81 * OROW;
-  static constexpr int SPARE = T1_BYTES + T2_BYTES + O_BYTES;  // 256 B: rows past the last pixel land here
-  static constexpr int LDS_TOTAL = SPARE + 256;
+  // conv2's image is 9 x 9 = 81 pixels = five whole 16-pixel tiles + pixel 80.  The frame loop runs the five tiles; pixel
+  // 80's input patch (the a1 records of rows 16 .. 19 x columns 16 .. 19, in tap order: 16 x 192 B) is copied into a ring
+  // of RING_S slots, and ONE tile over the ring's slots -- lane li takes slot li -- yields pixel 80 of RING_S frames.
+  // Slot stride 202 units (10 mod 16, as the pixel stride 2 Q of a tile inside T2): conflict-free ds_read_b128.
+  static constexpr int C2TILES = 5, C2PIX = C2TILES * 16;
+  static constexpr int O_BYTES = C2PIX * OROW;
+  static constexpr int RING_S = 5;
+  static constexpr int PATCH_UNITS = 16 * 12, SLOT_BYTES = 202 * 16;
+  static constexpr int RING = T1_BYTES + T2_BYTES + O_BYTES;
+  static constexpr int LDS_TOTAL = RING + RING_S * SLOT_BYTES;  // 160,352
   static_assert(LDS_TOTAL <= 160 * 1024, "LDS budget");
-  static constexpr int OV16 = 81 * 24, OIT = (OV16 + kT - 1) / kT;    // 16-byte chunks of an output tile: 8 per thread
+  static_assert(RING_S >= 1 && RING_S <= 16, "one slot per lane of a tile's column");
+  static constexpr int OV16 = C2PIX * 24, OIT = (OV16 + kT - 1) / kT;  // 16-byte chunks of an output tile: 8 per thread
   // staging by 16-byte row loads: a unit = four cells side by side (X0 .. X0 + 3) of one plane, six units per cell row
   // (X0 = 0, 4, 8, 12, 16 and 17: the sixth unit, cells 17 .. 20, re-writes the cells 17 .. 19 with the same bytes)
   static constexpr int UNITS = 4 * GW * 6, UIT = (UNITS + kT - 1) / kT;  // 504: two units per thread
@@ -279,19 +291,75 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
   auto no_hook = [](auto) {};
   static_assert(2 * F::OIT <= 20, "copy-out slots inside conv1's first pass");
 
-  uint32_t xbh[6];  // conv2's per-tile offsets into the a1 image (frame-invariant)
+  uint32_t xbh[F::C2TILES];  // conv2's per-tile offsets into the a1 image (frame-invariant)
 #pragma unroll
-  for (int t = 0; t < 6; ++t) {
-    const int m = t * 16 + li, mm = m < 81 ? m : 80;
-    const int oy = mm / 9, ox = mm - oy * 9;
+  for (int t = 0; t < F::C2TILES; ++t) {
+    const int m = t * 16 + li;
+    const int oy = m / 9, ox = m - oy * 9;
     xbh[t] = (uint32_t)((2 * oy * F::RQ + 2 * ox * F::Q + g) * 16);
   }
-  uint32_t o2dst[6];  // ... and into O (tile rows past the last pixel: the spare row)
+  uint32_t o2dst[F::C2TILES];  // ... and into O
 #pragma unroll
-  for (int t = 0; t < 6; ++t) {
-    const int m = t * 16 + li;
-    o2dst[t] = (uint32_t)((m < 81 ? F::T1_BYTES + F::T2_BYTES + m * F::OROW : F::SPARE) + ch2 * 2);
+  for (int t = 0; t < F::C2TILES; ++t) o2dst[t] = (uint32_t)(F::T1_BYTES + F::T2_BYTES + (t * 16 + li) * F::OROW + ch2 * 2);
+  // pixel 80's patch: thread t < 192 moves unit t % 12 of record t / 12 (tap order) from T2 into the ring (frame-invariant;
+  // the fourth wave repeats thread 191's unit: the same bytes to the same place, no branch)
+  uint32_t psrc, pdst;
+  {
+    const int t = min(tid, F::PATCH_UNITS - 1);
+    const int r = t / 12, u = t - r * 12;
+    psrc = (uint32_t)(((16 + (r >> 2)) * F::RQ + (16 + (r & 3)) * F::Q + u) * 16);
+    pdst = (uint32_t)(F::RING + t * 16);
   }
+  // ---- pixel 80 of the frames first, first + nblk, ... whose patches fill the ring's slots 0 .. cnt - 1: one conv2 tile,
+  // the same k-steps, the same six products into the same acc / accs as any other pixel; a lane past cnt takes the last
+  // slot and repeats its store.  The results go straight to HBM (part p of an a2 record at + 128 p).
+  auto pixel80_tile = [&](int cnt, int first) {
+    constexpr int D = 3;
+    const int sl = min(li, cnt - 1);
+    const uint8_t* rp = smem_c12 + F::RING + sl * F::SLOT_BYTES + g * 16;
+    uint4 xr[D][3];
+    auto a_issue = [&](auto ks_tag, int slot) {
+      constexpr int KS = decltype(ks_tag)::value;
+      const uint8_t* ap = rp + F::tap2(KS) * 192;
+      xr[slot][0] = *reinterpret_cast<const uint4*>(ap);
+      xr[slot][1] = *reinterpret_cast<const uint4*>(ap + 64);
+      xr[slot][2] = *reinterpret_cast<const uint4*>(ap + 128);
+    };
+    static_for<D>([&](auto i) { a_issue(i, decltype(i)::value); });
+    __builtin_amdgcn_sched_barrier(0);
+    f32x4 acc = bv2, accs = {0.f, 0.f, 0.f, 0.f};
+    static_for<F::KS2>([&](auto it) {
+      constexpr int KS = decltype(it)::value, SLOT = KS % D;
+      const bf16x8 x0 = __builtin_bit_cast(bf16x8, xr[SLOT][0]), x1 = __builtin_bit_cast(bf16x8, xr[SLOT][1]),
+                   x2 = __builtin_bit_cast(bf16x8, xr[SLOT][2]);
+      if constexpr (!kNoConv2) {
+        accs = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2[KS][2], x0, accs, 0, 0, 0);
+        accs = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2[KS][0], x2, accs, 0, 0, 0);
+        accs = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2[KS][1], x1, accs, 0, 0, 0);
+        accs = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2[KS][1], x0, accs, 0, 0, 0);
+        accs = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2[KS][0], x1, accs, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2[KS][0], x0, acc, 0, 0, 0);
+      } else {
+        asm volatile("" ::"v"(x0), "v"(x1), "v"(x2));
+      }
+      if constexpr (KS + D < F::KS2) a_issue(IC<KS + D>{}, SLOT);
+      __builtin_amdgcn_sched_barrier(0);
+    });
+    if constexpr (kNoEpi2) {
+      asm volatile("" ::"v"(acc), "v"(accs));
+    } else {
+      f32x4 v = acc + accs;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
+      uint2 p0, p1, p2;
+      split3_4(v, p0, p1, p2);
+      uint8_t* rec = out + (size_t)(first + sl * nblk) * (81 * 384) + (F::C2PIX * 384 + ch2 * 2);
+      *reinterpret_cast<uint2*>(rec) = p0;
+      *reinterpret_cast<uint2*>(rec + 128) = p1;
+      *reinterpret_cast<uint2*>(rec + 256) = p2;
+    }
+  };
+  int filled = 0;  // the ring's slots in use (uniform)
   for (; n < N; n += nblk) {
     const int nn = (n + nblk < N) ? n + nblk : n;  // (the last round re-stages its own frame)
     pin_weights();
@@ -302,8 +370,9 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
     __syncthreads();  // T2 complete, T1 and O free
     // ---- conv2 from T2, tile by tile; the next frame's cells go into T1 in the second half
     {
-      constexpr int NTILE = 6, TOT = NTILE * F::KS2, D = 3;
-      static_assert(NTILE == 6, "xbh / o2dst");
+      constexpr int TOT = F::C2TILES * F::KS2, D = 3;
+      // pixel 80's patch -> slot `filled` of the ring: read here, written behind item 2
+      const uint4 patch = *reinterpret_cast<const uint4*>(t2 + psrc);
       uint4 xr[D][3];
       auto a_issue = [&](auto idx_tag, int slot) {
         constexpr int IDX = decltype(idx_tag)::value, T = IDX / F::KS2, KS = IDX - T * F::KS2;
@@ -330,8 +399,9 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
           asm volatile("" ::"v"(x0), "v"(x1), "v"(x2));
         }
         if constexpr (IDX + D < TOT) a_issue(IC<IDX + D>{}, SLOT);
+        if constexpr (IDX == 2) *reinterpret_cast<uint4*>(smem_c12 + pdst + filled * F::SLOT_BYTES) = patch;
         // the next frame's two units: loaded behind items 1 and 13, their eight cells stored (sign bits flipped) behind
-        // items 48, 52, ..., 76
+        // items 40, 44, ..., 68
         static_for<4 * F::UIT>([&](auto jj) {
           constexpr int JJ = decltype(jj)::value;
           if constexpr (JJ < F::UIT && IDX == 1 + 12 * JJ && !kNoStage) g_load4(nn, JJ);
@@ -353,8 +423,14 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
         __builtin_amdgcn_sched_barrier(0);
       });
     }
-    __syncthreads();  // O complete, T1 ready, T2 free
+    __syncthreads();  // O complete, T1 ready, T2 free, the ring's slot written
     prev = n;
+    // the ring is full, or this was the block's last frame: its pixels 80 now (uniform branch).  The next write into the
+    // ring comes behind the next frame's first barrier, which every wave reaches only after this tile: no barrier here.
+    if (++filled == F::RING_S || n + nblk >= N) {
+      pixel80_tile(filled, n - (filled - 1) * nblk);
+      filled = 0;
+    }
   }
   {  // the last frame's output tile
     uint4* dst = reinterpret_cast<uint4*>(out + (size_t)prev * (81 * 384));

@@ -1,6 +1,7 @@
 // s3_probe.hip -- standalone check + timing of rela_amd/csrc/gemm_s3.h (f32x3 contractions over split3 records).
 //   hipcc --offload-arch=gfx950 -O3 -I rela_amd/csrc tools/ubench/s3_probe.hip -o tools/ubench/s3_probe
 //   tools/ubench/s3_probe [N = 6554] [iters = 20]
+//   tools/ubench/s3_probe N iters 12 | 13     conv12_s3<false> | <true> alone: time and checksums
 // For conv2 / conv3 / fc of the AtariFFNet trunk at N samples: runs the 6- and 9-product kernels on random ReLU-like
 // activations, compares sampled outputs with an f64 evaluation on the host and with a sequential f32 FMA chain (what
 // "f32 arithmetic" means for one dot product), and times the kernels with HIP events.  One JSON object per line.
@@ -232,10 +233,23 @@ static void run(const HostProb& hp, int N, int iters) {
   CK(hipFree(dP));
 }
 
-// timing only (random digits / weights / frames: the values do not matter for the clock): conv1 -> conv2 fused
+// timing (random digits / weights / frames: the values do not matter for the clock) of conv1 -> conv2 fused, two timed
+// repeats per run, and an FNV-1a checksum of the a2 records (and of a1_out) to compare builds on the same inputs
+static uint64_t fnv1a(const void* dev, size_t bytes) {
+  std::vector<uint8_t> h(bytes);
+  CK(hipMemcpy(h.data(), dev, bytes, hipMemcpyDeviceToHost));
+  uint64_t x = 1469598103934665603ull;
+  for (uint8_t b : h) x = (x ^ b) * 1099511628211ull;
+  return x;
+}
+
+template <bool A1OUT>
 static void time_conv12(int N, int iters) {
   using F = s3::Conv12S;
   uint8_t *in, *out;
+  float* a1 = nullptr;
+  const size_t a1_bytes = (size_t)N * 400 * 32 * 4;
+  if (A1OUT) CK(hipMalloc(&a1, a1_bytes));
   uint4 *W1d, *B2;
   float *sc, *b1, *b2;
   const size_t in_bytes = (size_t)N * F::IN_ELEMS, out_bytes = (size_t)N * 81 * 384;
@@ -256,14 +270,15 @@ static void time_conv12(int N, int iters) {
   std::vector<uint16_t> wb(16 * 4 * 3 * 64 * 8);
   for (auto& v : wb) v = (uint16_t)(0x3c00 + (rng() & 0xff));  // small positive bf16
   CK(hipMemcpy(B2, wb.data(), wb.size() * 2, hipMemcpyHostToDevice));
+  CK(hipMemset(out, 0xff, out_bytes));
   std::vector<float> f(64, 1e-9f);
   CK(hipMemcpy(sc, f.data(), 256, hipMemcpyHostToDevice));
   CK(hipMemcpy(b1, f.data(), 256, hipMemcpyHostToDevice));
   CK(hipMemcpy(b2, f.data(), 256, hipMemcpyHostToDevice));
-  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&s3::conv12_s3<false>), hipFuncAttributeMaxDynamicSharedMemorySize, F::LDS_TOTAL));
+  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&s3::conv12_s3<A1OUT>), hipFuncAttributeMaxDynamicSharedMemorySize, F::LDS_TOTAL));
   auto go = [&]() {
-    hipLaunchKernelGGL(s3::conv12_s3<false>, dim3(std::min(256, N)), dim3(F::kT), F::LDS_TOTAL, 0, in, W1d, sc, b1, B2, b2, out,
-                       (float*)nullptr, N);
+    hipLaunchKernelGGL(s3::conv12_s3<A1OUT>, dim3(std::min(256, N)), dim3(F::kT), F::LDS_TOTAL, 0, in, W1d, sc, b1, B2, b2, out, a1,
+                       N);
   };
   for (int i = 0; i < 3; ++i) go();
   CK(hipDeviceSynchronize());
@@ -271,20 +286,30 @@ static void time_conv12(int N, int iters) {
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
-  CK(hipEventRecord(e0, 0));
-  for (int i = 0; i < iters; ++i) go();
-  CK(hipEventRecord(e1, 0));
-  CK(hipEventSynchronize(e1));
-  float ms = 0;
-  CK(hipEventElapsedTime(&ms, e0, e1));
-  printf("{\"layer\": \"conv12\", \"N\": %d, \"us\": %.1f}\n", N, 1e3 * ms / iters);
+  float us[2];
+  for (int rep = 0; rep < 2; ++rep) {
+    CK(hipEventRecord(e0, 0));
+    for (int i = 0; i < iters; ++i) go();
+    CK(hipEventRecord(e1, 0));
+    CK(hipEventSynchronize(e1));
+    float ms = 0;
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    us[rep] = 1e3f * ms / iters;
+  }
+  CK(hipGetLastError());
+  printf("{\"layer\": \"conv12\", \"a1_out\": %d, \"N\": %d, \"us\": %.1f, \"us_repeat2\": %.1f, \"a2_fnv\": \"%016llx\", \"a1_fnv\": \"%016llx\"}\n",
+         (int)A1OUT, N, us[0], us[1], (unsigned long long)fnv1a(out, out_bytes), (unsigned long long)(A1OUT ? fnv1a(a1, a1_bytes) : 0));
 }
 
 int main(int argc, char** argv) {
   const int N = argc > 1 ? atoi(argv[1]) : 6554;
   const int iters = argc > 2 ? atoi(argv[2]) : 20;
-  if (argc > 3 && atoi(argv[3]) == 12) {
-    time_conv12(N, iters);
+  if (argc > 3 && atoi(argv[3]) == 12) {  // conv12_s3<false>; 13: conv12_s3<true> (also writes a1_out)
+    time_conv12<false>(N, iters);
+    return 0;
+  }
+  if (argc > 3 && atoi(argv[3]) == 13) {
+    time_conv12<true>(N, iters);
     return 0;
   }
   const HostProb p2{"conv2", 1, 512, 64, 81, 12800, x2, w2};
