@@ -553,6 +553,28 @@ __global__ __launch_bounds__(256) void replay_gather_small_remote(SmallFields t,
 
 using namespace rela_amd;
 
+// The row layout of a partition: what its owner sets (rela_replay_set_schema*) and an importer reads from the descriptor.
+struct ReplaySchema {
+  int nfields = 0;
+  std::vector<int64_t> row_bytes;  // per slot
+  std::vector<int32_t> steps;      // sub-rows per slot (1 = plain field)
+  // frame-stack de-duplication (rela_replay_set_schema_dedup): the stack fields hold int32 references into a ring of
+  // UNITS (one 84x84 plane, or one 4-plane stack)
+  int dd_ups = 0;              // units per stack (0 = de-duplication off)
+  int dd_field[2] = {-1, -1};  // sequence schema (rela_replay_set_schema_seq_dedup): one stack field, dd_field[1] = -1
+  int64_t dd_unit_bytes = 0;
+  int dd_steps = 0;  // sequence schema: stacks per slot (0 = transition schema, two stack fields)
+  bool is_stack(int f) const { return dd_ups > 0 && (f == dd_field[0] || f == dd_field[1]); }
+};
+
+static inline int vec16_ok(const void* a, const void* b, int64_t row_bytes) {
+  return ((row_bytes & 15) == 0) && (((uintptr_t)a & 15) == 0) && (((uintptr_t)b & 15) == 0);
+}
+// blocks along x of the row-copy kernels: `units` items per row, one per thread and pass
+static inline int grid_x(int64_t units) {
+  return (int)std::min<int64_t>(std::max<int64_t>(1, (units + kThreads - 1) / kThreads), 64);
+}
+
 struct rela_replay {
   int device = 0;
   int capacity = 0, ring = 0, prefetch = 0;
@@ -601,7 +623,7 @@ struct rela_replay {
   std::vector<hipEvent_t> ev_pool;
   // rela_replay_set_decoupled_insert: false (default) = an insert runs wholly on `stream`, in order with sample /
   // update; true = its row copies and priority staging run on `copy_stream` (see above)
-  bool legacy_insert = true;
+  bool decoupled_insert = false;
   hipStream_t copy_stream_own = nullptr;
   bool deferred_wait = false;  // rela_replay_set_deferred_wait: sample / update_priority do not stall the caller's stream
   float* d_w = nullptr;
@@ -615,23 +637,16 @@ struct rela_replay {
   double* d_eff = nullptr;
   uint32_t* d_draws = nullptr;
   float* d_prio = nullptr;  // staging for host-side priorities
-  std::vector<int64_t> row_bytes;
-  std::vector<int32_t> steps;  // sub-rows per slot (1 = plain field)
-  std::vector<uint8_t*> d_fields;
-  // chunk_bytes > 0: every field array is chunks of physical memory of at most that size behind one virtual range
-  // (vmm_field.h), so that a partition of any size can be exported to another process; 0: one hipMalloc per field, vmm[f] null
+  ReplaySchema sc;
+  std::vector<DevRange> fields;  // [sc.nfields]
+  // chunk_bytes > 0: every field array and the unit ring are chunks of physical memory of at most that size behind one
+  // virtual range (vmm_field.h), so that a partition of any size can be exported to another process; 0: one hipMalloc each
   int64_t chunk_bytes = 0;
-  std::vector<VmmRange*> vmm;
   SeqIndex ix;
   HostStage stage;  // pinned staging of the RNG draws / host-side priorities (guarded by m)
-  // frame-stack de-duplication (rela_replay_set_schema_dedup): the two stack fields hold int32 references
-  // into a ring of UNITS (one 84x84 plane, or one 4-plane stack) addressed by a monotone sequence number
-  int dd_ups = 0;                 // units per stack (0 = de-duplication off)
-  int64_t dd_unit_bytes = 0, dd_cap = 0;
-  uint8_t* d_units = nullptr;     // [dd_cap][dd_unit_bytes]
-  VmmRange* vmm_units = nullptr;  // chunked mode: d_units = vmm_units->base
-  int dd_field[2] = {-1, -1};     // sequence schema (rela_replay_set_schema_seq_dedup): one stack field, dd_field[1] = -1
-  int dd_steps = 0;               // sequence schema: stacks per slot (0 = transition schema, two stack fields)
+  // the unit ring of a de-duplicated schema (sc.dd_ups > 0), addressed by a monotone sequence number
+  DevRange units;  // [dd_cap][sc.dd_unit_bytes]
+  int64_t dd_cap = 0;
   int64_t dd_units_per_slot = 1;  // units a slot adds to the ring beyond the guard (transition schema: 1)
   int64_t dd_next_seq = 0;        // sequence number of the next unit
   std::vector<int64_t> dd_slot_min;  // [ring] smallest unit sequence a slot refers to (host; guarded by m)
@@ -719,22 +734,10 @@ extern "C" void rela_replay_destroy(rela_replay* r) {
   (void)hipEventDestroy(r->ev_cin);
   (void)hipEventDestroy(r->ev_cout);
   (void)hipStreamDestroy(r->copy_stream_own);
-  for (size_t f = 0; f < r->d_fields.size(); ++f) {
-    if (f < r->vmm.size() && r->vmm[f]) {
-      r->vmm[f]->destroy();
-      delete r->vmm[f];
-    } else {
-      (void)hipFree(r->d_fields[f]);
-    }
-  }
+  for (auto& d : r->fields) d.release();
   seq_index_free(&r->ix);
   r->stage.destroy();
-  if (r->vmm_units) {
-    r->vmm_units->destroy();
-    delete r->vmm_units;
-  } else {
-    (void)hipFree(r->d_units);
-  }
+  r->units.release();
   (void)hipFree(r->d_w);
   (void)hipFree(r->d_evicted);
   (void)hipFree(r->d_state);
@@ -758,9 +761,22 @@ extern "C" int rela_replay_set_schema_seq(rela_replay* r, int nfields, const int
 extern "C" int rela_replay_set_chunk_bytes(rela_replay* r, int64_t bytes) {
   RELA_CHECK(r && bytes >= 0, RELA_EINVAL, "rela_replay_set_chunk_bytes: bad arguments");
   std::lock_guard<std::mutex> lk(r->m);
-  RELA_CHECK(r->d_fields.empty(), RELA_ESTATE, "rela_replay_set_chunk_bytes: the schema is already set");
+  RELA_CHECK(r->fields.empty(), RELA_ESTATE, "rela_replay_set_chunk_bytes: the schema is already set");
   r->chunk_bytes = bytes;
   return RELA_OK;
+}
+
+// (caller holds r->m) a field array or the unit ring, plain or chunked as r->chunk_bytes says; `what` names it and
+// introduces its size in the message: "field 3:" / "unit ring of"
+static int create_range(rela_replay* r, DevRange* d, size_t bytes, const char* who, const char* what) {
+  const hipError_t e = d->create(bytes, (size_t)r->chunk_bytes, r->device);
+  if (e == hipSuccess) return RELA_OK;
+  if (r->chunk_bytes > 0)
+    set_last_error("%s: %s %.1f GB in chunks of %.1f GB: %s", who, what, (double)bytes / 1e9, (double)r->chunk_bytes / 1e9,
+                   hipGetErrorString(e));
+  else
+    set_last_error("%s: %s %.1f GB: %s", who, what, (double)bytes / 1e9, hipGetErrorString(e));
+  return e == hipErrorOutOfMemory ? RELA_ENOMEM : RELA_ENODEV;
 }
 
 extern "C" int rela_replay_set_schema(rela_replay* r, int nfields, const int64_t* row_bytes) {
@@ -771,7 +787,7 @@ extern "C" int rela_replay_set_schema_seq(rela_replay* r, int nfields, const int
                                           const int32_t* steps) {
   RELA_CHECK(r && nfields >= 0 && (nfields == 0 || row_bytes), RELA_EINVAL, "rela_replay_set_schema: bad arguments");
   std::lock_guard<std::mutex> lk(r->m);
-  RELA_CHECK(r->d_fields.empty() && r->num_add.load() == 0, RELA_ESTATE,
+  RELA_CHECK(r->fields.empty() && r->num_add.load() == 0, RELA_ESTATE,
              "rela_replay_set_schema: schema already set or replay not empty");
   DeviceGuard g(r->device);
   for (int f = 0; f < nfields; ++f) {
@@ -780,30 +796,17 @@ extern "C" int rela_replay_set_schema_seq(rela_replay* r, int nfields, const int
     const int st = steps ? steps[f] : 1;
     RELA_CHECK(st >= 1 && row_bytes[f] % st == 0, RELA_EINVAL, "rela_replay_set_schema: field %d: %lld bytes not divisible into %d steps",
                f, (long long)row_bytes[f], st);
-    uint8_t* p = nullptr;
-    VmmRange* v = nullptr;
-    const size_t bytes = (size_t)row_bytes[f] * (size_t)r->ring;
     // chunked mode takes EVERY field, also those of one chunk: mixing the two mappings in the importer is what failed -- after
     // the 37 GB frame-stack field had been mapped from its chunks, hipIpcOpenMemHandle of the partition's 4.03 GB sequence
     // field (one hipMalloc) did not return within 90 s (profiles/r05_vmm_mixed_import_hang.log)
-    if (r->chunk_bytes > 0) {
-      v = new VmmRange();
-      hipError_t e = v->create(bytes, (size_t)r->chunk_bytes, r->device);
-      if (e != hipSuccess) {
-        set_last_error("rela_replay_set_schema: field %d: %.1f GB in chunks of %.1f GB: %s", f, (double)bytes / 1e9,
-                       (double)r->chunk_bytes / 1e9, hipGetErrorString(e));
-        v->destroy();
-        delete v;
-        return e == hipErrorOutOfMemory ? RELA_ENOMEM : RELA_ENODEV;
-      }
-      p = v->base;
-    } else {
-      RELA_HIP(hipMalloc(&p, bytes));
-    }
-    r->d_fields.push_back(p);
-    r->vmm.push_back(v);
-    r->row_bytes.push_back(row_bytes[f]);
-    r->steps.push_back(st);
+    DevRange d;
+    char what[32];
+    snprintf(what, sizeof(what), "field %d:", f);
+    if (int rc = create_range(r, &d, (size_t)row_bytes[f] * (size_t)r->ring, "rela_replay_set_schema", what)) return rc;
+    r->fields.push_back(d);
+    r->sc.row_bytes.push_back(row_bytes[f]);
+    r->sc.steps.push_back(st);
+    r->sc.nfields += 1;
   }
   return RELA_OK;
 }
@@ -814,33 +817,15 @@ static int dedup_alloc_units(rela_replay* r, int64_t unit_bytes, int units_per_s
                              int64_t guard_units, const char* who) {
   DeviceGuard g(r->device);
   std::lock_guard<std::mutex> lk(r->m);
-  r->dd_ups = units_per_stack;
-  r->dd_unit_bytes = unit_bytes;
+  r->sc.dd_ups = units_per_stack;
+  r->sc.dd_unit_bytes = unit_bytes;
   r->dd_units_per_slot = units_per_slot;
   r->dd_cap = (int64_t)r->ring * units_per_slot + guard_units;
   RELA_CHECK(r->dd_cap < ((int64_t)1 << 31), RELA_EINVAL, "%s: unit ring too large", who);
-  const size_t unit_ring_bytes = (size_t)r->dd_cap * (size_t)unit_bytes;
-  if (r->chunk_bytes > 0) {  // exported like the field arrays (vmm_field.h)
-    r->vmm_units = new VmmRange();
-    hipError_t e = r->vmm_units->create(unit_ring_bytes, (size_t)r->chunk_bytes, r->device);
-    if (e != hipSuccess) {
-      set_last_error("%s: unit ring of %.1f GB in chunks of %.1f GB: %s", who, (double)unit_ring_bytes / 1e9,
-                     (double)r->chunk_bytes / 1e9, hipGetErrorString(e));
-      r->vmm_units->destroy();
-      delete r->vmm_units;
-      r->vmm_units = nullptr;
-      r->dd_ups = 0;
-      return e == hipErrorOutOfMemory ? RELA_ENOMEM : RELA_ENODEV;
-    }
-    r->d_units = r->vmm_units->base;
-  } else {
-    const hipError_t e = hipMalloc(&r->d_units, unit_ring_bytes);
-    if (e != hipSuccess) {
-      set_last_error("%s: unit ring of %.1f GB: %s", who, (double)unit_ring_bytes / 1e9, hipGetErrorString(e));
-      r->d_units = nullptr;
-      r->dd_ups = 0;
-      return e == hipErrorOutOfMemory ? RELA_ENOMEM : RELA_ENODEV;
-    }
+  if (int rc = create_range(r, &r->units, (size_t)r->dd_cap * (size_t)unit_bytes, who, "unit ring of")) {
+    r->units.base = nullptr;
+    r->sc.dd_ups = 0;
+    return rc;
   }
   r->dd_slot_min.assign((size_t)r->ring, 0);
   return RELA_OK;
@@ -859,8 +844,8 @@ extern "C" int rela_replay_set_schema_dedup(rela_replay* r, int nfields, const i
   rb[field_a] = rb[field_b] = (int64_t)sizeof(int32_t) * units_per_stack;  // references instead of frames
   int rc = rela_replay_set_schema_seq(r, nfields, rb.data(), nullptr);
   if (rc != RELA_OK) return rc;
-  r->dd_field[0] = field_a;
-  r->dd_field[1] = field_b;
+  r->sc.dd_field[0] = field_a;
+  r->sc.dd_field[1] = field_b;
   return dedup_alloc_units(r, unit_bytes, units_per_stack, 1, guard_units, "rela_replay_set_schema_dedup");
 }
 
@@ -877,15 +862,15 @@ extern "C" int rela_replay_set_schema_seq_dedup(rela_replay* r, int nfields, con
   rb[field] = (int64_t)sizeof(int32_t) * units_per_stack * steps[field];  // [T][units_per_stack] references
   int rc = rela_replay_set_schema_seq(r, nfields, rb.data(), steps);
   if (rc != RELA_OK) return rc;
-  r->dd_field[0] = field;
-  r->dd_field[1] = -1;
-  r->dd_steps = steps[field];
+  r->sc.dd_field[0] = field;
+  r->sc.dd_field[1] = -1;
+  r->sc.dd_steps = steps[field];
   return dedup_alloc_units(r, unit_bytes, units_per_stack, units_per_slot, guard_units, "rela_replay_set_schema_seq_dedup");
 }
 
 extern "C" int rela_replay_units_reserve(rela_replay* r, int count, int nonblocking, int64_t* first_seq,
                                          int32_t* first_index) {
-  RELA_CHECK(r && r->dd_ups > 0 && count > 0 && first_seq, RELA_EINVAL, "rela_replay_units_reserve: bad arguments");
+  RELA_CHECK(r && r->sc.dd_ups > 0 && count > 0 && first_seq, RELA_EINVAL, "rela_replay_units_reserve: bad arguments");
   RELA_CHECK(count <= r->dd_cap, RELA_EINVAL, "rela_replay_units_reserve: %d units exceed the unit ring", count);
   std::unique_lock<std::mutex> lk(r->m);
   // a unit may be overwritten only when no live (or reserved) slot refers to it: FIFO order makes the slot at
@@ -908,7 +893,7 @@ extern "C" int rela_replay_units_reserve(rela_replay* r, int count, int nonblock
 
 extern "C" int rela_replay_units_write(rela_replay* r, int64_t first_seq, int count, const void* src_dev,
                                        int64_t src_pitch, void* stream_) {
-  RELA_CHECK(r && r->dd_ups > 0 && count > 0 && src_dev && src_pitch >= r->dd_unit_bytes && src_pitch % 16 == 0 &&
+  RELA_CHECK(r && r->sc.dd_ups > 0 && count > 0 && src_dev && src_pitch >= r->sc.dd_unit_bytes && src_pitch % 16 == 0 &&
                  first_seq >= 0 && first_seq + count <= r->dd_next_seq && ((uintptr_t)src_dev & 15) == 0,
              RELA_EINVAL, "rela_replay_units_write: bad arguments");
   hipStream_t producer = (hipStream_t)stream_;
@@ -917,11 +902,9 @@ extern "C" int rela_replay_units_write(rela_replay* r, int64_t first_seq, int co
   RELA_HIP(hipEventRecord(r->ev_in, producer));
   RELA_HIP(hipStreamWaitEvent(r->stream, r->ev_in, 0));
   {
-    const int64_t nv = r->dd_unit_bytes >> 4;
-    const int gx = (int)std::min<int64_t>(std::max<int64_t>(1, (nv + kThreads - 1) / kThreads), 64);
     ProfScope prof("replay_scatter_rows", r->stream);
-    hipLaunchKernelGGL(replay_units_write, dim3(gx, std::min(count, 32768)), dim3(kThreads), 0, r->stream,
-                       (const uint8_t*)src_dev, src_pitch, r->d_units, r->dd_unit_bytes, r->dd_cap, first_seq, count);
+    hipLaunchKernelGGL(replay_units_write, dim3(grid_x(r->sc.dd_unit_bytes >> 4), std::min(count, 32768)), dim3(kThreads), 0, r->stream,
+                       (const uint8_t*)src_dev, src_pitch, r->units.base, r->sc.dd_unit_bytes, r->dd_cap, first_seq, count);
   }
   RELA_LAUNCH_CHECK();
   RELA_HIP(hipEventRecord(r->ev_out, r->stream));
@@ -930,7 +913,7 @@ extern "C" int rela_replay_units_write(rela_replay* r, int64_t first_seq, int co
 }
 
 extern "C" int rela_replay_set_block_min_unit(rela_replay* r, int first_slot, int n, int64_t min_seq) {
-  RELA_CHECK(r && r->dd_ups > 0 && n > 0 && first_slot >= 0 && first_slot < r->ring && n <= r->ring, RELA_EINVAL,
+  RELA_CHECK(r && r->sc.dd_ups > 0 && n > 0 && first_slot >= 0 && first_slot < r->ring && n <= r->ring, RELA_EINVAL,
              "rela_replay_set_block_min_unit: bad arguments");
   std::lock_guard<std::mutex> lk(r->m);
   // units_reserve protects the units the live slots declare (dd_slot_min); units a producer has stored AHEAD of the
@@ -948,16 +931,75 @@ extern "C" int rela_replay_set_block_min_unit(rela_replay* r, int first_slot, in
 extern "C" int rela_replay_dedup_info(const rela_replay* r, int* units_per_stack, int64_t* unit_bytes,
                                       int64_t* unit_capacity) {
   RELA_CHECK(r, RELA_EINVAL, "rela_replay_dedup_info: bad arguments");
-  if (units_per_stack) *units_per_stack = r->dd_ups;
-  if (unit_bytes) *unit_bytes = r->dd_unit_bytes;
+  if (units_per_stack) *units_per_stack = r->sc.dd_ups;
+  if (unit_bytes) *unit_bytes = r->sc.dd_unit_bytes;
   if (unit_capacity) *unit_capacity = r->dd_cap;
   return RELA_OK;
 }
 
-extern "C" int rela_replay_dedup_steps(const rela_replay* r) { return r && r->dd_ups > 0 ? r->dd_steps : 0; }
+extern "C" int rela_replay_dedup_steps(const rela_replay* r) { return r && r->sc.dd_ups > 0 ? r->sc.dd_steps : 0; }
 
-static inline int vec16_ok(const void* a, const void* b, int64_t row_bytes) {
-  return ((row_bytes & 15) == 0) && (((uintptr_t)a & 15) == 0) && (((uintptr_t)b & 15) == 0);
+// a field of few bytes per row joins the ONE launch that moves all of those (SmallFields); false: it is a large field
+static inline bool push_small(SmallFields& t, const uint8_t* src, uint8_t* dst, int64_t rb) {
+  if (rb <= kSmallRowBytes && t.n < kMaxSmallFields) {
+    t.src[t.n] = src;
+    t.dst[t.n] = dst;
+    t.row_bytes[t.n] = (int32_t)rb;
+    t.n += 1;
+    return true;
+  }
+  return false;
+}
+
+// How the rows of a sampled batch leave a partition, local (rela_replay_sample) or mapped from another process
+// (rela_replay_remote_gather): the small fields in the caller's one launch, the large ones in one replay_gather_big.
+// De-duplicated stack fields are in neither table: the callers rebuild them from the unit ring.
+struct GatherPlan {
+  SmallFields small{};
+  BigFields big{};
+  int nbig = 0;
+  dim3 grid;  // of replay_gather_big
+};
+// out_rows_dev[f] = NULL skips field f; the batch is rows [out_offset, out_offset + batch) of outputs with out_batch rows
+// per (time) step (0, 0: the outputs hold exactly this batch)
+static int plan_gather(GatherPlan* p, const ReplaySchema& sc, const DevRange* fields, void* const* out_rows_dev, int batch,
+                       int out_batch, int out_offset, const char* who) {
+  int max_y = 1;
+  int64_t max_units = 1;
+  p->big.out_batch = out_batch, p->big.out_off = out_offset;
+  for (int f = 0; f < sc.nfields; ++f) {
+    if (!out_rows_dev[f]) continue;
+    const int64_t rb = sc.row_bytes[f];
+    const int st = sc.steps[f];
+    if (sc.is_stack(f)) {
+      RELA_CHECK(((uintptr_t)out_rows_dev[f] & 15) == 0, RELA_EINVAL, "%s: unaligned stack output", who);
+      continue;
+    }
+    if (st == 1 && push_small(p->small, fields[f].base, (uint8_t*)out_rows_dev[f], rb)) continue;
+    RELA_CHECK(p->nbig < kMaxBigFields, RELA_EINVAL, "%s: more than %d large fields", who, kMaxBigFields);
+    const int64_t sub = rb / st;
+    const int v16 = vec16_ok(out_rows_dev[f], fields[f].base, sub) && (rb % 16 == 0);
+    p->big.field[p->nbig] = fields[f].base;
+    p->big.out[p->nbig] = (uint8_t*)out_rows_dev[f];
+    p->big.slot_bytes[p->nbig] = rb;
+    p->big.steps[p->nbig] = st;
+    p->big.vec16[p->nbig] = v16;
+    max_units = std::max<int64_t>(max_units, v16 ? (sub >> 4) : sub);
+    max_y = std::max(max_y, batch * st);
+    p->nbig += 1;
+  }
+  p->grid = dim3(grid_x(max_units), std::min(max_y, 32768), p->nbig);
+  return RELA_OK;
+}
+static void launch_gather_big(const GatherPlan& p, const int32_t* ids, int batch, hipStream_t s) {  // (p.nbig > 0)
+  hipLaunchKernelGGL(replay_gather_big, p.grid, dim3(kThreads), 0, s, p.big, ids, batch);
+}
+// the stacks of one field of a transition schema out of the unit ring: rows [out_offset, out_offset + batch) of `out`
+static void launch_gather_dedup(const ReplaySchema& sc, const uint8_t* refs, const uint8_t* units, const int32_t* ids,
+                                void* out, int batch, int out_offset, hipStream_t s) {
+  uint8_t* o = (uint8_t*)out + (int64_t)out_offset * sc.dd_ups * sc.dd_unit_bytes;
+  hipLaunchKernelGGL(replay_gather_dedup, dim3(grid_x(sc.dd_unit_bytes >> 4), std::min(batch * sc.dd_ups, 32768)),
+                     dim3(kThreads), 0, s, (const int32_t*)refs, ids, units, sc.dd_unit_bytes, sc.dd_ups, o, batch);
 }
 
 // (caller holds r->m) Opens a row copy of `count` slots from `start` on the copy stream: ordered after the producer's
@@ -995,7 +1037,7 @@ extern "C" int rela_replay_begin_add(rela_replay* r, int n, int nonblocking, int
     if (r->shut) return RELA_EWOULDBLOCK;
   }
   *first_slot = r->tail;
-  if (r->dd_ups > 0) {  // until the producer declares it (set_block_min_unit): nothing older than the guard window
+  if (r->sc.dd_ups > 0) {  // until the producer declares it (set_block_min_unit): nothing older than the guard window
     const int64_t lo = r->dd_next_seq - (r->dd_cap - r->ring * r->dd_units_per_slot);
     for (int i = 0; i < n; ++i) r->dd_slot_min[(size_t)((r->tail + i) % r->ring)] = lo;
   }
@@ -1008,7 +1050,7 @@ extern "C" int rela_replay_write_rows(rela_replay* r, int first_slot, int offset
                                       const void* const* rows_dev, void* stream_) {
   RELA_CHECK(r && count > 0 && offset >= 0 && first_slot >= 0 && first_slot < r->ring, RELA_EINVAL,
              "rela_replay_write_rows: bad arguments");
-  RELA_CHECK(r->d_fields.empty() || rows_dev, RELA_EINVAL, "rela_replay_write_rows: rows_dev is NULL");
+  RELA_CHECK(r->fields.empty() || rows_dev, RELA_EINVAL, "rela_replay_write_rows: rows_dev is NULL");
   hipStream_t producer = (hipStream_t)stream_;
   DeviceGuard g(r->device);
   std::lock_guard<std::mutex> lk(r->m);
@@ -1020,23 +1062,15 @@ extern "C" int rela_replay_write_rows(rela_replay* r, int first_slot, int offset
     if (rc != RELA_OK) return rc;
   }
   SmallFields small{};
-  for (size_t f = 0; f < r->d_fields.size(); ++f) {
+  for (size_t f = 0; f < r->fields.size(); ++f) {
     if (!rows_dev[f]) continue;
-    const int64_t rb = r->row_bytes[f];
-    if (rb <= kSmallRowBytes && small.n < kMaxSmallFields) {
-      small.src[small.n] = (const uint8_t*)rows_dev[f];
-      small.dst[small.n] = r->d_fields[f];
-      small.row_bytes[small.n] = (int32_t)rb;
-      small.n += 1;
-      continue;
-    }
-    const int v16 = vec16_ok(rows_dev[f], r->d_fields[f], rb);
-    const int64_t units = v16 ? (rb >> 4) : rb;
-    int gx = (int)std::min<int64_t>(std::max<int64_t>(1, (units + kThreads - 1) / kThreads), 64);
+    const int64_t rb = r->sc.row_bytes[f];
+    if (push_small(small, (const uint8_t*)rows_dev[f], r->fields[f].base, rb)) continue;
+    const int v16 = vec16_ok(rows_dev[f], r->fields[f].base, rb);
     {
       ProfScope prof("replay_scatter_rows", r->copy_stream);
-      hipLaunchKernelGGL(replay_scatter_rows, dim3(gx, std::min(count, 32768)), dim3(kThreads), 0, r->copy_stream,
-                         (const uint8_t*)rows_dev[f], r->d_fields[f], rb, count, r->ring, start, v16);
+      hipLaunchKernelGGL(replay_scatter_rows, dim3(grid_x(v16 ? (rb >> 4) : rb), std::min(count, 32768)), dim3(kThreads), 0,
+                         r->copy_stream, (const uint8_t*)rows_dev[f], r->fields[f].base, rb, count, r->ring, start, v16);
     }
   }
   if (small.n > 0) {
@@ -1060,22 +1094,57 @@ extern "C" int rela_replay_write_rows_gather(rela_replay* r, int first_slot, int
     const int rc = copy_begin(r, producer, first_slot, count);
     if (rc != RELA_OK) return rc;
   }
-  for (size_t f = 0; f < r->d_fields.size(); ++f) {
+  for (size_t f = 0; f < r->fields.size(); ++f) {
     if (!bases_dev[f]) continue;
     RELA_CHECK(src_index_dev[f], RELA_EINVAL, "rela_replay_write_rows_gather: field %d has no source index", (int)f);
-    const int64_t rb = r->row_bytes[f];
-    const int v16 = vec16_ok(bases_dev[f], r->d_fields[f], rb);
-    const int64_t units = v16 ? (rb >> 4) : rb;
-    int gx = (int)std::min<int64_t>(std::max<int64_t>(1, (units + kThreads - 1) / kThreads), 64);
+    const int64_t rb = r->sc.row_bytes[f];
+    const int v16 = vec16_ok(bases_dev[f], r->fields[f].base, rb);
     {
       ProfScope prof("replay_scatter_rows", r->copy_stream);
-      hipLaunchKernelGGL(replay_scatter_rows_indexed, dim3(gx, std::min(count, 32768)), dim3(kThreads), 0, r->copy_stream,
-                         (const uint8_t*)bases_dev[f], src_index_dev[f], dst_offset_dev, r->d_fields[f], rb, count,
-                         r->ring, first_slot, v16);
+      hipLaunchKernelGGL(replay_scatter_rows_indexed, dim3(grid_x(v16 ? (rb >> 4) : rb), std::min(count, 32768)),
+                         dim3(kThreads), 0, r->copy_stream, (const uint8_t*)bases_dev[f], src_index_dev[f], dst_offset_dev,
+                         r->fields[f].base, rb, count, r->ring, first_slot, v16);
     }
   }
   RELA_LAUNCH_CHECK();
   return copy_end(r, producer);
+}
+
+// (caller holds r->m) blockAppend's arithmetic for the n slots from first_slot, on the replay's stream.  Large grouped
+// blocks (a batched shard's tick): parallel pow + ordered sums; the single-workgroup kernel otherwise (an ungrouped block
+// is ONE float sum over all its rows: nothing to parallelise but the pow, and small blocks gain nothing from a second
+// launch)
+static int launch_append(rela_replay* r, const float* prio, int n, int first_slot, int group_rows) {
+  if (group_rows > 0 && n >= 1024) {
+    if (r->tmpw_cap < n) {
+      RELA_HIP(hipStreamSynchronize(r->stream));
+      (void)hipFree(r->d_tmpw);
+      r->d_tmpw = nullptr;
+      r->tmpw_cap = 0;
+      RELA_HIP(hipMalloc(&r->d_tmpw, sizeof(float) * (size_t)n));
+      r->tmpw_cap = n;
+    }
+    ProfScope prof("replay_append_weights", r->stream);
+    hipLaunchKernelGGL(replay_append_pow, dim3((n + 255) / 256), dim3(256), 0, r->stream, prio, n, r->alpha, r->d_w,
+                       r->ring, first_slot, group_rows, r->d_tmpw);
+    hipLaunchKernelGGL(replay_append_sums, dim3(1), dim3(kThreads), 0, r->stream, (const float*)r->d_tmpw, n, group_rows,
+                       r->d_state);
+  } else {
+    ProfScope prof("replay_append_weights", r->stream);
+    hipLaunchKernelGGL(replay_append_weights, dim3(1), dim3(kThreads), 0, r->stream, prio, n, r->alpha, r->d_w, r->ring,
+                       first_slot, group_rows, r->d_state);
+  }
+  RELA_LAUNCH_CHECK();
+  return RELA_OK;
+}
+
+// the block becomes visible to sample and the next block may commit (:70-73); `counted`: it holds transitions (:190)
+static void publish_block(rela_replay* r, std::unique_lock<std::mutex>& lk, int first_slot, int n, bool counted) {
+  r->safe_tail = (first_slot + n) % r->ring;
+  r->safe_size += n;
+  if (counted) r->num_add += n;
+  lk.unlock();
+  r->cv_tail.notify_all();
 }
 
 extern "C" int rela_replay_commit_add(rela_replay* r, int first_slot, int n, const float* priority_dev,
@@ -1091,41 +1160,18 @@ extern "C" int rela_replay_commit_add_grouped(rela_replay* r, int first_slot, in
   std::unique_lock<std::mutex> lk(r->m);
   r->cv_tail.wait(lk, [&] { return r->shut || r->safe_tail == first_slot; });  // in-order commit :69
   if (r->safe_tail != first_slot) return RELA_EWOULDBLOCK;  // shut down while an earlier block never committed
-  // The priorities go through a staging buffer filled on the copy stream -- behind the block's row copies, so its
-  // event also says "the rows are written" -- and the weights / sum_ update takes its turn on the replay stream;
-  // the producer waits for the staging copy only, never for the replay stream.
-  if (r->legacy_insert) {  // in-order form: the append reads the producer's buffer, the producer waits for it
+  if (!r->decoupled_insert) {  // in-order form: the append reads the producer's buffer, the producer waits for it
     RELA_HIP(hipEventRecord(r->ev_in, producer));
     RELA_HIP(hipStreamWaitEvent(r->stream, r->ev_in, 0));
-    if (group_rows > 0 && n >= 1024) {
-      if (r->tmpw_cap < n) {
-        RELA_HIP(hipStreamSynchronize(r->stream));
-        (void)hipFree(r->d_tmpw);
-        r->d_tmpw = nullptr;
-        r->tmpw_cap = 0;
-        RELA_HIP(hipMalloc(&r->d_tmpw, sizeof(float) * (size_t)n));
-        r->tmpw_cap = n;
-      }
-      ProfScope prof("replay_append_weights", r->stream);
-      hipLaunchKernelGGL(replay_append_pow, dim3((n + 255) / 256), dim3(256), 0, r->stream, priority_dev, n, r->alpha,
-                         r->d_w, r->ring, first_slot, group_rows, r->d_tmpw);
-      hipLaunchKernelGGL(replay_append_sums, dim3(1), dim3(kThreads), 0, r->stream, (const float*)r->d_tmpw, n,
-                         group_rows, r->d_state);
-    } else {
-      ProfScope prof("replay_append_weights", r->stream);
-      hipLaunchKernelGGL(replay_append_weights, dim3(1), dim3(kThreads), 0, r->stream, priority_dev, n, r->alpha,
-                         r->d_w, r->ring, first_slot, group_rows, r->d_state);
-    }
-    RELA_LAUNCH_CHECK();
+    if (int rc = launch_append(r, priority_dev, n, first_slot, group_rows)) return rc;
     RELA_HIP(hipEventRecord(r->ev_out, r->stream));
     RELA_HIP(hipStreamWaitEvent(producer, r->ev_out, 0));
-    r->safe_tail = (first_slot + n) % r->ring;
-    r->safe_size += n;
-    r->num_add += n;
-    lk.unlock();
-    r->cv_tail.notify_all();
+    publish_block(r, lk, first_slot, n, true);
     return RELA_OK;
   }
+  // Decoupled form: the priorities go through a staging buffer filled on the copy stream -- behind the block's row
+  // copies, so its event also says "the rows are written" -- and the weights / sum_ update takes its turn on the
+  // replay stream; the producer waits for the staging copy only, never for the replay stream.
   const int k = r->pstage_next;
   r->pstage_next = (k + 1) % rela_replay::kPrioStages;
   if (r->pstage_used[k]) RELA_HIP(hipStreamWaitEvent(r->copy_stream, r->ev_done[k], 0));  // its last reader finished
@@ -1146,37 +1192,10 @@ extern "C" int rela_replay_commit_add_grouped(rela_replay* r, int first_slot, in
   RELA_HIP(hipEventRecord(r->ev_stage[k], r->copy_stream));
   RELA_HIP(hipStreamWaitEvent(producer, r->ev_stage[k], 0));
   RELA_HIP(hipStreamWaitEvent(r->stream, r->ev_stage[k], 0));
-  const float* staged = r->d_pstage[k];
-  // large grouped blocks (a batched shard's tick): parallel pow + ordered sums; the single-workgroup kernel otherwise
-  // (an ungrouped block is ONE float sum over all its rows: nothing to parallelise but the pow, and small blocks
-  // gain nothing from a second launch)
-  if (group_rows > 0 && n >= 1024) {
-    if (r->tmpw_cap < n) {
-      RELA_HIP(hipStreamSynchronize(r->stream));
-      (void)hipFree(r->d_tmpw);
-      r->d_tmpw = nullptr;
-      r->tmpw_cap = 0;
-      RELA_HIP(hipMalloc(&r->d_tmpw, sizeof(float) * (size_t)n));
-      r->tmpw_cap = n;
-    }
-    ProfScope prof("replay_append_weights", r->stream);
-    hipLaunchKernelGGL(replay_append_pow, dim3((n + 255) / 256), dim3(256), 0, r->stream, staged, n, r->alpha,
-                       r->d_w, r->ring, first_slot, group_rows, r->d_tmpw);
-    hipLaunchKernelGGL(replay_append_sums, dim3(1), dim3(kThreads), 0, r->stream, (const float*)r->d_tmpw, n,
-                       group_rows, r->d_state);
-  } else {
-    ProfScope prof("replay_append_weights", r->stream);
-    hipLaunchKernelGGL(replay_append_weights, dim3(1), dim3(kThreads), 0, r->stream, staged, n, r->alpha,
-                       r->d_w, r->ring, first_slot, group_rows, r->d_state);
-  }
-  RELA_LAUNCH_CHECK();
+  if (int rc = launch_append(r, r->d_pstage[k], n, first_slot, group_rows)) return rc;
   RELA_HIP(hipEventRecord(r->ev_done[k], r->stream));
   r->pstage_used[k] = true;
-  r->safe_tail = (first_slot + n) % r->ring;  // :70-73
-  r->safe_size += n;
-  r->num_add += n;  // :190
-  lk.unlock();
-  r->cv_tail.notify_all();
+  publish_block(r, lk, first_slot, n, true);
   return RELA_OK;
 }
 
@@ -1193,21 +1212,18 @@ extern "C" int rela_replay_abort_add(rela_replay* r, int first_slot, int n) {
   const int first_part = std::min(n, r->ring - first_slot);
   RELA_HIP(hipMemsetAsync(r->d_w + first_slot, 0, sizeof(float) * (size_t)first_part, r->stream));
   if (n > first_part) RELA_HIP(hipMemsetAsync(r->d_w, 0, sizeof(float) * (size_t)(n - first_part), r->stream));
-  r->safe_tail = (first_slot + n) % r->ring;
-  r->safe_size += n;
-  lk.unlock();
-  r->cv_tail.notify_all();
+  publish_block(r, lk, first_slot, n, false);
   return RELA_OK;
 }
 
 extern "C" int rela_replay_add(rela_replay* r, int n, const void* const* rows_dev, const float* priority_dev,
                                int nonblocking, void* stream_) {
   RELA_CHECK(r && n > 0 && priority_dev, RELA_EINVAL, "rela_replay_add: bad arguments");
-  RELA_CHECK(r->d_fields.empty() || rows_dev, RELA_EINVAL, "rela_replay_add: rows_dev is NULL");
+  RELA_CHECK(r->fields.empty() || rows_dev, RELA_EINVAL, "rela_replay_add: rows_dev is NULL");
   int slot = 0;
   int rc = rela_replay_begin_add(r, n, nonblocking, &slot);
   if (rc != RELA_OK) return rc;
-  if (!r->d_fields.empty()) {
+  if (!r->fields.empty()) {
     rc = rela_replay_write_rows(r, slot, 0, n, rows_dev, stream_);
     if (rc != RELA_OK) {
       (void)rela_replay_abort_add(r, slot, n);
@@ -1274,69 +1290,32 @@ extern "C" int rela_replay_sample(rela_replay* r, int batch, void* const* out_ro
     r->size -= n_pop;
     r->safe_size -= n_pop;
   }
-  SmallFields small{};
-  BigFields big{};
-  int nbig = 0, max_y = 1;
-  int64_t max_units = 1;
-  if (out_rows_dev) {
-    for (size_t f = 0; f < r->d_fields.size(); ++f) {
-      if (!out_rows_dev[f]) continue;
-      const int64_t rb = r->row_bytes[f];
-      const int st = r->steps[f];
-      if (r->dd_ups > 0 && ((int)f == r->dd_field[0] || (int)f == r->dd_field[1])) continue;  // rebuilt below
-      if (st == 1 && rb <= kSmallRowBytes && small.n < kMaxSmallFields) {
-        small.src[small.n] = r->d_fields[f];
-        small.dst[small.n] = (uint8_t*)out_rows_dev[f];
-        small.row_bytes[small.n] = (int32_t)rb;
-        small.n += 1;
-        continue;
-      }
-      RELA_CHECK(nbig < kMaxBigFields, RELA_EINVAL, "rela_replay_sample: more than %d large fields", kMaxBigFields);
-      const int64_t sub = rb / st;
-      const int v16 = vec16_ok(out_rows_dev[f], r->d_fields[f], sub) && (rb % 16 == 0);
-      big.field[nbig] = r->d_fields[f];
-      big.out[nbig] = (uint8_t*)out_rows_dev[f];
-      big.slot_bytes[nbig] = rb;
-      big.steps[nbig] = st;
-      big.vec16[nbig] = v16;
-      max_units = std::max<int64_t>(max_units, v16 ? (sub >> 4) : sub);
-      max_y = std::max(max_y, batch * st);
-      nbig += 1;
-    }
-  }
+  GatherPlan plan;
+  if (out_rows_dev)
+    if (int rc = plan_gather(&plan, r->sc, r->fields.data(), out_rows_dev, batch, 0, 0, "rela_replay_sample")) return rc;
   {
     ProfScope prof("replay_finish", r->stream);
-    hipLaunchKernelGGL(replay_finish, dim3(1 + small.n), dim3(1024), 0, r->stream, (const float*)r->d_raw_w, batch,
-                       (float)full_size, r->beta, (const ReplayDevState*)r->d_state, out_weight_dev, small,
+    hipLaunchKernelGGL(replay_finish, dim3(1 + plan.small.n), dim3(1024), 0, r->stream, (const float*)r->d_raw_w, batch,
+                       (float)full_size, r->beta, (const ReplayDevState*)r->d_state, out_weight_dev, plan.small,
                        (const int32_t*)r->d_ids);
   }
-  if (out_rows_dev && r->dd_ups > 0 && r->dd_steps > 0 && out_rows_dev[r->dd_field[0]]) {  // [T][B] stacks of sequences
-    const int f = r->dd_field[0];
-    RELA_CHECK(((uintptr_t)out_rows_dev[f] & 15) == 0, RELA_EINVAL, "rela_replay_sample: unaligned stack output");
-    const int64_t rows = (int64_t)batch * r->dd_steps;
+  if (out_rows_dev && r->sc.dd_ups > 0 && r->sc.dd_steps > 0 && out_rows_dev[r->sc.dd_field[0]]) {  // [T][B] stacks of sequences
+    const int f = r->sc.dd_field[0];
+    const int64_t rows = (int64_t)batch * r->sc.dd_steps;
     ProfScope prof("replay_gather_rows", r->stream);
     hipLaunchKernelGGL(replay_gather_seq_dedup, dim3((unsigned)std::min<int64_t>(rows, 1 << 20)), dim3(kThreads), 0, r->stream,
-                       (const int32_t*)r->d_fields[f], (const int32_t*)r->d_ids, (const uint8_t*)r->d_units,
-                       r->dd_unit_bytes, r->dd_cap, r->dd_ups, r->dd_steps, (uint8_t*)out_rows_dev[f], batch);
+                       (const int32_t*)r->fields[f].base, (const int32_t*)r->d_ids, (const uint8_t*)r->units.base,
+                       r->sc.dd_unit_bytes, r->dd_cap, r->sc.dd_ups, r->sc.dd_steps, (uint8_t*)out_rows_dev[f], batch);
   }
-  if (out_rows_dev && r->dd_ups > 0 && r->dd_steps == 0) {
-    for (int q = 0; q < 2; ++q) {
-      const int f = r->dd_field[q];
-      if (!out_rows_dev[f]) continue;
-      RELA_CHECK(((uintptr_t)out_rows_dev[f] & 15) == 0, RELA_EINVAL, "rela_replay_sample: unaligned stack output");
-      const int64_t nv = r->dd_unit_bytes >> 4;
-      const int gx = (int)std::min<int64_t>(std::max<int64_t>(1, (nv + kThreads - 1) / kThreads), 64);
-      ProfScope prof("replay_gather_rows", r->stream);
-      hipLaunchKernelGGL(replay_gather_dedup, dim3(gx, std::min(batch * r->dd_ups, 32768)), dim3(kThreads), 0, r->stream,
-                         (const int32_t*)r->d_fields[f], (const int32_t*)r->d_ids, (const uint8_t*)r->d_units,
-                         r->dd_unit_bytes, r->dd_ups, (uint8_t*)out_rows_dev[f], batch);
-    }
-  }
-  if (nbig > 0) {
-    const int gx = (int)std::min<int64_t>(std::max<int64_t>(1, (max_units + kThreads - 1) / kThreads), 64);
+  for (int q = 0; q < 2 && out_rows_dev && r->sc.dd_ups > 0 && r->sc.dd_steps == 0; ++q) {
+    const int f = r->sc.dd_field[q];
+    if (!out_rows_dev[f]) continue;
     ProfScope prof("replay_gather_rows", r->stream);
-    hipLaunchKernelGGL(replay_gather_big, dim3(gx, std::min(max_y, 32768), nbig), dim3(kThreads), 0, r->stream, big,
-                       (const int32_t*)r->d_ids, batch);
+    launch_gather_dedup(r->sc, r->fields[f].base, r->units.base, r->d_ids, out_rows_dev[f], batch, 0, r->stream);
+  }
+  if (plan.nbig > 0) {
+    ProfScope prof("replay_gather_rows", r->stream);
+    launch_gather_big(plan, r->d_ids, batch, r->stream);
   }
   RELA_LAUNCH_CHECK();
   if (n_pop > 0) {  // the slots just evicted may be read by the gathers above until this point of the stream
@@ -1412,7 +1391,7 @@ extern "C" int rela_replay_set_decoupled_insert(rela_replay* r, int on) {
   std::unique_lock<std::mutex> lk(r->m);
   RELA_HIP(hipStreamSynchronize(r->copy_stream));
   RELA_HIP(hipStreamSynchronize(r->stream));
-  r->legacy_insert = on == 0;
+  r->decoupled_insert = on != 0;
   r->copy_stream = on ? r->copy_stream_own : r->stream;
   return RELA_OK;
 }
@@ -1508,14 +1487,14 @@ extern "C" int rela_replay_debug_weights(rela_replay* r, float* weights_host, ui
 }
 
 extern "C" int rela_replay_debug_read_rows(rela_replay* r, int field, int slot, int count, void* rows_host) {
-  RELA_CHECK(r && rows_host && field >= 0 && field < (int)r->d_fields.size() && slot >= 0 && count >= 0 &&
+  RELA_CHECK(r && rows_host && field >= 0 && field < (int)r->fields.size() && slot >= 0 && count >= 0 &&
                  slot + count <= r->ring,
              RELA_EINVAL, "rela_replay_debug_read_rows: bad arguments");
   DeviceGuard g(r->device);
   std::lock_guard<std::mutex> lk(r->m);
-  const size_t rb = (size_t)r->row_bytes[field];
+  const size_t rb = (size_t)r->sc.row_bytes[field];
   RELA_HIP(hipStreamSynchronize(r->copy_stream));
-  RELA_HIP(hipMemcpyAsync(rows_host, r->d_fields[field] + (size_t)slot * rb, rb * (size_t)count, hipMemcpyDeviceToHost,
+  RELA_HIP(hipMemcpyAsync(rows_host, r->fields[field].base + (size_t)slot * rb, rb * (size_t)count, hipMemcpyDeviceToHost,
                           r->stream));
   RELA_HIP(hipStreamSynchronize(r->stream));
   return RELA_OK;
@@ -1551,16 +1530,10 @@ extern "C" int rela_debug_pow(const float* x_dev, int n, float exponent, float* 
 // =====================================================================================================================
 struct rela_replay_remote {
   int device = 0;
-  int nfields = 0, ring = 0, max_batch = 0;
-  int64_t row_bytes[RELA_IPC_MAX_FIELDS] = {};
-  int32_t steps[RELA_IPC_MAX_FIELDS] = {};
-  uint8_t* fields[RELA_IPC_MAX_FIELDS] = {};
-  VmmRange* vmm[RELA_IPC_MAX_FIELDS] = {};  // fields that arrived as chunks (fields[f] = vmm[f]->base)
-  // de-duplicated partition: the two stack fields hold references into the owner's unit ring
-  int dd_ups = 0, dd_field[2] = {-1, -1};
-  int64_t dd_unit_bytes = 0;
-  uint8_t* units = nullptr;
-  VmmRange* vmm_units = nullptr;
+  int ring = 0, max_batch = 0;
+  ReplaySchema sc;  // from the descriptor
+  DevRange fields[RELA_IPC_MAX_FIELDS];
+  DevRange units;  // de-duplicated partition: the two stack fields hold references into the owner's unit ring
   int32_t* ids = nullptr;
   float* raw_w = nullptr;
   ReplayDevState* state = nullptr;
@@ -1569,19 +1542,19 @@ struct rela_replay_remote {
 // `chunks` == nullptr: the plain descriptor (every field one hipIpcMemHandle_t)
 static int export_partition(rela_replay* r, rela_replay_ipc_desc* out, rela_replay_chunk_desc* chunks, int* fds_out,
                             int max_fds, const char* who) {
-  RELA_CHECK(!r->d_fields.empty() && (int)r->d_fields.size() <= RELA_IPC_MAX_FIELDS, RELA_ESTATE,
+  RELA_CHECK(!r->fields.empty() && (int)r->fields.size() <= RELA_IPC_MAX_FIELDS, RELA_ESTATE,
              "%s: set the schema first (at most %d fields)", who, RELA_IPC_MAX_FIELDS);
-  RELA_CHECK(r->dd_ups == 0 || r->dd_steps == 0, RELA_EINVAL,
+  RELA_CHECK(r->sc.dd_ups == 0 || r->sc.dd_steps == 0, RELA_EINVAL,
              "%s: a sequence partition with de-duplicated stacks (rela_replay_set_schema_seq_dedup) cannot be exported: "
              "its consumers would read references, not frames", who);
-  RELA_CHECK(r->dd_ups == 0 || chunks, RELA_EINVAL,
+  RELA_CHECK(r->sc.dd_ups == 0 || chunks, RELA_EINVAL,
              "%s: a de-duplicated partition needs the unit ring next to its fields; export it with rela_replay_export_chunks", who);
   static_assert(sizeof(hipIpcMemHandle_t) == 64, "handle size");
   DeviceGuard g(r->device);
   std::lock_guard<std::mutex> lk(r->m);
   memset(out, 0, sizeof(*out));
   out->abi = 1;
-  out->nfields = (int32_t)r->d_fields.size();
+  out->nfields = (int32_t)r->fields.size();
   out->ring = r->ring;
   out->device = r->device;
   out->max_batch = kMaxBatch;
@@ -1590,48 +1563,46 @@ static int export_partition(rela_replay* r, rela_replay_ipc_desc* out, rela_repl
     for (int k = 0; k < nfds; ++k) (void)::close(fds_out[k]);
     return rc;
   };
-  for (size_t f = 0; f < r->d_fields.size(); ++f) {
-    out->row_bytes[f] = r->row_bytes[f];
-    out->steps[f] = r->steps[f];
-    if (VmmRange* v = r->vmm[f]) {
-      if (!chunks) {
-        set_last_error("%s: field %d is made of %d chunks (rela_replay_set_chunk_bytes); export it with "
-                       "rela_replay_export_chunks", who, (int)f, (int)v->handles.size());
-        return RELA_EINVAL;
-      }
-      const int n = (int)v->handles.size();
-      if (nfds + n > max_fds) {
-        set_last_error("%s: more than %d chunk descriptors; use larger chunks", who, max_fds);
-        return fail(RELA_EINVAL);
-      }
-      hipError_t e = v->export_fds(fds_out + nfds);
-      if (e != hipSuccess) {
-        set_last_error("%s: hipMemExportToShareableHandle (field %d): %s", who, (int)f, hipGetErrorString(e));
-        return fail(RELA_ENODEV);
-      }
-      nfds += n;
-      chunks->field_chunks[f] = n;
-      chunks->chunk_bytes[f] = (int64_t)v->chunk;
-      chunks->mapped_bytes[f] = (int64_t)v->bytes;
-      continue;
+  // one range as the importer reads it back (DevRange::export_to); `what` names it in the messages
+  auto put = [&](const DevRange& d, const char* what, unsigned char* handle, int32_t* n, int64_t* chunk_bytes,
+                 int64_t* mapped_bytes) {
+    if (nfds + d.chunks() > max_fds) {
+      set_last_error("%s: more than %d chunk descriptors; use larger chunks", who, max_fds);
+      return fail(RELA_EINVAL);
     }
-    {
-      // r4, this pool's boxes: hipIpcOpenMemHandle of a 37 GB allocation (one frame-stack field of a 2^20-row partition)
-      // did not return within 200 s in the importing process, 18.5 GB (2^19 rows) maps in under a second: refuse loudly
-      hipDeviceptr_t base = nullptr;
-      size_t bytes = 0;
-      if (hipMemGetAddressRange(&base, &bytes, r->d_fields[f]) == hipSuccess && bytes > ((size_t)24 << 30)) {
-        set_last_error("%s: field %d is one allocation of %.1f GB; HIP IPC imports above ~24 GB do not return on this "
-                       "platform -- create the partition with rela_replay_set_chunk_bytes (or RELA_REPLAY_CHUNK_GB) and "
-                       "export it with rela_replay_export_chunks", who, (int)f, (double)bytes / 1e9);
-        return fail(RELA_EINVAL);
-      }
-    }
-    hipError_t e = hipIpcGetMemHandle(reinterpret_cast<hipIpcMemHandle_t*>(out->field_handle[f]), r->d_fields[f]);
+    const hipError_t e = d.export_to(handle, fds_out + nfds, n, chunk_bytes, mapped_bytes);
     if (e != hipSuccess) {
-      set_last_error("%s: hipIpcGetMemHandle (field %d): %s", who, (int)f, hipGetErrorString(e));
+      set_last_error("%s: %s (%s): %s", who, d.chunked ? "hipMemExportToShareableHandle" : "hipIpcGetMemHandle", what,
+                     hipGetErrorString(e));
       return fail(RELA_ENODEV);
     }
+    nfds += d.chunks();
+    return (int)RELA_OK;
+  };
+  for (int f = 0; f < r->sc.nfields; ++f) {
+    const DevRange& d = r->fields[f];
+    out->row_bytes[f] = r->sc.row_bytes[f];
+    out->steps[f] = r->sc.steps[f];
+    if (d.chunked && !chunks) {
+      set_last_error("%s: field %d is made of %d chunks (rela_replay_set_chunk_bytes); export it with "
+                     "rela_replay_export_chunks", who, f, d.chunks());
+      return RELA_EINVAL;
+    }
+    // r4, this pool's boxes: hipIpcOpenMemHandle of a 37 GB allocation (one frame-stack field of a 2^20-row partition)
+    // did not return within 200 s in the importing process, 18.5 GB (2^19 rows) maps in under a second: refuse loudly
+    hipDeviceptr_t base = nullptr;
+    size_t bytes = 0;
+    if (!d.chunked && hipMemGetAddressRange(&base, &bytes, d.base) == hipSuccess && bytes > ((size_t)24 << 30)) {
+      set_last_error("%s: field %d is one allocation of %.1f GB; HIP IPC imports above ~24 GB do not return on this "
+                     "platform -- create the partition with rela_replay_set_chunk_bytes (or RELA_REPLAY_CHUNK_GB) and "
+                     "export it with rela_replay_export_chunks", who, f, (double)bytes / 1e9);
+      return fail(RELA_EINVAL);
+    }
+    char what[32];
+    snprintf(what, sizeof(what), "field %d", f);
+    if (int rc = put(d, what, out->field_handle[f], chunks ? &chunks->field_chunks[f] : nullptr,
+                     chunks ? &chunks->chunk_bytes[f] : nullptr, chunks ? &chunks->mapped_bytes[f] : nullptr))
+      return rc;
   }
   hipError_t e = hipIpcGetMemHandle(reinterpret_cast<hipIpcMemHandle_t*>(out->ids_handle), r->d_ids);
   if (e == hipSuccess) e = hipIpcGetMemHandle(reinterpret_cast<hipIpcMemHandle_t*>(out->raw_w_handle), r->d_raw_w);
@@ -1640,33 +1611,14 @@ static int export_partition(rela_replay* r, rela_replay_ipc_desc* out, rela_repl
     set_last_error("%s: hipIpcGetMemHandle: %s", who, hipGetErrorString(e));
     return fail(RELA_ENODEV);
   }
-  if (chunks && r->dd_ups > 0) {  // the unit ring the two stack fields refer into
-    chunks->dd_ups = r->dd_ups;
-    chunks->dd_field[0] = r->dd_field[0], chunks->dd_field[1] = r->dd_field[1];
-    chunks->dd_unit_bytes = r->dd_unit_bytes;
+  if (chunks && r->sc.dd_ups > 0) {  // the unit ring the two stack fields refer into
+    chunks->dd_ups = r->sc.dd_ups;
+    chunks->dd_field[0] = r->sc.dd_field[0], chunks->dd_field[1] = r->sc.dd_field[1];
+    chunks->dd_unit_bytes = r->sc.dd_unit_bytes;
     chunks->dd_cap = r->dd_cap;
-    if (VmmRange* v = r->vmm_units) {
-      const int n = (int)v->handles.size();
-      if (nfds + n > max_fds) {
-        set_last_error("%s: more than %d chunk descriptors; use larger chunks", who, max_fds);
-        return fail(RELA_EINVAL);
-      }
-      e = v->export_fds(fds_out + nfds);
-      if (e != hipSuccess) {
-        set_last_error("%s: hipMemExportToShareableHandle (unit ring): %s", who, hipGetErrorString(e));
-        return fail(RELA_ENODEV);
-      }
-      nfds += n;
-      chunks->units_chunks = n;
-      chunks->units_chunk_bytes = (int64_t)v->chunk;
-      chunks->units_mapped_bytes = (int64_t)v->bytes;
-    } else {
-      e = hipIpcGetMemHandle(reinterpret_cast<hipIpcMemHandle_t*>(chunks->units_handle), r->d_units);
-      if (e != hipSuccess) {
-        set_last_error("%s: hipIpcGetMemHandle (unit ring): %s", who, hipGetErrorString(e));
-        return fail(RELA_ENODEV);
-      }
-    }
+    if (int rc = put(r->units, "unit ring", chunks->units_handle, &chunks->units_chunks, &chunks->units_chunk_bytes,
+                     &chunks->units_mapped_bytes))
+      return rc;
   }
   if (chunks) chunks->nfds = nfds;
   return RELA_OK;
@@ -1691,7 +1643,10 @@ static int import_partition(rela_replay_remote** out, const rela_replay_ipc_desc
   DeviceGuard g(device);
   auto* rr = new rela_replay_remote();
   rr->device = device;
-  rr->nfields = desc->nfields, rr->ring = desc->ring, rr->max_batch = desc->max_batch;
+  rr->ring = desc->ring, rr->max_batch = desc->max_batch;
+  rr->sc.nfields = desc->nfields;
+  rr->sc.row_bytes.assign(desc->row_bytes, desc->row_bytes + desc->nfields);
+  rr->sc.steps.assign(desc->steps, desc->steps + desc->nfields);
   auto open = [&](const unsigned char* h, void** p) {
     hipIpcMemHandle_t mh;
     memcpy(&mh, h, sizeof(mh));
@@ -1700,59 +1655,47 @@ static int import_partition(rela_replay_remote** out, const rela_replay_ipc_desc
   hipError_t e = hipSuccess;
   const char* what = "hipIpcOpenMemHandle";
   int fd_at = 0;
+  // one range as export_partition wrote it (DevRange::import): its IPC handle, or the next n descriptors
+  auto take = [&](DevRange& d, const char* what_chunks, const unsigned char* handle, int n, int64_t chunk_bytes,
+                  int64_t mapped_bytes) {
+    e = d.import(handle, fds + fd_at, n, chunk_bytes, mapped_bytes, device);
+    if (n > 0) what = what_chunks, fd_at += n;
+  };
   // RELA_IPC_TRACE=1: one line per mapping step on stderr (an import that does not return is this platform's failure mode)
   const bool trace = getenv("RELA_IPC_TRACE") != nullptr;
   for (int f = 0; f < desc->nfields && e == hipSuccess; ++f) {
-    rr->row_bytes[f] = desc->row_bytes[f];
-    rr->steps[f] = desc->steps[f];
     const int n = chunks ? chunks->field_chunks[f] : 0;
+    const int64_t chunk_bytes = chunks ? chunks->chunk_bytes[f] : 0, mapped_bytes = chunks ? chunks->mapped_bytes[f] : 0;
     if (trace)
       fprintf(stderr, "[%s] field %d: %.3f GB as %s\n", who, f, (double)desc->row_bytes[f] * desc->ring / 1e9,
               n > 0 ? "chunks" : "one IPC handle");
-    if (n > 0) {
-      const int64_t need = desc->row_bytes[f] * (int64_t)desc->ring;
-      if (fd_at + n > nfds || chunks->chunk_bytes[f] <= 0 || chunks->mapped_bytes[f] < need ||
-          (chunks->mapped_bytes[f] + chunks->chunk_bytes[f] - 1) / chunks->chunk_bytes[f] != n) {
-        set_last_error("%s: field %d: %d chunks of %lld bytes do not describe %lld mapped bytes (%d descriptors given)", who, f,
-                       n, (long long)chunks->chunk_bytes[f], (long long)chunks->mapped_bytes[f], nfds);
-        rela_replay_remote_close(rr);
-        return RELA_EINVAL;
-      }
-      rr->vmm[f] = new VmmRange();
-      what = "mapping the chunks (hipMemImportFromShareableHandle / hipMemMap / hipMemSetAccess)";
-      e = rr->vmm[f]->import(fds + fd_at, n, (size_t)chunks->chunk_bytes[f], (size_t)chunks->mapped_bytes[f], device);
-      rr->fields[f] = rr->vmm[f]->base;
-      fd_at += n;
-    } else {
-      e = open(desc->field_handle[f], reinterpret_cast<void**>(&rr->fields[f]));
+    if (!DevRange::describes(n, chunk_bytes, mapped_bytes, desc->row_bytes[f] * (int64_t)desc->ring, nfds - fd_at)) {
+      set_last_error("%s: field %d: %d chunks of %lld bytes do not describe %lld mapped bytes (%d descriptors given)", who, f,
+                     n, (long long)chunk_bytes, (long long)mapped_bytes, nfds);
+      rela_replay_remote_close(rr);
+      return RELA_EINVAL;
     }
+    take(rr->fields[f], "mapping the chunks (hipMemImportFromShareableHandle / hipMemMap / hipMemSetAccess)",
+         desc->field_handle[f], n, chunk_bytes, mapped_bytes);
   }
   if (e == hipSuccess && chunks && chunks->dd_ups > 0) {
-    rr->dd_ups = chunks->dd_ups, rr->dd_unit_bytes = chunks->dd_unit_bytes;
-    rr->dd_field[0] = chunks->dd_field[0], rr->dd_field[1] = chunks->dd_field[1];
+    rr->sc.dd_ups = chunks->dd_ups, rr->sc.dd_unit_bytes = chunks->dd_unit_bytes;
+    rr->sc.dd_field[0] = chunks->dd_field[0], rr->sc.dd_field[1] = chunks->dd_field[1];
     const int n = chunks->units_chunks;
     const int64_t need = chunks->dd_cap * chunks->dd_unit_bytes;
     // (dd_field[1] < 0 would be a sequence partition's single stack field: never exported, refused here as well)
-    const bool fields_ok = rr->dd_field[0] >= 0 && rr->dd_field[0] < desc->nfields && rr->dd_field[1] >= 0 &&
-                           rr->dd_field[1] < desc->nfields && rr->dd_ups <= 16 && rr->dd_unit_bytes > 0 && rr->dd_unit_bytes % 16 == 0 &&
-                           desc->row_bytes[rr->dd_field[0]] == 4 * rr->dd_ups && desc->row_bytes[rr->dd_field[1]] == 4 * rr->dd_ups;
-    if (!fields_ok || (n > 0 && (fd_at + n > nfds || chunks->units_chunk_bytes <= 0 || chunks->units_mapped_bytes < need ||
-                                 (chunks->units_mapped_bytes + chunks->units_chunk_bytes - 1) / chunks->units_chunk_bytes != n))) {
+    const bool fields_ok = rr->sc.dd_field[0] >= 0 && rr->sc.dd_field[0] < desc->nfields && rr->sc.dd_field[1] >= 0 &&
+                           rr->sc.dd_field[1] < desc->nfields && rr->sc.dd_ups <= 16 && rr->sc.dd_unit_bytes > 0 && rr->sc.dd_unit_bytes % 16 == 0 &&
+                           desc->row_bytes[rr->sc.dd_field[0]] == 4 * rr->sc.dd_ups && desc->row_bytes[rr->sc.dd_field[1]] == 4 * rr->sc.dd_ups;
+    if (!fields_ok || !DevRange::describes(n, chunks->units_chunk_bytes, chunks->units_mapped_bytes, need, nfds - fd_at)) {
       set_last_error("%s: the unit ring's description is inconsistent (%d chunks, fields %d / %d, %d units per stack)", who, n,
-                     rr->dd_field[0], rr->dd_field[1], rr->dd_ups);
+                     rr->sc.dd_field[0], rr->sc.dd_field[1], rr->sc.dd_ups);
       rela_replay_remote_close(rr);
       return RELA_EINVAL;
     }
     if (trace) fprintf(stderr, "[%s] unit ring: %.3f GB as %s\n", who, (double)need / 1e9, n > 0 ? "chunks" : "one IPC handle");
-    if (n > 0) {
-      rr->vmm_units = new VmmRange();
-      what = "mapping the unit ring's chunks";
-      e = rr->vmm_units->import(fds + fd_at, n, (size_t)chunks->units_chunk_bytes, (size_t)chunks->units_mapped_bytes, device);
-      rr->units = rr->vmm_units->base;
-      fd_at += n;
-    } else {
-      e = open(chunks->units_handle, reinterpret_cast<void**>(&rr->units));
-    }
+    take(rr->units, "mapping the unit ring's chunks", chunks->units_handle, n, chunks->units_chunk_bytes,
+         chunks->units_mapped_bytes);
   }
   if (trace) fprintf(stderr, "[%s] fields mapped (%s); ids / weights / state\n", who, hipGetErrorString(e));
   if (e == hipSuccess) what = "hipIpcOpenMemHandle", e = open(desc->ids_handle, reinterpret_cast<void**>(&rr->ids));
@@ -1786,20 +1729,8 @@ extern "C" void rela_replay_remote_close(rela_replay_remote* rr) {
   if (!rr) return;
   DeviceGuard g(rr->device);
   (void)hipDeviceSynchronize();
-  for (int f = 0; f < rr->nfields; ++f) {
-    if (rr->vmm[f]) {
-      rr->vmm[f]->destroy();
-      delete rr->vmm[f];
-    } else if (rr->fields[f]) {
-      (void)hipIpcCloseMemHandle(rr->fields[f]);
-    }
-  }
-  if (rr->vmm_units) {
-    rr->vmm_units->destroy();
-    delete rr->vmm_units;
-  } else if (rr->units) {
-    (void)hipIpcCloseMemHandle(rr->units);
-  }
+  for (int f = 0; f < rr->sc.nfields; ++f) rr->fields[f].close();
+  rr->units.close();
   if (rr->ids) (void)hipIpcCloseMemHandle(rr->ids);
   if (rr->raw_w) (void)hipIpcCloseMemHandle(rr->raw_w);
   if (rr->state) (void)hipIpcCloseMemHandle(rr->state);
@@ -1814,56 +1745,18 @@ extern "C" int rela_replay_remote_gather(rela_replay_remote* rr, int batch, void
              "rela_replay_remote_gather: rows [%d, %d) do not fit an output of %d", out_offset, out_offset + batch, out_batch);
   hipStream_t s = (hipStream_t)stream_;
   DeviceGuard g(rr->device);
-  SmallFields small{};
-  BigFields big{};
-  int nbig = 0, max_y = 1;
-  int64_t max_units = 1;
-  for (int f = 0; f < rr->nfields; ++f) {
-    if (!out_rows_dev[f]) continue;
-    const int64_t rb = rr->row_bytes[f];
-    const int st = rr->steps[f];
-    if (rr->dd_ups > 0 && (f == rr->dd_field[0] || f == rr->dd_field[1])) {
-      RELA_CHECK(((uintptr_t)out_rows_dev[f] & 15) == 0, RELA_EINVAL, "rela_replay_remote_gather: unaligned stack output");
-      continue;  // rebuilt from the unit ring below
-    }
-    if (st == 1 && rb <= kSmallRowBytes && small.n < kMaxSmallFields) {
-      small.src[small.n] = rr->fields[f];
-      small.dst[small.n] = (uint8_t*)out_rows_dev[f];
-      small.row_bytes[small.n] = (int32_t)rb;
-      small.n += 1;
-      continue;
-    }
-    RELA_CHECK(nbig < kMaxBigFields, RELA_EINVAL, "rela_replay_remote_gather: more than %d large fields", kMaxBigFields);
-    const int64_t sub = rb / st;
-    const int v16 = vec16_ok(out_rows_dev[f], rr->fields[f], sub) && (rb % 16 == 0);
-    big.out_batch = out_batch, big.out_off = out_offset;
-    big.field[nbig] = rr->fields[f];
-    big.out[nbig] = (uint8_t*)out_rows_dev[f];
-    big.slot_bytes[nbig] = rb;
-    big.steps[nbig] = st;
-    big.vec16[nbig] = v16;
-    max_units = std::max<int64_t>(max_units, v16 ? (sub >> 4) : sub);
-    max_y = std::max(max_y, batch * st);
-    nbig += 1;
-  }
+  GatherPlan plan;
+  if (int rc = plan_gather(&plan, rr->sc, rr->fields, out_rows_dev, batch, out_batch, out_offset, "rela_replay_remote_gather"))
+    return rc;
   {
     ProfScope prof("replay_gather_remote", s);
-    hipLaunchKernelGGL(replay_gather_small_remote, dim3(1 + small.n), dim3(256), 0, s, small, (const int32_t*)rr->ids, batch,
-                       (const float*)rr->raw_w, (const ReplayDevState*)rr->state, raw_w_out, sum_f_out, out_offset);
-    if (nbig > 0) {
-      const int gx = (int)std::min<int64_t>(std::max<int64_t>(1, (max_units + kThreads - 1) / kThreads), 64);
-      hipLaunchKernelGGL(replay_gather_big, dim3(gx, std::min(max_y, 32768), nbig), dim3(kThreads), 0, s, big,
-                         (const int32_t*)rr->ids, batch);
-    }
-    for (int q = 0; q < 2 && rr->dd_ups > 0; ++q) {  // stacks out of the owner's unit ring (as rela_replay_sample does locally)
-      const int f = rr->dd_field[q];
+    hipLaunchKernelGGL(replay_gather_small_remote, dim3(1 + plan.small.n), dim3(256), 0, s, plan.small, (const int32_t*)rr->ids,
+                       batch, (const float*)rr->raw_w, (const ReplayDevState*)rr->state, raw_w_out, sum_f_out, out_offset);
+    if (plan.nbig > 0) launch_gather_big(plan, rr->ids, batch, s);
+    for (int q = 0; q < 2 && rr->sc.dd_ups > 0; ++q) {  // stacks out of the owner's unit ring (as rela_replay_sample does locally)
+      const int f = rr->sc.dd_field[q];
       if (!out_rows_dev[f]) continue;
-      const int64_t nv = rr->dd_unit_bytes >> 4;
-      const int gx = (int)std::min<int64_t>(std::max<int64_t>(1, (nv + kThreads - 1) / kThreads), 64);
-      uint8_t* out = (uint8_t*)out_rows_dev[f] + (int64_t)out_offset * rr->dd_ups * rr->dd_unit_bytes;
-      hipLaunchKernelGGL(replay_gather_dedup, dim3(gx, std::min(batch * rr->dd_ups, 32768)), dim3(kThreads), 0, s,
-                         (const int32_t*)rr->fields[f], (const int32_t*)rr->ids, (const uint8_t*)rr->units, rr->dd_unit_bytes,
-                         rr->dd_ups, out, batch);
+      launch_gather_dedup(rr->sc, rr->fields[f].base, rr->units.base, rr->ids, out_rows_dev[f], batch, out_offset, s);
     }
   }
   RELA_LAUNCH_CHECK();

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <unistd.h>
 
 #include <vector>
@@ -138,6 +139,70 @@ struct VmmRange {
     if (base) (void)hipMemAddressFree(base, bytes);
     handles.clear(), sizes.clear();
     base = nullptr, bytes = 0;
+  }
+};
+
+// One device range of a replay partition -- a field array or the unit ring -- in either of its two forms: one hipMalloc,
+// which travels to another process as one 64-byte hipIpcMemHandle_t, or a VmmRange, which travels as one descriptor per
+// chunk plus (chunks, chunk_bytes, mapped_bytes).  Kernels see `base` only.
+struct DevRange {
+  uint8_t* base = nullptr;
+  bool chunked = false;  // base = vmm.base
+  VmmRange vmm;
+
+  int chunks() const { return (int)vmm.handles.size(); }  // descriptors an export writes (plain: 0)
+
+  // owner: chunk_bytes = 0 is one hipMalloc.  Nothing stays allocated on failure.
+  hipError_t create(size_t bytes, size_t chunk_bytes, int device) {
+    if (chunk_bytes == 0) return hipMalloc(&base, bytes);
+    const hipError_t e = vmm.create(bytes, chunk_bytes, device);
+    if (e != hipSuccess) {
+      vmm.destroy();
+      return e;
+    }
+    chunked = true, base = vmm.base;
+    return hipSuccess;
+  }
+
+  void release() {  // owner
+    if (chunked) vmm.destroy();
+    else (void)hipFree(base);
+    base = nullptr, chunked = false;
+  }
+
+  // owner: plain -> the IPC handle; chunked -> chunks() descriptors into fds_out and what describes them
+  hipError_t export_to(unsigned char handle_out[64], int* fds_out, int32_t* chunks_out, int64_t* chunk_bytes_out,
+                       int64_t* mapped_bytes_out) const {
+    if (!chunked) return hipIpcGetMemHandle(reinterpret_cast<hipIpcMemHandle_t*>(handle_out), base);
+    const hipError_t e = vmm.export_fds(fds_out);
+    if (e != hipSuccess) return e;
+    *chunks_out = chunks(), *chunk_bytes_out = (int64_t)vmm.chunk, *mapped_bytes_out = (int64_t)vmm.bytes;
+    return hipSuccess;
+  }
+
+  // importer: do `n` chunks (of `avail` descriptors left) of `chunk_bytes` describe `mapped` bytes that hold `need`?
+  static bool describes(int n, int64_t chunk_bytes, int64_t mapped, int64_t need, int avail) {
+    return n <= 0 || (n <= avail && chunk_bytes > 0 && mapped >= need && (mapped + chunk_bytes - 1) / chunk_bytes == n);
+  }
+
+  // importer: what export_to wrote, back (n <= 0: the IPC handle).  A failed import is undone by close().
+  hipError_t import(const unsigned char handle[64], const int* fds, int n, int64_t chunk_bytes, int64_t mapped,
+                    int accessing_device) {
+    if (n <= 0) {
+      hipIpcMemHandle_t mh;
+      memcpy(&mh, handle, sizeof(mh));
+      return hipIpcOpenMemHandle(reinterpret_cast<void**>(&base), mh, hipIpcMemLazyEnablePeerAccess);
+    }
+    chunked = true;
+    const hipError_t e = vmm.import(fds, n, (size_t)chunk_bytes, (size_t)mapped, accessing_device);
+    base = vmm.base;
+    return e;
+  }
+
+  void close() {  // importer
+    if (chunked) vmm.destroy();
+    else if (base) (void)hipIpcCloseMemHandle(base);
+    base = nullptr, chunked = false;
   }
 };
 

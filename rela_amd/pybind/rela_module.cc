@@ -722,244 +722,98 @@ static torch::Device deviceOf(const std::string& device) {
   return want < 0 ? torch::Device(torch::kCPU) : torch::Device(torch::kCUDA, (c10::DeviceIndex)want);
 }
 
-// =====================================================================================
-// FFPrioritizedReplay (rela/prioritized_replay.h:173-348 as bound in pybind.cc:37-47)
-// =====================================================================================
-class FFPrioritizedReplay {
- public:
-  FFPrioritizedReplay(int capacity, int seed, float alpha, float beta, int prefetch)
-      : core_(capacity, seed, alpha, beta, prefetch) {}
+// RELA_REPLAY_DEDUP=stack|plane: frame-stack de-duplication (include/rela_amd.h).  "stack" is valid for
+// any env (what the reference's shared tensor views do); "plane" needs an env that slides its stack by one frame per
+// step as atari/game_state.h:53-82 does.  -> units per stack (0 = off); RELA_REPLAY_DEDUP_GUARD: units stored ahead of
+// their transitions
+static int dedupFromEnv(int64_t defaultGuard, int64_t* guard) {
+  const char* dd = std::getenv("RELA_REPLAY_DEDUP");
+  const char* gd = std::getenv("RELA_REPLAY_DEDUP_GUARD");
+  *guard = gd ? std::atoll(gd) : defaultGuard;
+  return dd && std::string(dd) == "stack" ? 1 : (dd && std::string(dd) == "plane" ? 4 : 0);
+}
 
-  ReplayParts& core() { return core_; }
+// What tells the transition form of the replay from the sequence form (PrioritizedReplay<Kind> below): the schema, the
+// tensors of a batch and the axis along which the partitions' shares of a batch concatenate.
+struct TransitionKind {
+  using Transition = FFTransition;
+  static constexpr const char* name = "FFPrioritizedReplay";
+  static constexpr const char* shapeWhat = "the action count";
+  static int64_t shapeKey(int numAction, int) { return numAction; }
 
-  // the partition of `lockerKey`, created lazily by the first actor that knows the device and the action count
-  rela_replay* handle(const void* lockerKey, int device, int numAction) {
-    {  // (several cohort leaders call this concurrently on their first act: ADVICE r4)
-      int seen = 0;
-      if (!numAction_.compare_exchange_strong(seen, numAction) && seen != numAction)
-        throw std::runtime_error("FFPrioritizedReplay: actors disagree on the action count");
+  static void setSchema(rela_replay* h, int numAction, int, int) {
+    const int64_t A = numAction;
+    const int64_t rb[10] = {kObsBytes, kObsBytes, 4, 4, 4 * A, 4 * A, 8, 4, 1, 4};
+    int64_t guard = 0;
+    const int ups = dedupFromEnv(131072, &guard);
+    if (ups > 0) {
+      check(rela_replay_set_schema_dedup(h, 10, rb, 0, 1, kObsBytes / ups, ups, guard), "rela_replay_set_schema_dedup");
+    } else {
+      check(rela_replay_set_schema(h, 10, rb), "rela_replay_set_schema");
     }
-    return core_.handle(lockerKey, device, [&](rela_replay* h) {
-      const int64_t A = numAction;
-      const int64_t rb[10] = {kObsBytes, kObsBytes, 4, 4, 4 * A, 4 * A, 8, 4, 1, 4};
-      // RELA_REPLAY_DEDUP=stack|plane: frame-stack de-duplication (include/rela_amd.h).  "stack" is
-      // valid for any env (what the reference's shared tensor views do); "plane" needs an env that slides its
-      // stack by one frame per step as atari/game_state.h:53-82 does.
-      const char* dd = std::getenv("RELA_REPLAY_DEDUP");
-      const int ups = dd && std::string(dd) == "stack" ? 1 : (dd && std::string(dd) == "plane" ? 4 : 0);
-      if (ups > 0) {
-        const char* gd = std::getenv("RELA_REPLAY_DEDUP_GUARD");
-        const int64_t guard = gd ? std::atoll(gd) : 131072;  // units stored ahead of their transitions
-        check(rela_replay_set_schema_dedup(h, 10, rb, 0, 1, kObsBytes / ups, ups, guard), "rela_replay_set_schema_dedup");
-      } else {
-        check(rela_replay_set_schema(h, 10, rb), "rela_replay_set_schema");
-      }
-    });
   }
 
-  int size() const { return core_.size(); }
-  int numAdd() const { return core_.numAdd(); }
-  void shutdown() { core_.shutdown(); }
-
-  // prefetch > 0 (rela/prioritized_replay.h:223-230: sampler futures that run next to the learner): here a DEVICE-side
-  // prefetch -- update_priority k queues sample k + 1 right behind itself on the replay's stream, so its latency-bound
-  // kernels run while the Python learner loop gets from update_priority back to sample; sample() then hands that
-  // batch over.  One outstanding batch at a time as in the library's protocol, and the same sequence of library calls
-  // as without prefetch: ids, weights and rows are bit-identical to prefetch = 0 (tests/test_e2e_gpu.py).
-  std::tuple<FFTransition, torch::Tensor> sample(int batchsize, const std::string& device) {
-    if (prefetched_ && prefetchedBatch_ == batchsize && prefetchedDevice_ == device) {
-      auto r = std::move(*prefetched_);
-      prefetched_.reset();
-      return r;
-    }
-    if (prefetched_) throw std::runtime_error("FFPrioritizedReplay.sample: batch size / device changed under prefetch");
-    return sampleNow(batchsize, device);
-  }
-
-  // B rows of one partition, on the partition's own device
-  std::tuple<FFTransition, torch::Tensor> samplePart(const ReplayParts::Part& p, int B_) {
-    const auto dev = torch::Device(torch::kCUDA, (c10::DeviceIndex)p.device);
-    auto u8 = torch::TensorOptions().dtype(torch::kUInt8).device(dev);
-    auto f32 = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
-    const int64_t B = B_, A = numAction_;
+  // B rows on `dev`; rows[] = the tensors in schema order
+  static FFTransition alloc(torch::Device dev, int64_t B, int64_t A, int64_t, void* rows[10]) {
+    auto opt = [&](torch::ScalarType t) { return torch::TensorOptions().dtype(t).device(dev); };
     FFTransition b;
-    b.obs["s"] = torch::empty({B, 4, 84, 84}, u8);
-    b.nextObs["s"] = torch::empty({B, 4, 84, 84}, u8);
-    b.obs["eps"] = torch::empty({B, 1}, f32);
-    b.nextObs["eps"] = torch::empty({B, 1}, f32);
-    b.obs["legal_move"] = torch::empty({B, A}, f32);
-    b.nextObs["legal_move"] = torch::empty({B, A}, f32);
-    b.action["a"] = torch::empty({B}, torch::TensorOptions().dtype(torch::kInt64).device(dev));
-    b.reward = torch::empty({B}, f32);
-    b.terminal = torch::empty({B}, torch::TensorOptions().dtype(torch::kBool).device(dev));
-    b.bootstrap = torch::empty({B}, f32);
-    auto weight = torch::empty({B}, f32);
-    void* rows[10] = {b.obs["s"].data_ptr(),          b.nextObs["s"].data_ptr(),          b.obs["eps"].data_ptr(),
-                      b.nextObs["eps"].data_ptr(),    b.obs["legal_move"].data_ptr(),     b.nextObs["legal_move"].data_ptr(),
-                      b.action["a"].data_ptr(),       b.reward.data_ptr(),                b.terminal.data_ptr(),
-                      b.bootstrap.data_ptr()};
-    check(rela_replay_sample(p.h, B_, rows, weight.data_ptr<float>(), torchCurrentStream(p.device)),
-          "FFPrioritizedReplay.sample");
-    return std::make_tuple(std::move(b), weight);
+    b.obs["s"] = torch::empty({B, 4, 84, 84}, opt(torch::kUInt8));
+    b.nextObs["s"] = torch::empty({B, 4, 84, 84}, opt(torch::kUInt8));
+    b.obs["eps"] = torch::empty({B, 1}, opt(torch::kFloat32));
+    b.nextObs["eps"] = torch::empty({B, 1}, opt(torch::kFloat32));
+    b.obs["legal_move"] = torch::empty({B, A}, opt(torch::kFloat32));
+    b.nextObs["legal_move"] = torch::empty({B, A}, opt(torch::kFloat32));
+    b.action["a"] = torch::empty({B}, opt(torch::kInt64));
+    b.reward = torch::empty({B}, opt(torch::kFloat32));
+    b.terminal = torch::empty({B}, opt(torch::kBool));
+    b.bootstrap = torch::empty({B}, opt(torch::kFloat32));
+    int i = 0;
+    each(b, [&](torch::Tensor& t, int) { rows[i++] = t.data_ptr(); });
+    return b;
   }
 
-  std::tuple<FFTransition, torch::Tensor> sampleNow(int batchsize, const std::string& device) {
-    auto parts = core_.parts();
-    if (parts.empty()) throw std::runtime_error("FFPrioritizedReplay.sample: the replay is empty");
-    const int G = (int)parts.size();
-    if (G != core_.expected())
-      throw std::runtime_error("FFPrioritizedReplay.sample: only " + std::to_string(G) + " of " +
-                               std::to_string(core_.expected()) + " partitions have received data yet");
-    if (batchsize % G != 0)
-      throw std::runtime_error("FFPrioritizedReplay.sample: the batch must split evenly over the " + std::to_string(G) +
-                               " partitions (one per ModelLocker)");
-    const auto target = deviceOf(device);
-    lastBatch_ = batchsize;
-    lastDevice_ = device;
-    lastCounts_.assign(G, batchsize / G);
-    if (G == 1) {
-      FFTransition b;
-      torch::Tensor weight;
-      std::tie(b, weight) = samplePart(parts[0], batchsize);
-      if (target != torch::Device(torch::kCUDA, (c10::DeviceIndex)parts[0].device)) {  // learner elsewhere: types.cc:34-43
-        auto mv = [&](torch::Tensor& t) { t = t.to(target); };
-        for (auto* d : {&b.obs, &b.action, &b.nextObs})
-          for (auto& kv : *d) mv(kv.second);
-        mv(b.reward);
-        mv(b.terminal);
-        mv(b.bootstrap);
-        mv(weight);
-      }
-      return std::make_tuple(std::move(b), weight);
-    }
-    std::vector<FFTransition> sub(G);
-    std::vector<torch::Tensor> raw, sum;
-    std::vector<int> size;
-    for (int g = 0; g < G; ++g) {
-      torch::Tensor w;
-      std::tie(sub[g], w) = samplePart(parts[g], batchsize / G);
-      auto r = lastSampleRaw(parts[g].h, parts[g].device, batchsize / G);
-      raw.push_back(std::get<0>(r).to(target));
-      sum.push_back(std::get<1>(r).to(target));
-      size.push_back(std::get<2>(r));
-    }
-    auto catOf = [&](auto get) {
-      std::vector<torch::Tensor> v;
-      for (int g = 0; g < G; ++g) v.push_back(get(sub[g]).to(target));
-      return torch::cat(v, 0);
-    };
-    FFTransition b;
+  // every tensor of a batch with its partition axis, in schema order
+  template <class F>
+  static void each(FFTransition& b, F&& f) {
     for (const char* k : {"s", "eps", "legal_move"}) {
-      b.obs[k] = catOf([&](FFTransition& t) { return t.obs.at(k); });
-      b.nextObs[k] = catOf([&](FFTransition& t) { return t.nextObs.at(k); });
+      f(b.obs.at(k), 0);
+      f(b.nextObs.at(k), 0);
     }
-    b.action["a"] = catOf([](FFTransition& t) { return t.action.at("a"); });
-    b.reward = catOf([](FFTransition& t) { return t.reward; });
-    b.terminal = catOf([](FFTransition& t) { return t.terminal; });
-    b.bootstrap = catOf([](FFTransition& t) { return t.bootstrap; });
-    return std::make_tuple(std::move(b), core_.globalWeights(raw, sum, size));
+    f(b.action.at("a"), 0);
+    f(b.reward, 0);
+    f(b.terminal, 0);
+    f(b.bootstrap, 0);
   }
-
-  // native partition exchange (not in the reference's surface): see ReplayParts::exportIpc / sampleIds
-  py::bytes exportIpc() { return core_.exportIpc(); }
-  std::pair<py::bytes, std::vector<int>> exportChunks() { return core_.exportChunks(); }
-  std::tuple<torch::Tensor, torch::Tensor, int> sampleIds(int n) {
-    auto r = core_.sampleIds(n);
-    lastBatch_ = n;
-    lastCounts_.assign(1, n);
-    lastDevice_.clear();  // (no device-side prefetch behind the next update_priority: the rows stay where they are)
-    return r;
-  }
-
-  std::tuple<torch::Tensor, torch::Tensor, int> lastSampleRaw_() {
-    auto parts = core_.parts();
-    if (parts.size() != 1) throw std::runtime_error("last_sample_raw: this replay has several partitions of its own");
-    return lastSampleRaw(parts[0].h, parts[0].device, lastBatch_);
-  }
-
-  void updatePriority(const torch::Tensor& priority) {
-    if (lastBatch_ == 0) throw std::runtime_error("FFPrioritizedReplay.update_priority: nothing was sampled");
-    if (priority.dim() != 1) throw std::invalid_argument("update_priority expects a 1-D tensor");  // :236
-    core_.updatePriority(priority, lastCounts_, "FFPrioritizedReplay.update_priority");
-    if (core_.prefetch_ > 0 && !lastDevice_.empty() && core_.size() >= lastBatch_) {
-      prefetched_.emplace(sampleNow(lastBatch_, lastDevice_));
-      prefetchedBatch_ = lastBatch_;
-      prefetchedDevice_ = lastDevice_;
-    }
-  }
-
- private:
-  ReplayParts core_;
-  std::atomic<int> numAction_{0};
-  int lastBatch_ = 0;
-  std::vector<int> lastCounts_;
-  std::string lastDevice_;
-  std::optional<std::tuple<FFTransition, torch::Tensor>> prefetched_;
-  int prefetchedBatch_ = 0;
-  std::string prefetchedDevice_;
 };
 
-// =====================================================================================
-// RNNPrioritizedReplay (PrioritizedReplay<RNNTransition>, pybind.cc:49-59): one slot = one sequence
-// of T = burn_in + seq_len + multi_step steps; batches come back time-major (types.cc:140-182).
-// =====================================================================================
-class RNNPrioritizedReplay {
- public:
-  RNNPrioritizedReplay(int capacity, int seed, float alpha, float beta, int prefetch)
-      : core_(capacity, seed, alpha, beta, prefetch) {}
-
-  ReplayParts& core() { return core_; }
+// one slot = one sequence of T = burn_in + seq_len + multi_step steps; batches come back time-major (types.cc:140-182)
+struct SequenceKind {
+  using Transition = RNNTransition;
+  static constexpr const char* name = "RNNPrioritizedReplay";
+  static constexpr const char* shapeWhat = "action count / window length";
+  static int64_t shapeKey(int numAction, int T) { return ((int64_t)numAction << 32) | (uint32_t)T; }
 
   // unitsPerSlot (de-duplication only): seq_len + multi_step, the new steps an env adds per sequence (csrc/actor_r2d2.hip)
-  rela_replay* handle(const void* lockerKey, int device, int numAction, int T, int unitsPerSlot) {
-    {  // (several cohort leaders call this concurrently on their first act: ADVICE r4)
-      int64_t seen = 0;
-      const int64_t mine = ((int64_t)numAction << 32) | (uint32_t)T;
-      if (!shape_.compare_exchange_strong(seen, mine) && seen != mine)
-        throw std::runtime_error("RNNPrioritizedReplay: actors disagree on action count / window length");
-      numAction_ = numAction;
-      T_ = T;
+  static void setSchema(rela_replay* h, int numAction, int T, int unitsPerSlot) {
+    const int64_t A = numAction, t = T;
+    const int64_t rb[10] = {t * kObsBytes, t * 4, t * 4 * A, t * 8, t * 4, t, t * 4, 2048, 2048, 4};
+    const int32_t st[10] = {T, T, T, T, T, T, T, 1, 1, 1};
+    // the T stacks of a sequence become [T][1 or 4] references into a unit ring of ring * unitsPerSlot + guard units.
+    // The default guard, 655,360 units, covers the (2 T + multi_step + 10) * envs a partition's producers need at
+    // T = 123 for up to 2,400 envs (the reference scripts: 80 x 20 and 60 x 40); 4.6 GB in plane units, 18.5 GB in
+    // stack units.  Batches are identical.
+    int64_t guard = 0;
+    const int ups = dedupFromEnv(655360, &guard);
+    if (ups > 0) {
+      check(rela_replay_set_schema_seq_dedup(h, 10, rb, st, 0, kObsBytes / ups, ups, unitsPerSlot, guard),
+            "rela_replay_set_schema_seq_dedup");
+    } else {
+      check(rela_replay_set_schema_seq(h, 10, rb, st), "rela_replay_set_schema_seq");
     }
-    return core_.handle(lockerKey, device, [&](rela_replay* h) {
-      const int64_t A = numAction, t = T;
-      const int64_t rb[10] = {t * kObsBytes, t * 4, t * 4 * A, t * 8, t * 4, t, t * 4, 2048, 2048, 4};
-      const int32_t st[10] = {T, T, T, T, T, T, T, 1, 1, 1};
-      // RELA_REPLAY_DEDUP=stack|plane as for FFPrioritizedReplay: the T stacks of a sequence become [T][1 or 4] references
-      // into a unit ring of ring * unitsPerSlot + guard units.  The default guard, 655,360 units, covers the
-      // (2 T + multi_step + 10) * envs a partition's producers need at T = 123 for up to 2,400 envs (the reference
-      // scripts: 80 x 20 and 60 x 40); 4.6 GB in plane units, 18.5 GB in stack units.  Batches are identical.
-      const char* dd = std::getenv("RELA_REPLAY_DEDUP");
-      const int ups = dd && std::string(dd) == "stack" ? 1 : (dd && std::string(dd) == "plane" ? 4 : 0);
-      if (ups > 0) {
-        const char* gd = std::getenv("RELA_REPLAY_DEDUP_GUARD");
-        const int64_t guard = gd ? std::atoll(gd) : 655360;
-        check(rela_replay_set_schema_seq_dedup(h, 10, rb, st, 0, kObsBytes / ups, ups, unitsPerSlot, guard),
-              "rela_replay_set_schema_seq_dedup");
-      } else {
-        check(rela_replay_set_schema_seq(h, 10, rb, st), "rela_replay_set_schema_seq");
-      }
-    });
   }
 
-  int size() const { return core_.size(); }
-  int numAdd() const { return core_.numAdd(); }
-  void shutdown() { core_.shutdown(); }
-
-  // (prefetch: as FFPrioritizedReplay::sample)
-  std::tuple<RNNTransition, torch::Tensor> sample(int batchsize, const std::string& device) {
-    if (prefetched_ && prefetchedBatch_ == batchsize && prefetchedDevice_ == device) {
-      auto r = std::move(*prefetched_);
-      prefetched_.reset();
-      return r;
-    }
-    if (prefetched_) throw std::runtime_error("RNNPrioritizedReplay.sample: batch size / device changed under prefetch");
-    return sampleNow(batchsize, device);
-  }
-
-  std::tuple<RNNTransition, torch::Tensor> samplePart(const ReplayParts::Part& p, int B_) {
-    const auto dev = torch::Device(torch::kCUDA, (c10::DeviceIndex)p.device);
+  static RNNTransition alloc(torch::Device dev, int64_t B, int64_t A, int64_t T, void* rows[10]) {
     auto opt = [&](torch::ScalarType t) { return torch::TensorOptions().dtype(t).device(dev); };
-    const int64_t B = B_, A = numAction_, T = T_;
     RNNTransition b;
     b.obs["s"] = torch::empty({T, B, 4, 84, 84}, opt(torch::kUInt8));
     b.obs["eps"] = torch::empty({T, B, 1}, opt(torch::kFloat32));
@@ -971,48 +825,111 @@ class RNNPrioritizedReplay {
     b.h0["h0"] = torch::empty({1, B, 512}, opt(torch::kFloat32));
     b.h0["c0"] = torch::empty({1, B, 512}, opt(torch::kFloat32));
     b.seqLen = torch::empty({B}, opt(torch::kFloat32));
-    auto weight = torch::empty({B}, opt(torch::kFloat32));
-    void* rows[10] = {b.obs["s"].data_ptr(), b.obs["eps"].data_ptr(), b.obs["legal_move"].data_ptr(),
-                      b.action["a"].data_ptr(), b.reward.data_ptr(), b.terminal.data_ptr(), b.bootstrap.data_ptr(),
-                      b.h0["h0"].data_ptr(), b.h0["c0"].data_ptr(), b.seqLen.data_ptr()};
-    check(rela_replay_sample(p.h, B_, rows, weight.data_ptr<float>(), torchCurrentStream(p.device)),
-          "RNNPrioritizedReplay.sample");
+    int i = 0;
+    each(b, [&](torch::Tensor& t, int) { rows[i++] = t.data_ptr(); });
+    return b;
+  }
+
+  // time-major fields stack along their batch axis (types.cc:140-182: dim 1), and so do h0 / c0 [1, B, 512]
+  template <class F>
+  static void each(RNNTransition& b, F&& f) {
+    for (const char* k : {"s", "eps", "legal_move"}) f(b.obs.at(k), 1);
+    f(b.action.at("a"), 1);
+    f(b.reward, 1);
+    f(b.terminal, 1);
+    f(b.bootstrap, 1);
+    for (const char* k : {"h0", "c0"}) f(b.h0.at(k), 1);
+    f(b.seqLen, 0);
+  }
+};
+
+// =====================================================================================
+// FFPrioritizedReplay (rela/prioritized_replay.h:173-348 as bound in pybind.cc:37-47) and RNNPrioritizedReplay
+// (PrioritizedReplay<RNNTransition>, pybind.cc:49-59)
+// =====================================================================================
+template <class Kind>
+class PrioritizedReplay {
+ public:
+  using Transition = typename Kind::Transition;
+  using Batch = std::tuple<Transition, torch::Tensor>;
+
+  PrioritizedReplay(int capacity, int seed, float alpha, float beta, int prefetch)
+      : core_(capacity, seed, alpha, beta, prefetch) {}
+
+  ReplayParts& core() { return core_; }
+
+  // the partition of `lockerKey`, created lazily by the first actor that knows the device and the batch shape (the
+  // transition form takes numAction only)
+  rela_replay* handle(const void* lockerKey, int device, int numAction, int T = 0, int unitsPerSlot = 0) {
+    {  // (several cohort leaders call this concurrently on their first act: ADVICE r4)
+      int64_t seen = 0;
+      const int64_t mine = Kind::shapeKey(numAction, T);
+      if (!shape_.compare_exchange_strong(seen, mine) && seen != mine)
+        throw std::runtime_error(std::string(Kind::name) + ": actors disagree on " + Kind::shapeWhat);
+      numAction_ = numAction;
+      T_ = T;
+    }
+    return core_.handle(lockerKey, device, [&](rela_replay* h) { Kind::setSchema(h, numAction, T, unitsPerSlot); });
+  }
+
+  int size() const { return core_.size(); }
+  int numAdd() const { return core_.numAdd(); }
+  void shutdown() { core_.shutdown(); }
+
+  // prefetch > 0 (rela/prioritized_replay.h:223-230: sampler futures that run next to the learner): here a DEVICE-side
+  // prefetch -- update_priority k queues sample k + 1 right behind itself on the replay's stream, so its latency-bound
+  // kernels run while the Python learner loop gets from update_priority back to sample; sample() then hands that
+  // batch over.  One outstanding batch at a time as in the library's protocol, and the same sequence of library calls
+  // as without prefetch: ids, weights and rows are bit-identical to prefetch = 0 (tests/test_e2e_gpu.py).
+  Batch sample(int batchsize, const std::string& device) {
+    if (prefetched_ && prefetchedBatch_ == batchsize && prefetchedDevice_ == device) {
+      auto r = std::move(*prefetched_);
+      prefetched_.reset();
+      return r;
+    }
+    if (prefetched_) throw std::runtime_error(where(".sample: batch size / device changed under prefetch"));
+    return sampleNow(batchsize, device);
+  }
+
+  // B rows of one partition, on the partition's own device
+  Batch samplePart(const ReplayParts::Part& p, int B) {
+    const auto dev = torch::Device(torch::kCUDA, (c10::DeviceIndex)p.device);
+    void* rows[10];
+    Transition b = Kind::alloc(dev, B, numAction_, T_, rows);
+    auto weight = torch::empty({B}, torch::TensorOptions().dtype(torch::kFloat32).device(dev));
+    static const std::string call = where(".sample");
+    check(rela_replay_sample(p.h, B, rows, weight.data_ptr<float>(), torchCurrentStream(p.device)), call.c_str());
     return std::make_tuple(std::move(b), weight);
   }
 
-  std::tuple<RNNTransition, torch::Tensor> sampleNow(int batchsize, const std::string& device) {
+  Batch sampleNow(int batchsize, const std::string& device) {
     auto parts = core_.parts();
-    if (parts.empty()) throw std::runtime_error("RNNPrioritizedReplay.sample: the replay is empty");
+    if (parts.empty()) throw std::runtime_error(where(".sample: the replay is empty"));
     const int G = (int)parts.size();
     if (G != core_.expected())
-      throw std::runtime_error("RNNPrioritizedReplay.sample: only " + std::to_string(G) + " of " +
-                               std::to_string(core_.expected()) + " partitions have received data yet");
+      throw std::runtime_error(where(".sample: only ") + std::to_string(G) + " of " + std::to_string(core_.expected()) +
+                               " partitions have received data yet");
     if (batchsize % G != 0)
-      throw std::runtime_error("RNNPrioritizedReplay.sample: the batch must split evenly over the " + std::to_string(G) +
+      throw std::runtime_error(where(".sample: the batch must split evenly over the ") + std::to_string(G) +
                                " partitions (one per ModelLocker)");
     const auto target = deviceOf(device);
     lastBatch_ = batchsize;
     lastDevice_ = device;
     lastCounts_.assign(G, batchsize / G);
     if (G == 1) {
-      RNNTransition b;
+      Transition b;
       torch::Tensor weight;
       std::tie(b, weight) = samplePart(parts[0], batchsize);
-      if (target != torch::Device(torch::kCUDA, (c10::DeviceIndex)parts[0].device)) {
-        auto mv = [&](torch::Tensor& t) { t = t.to(target); };
-        for (auto* d : {&b.obs, &b.action, &b.h0})
-          for (auto& kv : *d) mv(kv.second);
-        mv(b.reward);
-        mv(b.terminal);
-        mv(b.bootstrap);
-        mv(b.seqLen);
-        mv(weight);
+      if (target != torch::Device(torch::kCUDA, (c10::DeviceIndex)parts[0].device)) {  // learner elsewhere: types.cc:34-43
+        Kind::each(b, [&](torch::Tensor& t, int) { t = t.to(target); });
+        weight = weight.to(target);
       }
       return std::make_tuple(std::move(b), weight);
     }
-    std::vector<RNNTransition> sub(G);
+    std::vector<Transition> sub(G);
     std::vector<torch::Tensor> raw, sum;
     std::vector<int> size;
+    std::vector<std::vector<torch::Tensor>> shares;  // [tensor of the batch][partition], on `target`
     for (int g = 0; g < G; ++g) {
       torch::Tensor w;
       std::tie(sub[g], w) = samplePart(parts[g], batchsize / G);
@@ -1020,32 +937,15 @@ class RNNPrioritizedReplay {
       raw.push_back(std::get<0>(r).to(target));
       sum.push_back(std::get<1>(r).to(target));
       size.push_back(std::get<2>(r));
+      size_t i = 0;
+      Kind::each(sub[g], [&](torch::Tensor& t, int) {
+        if (g == 0) shares.emplace_back();
+        shares[i++].push_back(t.to(target));
+      });
     }
-    auto catOf = [&](auto get, int dim) {  // time-major fields stack along their batch axis (types.cc:140-182: dim 1)
-      std::vector<torch::Tensor> v;
-      for (int g = 0; g < G; ++g) v.push_back(get(sub[g]).to(target));
-      return torch::cat(v, dim);
-    };
-    RNNTransition b;
-    for (const char* k : {"s", "eps", "legal_move"}) b.obs[k] = catOf([&](RNNTransition& t) { return t.obs.at(k); }, 1);
-    b.action["a"] = catOf([](RNNTransition& t) { return t.action.at("a"); }, 1);
-    b.reward = catOf([](RNNTransition& t) { return t.reward; }, 1);
-    b.terminal = catOf([](RNNTransition& t) { return t.terminal; }, 1);
-    b.bootstrap = catOf([](RNNTransition& t) { return t.bootstrap; }, 1);
-    for (const char* k : {"h0", "c0"}) b.h0[k] = catOf([&](RNNTransition& t) { return t.h0.at(k); }, 1);
-    b.seqLen = catOf([](RNNTransition& t) { return t.seqLen; }, 0);
-    return std::make_tuple(std::move(b), core_.globalWeights(raw, sum, size));
-  }
-
-  void updatePriority(const torch::Tensor& priority) {
-    if (lastBatch_ == 0) throw std::runtime_error("RNNPrioritizedReplay.update_priority: nothing was sampled");
-    if (priority.dim() != 1) throw std::invalid_argument("update_priority expects a 1-D tensor");
-    core_.updatePriority(priority, lastCounts_, "RNNPrioritizedReplay.update_priority");
-    if (core_.prefetch_ > 0 && !lastDevice_.empty() && core_.size() >= lastBatch_) {
-      prefetched_.emplace(sampleNow(lastBatch_, lastDevice_));
-      prefetchedBatch_ = lastBatch_;
-      prefetchedDevice_ = lastDevice_;
-    }
+    size_t i = 0;
+    Kind::each(sub[0], [&](torch::Tensor& t, int axis) { t = torch::cat(shares[i++], axis); });
+    return std::make_tuple(std::move(sub[0]), core_.globalWeights(raw, sum, size));
   }
 
   // native partition exchange (not in the reference's surface): see ReplayParts::exportIpc / sampleIds
@@ -1065,17 +965,33 @@ class RNNPrioritizedReplay {
     return lastSampleRaw(parts[0].h, parts[0].device, lastBatch_);
   }
 
+  void updatePriority(const torch::Tensor& priority) {
+    if (lastBatch_ == 0) throw std::runtime_error(where(".update_priority: nothing was sampled"));
+    if (priority.dim() != 1) throw std::invalid_argument("update_priority expects a 1-D tensor");  // :236
+    static const std::string call = where(".update_priority");
+    core_.updatePriority(priority, lastCounts_, call.c_str());
+    if (core_.prefetch_ > 0 && !lastDevice_.empty() && core_.size() >= lastBatch_) {
+      prefetched_.emplace(sampleNow(lastBatch_, lastDevice_));
+      prefetchedBatch_ = lastBatch_;
+      prefetchedDevice_ = lastDevice_;
+    }
+  }
+
  private:
+  static std::string where(const char* what) { return std::string(Kind::name) + what; }
+
   ReplayParts core_;
-  std::atomic<int64_t> shape_{0};  // numAction << 32 | T, set once
+  std::atomic<int64_t> shape_{0};  // Kind::shapeKey of the actors, set once
   std::atomic<int> numAction_{0}, T_{0};
   int lastBatch_ = 0;
   std::vector<int> lastCounts_;
   std::string lastDevice_;
-  std::optional<std::tuple<RNNTransition, torch::Tensor>> prefetched_;
+  std::optional<Batch> prefetched_;
   int prefetchedBatch_ = 0;
   std::string prefetchedDevice_;
 };
+using FFPrioritizedReplay = PrioritizedReplay<TransitionKind>;
+using RNNPrioritizedReplay = PrioritizedReplay<SequenceKind>;
 
 // One actor shard of either algorithm behind one handle: the entry points the module calls, in the spelling of the
 // Ape-X shard (rela_apex_actor_*, nets are rela_ffnet) and of the R2D2 shard (rela_r2d2_actor_*, nets are rela_lstmnet).

@@ -192,19 +192,30 @@ CFG_R2D2_C4 = dict(K=4, multi_step=3, gamma=0.997, seq_len=80, burn_in=40, eta=0
                    online_seed=3003, target_seed=4004, env_seed=760)
 
 
-def run_lockstep_r2d2(rela, synth_atari, agent, act_device, sample_device, cfg=CFG_R2D2, quiet=1.0):
-    replay = rela.RNNPrioritizedReplay(cfg["capacity"], cfg["seed"], cfg["alpha"], cfg["beta"], 0)
-    locker = rela.ModelLocker([agent], act_device)
-    actor = rela.R2D2Actor(locker, cfg["multi_step"], cfg["K"], cfg["gamma"], cfg["seq_len"], cfg["burn_in"], replay)
-    vec = rela.VectorEnv()
-    games = []
-    for g in range(cfg["K"]):
-        ep_len = cfg["episode_lens"][g] if cfg.get("episode_lens") else cfg["episode_len"]
-        game = synth_atari.SyntheticAtariEnv(cfg["env_seed"] + g, 0.0, cfg["num_action"], ep_len)
-        games.append(game)
-        vec.append(game)
+# two lockers x 1 thread x 2 envs on one GPU, as CFG_TWO_LOCKERS: 2 partitions of 16 with seeds 11 and 12, batch 8 = 4 + 4.
+# Partition 0 sees exactly the stream of the single-replay golden (CFG_R2D2).
+CFG_R2D2_TWO_LOCKERS = dict(CFG_R2D2, threads=2, lockers=2, capacity=2 * CFG_R2D2["capacity"], batch=2 * CFG_R2D2["batch"])
+
+
+def run_lockstep_r2d2(rela, synth_atari, agent, act_device, sample_device, cfg=CFG_R2D2, quiet=1.0, prefetch=0):
+    replay = rela.RNNPrioritizedReplay(cfg["capacity"], cfg["seed"], cfg["alpha"], cfg["beta"], prefetch)
+    # cfg["lockers"] / cfg["threads"] (this repo's module only) as in run_lockstep: thread t on locker t % L, env seeds
+    # numbered through; every thread has thread 0's episode lengths, so the partitions fill and park in step
+    L = cfg.get("lockers", 1)
+    lockers = [rela.ModelLocker([agent], act_device) for _ in range(L)]
     ctx = rela.Context()
-    ctx.push_env_thread(rela.BasicThreadLoop(actor, vec, False))
+    games, actors = [], []
+    for t in range(cfg.get("threads", 1)):
+        actor = rela.R2D2Actor(lockers[t % L], cfg["multi_step"], cfg["K"], cfg["gamma"], cfg["seq_len"], cfg["burn_in"],
+                               replay)
+        vec = rela.VectorEnv()
+        for g in range(cfg["K"]):
+            ep_len = cfg["episode_lens"][g] if cfg.get("episode_lens") else cfg["episode_len"]
+            game = synth_atari.SyntheticAtariEnv(cfg["env_seed"] + t * cfg["K"] + g, 0.0, cfg["num_action"], ep_len)
+            games.append(game)
+            vec.append(game)
+        actors.append(actor)
+        ctx.push_env_thread(rela.BasicThreadLoop(actor, vec, False))
     ctx.start()
     rounds = []
     for r in range(cfg["rounds"]):
@@ -221,8 +232,13 @@ def run_lockstep_r2d2(rela, synth_atari, agent, act_device, sample_device, cfg=C
             seq_len=batch.seq_len.cpu().tolist(),
             h0_abs=batch.h0["h0"].cpu().abs().sum(2).reshape(-1).double().tolist(),
             c0_abs=batch.h0["c0"].cpu().abs().sum(2).reshape(-1).double().tolist(),
-            weight=w.cpu().double().tolist(), num_add=replay.num_add(), size=replay.size()))
-        replay.update_priority(torch.linspace(0.5, 2.0, cfg["batch"]) * (1 + 0.25 * r))
+            weight=w.cpu().double().tolist(), num_add=replay.num_add(), size=replay.size(),
+            shapes=dict(s=list(s.shape), eps=list(batch.obs["eps"].shape), legal_move=list(batch.obs["legal_move"].shape),
+                        a=list(batch.action["a"].shape), reward=list(batch.reward.shape),
+                        terminal=list(batch.terminal.shape), bootstrap=list(batch.bootstrap.shape),
+                        h0=list(batch.h0["h0"].shape), c0=list(batch.h0["c0"].shape), seq_len=list(batch.seq_len.shape),
+                        weight=list(w.shape))))
+        replay.update_priority(torch.linspace(0.5, 2.0, cfg["batch"] // L).repeat(L) * (1 + 0.25 * r))
     ctx.terminate()
     ctx.resume()
     t0 = time.time()

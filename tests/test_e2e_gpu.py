@@ -378,7 +378,10 @@ def test_lockstep_r2d2_matches_reference(mods):
     agent = R2D2Agent(lambda dev: AtariLSTMNet(dev, C["num_action"]), "cpu", C["multi_step"], C["gamma"], C["eta"],
                       C["seq_len"], C["burn_in"], 0)
     load_lstm_agent_params(agent)
-    rounds = run_lockstep_r2d2(rela, synth, agent, "cuda:0", "cuda:0")
+    _check_r2d2_rounds(run_lockstep_r2d2(rela, synth, agent, "cuda:0", "cuda:0"), gold)
+
+
+def _check_r2d2_rounds(rounds, gold):
     assert len(rounds) == len(gold["expect"])
     for r, (got, exp) in enumerate(zip(rounds, gold["expect"])):
         for key in ("s_sum", "a", "terminal", "bootstrap", "legal_sum", "seq_len", "num_add", "size", "eps_sum"):
@@ -387,6 +390,63 @@ def test_lockstep_r2d2_matches_reference(mods):
         np.testing.assert_allclose(got["h0_abs"], exp["h0_abs"], rtol=1e-4, atol=1e-4)
         np.testing.assert_allclose(got["c0_abs"], exp["c0_abs"], rtol=1e-4, atol=1e-4)
         np.testing.assert_allclose(got["weight"], exp["weight"], rtol=1e-3, err_msg="IS weights, round %d" % r)
+
+
+def _r2d2_agent(C):
+    from e2e_lockstep import load_lstm_agent_params
+    from rela_amd.pyrela.net import AtariLSTMNet
+    from rela_amd.pyrela.r2d2 import R2D2Agent
+
+    agent = R2D2Agent(lambda dev: AtariLSTMNet(dev, C["num_action"]), "cpu", C["multi_step"], C["gamma"], C["eta"],
+                      C["seq_len"], C["burn_in"], 0)
+    return load_lstm_agent_params(agent, C)
+
+
+def test_lockstep_r2d2_with_prefetch_matches_reference(mods):
+    """RNNPrioritizedReplay(..., prefetch = 2), as test_lockstep_with_prefetch_matches_reference for the transition form:
+    update_priority queues the next sample behind itself and sample() hands that batch over.  The library sees the same
+    calls in the same order as with prefetch = 0, so every round must still equal what the REAL reference (prefetch 0)
+    returned."""
+    from e2e_lockstep import CFG_R2D2, run_lockstep_r2d2
+
+    rela, synth = mods
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "e2e_lockstep_r2d2.json")))
+    assert gold["cfg"] == CFG_R2D2
+    _check_r2d2_rounds(run_lockstep_r2d2(rela, synth, _r2d2_agent(CFG_R2D2), "cuda:0", "cuda:0", prefetch=2), gold)
+
+
+def test_r2d2_two_lockers_give_two_partitions_with_reference_parity(mods):
+    """test_two_lockers_in_one_process_give_two_partitions_with_reference_parity for sequences: two lockers on cuda:0,
+    one thread of two envs each, so the replay owns two partitions (capacity 16, seeds 11 and 12) and a batch of 8 is 4
+    sequences of each.  Partition 0 is fed by thread 0 -- the envs, capacity, seed and per-round priorities of the
+    single-replay golden recorded from the REAL reference -- so the first half of every batch must be that golden's
+    batch and its importance weights the golden's up to the common factor of the global normalisation.  The time-major
+    tensors and h0 / c0 join along axis 1, seq_len along axis 0."""
+    from e2e_lockstep import CFG_R2D2, CFG_R2D2_TWO_LOCKERS as C, run_lockstep_r2d2
+
+    rela, synth = mods
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "e2e_lockstep_r2d2.json")))
+    assert gold["cfg"] == CFG_R2D2
+    rounds = run_lockstep_r2d2(rela, synth, _r2d2_agent(C), "cuda:0", "cuda:0", C)
+    assert len(rounds) == len(gold["expect"])
+    B, h = C["batch"], C["batch"] // 2
+    T = C["burn_in"] + C["seq_len"] + C["multi_step"]
+    A = C["num_action"]
+    for r, (got, exp) in enumerate(zip(rounds, gold["expect"])):
+        for key in ("s_sum", "a", "terminal", "bootstrap", "legal_sum", "seq_len"):
+            assert got[key][:h] == exp[key], (r, key)
+            assert len(got[key]) == B, (r, key)
+        assert np.array_equal(np.float32(got["reward"][:h]), np.float32(exp["reward"])), r
+        np.testing.assert_allclose(got["h0_abs"][:h], exp["h0_abs"], rtol=1e-4, atol=1e-4)
+        np.testing.assert_allclose(got["c0_abs"][:h], exp["c0_abs"], rtol=1e-4, atol=1e-4)
+        w = np.asarray(got["weight"])
+        assert w.max() == 1.0 and (w > 0).all()
+        np.testing.assert_allclose(w[:h] / w[:h].max(), np.asarray(exp["weight"]) / max(exp["weight"]), rtol=1e-3,
+                                   err_msg="IS weights of partition 0, round %d" % r)
+        assert got["shapes"] == dict(s=[T, B, 4, 84, 84], eps=[T, B, 1], legal_move=[T, B, A], a=[T, B], reward=[T, B],
+                                     terminal=[T, B], bootstrap=[T, B], h0=[1, B, 512], c0=[1, B, 512], seq_len=[B],
+                                     weight=[B]), r
+        assert got["num_add"] == 2 * exp["num_add"] and got["size"] == 2 * exp["size"], r
 
 
 def test_lockstep_r2d2_c4_shape_matches_reference(mods):
