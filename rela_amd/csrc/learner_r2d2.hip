@@ -769,6 +769,11 @@ int forward_pre(rela_r2d2_learner* l, int which, int Bn, const uint8_t* obs, con
   return RELA_OK;
 }
 
+// Launch census (prof.h): launch_gemm counts every f32 GEMM under one name, so the two split-K GEMMs of the per-step
+// recurrence are counted under these as well -- a test tells the per-step path from the chains by them.
+constexpr const char* kCensusRecFwdGemm = "gemm_lds<TileRec, ProbRecFwd>";
+constexpr const char* kCensusRecBwdGemm = "gemm_lds<TileRec, ProbRecBwd>";
+
 int forward_rec_steps(rela_r2d2_learner* l, int which, int Bn, const uint8_t* term, bool save, hipStream_t s) {
   const int T = l->T, burn = l->burn;
   float *H = l->Hs[which], *Cc = l->Cs[which], *gx = l->gxs[which];
@@ -776,14 +781,17 @@ int forward_rec_steps(rela_r2d2_learner* l, int which, int Bn, const uint8_t* te
   const int cell_grid = ceil_div((int64_t)Bn * kHid, 256);
   for (int t = 0; t < T; ++t) {
     if (t == burn && burn > 0) {  // state after the burn-in: zero it where the burn-in was a dummy
+      note_launch("zero_hidden_where_terminal");
       hipLaunchKernelGGL(zero_hidden_where_terminal, dim3(cell_grid), dim3(256), 0, s, term + (size_t)(burn - 1) * Bn,
                          Bn, H + t * blk, Cc + t * blk);
     }
     ProbRecFwd p{};
     p.M = Bn, p.N = kGates, p.K = kHid;
     p.h = H + t * blk, p.whhT = l->whhT[which], p.part = l->rec_part;
+    note_launch(kCensusRecFwdGemm);
     launch_gemm<TileRec>(p, kRecSplitF, s, "learner_lstm_rec_fwd");
     ProfScope prof("learner_lstm_cell", s);
+    note_launch("lstm_cell_fwd");
     hipLaunchKernelGGL(lstm_cell_fwd, dim3(cell_grid), dim3(256), 0, s, gx + (size_t)t * Bn * kGates,
                        (const float*)l->rec_part, kRecSplitF, Bn, (const float*)(Cc + t * blk), Cc + (t + 1) * blk,
                        H + (t + 1) * blk, (save && t >= burn) ? 1 : 0);
@@ -810,6 +818,7 @@ int forward_both(rela_r2d2_learner* l, int Bn, const uint8_t* obs, const float* 
     }
     ca.term = term, ca.tmo = l->rec_bar, ca.bar = l->rec_chain_bar, ca.T = T, ca.Tpad = Tpad, ca.Bn = Bn, ca.burn = burn;
     ProfScope prof("learner_lstm_rec_persist", s);
+    note_launch("lstm_rec_chain");
     hipLaunchKernelGGL(lstm_rec_chain<true>, dim3(8 * kChainBlocks), dim3(kRecThreads), 0, s, ca);
     RELA_LAUNCH_CHECK();
   } else {
@@ -1134,12 +1143,14 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
     ba.ga = ga_tr, ba.d_o = l->d_o, ba.whh = P.w_hh, ba.C = Cc, ba.dc_rec = l->dc_rec;
     ba.bar = l->rec_chain_bar, ba.tmo = l->rec_bar, ba.Tt = Tt, ba.Bn = Bn, ba.burn = burn;
     ProfScope prof("learner_lstm_bptt_persist", s);
+    note_launch("lstm_bptt_chain");
     hipLaunchKernelGGL(lstm_bptt_chain<false>, dim3(8 * kBpttBlocks), dim3(kRecThreads), 0, s, ba, Tpad_c);
   } else
   for (int t = Tt - 1; t >= 0; --t) {
     const int gs = burn + t;  // global step
     {
       ProfScope prof("learner_lstm_cell_bwd", s);
+      note_launch("lstm_cell_bwd");
       hipLaunchKernelGGL(lstm_cell_bwd, dim3(cell_grid), dim3(256), 0, s, ga_tr + (size_t)t * Bn * kGates,
                          (const float*)(l->d_o + (size_t)t * blk), (const float*)l->rec_part,
                          t == Tt - 1 ? 0 : kRecSplitB, Bn, (const float*)(Cc + (size_t)(gs + 1) * blk),
@@ -1149,6 +1160,7 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
       ProbRecBwd p{};
       p.M = Bn, p.N = kHid, p.K = kGates;
       p.dg = ga_tr + (size_t)t * Bn * kGates, p.whh = P.w_hh, p.part = l->rec_part;
+      note_launch(kCensusRecBwdGemm);
       launch_gemm<TileRec>(p, kRecSplitB, s, "learner_lstm_rec_bwd");
     }
   }

@@ -90,12 +90,17 @@ def apex_loss(p_on, p_tg, batch, weight, gamma, multi_step, dtype):
     return loss.detach(), err.detach().abs(), per_sample.detach(), {k: v.grad for k, v in on.items()}
 
 
-def _unroll(p, s, legal, h, c, dtype):
-    """[T, B, ...] frames from the state (h, c) [B, 512] -> (q [T, B, A], h, c): AtariLSTMNet.unroll_rnn + dueling heads"""
+def _unroll(p, s, legal, h, c, dtype, hooks=None, t0=0):
+    """[T, B, ...] frames from the state (h, c) [B, 512] -> (q [T, B, A], h, c): AtariLSTMNet.unroll_rnn + dueling heads.
+    hooks (optional, for tests that restate a defect; t0 = the batch's time index of s[0]):
+      "trunk": f(p, frames, dtype) in place of trunk;  "state": f(t0 + t, h, c) -> (h, c) entering step t0 + t"""
+    hooks = hooks or {}
     T, B = s.shape[:2]
-    x = trunk(p, s.reshape(T * B, *s.shape[2:]), dtype).view(T, B, FLAT)
+    x = hooks.get("trunk", trunk)(p, s.reshape(T * B, *s.shape[2:]), dtype).view(T, B, FLAT)
     outs = []
     for t in range(T):
+        if "state" in hooks:
+            h, c = hooks["state"](t0 + t, h, c)
         h, c = lstm_cell(p, x[t], h, c)
         outs.append(h)
     o = torch.stack(outs) if T else x.new_zeros(0, B, HIDDEN)
@@ -103,9 +108,24 @@ def _unroll(p, s, legal, h, c, dtype):
     return q, h, c
 
 
-def r2d2_loss(p_on, p_tg, batch, weight, gamma, multi_step, eta, seq_len, burn_in, dtype):
+def r2d2_loss(p_on, p_tg, batch, weight, gamma, multi_step, eta, seq_len, burn_in, dtype, hooks=None):
     """-> (loss, priority [B], loss per sequence [B], {key: grad of the online parameters}) of R2D2Agent.loss with the
-    loss (per_seq * weight).mean(); batch RNNTransition-shaped, time-major (tests/test_r2d2_learner_gpu.py)"""
+    loss (per_seq * weight).mean(); batch RNNTransition-shaped, time-major (tests/test_r2d2_learner_gpu.py).
+    hooks (optional, for tests that restate a defect; net = "online" | "target", t = time index in the batch):
+      "trunk": f(net, p, frames, dtype) in place of trunk (a parameter it never uses gets the gradient None)
+      "state": f(net, t, h, c) -> (h, c) entering step t
+      "keep": f(keep [B, 1]) -> the factor on the state after the burn-in
+      "per_seq": f(per_seq [B]) -> the losses that enter the weighted mean (the returned ones stay as computed)"""
+    hooks = hooks or {}
+
+    def hk(net):
+        out = {}
+        if "trunk" in hooks:
+            out["trunk"] = lambda p, frames, dt: hooks["trunk"](net, p, frames, dt)
+        if "state" in hooks:
+            out["state"] = lambda t, h, c: hooks["state"](net, t, h, c)
+        return out
+
     on, tg = params_as(p_on, dtype, True), params_as(p_tg, dtype)
     s = batch.obs["s"].cpu()
     legal = _t(batch.obs["legal_move"].cpu(), dtype)
@@ -117,16 +137,18 @@ def r2d2_loss(p_on, p_tg, batch, weight, gamma, multi_step, eta, seq_len, burn_i
         hon, con, htg, ctg = h0, c0, h0, c0
     else:
         with torch.no_grad():
-            _, hon, con = _unroll(on, s[:b], legal[:b], h0, c0, dtype)
-            _, htg, ctg = _unroll(tg, s[:b], legal[:b], h0, c0, dtype)
+            _, hon, con = _unroll(on, s[:b], legal[:b], h0, c0, dtype, hk("online"))
+            _, htg, ctg = _unroll(tg, s[:b], legal[:b], h0, c0, dtype, hk("target"))
         keep = (1 - terminal[b - 1]).unsqueeze(1)  # dummy burn-in at an episode's start
+        if "keep" in hooks:
+            keep = hooks["keep"](keep)
         hon, con, htg, ctg = hon * keep, con * keep, htg * keep, ctg * keep
-    q_on, _, _ = _unroll(on, s[b:], legal[b:], hon, con, dtype)
+    q_on, _, _ = _unroll(on, s[b:], legal[b:], hon, con, dtype, hk("online"), b)
     a_train = batch.action["a"].cpu()[b:]
     online_qa = q_on.gather(2, a_train.unsqueeze(2)).squeeze(2)
     with torch.no_grad():
         greedy = _greedy(q_on, legal[b:], 2)
-        q_tg, _, _ = _unroll(tg, s[b:], legal[b:], htg, ctg, dtype)
+        q_tg, _, _ = _unroll(tg, s[b:], legal[b:], htg, ctg, dtype, hk("target"), b)
         target_qa = q_tg.gather(2, greedy.unsqueeze(2)).squeeze(2)
     reward, boot = _t(batch.reward.cpu(), dtype)[b:], _t(batch.bootstrap.cpu(), dtype)[b:]
     gamma_n = gamma ** multi_step
@@ -137,7 +159,8 @@ def r2d2_loss(p_on, p_tg, batch, weight, gamma, multi_step, eta, seq_len, burn_i
         cols.append((target - online_qa[i]) * (1 - pad))
     err = torch.stack(cols, 1)
     per_seq = F.smooth_l1_loss(err, torch.zeros_like(err), reduction="none").sum(1)
-    loss = (per_seq * _t(weight.cpu(), dtype)).mean()
+    loss = (hooks["per_seq"](per_seq) if "per_seq" in hooks else per_seq) * _t(weight.cpu(), dtype)
+    loss = loss.mean()
     loss.backward()
     with torch.no_grad():
         pr = err.abs()

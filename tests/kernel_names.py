@@ -11,3 +11,12 @@ SPLIT_BF16 = frozenset({CONV12, CONV12_JOBS, "conv_bf16s<Conv3F>", "conv3_bf16s_
                         "wgrad_conv3_bf16", "dgrad_conv2_bf16", "dgrad_conv3_bf16"})
 X3_FFNET = frozenset({"conv12_s3", "conv3_img_s3", "gemm_s3<fc>"})
 X3_LSTM = frozenset({"conv12_s3", "conv3_img_s3", "gemm_s3<gates_x>"})
+
+# The R2D2 learner's LSTM recurrence (csrc/learner_r2d2.hip): one persistent launch per half of the step, or one split-K
+# GEMM + one cell kernel per time step (the two GEMMs are counted under "gemm_lds (f32)" as well, like every f32 GEMM).
+# The per-step forward also launches R2D2_REC_ZERO once per net when there is a burn-in; the chains zero in the kernel.
+R2D2_REC_CHAIN = {"lstm_rec_chain"}
+R2D2_BPTT_CHAIN = {"lstm_bptt_chain"}
+R2D2_REC_STEPS = {"gemm_lds<TileRec, ProbRecFwd>", "lstm_cell_fwd"}
+R2D2_BPTT_STEPS = {"gemm_lds<TileRec, ProbRecBwd>", "lstm_cell_bwd"}
+R2D2_REC_ZERO = "zero_hidden_where_terminal"
