@@ -622,6 +622,42 @@ int rela_debug_trunk_backward(int frames, int mode, int lanes, int fast_wgrad_mi
                               const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b, float* g_c3w,
                               float* g_c3b, float* d_a2, float* d_a1, void* stream);
 
+/* Test tap: what rela_apex_learner_loss launches after its three forwards -- TD error, priorities, loss and the head
+ * gradient d_ha (csrc/learner_common.h: learner_td_loss_grad, or td_kernel + learner_loss_grad) -- with the Q tables as
+ * inputs of the call.  All pointers are device pointers; the call synchronises.
+ *   q, qno, qnt      f32 [batch][A]   online(obs), online(next_obs), target(next_obs)
+ *   nlegal, legal    f32 [batch][A]   legal moves of next_obs / obs
+ *   act              i64 [batch];  reward, bootstrap, weight   f32 [batch]
+ *   td, prio         out: f32 [batch]   signed TD error and its absolute value
+ *   d_ha             out: f32 [batch][32]   columns 0..A-1 = d loss / d fc_a, 31 = d loss / d fc_v, A..30 zero
+ *   loss             out: f32 [1]   mean(smooth_l1(td) * weight)
+ * form: 0 = as the learner chooses (batch <= 1024: the fused kernel), 1 = learner_td_loss_grad, 2 = td_kernel +
+ * learner_loss_grad.  vr_eps: value rescaling of the target, <= 0 off.  1 <= batch <= 32,768, 1 <= A <= 31.         */
+int rela_debug_loss_grad(int batch, int A, int form, const float* q, const float* qno, const float* qnt,
+                         const float* nlegal, const int64_t* act, const float* reward, const float* bootstrap,
+                         float gamma_n, float vr_eps, const float* weight, const float* legal, float* td, float* prio,
+                         float* d_ha, float* loss, void* stream);
+/* Test tap: the backward pass between d_ha and d_a3 (csrc/learner.hip: head_fc_backward, the four head / fc GEMMs of
+ * rela_apex_learner_grad), then the two column sums through the learner's multi-job launcher and head_bias_grad, as one
+ * call whose inputs are the forward's activations, so their > 0 patterns -- the ReLU masks -- are data of the call.
+ * All pointers are device pointers; the call allocates its own scratch (the fc weight in a3's column order is packed
+ * with the learner's permute_weights), synchronises both lanes and frees it.
+ *   d_ha     f32 [batch][32]   as rela_debug_loss_grad leaves it; columns A..30 take no part
+ *   h, a3    f32 [batch][512], [batch][49][64]   relu(fc), relu(conv3) channel-last (csrc/ffnet_layout.h)
+ *   fc_a_w, fc_v_w, fc_w   [A][512], [1][512], [512][3136]   (state_dict layout)
+ *   g_fc_a_w .. g_fc_b     out: the six gradients in state_dict layout ([A][512], [A], [1][512], [1], [512][3136], [512])
+ *   d_h, d_a3              out: [batch][512] masked by h > 0, [batch][49][64] channel-last masked by a3 > 0
+ * mode: 0 f32, 1 bf16x2, 2 f32x3 (the learner's precision modes).  lanes: 1 = the weight gradients and the column sums on
+ * a side lane, as rela_apex_learner_grad runs them; 0 = one lane (RELA_LEARNER_LANES=1).
+ * 1 <= batch <= 32,768, 1 <= A <= 31.                                                                              */
+int rela_debug_head_fc_backward(int batch, int A, int mode, int lanes, const float* d_ha, const float* h, const float* a3,
+                                const float* fc_a_w, const float* fc_v_w, const float* fc_w, float* g_fc_a_w,
+                                float* g_fc_a_b, float* g_fc_v_w, float* g_fc_v_b, float* g_fc_w, float* g_fc_b, float* d_h,
+                                float* d_a3, void* stream);
+/* Debug / tests: the learner's own d_ha [B][32], d_h [B][512] and d_a3 [B][49][64] of the last rela_apex_learner_grad
+ * (d_ha: of the last rela_apex_learner_loss).  Valid until the next rela_apex_learner_loss.                        */
+int rela_apex_learner_debug_head_grads(rela_apex_learner* l, float** d_ha, float** d_h, float** d_a3);
+
 /* ===================================================================================
  * R2D2 learner step  --  pyrela/main.py:206-251 with R2D2Agent.loss (pyrela/r2d2.py:189-206):
  * td_err (:122-187: burn-in unroll without gradient, state zeroed where terminal[burn_in-1], training

@@ -76,6 +76,84 @@ int repack(rela_apex_learner* l, bool online, bool target, hipStream_t s) {
   }
   return RELA_OK;
 }
+
+// ---- loss and head gradient d_ha from the three Q tables: what rela_apex_learner_loss launches after its forwards ----
+// fused: learner_td_loss_grad, one workgroup (the learner: batch <= kFusedLossMaxBatch); else td_from_q + learner_loss_grad
+constexpr int kFusedLossMaxBatch = 1024;
+int launch_loss_grad(int Bn, int A, bool fused, const float* q_on, const float* q_no, const float* q_nt, const float* nlegal,
+                     const int64_t* act, const float* reward, const float* boot, float gamma_n, float vr_eps,
+                     const float* weight, const float* legal, float* td, float* prio, float* d_ha, float* loss, hipStream_t s) {
+  if (fused) {
+    ProfScope prof("learner_loss_grad", s);
+    note_launch("learner_td_loss_grad");
+    hipLaunchKernelGGL(learner_td_loss_grad, dim3(1), dim3(1024), 0, s, Bn, A, q_on, q_no, q_nt, nlegal, act, reward, boot,
+                       gamma_n, vr_eps, weight, legal, td, prio, d_ha, loss);
+  } else {
+    int rc = td_from_q(Bn, A, 0, q_on, q_no, q_nt, nlegal, act, reward, boot, gamma_n, vr_eps, td, prio, s);
+    if (rc != RELA_OK) return rc;
+    note_launch("td_kernel");
+    ProfScope prof("learner_loss_grad", s);
+    note_launch("learner_loss_grad");
+    hipLaunchKernelGGL(learner_loss_grad, dim3(1), dim3(kLT), 0, s, (const float*)td, weight, act, legal, Bn, A, d_ha, loss);
+  }
+  return RELA_OK;
+}
+
+// ---- the backward pass between d_ha and d_a3: the dueling heads and the fc layer, four GEMMs and two column sums ------
+struct HeadFcBwd {
+  int Bn, A;
+  const float* d_ha;            // [Bn][32] from the loss kernel: columns 0..A-1 = fc_a, 31 = fc_v
+  const float *h, *a3;          // relu(fc) [Bn][512], relu(conv3) [Bn][49][64] channel-last (ffnet_layout.h)
+  const float *a_w, *v_w;       // fc_a.weight [A][512], fc_v.weight [512] (state_dict layout)
+  const float* wfcp;            // the fc weight in a3's column order (permute_weights, kPermFc)
+  float *d_h, *d_a3;            // out: [Bn][512] masked by h > 0, [Bn][49][64] masked by a3 > 0
+  float *g_a_w, *g_v_w, *g_fc_w, *g_fc_b;  // out: gradients, state_dict layout
+  float* s32;                   // the column sums of d_ha, for head_bias_grad after the queued sums have run
+  bool g3 = false, g6 = false;  // the GEMMs on bf16 MFMA with two-part (bf16x2) / three-part (f32x3) operands, else f32
+  hipEvent_t ev_dh = nullptr;   // (two lanes) d_h is ready
+};
+// s: the data-gradient chain; sw: the lane of the weight gradients (== s: one lane).  The two bias gradients' column
+// sums are queued on `sums` for the launch pair at the end of trunk_backward.
+void head_fc_backward(const HeadFcBwd& t, hipStream_t s, hipStream_t sw, ColsumJobs* sums) {
+  const int Bn = t.Bn;
+  // heads: d_h, dWh, db
+  {
+    ProbHeadDgrad p{};
+    p.M = Bn, p.N = 512, p.K = 32;
+    p.d_ha = t.d_ha, p.a_w = t.a_w, p.v_w = t.v_w, p.h = t.h, p.d_h = t.d_h, p.A = t.A;
+    if (t.g3) (void)gemm3::launch_gemm<Tile3Dgrad>(p, 1, s, "learner_dgrad_heads");
+    else if (t.g6) (void)gemm3::launch_gemm<Tile6Dgrad>(p, 1, s, "learner_dgrad_heads");
+    else launch_gemm<TileDgrad>(p, 1, s, "learner_dgrad_heads");
+  }
+  {
+    ProbHeadWgrad p{};
+    p.M = 32, p.N = 512, p.K = Bn;
+    p.d_ha = t.d_ha, p.h = t.h, p.g_a_w = t.g_a_w, p.g_v_w = t.g_v_w, p.A = t.A;
+    if (t.g3) (void)gemm3::launch_gemm<Tile3W32>(p, 1, sw, "learner_wgrad_heads");
+    else if (t.g6) (void)gemm3::launch_gemm<Tile6W32>(p, 1, sw, "learner_wgrad_heads");
+    else launch_gemm<TileW32>(p, 1, sw, "learner_wgrad_heads");
+  }
+  sums->add(t.d_ha, Bn, 32, t.s32);
+  if (sw != s) lane_dep(t.ev_dh, s, sw);  // d_h is ready
+  // fc: d_a3, dWfc, db
+  {
+    ProbFcDgrad p{};
+    p.M = Bn, p.N = 3136, p.K = 512;
+    p.d_h = t.d_h, p.wfcp = t.wfcp, p.a3 = t.a3, p.d_a3 = t.d_a3;
+    if (t.g3) (void)gemm3::launch_gemm<Tile3Dgrad>(p, 1, s, "learner_dgrad_fc");
+    else if (t.g6) (void)gemm3::launch_gemm<Tile6Dgrad>(p, 1, s, "learner_dgrad_fc");
+    else launch_gemm<TileDgrad>(p, 1, s, "learner_dgrad_fc");
+  }
+  {
+    ProbFcWgrad p{};
+    p.M = 512, p.N = 3136, p.K = Bn;
+    p.d_h = t.d_h, p.a3 = t.a3, p.g_fc_w = t.g_fc_w;
+    if (t.g3) (void)gemm3::launch_gemm<Tile3Wfc>(p, 1, sw, "learner_wgrad_fc");
+    else if (t.g6) (void)gemm3::launch_gemm<Tile6Wfc>(p, 1, sw, "learner_wgrad_fc");
+    else launch_gemm<TileWfc>(p, 1, sw, "learner_wgrad_fc");
+  }
+  sums->add(t.d_h, Bn, 512, t.g_fc_b);
+}
 }  // namespace
 
 namespace {
@@ -309,18 +387,9 @@ extern "C" int rela_apex_learner_loss(rela_apex_learner* l, int batch, const voi
     rc = ffnet_forward_mode(l->online, Bn, obs, legal, q_on, l->ws_on, l->ws_bytes, s, rela_ffnet_precision(l->online) == 2 ? 3 : 0);
     if (rc != RELA_OK) return rc;
   }
-  if (Bn <= 1024) {
-    ProfScope prof("learner_loss_grad", s);
-    hipLaunchKernelGGL(learner_td_loss_grad, dim3(1), dim3(1024), 0, s, Bn, A, (const float*)q_on, (const float*)q_no,
-                       (const float*)q_nt, nlegal, act, reward, boot, l->gamma_n, l->vr_eps, weight_dev, legal, l->td,
-                       priority_dev, l->d_ha, l->loss);
-  } else {
-    rc = td_from_q(Bn, A, 0, q_on, q_no, q_nt, nlegal, act, reward, boot, l->gamma_n, l->vr_eps, l->td, priority_dev, s);
-    if (rc != RELA_OK) return rc;
-    ProfScope prof("learner_loss_grad", s);
-    hipLaunchKernelGGL(learner_loss_grad, dim3(1), dim3(kLT), 0, s, (const float*)l->td, weight_dev, act, legal, Bn,
-                       A, l->d_ha, l->loss);
-  }
+  rc = launch_loss_grad(Bn, A, Bn <= kFusedLossMaxBatch, q_on, q_no, q_nt, nlegal, act, reward, boot, l->gamma_n, l->vr_eps,
+                        weight_dev, legal, l->td, priority_dev, l->d_ha, l->loss, s);
+  if (rc != RELA_OK) return rc;
   if (loss_dev) RELA_HIP(dev_copy2(loss_dev, l->loss, sizeof(float), nullptr, nullptr, 0, s));  // (a kernel, not a blit: common.h)
   if (unsplit_side) lane_dep(l->ev[1], l->side, s);  // the caller's stream owns the workspace again from here
   RELA_LAUNCH_CHECK();
@@ -350,43 +419,13 @@ extern "C" int rela_apex_learner_grad(rela_apex_learner* l, void* stream_) {
   hipStream_t sw = lanes ? l->side : s;  // the weight-gradient lane
   if (lanes) lane_dep(l->ev[2], s, sw);  // d_ha and the forward's activations are ready
 
-  // heads: d_h, dWh, db
-  {
-    ProbHeadDgrad p{};
-    p.M = Bn, p.N = 512, p.K = 32;
-    p.d_ha = l->d_ha, p.a_w = P.a_w, p.v_w = P.v_w, p.h = w.h, p.d_h = l->d_h, p.A = A;
-    if (g3) (void)gemm3::launch_gemm<Tile3Dgrad>(p, 1, s, "learner_dgrad_heads");
-    else if (g6) (void)gemm3::launch_gemm<Tile6Dgrad>(p, 1, s, "learner_dgrad_heads");
-    else launch_gemm<TileDgrad>(p, 1, s, "learner_dgrad_heads");
+  {  // heads and fc: d_h, dWh, d_a3, dWfc; their bias gradients queued on `sums`
+    HeadFcBwd t{};
+    t.Bn = Bn, t.A = A, t.d_ha = l->d_ha, t.h = w.h, t.a3 = w.a3, t.a_w = P.a_w, t.v_w = P.v_w, t.wfcp = l->wfcp;
+    t.d_h = l->d_h, t.d_a3 = l->d_a3, t.g_a_w = Gm[10], t.g_v_w = Gm[8], t.g_fc_w = Gm[6], t.g_fc_b = Gm[7], t.s32 = l->s32;
+    t.g3 = g3, t.g6 = g6, t.ev_dh = l->ev[3];
+    head_fc_backward(t, s, sw, &sums);
   }
-  {
-    ProbHeadWgrad p{};
-    p.M = 32, p.N = 512, p.K = Bn;
-    p.d_ha = l->d_ha, p.h = w.h, p.g_a_w = Gm[10], p.g_v_w = Gm[8], p.A = A;
-    if (g3) (void)gemm3::launch_gemm<Tile3W32>(p, 1, sw, "learner_wgrad_heads");
-    else if (g6) (void)gemm3::launch_gemm<Tile6W32>(p, 1, sw, "learner_wgrad_heads");
-    else launch_gemm<TileW32>(p, 1, sw, "learner_wgrad_heads");
-  }
-  sums.add(l->d_ha, Bn, 32, l->s32);
-  if (lanes) lane_dep(l->ev[3], s, sw);  // d_h is ready
-  // fc: d_a3, dWfc, db
-  {
-    ProbFcDgrad p{};
-    p.M = Bn, p.N = 3136, p.K = 512;
-    p.d_h = l->d_h, p.wfcp = l->wfcp, p.a3 = w.a3, p.d_a3 = l->d_a3;
-    if (g3) (void)gemm3::launch_gemm<Tile3Dgrad>(p, 1, s, "learner_dgrad_fc");
-    else if (g6) (void)gemm3::launch_gemm<Tile6Dgrad>(p, 1, s, "learner_dgrad_fc");
-    else launch_gemm<TileDgrad>(p, 1, s, "learner_dgrad_fc");
-  }
-  {
-    ProbFcWgrad p{};
-    p.M = 512, p.N = 3136, p.K = Bn;
-    p.d_h = l->d_h, p.a3 = w.a3, p.g_fc_w = Gm[6];
-    if (g3) (void)gemm3::launch_gemm<Tile3Wfc>(p, 1, sw, "learner_wgrad_fc");
-    else if (g6) (void)gemm3::launch_gemm<Tile6Wfc>(p, 1, sw, "learner_wgrad_fc");
-    else launch_gemm<TileWfc>(p, 1, sw, "learner_wgrad_fc");
-  }
-  sums.add(l->d_h, Bn, 512, Gm[7]);
   {
     TrunkBwd t{};
     t.Bn = Bn, t.obs = obs, t.a1 = w.a1, t.a2 = w.a2, t.d_a3 = l->d_a3, t.d_a2 = l->d_a2, t.d_a1 = l->d_a1;
@@ -470,6 +509,77 @@ extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fa
   if (sc.side) (void)hipStreamSynchronize(sc.side);
   RELA_HIP(launched);
   RELA_HIP(done);
+  return RELA_OK;
+}
+
+// Test tap: launch_loss_grad on its own, the three Q tables and the batch's fields as inputs of the call.
+extern "C" int rela_debug_loss_grad(int batch, int A, int form, const float* q, const float* qno, const float* qnt,
+                                    const float* nlegal, const int64_t* act, const float* reward, const float* bootstrap,
+                                    float gamma_n, float vr_eps, const float* weight, const float* legal, float* td,
+                                    float* prio, float* d_ha, float* loss, void* stream_) {
+  RELA_CHECK(batch >= 1 && batch <= kTrunkMaxFrames && A >= 1 && A <= 31 && form >= 0 && form <= 2, RELA_EINVAL,
+             "rela_debug_loss_grad: bad arguments (batch %d, A %d, form %d)", batch, A, form);
+  RELA_CHECK(q && qno && qnt && nlegal && act && reward && bootstrap && weight && legal && td && prio && d_ha && loss,
+             RELA_EINVAL, "rela_debug_loss_grad: a pointer is NULL");
+  hipStream_t s = (hipStream_t)stream_;
+  const bool fused = form == 0 ? batch <= kFusedLossMaxBatch : form == 1;
+  if (int rc = launch_loss_grad(batch, A, fused, q, qno, qnt, nlegal, act, reward, bootstrap, gamma_n, vr_eps, weight, legal,
+                                td, prio, d_ha, loss, s))
+    return rc;
+  RELA_LAUNCH_CHECK();
+  RELA_HIP(hipStreamSynchronize(s));
+  return RELA_OK;
+}
+
+// Test tap: head_fc_backward on its own, then the two queued column sums and head_bias_grad as the learner's lanes run
+// them (the side lane's launch pair at the end of trunk_backward's side lane, or the caller's stream with one lane).
+extern "C" int rela_debug_head_fc_backward(int batch, int A, int mode, int lanes, const float* d_ha, const float* h,
+                                           const float* a3, const float* fc_a_w, const float* fc_v_w, const float* fc_w,
+                                           float* g_fc_a_w, float* g_fc_a_b, float* g_fc_v_w, float* g_fc_v_b, float* g_fc_w,
+                                           float* g_fc_b, float* d_h, float* d_a3, void* stream_) {
+  RELA_CHECK(batch >= 1 && batch <= kTrunkMaxFrames && A >= 1 && A <= 31 && mode >= 0 && mode <= 2 &&
+                 (lanes == 0 || lanes == 1),
+             RELA_EINVAL, "rela_debug_head_fc_backward: bad arguments (batch %d, A %d, mode %d, lanes %d)", batch, A, mode,
+             lanes);
+  RELA_CHECK(d_ha && h && a3 && fc_a_w && fc_v_w && fc_w && g_fc_a_w && g_fc_a_b && g_fc_v_w && g_fc_v_b && g_fc_w && g_fc_b &&
+                 d_h && d_a3,
+             RELA_EINVAL, "rela_debug_head_fc_backward: a pointer is NULL");
+  hipStream_t s = (hipStream_t)stream_;
+  TrunkTapScratch sc;
+  float *wfcp = nullptr, *cpart = nullptr, *s32 = nullptr;
+  if (int rc = sc.mem.alloc(&wfcp, 512 * 3136, false)) return rc;
+  if (int rc = sc.mem.alloc(&cpart, (size_t)kColsumBlocks * (32 + 512), false)) return rc;
+  if (int rc = sc.mem.alloc(&s32, 32, false)) return rc;
+  hipLaunchKernelGGL(permute_weights, dim3(ceil_div(512 * 3136, 256)), dim3(256), 0, s, kPermFc, fc_w, wfcp, 512 * 3136);
+  hipStream_t sw = s;
+  if (lanes) {  // as rela_apex_learner_grad: the weight gradients and the column sums on a side lane
+    RELA_HIP(hipStreamCreateWithFlags(&sc.side, hipStreamNonBlocking));
+    for (hipEvent_t& e : sc.ev) RELA_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    sw = sc.side;
+    lane_dep(sc.ev[0], s, sw);  // the inputs (and wfcp) are ready
+  }
+  HeadFcBwd t{};
+  t.Bn = batch, t.A = A, t.d_ha = d_ha, t.h = h, t.a3 = a3, t.a_w = fc_a_w, t.v_w = fc_v_w, t.wfcp = wfcp;
+  t.d_h = d_h, t.d_a3 = d_a3, t.g_a_w = g_fc_a_w, t.g_v_w = g_fc_v_w, t.g_fc_w = g_fc_w, t.g_fc_b = g_fc_b, t.s32 = s32;
+  t.g3 = mode == 1 && gemm_bf16x3_on(), t.g6 = mode == 2, t.ev_dh = sc.ev[1];
+  ColsumJobs sums;
+  head_fc_backward(t, s, sw, &sums);
+  colsum_multi_launch(sums, cpart, sw);
+  hipLaunchKernelGGL(head_bias_grad, dim3(1), dim3(32), 0, sw, (const float*)s32, A, g_fc_a_b, g_fc_v_b);
+  if (lanes) lane_dep(sc.ev[2], sw, s);
+  const hipError_t launched = hipGetLastError();
+  // (the scratch goes away with `sc`: both lanes must be done with it whatever happened)
+  const hipError_t done = hipStreamSynchronize(s);
+  if (sc.side) (void)hipStreamSynchronize(sc.side);
+  RELA_HIP(launched);
+  RELA_HIP(done);
+  return RELA_OK;
+}
+
+extern "C" int rela_apex_learner_debug_head_grads(rela_apex_learner* l, float** d_ha, float** d_h, float** d_a3) {
+  RELA_CHECK(l && d_ha && d_h && d_a3, RELA_EINVAL, "rela_apex_learner_debug_head_grads: bad arguments");
+  RELA_CHECK(l->last_B > 0, RELA_ESTATE, "rela_apex_learner_debug_head_grads: no rela_apex_learner_loss yet");
+  *d_ha = l->d_ha, *d_h = l->d_h, *d_a3 = l->d_a3;
   return RELA_OK;
 }
 

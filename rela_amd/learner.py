@@ -241,6 +241,15 @@ class HipApexLearner(_HipLearner):
         shapes = [(b.value, 400, 32), (b.value, 81, 64), (b.value, 49, 64), (b.value, 512)]
         return [self._view(x.value, sh) for x, sh in zip(p, shapes)]
 
+    def debug_head_grads(self):
+        """f32 views of the learner's own d_ha [B,32], d_h [B,512] and d_a3 [B,49,64] of the last grad(); valid until
+        the next loss()."""
+        C = self._C
+        p = [C.c_void_p() for _ in range(3)]
+        self._call("debug_head_grads", *[C.byref(x) for x in p])
+        b = self.debug_activations()[3].shape[0]
+        return [self._view(x.value, sh) for x, sh in zip(p, [(b, 32), (b, 512), (b, 49, 64)])]
+
     def backward(self, batch, weight):
         """batch: the namespace FFReplay.sample returns (or any object with obs / next_obs / action /
         reward / terminal / bootstrap of cuda tensors); weight: cuda f32[B].  -> (loss[1], priority[B])."""
