@@ -1721,10 +1721,9 @@ using TileFcSmall = gemm::TileCfg<128, 64, 4, 2, false>;
 struct ProbFcFwd : gemm::ProbBase {
   const float *a3, *wt;  // a3 [N][3136] (k = pos*64+c), wt [3136][512]
   float* part;           // [splits][N][512]
-  __device__ float4 loadA(int m, int k) const {
-    return m < M ? *reinterpret_cast<const float4*>(a3 + (size_t)m * 3136 + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  __device__ float4 loadB(int k, int n) const { return *reinterpret_cast<const float4*>(wt + (size_t)k * 512 + n); }
+  __device__ float4 fetchA(int m, int k) const { return gemm::ld4(a3 + (size_t)min(m, M - 1) * 3136 + k); }
+  __device__ float4 fixA(float4 v, int m, int) const { return gemm::keep4(m < M, v); }
+  __device__ float4 fetchB(int k, int n) const { return gemm::ld4(wt + (size_t)k * 512 + n); }
   __device__ void store(int z, int m, int n, float v) const { part[((size_t)z * M + m) * 512 + n] = v; }
 };
 

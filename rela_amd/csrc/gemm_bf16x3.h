@@ -1,7 +1,8 @@
 // gemm_bf16x3.h -- the learner's small f32 GEMMs on the bf16 matrix cores, with the SAME loader functors as gemm_lds.h.
 //
-//   C[M][N] = sum_k A(m,k) * B(k,n),  A and B delivered as f32 by the Problem's loadA / loadB (im2col, transposition and
-//   u8 -> f32 conversion stay index arithmetic in the loader), optional split-K over blockIdx.z -> Problem::store(z, ..).
+//   C[M][N] = sum_k A(m,k) * B(k,n),  A and B delivered by the Problem's fetchA / fetchB and made f32 by its fixA / fixB
+//   (gemm_lds.h, the loader contract: im2col and transposition stay index arithmetic in the fetch), optional split-K
+//   over blockIdx.z -> Problem::store(z, ..).
 //
 // gemm_lds.h multiplies on v_mfma_f32_16x16x4_f32 (157 TFLOP/s peak); at the learner's sizes (batch 512: K = 512 for
 // the fc layer, 25 k - 41 k for the conv weight gradients, 64 - 512 output rows) its blocks also wait out every K-chunk's
@@ -68,8 +69,8 @@ __device__ __forceinline__ void split4x3(float4 v, uint2& hi, uint2& mid, uint2&
   lo = make_uint2(__builtin_bit_cast(uint32_t, la), __builtin_bit_cast(uint32_t, lb));
 }
 
-// AMC as in gemm_lds.h: true = loadA(k, m) returns A[m..m+3][k] (m-contiguous, k-major image, transposed reads);
-// false = loadA(m, k) returns A[m][k..k+3] (k-contiguous, [m][k] image, row reads).  B: loadB(k, n) -> B[k][n..n+3].
+// AMC as in gemm_lds.h: true = A(k, m) is A[m..m+3][k] (m-contiguous, k-major image, transposed reads);
+// false = A(m, k) is A[m][k..k+3] (k-contiguous, [m][k] image, row reads).  B(k, n) is B[k][n..n+3].
 // PARTS = 2: the split-bf16 fast arithmetic above.  PARTS = 3: every f32 operand as THREE bf16 parts (hi, mid, lo: an exact
 // split, see gemm_f32emu.h) and the six products with i + j <= 2, the five small ones in accumulators of their own:
 // f32 accuracy at 16 / 6 the f32 MFMA rate -- the learner's GEMMs of the f32x3 mode.
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(kT) void gemm_bf16x3(const P p, const GridMap gm) {
   const int wave = tid >> 6, lane = tid & 63;
   const int li = lane & 15, g = lane >> 4;
   const int wm = wave / T::WN, wn = wave % T::WN;
-  const int m0 = by * T::BM, n0 = bx * T::BN;
+  const int bm0 = by * T::BM, bn0 = bx * T::BN;
   const int nch = (p.K + BK - 1) / BK;
   const int c0 = bz * p.kslice;
   const int c1 = min(nch, c0 + p.kslice);
@@ -146,47 +147,55 @@ __global__ __launch_bounds__(kT) void gemm_bf16x3(const P p, const GridMap gm) {
   // Staging registers: D chunks in flight.  A chunk is 24 (or fewer) MFMAs per wave -- far less than one load's
   // latency -- and these GEMMs have only a handful of chunks per block (fc at batch 512: 16), so with ONE chunk
   // ahead (gemm_lds.h) every chunk waited out its loads: 29 us for the fc weight gradient, 16 x ~1.5 us.  Chunk c of
-  // the block lives in register set (c - c0) % D; the chunk loop is unrolled by D so that the sets are named statically.
+  // the block lives in register set (c - c0) % D (gemm::chunk_ring).  The sets hold what the Problem's fetchA / fetchB
+  // return (gemm_lds.h, the loader contract: unconditional loads, so the waits in the chunk loop are counted and D - 1
+  // chunks stay outstanding); fixA / fixB and the bf16 split run when a set goes to LDS.
   constexpr int D = 4;
-  float4 ra[D][T::A_IT], rb[D][T::B_IT];
+  typename P::StageA ra[D][T::A_IT];
+  typename P::StageB rb[D][T::B_IT];
   auto gload = [&](int ch, auto set) {
     constexpr int S = decltype(set)::value;
-    const int k0 = ch * BK;
+    const int k0 = ch * BK, m0 = bm0, n0 = bn0;
 #pragma unroll
     for (int j = 0; j < T::A_IT; ++j) {
       const int idx = min(tid + j * kT, T::A_V4 - 1);  // (clamped, not predicated: a surplus thread repeats a neighbour)
       if constexpr (T::AMC) {
         const int kr = idx / (T::BM / 4), q = idx % (T::BM / 4);
-        ra[S][j] = p.loadA(k0 + kr, m0 + 4 * q);
+        ra[S][j] = p.fetchA(k0 + kr, m0 + 4 * q);
       } else {
         const int r = idx >> 3, q = idx & 7;
-        ra[S][j] = p.loadA(m0 + r, k0 + 4 * q);
+        ra[S][j] = p.fetchA(m0 + r, k0 + 4 * q);
       }
     }
 #pragma unroll
     for (int j = 0; j < T::B_IT; ++j) {
       const int idx = min(tid + j * kT, T::B_V4 - 1);
       const int kr = idx / (T::BN / 4), q = idx % (T::BN / 4);
-      rb[S][j] = p.loadB(k0 + kr, n0 + 4 * q);
+      rb[S][j] = p.fetchB(k0 + kr, n0 + 4 * q);
     }
   };
-  auto sstore = [&](int buf, auto set) {
+  auto sstore = [&](int buf, int ch, auto set) {
     constexpr int S = decltype(set)::value;
+    const int z = gemm::store_point();  // (keeps the fix-ups, and their waits, here)
+    const int k0 = ch * BK + z, m0 = bm0 + z, n0 = bn0 + z;
     uint8_t* base = smem + buf * T::BUF;
 #pragma unroll
     for (int j = 0; j < T::A_IT; ++j) {
       const int idx = min(tid + j * kT, T::A_V4 - 1);
       uint2 hi, mid, lo;
-      if constexpr (T::PARTS == 3) split4x3(ra[S][j], hi, mid, lo);
-      else split4(ra[S][j], hi, lo);
+      float4 v;
       int off;
       if constexpr (T::AMC) {
         const int kr = idx / (T::BM / 4), q = idx % (T::BM / 4);
+        v = p.fixA(ra[S][j], k0 + kr, m0 + 4 * q);
         off = krow(kr) * T::LDA + q * 8;
       } else {
         const int r = idx >> 3, q = idx & 7;
+        v = p.fixA(ra[S][j], m0 + r, k0 + 4 * q);
         off = r * T::LDA + q * 8;
       }
+      if constexpr (T::PARTS == 3) split4x3(v, hi, mid, lo);
+      else split4(v, hi, lo);
       *reinterpret_cast<uint2*>(base + off) = hi;
       if constexpr (T::PARTS == 3) *reinterpret_cast<uint2*>(base + T::A_HALF + off) = mid;
       *reinterpret_cast<uint2*>(base + (T::PARTS - 1) * T::A_HALF + off) = lo;
@@ -197,8 +206,9 @@ __global__ __launch_bounds__(kT) void gemm_bf16x3(const P p, const GridMap gm) {
       const int idx = min(tid + j * kT, T::B_V4 - 1);
       const int kr = idx / (T::BN / 4), q = idx % (T::BN / 4);
       uint2 hi, mid, lo;
-      if constexpr (T::PARTS == 3) split4x3(rb[S][j], hi, mid, lo);
-      else split4(rb[S][j], hi, lo);
+      const float4 v = p.fixB(rb[S][j], k0 + kr, n0 + 4 * q);
+      if constexpr (T::PARTS == 3) split4x3(v, hi, mid, lo);
+      else split4(v, hi, lo);
       const int off = krow(kr) * T::LDB + q * 8;
       *reinterpret_cast<uint2*>(bb + off) = hi;
       if constexpr (T::BPARTS == 3) *reinterpret_cast<uint2*>(bb + T::B_HALF + off) = mid;
@@ -231,21 +241,8 @@ __global__ __launch_bounds__(kT) void gemm_bf16x3(const P p, const GridMap gm) {
       if constexpr (T::PARTS == 3) accs[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 
-  using S0 = std::integral_constant<int, 0>;
-  using S1 = std::integral_constant<int, 1>;
-  using S2 = std::integral_constant<int, 2>;
-  using S3 = std::integral_constant<int, 3>;
-  if (c0 < c1) gload(c0, S0{});
-  if (c0 + 1 < c1) gload(c0 + 1, S1{});
-  if (c0 + 2 < c1) gload(c0 + 2, S2{});
-  if (c0 + 3 < c1) gload(c0 + 3, S3{});
-  if (c0 < c1) sstore(0, S0{});
-  __syncthreads();
-  // one chunk: LDS[buf] holds chunk `cur` (stored a step ago from set `cs`, which is free now): refill that set with
-  // chunk cur + D, multiply chunk cur, store chunk cur + 1 (set `ns`, loaded D - 1 steps ago) into the other buffer
-  auto step = [&](int cur, auto cs, auto ns) {
-    const int buf = (cur - c0) & 1;
-    if (cur + D < c1) gload(cur + D, cs);
+  // one chunk: LDS[buf] holds it
+  auto mma = [&](int buf, int) {
     const uint8_t* base = smem + buf * T::BUF;
     const uint8_t* bb = base + T::PARTS * T::A_HALF;
     bf16x8 bp[T::TN][T::BPARTS];  // [..][0] = hi ... [..][BPARTS - 1] = lo
@@ -284,15 +281,9 @@ __global__ __launch_bounds__(kT) void gemm_bf16x3(const P p, const GridMap gm) {
         }
       }
     }
-    if (cur + 1 < c1) sstore(buf ^ 1, ns);
-    __syncthreads();
   };
-  for (int base = c0; base < c1; base += D) {  // (the conditions below are block-uniform)
-    step(base, S0{}, S1{});
-    if (base + 1 < c1) step(base + 1, S1{}, S2{});
-    if (base + 2 < c1) step(base + 2, S2{}, S3{});
-    if (base + 3 < c1) step(base + 3, S3{}, S0{});
-  }
+  // (a block whose slice is empty fetches nothing and stores its zeros: the split reductions read every split)
+  if (c0 < c1) gemm::chunk_ring<D>(c0, c1, gload, sstore, mma);
 
 #pragma unroll
   for (int t = 0; t < T::TM; ++t)
@@ -300,8 +291,8 @@ __global__ __launch_bounds__(kT) void gemm_bf16x3(const P p, const GridMap gm) {
     for (int u = 0; u < T::TN; ++u)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int m = m0 + (wm * T::TM + t) * 16 + g * 4 + r;
-        const int n = n0 + (wn * T::TN + u) * 16 + li;
+        const int m = bm0 + (wm * T::TM + t) * 16 + g * 4 + r;
+        const int n = bn0 + (wn * T::TN + u) * 16 + li;
         if (m < p.M && n < p.N) {
           if constexpr (T::PARTS == 3) p.store(bz, m, n, acc[t][u][r] + accs[t][u][r]);
           else p.store(bz, m, n, acc[t][u][r]);

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 #include "prof.h"
@@ -18,11 +19,27 @@ constexpr int BK = 32;    // K chunk staged per barrier (8 MFMA k-steps)
 
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+// a fix-up's zero: a select on a value that is already in registers (see the loader contract below)
+__device__ __forceinline__ float4 keep4(bool in_range, float4 v) {
+  return make_float4(in_range ? v.x : 0.f, in_range ? v.y : 0.f, in_range ? v.z : 0.f, in_range ? v.w : 0.f);
+}
 
 // ---- generic LDS-tiled MFMA GEMM:  C[M][N] = sum_k A(m,k) * B(k,n) ---------------------------
-// A arrives either k-contiguous (AMC = false: loadA(m, k) -> A[m][k..k+3]) or m-contiguous
-// (AMC = true: loadA(k, m) -> A[m..m+3][k], the transposed operand of a weight gradient);
-// B is always n-contiguous: loadB(k, n) -> B[k][n..n+3].  Loaders return zeros out of range.
+// A arrives either k-contiguous (AMC = false: A(m, k) -> A[m][k..k+3]) or m-contiguous
+// (AMC = true: A(k, m) -> A[m..m+3][k], the transposed operand of a weight gradient);
+// B is always n-contiguous: B(k, n) -> B[k][n..n+3].
+//
+// The loader contract (this kernel and gemm_bf16x3.h): a Problem delivers an operand element in TWO steps.
+//   fetchA(i, j) / fetchB(k, n) -> StageA / StageB   one load from an address that is ALWAYS valid: rows, k and image
+//       coordinates are clamped into range, nothing is decided and nothing is computed on the result.  The kernel
+//       calls it when it issues a chunk's loads; the value stays in a register ring until the chunk is consumed.
+//   fixA(v, i, j) / fixB(v, k, n) -> float4          applied when the chunk goes to LDS, with the indices of the fetch:
+//       the zero of an element out of range -- a SELECT, never a multiplication: a clamped fetch may have returned
+//       anything, NaN and Inf included -- and any conversion (ProbW1: StageB is the raw u8 word).
+// A `cond ? load : zero` in the loader makes hipcc branch around the load (s_cbranch_execz) and, unable to count loads
+// across the join, wait s_waitcnt vmcnt(0) at every use: a ring of chunks "in flight" then holds nothing but the loads of
+// the current step.  With unconditional fetches the waits are counted and D - 1 chunks stay outstanding.
+// ProbBase supplies the defaults: float4 stages and identity fix-ups.
 template <int BM_, int BN_, int WM_, int WN_, bool AMC_>
 struct TileCfg {
   static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
@@ -53,6 +70,67 @@ struct fold_chunks<P, std::void_t<decltype(P::kFoldChunks)>> {
   static constexpr int value = P::kFoldChunks;
 };
 
+// ---- the chunk pipeline of gemm_lds and gemm_bf16x3 ----------------------------------------------------------------------
+// D register sets, two LDS buffers.  Chunk c of the block's slice [c0, c1) lives in set (c - c0) % D and is multiplied from
+// LDS buffer (c - c0) & 1.  A step: refill the set of the current chunk (it went to LDS a step ago) with chunk cur + D,
+// multiply chunk cur, store chunk cur + 1 (fetched D - 1 steps ago) into the other buffer, barrier.  The loop is unrolled
+// by D so that the sets are named statically, and its body has no branch: a refill past the slice's end re-reads the last
+// chunk (never stored), and the last 1 .. D chunks run in a peeled tail that fetches nothing.
+//   gload(chunk, set)   issue the chunk's fetches into register set `set` (std::integral_constant)
+//   sstore(buf, chunk, set)   fix up and write set `set`, holding `chunk`, into LDS buffer buf
+//   mma(buf, chunk)     multiply the chunk in LDS buffer buf
+// Needs c0 < c1; every condition is block-uniform.
+//
+// store_point(): an integer zero the compiler cannot see through (an empty asm statement: one scalar move), added to the
+// indices a fix-up gets.  A fix-up is a select on a fetched value and nothing else ties it to the store: hipcc evaluated
+// the selects of all D sets at the top of a round, right behind the refill issued there, and waited for that refill at
+// once.  A predicate that exists only from the store on keeps the select, and with it the wait, at the store.
+__device__ __forceinline__ int store_point() {
+  int z = 0;
+  asm volatile("" : "+s"(z));
+  return z;
+}
+template <class F, int... I>
+__device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int D, class Load, class Store, class Mma>
+__device__ __forceinline__ void chunk_ring(int c0, int c1, Load&& gload, Store&& sstore, Mma&& mma) {
+  using Sets = std::make_integer_sequence<int, D>;
+  static_for([&](auto j) { gload(min(c0 + j.value, c1 - 1), j); }, Sets{});
+  sstore(0, c0, std::integral_constant<int, 0>{});
+  __syncthreads();
+  int base = c0;
+  for (; base + D < c1; base += D) {
+    static_for(
+        [&](auto j) {
+          const int cur = base + j.value, buf = (cur - c0) & 1;
+          gload(min(cur + D, c1 - 1), j);
+          __builtin_amdgcn_sched_barrier(0);  // (the refill is issued before anything waits)
+          mma(buf, cur);
+          __builtin_amdgcn_sched_barrier(0);
+          sstore(buf ^ 1, cur + 1, std::integral_constant<int, (j.value + 1) % D>{});
+          __syncthreads();
+          // the body is one basic block: without this, hipcc hoists the fix-up arithmetic of the NEXT steps' stores over
+          // the barrier and with it their waits, draining the ring in the first step of every round
+          __builtin_amdgcn_sched_barrier(0);
+        },
+        Sets{});
+  }
+  static_for(
+      [&](auto j) {
+        const int cur = base + j.value, buf = (cur - c0) & 1;
+        if (cur < c1) {
+          mma(buf, cur);
+          if (cur + 1 < c1) sstore(buf ^ 1, cur + 1, std::integral_constant<int, (j.value + 1) % D>{});
+          __syncthreads();
+        }
+      },
+      Sets{});
+}
+
+constexpr int kRing = 2;  // register sets of gemm_lds: one chunk outstanding behind the one being multiplied (measured: 2 < 3 < 4)
+
 template <class T, class P>
 __global__ __launch_bounds__(kLT) void gemm_lds(const P p) {
   __shared__ __attribute__((aligned(16))) float sA[2][T::A_FLOATS];
@@ -61,59 +139,58 @@ __global__ __launch_bounds__(kLT) void gemm_lds(const P p) {
   const int wave = tid >> 6, lane = tid & 63;
   const int li = lane & 15, kk = lane >> 4;
   const int wm = wave / T::WN, wn = wave % T::WN;
-  const int m0 = blockIdx.y * T::BM, n0 = blockIdx.x * T::BN;
+  const int bm0 = blockIdx.y * T::BM, bn0 = blockIdx.x * T::BN;
   const int nch = (p.K + BK - 1) / BK;
   const int c0 = blockIdx.z * p.kslice;
   const int c1 = min(nch, c0 + p.kslice);
 
-  float4 ra[T::A_IT], rb[T::B_IT];
-  auto gload = [&](int ch) {
-    const int k0 = ch * BK;
+  // (idx clamped, not predicated: a surplus thread repeats its neighbour's fetch and LDS write)
+  typename P::StageA ra[kRing][T::A_IT];
+  typename P::StageB rb[kRing][T::B_IT];
+  auto gload = [&](int ch, auto set) {
+    constexpr int S = decltype(set)::value;
+    const int k0 = ch * BK, m0 = bm0, n0 = bn0;
 #pragma unroll
     for (int j = 0; j < T::A_IT; ++j) {
-      const int idx = tid + j * kLT;
-      if (idx < T::A_V4) {
-        if constexpr (T::AMC) {
-          const int kr = idx / (T::BM / 4), q = idx % (T::BM / 4);
-          ra[j] = p.loadA(k0 + kr, m0 + 4 * q);
-        } else {
-          const int r = idx >> 3, q = idx & 7;
-          ra[j] = p.loadA(m0 + r, k0 + 4 * q);
-        }
+      const int idx = min(tid + j * kLT, T::A_V4 - 1);
+      if constexpr (T::AMC) {
+        const int kr = idx / (T::BM / 4), q = idx % (T::BM / 4);
+        ra[S][j] = p.fetchA(k0 + kr, m0 + 4 * q);
+      } else {
+        const int r = idx >> 3, q = idx & 7;
+        ra[S][j] = p.fetchA(m0 + r, k0 + 4 * q);
       }
     }
 #pragma unroll
     for (int j = 0; j < T::B_IT; ++j) {
-      const int idx = tid + j * kLT;
-      if (idx < T::B_V4) {
-        const int kr = idx / (T::BN / 4), q = idx % (T::BN / 4);
-        rb[j] = p.loadB(k0 + kr, n0 + 4 * q);
-      }
+      const int idx = min(tid + j * kLT, T::B_V4 - 1);
+      const int kr = idx / (T::BN / 4), q = idx % (T::BN / 4);
+      rb[S][j] = p.fetchB(k0 + kr, n0 + 4 * q);
     }
   };
-  auto sstore = [&](int buf) {
+  auto sstore = [&](int buf, int ch, auto set) {
+    constexpr int S = decltype(set)::value;
+    const int z = store_point();
+    const int k0 = ch * BK + z, m0 = bm0 + z, n0 = bn0 + z;
 #pragma unroll
     for (int j = 0; j < T::A_IT; ++j) {
-      const int idx = tid + j * kLT;
-      if (idx < T::A_V4) {
-        if constexpr (T::AMC) {
-          const int kr = idx / (T::BM / 4), q = idx % (T::BM / 4);
-          *reinterpret_cast<float4*>(&sA[buf][kr * T::LDA + 4 * q]) = ra[j];
-        } else {
-          const int r = idx >> 3, q = idx & 7;
-          float* d = &sA[buf][r * T::LDA + 4 * q];
-          *reinterpret_cast<float2*>(d) = make_float2(ra[j].x, ra[j].y);
-          *reinterpret_cast<float2*>(d + 2) = make_float2(ra[j].z, ra[j].w);
-        }
+      const int idx = min(tid + j * kLT, T::A_V4 - 1);
+      if constexpr (T::AMC) {
+        const int kr = idx / (T::BM / 4), q = idx % (T::BM / 4);
+        *reinterpret_cast<float4*>(&sA[buf][kr * T::LDA + 4 * q]) = p.fixA(ra[S][j], k0 + kr, m0 + 4 * q);
+      } else {
+        const int r = idx >> 3, q = idx & 7;
+        const float4 v = p.fixA(ra[S][j], m0 + r, k0 + 4 * q);
+        float* d = &sA[buf][r * T::LDA + 4 * q];
+        *reinterpret_cast<float2*>(d) = make_float2(v.x, v.y);
+        *reinterpret_cast<float2*>(d + 2) = make_float2(v.z, v.w);
       }
     }
 #pragma unroll
     for (int j = 0; j < T::B_IT; ++j) {
-      const int idx = tid + j * kLT;
-      if (idx < T::B_V4) {
-        const int kr = idx / (T::BN / 4), q = idx % (T::BN / 4);
-        *reinterpret_cast<float4*>(&sB[buf][kr * T::LDB + 4 * q]) = rb[j];
-      }
+      const int idx = min(tid + j * kLT, T::B_V4 - 1);
+      const int kr = idx / (T::BN / 4), q = idx % (T::BN / 4);
+      *reinterpret_cast<float4*>(&sB[buf][kr * T::LDB + 4 * q]) = p.fixB(rb[S][j], k0 + kr, n0 + 4 * q);
     }
   };
 
@@ -131,14 +208,7 @@ __global__ __launch_bounds__(kLT) void gemm_lds(const P p) {
       for (int u = 0; u < T::TN; ++u) tot[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
-  if (c0 < c1) {
-    gload(c0);
-    sstore(0);
-  }
-  __syncthreads();
-  for (int ch = c0; ch < c1; ++ch) {
-    const int buf = (ch - c0) & 1;
-    if (ch + 1 < c1) gload(ch + 1);
+  auto mma = [&](int buf, int ch) {
 #pragma unroll
     for (int ks = 0; ks < BK / 4; ++ks) {
       float a[T::TM], b[T::TN];
@@ -165,9 +235,9 @@ __global__ __launch_bounds__(kLT) void gemm_lds(const P p) {
           }
       }
     }
-    if (ch + 1 < c1) sstore(buf ^ 1);
-    __syncthreads();
-  }
+  };
+  // (a block whose slice is empty fetches nothing and stores its zeros: the split reductions read every split)
+  if (c0 < c1) chunk_ring<kRing>(c0, c1, gload, sstore, mma);
 
 #pragma unroll
   for (int t = 0; t < T::TM; ++t)
@@ -175,8 +245,8 @@ __global__ __launch_bounds__(kLT) void gemm_lds(const P p) {
     for (int u = 0; u < T::TN; ++u)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int m = m0 + (wm * T::TM + t) * 16 + kk * 4 + r;
-        const int n = n0 + (wn * T::TN + u) * 16 + li;
+        const int m = bm0 + (wm * T::TM + t) * 16 + kk * 4 + r;
+        const int n = bn0 + (wn * T::TN + u) * 16 + li;
         if (m < p.M && n < p.N) {
           if constexpr (FOLD > 0) p.store(blockIdx.z, m, n, tot[t][u][r]);
           else p.store(blockIdx.z, m, n, acc[t][u][r]);
@@ -186,6 +256,10 @@ __global__ __launch_bounds__(kLT) void gemm_lds(const P p) {
 
 struct ProbBase {
   int M, N, K, kslice;
+  using StageA = float4;
+  using StageB = float4;
+  __device__ float4 fixA(float4 v, int, int) const { return v; }
+  __device__ float4 fixB(float4 v, int, int) const { return v; }
 };
 
 template <class T, class P>

@@ -56,12 +56,13 @@ struct ProbHeadDgrad : ProbBase {
   const float *d_ha, *a_w, *v_w, *h;
   float* d_h;
   int A;
-  __device__ float4 loadA(int m, int k) const { return m < M ? ld4(d_ha + (size_t)m * 32 + k) : zero4(); }
-  __device__ float4 loadB(int k, int n) const {
-    if (k < A) return ld4(a_w + (size_t)k * 512 + n);
-    if (k == 31) return ld4(v_w + n);
-    return zero4();
+  __device__ float4 fetchA(int m, int k) const { return ld4(d_ha + (size_t)min(m, M - 1) * 32 + k); }
+  __device__ float4 fixA(float4 v, int m, int) const { return keep4(m < M, v); }
+  __device__ float4 fetchB(int k, int n) const {  // (rows A .. 30 fetch fc_v's row and are zeroed)
+    const float* row = k < A ? a_w + (size_t)k * 512 : v_w;
+    return ld4(row + n);
   }
+  __device__ float4 fixB(float4 v, int k, int) const { return keep4(k < A || k == 31, v); }
   __device__ void store(int, int m, int n, float v) const {
     const size_t i = (size_t)m * 512 + n;
     d_h[i] = h[i] > 0.f ? v : 0.f;
@@ -73,8 +74,10 @@ struct ProbHeadDgrad : ProbBase {
 struct ProbHeadWgradPart : ProbBase {
   const float *d_ha, *h;
   float* part;
-  __device__ float4 loadA(int b, int m) const { return b < K ? ld4(d_ha + (size_t)b * 32 + m) : zero4(); }
-  __device__ float4 loadB(int b, int n) const { return b < K ? ld4(h + (size_t)b * 512 + n) : zero4(); }
+  __device__ float4 fetchA(int b, int m) const { return ld4(d_ha + (size_t)min(b, K - 1) * 32 + m); }
+  __device__ float4 fetchB(int b, int n) const { return ld4(h + (size_t)min(b, K - 1) * 512 + n); }
+  __device__ float4 fixA(float4 v, int b, int) const { return keep4(b < K, v); }
+  __device__ float4 fixB(float4 v, int b, int) const { return keep4(b < K, v); }
   __device__ void store(int z, int m, int n, float v) const { part[((size_t)z * 32 + m) * 512 + n] = v; }
 };
 __global__ void head_wgrad_reduce(const float* __restrict__ part, int splits, int A, float* __restrict__ g_a_w,
@@ -95,8 +98,10 @@ struct ProbHeadWgrad : ProbBase {
   const float *d_ha, *h;
   float *g_a_w, *g_v_w;
   int A;
-  __device__ float4 loadA(int b, int m) const { return b < K ? ld4(d_ha + (size_t)b * 32 + m) : zero4(); }
-  __device__ float4 loadB(int b, int n) const { return b < K ? ld4(h + (size_t)b * 512 + n) : zero4(); }
+  __device__ float4 fetchA(int b, int m) const { return ld4(d_ha + (size_t)min(b, K - 1) * 32 + m); }
+  __device__ float4 fetchB(int b, int n) const { return ld4(h + (size_t)min(b, K - 1) * 512 + n); }
+  __device__ float4 fixA(float4 v, int b, int) const { return keep4(b < K, v); }
+  __device__ float4 fixB(float4 v, int b, int) const { return keep4(b < K, v); }
   __device__ void store(int, int m, int n, float v) const {
     if (m < A) g_a_w[(size_t)m * 512 + n] = v;
     else if (m == 31) g_v_w[n] = v;
@@ -107,8 +112,9 @@ struct ProbHeadWgrad : ProbBase {
 struct ProbFcDgrad : ProbBase {
   const float *d_h, *wfcp, *a3;
   float* d_a3;
-  __device__ float4 loadA(int m, int k) const { return m < M ? ld4(d_h + (size_t)m * 512 + k) : zero4(); }
-  __device__ float4 loadB(int k, int n) const { return ld4(wfcp + (size_t)k * 3136 + n); }
+  __device__ float4 fetchA(int m, int k) const { return ld4(d_h + (size_t)min(m, M - 1) * 512 + k); }
+  __device__ float4 fixA(float4 v, int m, int) const { return keep4(m < M, v); }
+  __device__ float4 fetchB(int k, int n) const { return ld4(wfcp + (size_t)k * 3136 + n); }
   __device__ void store(int, int m, int n, float v) const {
     const size_t i = (size_t)m * 3136 + n;
     d_a3[i] = a3[i] > 0.f ? v : 0.f;
@@ -119,8 +125,10 @@ struct ProbFcDgrad : ProbBase {
 struct ProbFcWgrad : ProbBase {
   const float *d_h, *a3;
   float* g_fc_w;
-  __device__ float4 loadA(int b, int m) const { return b < K ? ld4(d_h + (size_t)b * 512 + m) : zero4(); }
-  __device__ float4 loadB(int b, int n) const { return b < K ? ld4(a3 + (size_t)b * 3136 + n) : zero4(); }
+  __device__ float4 fetchA(int b, int m) const { return ld4(d_h + (size_t)min(b, K - 1) * 512 + m); }
+  __device__ float4 fetchB(int b, int n) const { return ld4(a3 + (size_t)min(b, K - 1) * 3136 + n); }
+  __device__ float4 fixA(float4 v, int b, int) const { return keep4(b < K, v); }
+  __device__ float4 fixB(float4 v, int b, int) const { return keep4(b < K, v); }
   __device__ void store(int, int m, int n, float v) const {
     const int pos = n >> 6, c = n & 63;
     g_fc_w[(size_t)m * 3136 + c * 49 + pos] = v;
@@ -130,7 +138,7 @@ struct ProbFcWgrad : ProbBase {
 // ---- conv3 / conv2 data gradients: the transposed convolution as ONE GEMM over the pixels of the layer's INPUT ----------
 // Rows are the pixels whose gradient is wanted, k runs over (tap, output channel), and the A loader gathers the output
 // pixel that the tap connects to the row's pixel (zeros outside the output image) -- index arithmetic, as im2col is in
-// ProbConvWgrad::loadB.  The ReLU mask of the layer below is applied in the epilogue: no column buffer, no col2im pass.
+// ProbConvWgrad::fetchB.  The ReLU mask of the layer below is applied in the epilogue: no column buffer, no col2im pass.
 // A tap is two chunks of 32 k (64 output channels), and the sum is folded tap by tap (gemm_lds.h: kFoldChunks): each
 // tap's 64 terms from zero in channel order, the taps added in (kh, kw) order -- the association of the column form
 // this replaces (a 64-term GEMM per tap, then col2im's sum over the taps), so every element has the same bits as before.
@@ -141,17 +149,26 @@ struct ProbDgrad3 : ProbBase {
   static constexpr int kFoldChunks = 2;
   const float *d_out, *wp, *a2;  // d_out [b][49][64]; wp = w3p (permute_weights); a2 [b][81][64]
   float* d_a2;
-  __device__ float4 loadA(int m, int k) const {
-    if (m >= M) return zero4();
-    const int b = m / 81, pix = m - b * 81;
-    const int y = pix / 9, x = pix - y * 9;
-    const int tap = k >> 6, oc = k & 63;
-    const int kh = tap / 3, kw = tap - kh * 3;
-    const int oy = y - kh, ox = x - kw;
-    if ((unsigned)oy >= 7u || (unsigned)ox >= 7u) return zero4();
-    return ld4(d_out + ((size_t)b * 49 + oy * 7 + ox) * 64 + oc);
+  // the output pixel (oy, ox) of frame b that tap k >> 6 connects to row m (m clamped; oy, ox may lie outside the image)
+  __device__ void tap_pixel(int m, int k, int& b, int& oy, int& ox) const {
+    m = min(m, M - 1);
+    b = m / 81;
+    const int pix = m - b * 81, y = pix / 9, x = pix - y * 9;
+    const int tap = k >> 6, kh = tap / 3, kw = tap - kh * 3;
+    oy = y - kh, ox = x - kw;
   }
-  __device__ float4 loadB(int k, int n) const { return ld4(wp + (size_t)(k & 63) * 576 + (k >> 6) * 64 + n); }
+  __device__ float4 fetchA(int m, int k) const {
+    int b, oy, ox;
+    tap_pixel(m, k, b, oy, ox);
+    oy = min(max(oy, 0), 6), ox = min(max(ox, 0), 6);
+    return ld4(d_out + ((size_t)b * 49 + oy * 7 + ox) * 64 + (k & 63));
+  }
+  __device__ float4 fixA(float4 v, int m, int k) const {
+    int b, oy, ox;
+    tap_pixel(m, k, b, oy, ox);
+    return keep4(m < M && (unsigned)oy < 7u && (unsigned)ox < 7u, v);
+  }
+  __device__ float4 fetchB(int k, int n) const { return ld4(wp + (size_t)(k & 63) * 576 + (k >> 6) * 64 + n); }
   __device__ void store(int, int m, int n, float v) const {
     const size_t i = (size_t)m * 64 + n;
     d_a2[i] = a2[i] > 0.f ? v : 0.f;
@@ -168,16 +185,25 @@ struct ProbDgrad2 : ProbBase {
   static constexpr int kFoldChunks = 2;
   const float *d_out, *wp, *a1;  // d_out [b][81][64]; wp = w2p (permute_weights); a1 [b][400][32]
   float* d_a1;
-  __device__ float4 loadA(int m, int k) const {
-    if (m >= M) return zero4();
-    const int b = m / 100, pix = m - b * 100;
-    const int yh = pix / 10, xh = pix - yh * 10;
-    const int t = k >> 6, oc = k & 63;
-    const int oy = yh - (t >> 1), ox = xh - (t & 1);
-    if ((unsigned)oy >= 9u || (unsigned)ox >= 9u) return zero4();
-    return ld4(d_out + ((size_t)b * 81 + oy * 9 + ox) * 64 + oc);
+  __device__ void tap_pixel(int m, int k, int& b, int& oy, int& ox) const {  // (as ProbDgrad3's)
+    m = min(m, M - 1);
+    b = m / 100;
+    const int pix = m - b * 100, yh = pix / 10, xh = pix - yh * 10;
+    const int t = k >> 6;
+    oy = yh - (t >> 1), ox = xh - (t & 1);
   }
-  __device__ float4 loadB(int k, int n) const {
+  __device__ float4 fetchA(int m, int k) const {
+    int b, oy, ox;
+    tap_pixel(m, k, b, oy, ox);
+    oy = min(max(oy, 0), 8), ox = min(max(ox, 0), 8);
+    return ld4(d_out + ((size_t)b * 81 + oy * 9 + ox) * 64 + (k & 63));
+  }
+  __device__ float4 fixA(float4 v, int m, int k) const {
+    int b, oy, ox;
+    tap_pixel(m, k, b, oy, ox);
+    return keep4(m < M && (unsigned)oy < 9u && (unsigned)ox < 9u, v);
+  }
+  __device__ float4 fetchB(int k, int n) const {
     const int cls = n >> 5, t = k >> 6;
     const int kh = (t & 2) + (cls >> 1), kw = 2 * (t & 1) + (cls & 1);
     return ld4(wp + (size_t)(k & 63) * 512 + (kh * 4 + kw) * 32 + (n & 31));
@@ -196,9 +222,11 @@ template <int OC, int CIN, int KH, int KW, int STRIDE, int OH, int OW, int IH, i
 struct ProbConvWgrad : ProbBase {
   const float *d_out, *in;  // d_out [(b,pos)][OC]; in [b][IH][IW][CIN] channel-last
   float* part;
-  __device__ float4 loadA(int k, int m) const { return k < K ? ld4(d_out + (size_t)k * OC + m) : zero4(); }
-  __device__ float4 loadB(int k, int n) const {
-    if (k >= K) return zero4();
+  __device__ float4 fetchA(int k, int m) const { return ld4(d_out + (size_t)min(k, K - 1) * OC + m); }
+  __device__ float4 fixA(float4 v, int k, int) const { return keep4(k < K, v); }
+  __device__ float4 fixB(float4 v, int k, int) const { return keep4(k < K, v); }
+  __device__ float4 fetchB(int k, int n) const {
+    k = min(k, K - 1);
     const int b = k / (OH * OW), pos = k - b * (OH * OW);
     const int oy = pos / OW, ox = pos - oy * OW;
     const int r = n / CIN, c = n - r * CIN;
@@ -217,15 +245,19 @@ struct ProbW1 : ProbBase {
   const float* d_out;  // [(b,pos)][32]
   const uint8_t* obs;
   float* part;
-  __device__ float4 loadA(int k, int m) const { return k < K ? ld4(d_out + (size_t)k * 32 + m) : zero4(); }
-  __device__ float4 loadB(int k, int n) const {
-    if (k >= K) return zero4();
+  using StageB = uint32_t;  // four u8 pixels as fetched: converted when the chunk goes to LDS
+  __device__ float4 fetchA(int k, int m) const { return ld4(d_out + (size_t)min(k, K - 1) * 32 + m); }
+  __device__ float4 fixA(float4 v, int k, int) const { return keep4(k < K, v); }
+  __device__ uint32_t fetchB(int k, int n) const {
+    k = min(k, K - 1);
     const int b = k / 400, pos = k - b * 400;
     const int oy = pos / 20, ox = pos - oy * 20;
     const int c = n >> 6, kh = (n >> 3) & 7, kw = n & 7;
-    const uint32_t d = *reinterpret_cast<const uint32_t*>(obs + (size_t)b * 28224 + c * 7056 + (oy * 4 + kh) * 84 +
-                                                          ox * 4 + kw);
-    return make_float4((float)(d & 0xff), (float)((d >> 8) & 0xff), (float)((d >> 16) & 0xff), (float)(d >> 24));
+    return *reinterpret_cast<const uint32_t*>(obs + (size_t)b * 28224 + c * 7056 + (oy * 4 + kh) * 84 + ox * 4 + kw);
+  }
+  __device__ float4 fixB(uint32_t d, int k, int) const {
+    return keep4(k < K,
+                 make_float4((float)(d & 0xff), (float)((d >> 8) & 0xff), (float)((d >> 16) & 0xff), (float)(d >> 24)));
   }
   __device__ void store(int z, int m, int n, float v) const { part[((size_t)z * M + m) * N + n] = v; }
 };

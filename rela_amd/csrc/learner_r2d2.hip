@@ -38,40 +38,47 @@ using TileW32r = TileCfg<32, 64, 2, 4, true>;    // head weight gradients (M = 3
 struct ProbGateX : ProbBase {
   const float *a3, *wihT, *bias;
   float* gx;
-  __device__ float4 loadA(int m, int k) const { return m < M ? ld4(a3 + (size_t)m * kFeat + k) : zero4(); }
-  __device__ float4 loadB(int k, int n) const { return ld4(wihT + (size_t)k * kGates + n); }
+  __device__ float4 fetchA(int m, int k) const { return ld4(a3 + (size_t)min(m, M - 1) * kFeat + k); }
+  __device__ float4 fixA(float4 v, int m, int) const { return keep4(m < M, v); }
+  __device__ float4 fetchB(int k, int n) const { return ld4(wihT + (size_t)k * kGates + n); }
   __device__ void store(int, int m, int n, float v) const { gx[(size_t)m * kGates + n] = v + bias[n]; }
 };
 // part[z][b][g] = sum_{k in slice z} h[b][k] * whhT[k][g]
 struct ProbRecFwd : ProbBase {
   const float *h, *whhT;
   float* part;
-  __device__ float4 loadA(int m, int k) const { return m < M ? ld4(h + (size_t)m * kHid + k) : zero4(); }
-  __device__ float4 loadB(int k, int n) const { return ld4(whhT + (size_t)k * kGates + n); }
+  __device__ float4 fetchA(int m, int k) const { return ld4(h + (size_t)min(m, M - 1) * kHid + k); }
+  __device__ float4 fixA(float4 v, int m, int) const { return keep4(m < M, v); }
+  __device__ float4 fetchB(int k, int n) const { return ld4(whhT + (size_t)k * kGates + n); }
   __device__ void store(int z, int m, int n, float v) const { part[((size_t)z * M + m) * kGates + n] = v; }
 };
 // part[z][b][k] = sum_{g in slice z} dg[b][g] * whh[g][k]
 struct ProbRecBwd : ProbBase {
   const float *dg, *whh;
   float* part;
-  __device__ float4 loadA(int m, int k) const { return m < M ? ld4(dg + (size_t)m * kGates + k) : zero4(); }
-  __device__ float4 loadB(int k, int n) const { return ld4(whh + (size_t)k * kHid + n); }
+  __device__ float4 fetchA(int m, int k) const { return ld4(dg + (size_t)min(m, M - 1) * kGates + k); }
+  __device__ float4 fixA(float4 v, int m, int) const { return keep4(m < M, v); }
+  __device__ float4 fetchB(int k, int n) const { return ld4(whh + (size_t)k * kHid + n); }
   __device__ void store(int z, int m, int n, float v) const { part[((size_t)z * M + m) * kHid + n] = v; }
 };
 // dW_hh[g][k] = sum_r dg[r][g] * hprev[r][k]
 struct ProbWhh : ProbBase {
   const float *dg, *hprev;
   float* out;
-  __device__ float4 loadA(int r, int m) const { return r < K ? ld4(dg + (size_t)r * kGates + m) : zero4(); }
-  __device__ float4 loadB(int r, int n) const { return r < K ? ld4(hprev + (size_t)r * kHid + n) : zero4(); }
+  __device__ float4 fetchA(int r, int m) const { return ld4(dg + (size_t)min(r, K - 1) * kGates + m); }
+  __device__ float4 fixA(float4 v, int r, int) const { return keep4(r < K, v); }
+  __device__ float4 fetchB(int r, int n) const { return ld4(hprev + (size_t)min(r, K - 1) * kHid + n); }
+  __device__ float4 fixB(float4 v, int r, int) const { return keep4(r < K, v); }
   __device__ void store(int, int m, int n, float v) const { out[(size_t)m * kHid + n] = v; }
 };
 // dW_ih[g][c*49+pos] = sum_r dg[r][g] * a3[r][pos*64+c]     (written in state_dict order, net.py:105-106)
 struct ProbWih : ProbBase {
   const float *dg, *a3;
   float* out;
-  __device__ float4 loadA(int r, int m) const { return r < K ? ld4(dg + (size_t)r * kGates + m) : zero4(); }
-  __device__ float4 loadB(int r, int n) const { return r < K ? ld4(a3 + (size_t)r * kFeat + n) : zero4(); }
+  __device__ float4 fetchA(int r, int m) const { return ld4(dg + (size_t)min(r, K - 1) * kGates + m); }
+  __device__ float4 fixA(float4 v, int r, int) const { return keep4(r < K, v); }
+  __device__ float4 fetchB(int r, int n) const { return ld4(a3 + (size_t)min(r, K - 1) * kFeat + n); }
+  __device__ float4 fixB(float4 v, int r, int) const { return keep4(r < K, v); }
   __device__ void store(int, int m, int n, float v) const {
     const int pos = n >> 6, c = n & 63;
     out[(size_t)m * kFeat + c * 49 + pos] = v;
@@ -81,8 +88,9 @@ struct ProbWih : ProbBase {
 struct ProbIhDgrad : ProbBase {
   const float *dg, *wihp, *a3;
   float* d_a3;
-  __device__ float4 loadA(int m, int k) const { return m < M ? ld4(dg + (size_t)m * kGates + k) : zero4(); }
-  __device__ float4 loadB(int k, int n) const { return ld4(wihp + (size_t)k * kFeat + n); }
+  __device__ float4 fetchA(int m, int k) const { return ld4(dg + (size_t)min(m, M - 1) * kGates + k); }
+  __device__ float4 fixA(float4 v, int m, int) const { return keep4(m < M, v); }
+  __device__ float4 fetchB(int k, int n) const { return ld4(wihp + (size_t)k * kFeat + n); }
   __device__ void store(int, int m, int n, float v) const {
     const size_t i = (size_t)m * kFeat + n;
     d_a3[i] = a3[i] > 0.f ? v : 0.f;
@@ -93,12 +101,13 @@ struct ProbHeadDgradSeq : ProbBase {
   const float *d_ha, *a_w, *v_w;
   float* d_o;
   int A;
-  __device__ float4 loadA(int m, int k) const { return m < M ? ld4(d_ha + (size_t)m * 32 + k) : zero4(); }
-  __device__ float4 loadB(int k, int n) const {
-    if (k < A) return ld4(a_w + (size_t)k * kHid + n);
-    if (k == 31) return ld4(v_w + n);
-    return zero4();
+  __device__ float4 fetchA(int m, int k) const { return ld4(d_ha + (size_t)min(m, M - 1) * 32 + k); }
+  __device__ float4 fixA(float4 v, int m, int) const { return keep4(m < M, v); }
+  __device__ float4 fetchB(int k, int n) const {  // (rows A .. 30 fetch fc_v's row and are zeroed)
+    const float* row = k < A ? a_w + (size_t)k * kHid : v_w;
+    return ld4(row + n);
   }
+  __device__ float4 fixB(float4 v, int k, int) const { return keep4(k < A || k == 31, v); }
   __device__ void store(int, int m, int n, float v) const { d_o[(size_t)m * kHid + n] = v; }
 };
 
