@@ -312,6 +312,13 @@ int rela_ffnet_debug_conv12_stamps(const rela_ffnet* net, int n, const uint8_t* 
  * csrc/ffnet.hip: conv12_i8). */
 int rela_ffnet_debug_conv12_records(const rela_ffnet* net, int n, const uint8_t* s_dev, uint8_t* a1_records,
                                     uint8_t* a2_records, float* scale_host, float* bias_host, void* stream);
+/* Test hook: row `index` of the net's rows of the weight-layout table (csrc/ffnet.hip: one row per kernel-layout copy
+ * of the weights, 0 .. the net's last; RELA_EINVAL past it).  *name: the layout's name (static storage), *bytes: its
+ * size, *packed: whether the net's last load packed it (a net whose owner declared a row limit skips layouts only larger
+ * batches read; nothing before the first load).  host_dst, where not NULL and the layout is packed, receives its bytes
+ * after a device synchronisation.  name, bytes, packed and host_dst may each be NULL. */
+int rela_ffnet_debug_layout(const rela_ffnet* net, int index, const char** name, int64_t* bytes, int* packed,
+                            void* host_dst);
 /* The same for conv3 of the split-bf16 mode (the first 8 groups of two frames of block 0; 5 points per group). */
 int rela_ffnet_debug_conv3_stamps(const rela_ffnet* net, int n, const uint8_t* a2_records, unsigned long long* out_host,
                                   void* stream);
@@ -364,6 +371,9 @@ int rela_lstmnet_create(rela_lstmnet** out, int num_action, int device);
 void rela_lstmnet_destroy(rela_lstmnet* net);
 int rela_lstmnet_load(rela_lstmnet* net, const rela_lstmnet_params* params, int params_on_device,
                       void* stream);
+/* as rela_ffnet_debug_layout, over the rows an AtariLSTMNet holds (a load packs all of them) */
+int rela_lstmnet_debug_layout(const rela_lstmnet* net, int index, const char** name, int64_t* bytes, int* packed,
+                              void* host_dst);
 /* 0 = exact f32 (default), 1 = split-bf16 MFMA conv trunk for batches of 128 rows and more (as
  * rela_ffnet_set_precision) and, from 1,024 rows up, the input side of the LSTM gate GEMM as well (h x W_hh, the
  * cell and the heads stay f32); h, c, Q within 4e-6 of mode 0.  Bumps the weight version. */
@@ -641,7 +651,7 @@ int rela_debug_loss_grad(int batch, int A, int form, const float* q, const float
  * rela_apex_learner_grad), then the two column sums through the learner's multi-job launcher and head_bias_grad, as one
  * call whose inputs are the forward's activations, so their > 0 patterns -- the ReLU masks -- are data of the call.
  * All pointers are device pointers; the call allocates its own scratch (the fc weight in a3's column order is packed
- * with the learner's permute_weights), synchronises both lanes and frees it.
+ * with the pack segments of the learner's re-pack), synchronises both lanes and frees it.
  *   d_ha     f32 [batch][32]   as rela_debug_loss_grad leaves it; columns A..30 take no part
  *   h, a3    f32 [batch][512], [batch][49][64]   relu(fc), relu(conv3) channel-last (csrc/ffnet_layout.h)
  *   fc_a_w, fc_v_w, fc_w   [A][512], [1][512], [512][3136]   (state_dict layout)

@@ -166,6 +166,8 @@ _sig("rela_ffnet_debug_conv12_stamps", i32, [vp, i32, vp, vp, vp])
 _sig("rela_ffnet_debug_fc_stamps", i32, [vp, i32, vp, vp, vp])
 _sig("rela_ffnet_debug_conv3_stamps", i32, [vp, i32, vp, vp, vp])
 _sig("rela_ffnet_debug_conv12_records", i32, [vp, i32, vp, vp, vp, vp, vp, vp])
+_sig("rela_ffnet_debug_layout", i32, [vp, i32, P(C.c_char_p), P(i64), P(i32), vp])
+_sig("rela_lstmnet_debug_layout", i32, [vp, i32, P(C.c_char_p), P(i64), P(i32), vp])
 _sig("rela_lstmnet_set_precision", i32, [vp, i32])
 _sig("rela_lstmnet_precision", i32, [vp])
 _sig("rela_ffnet_workspace_bytes", i64, [vp, i32])

@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/rela_amd.h"
 
 namespace rela_amd {
@@ -43,6 +45,25 @@ struct DeviceGuard {
   }
   ~DeviceGuard() {
     if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+// the device buffers of one owner (a net's weight layouts, a learner's everything): every pointer handed out is
+// recorded, free_all releases them
+struct DevBuffers {
+  std::vector<void*> ptrs;
+  template <class T>
+  int alloc(T** p, size_t count, bool zero) {
+    void* v = nullptr;
+    RELA_HIP(hipMalloc(&v, sizeof(T) * count));
+    ptrs.push_back(v);
+    *p = static_cast<T*>(v);
+    if (zero) RELA_HIP(hipMemset(v, 0, sizeof(T) * count));
+    return RELA_OK;
+  }
+  void free_all() {
+    for (void* p : ptrs) (void)hipFree(p);
+    ptrs.clear();
   }
 };
 

@@ -39,6 +39,8 @@
 #include "gemm_lds.h"
 #include "param_layout.h"
 #include "prof.h"
+#define RELA_WEIGHT_PACK_KERNEL  // this translation unit holds the library's one pack kernel
+#include "weight_pack.h"
 
 namespace rela_amd {
 
@@ -55,12 +57,17 @@ struct FFNetDev {
   // split-bf16 fast path: [ct][ks][hi, lo][lane] x 8 bf16 (see "Split-bf16" below)
   uint4 *B2f = nullptr, *B3f = nullptr, *Bff = nullptr;
   float* Bhp = nullptr;  // heads weights [ct 2][wave 4][j 32][lane 64] in the k order of heads_duel
-  // conv1 for the int8 matrix cores (conv12_i8): digits [hi, mid, lo][ct 2][tap 4][lane 64] x 16 int8, the channels'
-  // scales s_c and the biases b_c + 128 s_c sum_k q_k
+  // conv1 for the int8 matrix cores (conv12_i8): digits [hi, mid, lo][ct 2][tap 4][lane 64] x 16 int8, then (the same
+  // layout, s1q and b1q point into it) the channels' scales s_c and the biases b_c + 128 s_c sum_k q_k
   uint4* W1d = nullptr;
   float *s1q = nullptr, *b1q = nullptr;
   // f32-accurate mode on the bf16 matrix cores (gemm_f32emu.h): bf16 triples in fragment order [cg][ks][u][part][lane]
   uint4 *B2e = nullptr, *B3e = nullptr, *Bfe = nullptr;
+  // AtariLSTMNet only
+  float* Bl = nullptr;      // lstm frags [128][912][64]
+  float* bl = nullptr;      // b_ih + b_hh, permuted [2048]
+  uint8_t* Wrec = nullptr;  // weight_ih_l0 as rec64 rows in the permuted column order [2048][49][64 hi | 64 lo]
+  uint4* Wx3 = nullptr;     // ... as three-part bf16 fragments in the same column order (gemm_s3.h; f32x3 mode)
 };
 
 namespace {
@@ -539,36 +546,7 @@ __global__ __launch_bounds__(kThreads) void conv1_bf16x3(const uint8_t* __restri
   }
 }
 
-__device__ __forceinline__ uint16_t f32_to_bf16_rne(float x) {
-  uint32_t u = __float_as_uint(x);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-
-// conv1 weights (32,4,8,8)/255 -> three bf16 planes in MFMA 16x16x32 fragment order.
-// w == hi + mid + lo exactly for every finite fp32 weight (each residual is exact in fp32).
-// plane_major: k-step ks = kernel row ks of all four planes (lane group g = plane; unused since the half-frame kernels went in r4)
-// its LDS image in; otherwise k runs (c, kh, kw) linearly (conv1_bf16x3).
-__device__ __forceinline__ void pack_conv1_bf16x3_at(int idx, const float* __restrict__ w, uint16_t* __restrict__ frag, int plane_major) {
-  if (idx >= 2 * 8 * 64 * 8) return;
-  const int j = idx & 7, lane = (idx >> 3) & 63, ks = (idx >> 9) & 7, ct = idx >> 12;
-  const int k = plane_major ? (lane >> 4) * 64 + ks * 8 + j : ks * 32 + (lane >> 4) * 8 + j;
-  const int oc = ct * 16 + (lane & 15);
-  const float v = w[oc * 256 + k] / 255.0f;
-  const uint16_t hi = f32_to_bf16_rne(v);
-  const float r1 = v - bf16_to_f32(hi);
-  const uint16_t mid = f32_to_bf16_rne(r1);
-  const float r2 = r1 - bf16_to_f32(mid);
-  const uint16_t lo = f32_to_bf16_rne(r2);
-  const int plane = 2 * 8 * 64 * 8;
-  frag[idx] = hi;
-  frag[plane + idx] = mid;
-  frag[2 * plane + idx] = lo;
-}
-__global__ void pack_conv1_bf16x3(const float* __restrict__ w, uint16_t* __restrict__ frag, int plane_major) {
-  pack_conv1_bf16x3_at((int)blockIdx.x * blockDim.x + threadIdx.x, w, frag, plane_major);
-}
 
 // =====================================================================================================
 // Split-bf16 ("fast") path: conv2 / conv3 / fc on v_mfma_f32_16x16x32_bf16 (16x the f32 MFMA rate).
@@ -1412,35 +1390,6 @@ __global__ __launch_bounds__(kThreads) void fc_bf16s(const uint8_t* __restrict__
     }
 }
 
-// weights -> [ct][ks][hi, lo][lane] x 8 bf16 in MFMA 16x16x32 fragment order.  mode: kPackConv2 (k = tap*32 + c),
-// kPackConv3 (k = tap*64 + c), kPackFc (k = pos*64 + c  <-  torch flatten c*49 + pos)
-__device__ __forceinline__ void pack_frags_bf16s_at(int64_t idx, int mode, const float* __restrict__ w, uint16_t* __restrict__ frag, int CT, int KS) {
-  if (idx >= (int64_t)CT * KS * 64 * 8) return;
-  const int j = (int)(idx & 7), lane = (int)((idx >> 3) & 63);
-  const int ks = (int)((idx >> 9) % KS), ct = (int)((idx >> 9) / KS);
-  const int k = ks * 32 + (lane >> 4) * 8 + j;
-  const int oc = ct * 16 + (lane & 15);
-  float v;
-  if (mode == 1) {  // conv2: (64,32,4,4)
-    const int c = k & 31, tap = k >> 5;
-    v = w[((oc * 32 + c) * 4 + (tap >> 2)) * 4 + (tap & 3)];
-  } else if (mode == 2) {  // conv3: (64,64,3,3)
-    const int c = k & 63, tap = k >> 6;
-    v = w[((oc * 64 + c) * 3 + tap / 3) * 3 + tap % 3];
-  } else {  // fc: (512,3136)
-    const int c = k & 63, pos = k >> 6;
-    v = w[(size_t)oc * 3136 + c * 49 + pos];
-  }
-  const uint16_t hi = f32_to_bf16_rne(v);
-  const uint16_t lo = f32_to_bf16_rne(v - bf16_to_f32(hi));
-  const size_t base = (((size_t)ct * KS + ks) * 2) * 64 * 8;
-  frag[base + (size_t)lane * 8 + j] = hi;
-  frag[base + 64 * 8 + (size_t)lane * 8 + j] = lo;
-}
-__global__ void pack_frags_bf16s(int mode, const float* __restrict__ w, uint16_t* __restrict__ frag, int CT, int KS) {
-  pack_frags_bf16s_at((int64_t)blockIdx.x * blockDim.x + threadIdx.x, mode, w, frag, CT, KS);
-}
-
 // Dense layer  out[N][OC] = act(A[N][K] * W + bias)  on the same MFMA tiling.
 // Block = BM rows x (CTB*16) columns; A is staged through LDS in K-chunks of 32 (double
 // buffered, row stride 34 floats -> conflict-free fragment reads), B fragments stream from L2.
@@ -1624,20 +1573,8 @@ __global__ void dueling_kernel(const float* __restrict__ ha, const float* __rest
 // one-thread-per-row kernel) cost 18 + 10 us at N = 6,400 and 17 + 9 us at N = 512 for 0.2 GFLOP: launch and latency,
 // not work.  Block = 16 rows, 4 waves; wave w multiplies the k-slice [128w, 128w + 128) on v_mfma_f32_16x16x4_f32 (a
 // lane reads 32 CONTIGUOUS floats of its row: k-step j of lane group g is k = 128w + 32g + j, the weights are packed
-// in that order by pack_heads_perm), the four partial tiles meet in LDS, then 16 threads per row finish the row.
+// in that order by pack_heads_perm_at, weight_pack.h), the four partial tiles meet in LDS, then 16 threads per row finish the row.
 constexpr int kHeadRows = 16;
-__device__ __forceinline__ void pack_heads_perm_at(int idx, const float* __restrict__ a_w, const float* __restrict__ v_w, int A,
-                                float* __restrict__ out) {
-  if (idx >= 2 * 4 * 32 * 64) return;
-  const int lane = idx & 63, j = (idx >> 6) & 31, w = (idx >> 11) & 3, ct = idx >> 13;
-  const int k = 128 * w + 32 * (lane >> 4) + j, col = ct * 16 + (lane & 15);
-  out[idx] = col < A ? a_w[(size_t)col * 512 + k] : (col == 31 ? v_w[k] : 0.f);
-}
-__global__ void pack_heads_perm(const float* __restrict__ a_w, const float* __restrict__ v_w, int A,
-                                float* __restrict__ out) {
-  pack_heads_perm_at((int)blockIdx.x * blockDim.x + threadIdx.x, a_w, v_w, A, out);
-}
-
 __device__ __forceinline__ void heads_duel_body(const float* __restrict__ h, const float* __restrict__ Bhp,
                                                 const float* __restrict__ bias, const float* __restrict__ legal,
                                                 float* __restrict__ ha, float* __restrict__ q, int N, int A, int bid) {
@@ -1740,219 +1677,6 @@ __global__ void fc_reduce(const float* __restrict__ part, int splits, int N, con
   }
   *reinterpret_cast<float4*>(h + off) =
       make_float4(s.x > 0.f ? s.x : 0.f, s.y > 0.f ? s.y : 0.f, s.z > 0.f ? s.z : 0.f, s.w > 0.f ? s.w : 0.f);
-}
-
-// wt[k = pos*64 + c][u] = linear.0.weight[u][c*49 + pos]   (net.py:49 flattens channel-first)
-__device__ __forceinline__ void pack_fc_t_at(int idx, const float* __restrict__ w, float* __restrict__ wt) {
-  if (idx >= 3136 * 512) return;
-  const int k = idx >> 9, u = idx & 511;
-  const int c = k & 63, pos = k >> 6;
-  wt[idx] = w[(size_t)u * 3136 + c * 49 + pos];
-}
-__global__ void pack_fc_t(const float* __restrict__ w, float* __restrict__ wt) {
-  pack_fc_t_at((int)blockIdx.x * blockDim.x + threadIdx.x, w, wt);
-}
-
-enum PackMode { kPackConv1 = 0, kPackConv2 = 1, kPackConv3 = 2, kPackFc = 3, kPackHeads = 4, kPackLstm = 5 };
-
-__device__ __forceinline__ void pack_frags_at(int64_t idx, int mode, const float* __restrict__ w, const float* __restrict__ w2, int num_action,
-                           float* __restrict__ frag, int CT, int KS) {
-  const int64_t total = (int64_t)CT * KS * 64;
-  if (idx >= total) return;
-  const int lane = (int)(idx & 63);
-  const int ks = (int)((idx >> 6) % KS);
-  const int ct = (int)((idx >> 6) / KS);
-  const int k = ks * 4 + (lane >> 4);
-  const int oc = ct * 16 + (lane & 15);
-  float v = 0.f;
-  switch (mode) {
-    case kPackConv1:  // k = (c, kh, kw) = state_dict order; fold s/255 (net.py:46)
-      v = w[oc * 256 + k] / 255.0f;
-      break;
-    case kPackConv2: {  // k = (kh, kw, c)
-      const int c = k & 31, kw = (k >> 5) & 3, kh = k >> 7;
-      v = w[((oc * 32 + c) * 4 + kh) * 4 + kw];
-      break;
-    }
-    case kPackConv3: {  // k = (kh, kw, c)
-      const int c = k & 63, r = k >> 6, kw = r % 3, kh = r / 3;
-      v = w[((oc * 64 + c) * 3 + kh) * 3 + kw];
-      break;
-    }
-    case kPackFc: {  // k = pos*64 + c  <-  torch flatten c*49 + pos (net.py:49)
-      const int c = k & 63, p = k >> 6;
-      v = w[(size_t)oc * 3136 + c * 49 + p];
-      break;
-    }
-    case kPackLstm: {  // col' = 4*unit + gate  <-  row gate*512 + unit of weight_ih_l0 / weight_hh_l0
-      const int row = (oc & 3) * 512 + (oc >> 2);
-      if (k < 3136) {
-        const int c = k & 63, p = k >> 6;  // k = pos*64 + c  <-  c*49 + pos (net.py:105-106)
-        v = w[(size_t)row * 3136 + c * 49 + p];
-      } else {
-        v = w2[(size_t)row * 512 + (k - 3136)];
-      }
-      break;
-    }
-    case kPackHeads:
-      if (oc < num_action)
-        v = w[oc * 512 + k];  // fc_a
-      else if (oc == 31)
-        v = w2[k];  // fc_v
-      break;
-  }
-  frag[idx] = v;
-}
-__global__ void pack_frags(int mode, const float* __restrict__ w, const float* __restrict__ w2, int num_action,
-                           float* __restrict__ frag, int CT, int KS) {
-  pack_frags_at((int64_t)blockIdx.x * blockDim.x + threadIdx.x, mode, w, w2, num_action, frag, CT, KS);
-}
-
-// weight_ih_l0 [gate*512 + unit][c*49 + pos] -> rec64 rows in the gate GEMM's permuted column order:
-// rec[col = 4*unit + gate][chunk = pos][64 hi | 64 lo] over c (the B operand of gemm16::gemm_rec64_nt for the x part)
-__global__ void pack_wih_rec64_perm(const float* __restrict__ wih, uint8_t* __restrict__ rec) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // one thread per 8 channels
-  if (i >= (int64_t)2048 * 392) return;
-  const int col = (int)(i / 392), o = (int)(i - (int64_t)col * 392);
-  const int pos = o >> 3, c0 = (o & 7) * 8;
-  const float* w = wih + (size_t)((col & 3) * 512 + (col >> 2)) * 3136 + pos;
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = w[(c0 + j) * 49];
-  uint4 hi, lo;
-  gemm16::split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), hi, lo);
-  uint8_t* r = rec + ((size_t)col * 49 + pos) * 256 + (o & 7) * 16;
-  *reinterpret_cast<uint4*>(r) = hi;
-  *reinterpret_cast<uint4*>(r + 128) = lo;
-}
-__global__ void pack_lstm_bias(const float* __restrict__ bih, const float* __restrict__ bhh, float* __restrict__ out) {
-  const int oc = blockIdx.x * blockDim.x + threadIdx.x;
-  if (oc < 2048) {
-    const int row = (oc & 3) * 512 + (oc >> 2);
-    out[oc] = bih[row] + bhh[row];
-  }
-}
-
-__global__ void pack_head_bias(const float* __restrict__ ab, const float* __restrict__ vb, int A, float* __restrict__ out) {
-  const int j = threadIdx.x;
-  if (j < 32) out[j] = j < A ? ab[j] : (j == 31 ? vb[0] : 0.f);
-}
-
-// conv1 for conv12_i8: one block of 256 threads per output channel c (thread = weight k = p*64 + ky*8 + kx of
-// state_dict's [32][4][8][8]).  s_c = max|w| / QMAX rounded UP to f32 (so that |w / s_c| <= QMAX), q = rint(w / s_c) in
-// double, balanced base-256 digits; b' = b + 128 s_c sum q in double, rounded once.  Digit d of (c, k) is byte
-// j = (ky % 4) * 4 + kx % 4 of lane (g = p) * 16 + c % 16 of fragment [d][c / 16][tap (ky / 4) * 2 + kx / 4].
-constexpr int kConv1QMax = 127 * 65536 + 127 * 256 + 127;
-__device__ __forceinline__ void pack_conv1_i8_block(int c, const float* __restrict__ w, const float* __restrict__ b,
-                                                    uint8_t* __restrict__ W1d, float* __restrict__ s1q, float* __restrict__ b1q) {
-  __shared__ float amax[256];
-  __shared__ long long qsum[256];
-  const int k = threadIdx.x;
-  const float wv = w[c * 256 + k] / 255.0f;  // the s / 255 of net.py:46, folded as in the other conv1 packs
-  amax[k] = fabsf(wv);
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (k < o) amax[k] = fmaxf(amax[k], amax[k + o]);
-    __syncthreads();
-  }
-  const float mx = amax[0];
-  float sc = 1.0f;
-  if (mx > 0.f) {
-    sc = (float)((double)mx / (double)kConv1QMax);
-    if (sc <= 0.f || (double)mx / (double)sc > (double)kConv1QMax) sc = nextafterf(sc, INFINITY);
-  }
-  long long q = llrint((double)wv / (double)sc);
-  q = q > kConv1QMax ? kConv1QMax : (q < -kConv1QMax ? -kConv1QMax : q);
-  qsum[k] = q;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (k < o) qsum[k] += qsum[k + o];
-    __syncthreads();
-  }
-  if (k == 0) {
-    s1q[c] = sc;
-    b1q[c] = (float)((double)b[c] + 128.0 * (double)sc * (double)qsum[0]);
-  }
-  // balanced digits: lo, mid in [-128, 127], hi = the rest (|hi| <= 127 by the bound on q)
-  const int qi = (int)q;
-  const int lo = ((qi + 128) & 255) - 128;
-  const int q1 = (qi - lo) >> 8;
-  const int mid = ((q1 + 128) & 255) - 128;
-  const int hi = (q1 - mid) >> 8;
-  const int pl = k >> 6, ky = (k >> 3) & 7, kx = k & 7;
-  const int tap = (ky >> 2) * 2 + (kx >> 2), j = (ky & 3) * 4 + (kx & 3);
-  const int lane = pl * 16 + (c & 15), ct = c >> 4;
-  const int dig[3] = {hi, mid, lo};
-#pragma unroll
-  for (int d = 0; d < 3; ++d) W1d[((size_t)((d * 2 + ct) * 4 + tap) * 64 + lane) * 16 + j] = (uint8_t)(int8_t)dig[d];
-}
-
-__global__ __launch_bounds__(256) void pack_conv1_i8(const float* __restrict__ w, const float* __restrict__ b, uint8_t* __restrict__ W1d,
-                                                     float* __restrict__ s1q, float* __restrict__ b1q) {
-  pack_conv1_i8_block((int)blockIdx.x, w, b, W1d, s1q, b1q);
-}
-
-__global__ void pack_f32emu(int mode, const float* __restrict__ w, uint16_t* __restrict__ frag, int NCG, int KS) {
-  f32emu::pack_f32emu_at((int64_t)blockIdx.x * blockDim.x + threadIdx.x, mode, w, frag, NCG, KS);
-}
-
-// Every kernel-layout copy of an AtariFFNet's weights in ONE launch (a learner re-packs after every optimiser step:
-// twelve pack kernels, four device copies and the head bias were seventeen launches).  A block finds its job in a
-// table of first-block indices; the job bodies are the *_at functions of the separate kernels.
-// the segments of the launch, in block order
-enum PackSeg {
-  kSegB1, kSegUnused1, kSegB2, kSegB3, kSegBf, kSegBfT, kSegBh, kSegBhp, kSegB2f, kSegB3f, kSegBff, kSegBiases,
-  kSegHeadBias, kSegW2p, kSegW3p, kSegWfcp, kSegW1d, kSegB2e, kSegB3e, kSegBfe, kPackSegs
-};
-struct PackAllArgs {
-  const float* p[12];  // rela_ffnet_params order
-  uint16_t *B1, *B2f, *B3f, *Bff;
-  float *B2, *B3, *Bf, *BfT, *Bh, *Bhp, *b1, *b2, *b3, *bf, *bh;
-  int A;
-  float *w2p, *w3p, *wfcp;  // the learner's dgrad operand copies (ffnet_layout.h), or NULL
-  uint8_t* W1d;             // conv1 for the int8 matrix cores (pack_conv1_i8_block)
-  float *s1q, *b1q;
-  uint16_t *B2e, *B3e, *Bfe;  // bf16 triples of the f32-accurate mode (f32emu::pack_f32emu_at)
-  int first[kPackSegs + 1];  // first block of segment j; first[kPackSegs] = total
-};
-__global__ void pack_ffnet_all(PackAllArgs a) {
-  const int b = blockIdx.x;
-  int j = 0;
-  while (b >= a.first[j + 1]) ++j;
-  const int64_t idx = (int64_t)(b - a.first[j]) * 256 + threadIdx.x;
-  switch (j) {
-    case kSegB1: pack_conv1_bf16x3_at((int)idx, a.p[0], a.B1, 0); break;
-    case kSegUnused1: break;  // (was: plane-major conv1 fragments of the half-frame bf16 kernels, removed in r4; zero blocks)
-    case kSegB2: pack_frags_at(idx, kPackConv2, a.p[2], nullptr, a.A, a.B2, 4, 128); break;
-    case kSegB3: pack_frags_at(idx, kPackConv3, a.p[4], nullptr, a.A, a.B3, 4, 144); break;
-    case kSegBf: pack_frags_at(idx, kPackFc, a.p[6], nullptr, a.A, a.Bf, 32, 784); break;
-    case kSegBfT: pack_fc_t_at((int)idx, a.p[6], a.BfT); break;
-    case kSegBh: pack_frags_at(idx, kPackHeads, a.p[10], a.p[8], a.A, a.Bh, 2, 128); break;
-    case kSegBhp: pack_heads_perm_at((int)idx, a.p[10], a.p[8], a.A, a.Bhp); break;
-    case kSegB2f: pack_frags_bf16s_at(idx, 1, a.p[2], a.B2f, Conv2F::CT, Conv2F::KS); break;
-    case kSegB3f: pack_frags_bf16s_at(idx, 2, a.p[4], a.B3f, Conv3F::CT, Conv3F::KS); break;
-    case kSegBff: pack_frags_bf16s_at(idx, 3, a.p[6], a.Bff, 32, FcFast::KS); break;
-    case kSegBiases: {  // biases: conv1 32 | conv2 64 | conv3 64 | fc 512
-      const int i = (int)idx;
-      if (i < 32) a.b1[i] = a.p[1][i];
-      else if (i < 96) a.b2[i - 32] = a.p[3][i - 32];
-      else if (i < 160) a.b3[i - 96] = a.p[5][i - 96];
-      else if (i < 672) a.bf[i - 160] = a.p[7][i - 160];
-      break;
-    }
-    case kSegHeadBias: {  // head bias
-      const int i = (int)idx;
-      if (i < 32) a.bh[i] = i < a.A ? a.p[11][i] : (i == 31 ? a.p[9][0] : 0.f);
-      break;
-    }
-    case kSegW2p: if (idx < 64 * 512) permute_weight_at(kPermConv2, (int)idx, a.p[2], a.w2p); break;
-    case kSegW3p: if (idx < 64 * 576) permute_weight_at(kPermConv3, (int)idx, a.p[4], a.w3p); break;
-    case kSegWfcp: if (idx < 512 * 3136) permute_weight_at(kPermFc, (int)idx, a.p[6], a.wfcp); break;
-    case kSegW1d: pack_conv1_i8_block(b - a.first[kSegW1d], a.p[0], a.p[1], a.W1d, a.s1q, a.b1q); break;  // (block-uniform: it synchronises)
-    case kSegB2e: f32emu::pack_f32emu_at(idx, 1, a.p[2], a.B2e, f32emu::ProbConv2::NCG, f32emu::ProbConv2::KS); break;
-    case kSegB3e: f32emu::pack_f32emu_at(idx, 2, a.p[4], a.B3e, f32emu::ProbConv3::NCG, f32emu::ProbConv3::KS); break;
-    default: f32emu::pack_f32emu_at(idx, 3, a.p[6], a.Bfe, f32emu::ProbFc::NCG, f32emu::ProbFc::KS); break;  // kSegBfe
-  }
 }
 
 }  // namespace
@@ -2101,23 +1825,99 @@ TrunkJob trunk_job(const FFNetDev& d, const uint8_t* in0, const uint8_t* in1, in
 
 // ---- create / load helpers ---------------------------------------------------------------------------------------------
 
-// the weight layouts every net with a conv trunk and dueling heads holds (an AtariFFNet adds its fc's and Bhp)
-int alloc_trunk(FFNetDev& d) {
-  RELA_HIP(hipMalloc(&d.B1, sizeof(uint4) * Conv1B::FRAG_UINT4));
-  RELA_HIP(hipMalloc(&d.b1, sizeof(float) * 32));
-  RELA_HIP(hipMalloc(&d.B2, sizeof(float) * 4 * 128 * 64));
-  RELA_HIP(hipMalloc(&d.b2, sizeof(float) * 64));
-  RELA_HIP(hipMalloc(&d.B3, sizeof(float) * 4 * 144 * 64));
-  RELA_HIP(hipMalloc(&d.b3, sizeof(float) * 64));
-  RELA_HIP(hipMalloc(&d.Bh, sizeof(float) * 2 * 128 * 64));
-  RELA_HIP(hipMalloc(&d.bh, sizeof(float) * 32));
-  RELA_HIP(hipMalloc(&d.W1d, sizeof(uint4) * Conv12I::W1_UINT4));
-  RELA_HIP(hipMalloc(&d.s1q, sizeof(float) * 32));
-  RELA_HIP(hipMalloc(&d.b1q, sizeof(float) * 32));
-  RELA_HIP(hipMalloc(&d.B2f, sizeof(uint4) * Conv2F::CT * Conv2F::KS * 2 * 64));
-  RELA_HIP(hipMalloc(&d.B3f, sizeof(uint4) * Conv3F::CT * Conv3F::KS * 2 * 64));
-  RELA_HIP(hipMalloc(&d.B2e, sizeof(uint4) * f32emu::packed_u4<f32emu::ProbConv2>()));
-  RELA_HIP(hipMalloc(&d.B3e, sizeof(uint4) * f32emu::packed_u4<f32emu::ProbConv3>()));
+// THE LAYOUT TABLE: one row per kernel-layout weight copy, in the order of `Layout` (ffnet_plan.h).  A layout is
+// `elements` units of `unit` bytes -- one unit per thread of its pack body (weight_pack.h) -- plus `tail` bytes, and is
+// packed by a segment of `kind` from the parameters s0 and s1 with the integers a0 and a1.  create allocates it and points
+// FFNetDev's field at it, a load makes the segment, rela_*_debug_layout reports the row: no size is written anywhere else.
+// Parameters are indices of the load's tensors in state_dict order (conv1_w 0 .. conv3_b 5, then the net's own); both
+// nets end in fc_v.weight, fc_v.bias, fc_a.weight, fc_a.bias, which the table counts from the end.
+enum { kVw = -4, kVb = -3, kAw = -2, kAb = -1, kNoSrc = 99, kNumAction = -1 /* a0: the net's num_action */ };
+struct LayoutRow {
+  const char* name;
+  size_t field;  // offsetof(FFNetDev, the pointer)
+  int64_t elements;
+  int unit, tail, kind, s0, s1, a0, a1;
+  int64_t bytes() const { return elements * unit + tail; }
+};
+template <class P>
+constexpr int64_t emu_triples() { return f32emu::packed_u4<P>() * 8 / 3; }  // bf16 triples of a gemm_f32emu.h layout
+#define RELA_LAYOUT(field, elements, unit, tail, ...) {#field, offsetof(FFNetDev, field), (int64_t)(elements), unit, tail, __VA_ARGS__}
+const LayoutRow kLayouts[kLayCount] = {
+    RELA_LAYOUT(B1, 2 * 8 * 64 * 8, 6, 0, kPackConv1x3, 0, kNoSrc, 0, 0),  // a thread: one bf16 of each of the three planes
+    RELA_LAYOUT(b1, 32, 4, 0, kPackCopy, 1, kNoSrc, 0, 0),
+    RELA_LAYOUT(B2, 4 * 128 * 64, 4, 0, kPackFragsConv2, 2, kNoSrc, 4, 128),
+    RELA_LAYOUT(b2, 64, 4, 0, kPackCopy, 3, kNoSrc, 0, 0),
+    RELA_LAYOUT(B3, 4 * 144 * 64, 4, 0, kPackFragsConv3, 4, kNoSrc, 4, 144),
+    RELA_LAYOUT(b3, 64, 4, 0, kPackCopy, 5, kNoSrc, 0, 0),
+    RELA_LAYOUT(Bh, kHeadsCT * kHeadsKS * 64, 4, 0, kPackFragsHeads, kAw, kVw, kNumAction, 0),
+    RELA_LAYOUT(bh, 32, 4, 0, kPackHeadBias, kAb, kVb, kNumAction, 0),
+    RELA_LAYOUT(W1d, kConv1I8Weights, 3, 2 * 32 * 4, kPackConv1I8, 0, 1, 0, 0),  // three int8 digits; tail: s1q [32] | b1q [32]
+    RELA_LAYOUT(B2f, Conv2F::CT * Conv2F::KS * 64 * 8, 4, 0, kPackBf16sConv2, 2, kNoSrc, Conv2F::CT, Conv2F::KS),  // a hi and a lo bf16
+    RELA_LAYOUT(B3f, Conv3F::CT * Conv3F::KS * 64 * 8, 4, 0, kPackBf16sConv3, 4, kNoSrc, Conv3F::CT, Conv3F::KS),
+    RELA_LAYOUT(B2e, emu_triples<f32emu::ProbConv2>(), 6, 0, kPackEmuConv2, 2, kNoSrc, f32emu::ProbConv2::NCG, f32emu::ProbConv2::KS),
+    RELA_LAYOUT(B3e, emu_triples<f32emu::ProbConv3>(), 6, 0, kPackEmuConv3, 4, kNoSrc, f32emu::ProbConv3::NCG, f32emu::ProbConv3::KS),
+    // AtariFFNet: linear.0.weight 6, linear.0.bias 7
+    RELA_LAYOUT(Bf, 32 * 784 * 64, 4, 0, kPackFragsFc, 6, kNoSrc, 32, 784),
+    RELA_LAYOUT(BfT, 3136 * 512, 4, 0, kPackFcT, 6, kNoSrc, 0, 0),
+    RELA_LAYOUT(bf, 512, 4, 0, kPackCopy, 7, kNoSrc, 0, 0),
+    RELA_LAYOUT(Bhp, 2 * 4 * 32 * 64, 4, 0, kPackHeadsPerm, kAw, kVw, kNumAction, 0),
+    RELA_LAYOUT(Bff, 32 * FcFast::KS * 64 * 8, 4, 0, kPackBf16sFc, 6, kNoSrc, 32, FcFast::KS),
+    RELA_LAYOUT(Bfe, emu_triples<f32emu::ProbFc>(), 6, 0, kPackEmuFc, 6, kNoSrc, f32emu::ProbFc::NCG, f32emu::ProbFc::KS),
+    // AtariLSTMNet: weight_ih_l0 6, weight_hh_l0 7, bias_ih_l0 8, bias_hh_l0 9
+    RELA_LAYOUT(Bl, (int64_t)GemmLstm::CT * GemmLstm::KS * 64, 4, 0, kPackFragsLstm, 6, 7, GemmLstm::CT, GemmLstm::KS),
+    RELA_LAYOUT(bl, 2048, 4, 0, kPackLstmBias, 8, 9, 0, 0),
+    RELA_LAYOUT(Wrec, 2048 * 392, 32, 0, kPackWihRec64, 6, kNoSrc, 0, 0),  // 8 channels of a rec64 row: 16 B of hi, 16 B of lo
+    RELA_LAYOUT(Wx3, emu_triples<f32emu::ProbGateX>(), 6, 0, kPackEmuGatesPerm, 6, kNoSrc, f32emu::ProbGateX::NCG, f32emu::ProbGateX::KS),
+};
+#undef RELA_LAYOUT
+static_assert(2 * 8 * 64 * 8 * 6 == sizeof(uint4) * Conv1B::FRAG_UINT4 && kConv1I8Weights * 3 == sizeof(uint4) * Conv12I::W1_UINT4,
+              "the layout table and the conv1 kernels disagree about their fragments");
+constexpr uint32_t kLstmNetLayouts = (lay_bit(kLayShared) - 1) | (lay_bit(kLayCount) - lay_bit(kLayBl));
+
+void*& layout_ptr(FFNetDev& d, int layout) {
+  return *reinterpret_cast<void**>(reinterpret_cast<uint8_t*>(&d) + kLayouts[layout].field);
+}
+// the rows in `set`, owned by `mem`
+int alloc_layouts(FFNetDev& d, DevBuffers& mem, uint32_t set) {
+  for (int l = 0; l < kLayCount; ++l) {
+    uint8_t* p = nullptr;
+    if (!(set & lay_bit(l))) continue;
+    if (int rc = mem.alloc(&p, (size_t)kLayouts[l].bytes(), false)) return rc;
+    layout_ptr(d, l) = p;
+  }
+  d.s1q = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(d.W1d) + kConv1I8Weights * 3);
+  d.b1q = d.s1q + 32;
+  return RELA_OK;
+}
+
+// ONE launch packs the layouts in `set` from the load's n tensors dv[] and, where `extra` has pointers, the learners'
+// dgrad operand copies (ffnet_layout.h) of conv2 / conv3 / fc_w (NULL: the net has none)
+int pack_layouts(FFNetDev& d, uint32_t set, const float* const* dv, int n, int A, const ExtraPacks& extra, const float* fc_w,
+                 hipStream_t s) {
+  PackList list;
+  const auto src = [&](int i) { return i == kNoSrc ? nullptr : dv[i < 0 ? n + i : i]; };
+  for (int l = 0; l < kLayCount; ++l) {
+    const LayoutRow& r = kLayouts[l];
+    if (set & lay_bit(l)) list.add(r.kind, src(r.s0), src(r.s1), layout_ptr(d, l), r.a0 == kNumAction ? A : r.a0, r.a1, r.elements);
+  }
+  float* const copy[3] = {extra.w2p, extra.w3p, fc_w ? extra.wfcp : nullptr};
+  const float* const from[3] = {dv[2], dv[4], fc_w};
+  for (int mode = 0; mode < 3; ++mode)
+    if (copy[mode]) list.add(kPackPermute, from[mode], nullptr, copy[mode], mode, 0, kPermFloats[mode]);
+  return launch_weight_pack(list, s);
+}
+
+// rela_*_debug_layout: one row of the table
+int report_layout(FFNetDev& d, int layout, uint32_t packed_set, const char** name, int64_t* bytes, int* packed, void* host_dst) {
+  const LayoutRow& row = kLayouts[layout];
+  const bool is_packed = (packed_set & lay_bit(layout)) != 0;
+  if (name) *name = row.name;
+  if (bytes) *bytes = row.bytes();
+  if (packed) *packed = is_packed;
+  if (host_dst && is_packed) {
+    RELA_HIP(hipDeviceSynchronize());
+    RELA_HIP(hipMemcpy(host_dst, layout_ptr(d, layout), (size_t)row.bytes(), hipMemcpyDeviceToHost));
+  }
   return RELA_OK;
 }
 
@@ -2144,6 +1944,36 @@ int opt_in_dynamic_lds() {
       {reinterpret_cast<const void*>(&conv_mfma_bstat<Conv3>), 2 * Conv3::LDS_BYTES},
   };
   return opt_in(ks, (int)(sizeof(ks) / sizeof(ks[0])));
+}
+
+// rela_*_create: a net with the rows `layouts` of the table, opted in to its kernels' dynamic LDS (own: what only this
+// net launches); a failure frees what was allocated and the net.  rela_*_destroy: free_all.
+template <class Net>
+int create_net(Net** out, int num_action, int device, const char* who, uint32_t layouts, const LdsOptIn* own, int n_own) {
+  RELA_CHECK(out && num_action >= 1 && num_action <= 31, RELA_EINVAL, "%s: num_action must be in 1..31 (got %d)", who, num_action);
+  if (int rc = check_device(device, who)) return rc;
+  DeviceGuard g(device);
+  auto* n = new Net();
+  n->device = device;
+  n->num_action = num_action;
+  int rc = alloc_layouts(n->d, n->mem, layouts);
+  if (rc == RELA_OK) rc = opt_in_dynamic_lds();
+  if (rc == RELA_OK) rc = opt_in(own, n_own);
+  if (rc != RELA_OK) {
+    n->mem.free_all();
+    delete n;
+    return rc;
+  }
+  *out = n;
+  return RELA_OK;
+}
+template <class Net>
+void destroy_net(Net* n) {
+  if (!n) return;
+  DeviceGuard g(n->device);
+  (void)hipDeviceSynchronize();
+  n->mem.free_all();
+  delete n;
 }
 
 // The n parameter tensors of a load as device pointers dv[]: the caller's own (on_device), or copies in ONE staging
@@ -2204,44 +2034,26 @@ struct rela_ffnet {
   // "fast" mode) | 2 = f32 operands as THREE bf16 parts on the bf16 MFMA (gemm_f32emu.h: f32 accuracy)
   int precision = 0;
   int max_rows = 0;  // > 0: the owner never runs more rows (a learner's batch): layouts only larger batches read are not packed
-  // BfT (the f32 split-K fc's weights) of such a net in the split-bf16 mode: no kernel of that mode reads it from 128
-  // rows up, so the per-step re-pack skips it (6.4 MB) and the f32 path packs it on demand from the owner's buffer
-  mutable bool bft_stale = false;
+  // the layouts the last load packed (ffnet_pack_set, ffnet_plan.h); bft_src: the owner's fc weight where that load
+  // left BfT to be packed on demand -- by the forward that reads it, which then adds it to the set
+  mutable uint32_t packed = 0;
   const float* bft_src = nullptr;
+  DevBuffers mem;  // the layouts
 };
 
 extern "C" int rela_ffnet_create(rela_ffnet** out, int num_action, int device) {
-  RELA_CHECK(out && num_action >= 1 && num_action <= 31, RELA_EINVAL,
-             "rela_ffnet_create: num_action must be in 1..31 (got %d)", num_action);
-  if (int rc = check_device(device, "rela_ffnet_create")) return rc;
-  DeviceGuard g(device);
-  auto* n = new rela_ffnet();
-  n->device = device;
-  n->num_action = num_action;
-  FFNetDev& d = n->d;
-  if (int rc = alloc_trunk(d)) return rc;
-  RELA_HIP(hipMalloc(&d.Bf, sizeof(float) * 32 * 784 * 64));
-  RELA_HIP(hipMalloc(&d.BfT, sizeof(float) * 3136 * 512));
-  RELA_HIP(hipMalloc(&d.bf, sizeof(float) * 512));
-  RELA_HIP(hipMalloc(&d.Bhp, sizeof(float) * 2 * 4 * 32 * 64));
-  RELA_HIP(hipMalloc(&d.Bff, sizeof(uint4) * 32 * FcFast::KS * 2 * 64));
-  RELA_HIP(hipMalloc(&d.Bfe, sizeof(uint4) * f32emu::packed_u4<f32emu::ProbFc>()));
-  if (int rc = opt_in_dynamic_lds()) return rc;
   const LdsOptIn fc[] = {{reinterpret_cast<const void*>(&fc_bf16s<FcFast, true>), FcFast::LDS_BYTES},
                          {reinterpret_cast<const void*>(&fc_bf16s<FcFast>), FcFast::LDS_BYTES}};
-  if (int rc = opt_in(fc, 2)) return rc;
-  *out = n;
-  return RELA_OK;
+  return create_net(out, num_action, device, "rela_ffnet_create", lay_bit(kLayFFNetEnd) - 1, fc, 2);
 }
+extern "C" void rela_ffnet_destroy(rela_ffnet* n) { destroy_net(n); }
 
-extern "C" void rela_ffnet_destroy(rela_ffnet* n) {
-  if (!n) return;
+extern "C" int rela_ffnet_debug_layout(const rela_ffnet* n, int index, const char** name, int64_t* bytes, int* packed,
+                                       void* host_dst) {
+  RELA_CHECK(n && index >= 0 && index < kLayFFNetEnd, RELA_EINVAL, "rela_ffnet_debug_layout: an AtariFFNet has %d layouts (index %d)",
+             (int)kLayFFNetEnd, index);
   DeviceGuard g(n->device);
-  (void)hipDeviceSynchronize();
-  void* ps[] = {n->d.B1, n->d.b1, n->d.B2, n->d.b2, n->d.B3, n->d.b3, n->d.Bf, n->d.bf, n->d.Bh, n->d.bh,
-                n->d.BfT, n->d.B2f, n->d.B3f, n->d.Bff, n->d.Bhp, n->d.W1d, n->d.s1q, n->d.b1q, n->d.B2e, n->d.B3e, n->d.Bfe};
-  for (void* p : ps) (void)hipFree(p);
-  delete n;
+  return report_layout(const_cast<FFNetDev&>(n->d), index, n->packed, name, bytes, packed, host_dst);
 }
 
 // Diagnostic: the fused conv1 -> conv2 kernel (conv12_i8) with shader-clock stamps at its phase boundaries (block 0,
@@ -2329,7 +2141,8 @@ extern "C" int rela_runtime_set_cu_reserve(int cus) {
 }
 extern "C" int rela_ffnet_num_action(const rela_ffnet* n) { return n ? n->num_action : 0; }
 namespace rela_amd {
-int ffnet_load_impl(rela_ffnet* n, const rela_ffnet_params* p, int on_device, void* stream_, const FFNetExtraPacks& extra);
+int ffnet_load_impl(rela_ffnet* n, const rela_ffnet_params* p, int on_device, void* stream_, const ExtraPacks& extra);
+int lstmnet_load_impl(rela_lstmnet* n, const rela_lstmnet_params* p, int on_device, void* stream_, const ExtraPacks& extra);
 void ffnet_label_as_learner(rela_ffnet* n) { n->prof_names = kProfLearner; }
 void ffnet_set_max_rows(rela_ffnet* n, int rows) { n->max_rows = rows; }
 }  // namespace rela_amd
@@ -2357,14 +2170,14 @@ extern "C" int64_t rela_ffnet_workspace_bytes(const rela_ffnet* n, int batch) {
 }
 
 extern "C" int rela_ffnet_load(rela_ffnet* n, const rela_ffnet_params* p, int on_device, void* stream_) {
-  return rela_amd::ffnet_load_impl(n, p, on_device, stream_, rela_amd::FFNetExtraPacks{});
+  return rela_amd::ffnet_load_impl(n, p, on_device, stream_, rela_amd::ExtraPacks{});
 }
-int rela_amd::ffnet_load_extra(rela_ffnet* n, const rela_ffnet_params* p, void* stream_, const FFNetExtraPacks& extra) {
+int rela_amd::ffnet_load_extra(rela_ffnet* n, const rela_ffnet_params* p, void* stream_, const ExtraPacks& extra) {
   return ffnet_load_impl(n, p, 1, stream_, extra);
 }
 
 int rela_amd::ffnet_load_impl(rela_ffnet* n, const rela_ffnet_params* p, int on_device, void* stream_,
-                              const FFNetExtraPacks& extra) {
+                              const ExtraPacks& extra) {
   RELA_CHECK(n && p, RELA_EINVAL, "rela_ffnet_load: bad arguments");
   hipStream_t s = (hipStream_t)stream_;
   DeviceGuard g(n->device);
@@ -2376,50 +2189,11 @@ int rela_amd::ffnet_load_impl(rela_ffnet* n, const rela_ffnet_params* p, int on_
   const float* dv[12];
   float* tmp = nullptr;
   if (int rc = stage_params(src, cnt, 12, on_device, "rela_ffnet_load", &tmp, dv, s)) return rc;
-  PackAllArgs a{};
-  for (int i = 0; i < 12; ++i) a.p[i] = dv[i];
-  a.B1 = reinterpret_cast<uint16_t*>(n->d.B1);
-  a.B2f = reinterpret_cast<uint16_t*>(n->d.B2f), a.B3f = reinterpret_cast<uint16_t*>(n->d.B3f);
-  a.Bff = reinterpret_cast<uint16_t*>(n->d.Bff);
-  a.B2 = n->d.B2, a.B3 = n->d.B3, a.Bf = n->d.Bf, a.BfT = n->d.BfT, a.Bh = n->d.Bh, a.Bhp = n->d.Bhp;
-  a.b1 = n->d.b1, a.b2 = n->d.b2, a.b3 = n->d.b3, a.bf = n->d.bf, a.bh = n->d.bh, a.A = A;
-  a.w2p = extra.w2p, a.w3p = extra.w3p, a.wfcp = extra.wfcp;
-  a.W1d = reinterpret_cast<uint8_t*>(n->d.W1d), a.s1q = n->d.s1q, a.b1q = n->d.b1q;
-  a.B2e = reinterpret_cast<uint16_t*>(n->d.B2e), a.B3e = reinterpret_cast<uint16_t*>(n->d.B3e);
-  a.Bfe = reinterpret_cast<uint16_t*>(n->d.Bfe);
-  // elements (threads) per segment of pack_ffnet_all; a segment of zero elements gets no blocks
-  int64_t el[kPackSegs] = {};
-  el[kSegB1] = 2 * 8 * 64 * 8;
-  el[kSegB2] = 4 * 128 * 64, el[kSegB3] = 4 * 144 * 64, el[kSegBf] = (int64_t)32 * 784 * 64;
-  el[kSegBfT] = (int64_t)3136 * 512;
-  el[kSegBh] = 2 * 128 * 64, el[kSegBhp] = 2 * 4 * 32 * 64;
-  el[kSegB2f] = (int64_t)Conv2F::CT * Conv2F::KS * 64 * 8, el[kSegB3f] = (int64_t)Conv3F::CT * Conv3F::KS * 64 * 8;
-  el[kSegBff] = (int64_t)32 * FcFast::KS * 64 * 8;
-  el[kSegBiases] = 672, el[kSegHeadBias] = 32;
-  el[kSegW2p] = extra.w2p ? 64 * 512 : 0, el[kSegW3p] = extra.w3p ? 64 * 576 : 0;
-  el[kSegWfcp] = extra.wfcp ? (int64_t)512 * 3136 : 0;
-  el[kSegW1d] = 32 * 256;
-  // (one thread per bf16 TRIPLE of the f32-accurate layouts: a third of their 2-byte elements)
-  el[kSegB2e] = f32emu::packed_u4<f32emu::ProbConv2>() * 8 / 3, el[kSegB3e] = f32emu::packed_u4<f32emu::ProbConv3>() * 8 / 3;
-  el[kSegBfe] = f32emu::packed_u4<f32emu::ProbFc>() * 8 / 3;
-  // a net whose owner never runs large batches (a learner re-packs after every step) skips the two fc layouts
-  // only large batches read: Bf (f32 fragments, N >= kFcSplitBelow) and Bff (bf16 fragments, N >= kFastMinN)
-  // (... nor the layouts of the f32x3 mode its batches are too small for)
-  const int max_rows = n->max_rows;
-  if (max_rows > 0 && max_rows < kEmuConvMinN) el[kSegB2e] = el[kSegB3e] = 0;
-  if (max_rows > 0 && max_rows < kEmuFcMinN) el[kSegBfe] = 0;
-  if (max_rows > 0 && max_rows < kFcSplitBelow) el[kSegBf] = 0;
-  if (!packs_bf16_fc(max_rows)) el[kSegBff] = 0;  // (the split-K fc_bf16s serves 128 rows and up)
-  n->bft_stale = false;
-  if (max_rows >= kFastTrunkMinN && on_device && n->precision == 1) {  // (the owner's buffer outlives this call)
-    el[kSegBfT] = 0;
-    n->bft_stale = true;
-    n->bft_src = dv[6];
-  }
-  a.first[0] = 0;
-  for (int jn = 0; jn < kPackSegs; ++jn) a.first[jn + 1] = a.first[jn] + (int)ceil_div(el[jn], 256);
-  hipLaunchKernelGGL(pack_ffnet_all, dim3(a.first[kPackSegs]), dim3(256), 0, s, a);
-  RELA_LAUNCH_CHECK();
+  // what this load packs: everything, less what a net with a row limit never reads (ffnet_pack_set)
+  const uint32_t set = ffnet_pack_set(n->max_rows, n->precision, on_device != 0);
+  n->bft_src = ffnet_bft_on_demand(n->max_rows, n->precision, on_device != 0) ? dv[6] : nullptr;  // (the owner's buffer outlives this call)
+  if (int rc = pack_layouts(n->d, set, dv, 12, A, extra, dv[6], s)) return rc;
+  n->packed = set;
   if (int rc = free_staging(tmp, s)) return rc;
   n->loaded = true;
   n->version += 1;
@@ -2432,21 +2206,31 @@ extern "C" int rela_ffnet_forward(const rela_ffnet* n, int N, const uint8_t* s_d
 }
 
 int rela_amd::ffnet_forward_mode(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev, float* q_dev,
-                                 void* ws, int64_t ws_bytes, void* stream_, int mode) {
+                                 void* ws, int64_t ws_bytes, void* stream_, int mode, int rows_limit) {
   RELA_CHECK(n && n->loaded, RELA_ESTATE, "rela_ffnet_forward: parameters were never loaded");
+  const int max_rows = rows_limit < 0 ? n->max_rows : rows_limit;
   RELA_CHECK(N >= 1 && s_dev && legal_dev && q_dev && ws, RELA_EINVAL, "rela_ffnet_forward: bad arguments");
   RELA_CHECK(ws_bytes >= rela_ffnet_workspace_bytes(n, N), RELA_EINVAL,
              "rela_ffnet_forward: workspace of %lld bytes is too small for batch %d", (long long)ws_bytes, N);
   RELA_CHECK(((uintptr_t)s_dev & 15) == 0 && ((uintptr_t)ws & 15) == 0, RELA_EINVAL,
              "rela_ffnet_forward: s_dev and workspace must be 16-byte aligned");
-  RELA_CHECK(n->max_rows <= 0 || N <= n->max_rows, RELA_EINVAL,
-             "rela_ffnet_forward: batch %d on a net whose owner declared at most %d rows", N, n->max_rows);
+  RELA_CHECK(max_rows <= 0 || N <= max_rows, RELA_EINVAL,
+             "rela_ffnet_forward: batch %d on a net whose owner declared at most %d rows", N, max_rows);
   hipStream_t s = (hipStream_t)stream_;
   const FFNetWs w = ffnet_ws(ws, N);
   const FFNetDev& d = n->d;
   const char* const* names = n->prof_names ? n->prof_names : kProfActor;
   const char* name12 = n->prof_names ? "learner_fwd_conv12" : "conv12_fused";  // conv1 -> conv2 in one launch
-  const FfnetPlan plan = plan_ffnet_forward(mode, n->precision, N, n->max_rows);
+  const FfnetPlan plan = plan_ffnet_forward(mode, n->precision, N, max_rows);
+  uint32_t missing = ffnet_plan_reads(plan) & ~n->packed;
+  if (missing == lay_bit(kLayBfT) && n->bft_src) {  // (see rela_ffnet::bft_src)
+    if (int rc = pack_one(kLayouts[kLayBfT].kind, n->bft_src, nullptr, n->d.BfT, 0, 0, kLayouts[kLayBfT].elements, s)) return rc;
+    n->packed |= lay_bit(kLayBfT);
+    missing = 0;
+  }
+  RELA_CHECK(missing == 0, RELA_ESTATE,
+             "rela_ffnet_forward: %d rows in mode %d read layouts (bits 0x%x) the net's last load did not pack (row limit %d)", N,
+             plan.precision, missing, n->max_rows);
 
   // the trunk: a3 as f32, as split-bf16 records in its own place, or as split3 records at rec3 -- whatever plan.fc reads
   uint8_t* rec2 = static_cast<uint8_t*>(ws) + ws_records_offset(N);
@@ -2484,14 +2268,6 @@ int rela_amd::ffnet_forward_mode(const rela_ffnet* n, int N, const uint8_t* s_de
     }
     case kFcF32SplitK: {
       float* part = fc_part_ptr(ws, w.ha, N);
-      if (n->bft_stale) {  // (see rela_ffnet::bft_stale)
-        PackAllArgs a{};
-        a.p[6] = n->bft_src, a.BfT = d.BfT;
-        for (int jn = 0; jn < kPackSegs; ++jn)
-          a.first[jn + 1] = a.first[jn] + (jn == kSegBfT ? (int)ceil_div((int64_t)3136 * 512, 256) : 0);
-        hipLaunchKernelGGL(pack_ffnet_all, dim3(a.first[kPackSegs]), dim3(256), 0, s, a);
-        n->bft_stale = false;
-      }
       ProbFcFwd p{};
       p.M = N, p.N = 512, p.K = 3136;
       p.a3 = w.a3, p.wt = d.BfT, p.part = part;
@@ -2637,11 +2413,8 @@ int ffnet_learner_unsplit(int B, void* ws_on, hipStream_t s) {
 struct rela_lstmnet {
   int device = 0;
   int num_action = 0;
-  FFNetDev d;            // B1..b3 (trunk) and Bh/bh (heads); Bf/bf unused
-  float* Bl = nullptr;   // lstm frags [128][912][64]
-  float* bl = nullptr;   // b_ih + b_hh, permuted [2048]
-  uint8_t* Wrec = nullptr;  // weight_ih_l0 as rec64 rows in the permuted column order [2048][49][64 hi | 64 lo]
-  uint4* Wx3 = nullptr;     // ... as three-part bf16 fragments in the same column order (gemm_s3.h; f32x3 mode)
+  FFNetDev d;       // the shared layouts (trunk, Bh / bh) and Bl, bl, Wrec, Wx3; the AtariFFNet's own stay NULL
+  DevBuffers mem;   // ... which it owns
   bool loaded = false;
   uint64_t version = 0;  // bumped by every load
   // 0 = exact f32; 1 = split-bf16 conv trunk and, from kFastMinN rows up, the x part of the gate GEMM on split-bf16
@@ -2664,31 +2437,19 @@ inline TrunkLabels lstm_trunk_labels(const char* const* names) { return {names[0
 }  // namespace
 
 extern "C" int rela_lstmnet_create(rela_lstmnet** out, int num_action, int device) {
-  RELA_CHECK(out && num_action >= 1 && num_action <= 31, RELA_EINVAL,
-             "rela_lstmnet_create: num_action must be in 1..31 (got %d)", num_action);
-  if (int rc = check_device(device, "rela_lstmnet_create")) return rc;
-  DeviceGuard g(device);
-  auto* n = new rela_lstmnet();
-  n->device = device;
-  n->num_action = num_action;
-  if (int rc = alloc_trunk(n->d)) return rc;
-  RELA_HIP(hipMalloc(&n->Bl, sizeof(float) * (size_t)GemmLstm::CT * GemmLstm::KS * 64));
-  RELA_HIP(hipMalloc(&n->bl, sizeof(float) * 2048));
-  RELA_HIP(hipMalloc(&n->Wrec, (size_t)2048 * 49 * 256));
-  RELA_HIP(hipMalloc(&n->Wx3, sizeof(uint4) * f32emu::packed_u4<f32emu::ProbGateX>()));
-  if (int rc = opt_in_dynamic_lds()) return rc;
-  *out = n;
-  return RELA_OK;
+  return create_net(out, num_action, device, "rela_lstmnet_create", kLstmNetLayouts, nullptr, 0);
 }
+extern "C" void rela_lstmnet_destroy(rela_lstmnet* n) { destroy_net(n); }
 
-extern "C" void rela_lstmnet_destroy(rela_lstmnet* n) {
-  if (!n) return;
+// (a load of an AtariLSTMNet packs every layout it holds)
+extern "C" int rela_lstmnet_debug_layout(const rela_lstmnet* n, int index, const char** name, int64_t* bytes, int* packed,
+                                         void* host_dst) {
+  constexpr int rows = kLayShared + (kLayCount - kLayBl);
+  RELA_CHECK(n && index >= 0 && index < rows, RELA_EINVAL, "rela_lstmnet_debug_layout: an AtariLSTMNet has %d layouts (index %d)", rows,
+             index);
   DeviceGuard g(n->device);
-  (void)hipDeviceSynchronize();
-  void* ps[] = {n->d.B1, n->d.b1, n->d.B2, n->d.b2, n->d.B3, n->d.b3, n->d.Bh, n->d.bh, n->Bl, n->bl,
-                n->d.B2f, n->d.B3f, n->Wrec, n->d.W1d, n->d.s1q, n->d.b1q, n->d.B2e, n->d.B3e, n->Wx3};
-  for (void* p : ps) (void)hipFree(p);
-  delete n;
+  return report_layout(const_cast<FFNetDev&>(n->d), index < kLayShared ? index : kLayBl + (index - kLayShared),
+                       n->loaded ? kLstmNetLayouts : 0u, name, bytes, packed, host_dst);
 }
 
 extern "C" int rela_lstmnet_set_precision(rela_lstmnet* n, int mode) {
@@ -2709,6 +2470,14 @@ extern "C" int64_t rela_lstmnet_workspace_bytes(const rela_lstmnet* n, int batch
 }
 
 extern "C" int rela_lstmnet_load(rela_lstmnet* n, const rela_lstmnet_params* p, int on_device, void* stream_) {
+  return rela_amd::lstmnet_load_impl(n, p, on_device, stream_, rela_amd::ExtraPacks{});
+}
+int rela_amd::lstmnet_load_extra(rela_lstmnet* n, const rela_lstmnet_params* p, void* stream_, const ExtraPacks& extra) {
+  return lstmnet_load_impl(n, p, 1, stream_, extra);
+}
+
+int rela_amd::lstmnet_load_impl(rela_lstmnet* n, const rela_lstmnet_params* p, int on_device, void* stream_,
+                                const ExtraPacks& extra) {
   RELA_CHECK(n && p, RELA_EINVAL, "rela_lstmnet_load: bad arguments");
   hipStream_t s = (hipStream_t)stream_;
   DeviceGuard g(n->device);
@@ -2720,35 +2489,7 @@ extern "C" int rela_lstmnet_load(rela_lstmnet* n, const rela_lstmnet_params* p, 
   const float* dv[14];
   float* tmp = nullptr;
   if (int rc = stage_params(src, cnt, 14, on_device, "rela_lstmnet_load", &tmp, dv, s)) return rc;
-  auto pack = [&](int mode, const float* w, const float* w2, float* frag, int CT, int KS) {
-    const int64_t total = (int64_t)CT * KS * 64;
-    hipLaunchKernelGGL(pack_frags, dim3(ceil_div(total, 256)), dim3(256), 0, s, mode, w, w2, A, frag, CT, KS);
-  };
-  hipLaunchKernelGGL(pack_conv1_bf16x3, dim3(ceil_div(2 * 8 * 64 * 8, 256)), dim3(256), 0, s, dv[0],
-                     reinterpret_cast<uint16_t*>(n->d.B1), 0);
-  pack(kPackConv2, dv[2], nullptr, n->d.B2, 4, 128);
-  pack(kPackConv3, dv[4], nullptr, n->d.B3, 4, 144);
-  hipLaunchKernelGGL(pack_f32emu, dim3(ceil_div(f32emu::packed_u4<f32emu::ProbConv2>() * 8 / 3, 256)), dim3(256), 0, s, 1, dv[2],
-                     reinterpret_cast<uint16_t*>(n->d.B2e), f32emu::ProbConv2::NCG, f32emu::ProbConv2::KS);
-  hipLaunchKernelGGL(pack_f32emu, dim3(ceil_div(f32emu::packed_u4<f32emu::ProbConv3>() * 8 / 3, 256)), dim3(256), 0, s, 2, dv[4],
-                     reinterpret_cast<uint16_t*>(n->d.B3e), f32emu::ProbConv3::NCG, f32emu::ProbConv3::KS);
-  pack(kPackLstm, dv[6], dv[7], n->Bl, GemmLstm::CT, GemmLstm::KS);
-  hipLaunchKernelGGL(pack_wih_rec64_perm, dim3(ceil_div((int64_t)2048 * 3136 / 8, 256)), dim3(256), 0, s, dv[6], n->Wrec);
-  hipLaunchKernelGGL(pack_f32emu, dim3((unsigned)ceil_div(f32emu::packed_u4<f32emu::ProbGateX>() * 8 / 3, 256)), dim3(256), 0, s, 4, dv[6],
-                     reinterpret_cast<uint16_t*>(n->Wx3), f32emu::ProbGateX::NCG, f32emu::ProbGateX::KS);
-  pack(kPackHeads, dv[12], dv[10], n->d.Bh, 2, 128);
-  hipLaunchKernelGGL(pack_conv1_i8, dim3(32), dim3(256), 0, s, dv[0], dv[1], reinterpret_cast<uint8_t*>(n->d.W1d), n->d.s1q,
-                     n->d.b1q);
-  hipLaunchKernelGGL(pack_frags_bf16s, dim3(ceil_div((int64_t)Conv2F::CT * Conv2F::KS * 64 * 8, 256)), dim3(256), 0, s, 1,
-                     dv[2], reinterpret_cast<uint16_t*>(n->d.B2f), Conv2F::CT, Conv2F::KS);
-  hipLaunchKernelGGL(pack_frags_bf16s, dim3(ceil_div((int64_t)Conv3F::CT * Conv3F::KS * 64 * 8, 256)), dim3(256), 0, s, 2,
-                     dv[4], reinterpret_cast<uint16_t*>(n->d.B3f), Conv3F::CT, Conv3F::KS);
-  RELA_HIP(hipMemcpyAsync(n->d.b1, dv[1], sizeof(float) * 32, hipMemcpyDeviceToDevice, s));
-  RELA_HIP(hipMemcpyAsync(n->d.b2, dv[3], sizeof(float) * 64, hipMemcpyDeviceToDevice, s));
-  RELA_HIP(hipMemcpyAsync(n->d.b3, dv[5], sizeof(float) * 64, hipMemcpyDeviceToDevice, s));
-  hipLaunchKernelGGL(pack_lstm_bias, dim3(8), dim3(256), 0, s, dv[8], dv[9], n->bl);
-  hipLaunchKernelGGL(pack_head_bias, dim3(1), dim3(64), 0, s, dv[13], dv[11], A, n->d.bh);
-  RELA_LAUNCH_CHECK();
+  if (int rc = pack_layouts(n->d, kLstmNetLayouts, dv, 14, A, extra, nullptr, s)) return rc;
   if (int rc = free_staging(tmp, s)) return rc;
   n->loaded = true;
   n->version += 1;
@@ -2788,10 +2529,10 @@ extern "C" int rela_lstmnet_step(const rela_lstmnet* n, int N, const uint8_t* s_
   if (tp.trunk == kTrunkS3) {
     ProfScope prof("lstm_gates_x_f32x3", s);
     note_launch("gemm_s3<gates_x>");
-    s3::launch<ProbGateX3, s3::kEpiRaw>(rec3, n->Wx3, nullptr, gx, N, s);
+    s3::launch<ProbGateX3, s3::kEpiRaw>(rec3, n->d.Wx3, nullptr, gx, N, s);
     x_in_gx = true;
   } else if (tp.trunk == kTrunkBf16 && tp.a3_records) {
-    int rc = gemm16::launch_rec64_nt(reinterpret_cast<const uint8_t*>(a3), n->Wrec, N, 2048, 49, gemm16::EpiPlain{gx, 2048}, s,
+    int rc = gemm16::launch_rec64_nt(reinterpret_cast<const uint8_t*>(a3), n->d.Wrec, N, 2048, 49, gemm16::EpiPlain{gx, 2048}, s,
                                      "lstm_gates_x_bf16");
     if (rc != RELA_OK) return rc;
     x_in_gx = true;
@@ -2800,10 +2541,10 @@ extern "C" int rela_lstmnet_step(const rela_lstmnet* n, int N, const uint8_t* s_
     ProfScope prof("lstm_gates_mfma", s);
     if (x_in_gx) {  // the f32 MFMA kernel adds h x W_hh (K = 512) and the bias and runs the cell
       note_launch("gemm_mfma<GemmLstmH> (f32)");
-      launch_gemm_bm<GemmLstmH, GemmLstmH112>(h_in, gx, n->Bl, n->bl, h_out, c_in, c_out, N, s);
+      launch_gemm_bm<GemmLstmH, GemmLstmH112>(h_in, gx, n->d.Bl, n->d.bl, h_out, c_in, c_out, N, s);
     } else {
       note_launch("gemm_mfma<GemmLstm> (f32)");
-      launch_gemm_bm<GemmLstm, GemmLstm112>(a3, h_in, n->Bl, n->bl, h_out, c_in, c_out, N, s);
+      launch_gemm_bm<GemmLstm, GemmLstm112>(a3, h_in, n->d.Bl, n->d.bl, h_out, c_in, c_out, N, s);
     }
   }
   if (q_dev || adv_dev) {
@@ -2842,13 +2583,11 @@ int lstmnet_trunk(const rela_lstmnet* n, int N, const uint8_t* s_dev, float* a1,
   return RELA_OK;
 }
 
-int64_t gate_x3_packed_bytes() { return (int64_t)sizeof(uint4) * f32emu::packed_u4<f32emu::ProbGateX>(); }
+int64_t gate_x3_packed_bytes() { return kLayouts[kLayWx3].bytes(); }
 int pack_gate_x3(const float* w_ih_dev, void* dst, bool permuted, hipStream_t s) {
   RELA_CHECK(w_ih_dev && dst, RELA_EINVAL, "pack_gate_x3: bad arguments");
-  hipLaunchKernelGGL(pack_f32emu, dim3((unsigned)ceil_div(f32emu::packed_u4<f32emu::ProbGateX>() * 8 / 3, 256)), dim3(256), 0, s,
-                     permuted ? 4 : 3, w_ih_dev, reinterpret_cast<uint16_t*>(dst), f32emu::ProbGateX::NCG, f32emu::ProbGateX::KS);
-  RELA_LAUNCH_CHECK();
-  return RELA_OK;
+  return pack_one(permuted ? kPackEmuGatesPerm : kPackEmuFc, w_ih_dev, nullptr, dst, f32emu::ProbGateX::NCG, f32emu::ProbGateX::KS,
+                  kLayouts[kLayWx3].elements, s);
 }
 int gate_x3_gemm(const uint8_t* a3_records, const void* packed, const float* bias, float* gx, int M, hipStream_t s) {
   RELA_CHECK(a3_records && packed && bias && gx && M >= 1, RELA_EINVAL, "gate_x3_gemm: bad arguments");

@@ -34,6 +34,7 @@ inline FFNetWs ffnet_ws(void* ws, int N) {
 // weight copies in the k order the learner's dgrad GEMMs read (one element per call):
 //   conv2: dst[oc][(kh*4+kw)*32+c], conv3: dst[oc][(kh*3+kw)*64+c], fc: dst[u][pos*64+c] <- src[u][c*49+pos]
 enum { kPermConv2 = 0, kPermConv3 = 1, kPermFc = 2 };
+constexpr int kPermFloats[3] = {64 * 512, 64 * 576, 512 * 3136};  // floats of a copy (= of the tensor), by mode
 __device__ __forceinline__ void permute_weight_at(int mode, int idx, const float* __restrict__ src, float* __restrict__ dst) {
   if (mode == kPermConv2) {
     const int oc = idx >> 9, n = idx & 511, c = n & 31, r = n >> 5;
@@ -47,25 +48,31 @@ __device__ __forceinline__ void permute_weight_at(int mode, int idx, const float
   }
 }
 // the three copies above, made by the SAME launch that re-packs the net's own layouts (a learner re-packs after
-// every optimiser step: three more launches otherwise); any pointer may be NULL
-struct FFNetExtraPacks {
+// every optimiser step: three more launches otherwise); any pointer may be NULL (an AtariLSTMNet has no fc: wfcp is ignored)
+struct ExtraPacks {
   float *w2p = nullptr, *w3p = nullptr, *wfcp = nullptr;
 };
 }  // namespace rela_amd
 
 #include "../../include/rela_amd.h"
 namespace rela_amd {
-// rela_ffnet_load from device pointers + the learner's dgrad operand copies in the same launch
-int ffnet_load_extra(rela_ffnet* n, const rela_ffnet_params* p, void* stream, const FFNetExtraPacks& extra);
+// rela_ffnet_load / rela_lstmnet_load from device pointers + the learner's dgrad operand copies in the same launch
+int ffnet_load_extra(rela_ffnet* n, const rela_ffnet_params* p, void* stream, const ExtraPacks& extra);
+int lstmnet_load_extra(rela_lstmnet* n, const rela_lstmnet_params* p, void* stream, const ExtraPacks& extra);
 // per-kernel timing labels "learner_fwd_*" instead of the actor-side names (prof.h)
 void ffnet_label_as_learner(rela_ffnet* n);
-// the owner never runs more than `rows` rows through this net: rela_ffnet_load skips the layouts only larger batches read
+// the owner never runs more than `rows` rows through this net: rela_ffnet_load skips the layouts only larger batches
+// read (ffnet_pack_set, ffnet_plan.h)
 void ffnet_set_max_rows(rela_ffnet* n, int rows);
 // rela_ffnet_forward with the precision chosen by the caller: mode is an FfnetMode (ffnet_plan.h, which also says what
 // runs in each): kModeNet (-1) = the net's own (rela_ffnet_set_precision), kModeF32 (0) = exact f32 whatever the net says
-// -- the learner's pass that keeps a1 / a2 / a3 / h for the backward kernels
+// -- the learner's pass that keeps a1 / a2 / a3 / h for the backward kernels.
+// rows_limit: the most rows of this call, which the plan is made for (< 0: the net's own limit, 0: none).  The limit a net
+// declares says which layouts its loads pack; a caller that knows the layouts of a larger batch are packed -- the
+// learner's merged f32x3 forward over 2 x batch rows -- passes its own.  RELA_ESTATE if the plan reads a layout the net's
+// last load did not pack.
 int ffnet_forward_mode(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev, float* q_dev, void* ws,
-                       int64_t ws_bytes, void* stream, int mode);
+                       int64_t ws_bytes, void* stream, int mode, int rows_limit = -1);
 // The Ape-X learner's three forwards of td_err (apex.py:30-45) in split-bf16 with one launch per layer: online over
 // [s ; s'] (2 B rows) and target over s' (B rows).  ws_on: ffnet_ws layout for 2 B rows, ws_tg for B rows; a1 (rows < B),
 // a2, a3 come out as split records; ffnet_learner_unsplit turns the rows < B into f32 in place for the backward pass.

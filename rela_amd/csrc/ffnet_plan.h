@@ -45,8 +45,39 @@ enum FcKind {
   kFcS3SplitK = 5,    // gemm_s3<fc>, free to split K: s3::plan picks the slices (fc_reduce if more than one)
 };
 
+// ---- weight layouts -------------------------------------------------------------------------------------------------
+// The kernel-layout copies a net holds of its weights; the index is the row of the layout table (ffnet.hip: names,
+// sizes, pack bodies).  Both nets hold the rows below kLayShared, an AtariFFNet adds [kLayShared, kLayFFNetEnd), an
+// AtariLSTMNet [kLayFFNetEnd, kLayCount).
+enum Layout {
+  kLayB1, kLayb1, kLayB2, kLayb2, kLayB3, kLayb3, kLayBh, kLaybh, kLayW1d, kLayB2f, kLayB3f, kLayB2e, kLayB3e, kLayShared,
+  kLayBf = kLayShared, kLayBfT, kLaybf, kLayBhp, kLayBff, kLayBfe, kLayFFNetEnd,
+  kLayBl = kLayFFNetEnd, kLaybl, kLayWrec, kLayWx3, kLayCount
+};
+constexpr uint32_t lay_bit(int layout) { return 1u << layout; }
+
 // does a net whose owner declared max_rows (0: no limit) pack the bf16 fc fragments (Bff)?
 inline bool packs_bf16_fc(int max_rows) { return !(max_rows > 0 && max_rows < kFastTrunkMinN); }
+
+// The layouts a load of an AtariFFNet packs.  A net whose owner never runs more than max_rows rows (a learner, which
+// re-packs after every step) skips the fc layouts only larger batches read -- Bf (f32 fragments, N >= kFcSplitBelow),
+// Bff (bf16 fragments, the split-K fc_bf16s serves 128 rows and up) -- and the layouts of the f32x3 mode its batches are
+// too small for.  BfT (the f32 split-K fc's weights, 6.4 MB) of such a net in the split-bf16 mode: no kernel of that
+// mode reads it from 128 rows up, so a load from device pointers leaves it out and the f32 path packs it on demand from
+// the owner's buffer, which outlives the load (ffnet_forward_mode).
+inline bool ffnet_bft_on_demand(int max_rows, int precision, bool on_device) {
+  return max_rows >= kFastTrunkMinN && on_device && precision == kModeBf16x2;
+}
+inline uint32_t ffnet_pack_set(int max_rows, int precision, bool on_device) {
+  uint32_t set = lay_bit(kLayFFNetEnd) - 1;
+  const bool limited = max_rows > 0;
+  if (limited && max_rows < kEmuConvMinN) set &= ~(lay_bit(kLayB2e) | lay_bit(kLayB3e));
+  if (limited && max_rows < kEmuFcMinN) set &= ~lay_bit(kLayBfe);
+  if (limited && max_rows < kFcSplitBelow) set &= ~lay_bit(kLayBf);
+  if (!packs_bf16_fc(max_rows)) set &= ~lay_bit(kLayBff);
+  if (ffnet_bft_on_demand(max_rows, precision, on_device)) set &= ~lay_bit(kLayBfT);
+  return set;
+}
 
 // slices of the f32 split-K fc
 inline int fc_splits(int N) {
@@ -75,7 +106,19 @@ struct FfnetPlan {
   int fc_slices, fc_per;  // kFcF32SplitK: slices | kFcBf16SplitK: slices and positions per slice | else 1, 0
 };
 
-// mode: an FfnetMode; net_precision: what rela_ffnet_set_precision left; max_rows: ffnet_set_max_rows (0: no limit)
+// the layouts the kernels of a plan read (ffnet_forward_mode refuses a plan whose layouts the net's load did not pack):
+// the biases of conv2, conv3, fc and the heads with Bhp always, then by TrunkKind (conv1's bias is folded into W1d's tail)
+// and by FcKind
+inline uint32_t ffnet_plan_reads(const FfnetPlan& p) {
+  const uint32_t trunk[3] = {lay_bit(kLayB1) | lay_bit(kLayb1) | lay_bit(kLayB2) | lay_bit(kLayB3),
+                             lay_bit(kLayW1d) | lay_bit(kLayB2f) | lay_bit(kLayB3f),
+                             lay_bit(kLayW1d) | lay_bit(kLayB2e) | lay_bit(kLayB3e)};
+  const int fc[6] = {kLayBfT, kLayBf, kLayBff, kLayBff, kLayBfe, kLayBfe};
+  return lay_bit(kLayb2) | lay_bit(kLayb3) | lay_bit(kLaybf) | lay_bit(kLayBhp) | lay_bit(kLaybh) | trunk[p.trunk] | lay_bit(fc[p.fc]);
+}
+
+// mode: an FfnetMode; net_precision: what rela_ffnet_set_precision left; max_rows: the rows limit of the call -- the
+// net's own (ffnet_set_max_rows, 0: no limit) unless the caller of ffnet_forward_mode passes another
 inline FfnetPlan plan_ffnet_forward(int mode, int net_precision, int N, int max_rows) {
   FfnetPlan p{};
   p.keep_f32 = mode == kModeF32x3KeepF32;

@@ -63,7 +63,7 @@ rela_ffnet_params params_at(const rela_apex_learner* l, const float* base) {
 int repack(rela_apex_learner* l, bool online, bool target, hipStream_t s) {
   if (online) {
     const rela_ffnet_params p = params_at(l, l->P);
-    FFNetExtraPacks extra;  // the dgrad operand copies ride along in the re-pack launch
+    ExtraPacks extra;  // the dgrad operand copies ride along in the re-pack launch
     extra.w2p = l->w2p, extra.w3p = l->w3p, extra.wfcp = l->wfcp;
     int rc = ffnet_load_extra(l->online, &p, s, extra);
     if (rc != RELA_OK) return rc;
@@ -105,7 +105,7 @@ struct HeadFcBwd {
   const float* d_ha;            // [Bn][32] from the loss kernel: columns 0..A-1 = fc_a, 31 = fc_v
   const float *h, *a3;          // relu(fc) [Bn][512], relu(conv3) [Bn][49][64] channel-last (ffnet_layout.h)
   const float *a_w, *v_w;       // fc_a.weight [A][512], fc_v.weight [512] (state_dict layout)
-  const float* wfcp;            // the fc weight in a3's column order (permute_weights, kPermFc)
+  const float* wfcp;            // the fc weight in a3's column order (permute_weight_at, kPermFc)
   float *d_h, *d_a3;            // out: [Bn][512] masked by h > 0, [Bn][49][64] masked by a3 > 0
   float *g_a_w, *g_v_w, *g_fc_w, *g_fc_b;  // out: gradients, state_dict layout
   float* s32;                   // the column sums of d_ha, for head_bias_grad after the queued sums have run
@@ -174,9 +174,9 @@ int build_learner(rela_apex_learner* l, int num_action, int max_batch, int multi
   ffnet_set_max_rows(l->online, max_batch);
   ffnet_set_max_rows(l->target, max_batch);
   DevBuffers& m = l->mem;
-  if (int rc = m.alloc(&l->w2p, 64 * 512, false)) return rc;
-  if (int rc = m.alloc(&l->w3p, 64 * 576, false)) return rc;
-  if (int rc = m.alloc(&l->wfcp, 512 * 3136, false)) return rc;
+  if (int rc = m.alloc(&l->w2p, kPermFloats[kPermConv2], false)) return rc;
+  if (int rc = m.alloc(&l->w3p, kPermFloats[kPermConv3], false)) return rc;
+  if (int rc = m.alloc(&l->wfcp, kPermFloats[kPermFc], false)) return rc;
   // (the merged split-bf16 forward runs the online net over 2 x batch rows: [s ; s'])
   l->ws_bytes = std::max(rela_ffnet_workspace_bytes(nullptr, max_batch), rela_ffnet_workspace_bytes(nullptr, 2 * max_batch));
   if (int rc = m.alloc(&l->ws_on, (size_t)l->ws_bytes, false)) return rc;
@@ -372,10 +372,8 @@ extern "C" int rela_apex_learner_loss(rela_apex_learner* l, int batch, const voi
     rc = rela_ffnet_forward(l->target, Bn, nobs, nlegal, q_nt, l->ws_tmp, l->ws_bytes, s);
     if (rc != RELA_OK) return rc;
     // (the net's declared batch limit only says which weight layouts its loads pack; the three-part ones this launch reads
-    // are packed from 512 rows up, and the workspaces are sized for 2 x the batch)
-    ffnet_set_max_rows(l->online, 2 * l->Bmax);
-    rc = ffnet_forward_mode(l->online, 2 * Bn, in2, legal2, q_on, l->ws_on, l->ws_bytes, s, 3);  // q_no = q_on + Bn * A
-    ffnet_set_max_rows(l->online, l->Bmax);
+    // are packed from 512 rows up, and the workspaces are sized for 2 x the batch: the call brings its own limit)
+    rc = ffnet_forward_mode(l->online, 2 * Bn, in2, legal2, q_on, l->ws_on, l->ws_bytes, s, 3, 2 * l->Bmax);  // q_no = q_on + Bn * A
     if (rc != RELA_OK) return rc;
     l->pend_rows = 2 * Bn;  // the workspace layout the backward must address (it reads the first Bn rows)
   } else {
@@ -449,6 +447,10 @@ extern "C" int rela_apex_learner_grad(rela_apex_learner* l, void* stream_) {
 // Test tap: trunk_backward (learner_common.h) on its own, with the activations and the masked d_a3 as inputs of the call.
 // Everything the learners keep across steps (scratch, the permuted weight copies, the side lane) lives for this one call.
 namespace {
+// one of the dgrad operand copies on its own, as a pack list of one segment (the learners' re-pack makes them in its launch)
+int permute_weight(int mode, const float* src, float* dst, hipStream_t s) {
+  return pack_one(kPackPermute, src, nullptr, dst, mode, 0, kPermFloats[mode], s);
+}
 struct TrunkTapScratch {
   DevBuffers mem;
   hipStream_t side = nullptr;
@@ -475,10 +477,10 @@ extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fa
   TrunkTapScratch sc;
   const size_t cpart_floats = (size_t)kColsumBlocks * (32 + 512 + 64 + 64 + 32);  // as the learners size it
   float *w2p = nullptr, *w3p = nullptr;
-  if (int rc = sc.mem.alloc(&w2p, 64 * 512, false)) return rc;
-  if (int rc = sc.mem.alloc(&w3p, 64 * 576, false)) return rc;
-  hipLaunchKernelGGL(permute_weights, dim3(ceil_div(64 * 512, 256)), dim3(256), 0, s, kPermConv2, conv2_w, w2p, 64 * 512);
-  hipLaunchKernelGGL(permute_weights, dim3(ceil_div(64 * 576, 256)), dim3(256), 0, s, kPermConv3, conv3_w, w3p, 64 * 576);
+  if (int rc = sc.mem.alloc(&w2p, kPermFloats[kPermConv2], false)) return rc;
+  if (int rc = sc.mem.alloc(&w3p, kPermFloats[kPermConv3], false)) return rc;
+  if (int rc = permute_weight(kPermConv2, conv2_w, w2p, s)) return rc;
+  if (int rc = permute_weight(kPermConv3, conv3_w, w3p, s)) return rc;
   TrunkBwd t{};
   t.Bn = frames, t.obs = obs, t.a1 = a1, t.a2 = a2, t.d_a3 = d_a3, t.d_a2 = d_a2, t.d_a1 = d_a1;
   t.w2p = w2p, t.w3p = w3p;
@@ -547,10 +549,10 @@ extern "C" int rela_debug_head_fc_backward(int batch, int A, int mode, int lanes
   hipStream_t s = (hipStream_t)stream_;
   TrunkTapScratch sc;
   float *wfcp = nullptr, *cpart = nullptr, *s32 = nullptr;
-  if (int rc = sc.mem.alloc(&wfcp, 512 * 3136, false)) return rc;
+  if (int rc = sc.mem.alloc(&wfcp, kPermFloats[kPermFc], false)) return rc;
   if (int rc = sc.mem.alloc(&cpart, (size_t)kColsumBlocks * (32 + 512), false)) return rc;
   if (int rc = sc.mem.alloc(&s32, 32, false)) return rc;
-  hipLaunchKernelGGL(permute_weights, dim3(ceil_div(512 * 3136, 256)), dim3(256), 0, s, kPermFc, fc_w, wfcp, 512 * 3136);
+  if (int rc = permute_weight(kPermFc, fc_w, wfcp, s)) return rc;
   hipStream_t sw = s;
   if (lanes) {  // as rela_apex_learner_grad: the weight gradients and the column sums on a side lane
     RELA_HIP(hipStreamCreateWithFlags(&sc.side, hipStreamNonBlocking));

@@ -1,8 +1,8 @@
 // learner_common.h -- pieces shared by the two hand-written learner steps (learner.hip: Ape-X /
 // AtariFFNet; learner_r2d2.hip: R2D2 / AtariLSTMNet): the gemm_lds problem descriptions of the conv trunk's
 // backward pass, split-K reduction, column sums, global-norm clipping and the optimisers, and -- host side, at the
-// end -- DevBuffers (the owner of a learner's device buffers) and LearnerCore, the base of rela_apex_learner and
-// rela_r2d2_learner: the flat parameter / gradient / optimiser-state store and what the entry points do with it.
+// end -- LearnerCore, the base of rela_apex_learner and rela_r2d2_learner: the flat parameter / gradient /
+// optimiser-state store and what the entry points do with it (its device buffers belong to a DevBuffers, common.h).
 // Everything sits in an anonymous namespace: each translation unit gets its own copy of the kernels.
 #pragma once
 #include <cmath>
@@ -16,6 +16,7 @@
 #include "param_layout.h"
 #include "prof.h"
 #include "value_rescale.h"
+#include "weight_pack.h"
 #include "dgrad_conv_bf16.h"
 #include "wgrad_conv1_bf16.h"
 #include "wgrad_conv2_bf16.h"
@@ -147,7 +148,7 @@ struct ProbFcWgrad : ProbBase {
 //   M = frames * 81, N = 64, K = 9 * 64, k = (kh*3+kw)*64 + oc
 struct ProbDgrad3 : ProbBase {
   static constexpr int kFoldChunks = 2;
-  const float *d_out, *wp, *a2;  // d_out [b][49][64]; wp = w3p (permute_weights); a2 [b][81][64]
+  const float *d_out, *wp, *a2;  // d_out [b][49][64]; wp = w3p (permute_weight_at, ffnet_layout.h); a2 [b][81][64]
   float* d_a2;
   // the output pixel (oy, ox) of frame b that tap k >> 6 connects to row m (m clamped; oy, ox may lie outside the image)
   __device__ void tap_pixel(int m, int k, int& b, int& oy, int& ox) const {
@@ -183,7 +184,7 @@ struct ProbDgrad3 : ProbBase {
 //   M = frames * 100, N = 4 * 32 (n = (2s+r)*32 + c), K = 4 * 64, k = (2p+q)*64 + oc
 struct ProbDgrad2 : ProbBase {
   static constexpr int kFoldChunks = 2;
-  const float *d_out, *wp, *a1;  // d_out [b][81][64]; wp = w2p (permute_weights); a1 [b][400][32]
+  const float *d_out, *wp, *a1;  // d_out [b][81][64]; wp = w2p (permute_weight_at, ffnet_layout.h); a1 [b][400][32]
   float* d_a1;
   __device__ void tap_pixel(int m, int k, int& b, int& oy, int& ox) const {  // (as ProbDgrad3's)
     m = min(m, M - 1);
@@ -498,12 +499,6 @@ __global__ __launch_bounds__(1024) void learner_td_loss_grad(int Bn, int A, cons
   if (threadIdx.x == 0) loss_out[0] = red[0] * inv_b;
 }
 
-// ---- weight copies in the k order the dgrad GEMMs read (ffnet_layout.h: permute_weight_at) ------
-__global__ void permute_weights(int mode, const float* __restrict__ src, float* __restrict__ dst, int total) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx < total) permute_weight_at(mode, idx, src, dst);
-}
-
 // ---- clip_grad_norm_ + optimiser over the flat buffers ----------------------------------------
 constexpr int kNormBlocks = 256;
 __global__ __launch_bounds__(256) void sumsq_partial(const float* __restrict__ g, int64_t n, double* __restrict__ part) {
@@ -624,7 +619,7 @@ struct TrunkBwd {
   float *d_a2, *d_a1;  // scratch [Bn][81][64], [Bn][400][32]
   float* part;         // scratch, kTrunkPartFloats
   float* cpart;        // scratch, kColsumBlocks * 512
-  const float *w2p, *w3p;  // conv2 / conv3 weights in dgrad k order (permute_weights)
+  const float *w2p, *w3p;  // conv2 / conv3 weights in dgrad k order (permute_weight_at, ffnet_layout.h)
   float *g_c1w, *g_c1b, *g_c2w, *g_c2b, *g_c3w, *g_c3b;  // gradients, state_dict layout
   bool fast = false;   // the learner's bf16x2 mode: conv1's weight gradient on bf16 MFMA
   // the f32x3 mode: the weight-gradient GEMMs below (contraction over batch x positions) on the bf16 MFMA with three-part
@@ -801,24 +796,6 @@ inline void optimizer_apply(OptimState& o, float* P, const float* G, float* S1, 
                        bc1, bc2s, (const float*)norm);
   }
 }
-
-// ---- the device buffers of one owner: every pointer handed out is recorded, free_all releases them -----------------
-struct DevBuffers {
-  std::vector<void*> ptrs;
-  template <class T>
-  int alloc(T** p, size_t count, bool zero) {
-    void* v = nullptr;
-    RELA_HIP(hipMalloc(&v, sizeof(T) * count));
-    ptrs.push_back(v);
-    *p = static_cast<T*>(v);
-    if (zero) RELA_HIP(hipMemset(v, 0, sizeof(T) * count));
-    return RELA_OK;
-  }
-  void free_all() {
-    for (void* p : ptrs) (void)hipFree(p);
-    ptrs.clear();
-  }
-};
 
 // ---- what the two learners share on the host ------------------------------------------------------------------------
 // The flat store: P (online), PT (target), G (gradients), S1 / S2 (optimiser state), each off[nseg] floats with the

@@ -662,12 +662,10 @@ int repack_r2d2(rela_r2d2_learner* l, bool online, bool target, hipStream_t s) {
   RELA_HIP(pack_attr);
   if (online) {
     const rela_lstmnet_params p = lparams_at(l, l->P);
-    int rc = rela_lstmnet_load(l->online, &p, 1, s);
+    ExtraPacks extra;  // the dgrad operand copies ride along in the re-pack launch
+    extra.w2p = l->w2p, extra.w3p = l->w3p;
+    int rc = lstmnet_load_extra(l->online, &p, s, extra);
     if (rc != RELA_OK) return rc;
-    hipLaunchKernelGGL(permute_weights, dim3(ceil_div(64 * 512, 256)), dim3(256), 0, s, kPermConv2, p.conv2_w, l->w2p,
-                       64 * 512);
-    hipLaunchKernelGGL(permute_weights, dim3(ceil_div(64 * 576, 256)), dim3(256), 0, s, kPermConv3, p.conv3_w, l->w3p,
-                       64 * 576);
     hipLaunchKernelGGL(pack_lstm_learner, dim3(kGates / kPackRows), dim3(256), kPackRows * kFeat * sizeof(float), s, p.w_ih, p.w_hh, p.b_ih, p.b_hh,
                        l->wihT[0], l->wihp, l->whhT[0], l->bsum[0]);
     RELA_LAUNCH_CHECK();
@@ -865,8 +863,8 @@ int build_learner(rela_r2d2_learner* l, int num_action, int max_batch, int multi
   if (int rc = rela_lstmnet_create(&l->online, num_action, device)) return rc;
   if (int rc = rela_lstmnet_create(&l->target, num_action, device)) return rc;
   DevBuffers& m = l->mem;
-  if (int rc = m.alloc(&l->w2p, 64 * 512, false)) return rc;
-  if (int rc = m.alloc(&l->w3p, 64 * 576, false)) return rc;
+  if (int rc = m.alloc(&l->w2p, kPermFloats[kPermConv2], false)) return rc;
+  if (int rc = m.alloc(&l->w3p, kPermFloats[kPermConv3], false)) return rc;
   for (int w = 0; w < 2; ++w) {
     if (int rc = m.alloc(&l->wihT[w], (size_t)kGates * kFeat, false)) return rc;
     if (int rc = m.alloc(&l->whhT[w], (size_t)kGates * kHid, false)) return rc;

@@ -21,46 +21,60 @@ from . import _capi as capi
 from .replay import OBS_BYTES
 
 
-class FFNetHandle:
-    """One immutable device copy of AtariFFNet parameters in kernel layout (rela_ffnet_*)."""
+class _NetHandle:
+    """One immutable device copy of a net's parameters in kernel layout: the handle of rela_<_PREFIX>_*, loaded from
+    the state_dict keys KEYS in the order of the fields of _PARAMS."""
 
-    KEYS = ("net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.weight", "net.4.bias",
-            "linear.0.weight", "linear.0.bias", "fc_v.weight", "fc_v.bias", "fc_a.weight", "fc_a.bias")
+    _PREFIX = _PARAMS = KEYS = None
+
+    def _fn(self, what):
+        return getattr(capi.lib, "rela_%s_%s" % (self._PREFIX, what))
 
     def __init__(self, num_action, device="cuda:0"):
         self.device = torch.device(device)
         self.num_action = num_action
         h = C.c_void_p()
-        capi.check(capi.lib.rela_ffnet_create(C.byref(h), num_action, self.device.index or 0), "rela_ffnet_create")
+        capi.check(self._fn("create")(C.byref(h), num_action, self.device.index or 0), "rela_%s_create" % self._PREFIX)
         self.h = h
 
     def load_state_dict(self, sd, prefix=""):
-        """sd: a (sub-)state_dict with the N1 keys; tensors may live on the CPU or on this GPU."""
-        p = capi.FFNetParams()
+        """sd: a (sub-)state_dict with the net's keys; tensors may live on the CPU or on this GPU."""
+        p = self._PARAMS()
         keep = []
-        for (field, _), key in zip(capi.FFNetParams._fields_, self.KEYS):
+        for (field, _), key in zip(self._PARAMS._fields_, self.KEYS):
             t = sd[prefix + key].detach().to(self.device, torch.float32).contiguous()
             keep.append(t)
             setattr(p, field, t.data_ptr())
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        capi.check(capi.lib.rela_ffnet_load(self.h, C.byref(p), 1, stream), "rela_ffnet_load")
+        capi.check(self._fn("load")(self.h, C.byref(p), 1, stream), "rela_%s_load" % self._PREFIX)
         self._keep = keep  # packing kernels are stream-ordered; keep sources alive until the next load
 
     def set_precision(self, mode):
-        """"f32" (default: exact f32 MFMA), "f32x3" (conv2 / conv3 / fc with both f32 operands as three bf16 parts on
-        the bf16 matrix cores: f32 accuracy, csrc/gemm_f32emu.h) or "bf16x2" (the fast mode: two bf16 parts, 16-bit
-        significands, |dQ| < 2e-5 max|Q|); include/rela_amd.h rela_ffnet_set_precision."""
-        capi.check(capi.lib.rela_ffnet_set_precision(self.h, {"f32": 0, "bf16x2": 1, "f32x3": 2}[mode]),
-                   "rela_ffnet_set_precision")
+        capi.check(self._fn("set_precision")(self.h, {"f32": 0, "bf16x2": 1, "f32x3": 2}[mode]),
+                   "rela_%s_set_precision" % self._PREFIX)
 
     def close(self):
         if getattr(self, "h", None):
-            capi.lib.rela_ffnet_destroy(self.h)
+            self._fn("destroy")(self.h)
             self.h = None
 
     def __del__(self):
         if capi is not None and getattr(capi, "lib", None) is not None:  # module globals die first at exit
             self.close()
+
+
+class FFNetHandle(_NetHandle):
+    """One immutable device copy of AtariFFNet parameters in kernel layout (rela_ffnet_*)."""
+
+    _PREFIX, _PARAMS = "ffnet", capi.FFNetParams
+    KEYS = ("net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.weight", "net.4.bias",
+            "linear.0.weight", "linear.0.bias", "fc_v.weight", "fc_v.bias", "fc_a.weight", "fc_a.bias")
+
+    def set_precision(self, mode):
+        """"f32" (default: exact f32 MFMA), "f32x3" (conv2 / conv3 / fc with both f32 operands as three bf16 parts on
+        the bf16 matrix cores: f32 accuracy, csrc/gemm_f32emu.h) or "bf16x2" (the fast mode: two bf16 parts, 16-bit
+        significands, |dQ| < 2e-5 max|Q|); include/rela_amd.h rela_ffnet_set_precision."""
+        super().set_precision(mode)
 
 
 class _DevMem:
@@ -156,46 +170,19 @@ class ApexActorEngine:
         return bool(ins.value)
 
 
-class LSTMNetHandle:
+class LSTMNetHandle(_NetHandle):
     """One immutable device copy of AtariLSTMNet parameters in kernel layout (rela_lstmnet_*)."""
 
+    _PREFIX, _PARAMS = "lstmnet", capi.LSTMNetParams
     KEYS = ("net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.weight", "net.4.bias",
             "lstm.weight_ih_l0", "lstm.weight_hh_l0", "lstm.bias_ih_l0", "lstm.bias_hh_l0", "fc_v.weight", "fc_v.bias",
             "fc_a.weight", "fc_a.bias")
 
-    def __init__(self, num_action, device="cuda:0"):
-        self.device = torch.device(device)
-        self.num_action = num_action
-        h = C.c_void_p()
-        capi.check(capi.lib.rela_lstmnet_create(C.byref(h), num_action, self.device.index or 0), "rela_lstmnet_create")
-        self.h = h
-
-    def load_state_dict(self, sd, prefix=""):
-        p = capi.LSTMNetParams()
-        keep = []
-        for (field, _), key in zip(capi.LSTMNetParams._fields_, self.KEYS):
-            t = sd[prefix + key].detach().to(self.device, torch.float32).contiguous()
-            keep.append(t)
-            setattr(p, field, t.data_ptr())
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        capi.check(capi.lib.rela_lstmnet_load(self.h, C.byref(p), 1, stream), "rela_lstmnet_load")
-        self._keep = keep
-
     def set_precision(self, mode):
-        """"f32" (default) or "bf16x2": the conv trunk on split-bf16 MFMA for batches of 128 rows and more and, from
-        1,024 rows up, the input side of the LSTM gate GEMM (h x W_hh, the cell and the heads stay f32);
-        rela_lstmnet_set_precision."""
-        capi.check(capi.lib.rela_lstmnet_set_precision(self.h, {"f32": 0, "bf16x2": 1, "f32x3": 2}[mode]),
-                   "rela_lstmnet_set_precision")  # (f32x3: conv2 / conv3 of the trunk, from 512 rows; the rest exact f32)
-
-    def close(self):
-        if getattr(self, "h", None):
-            capi.lib.rela_lstmnet_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        if capi is not None and getattr(capi, "lib", None) is not None:
-            self.close()
+        """"f32" (default), "bf16x2": the conv trunk on split-bf16 MFMA for batches of 128 rows and more and, from
+        1,024 rows up, the input side of the LSTM gate GEMM (h x W_hh, the cell and the heads stay f32), or "f32x3":
+        conv2 / conv3 of the trunk, from 512 rows, the rest exact f32; rela_lstmnet_set_precision."""
+        super().set_precision(mode)
 
 
 class R2D2ActorEngine:

@@ -139,6 +139,70 @@ def test_a_net_packed_for_fewer_rows_never_reads_layouts_it_skipped(shim):
     assert shim.shim_packs_bf16_fc(0) and shim.shim_packs_bf16_fc(128)
 
 
+# ---- which layouts a load packs (ffnet_pack_set) ---------------------------------------------------------------------
+FFNET_LAYOUTS = ("B1", "b1", "B2", "b2", "B3", "b3", "Bh", "bh", "W1d", "B2f", "B3f", "B2e", "B3e", "Bf", "BfT", "bf", "Bhp",
+                 "Bff", "Bfe")
+# What rela_ffnet_load left out at the commit before the pack set became a function, read off the gates of its
+# ffnet_load_impl (max_rows > 0 and below: 512 -> B2e, B3e; 512 -> Bfe; 2048 -> Bf; 128 -> Bff), by declared rows ...
+PACK_SKIPS = {0: (), 64: ("B2e", "B3e", "Bfe", "Bf", "Bff"), 127: ("B2e", "B3e", "Bfe", "Bf", "Bff"),
+              128: ("B2e", "B3e", "Bfe", "Bf"), 511: ("B2e", "B3e", "Bfe", "Bf"), 512: ("Bf",), 2047: ("Bf",), 2048: ()}
+# ... and BfT, which a load from device pointers of a split-bf16 net of 128 declared rows and more left to the first
+# forward that reads it
+LAZY_BFT_ROWS = (128, 511, 512, 2047, 2048)
+
+
+def _layout_bits(shim):
+    rows = (C.c_int * 32)()
+    assert shim.shim_ffnet_layouts(rows) == len(FFNET_LAYOUTS)
+    assert sorted(rows[:len(FFNET_LAYOUTS)]) == list(range(len(FFNET_LAYOUTS)))
+    return {name: 1 << rows[i] for i, name in enumerate(FFNET_LAYOUTS)}
+
+
+def test_pack_set_is_what_the_load_gates_packed(shim):
+    shim.shim_ffnet_pack_set.restype = C.c_uint
+    bit = _layout_bits(shim)
+    for max_rows, skips in PACK_SKIPS.items():
+        for precision in (0, 1, 2):
+            for on_device in (0, 1):
+                lazy = bool(on_device and precision == 1 and max_rows in LAZY_BFT_ROWS)
+                want = set(FFNET_LAYOUTS) - set(skips) - ({"BfT"} if lazy else set())
+                got = shim.shim_ffnet_pack_set(max_rows, precision, on_device)
+                assert {n for n in FFNET_LAYOUTS if got & bit[n]} == want, (max_rows, precision, on_device)
+                assert got == sum(bit[n] for n in want)  # no bits beyond the net's rows
+                assert bool(shim.shim_ffnet_bft_on_demand(max_rows, precision, on_device)) == lazy
+
+
+def test_every_plan_reads_only_layouts_the_load_packed(shim):
+    """for every forward that runs (N within the declared rows) in every mode, whatever precision the net had when it
+    was loaded: the layouts the plan's kernels read are in the pack set -- or are BfT where the load left it to be
+    packed on demand"""
+    shim.shim_ffnet_pack_set.restype = shim.shim_ffnet_plan_reads.restype = C.c_uint
+    bit = _layout_bits(shim)
+    checked = 0
+    for N in NS:
+        for max_rows in MAX_ROWS + [2047, 2048]:
+            if not reachable(N, max_rows):
+                continue
+            for net_precision in (0, 1, 2):
+                for on_device in (0, 1):
+                    have = shim.shim_ffnet_pack_set(max_rows, net_precision, on_device)
+                    if shim.shim_ffnet_bft_on_demand(max_rows, net_precision, on_device):
+                        assert not have & bit["BfT"]
+                        have |= bit["BfT"]
+                    for mode in (-1, 0, 1, 2, 3):
+                        reads = shim.shim_ffnet_plan_reads(mode, net_precision, N, max_rows)
+                        assert reads and reads & ~have == 0, (N, max_rows, net_precision, on_device, mode,
+                                                              [n for n in FFNET_LAYOUTS if reads & ~have & bit[n]])
+                        checked += 1
+    assert checked >= 30 * len(NS)
+    # the learner's merged f32x3 forward: 2 B rows through a net that declared B, with the limit 2 B handed to the call
+    for B in (512, 600, 1024):
+        have = shim.shim_ffnet_pack_set(B, 2, 1)
+        assert shim.shim_ffnet_plan_reads(MODE_LEARNER_F32X3, 2, 2 * B, 2 * B) & ~have == 0
+        p = plan(shim, MODE_LEARNER_F32X3, 2, 2 * B, 2 * B)
+        assert p["trunk"] == TRUNK_S3 and p["fc"] == (FC_S3_SPLITK if 2 * B == 1024 else FC_S3)
+
+
 def test_learner_merged_forward_matches_the_learner_table(shim):
     """test_learner_gpu's statement of which batches the merged split-bf16 forward serves, and what it launches"""
     for B in NS:

@@ -532,7 +532,7 @@ def test_actor_net_loaded_from_flat_buffer_matches_publish():
 def test_f32_fc_layout_is_packed_on_demand_after_a_fast_mode_step():
     """In the split-bf16 mode no kernel reads the f32 split-K fc's weight layout (BfT) from 128 rows up, so a learner
     whose batch can reach 128 rows skips it in the re-pack after every step and the f32 path packs it when it is next
-    needed (csrc/ffnet.hip: rela_ffnet::bft_stale).  After a fast-mode step at B = 256, a 64-row batch -- whose forwards
+    needed (csrc/ffnet.hip: rela_ffnet::bft_src).  After a fast-mode step at B = 256, a 64-row batch -- whose forwards
     run the f32 kernels, BfT included -- must give exactly what a learner with the SAME parameters and a 64-row maximum
     (which packs BfT eagerly) gives, and so must the f32 mode at 256 rows."""
     import torch
