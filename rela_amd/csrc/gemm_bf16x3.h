@@ -74,23 +74,30 @@ __device__ __forceinline__ void split4x3(float4 v, uint2& hi, uint2& mid, uint2&
 // PARTS = 2: the split-bf16 fast arithmetic above.  PARTS = 3: every f32 operand as THREE bf16 parts (hi, mid, lo: an exact
 // split, see gemm_f32emu.h) and the six products with i + j <= 2, the five small ones in accumulators of their own:
 // f32 accuracy at 16 / 6 the f32 MFMA rate -- the learner's GEMMs of the f32x3 mode.
-template <int BM_, int BN_, int WM_, int WN_, bool AMC_, int PARTS_ = 2>
+// S (1, 2, 4) = the stage depth of gemm_lds.h: the chunks of 32 k per barrier.  A part's image of a stage is S chunk images
+// one behind the other, each with krow()'s row order and the strides below; the S MFMA steps of a stage run in k order,
+// each with the part products in the order of the S = 1 kernel, so every accumulator keeps its sequence of MFMAs.
+template <int BM_, int BN_, int WM_, int WN_, bool AMC_, int PARTS_ = 2, int S_ = 1>
 struct TileCfg {
-  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, PARTS = PARTS_;
+  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, PARTS = PARTS_, S = S_;
   static constexpr int BPARTS = PARTS;  // parts of the B operand (SinglePartB below: 1)
   static constexpr bool AMC = AMC_;
+  static_assert(S == 1 || S == 2 || S == 4, "stage depth");
   static_assert(PARTS == 2 || PARTS == 3, "two or three bf16 parts per operand");
   static_assert(WM * WN == 8, "8 wavefronts per block");
   static_assert(BM % 32 == 0 && BN % 32 == 0, "k-major row strides need multiples of 32 columns");
   static constexpr int TM = BM / 16 / WM, TN = BN / 16 / WN;  // 16x16 tiles per wave
   static_assert(TM >= 1 && TN >= 1, "tile too small for the wave grid");
   static constexpr int LDA = AMC ? BM * 2 + 32 : BK * 2 + 16;  // bytes per image row ([k][m] or [m][k])
-  static constexpr int A_HALF = AMC ? BK * LDA : BM * LDA;     // bytes of one of hi / lo
+  static constexpr int A_CHUNK = AMC ? BK * LDA : BM * LDA;    // bytes of one chunk's image of one part
+  static constexpr int A_HALF = S * A_CHUNK;                   // bytes of one of hi / lo
   static constexpr int LDB = BN * 2 + 32;
-  static constexpr int B_HALF = BK * LDB;
+  static constexpr int B_CHUNK = BK * LDB;
+  static constexpr int B_HALF = S * B_CHUNK;
   static constexpr int BUF = PARTS * (A_HALF + B_HALF);        // one stage: A parts, then B parts
   static constexpr int LDS_BYTES = 2 * BUF;
-  static constexpr int A_V4 = BM * BK / 4, B_V4 = BN * BK / 4;
+  static constexpr int A_V4C = BM * BK / 4, B_V4C = BN * BK / 4;  // float4s of one chunk
+  static constexpr int A_V4 = S * A_V4C, B_V4 = S * B_V4C;
   static constexpr int A_IT = (A_V4 + kT - 1) / kT, B_IT = (B_V4 + kT - 1) / kT;
 };
 // A three-part tile whose B operand is exact in ONE bf16 (conv1's weight gradient: B = the u8 frames, 8 significant bits):
@@ -143,6 +150,12 @@ __global__ __launch_bounds__(kT) void gemm_bf16x3(const P p, const GridMap gm) {
   const int nch = (p.K + BK - 1) / BK;
   const int c0 = bz * p.kslice;
   const int c1 = min(nch, c0 + p.kslice);
+  constexpr int S = T::S;
+  // what chunk_ring counts: chunks [c0, c1) at S = 1, else the slice's stages [0, ns) of S chunks (the last may be short)
+  const int r0 = S == 1 ? c0 : 0, r1 = S == 1 ? c1 : (c1 - c0 + S - 1) / S;
+  // first k of chunk `sub` of ring item `it`.  A short last stage repeats the slice's last chunk in its surplus chunks
+  // (as a ring refill past the slice's end does): no fetch leaves the slice, and those chunks are never multiplied.
+  auto kbase = [&](int it, int sub) { return S == 1 ? it * BK : min(c0 + it * S + sub, c1 - 1) * BK; };
 
   // Staging registers: D chunks in flight.  A chunk is 24 (or fewer) MFMAs per wave -- far less than one load's
   // latency -- and these GEMMs have only a handful of chunks per block (fc at batch 512: 16), so with ONE chunk
@@ -154,45 +167,50 @@ __global__ __launch_bounds__(kT) void gemm_bf16x3(const P p, const GridMap gm) {
   typename P::StageA ra[D][T::A_IT];
   typename P::StageB rb[D][T::B_IT];
   auto gload = [&](int ch, auto set) {
-    constexpr int S = decltype(set)::value;
-    const int k0 = ch * BK, m0 = bm0, n0 = bn0;
+    constexpr int R = decltype(set)::value;
+    const int m0 = bm0, n0 = bn0;
 #pragma unroll
     for (int j = 0; j < T::A_IT; ++j) {
       const int idx = min(tid + j * kT, T::A_V4 - 1);  // (clamped, not predicated: a surplus thread repeats a neighbour)
+      const int sub = idx / T::A_V4C, ic = idx % T::A_V4C;
+      const int k0 = kbase(ch, sub);
       if constexpr (T::AMC) {
-        const int kr = idx / (T::BM / 4), q = idx % (T::BM / 4);
-        ra[S][j] = p.fetchA(k0 + kr, m0 + 4 * q);
+        const int kr = ic / (T::BM / 4), q = ic % (T::BM / 4);
+        ra[R][j] = p.fetchA(k0 + kr, m0 + 4 * q);
       } else {
-        const int r = idx >> 3, q = idx & 7;
-        ra[S][j] = p.fetchA(m0 + r, k0 + 4 * q);
+        const int r = ic >> 3, q = ic & 7;
+        ra[R][j] = p.fetchA(m0 + r, k0 + 4 * q);
       }
     }
 #pragma unroll
     for (int j = 0; j < T::B_IT; ++j) {
       const int idx = min(tid + j * kT, T::B_V4 - 1);
-      const int kr = idx / (T::BN / 4), q = idx % (T::BN / 4);
-      rb[S][j] = p.fetchB(k0 + kr, n0 + 4 * q);
+      const int sub = idx / T::B_V4C, ic = idx % T::B_V4C;
+      const int kr = ic / (T::BN / 4), q = ic % (T::BN / 4);
+      rb[R][j] = p.fetchB(kbase(ch, sub) + kr, n0 + 4 * q);
     }
   };
   auto sstore = [&](int buf, int ch, auto set) {
-    constexpr int S = decltype(set)::value;
+    constexpr int R = decltype(set)::value;
     const int z = gemm::store_point();  // (keeps the fix-ups, and their waits, here)
-    const int k0 = ch * BK + z, m0 = bm0 + z, n0 = bn0 + z;
+    const int m0 = bm0 + z, n0 = bn0 + z;
     uint8_t* base = smem + buf * T::BUF;
 #pragma unroll
     for (int j = 0; j < T::A_IT; ++j) {
       const int idx = min(tid + j * kT, T::A_V4 - 1);
+      const int sub = idx / T::A_V4C, ic = idx % T::A_V4C;
+      const int k0 = kbase(ch, sub) + z;
       uint2 hi, mid, lo;
       float4 v;
       int off;
       if constexpr (T::AMC) {
-        const int kr = idx / (T::BM / 4), q = idx % (T::BM / 4);
-        v = p.fixA(ra[S][j], k0 + kr, m0 + 4 * q);
-        off = krow(kr) * T::LDA + q * 8;
+        const int kr = ic / (T::BM / 4), q = ic % (T::BM / 4);
+        v = p.fixA(ra[R][j], k0 + kr, m0 + 4 * q);
+        off = sub * T::A_CHUNK + krow(kr) * T::LDA + q * 8;
       } else {
-        const int r = idx >> 3, q = idx & 7;
-        v = p.fixA(ra[S][j], m0 + r, k0 + 4 * q);
-        off = r * T::LDA + q * 8;
+        const int r = ic >> 3, q = ic & 7;
+        v = p.fixA(ra[R][j], m0 + r, k0 + 4 * q);
+        off = sub * T::A_CHUNK + r * T::LDA + q * 8;
       }
       if constexpr (T::PARTS == 3) split4x3(v, hi, mid, lo);
       else split4(v, hi, lo);
@@ -204,12 +222,13 @@ __global__ __launch_bounds__(kT) void gemm_bf16x3(const P p, const GridMap gm) {
 #pragma unroll
     for (int j = 0; j < T::B_IT; ++j) {
       const int idx = min(tid + j * kT, T::B_V4 - 1);
-      const int kr = idx / (T::BN / 4), q = idx % (T::BN / 4);
+      const int sub = idx / T::B_V4C, ic = idx % T::B_V4C;
+      const int kr = ic / (T::BN / 4), q = ic % (T::BN / 4);
       uint2 hi, mid, lo;
-      const float4 v = p.fixB(rb[S][j], k0 + kr, n0 + 4 * q);
+      const float4 v = p.fixB(rb[R][j], kbase(ch, sub) + z + kr, n0 + 4 * q);
       if constexpr (T::PARTS == 3) split4x3(v, hi, mid, lo);
       else split4(v, hi, lo);
-      const int off = krow(kr) * T::LDB + q * 8;
+      const int off = sub * T::B_CHUNK + krow(kr) * T::LDB + q * 8;
       *reinterpret_cast<uint2*>(bb + off) = hi;
       if constexpr (T::BPARTS == 3) *reinterpret_cast<uint2*>(bb + T::B_HALF + off) = mid;
       if constexpr (T::BPARTS > 1) *reinterpret_cast<uint2*>(bb + (T::BPARTS - 1) * T::B_HALF + off) = lo;
@@ -241,49 +260,56 @@ __global__ __launch_bounds__(kT) void gemm_bf16x3(const P p, const GridMap gm) {
       if constexpr (T::PARTS == 3) accs[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
 
-  // one chunk: LDS[buf] holds it
-  auto mma = [&](int buf, int) {
-    const uint8_t* base = smem + buf * T::BUF;
-    const uint8_t* bb = base + T::PARTS * T::A_HALF;
-    bf16x8 bp[T::TN][T::BPARTS];  // [..][0] = hi ... [..][BPARTS - 1] = lo
+  // one stage: LDS[buf] holds its S chunks
+  auto mma = [&](int buf, int ch, auto full) {
+    const int left = c1 - c0 - ch * S;  // (S > 1, the tail) chunks of the slice from this stage on
 #pragma unroll
-    for (int u = 0; u < T::TN; ++u) {
-      const int col0 = (wn * T::TN + u) * 16;
+    for (int sub = 0; sub < S; ++sub) {
+      // (block-uniform) a short last stage: the chunks past the slice's end belong to nobody and are not multiplied
+      if (S == 1 || decltype(full)::value || sub < left) {
+        const uint8_t* base = smem + buf * T::BUF + sub * T::A_CHUNK;
+        const uint8_t* bb = smem + buf * T::BUF + T::PARTS * T::A_HALF + sub * T::B_CHUNK;
+        bf16x8 bp[T::TN][T::BPARTS];  // [..][0] = hi ... [..][BPARTS - 1] = lo
 #pragma unroll
-      for (int q = 0; q < T::BPARTS; ++q) bp[u][q] = frag_tr(bb + q * T::B_HALF, T::LDB, col0);
-    }
+        for (int u = 0; u < T::TN; ++u) {
+          const int col0 = (wn * T::TN + u) * 16;
 #pragma unroll
-    for (int t = 0; t < T::TM; ++t) {
-      const int row0 = (wm * T::TM + t) * 16;
-      bf16x8 ap[T::PARTS];
+          for (int q = 0; q < T::BPARTS; ++q) bp[u][q] = frag_tr(bb + q * T::B_HALF, T::LDB, col0);
+        }
 #pragma unroll
-      for (int q = 0; q < T::PARTS; ++q) {
-        if constexpr (T::AMC) ap[q] = frag_tr(base + q * T::A_HALF, T::LDA, row0);
-        else ap[q] = frag_row(base + q * T::A_HALF, row0 + li);
-      }
+        for (int t = 0; t < T::TM; ++t) {
+          const int row0 = (wm * T::TM + t) * 16;
+          bf16x8 ap[T::PARTS];
 #pragma unroll
-      for (int u = 0; u < T::TN; ++u) {
-        if constexpr (T::PARTS == 2) {
-          acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[1], bp[u][0], acc[t][u], 0, 0, 0);
-          acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][1], acc[t][u], 0, 0, 0);
-          acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][0], acc[t][u], 0, 0, 0);
-        } else if constexpr (T::BPARTS == 1) {  // b = its hi part: the three products of the six below that are not zero
-          accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[2], bp[u][0], accs[t][u], 0, 0, 0);
-          accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[1], bp[u][0], accs[t][u], 0, 0, 0);
-          acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][0], acc[t][u], 0, 0, 0);
-        } else {  // (a part, b part) with i + j <= 2, smallest first; hi * hi alone in the main accumulator
-          accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[2], bp[u][0], accs[t][u], 0, 0, 0);
-          accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][2], accs[t][u], 0, 0, 0);
-          accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[1], bp[u][1], accs[t][u], 0, 0, 0);
-          accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[1], bp[u][0], accs[t][u], 0, 0, 0);
-          accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][1], accs[t][u], 0, 0, 0);
-          acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][0], acc[t][u], 0, 0, 0);
+          for (int q = 0; q < T::PARTS; ++q) {
+            if constexpr (T::AMC) ap[q] = frag_tr(base + q * T::A_HALF, T::LDA, row0);
+            else ap[q] = frag_row(base + q * T::A_HALF, row0 + li);
+          }
+#pragma unroll
+          for (int u = 0; u < T::TN; ++u) {
+            if constexpr (T::PARTS == 2) {
+              acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[1], bp[u][0], acc[t][u], 0, 0, 0);
+              acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][1], acc[t][u], 0, 0, 0);
+              acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][0], acc[t][u], 0, 0, 0);
+            } else if constexpr (T::BPARTS == 1) {  // b = its hi part: the three products of the six below that are not zero
+              accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[2], bp[u][0], accs[t][u], 0, 0, 0);
+              accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[1], bp[u][0], accs[t][u], 0, 0, 0);
+              acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][0], acc[t][u], 0, 0, 0);
+            } else {  // (a part, b part) with i + j <= 2, smallest first; hi * hi alone in the main accumulator
+              accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[2], bp[u][0], accs[t][u], 0, 0, 0);
+              accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][2], accs[t][u], 0, 0, 0);
+              accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[1], bp[u][1], accs[t][u], 0, 0, 0);
+              accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[1], bp[u][0], accs[t][u], 0, 0, 0);
+              accs[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][1], accs[t][u], 0, 0, 0);
+              acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[0], bp[u][0], acc[t][u], 0, 0, 0);
+            }
+          }
         }
       }
     }
   };
   // (a block whose slice is empty fetches nothing and stores its zeros: the split reductions read every split)
-  if (c0 < c1) gemm::chunk_ring<D>(c0, c1, gload, sstore, mma);
+  if (c0 < c1) gemm::chunk_ring<D>(r0, r1, gload, sstore, mma);
 
 #pragma unroll
   for (int t = 0; t < T::TM; ++t)
@@ -303,6 +329,7 @@ __global__ __launch_bounds__(kT) void gemm_bf16x3(const P p, const GridMap gm) {
 // same contract as gemm::launch_gemm (the Problem's kslice is counted in chunks of BK = 32 here as well)
 template <class T, class P>
 int launch_gemm(P p, int splits, hipStream_t s, const char* name) {
+  static_assert(T::LDS_BYTES <= 160 * 1024, "two stages must fit the CU's LDS");
   static const hipError_t attr_set = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16x3<T, P>),
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES);
   RELA_HIP(attr_set);

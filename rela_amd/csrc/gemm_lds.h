@@ -40,21 +40,33 @@ __device__ __forceinline__ float4 keep4(bool in_range, float4 v) {
 // across the join, wait s_waitcnt vmcnt(0) at every use: a ring of chunks "in flight" then holds nothing but the loads of
 // the current step.  With unconditional fetches the waits are counted and D - 1 chunks stay outstanding.
 // ProbBase supplies the defaults: float4 stages and identity fix-ups.
-template <int BM_, int BN_, int WM_, int WN_, bool AMC_>
+//
+// S (1, 2, 4) = the stage depth: the chunks of 32 k that are fetched, stored and multiplied per barrier.  A stage's LDS
+// image is S chunk images one behind the other, each with the strides below, and its S chunks are multiplied one after
+// the other in k order: every accumulator sees the MFMAs of the S = 1 kernel in the same order, so the sums keep their
+// bits; splits, kslice and kFoldChunks stay counted in chunks.  Per barrier a block then pays the fixed costs of a step --
+// the wait for the ring, the LDS round trip, the barrier -- once for S x 32 k.
+template <int BM_, int BN_, int WM_, int WN_, bool AMC_, int S_ = 1>
 struct TileCfg {
-  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_;
+  static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, S = S_;
   static constexpr bool AMC = AMC_;
+  static_assert(S == 1 || S == 2 || S == 4, "stage depth");
   static_assert(WM * WN == 8, "8 wavefronts per block");
   static constexpr int TM = BM / 16 / WM, TN = BN / 16 / WN;  // 16x16 tiles per wave
   static_assert(TM >= 1 && TN >= 1, "tile too small for the wave grid");
   // leading dimensions = 16 (mod 32) floats, or k+2: a fragment read (16 rows x 4 k) touches
   // every bank exactly twice, the minimum for 64 lanes
   static constexpr int LDA = AMC ? BM + 16 : BK + 2;
-  static constexpr int A_FLOATS = AMC ? BK * LDA : BM * LDA;
+  static constexpr int A_CHUNK = AMC ? BK * LDA : BM * LDA;  // floats of one chunk's image
+  static constexpr int A_FLOATS = S * A_CHUNK;
   static constexpr int LDB = BN + 16;
-  static constexpr int B_FLOATS = BK * LDB;
-  static constexpr int A_V4 = BM * BK / 4, B_V4 = BN * BK / 4;
+  static constexpr int B_CHUNK = BK * LDB;
+  static constexpr int B_FLOATS = S * B_CHUNK;
+  static constexpr int A_V4C = BM * BK / 4, B_V4C = BN * BK / 4;  // float4s of one chunk
+  static constexpr int A_V4 = S * A_V4C, B_V4 = S * B_V4C;
   static constexpr int A_IT = (A_V4 + kLT - 1) / kLT, B_IT = (B_V4 + kLT - 1) / kLT;
+  static constexpr int LDS_BYTES = 2 * (A_FLOATS + B_FLOATS) * 4;
+  static constexpr bool DYN_LDS = LDS_BYTES > 64 * 1024;  // past the static limit: dynamic LDS, sized at the launch
 };
 
 // Optional (compile time): a Problem with a member `static constexpr int kFoldChunks = F` gets its sum in GROUPS of F
@@ -78,8 +90,11 @@ struct fold_chunks<P, std::void_t<decltype(P::kFoldChunks)>> {
 // chunk (never stored), and the last 1 .. D chunks run in a peeled tail that fetches nothing.
 //   gload(chunk, set)   issue the chunk's fetches into register set `set` (std::integral_constant)
 //   sstore(buf, chunk, set)   fix up and write set `set`, holding `chunk`, into LDS buffer buf
-//   mma(buf, chunk)     multiply the chunk in LDS buffer buf
+//   mma(buf, chunk, full)   multiply the chunk in LDS buffer buf; `full` (std::bool_constant) is true in the loop, whose
+//                       chunks all lie before the slice's last one
 // Needs c0 < c1; every condition is block-uniform.
+// With a stage depth S > 1 (TileCfg) what the ring counts are STAGES of S chunks, numbered from 0 within the block's
+// slice; only the last stage of a slice can be short, and it is always multiplied in the tail (full = false).
 //
 // store_point(): an integer zero the compiler cannot see through (an empty asm statement: one scalar move), added to the
 // indices a fix-up gets.  A fix-up is a select on a fetched value and nothing else ties it to the store: hipcc evaluated
@@ -107,7 +122,7 @@ __device__ __forceinline__ void chunk_ring(int c0, int c1, Load&& gload, Store&&
           const int cur = base + j.value, buf = (cur - c0) & 1;
           gload(min(cur + D, c1 - 1), j);
           __builtin_amdgcn_sched_barrier(0);  // (the refill is issued before anything waits)
-          mma(buf, cur);
+          mma(buf, cur, std::true_type{});
           __builtin_amdgcn_sched_barrier(0);
           sstore(buf ^ 1, cur + 1, std::integral_constant<int, (j.value + 1) % D>{});
           __syncthreads();
@@ -121,7 +136,7 @@ __device__ __forceinline__ void chunk_ring(int c0, int c1, Load&& gload, Store&&
       [&](auto j) {
         const int cur = base + j.value, buf = (cur - c0) & 1;
         if (cur < c1) {
-          mma(buf, cur);
+          mma(buf, cur, std::false_type{});
           if (cur + 1 < c1) sstore(buf ^ 1, cur + 1, std::integral_constant<int, (j.value + 1) % D>{});
           __syncthreads();
         }
@@ -133,8 +148,20 @@ constexpr int kRing = 2;  // register sets of gemm_lds: one chunk outstanding be
 
 template <class T, class P>
 __global__ __launch_bounds__(kLT) void gemm_lds(const P p) {
-  __shared__ __attribute__((aligned(16))) float sA[2][T::A_FLOATS];
-  __shared__ __attribute__((aligned(16))) float sB[2][T::B_FLOATS];
+  constexpr int S = T::S;
+  // static LDS ends at 64 KB: a deeper stage's images come from the launch's dynamic LDS (the static arrays then hold
+  // one vector each and are not used)
+  __shared__ __attribute__((aligned(16))) float sA_[2][T::DYN_LDS ? 4 : T::A_FLOATS];
+  __shared__ __attribute__((aligned(16))) float sB_[2][T::DYN_LDS ? 4 : T::B_FLOATS];
+  extern __shared__ __attribute__((aligned(16))) float gemm_lds_dyn[];
+  auto pA = [&](int buf, int off) -> float* {
+    if constexpr (T::DYN_LDS) return gemm_lds_dyn + buf * T::A_FLOATS + off;
+    else return &sA_[buf][off];
+  };
+  auto pB = [&](int buf, int off) -> float* {
+    if constexpr (T::DYN_LDS) return gemm_lds_dyn + (2 * T::A_FLOATS + buf * T::B_FLOATS) + off;
+    else return &sB_[buf][off];
+  };
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
   const int li = lane & 15, kk = lane >> 4;
@@ -143,45 +170,55 @@ __global__ __launch_bounds__(kLT) void gemm_lds(const P p) {
   const int nch = (p.K + BK - 1) / BK;
   const int c0 = blockIdx.z * p.kslice;
   const int c1 = min(nch, c0 + p.kslice);
+  // what chunk_ring counts: chunks [c0, c1) at S = 1, else the slice's stages [0, ns) of S chunks (the last may be short)
+  const int r0 = S == 1 ? c0 : 0, r1 = S == 1 ? c1 : (c1 - c0 + S - 1) / S;
+  // first k of chunk `sub` of ring item `it`.  A short last stage repeats the slice's last chunk in its surplus chunks
+  // (as a ring refill past the slice's end does): no fetch leaves the slice, and those chunks are never multiplied.
+  auto kbase = [&](int it, int sub) { return S == 1 ? it * BK : min(c0 + it * S + sub, c1 - 1) * BK; };
 
   // (idx clamped, not predicated: a surplus thread repeats its neighbour's fetch and LDS write)
   typename P::StageA ra[kRing][T::A_IT];
   typename P::StageB rb[kRing][T::B_IT];
   auto gload = [&](int ch, auto set) {
-    constexpr int S = decltype(set)::value;
-    const int k0 = ch * BK, m0 = bm0, n0 = bn0;
+    constexpr int R = decltype(set)::value;
+    const int m0 = bm0, n0 = bn0;
 #pragma unroll
     for (int j = 0; j < T::A_IT; ++j) {
       const int idx = min(tid + j * kLT, T::A_V4 - 1);
+      const int sub = S == 1 ? 0 : idx / T::A_V4C, ic = S == 1 ? idx : idx % T::A_V4C;
+      const int k0 = kbase(ch, sub);
       if constexpr (T::AMC) {
-        const int kr = idx / (T::BM / 4), q = idx % (T::BM / 4);
-        ra[S][j] = p.fetchA(k0 + kr, m0 + 4 * q);
+        const int kr = ic / (T::BM / 4), q = ic % (T::BM / 4);
+        ra[R][j] = p.fetchA(k0 + kr, m0 + 4 * q);
       } else {
-        const int r = idx >> 3, q = idx & 7;
-        ra[S][j] = p.fetchA(m0 + r, k0 + 4 * q);
+        const int r = ic >> 3, q = ic & 7;
+        ra[R][j] = p.fetchA(m0 + r, k0 + 4 * q);
       }
     }
 #pragma unroll
     for (int j = 0; j < T::B_IT; ++j) {
       const int idx = min(tid + j * kLT, T::B_V4 - 1);
-      const int kr = idx / (T::BN / 4), q = idx % (T::BN / 4);
-      rb[S][j] = p.fetchB(k0 + kr, n0 + 4 * q);
+      const int sub = S == 1 ? 0 : idx / T::B_V4C, ic = S == 1 ? idx : idx % T::B_V4C;
+      const int kr = ic / (T::BN / 4), q = ic % (T::BN / 4);
+      rb[R][j] = p.fetchB(kbase(ch, sub) + kr, n0 + 4 * q);
     }
   };
   auto sstore = [&](int buf, int ch, auto set) {
-    constexpr int S = decltype(set)::value;
+    constexpr int R = decltype(set)::value;
     const int z = store_point();
-    const int k0 = ch * BK + z, m0 = bm0 + z, n0 = bn0 + z;
+    const int k00 = kbase(ch, 0) + z, m0 = bm0 + z, n0 = bn0 + z;
 #pragma unroll
     for (int j = 0; j < T::A_IT; ++j) {
       const int idx = min(tid + j * kLT, T::A_V4 - 1);
+      const int sub = S == 1 ? 0 : idx / T::A_V4C, ic = S == 1 ? idx : idx % T::A_V4C;
+      const int k0 = S == 1 ? k00 : kbase(ch, sub) + z;
       if constexpr (T::AMC) {
-        const int kr = idx / (T::BM / 4), q = idx % (T::BM / 4);
-        *reinterpret_cast<float4*>(&sA[buf][kr * T::LDA + 4 * q]) = p.fixA(ra[S][j], k0 + kr, m0 + 4 * q);
+        const int kr = ic / (T::BM / 4), q = ic % (T::BM / 4);
+        *reinterpret_cast<float4*>(pA(buf, sub * T::A_CHUNK + kr * T::LDA + 4 * q)) = p.fixA(ra[R][j], k0 + kr, m0 + 4 * q);
       } else {
-        const int r = idx >> 3, q = idx & 7;
-        const float4 v = p.fixA(ra[S][j], m0 + r, k0 + 4 * q);
-        float* d = &sA[buf][r * T::LDA + 4 * q];
+        const int r = ic >> 3, q = ic & 7;
+        const float4 v = p.fixA(ra[R][j], m0 + r, k0 + 4 * q);
+        float* d = pA(buf, sub * T::A_CHUNK + r * T::LDA + 4 * q);
         *reinterpret_cast<float2*>(d) = make_float2(v.x, v.y);
         *reinterpret_cast<float2*>(d + 2) = make_float2(v.z, v.w);
       }
@@ -189,8 +226,10 @@ __global__ __launch_bounds__(kLT) void gemm_lds(const P p) {
 #pragma unroll
     for (int j = 0; j < T::B_IT; ++j) {
       const int idx = min(tid + j * kLT, T::B_V4 - 1);
-      const int kr = idx / (T::BN / 4), q = idx % (T::BN / 4);
-      *reinterpret_cast<float4*>(&sB[buf][kr * T::LDB + 4 * q]) = p.fixB(rb[S][j], k0 + kr, n0 + 4 * q);
+      const int sub = S == 1 ? 0 : idx / T::B_V4C, ic = S == 1 ? idx : idx % T::B_V4C;
+      const int kr = ic / (T::BN / 4), q = ic % (T::BN / 4);
+      *reinterpret_cast<float4*>(pB(buf, sub * T::B_CHUNK + kr * T::LDB + 4 * q)) =
+          p.fixB(rb[R][j], (S == 1 ? k00 : kbase(ch, sub) + z) + kr, n0 + 4 * q);
     }
   };
 
@@ -208,36 +247,44 @@ __global__ __launch_bounds__(kLT) void gemm_lds(const P p) {
       for (int u = 0; u < T::TN; ++u) tot[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
-  auto mma = [&](int buf, int ch) {
+  auto mma = [&](int buf, int ch, auto full) {
+    const int left = c1 - c0 - ch * S;  // (S > 1, the tail) chunks of the slice from this stage on
 #pragma unroll
-    for (int ks = 0; ks < BK / 4; ++ks) {
-      float a[T::TM], b[T::TN];
+    for (int sub = 0; sub < S; ++sub) {
+      // (block-uniform) a short last stage: the chunks past the slice's end belong to nobody and are not multiplied
+      if (S == 1 || decltype(full)::value || sub < left) {
 #pragma unroll
-      for (int t = 0; t < T::TM; ++t) {
-        const int row = (wm * T::TM + t) * 16 + li;
-        a[t] = T::AMC ? sA[buf][(4 * ks + kk) * T::LDA + row] : sA[buf][row * T::LDA + 4 * ks + kk];
-      }
+        for (int ks = 0; ks < BK / 4; ++ks) {
+          float a[T::TM], b[T::TN];
 #pragma unroll
-      for (int u = 0; u < T::TN; ++u) b[u] = sB[buf][(4 * ks + kk) * T::LDB + (wn * T::TN + u) * 16 + li];
-#pragma unroll
-      for (int t = 0; t < T::TM; ++t)
-#pragma unroll
-        for (int u = 0; u < T::TN; ++u) acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], b[u], acc[t][u], 0, 0, 0);
-    }
-    if constexpr (FOLD > 0) {
-      if ((ch - c0 + 1) % FOLD == 0) {  // (block-uniform) a group is complete
-#pragma unroll
-        for (int t = 0; t < T::TM; ++t)
-#pragma unroll
-          for (int u = 0; u < T::TN; ++u) {
-            tot[t][u] += acc[t][u];
-            acc[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+          for (int t = 0; t < T::TM; ++t) {
+            const int row = (wm * T::TM + t) * 16 + li;
+            a[t] = *pA(buf, sub * T::A_CHUNK + (T::AMC ? (4 * ks + kk) * T::LDA + row : row * T::LDA + 4 * ks + kk));
           }
+#pragma unroll
+          for (int u = 0; u < T::TN; ++u) b[u] = *pB(buf, sub * T::B_CHUNK + (4 * ks + kk) * T::LDB + (wn * T::TN + u) * 16 + li);
+#pragma unroll
+          for (int t = 0; t < T::TM; ++t)
+#pragma unroll
+            for (int u = 0; u < T::TN; ++u) acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], b[u], acc[t][u], 0, 0, 0);
+        }
+        if constexpr (FOLD > 0) {
+          const int done = S == 1 ? ch - c0 + 1 : ch * S + sub + 1;  // chunks of the slice multiplied so far
+          if (done % FOLD == 0) {  // (block-uniform) a group is complete
+#pragma unroll
+            for (int t = 0; t < T::TM; ++t)
+#pragma unroll
+              for (int u = 0; u < T::TN; ++u) {
+                tot[t][u] += acc[t][u];
+                acc[t][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+              }
+          }
+        }
       }
     }
   };
   // (a block whose slice is empty fetches nothing and stores its zeros: the split reductions read every split)
-  if (c0 < c1) chunk_ring<kRing>(c0, c1, gload, sstore, mma);
+  if (c0 < c1) chunk_ring<kRing>(r0, r1, gload, sstore, mma);
 
 #pragma unroll
   for (int t = 0; t < T::TM; ++t)
@@ -268,7 +315,14 @@ void launch_gemm(P p, int splits, hipStream_t s, const char* name) {
   p.kslice = ceil_div(nch, splits);
   ProfScope prof(name, s);
   note_launch("gemm_lds (f32)");
-  hipLaunchKernelGGL((gemm_lds<T, P>), dim3(ceil_div(p.N, T::BN), ceil_div(p.M, T::BM), splits), dim3(kLT), 0, s, p);
+  static_assert(T::LDS_BYTES <= 160 * 1024, "two stages must fit the CU's LDS");
+  if constexpr (T::DYN_LDS) {
+    static const hipError_t attr_set = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_lds<T, P>),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, T::LDS_BYTES);
+    (void)attr_set;
+  }
+  hipLaunchKernelGGL((gemm_lds<T, P>), dim3(ceil_div(p.N, T::BN), ceil_div(p.M, T::BM), splits), dim3(kLT),
+                     T::DYN_LDS ? T::LDS_BYTES : 0, s, p);
 }
 
 }  // namespace gemm

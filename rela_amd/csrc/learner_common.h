@@ -30,7 +30,11 @@ using namespace gemm;
 using TileDgrad = TileCfg<128, 64, 4, 2, false>;  // M = batch rows, A k-contiguous
 using TileWfc = TileCfg<128, 64, 4, 2, true>;     // fc weight gradient (M = 512 units)
 using TileW64 = TileCfg<64, 64, 2, 4, true>;      // conv2 / conv3 weight gradients (M = 64 channels)
-using TileW32 = TileCfg<32, 64, 2, 4, true>;      // conv1 / head weight gradients (M = 32)
+using TileW32 = TileCfg<32, 64, 2, 4, true>;      // head weight gradients (M = 32)
+// conv1's weight gradient: stages of FOUR chunks per barrier (gemm_lds.h, S; 128 KB of dynamic LDS, one block per CU as
+// before: 256 blocks).  Measured alone at 512 / 5,312 frames: S = 1 60 / 627 us, S = 2 53 / 590, S = 4 54 / 553.
+// conv2 / conv3 (TileW64) stay at S = 1: at S = 2 they measured 4 us (512 frames) and 3 - 11 us (5,312) BEHIND.
+using TileW1 = TileCfg<32, 64, 2, 4, true, 4>;
 // conv3's / conv2's data gradients (N = 64 / 32 input channels): 64 rows per block measured ahead of 128 (and of 256 for
 // conv2) at 512 frames -- K is only 576 / 256, so more and smaller blocks hide more of each block's fixed costs
 using TileDgrad3 = TileCfg<64, 64, 2, 4, false>;
@@ -49,7 +53,10 @@ using Tile6Wfc = gemm3::TileCfg<128, 64, 4, 2, true, 3>;
 using Tile6W64 = gemm3::TileCfg<64, 64, 2, 4, true, 3>;
 using Tile6W32 = gemm3::TileCfg<32, 64, 2, 4, true, 3>;
 // conv1's weight gradient: the B operand is the u8 frame, exact in ONE bf16 part -- its mid and lo parts would be zeros
-using Tile6W32U8 = gemm3::SinglePartB<Tile6W32>;
+// ... at a stage of TWO chunks: 45 -> 37 us alone at 512 frames.  S = 4 measured 36 us but takes 112 KB of LDS and 138
+// registers: a second block no longer fits the CU (tests/test_trunk_backward_resources_cpu.py); S = 2 keeps 56 KB, 72 registers.
+// The 64 x 64 tiles stay at S = 1: at S = 2 one block fits a CU instead of two and conv2 / conv3 measured 8 / 7 us behind.
+using Tile6W32U8 = gemm3::SinglePartB<gemm3::TileCfg<32, 64, 2, 4, true, 3, 2>>;
 
 
 // d_h[b][u] = relu'(h) * sum_k d_ha[b][k] * Wh[k][u]      Wh rows: 0..A-1 = fc_a.weight, 31 = fc_v.weight
@@ -764,7 +771,7 @@ inline void trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending
     // 69-75 us at 512 frames, but another split changes the association of g_c1w and with it the bits of a step)
     const int split1 = kSplitW1;
     if (t.emu) (void)gemm3::launch_gemm<Tile6W32U8>(p, split1, s, "learner_wgrad_conv1");
-    else launch_gemm<TileW32>(p, split1, s, "learner_wgrad_conv1");
+    else launch_gemm<TileW1>(p, split1, s, "learner_wgrad_conv1");
     hipLaunchKernelGGL(reduce_splits, dim3(ceil_div(32 * 256, 256)), dim3(256), 0, s, (const float*)t.part, split1, 32,
                        256, kRedConv1, t.g_c1w);
   }
