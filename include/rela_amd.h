@@ -717,7 +717,15 @@ int rela_r2d2_learner_check(rela_r2d2_learner* l, void* stream);
  * and the conv data gradients (hi + lo bf16 operands, f32 accumulation); the online net's conv trunk, whose
  * activations and ReLU masks the backward kernels read, stays f32.  Loss, priorities within 2e-5, gradients within
  * 2e-4 of their largest entry of mode 0.  0 (default): everything f32.  2 ("f32x3"): conv2 / conv3 of BOTH nets' trunk
- * forwards on the three-part bf16 kernels (f32 accuracy, mode 0's tolerances); everything else as in mode 0. */
+ * forwards on the three-part bf16 kernels (f32 accuracy, mode 0's tolerances); everything else as in mode 0.
+ * 3 ("f32x3_bwd"): the forwards of mode 2, kernel for kernel -- loss, per-sequence loss and priorities are mode 2's bits --
+ * and the backward GEMMs over all training rows on the bf16 MFMA with every operand in three bf16 parts (gemm_bf16x3.h,
+ * PARTS = 3: f32 accuracy, mode 0's tolerances): dW_hh, dW_ih, the input-side data gradient d_a3 (ReLU mask fused) and the
+ * conv1 / conv2 / conv3 weight gradients (with twice mode 0's split-K slices), six GEMM launches, at every batch size.
+ * The heads' two GEMMs (K = 32 / M = 32) were measured slower in three parts and stay on the f32 MFMA, as do the
+ * recurrent chains and per-step recurrent GEMMs, the cell kernels, the conv data gradients, column sums, loss, clip and
+ * optimiser.  Every split-K sum is reduced in a fixed order: a step gives the same bits every time.
+ * Other values: RELA_EINVAL. */
 int rela_r2d2_learner_set_precision(rela_r2d2_learner* l, int mode);
 /* as rela_apex_learner_set_value_rescale, for the per-timestep target of td_err (r2d2.py:172-176):
  * h(reward[i] + bootstrap[i] * gamma ** n * h_inv(target_qa[i + n])).  Padding, the eta-mixed priority and the gradient

@@ -611,6 +611,7 @@ static_assert(kTrunkPartFloats >= (size_t)kSplitW3 * 64 * 576 && kTrunkPartFloat
                   kTrunkPartFloats >= (size_t)w2fast::kMaxBlocks * 64 * 512,
               "part size");
 static_assert(kSplitW3 * 64 * 576 >= kSplitW2 * 64 * 512 && kSplitW3 * 64 * 576 >= kSplitW1 * 32 * 256, "part size");
+constexpr int kMaxSplitMul = 8;  // of TrunkBwd::emu_split_mul: what the assertions above leave room for
 
 constexpr int kFastWgradMinFrames = 2048;
 // the most frames of one trunk_backward call: the data gradients put frames * 100 / 64 (conv2) and frames * 81 / 64
@@ -632,6 +633,10 @@ struct TrunkBwd {
   // the f32x3 mode: the weight-gradient GEMMs below (contraction over batch x positions) on the bf16 MFMA with three-part
   // operands, f32 accuracy (r4 at 512 frames, us f32 -> three-part: conv3 49 -> 35, conv2 63 -> 52, conv1 110 -> 102)
   bool emu = false;
+  // (with emu) multipliers on the split counts of conv1's / conv2's / conv3's three-part weight gradients: conv1 at every
+  // frame count, conv2 / conv3 above 1,024 frames (below, their splits are tripled already).  Another split count is another
+  // association of the sum, so both learners' existing modes keep 1; the R2D2 learner's mode 3 sets its own.
+  int emu_split_mul[3] = {1, 1, 1};
   // frames from which `fast` runs conv2's / conv3's weight gradients on wgrad_conv{2,3}_bf16 (both learners keep the
   // default; rela_debug_trunk_backward lowers it so that small ragged frame counts reach those kernels)
   int fast_wgrad_min_frames = kFastWgradMinFrames;
@@ -702,7 +707,7 @@ inline void trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending
     // (a few hundred frames: 3 x the splits = 3-4 blocks per CU instead of one; a block alone on its CU waits out
     // every chunk's load latency with two waves per SIMD)
     static const int mul = 3  /* (<= 8: what kTrunkPartFloats holds; flat between 2 and 4 in the r3 sweep) */;
-    const int split3 = Bn <= 1024 ? kSplitW3 * mul : kSplitW3;
+    const int split3 = Bn <= 1024 ? kSplitW3 * mul : kSplitW3 * (t.emu ? t.emu_split_mul[2] : 1);
     if (t.fast && gemm_bf16x3_on()) (void)gemm3::launch_gemm<Tile3W64>(p, split3, sw, "learner_wgrad_conv3");
     else if (t.emu) (void)gemm3::launch_gemm<Tile6W64>(p, split3, sw, "learner_wgrad_conv3");
     else launch_gemm<TileW64>(p, split3, sw, "learner_wgrad_conv3");
@@ -733,7 +738,7 @@ inline void trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending
     p.M = 64, p.N = 512, p.K = Bn * 81;
     p.d_out = t.d_a2, p.in = t.a1, p.part = partw;
     static const int mul = 3  /* (<= 8: what kTrunkPartFloats holds; flat between 2 and 4 in the r3 sweep) */;
-    const int split2 = Bn <= 1024 ? kSplitW2 * mul : kSplitW2;
+    const int split2 = Bn <= 1024 ? kSplitW2 * mul : kSplitW2 * (t.emu ? t.emu_split_mul[1] : 1);
     if (t.fast && gemm_bf16x3_on()) (void)gemm3::launch_gemm<Tile3W64>(p, split2, sw, "learner_wgrad_conv2");
     else if (t.emu) (void)gemm3::launch_gemm<Tile6W64>(p, split2, sw, "learner_wgrad_conv2");
     else launch_gemm<TileW64>(p, split2, sw, "learner_wgrad_conv2");
@@ -769,7 +774,7 @@ inline void trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending
     p.d_out = t.d_a1, p.obs = t.obs, p.part = t.part;
     // (kSplitW1 splits at every frame count: 3-4 x the splits at <= 1,024 frames, as conv3 / conv2 above, measured 105 ->
     // 69-75 us at 512 frames, but another split changes the association of g_c1w and with it the bits of a step)
-    const int split1 = kSplitW1;
+    const int split1 = kSplitW1 * (t.emu ? t.emu_split_mul[0] : 1);
     if (t.emu) (void)gemm3::launch_gemm<Tile6W32U8>(p, split1, s, "learner_wgrad_conv1");
     else launch_gemm<TileW1>(p, split1, s, "learner_wgrad_conv1");
     hipLaunchKernelGGL(reduce_splits, dim3(ceil_div(32 * 256, 256)), dim3(256), 0, s, (const float*)t.part, split1, 32,

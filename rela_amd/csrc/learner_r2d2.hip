@@ -33,6 +33,16 @@ using TileRows = TileCfg<128, 64, 4, 2, false>;  // M = many rows, A k-contiguou
 using TileRec = TileCfg<64, 64, 2, 4, false>;    // M = batch rows of one time step
 using TileWg = TileCfg<128, 64, 4, 2, true>;     // weight gradients, M = 2048 gate rows
 using TileW32r = TileCfg<32, 64, 2, 4, true>;    // head weight gradients (M = 32)
+// The backward GEMMs of mode 3 (f32x3_bwd): every operand as three bf16 parts (gemm_bf16x3.h, PARTS = 3), f32 accuracy on
+// the bf16 matrix cores.  64 x 64 tiles (100 registers, 60 KB of LDS: two blocks per CU) measured ahead of the 128 x 64
+// tiles of TileRows / TileWg (172 registers, 84 KB: one block) at 5,312 training rows: dW_ih 0.66 -> 0.58 ms, dW_hh 0.15 ->
+// 0.10, d_a3 0.61 -> 0.58.  The conv weight gradients run one block per CU at their f32 split counts (conv3 0.28 ms against
+// 0.24 in f32); twice the splits: conv1 0.35 -> 0.28 ms, conv2 0.31 -> 0.25, conv3 0.28 -> 0.15 (four times: the same).
+// The heads' two GEMMs (K = 32, M = 32) are 11 / 10 us in three parts against 10 / 8 us and stay on gemm_lds.
+using Tile6Rows = gemm3::TileCfg<64, 64, 2, 4, false, 3>;
+using Tile6Wg = Tile6W64;
+constexpr int kX6SplitMul[3] = {2, 2, 2};  // conv1, conv2, conv3 (TrunkBwd::emu_split_mul)
+static_assert(kX6SplitMul[0] <= kMaxSplitMul && kX6SplitMul[1] <= kMaxSplitMul && kX6SplitMul[2] <= kMaxSplitMul, "part size");
 
 // GX[r][g] = bias[g] + sum_k a3[r][k] * wihT[k][g]
 struct ProbGateX : ProbBase {
@@ -729,7 +739,7 @@ int forward_pre(rela_r2d2_learner* l, int which, int Bn, const uint8_t* obs, con
     a3_records = true;
   } else {
     // (f32x3: on split3 records; only the online pass leaves a1 / a2 / a3 in f32, for the backward kernels)
-    const bool x3 = l->precision == 2 && l->s3rec != nullptr;
+    const bool x3 = l->precision >= 2 && l->s3rec != nullptr;
     rc = lstmnet_trunk(net, rowsAll, obs, l->a1, l->a2, l->a3, s, kTrunkNames, fast_target,
                        (fast_target || x3) ? &a3_records : nullptr, x3 ? l->s3rec : nullptr, which == 0);
   }
@@ -1011,13 +1021,15 @@ extern "C" int rela_r2d2_learner_set_value_rescale(rela_r2d2_learner* l, float e
 }
 
 extern "C" int rela_r2d2_learner_set_precision(rela_r2d2_learner* l, int mode) {
-  RELA_CHECK(l && mode >= 0 && mode <= 2, RELA_EINVAL, "rela_r2d2_learner_set_precision: mode must be 0, 1 or 2");
+  RELA_CHECK(l && mode >= 0 && mode <= 3, RELA_EINVAL, "rela_r2d2_learner_set_precision: mode must be 0, 1, 2 or 3");
   l->precision = mode;
   // 2 (f32x3): conv2 / conv3 of both nets' trunks on the three-part bf16 kernels (csrc/gemm_f32emu.h, f32 accuracy);
   // everything else -- gate GEMMs, recurrences, backward -- as in mode 0.  (Mode 1 passes its choices per call.)
-  int rc = rela_lstmnet_set_precision(l->online, mode == 2 ? 2 : 0);
+  // 3 (f32x3_bwd): the forwards of mode 2, and the batched backward GEMMs on three-part operands (rela_r2d2_learner_grad).
+  const int net_mode = mode >= 2 ? 2 : 0;
+  int rc = rela_lstmnet_set_precision(l->online, net_mode);
   if (rc != RELA_OK) return rc;
-  return rela_lstmnet_set_precision(l->target, mode == 2 ? 2 : 0);
+  return rela_lstmnet_set_precision(l->target, net_mode);
 }
 
 extern "C" int rela_r2d2_learner_check(rela_r2d2_learner* l, void* stream_) {
@@ -1115,6 +1127,10 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
   const size_t blk = (size_t)Bn * kHid;
   float *H = l->Hs[0], *Cc = l->Cs[0];
   const float* o_tr = H + (size_t)(burn + 1) * blk;  // LSTM outputs of the training steps
+  // mode 3: the large GEMMs over all training rows at once (dW_hh, dW_ih, d_a3, the conv weight gradients), with the
+  // Problems of mode 0, on gemm_bf16x3 with three-part operands (f32 accuracy); the heads' GEMMs, the recurrence, the cell
+  // kernels and the conv data gradients stay what they are in mode 0
+  const bool x6 = l->precision == 3;
   // heads: d_o, dW, db
   {
     ProbHeadDgradSeq p{};
@@ -1178,7 +1194,8 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
     ProbWhh p{};
     p.M = kGates, p.N = kHid, p.K = rowsTr;
     p.dg = DG, p.hprev = hprev, p.out = Gm[7];
-    launch_gemm<TileWg>(p, 1, s, "learner_wgrad_lstm_hh");
+    if (x6) (void)gemm3::launch_gemm<Tile6Wg>(p, 1, s, "learner_wgrad_lstm_hh");
+    else launch_gemm<TileWg>(p, 1, s, "learner_wgrad_lstm_hh");
   }
   if (l->precision == 1) {
     // dW_ih[g][c*49+pos] = sum_r dg[r][g] * a3[r][pos*64+c]: both operands transposed into rec64 rows of 64 r each
@@ -1206,7 +1223,8 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
     ProbWih p{};
     p.M = kGates, p.N = kFeat, p.K = rowsTr;
     p.dg = DG, p.a3 = a3_tr, p.out = Gm[6];
-    launch_gemm<TileWg>(p, 1, s, "learner_wgrad_lstm_ih");
+    if (x6) (void)gemm3::launch_gemm<Tile6Wg>(p, 1, s, "learner_wgrad_lstm_ih");
+    else launch_gemm<TileWg>(p, 1, s, "learner_wgrad_lstm_ih");
   }
   colsum_launch(DG, rowsTr, kGates, l->cpart, Gm[8], s);  // bias_ih_l0 and bias_hh_l0 see the same gradient
   RELA_HIP(hipMemcpyAsync(Gm[9], Gm[8], sizeof(float) * kGates, hipMemcpyDeviceToDevice, s));
@@ -1224,7 +1242,8 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
     ProbIhDgrad p{};
     p.M = rowsTr, p.N = kFeat, p.K = kGates;
     p.dg = DG, p.wihp = l->wihp, p.a3 = a3_tr, p.d_a3 = l->d_a3;
-    launch_gemm<TileRows>(p, 1, s, "learner_dgrad_lstm_ih");
+    if (x6) (void)gemm3::launch_gemm<Tile6Rows>(p, 1, s, "learner_dgrad_lstm_ih");
+    else launch_gemm<TileRows>(p, 1, s, "learner_dgrad_lstm_ih");
   }
   {
     TrunkBwd t{};
@@ -1233,6 +1252,8 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
     t.w2p = l->w2p, t.w3p = l->w3p;
     t.g_c1w = Gm[0], t.g_c1b = Gm[1], t.g_c2w = Gm[2], t.g_c2b = Gm[3], t.g_c3w = Gm[4], t.g_c3b = Gm[5];
     t.fast = l->precision == 1;
+    t.emu = x6;  // conv1 / conv2 / conv3 weight gradients on three-part operands, one lane
+    for (int i = 0; i < 3; ++i) t.emu_split_mul[i] = kX6SplitMul[i];
     trunk_backward(t, s);
   }
   RELA_LAUNCH_CHECK();

@@ -154,8 +154,12 @@ class _HipLearner:
         """cuda f32[2]: gradient norm before clipping, clip coefficient of the last apply()."""
         return self._view(getattr(self._capi.lib, self._PREFIX + "stats_dev")(self.h), (2,))
 
+    _PRECISIONS = {"f32": 0, "bf16x2": 1, "f32x3": 2}
+
     def _set_precision(self, mode):
-        self._call("set_precision", {"f32": 0, "bf16x2": 1, "f32x3": 2}[mode])
+        if mode not in self._PRECISIONS:
+            raise ValueError("%s.set_precision: %r is not one of %s" % (type(self).__name__, mode, sorted(self._PRECISIONS)))
+        self._call("set_precision", self._PRECISIONS[mode])
 
     def grad(self):
         self._call("grad", self._stream())
@@ -228,7 +232,10 @@ class HipApexLearner(_HipLearner):
     def set_precision(self, mode):
         """"f32" (default) or "bf16x2": the arithmetic of the two gradient-free forwards of td_err (the pass whose
         activations feed the backward kernels stays f32).  "f32x3": conv2 / conv3 of all three forwards on the f32-accurate
-        bf16 kernels (csrc/gemm_f32emu.h, from 512 rows); fc, heads, loss, backward and optimiser in exact f32."""
+        bf16 kernels (csrc/gemm_f32emu.h, from 512 rows); fc, heads, loss, backward and optimiser in exact f32.
+        ("f32x3_bwd" is the R2D2 learner's mode for its backward GEMMs on f32-accurate three-part bf16 operands; this
+        learner's "f32x3" already runs its head, fc and conv weight-gradient GEMMs that way (csrc/learner.hip), so the name
+        is refused with ValueError.)"""
         self._set_precision(mode)
 
     def debug_activations(self):
@@ -314,9 +321,16 @@ class HipR2D2Learner(_HipLearner):
         self.load_state_dicts(agent.online_net.state_dict(), agent.target_net.state_dict())
         return self
 
+    _PRECISIONS = dict(_HipLearner._PRECISIONS, f32x3_bwd=3)
+
     def set_precision(self, mode):
         """"f32" (default); "bf16x2": the target net's conv trunk on split-bf16 MFMA (no gradient flows through it);
-        "f32x3": conv2 / conv3 of both trunks on the f32-accurate three-part bf16 kernels (csrc/gemm_f32emu.h)."""
+        "f32x3": conv2 / conv3 of both trunks on the f32-accurate three-part bf16 kernels (csrc/gemm_f32emu.h).
+        "f32x3_bwd": the forwards of "f32x3" (loss and priorities are the same bits), and the large backward GEMMs over
+        all training rows -- dW_hh, dW_ih, the input-side data gradient and the conv1 / conv2 / conv3 weight gradients --
+        with three-part bf16 operands on the bf16 matrix cores (csrc/gemm_bf16x3.h, f32 accuracy; 12 % off the step at
+        B = 64).  The heads' two small GEMMs (slower in three parts), the recurrent chains and per-step recurrent GEMMs,
+        the cell kernels, the conv data gradients, the column sums, loss, clip and optimiser stay in exact f32."""
         self._set_precision(mode)
 
     def check(self):

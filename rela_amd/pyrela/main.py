@@ -30,6 +30,9 @@ from rela_amd.pyrela.r2d2 import R2D2Agent  # noqa: E402
 rela = create_env.rela
 
 
+LEARNER_PRECISIONS = ("f32", "bf16x2", "f32x3", "f32x3_bwd")
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Ape-X on synthetic Atari-shaped envs (MI355X)")
     p.add_argument("--save_dir", type=str, default="exps/exp1")
@@ -76,12 +79,31 @@ def parse_args(argv=None):
     p.add_argument("--hip_learner", type=int, default=1,
                    help="run loss / backward / clip / optimiser through the hand-written HIP learner step "
                         "(csrc/learner.hip for apex, csrc/learner_r2d2.hip for r2d2) instead of PyTorch autograd")
+    p.add_argument("--learner_precision", type=str, default="f32", choices=LEARNER_PRECISIONS,
+                   help="arithmetic of the HIP learner step (set_precision of rela_amd/learner.py): f32 = exact f32; bf16x2 "
+                        "= two-part bf16 on the gradient-free forwards; f32x3 = f32-accurate three-part bf16 forwards; "
+                        "f32x3_bwd (r2d2 only) = f32x3 plus the backward GEMMs on three-part bf16 operands")
     return p.parse_args(argv)
+
+
+def learner_precision(args):
+    """--learner_precision, checked against --algo and --hip_learner (an args object without it means f32)."""
+    mode = getattr(args, "learner_precision", "f32")
+    if mode not in LEARNER_PRECISIONS:
+        raise SystemExit("--learner_precision must be one of %s" % ", ".join(LEARNER_PRECISIONS))
+    if mode != "f32" and not getattr(args, "hip_learner", 1):
+        raise SystemExit("--learner_precision %s needs the HIP learner step (--hip_learner 1): the PyTorch autograd step "
+                         "runs in f32 only" % mode)
+    if mode == "f32x3_bwd" and args.algo == "apex":
+        raise SystemExit("--learner_precision f32x3_bwd is the R2D2 learner's mode (--algo r2d2): with --algo apex, f32x3 "
+                         "already runs the backward GEMMs on three-part bf16 operands")
+    return mode
 
 
 def train(args, on_epoch=None):
     if args.algo not in ("apex", "r2d2"):
         raise SystemExit("--algo must be apex or r2d2")
+    precision = learner_precision(args)
     torch.manual_seed(args.seed + 2)
     torch.cuda.manual_seed(args.seed + 3)
     pprint.pprint(vars(args))
@@ -104,6 +126,8 @@ def train(args, on_epoch=None):
 
         cls = HipR2D2Learner if args.algo == "r2d2" else HipApexLearner
         learner = cls.from_agent(agent, args.batchsize, lr=args.lr, eps=args.eps, grad_clip=args.grad_clip)
+        if precision != "f32":
+            learner.set_precision(precision)
 
     # create eval locker here, as upstream (main.py:115-116): replicas on the host, device string "cpu"
     eval_locker = rela.ModelLocker([type(agent).clone(agent, "cpu")], "cpu")
@@ -282,6 +306,8 @@ def _multi_worker(rank, world, args, port, results):
     assert args.batchsize % G == 0 and args.num_thread % G == 0
     if rank == 0:
         learner = learner_cls.from_agent(agent, args.batchsize, lr=args.lr, eps=args.eps, grad_clip=args.grad_clip)
+        if learner_precision(args) != "f32":
+            learner.set_precision(learner_precision(args))
         # scheduled exchange: command words (a host synchronisation on every rank) only with the weight publish every
         # actor_sync_freq steps; the sample / update_priority pairs in between follow the announced cycle
         if native:  # partitions and flat buffers mapped through HIP IPC: rows and weights never enter a collective
@@ -436,6 +462,7 @@ def train_multi(args):
 
     if args.algo not in ("apex", "r2d2"):
         raise SystemExit("--algo must be apex or r2d2")
+    learner_precision(args)  # (refused here, before any process is spawned)
     if args.algo == "r2d2" and os.environ.get("RELA_REPLAY_DEDUP"):
         # the learner process would read the partitions' rows through IPC, and a sequence partition with de-duplicated
         # stacks holds references, not frames: the library refuses to export it (rela_replay_export_chunks)

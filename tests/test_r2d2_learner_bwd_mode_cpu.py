@@ -1,0 +1,97 @@
+"""CPU checks of the R2D2 learner's "f32x3_bwd" mode (tests/test_r2d2_learner_bwd_mode_gpu.py has the GPU half).
+
+Resources: mode 3 instantiates gemm_bf16x3 (csrc/gemm_bf16x3.h) with three-part 64 x 64 tiles for three Problems of
+csrc/learner_r2d2.hip -- ProbWhh, ProbWih, ProbIhDgrad -- next to the conv weight gradients' three.  A block holds four
+register sets of staged loads next to two accumulators per 16 x 16 tile and runs with a second block on its CU; a spill would
+put scratch traffic inside the chunk loop without any test of the results noticing.  So the compiler's own account is asserted
+(as tests/test_trunk_backward_resources_cpu.py does for csrc/learner.hip): csrc/learner_r2d2.hip is compiled device-only
+with build.py's HIP_FLAGS plus -Rpass-analysis=kernel-resource-usage, and every three-part gemm_bf16x3 kernel of the file
+must report `ScratchSize [bytes/lane]: 0`, `VGPRs Spill: 0`, `SGPRs Spill: 0` and an occupancy of at least 4 waves per
+SIMD (a block is 2: the tiles were chosen for two blocks per CU).  Only the remarks are read.
+
+Arguments: rela_amd/pyrela/main.py's --learner_precision and its two refusals.
+"""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# mangled: gemm_bf16x3<TileCfg<BM, BN, WM, WN, AMC, 3, S>, Problem>
+THREE_PART = re.compile(r"11gemm_bf16x3I.*7TileCfgILi\d+ELi\d+ELi\d+ELi\d+ELb[01]ELi3ELi\d+EE")
+NEW_PROBLEMS = ("7ProbWhhE", "7ProbWihE", "11ProbIhDgradE")
+
+
+@pytest.fixture(scope="module")
+def resources(tmp_path_factory):
+    """{mangled kernel name: {remark key: int}} of csrc/learner_r2d2.hip's kernels"""
+    from rela_amd import build as b
+
+    hipcc = b.HIPCC if os.path.exists(b.HIPCC) else shutil.which("hipcc")
+    if not hipcc:
+        pytest.skip("no hipcc here")
+    obj = str(tmp_path_factory.mktemp("r2d2res") / "learner_r2d2_dev.o")
+    cmd = [hipcc] + b.HIP_FLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
+                                   os.path.join(b.CSRC, "learner_r2d2.hip"), "-o", obj]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    out = {}
+    name = None
+    for line in r.stderr.splitlines():
+        m = re.search(r"remark: Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            out[name] = {}
+            continue
+        m = re.search(r"remark:\s+(.+?): (\d+) \[-Rpass-analysis", line)
+        if m and name:
+            out[name][m.group(1)] = int(m.group(2))
+    return out
+
+
+def test_three_part_gemms_have_no_scratch_and_no_spills(resources):
+    mine = {n: v for n, v in resources.items() if THREE_PART.search(n)}
+    for prob in NEW_PROBLEMS:
+        assert sum(prob in n for n in mine) == 1, (prob, sorted(mine))
+    for name, v in sorted(mine.items()):
+        print(name, v)
+        assert v["ScratchSize [bytes/lane]"] == 0, (name, v)
+        assert v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0, (name, v)
+        assert v["Occupancy [waves/SIMD]"] >= 4, (name, v)  # (8 waves per block over 4 SIMDs: two blocks need four)
+
+
+@pytest.fixture(scope="module")
+def entry():
+    from rela_amd.pyrela import main
+
+    return main
+
+
+def test_learner_precision_flag_parses_and_defaults_to_f32(entry):
+    assert entry.parse_args([]).learner_precision == "f32"
+    for mode in ("f32", "bf16x2", "f32x3", "f32x3_bwd"):
+        args = entry.parse_args(["--algo", "r2d2", "--learner_precision", mode])
+        assert args.learner_precision == mode and entry.learner_precision(args) == mode
+    for mode in ("f32", "bf16x2", "f32x3"):
+        assert entry.learner_precision(entry.parse_args(["--algo", "apex", "--learner_precision", mode])) == mode
+    with pytest.raises(SystemExit):
+        entry.parse_args(["--learner_precision", "fp8"])
+
+
+@pytest.mark.parametrize("argv", [["--algo", "apex", "--learner_precision", "f32x3_bwd"],
+                                  ["--algo", "r2d2", "--hip_learner", "0", "--learner_precision", "f32x3_bwd"],
+                                  ["--algo", "r2d2", "--hip_learner", "0", "--learner_precision", "f32x3"],
+                                  ["--algo", "apex", "--hip_learner", "0", "--learner_precision", "bf16x2"]],
+                         ids=lambda a: " ".join(a))
+def test_learner_precision_refusals(entry, argv, capsys):
+    """f32x3_bwd with --algo apex, and anything but f32 with --hip_learner 0: train() and train_multi() end with a
+    SystemExit that says why, before anything is built; f32 with --hip_learner 0 passes the check."""
+    args = entry.parse_args(argv)
+    for run in (entry.train, entry.train_multi):
+        with pytest.raises(SystemExit) as e:
+            run(args)
+        assert "--learner_precision" in str(e.value) and ("--hip_learner 1" in str(e.value) or "--algo r2d2" in str(e.value))
+    assert entry.learner_precision(entry.parse_args(["--hip_learner", "0"])) == "f32"
