@@ -664,6 +664,23 @@ int rela_debug_head_fc_backward(int batch, int A, int mode, int lanes, const flo
                                 const float* fc_a_w, const float* fc_v_w, const float* fc_w, float* g_fc_a_w,
                                 float* g_fc_a_b, float* g_fc_v_w, float* g_fc_v_b, float* g_fc_w, float* g_fc_b, float* d_h,
                                 float* d_a3, void* stream);
+/* Test tap: the LSTM's input-side backward of rela_r2d2_learner_grad (csrc/learner_r2d2.hip: lstm_input_backward, between
+ * the BPTT and the trunk's backward) as one call: dW_hh, dW_ih, the gate column sum copied into both bias gradients, and
+ * d_a3 with its ReLU mask, whose pattern -- a3 > 0 -- is data of the call.  All pointers are device pointers; the call
+ * allocates its own scratch (the copies of W_ih come from the learner's own pack kernels), synchronises and frees it.
+ *   dg       f32 [rows][2048]      gate gradients of every training row
+ *   hprev    f32 [rows][512]       h_{t-1} of every training row
+ *   a3       f32 [rows][49][64]    relu(conv3), channel-last (csrc/ffnet_layout.h)
+ *   w_ih     f32 [2048][3136]      weight_ih_l0 (state_dict layout, column c * 49 + pos)
+ *   g_w_ih, g_w_hh   out: [2048][3136], [2048][512] in state_dict layout;  g_b_ih, g_b_hh   out: [2048] each
+ *   d_a3     out: [rows][49][64] channel-last, masked by a3 > 0
+ * mode (rela_r2d2_learner_set_precision): 0 f32 (gemm_lds); 1 bf16x2, the rec64 path (split_cols_rec64 / split_rows_rec64 /
+ * gemm_rec64_nt); 2 f32x3, which runs mode 0's kernels here; 3 f32x3_bwd, the three GEMMs on three-part bf16 operands.
+ * 1 <= rows <= 32,768.  Bad arguments, NULL pointers and an output that overlaps another buffer of the call are
+ * RELA_EINVAL before anything is launched.                                                                         */
+int rela_debug_lstm_input_backward(int rows, int mode, const float* dg, const float* hprev, const float* a3,
+                                   const float* w_ih, float* g_w_ih, float* g_w_hh, float* g_b_ih, float* g_b_hh,
+                                   float* d_a3, void* stream);
 /* Debug / tests: the learner's own d_ha [B][32], d_h [B][512] and d_a3 [B][49][64] of the last rela_apex_learner_grad
  * (d_ha: of the last rela_apex_learner_loss).  Valid until the next rela_apex_learner_loss.                        */
 int rela_apex_learner_debug_head_grads(rela_apex_learner* l, float** d_ha, float** d_h, float** d_a3);

@@ -237,6 +237,7 @@ _sig("rela_apex_learner_debug_activations", i32, [vp, P(vp), P(vp), P(vp), P(vp)
 _sig("rela_debug_trunk_backward", i32, [i32, i32, i32, i32] + [vp] * 15)
 _sig("rela_debug_loss_grad", i32, [i32, i32, i32] + [vp] * 7 + [f32, f32] + [vp] * 7)
 _sig("rela_debug_head_fc_backward", i32, [i32, i32, i32, i32] + [vp] * 15)
+_sig("rela_debug_lstm_input_backward", i32, [i32, i32] + [vp] * 10)
 _sig("rela_apex_learner_debug_head_grads", i32, [vp, P(vp), P(vp), P(vp)])
 _sig("rela_r2d2_learner_create", i32, [P(vp), i32, i32, i32, f32, i32, i32, f64, i32, f32, f32, f32, i32])
 _sig("rela_r2d2_learner_destroy", None, [vp])

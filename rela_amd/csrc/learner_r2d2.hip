@@ -665,29 +665,36 @@ rela_lstmnet_params lparams_at(const rela_r2d2_learner* l, const float* base) {
   return p;
 }
 
-int repack_r2d2(rela_r2d2_learner* l, bool online, bool target, hipStream_t s) {
+// one pack_lstm_learner launch (wihp may be NULL: the target net keeps no dgrad copy); repack_r2d2 and the test tap
+int launch_pack_lstm(const float* wih, const float* whh, const float* bih, const float* bhh, float* wihT, float* wihp,
+                     float* whhT, float* bsum, hipStream_t s) {
   static const hipError_t pack_attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&pack_lstm_learner),
                                                          hipFuncAttributeMaxDynamicSharedMemorySize,
                                                          (int)(kPackRows * kFeat * sizeof(float)));
   RELA_HIP(pack_attr);
+  hipLaunchKernelGGL(pack_lstm_learner, dim3(kGates / kPackRows), dim3(256), kPackRows * kFeat * sizeof(float), s, wih, whh, bih,
+                     bhh, wihT, wihp, whhT, bsum);
+  RELA_LAUNCH_CHECK();
+  return RELA_OK;
+}
+
+int repack_r2d2(rela_r2d2_learner* l, bool online, bool target, hipStream_t s) {
   if (online) {
     const rela_lstmnet_params p = lparams_at(l, l->P);
     ExtraPacks extra;  // the dgrad operand copies ride along in the re-pack launch
     extra.w2p = l->w2p, extra.w3p = l->w3p;
     int rc = lstmnet_load_extra(l->online, &p, s, extra);
     if (rc != RELA_OK) return rc;
-    hipLaunchKernelGGL(pack_lstm_learner, dim3(kGates / kPackRows), dim3(256), kPackRows * kFeat * sizeof(float), s, p.w_ih, p.w_hh, p.b_ih, p.b_hh,
-                       l->wihT[0], l->wihp, l->whhT[0], l->bsum[0]);
-    RELA_LAUNCH_CHECK();
+    rc = launch_pack_lstm(p.w_ih, p.w_hh, p.b_ih, p.b_hh, l->wihT[0], l->wihp, l->whhT[0], l->bsum[0], s);
+    if (rc != RELA_OK) return rc;
     l->wver[0] += 1;
   }
   if (target) {
     const rela_lstmnet_params p = lparams_at(l, l->PT);
     int rc = rela_lstmnet_load(l->target, &p, 1, s);
     if (rc != RELA_OK) return rc;
-    hipLaunchKernelGGL(pack_lstm_learner, dim3(kGates / kPackRows), dim3(256), kPackRows * kFeat * sizeof(float), s, p.w_ih, p.w_hh, p.b_ih, p.b_hh,
-                       l->wihT[1], (float*)nullptr, l->whhT[1], l->bsum[1]);
-    RELA_LAUNCH_CHECK();
+    rc = launch_pack_lstm(p.w_ih, p.w_hh, p.b_ih, p.b_hh, l->wihT[1], nullptr, l->whhT[1], l->bsum[1], s);
+    if (rc != RELA_OK) return rc;
     l->wver[1] += 1;
   }
   return RELA_OK;
@@ -711,6 +718,84 @@ int refresh_weight_records(rela_r2d2_learner* l, int which, hipStream_t s) {
   }
   RELA_LAUNCH_CHECK();
   l->rec_ver[which] = l->wver[which];
+  return RELA_OK;
+}
+
+// The LSTM's input side over all training rows at once, between the BPTT and trunk_backward: dW_hh, dW_ih, the gate
+// column sum (both bias gradients) and the masked d_a3.  precision as rela_r2d2_learner_set_precision: 1 runs the rec64
+// path (gemm_bf16s.h), 3 the Problems of mode 0 on gemm_bf16x3 with three-part operands, 0 and 2 gemm_lds.
+struct LstmInBwd {
+  int rowsTr;
+  int precision;
+  const float* dg;     // [rowsTr][2048] gate gradients
+  const float* hprev;  // [rowsTr][512] h_{t-1} of every training row
+  const float* a3;     // [rowsTr][49][64] relu(conv3), channel-last: operand of dW_ih and the mask of d_a3
+  const float* wihp;   // (precision != 1) W_ih in k order, k = pos * 64 + c
+  const uint8_t* wTrec;          // (precision 1) W_ih^T as rec64 [3136][32 chunks]
+  uint8_t *arec, *trec;          // (precision 1) scratch: rowsTr * 2048 * 4 and (2048 + 3136) * ceil(rowsTr / 64) * 256 bytes
+  float* cpart;                  // scratch, kColsumBlocks * 2048
+  float *g_w_ih, *g_w_hh, *g_b_ih, *g_b_hh;  // state_dict layout
+  float* d_a3;                   // [rowsTr][49][64]
+};
+int lstm_input_backward(const LstmInBwd& t, hipStream_t s) {
+  const int rowsTr = t.rowsTr;
+  const bool x6 = t.precision == 3;
+  const float *DG = t.dg, *hprev = t.hprev, *a3_tr = t.a3;
+  if (t.precision != 1) {
+    ProbWhh p{};
+    p.M = kGates, p.N = kHid, p.K = rowsTr;
+    p.dg = DG, p.hprev = hprev, p.out = t.g_w_hh;
+    if (x6) (void)gemm3::launch_gemm<Tile6Wg>(p, 1, s, "learner_wgrad_lstm_hh");
+    else launch_gemm<TileWg>(p, 1, s, "learner_wgrad_lstm_hh");
+  }
+  if (t.precision == 1) {
+    // dW_ih[g][c*49+pos] = sum_r dg[r][g] * a3[r][pos*64+c]: both operands transposed into rec64 rows of 64 r each
+    // (a3's columns land in weight_ih_l0's own column order, so the result is stored row-major as it is)
+    using namespace gemm16;
+    const int chunks = ceil_div(rowsTr, 64);
+    uint8_t* dgT = t.trec;
+    uint8_t* a3T = t.trec + (size_t)kGates * chunks * REC;
+    {
+      ProfScope prof("learner_lstm_split_cols", s);
+      hipLaunchKernelGGL(split_cols_rec64, dim3(kGates / 64, chunks), dim3(256), 0, s, DG, (int64_t)rowsTr, kGates, 0, dgT);
+      hipLaunchKernelGGL(split_cols_rec64, dim3(kFeat / 64, chunks), dim3(256), 0, s, a3_tr, (int64_t)rowsTr, kFeat, 1, a3T);
+    }
+    int rc = launch_rec64_nt(dgT, a3T, kGates, kFeat, chunks, EpiPlain{t.g_w_ih, kFeat}, s, "learner_wgrad_lstm_ih");
+    if (rc != RELA_OK) return rc;
+    // dW_hh[g][k] = sum_r dg[r][g] * hprev[r][k]: the same transposed gate gradients against hprev^T (which takes
+    // the place of a3^T, consumed by the launch above)
+    {
+      ProfScope prof("learner_lstm_split_cols", s);
+      hipLaunchKernelGGL(split_cols_rec64, dim3(kHid / 64, chunks), dim3(256), 0, s, hprev, (int64_t)rowsTr, kHid, 0, a3T);
+    }
+    rc = launch_rec64_nt(dgT, a3T, kGates, kHid, chunks, EpiPlain{t.g_w_hh, kHid}, s, "learner_wgrad_lstm_hh");
+    if (rc != RELA_OK) return rc;
+  } else {
+    ProbWih p{};
+    p.M = kGates, p.N = kFeat, p.K = rowsTr;
+    p.dg = DG, p.a3 = a3_tr, p.out = t.g_w_ih;
+    if (x6) (void)gemm3::launch_gemm<Tile6Wg>(p, 1, s, "learner_wgrad_lstm_ih");
+    else launch_gemm<TileWg>(p, 1, s, "learner_wgrad_lstm_ih");
+  }
+  colsum_launch(DG, rowsTr, kGates, t.cpart, t.g_b_ih, s);  // bias_ih_l0 and bias_hh_l0 see the same gradient
+  RELA_HIP(hipMemcpyAsync(t.g_b_hh, t.g_b_ih, sizeof(float) * kGates, hipMemcpyDeviceToDevice, s));
+  if (t.precision == 1) {
+    using namespace gemm16;
+    {
+      ProfScope prof("learner_lstm_split_rows", s);
+      hipLaunchKernelGGL(split_rows_rec64, dim3(ceil_div((int64_t)rowsTr * kGates / 8, 256)), dim3(256), 0, s, DG,
+                         (int64_t)rowsTr, kGates, t.arec);
+    }
+    int rc = launch_rec64_nt(t.arec, t.wTrec, rowsTr, kFeat, kGates / 64, EpiReluMask{t.d_a3, a3_tr, kFeat}, s,
+                             "learner_dgrad_lstm_ih");
+    if (rc != RELA_OK) return rc;
+  } else {
+    ProbIhDgrad p{};
+    p.M = rowsTr, p.N = kFeat, p.K = kGates;
+    p.dg = DG, p.wihp = t.wihp, p.a3 = a3_tr, p.d_a3 = t.d_a3;
+    if (x6) (void)gemm3::launch_gemm<Tile6Rows>(p, 1, s, "learner_dgrad_lstm_ih");
+    else launch_gemm<TileRows>(p, 1, s, "learner_dgrad_lstm_ih");
+  }
   return RELA_OK;
 }
 
@@ -1187,63 +1272,16 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
       launch_gemm<TileRec>(p, kRecSplitB, s, "learner_lstm_rec_bwd");
     }
   }
-  const float* DG = ga_tr;                          // [rowsTr][2048]
-  const float* hprev = H + (size_t)burn * blk;      // h_{t-1} of training step t = H[burn + t]
-  const float* a3_tr = l->a3 + tr0 * kA3;
-  if (l->precision != 1) {
-    ProbWhh p{};
-    p.M = kGates, p.N = kHid, p.K = rowsTr;
-    p.dg = DG, p.hprev = hprev, p.out = Gm[7];
-    if (x6) (void)gemm3::launch_gemm<Tile6Wg>(p, 1, s, "learner_wgrad_lstm_hh");
-    else launch_gemm<TileWg>(p, 1, s, "learner_wgrad_lstm_hh");
-  }
-  if (l->precision == 1) {
-    // dW_ih[g][c*49+pos] = sum_r dg[r][g] * a3[r][pos*64+c]: both operands transposed into rec64 rows of 64 r each
-    // (a3's columns land in weight_ih_l0's own column order, so the result is stored row-major as it is)
-    using namespace gemm16;
-    const int chunks = ceil_div(rowsTr, 64);
-    uint8_t* dgT = l->trec;
-    uint8_t* a3T = l->trec + (size_t)kGates * chunks * REC;
-    {
-      ProfScope prof("learner_lstm_split_cols", s);
-      hipLaunchKernelGGL(split_cols_rec64, dim3(kGates / 64, chunks), dim3(256), 0, s, DG, (int64_t)rowsTr, kGates, 0, dgT);
-      hipLaunchKernelGGL(split_cols_rec64, dim3(kFeat / 64, chunks), dim3(256), 0, s, a3_tr, (int64_t)rowsTr, kFeat, 1, a3T);
-    }
-    int rc = launch_rec64_nt(dgT, a3T, kGates, kFeat, chunks, EpiPlain{Gm[6], kFeat}, s, "learner_wgrad_lstm_ih");
+  {
+    LstmInBwd t{};
+    t.rowsTr = rowsTr, t.precision = l->precision;
+    t.dg = ga_tr;                          // [rowsTr][2048]
+    t.hprev = H + (size_t)burn * blk;      // h_{t-1} of training step t = H[burn + t]
+    t.a3 = l->a3 + tr0 * kA3;
+    t.wihp = l->wihp, t.wTrec = l->wTrec, t.arec = l->arec, t.trec = l->trec, t.cpart = l->cpart;
+    t.g_w_ih = Gm[6], t.g_w_hh = Gm[7], t.g_b_ih = Gm[8], t.g_b_hh = Gm[9], t.d_a3 = l->d_a3;
+    int rc = lstm_input_backward(t, s);
     if (rc != RELA_OK) return rc;
-    // dW_hh[g][k] = sum_r dg[r][g] * hprev[r][k]: the same transposed gate gradients against hprev^T (which takes
-    // the place of a3^T, consumed by the launch above)
-    {
-      ProfScope prof("learner_lstm_split_cols", s);
-      hipLaunchKernelGGL(split_cols_rec64, dim3(kHid / 64, chunks), dim3(256), 0, s, hprev, (int64_t)rowsTr, kHid, 0, a3T);
-    }
-    rc = launch_rec64_nt(dgT, a3T, kGates, kHid, chunks, EpiPlain{Gm[7], kHid}, s, "learner_wgrad_lstm_hh");
-    if (rc != RELA_OK) return rc;
-  } else {
-    ProbWih p{};
-    p.M = kGates, p.N = kFeat, p.K = rowsTr;
-    p.dg = DG, p.a3 = a3_tr, p.out = Gm[6];
-    if (x6) (void)gemm3::launch_gemm<Tile6Wg>(p, 1, s, "learner_wgrad_lstm_ih");
-    else launch_gemm<TileWg>(p, 1, s, "learner_wgrad_lstm_ih");
-  }
-  colsum_launch(DG, rowsTr, kGates, l->cpart, Gm[8], s);  // bias_ih_l0 and bias_hh_l0 see the same gradient
-  RELA_HIP(hipMemcpyAsync(Gm[9], Gm[8], sizeof(float) * kGates, hipMemcpyDeviceToDevice, s));
-  if (l->precision == 1) {
-    using namespace gemm16;
-    {
-      ProfScope prof("learner_lstm_split_rows", s);
-      hipLaunchKernelGGL(split_rows_rec64, dim3(ceil_div((int64_t)rowsTr * kGates / 8, 256)), dim3(256), 0, s, DG,
-                         (int64_t)rowsTr, kGates, l->arec);
-    }
-    int rc = launch_rec64_nt(l->arec, l->wTrec, rowsTr, kFeat, kGates / 64, EpiReluMask{l->d_a3, a3_tr, kFeat}, s,
-                             "learner_dgrad_lstm_ih");
-    if (rc != RELA_OK) return rc;
-  } else {
-    ProbIhDgrad p{};
-    p.M = rowsTr, p.N = kFeat, p.K = kGates;
-    p.dg = DG, p.wihp = l->wihp, p.a3 = a3_tr, p.d_a3 = l->d_a3;
-    if (x6) (void)gemm3::launch_gemm<Tile6Rows>(p, 1, s, "learner_dgrad_lstm_ih");
-    else launch_gemm<TileRows>(p, 1, s, "learner_dgrad_lstm_ih");
   }
   {
     TrunkBwd t{};
@@ -1257,6 +1295,90 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
     trunk_backward(t, s);
   }
   RELA_LAUNCH_CHECK();
+  return RELA_OK;
+}
+
+// The tap writes its outputs while kernels still read the inputs: every output must be a buffer of its own.
+// bufs[0 .. n): the call's buffers with their sizes, the outputs from index first_out on -> does an output overlap any
+// other buffer of the call?  (A caller that hands in one pointer for everything is refused before anything is launched.)
+// Only this tap has the guard: it runs in every mode it does not refuse, so its own bad-argument test, which probes the NULL
+// and range refusals with one pointer for all nine buffers, would otherwise be one slip away from a launch through that
+// pointer.  The two older taps (csrc/learner.hip) take such calls only with arguments they refuse; they are left as they are.
+namespace {
+// as many rows as a learner can have: rela_r2d2_learner_create admits at most kTrunkMaxFrames training rows per step
+constexpr int kLstmTapMaxRows = kTrunkMaxFrames;
+struct TapBuf {
+  const void* p;
+  size_t bytes;
+};
+bool tap_output_overlaps(const TapBuf* bufs, int n, int first_out) {
+  for (int i = first_out; i < n; ++i) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(bufs[i].p), a1 = a0 + bufs[i].bytes;
+    for (int j = 0; j < n; ++j) {
+      if (j == i) continue;
+      const uintptr_t b0 = reinterpret_cast<uintptr_t>(bufs[j].p), b1 = b0 + bufs[j].bytes;
+      if (a0 < b1 && b0 < a1) return true;
+    }
+  }
+  return false;
+}
+}  // namespace
+
+// Test tap: lstm_input_backward on its own, with the gate gradients, h_{t-1}, a3 and weight_ih_l0 as inputs of the call.
+// Everything the learner keeps across steps (the packed copies of W_ih, the rec64 scratch, cpart) lives for this one call;
+// the copies come from the learner's own pack kernels (pack_lstm_learner, and for mode 1 split_rows_rec64 of wihT).
+extern "C" int rela_debug_lstm_input_backward(int rows, int mode, const float* dg, const float* hprev, const float* a3,
+                                              const float* w_ih, float* g_w_ih, float* g_w_hh, float* g_b_ih, float* g_b_hh,
+                                              float* d_a3, void* stream_) {
+  RELA_CHECK(rows >= 1 && rows <= kLstmTapMaxRows && mode >= 0 && mode <= 3, RELA_EINVAL,
+             "rela_debug_lstm_input_backward: bad arguments (rows %d, mode %d)", rows, mode);
+  RELA_CHECK(dg && hprev && a3 && w_ih && g_w_ih && g_w_hh && g_b_ih && g_b_hh && d_a3, RELA_EINVAL,
+             "rela_debug_lstm_input_backward: a pointer is NULL");
+  {
+    const size_t n = (size_t)rows, f = sizeof(float);
+    const TapBuf bufs[9] = {{dg, n * kGates * f},          {hprev, n * kHid * f},        {a3, n * kFeat * f},
+                            {w_ih, (size_t)kGates * kFeat * f}, {g_w_ih, (size_t)kGates * kFeat * f}, {g_w_hh, (size_t)kGates * kHid * f},
+                            {g_b_ih, kGates * f},          {g_b_hh, kGates * f},         {d_a3, n * kFeat * f}};
+    RELA_CHECK(!tap_output_overlaps(bufs, 9, 4), RELA_EINVAL,
+               "rela_debug_lstm_input_backward: an output buffer overlaps another buffer of the call");
+  }
+  hipStream_t s = (hipStream_t)stream_;
+  struct Scratch {
+    DevBuffers mem;
+    ~Scratch() { mem.free_all(); }
+  } sc;
+  LstmInBwd t{};
+  t.rowsTr = rows, t.precision = mode, t.dg = dg, t.hprev = hprev, t.a3 = a3;
+  t.g_w_ih = g_w_ih, t.g_w_hh = g_w_hh, t.g_b_ih = g_b_ih, t.g_b_hh = g_b_hh, t.d_a3 = d_a3;
+  // pack_lstm_learner also transposes W_hh and sums the biases: zeros stand in for them, their outputs are not read
+  float *wihT = nullptr, *wihp = nullptr, *zeros = nullptr, *whhT = nullptr, *bsum = nullptr;
+  if (int rc = sc.mem.alloc(&wihT, (size_t)kFeat * kGates, false)) return rc;
+  if (int rc = sc.mem.alloc(&wihp, (size_t)kGates * kFeat, false)) return rc;
+  if (int rc = sc.mem.alloc(&zeros, (size_t)kGates * kHid, false)) return rc;
+  if (int rc = sc.mem.alloc(&whhT, (size_t)kHid * kGates, false)) return rc;
+  if (int rc = sc.mem.alloc(&bsum, (size_t)kGates, false)) return rc;
+  if (int rc = sc.mem.alloc(&t.cpart, (size_t)kColsumBlocks * kGates, false)) return rc;
+  RELA_HIP(hipMemsetAsync(zeros, 0, sizeof(float) * kGates * kHid, s));
+  if (int rc = launch_pack_lstm(w_ih, zeros, zeros, zeros, wihT, wihp, whhT, bsum, s)) return rc;
+  t.wihp = wihp;
+  if (mode == 1) {  // as refresh_weight_records (online net) and the learner's sizes of arec / trec, for `rows` rows
+    using namespace gemm16;
+    uint8_t* wTrec = nullptr;
+    const size_t chunks = ((size_t)rows + 63) / 64;
+    if (int rc = sc.mem.alloc(&wTrec, (size_t)kFeat * (kGates / 64) * REC, false)) return rc;
+    if (int rc = sc.mem.alloc(&t.arec, (size_t)rows * (kGates / 64) * REC, false)) return rc;
+    if (int rc = sc.mem.alloc(&t.trec, (size_t)(kGates + kFeat) * chunks * REC, false)) return rc;
+    hipLaunchKernelGGL(split_rows_rec64, dim3(ceil_div((int64_t)kGates * kFeat / 8, 256)), dim3(256), 0, s,
+                       (const float*)wihT, (int64_t)kFeat, kGates, wTrec);
+    RELA_LAUNCH_CHECK();
+    t.wTrec = wTrec;
+  }
+  const int rc = lstm_input_backward(t, s);
+  const hipError_t launched = hipGetLastError();
+  const hipError_t done = hipStreamSynchronize(s);  // (the scratch goes away with `sc`)
+  if (rc != RELA_OK) return rc;
+  RELA_HIP(launched);
+  RELA_HIP(done);
   return RELA_OK;
 }
 

@@ -13,6 +13,8 @@ Shapes (A, B, seq, burn, n):
                        the forwards stay on the f32 kernels (fewer than 512 frames)
   (18, 33, 12, 6, 3)   693 frames, 495 training rows: ragged, the three-part forwards run too
   (6, 130, 3, 1, 1)    650 frames, 520 training rows: B > 128 takes the per-step recurrence
+  (6, 33, 30, 0, 2)    1,056 frames, 1,056 training rows: above 1,024, where conv2's / conv3's weight gradients run at twice
+                       mode 0's split-K slices (54 / 56: TrunkBwd::emu_split_mul)
 
 Modes 0, 1 and 2 must not move a bit: sha256 of the flat gradient buffer, the loss and the priorities of the first two
 shapes are compared with tests/golden/r2d2_learner_parent_bits.json, recorded on an MI355X with this file's `compute()`
@@ -36,8 +38,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 FIXTURE = os.path.join(HERE, "golden", "r2d2_learner_parent_bits.json")
 
-SMALL, RAGGED, PER_STEP = (6, 5, 7, 0, 2), (18, 33, 12, 6, 3), (6, 130, 3, 1, 1)
-SHAPES = [SMALL, RAGGED, PER_STEP]
+SMALL, RAGGED, PER_STEP, ABOVE_1024 = (6, 5, 7, 0, 2), (18, 33, 12, 6, 3), (6, 130, 3, 1, 1), (6, 33, 30, 0, 2)
+SHAPES = [SMALL, RAGGED, PER_STEP, ABOVE_1024]
 PARENT_SHAPES = [RAGGED, SMALL]
 PARENT_MODES = ("f32", "bf16x2", "f32x3")
 # the GEMM launches that leave "gemm_lds (f32)" for "gemm_bf16x3" between mode 2 and mode 3 (DESIGN 4.7 has the table)
@@ -269,7 +271,7 @@ def test_existing_modes_keep_the_parents_bits(shape, mode):
 
 
 # ---- determinism, the split entry points, the update -------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", [SMALL, RAGGED], ids=["45-frames", "693-frames"])
+@pytest.mark.parametrize("shape", [SMALL, RAGGED, ABOVE_1024], ids=["45-frames", "693-frames", "1056-frames"])
 def test_mode_3_is_reproducible_and_loss_plus_grad_equals_backward(shape):
     """two backward() calls on one batch leave the same gradient bits (any split-K reduces in a fixed order), and
     loss() + grad() leave the bits of backward()"""

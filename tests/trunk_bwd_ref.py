@@ -152,6 +152,34 @@ def bf16_hi(t):
     return t.to(torch.float32).to(torch.bfloat16).to(torch.float64)
 
 
+def bf16_parts(t, n=3):
+    """-> the first n bf16 parts of the float32 values of t, as float64 tensors: hi = bf16(x), mid = bf16(x - hi),
+    lo = bf16(x - hi - mid), every rounding to nearest-even as the kernels split their operands"""
+    rest = torch.as_tensor(t).detach().to(torch.float32)
+    parts = []
+    for _ in range(n):
+        part = rest.to(torch.bfloat16).to(torch.float32)
+        parts.append(part.to(torch.float64))
+        rest = rest - part
+    return parts
+
+
+def bf16_two(t):
+    """hi + mid: an operand rounded to two bf16 parts"""
+    hi, mid = bf16_parts(t, 2)
+    return hi + mid
+
+
+def parts_needed(t, dims=None):
+    """how many bf16 parts the entries of t need (0 for zero, at most 3 for whatever float32 holds): the largest over the
+    whole tensor, or with `dims` the largest over those dimensions"""
+    t = torch.as_tensor(t).detach().to(torch.float64)
+    hi, mid, lo = bf16_parts(t, 3)
+    assert bool((hi + mid + lo == t).all()), "an entry does not fit three bf16 parts"
+    need = (hi != 0).to(torch.int64) + (mid != 0).to(torch.int64) + (lo != 0).to(torch.int64)
+    return int(need.max()) if dims is None else need.amax(dims)
+
+
 # ---- integer data: every product and every partial sum exactly representable ------------------------------------
 # d_a3 = integers * 2^-6, weights = integers * 2^-4, a1 / a2 small non-negative integers, u8 frames: every term of every
 # output is an integer multiple of UNIT[key], so a float32 sum is exact -- whatever its order, split or tiling, and in
