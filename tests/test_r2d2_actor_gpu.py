@@ -12,11 +12,10 @@ KEYS = ["net.0.weight", "net.0.bias", "net.2.weight", "net.2.bias", "net.4.weigh
         "fc_a.weight", "fc_a.bias"]
 
 
-def _net(capi, A, seed):
+def _load(capi, h, A, seed):
+    """synth_lstm_params(A, seed) into the net h -> (params struct, the arrays it points to)"""
     from synth import synth_lstm_params
 
-    h = C.c_void_p()
-    capi.check(capi.lib.rela_lstmnet_create(C.byref(h), A, 0), "rela_lstmnet_create")
     p, keep = capi.LSTMNetParams(), []
     params = synth_lstm_params(A, seed)
     for (field, _), k in zip(capi.LSTMNetParams._fields_, KEYS):
@@ -24,11 +23,24 @@ def _net(capi, A, seed):
         keep.append(a)
         setattr(p, field, a.ctypes.data_as(C.c_void_p))
     capi.check(capi.lib.rela_lstmnet_load(h, C.byref(p), 0, None), "rela_lstmnet_load")
-    return h, (p, keep)
+    return p, keep
 
 
-def _run(mode, R=8, K=4, precision="f32"):
-    """mode: "reuse" | "switch" (set_reuse(0)) | "reload" (same weights re-loaded before every post_step)."""
+def _net(capi, A, seed):
+    h = C.c_void_p()
+    capi.check(capi.lib.rela_lstmnet_create(C.byref(h), A, 0), "rela_lstmnet_create")
+    return h, _load(capi, h, A, seed)
+
+
+# _run: the ticks before which the online / the target net receive other weights (synth_lstm_params seeds 3 / 4)
+NEW_ONLINE_TICK, NEW_TARGET_TICK = 9, 17
+
+
+def _run(mode, R=8, K=4, precision="f32", change=("online", "target")):
+    """mode: "reuse" | "switch" (set_reuse(0)) | "reload" (the current weights re-loaded before every post_step).
+    change: the nets that receive DIFFERENT weights on the way, in every mode: the online net before tick
+    NEW_ONLINE_TICK's act, the target net before tick NEW_TARGET_TICK's -- a memoised act-step forward of the old
+    weights must then be dropped for the ticks that straddle the change."""
     import torch
 
     from rela_amd import _capi as capi
@@ -54,6 +66,12 @@ def _run(mode, R=8, K=4, precision="f32"):
     rng = np.random.default_rng(5)
     prios, acts, nseq_total = [], [], 0
     for t in range(26):
+        if t == NEW_ONLINE_TICK and "online" in change:
+            v0 = capi.lib.rela_lstmnet_version(online)
+            keep_on = _load(capi, online, A, 3)
+            assert capi.lib.rela_lstmnet_version(online) == v0 + 1
+        if t == NEW_TARGET_TICK and "target" in change:
+            _keep_tg = _load(capi, target, A, 4)
         obs = synth_obs(R, 500 + t)
         eps = np.full(R, 0.0, np.float32)
         legal = (rng.uniform(size=(R, A)) < 0.8).astype(np.float32)
@@ -96,7 +114,11 @@ def test_post_step_reuses_the_act_step_bit_identically(R, K, precision):
     """(r4: also at 128 rows in BOTH precision modes: from 128 rows up the bf16x2 LSTM net runs its conv trunk on the
     split-bf16 kernels -- asserted through the launch census -- and the memoised step must still be bit-identical.
     Also in f32x3, bench.py's R2D2 precision, at 512 rows and at bench.py's R2D2 actor shape of 3,200 rows: the census
-    asserts the three-part trunk and gate GEMM ran, and no split-bf16 kernel.)"""
+    asserts the three-part trunk and gate GEMM ran, and no split-bf16 kernel.)
+    In every mode the online net receives other weights before tick NEW_ONLINE_TICK and the target net before tick
+    NEW_TARGET_TICK (as tests/test_agent_ops_gpu.py does for the Ape-X shard): a memoised forward that outlived the
+    change would part the reusing run from the recomputing ones, and runs without either change show that the new
+    weights reached the priorities."""
     from kernel_names import CONV12, SPLIT_BF16, X3_LSTM
     from rela_amd import _capi as capi
 
@@ -116,6 +138,14 @@ def test_post_step_reuses_the_act_step_bit_identically(R, K, precision):
         assert np.array_equal(base[0], other[0])
         assert np.array_equal(base[1].view(np.uint32), other[1].view(np.uint32)), mode
         assert np.array_equal(base[2].view(np.uint32), other[2].view(np.uint32)), mode
+    # the new weights were used: without the change of a net the priorities are the same bits up to its tick and other
+    # bits at every tick from there on (the target net's own control at the shapes where a run is cheap)
+    bits = lambda run, t: run[1][t].view(np.uint32)
+    controls = (((), NEW_ONLINE_TICK), (("online",), NEW_TARGET_TICK))
+    for change, tick in controls[:2 if R <= 512 else 1]:
+        plain = _run("reuse", R, K, precision, change=change)
+        for t in range(len(base[1])):
+            assert np.array_equal(bits(base, t), bits(plain, t)) == (t < tick), (change, t)
 
 
 def test_device_windows_at_c4_shape_match_the_oracle_buffer():
