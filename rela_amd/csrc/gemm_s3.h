@@ -122,9 +122,16 @@ __device__ __forceinline__ void split3_4(const f32x4& v, uint2& p0, uint2& p1, u
 //   * WEIGHTS: a wave's own three fragments per k-step arrive by LDS-DMA too (fragment order = lane order: 1 KB
 //     contiguous reads), into a private two-slot ring -- no register holds data in flight, so nothing the compiler does
 //     to registers can touch an outstanding load;
-//   * two activation buffers: pair P + 1 is issued when pair P starts; ONE raw s_barrier per pair (it publishes pair
-//     P's lines and retires the reads of the buffer pair P + 1 lands in); counted vmcnt, never 0 in the loop; the
-//     pipeline runs on across pass boundaries (next pass's rows, same weights);
+//   * two activation buffers and ONE raw s_barrier per pair (it publishes pair P's lines and retires the reads of the
+//     buffer pair P + 1 lands in).  What a wave issues per pair -- the J lines of pair P + 1 and the weights of k-steps
+//     2P + 2 and 2P + 3, two k-steps ahead of their use -- goes out ONE PIECE AT A TIME behind the MFMAs of the pair's
+//     tiles (PairSched below: at most kMaxGldsRun = 2 pieces between two MFMA groups, one for passes of 6 and 7 tiles),
+//     not in a burst behind the barrier, where all eight waves would issue loads at the moment nobody has MFMAs to
+//     issue: a wave's piece is issued under its SIMD partner's MFMAs.  (r16, same box, alternated: fc at 6,400 rows
+//     114.6 -> 108.2 us, the x-gates at 3,200 rows 203.2 -> 190.1 us; without the activation loads the old loop took
+//     100.8 / 178.1 us and without the weight loads 103.5 / 174.4: profiles/r16_gemm_s3_issue_ab.md.)  Three counted
+//     vmcnt waits per pair, never 0 in the loop, the in-flight list at each above k_pass; the pipeline runs on across
+//     pass boundaries (next pass's rows, same weights);
 //   * LDS reads are inline asm (the compiler would drain vmcnt before any LDS read it can see while an LDS-DMA is
 //     pending) with counted lgkmcnt: a tile's three fragments are read while the tile before issues its 6 MFMAs.
 // ---------------------------------------------------------------------------------------------------------------------
@@ -185,7 +192,8 @@ struct Pipe {            // what the k-loop carries from pass to pass
   uint32_t s;            // global k-step counter (weight slot = s & 1)
 };
 
-// this wave's weights of k-step k -> ring slot `slot`: [column tile j][part] x 1 KB, lane-linear
+// this wave's weights of k-step k -> ring slot `slot`: [column tile j][part] x 1 KB, lane-linear (the prologue's form;
+// the loop issues the same pieces one at a time)
 template <class P>
 __device__ __forceinline__ void issue_weights(const uint8_t* wsrc, uint8_t* lds, uint32_t bring, int k, uint32_t slot, uint32_t lane) {
   const uint8_t* src = wsrc + (size_t)k * (kStageU4 * 16) + lane * 16;
@@ -195,46 +203,129 @@ __device__ __forceinline__ void issue_weights(const uint8_t* wsrc, uint8_t* lds,
   for (int q = 0; q < CT * 3; ++q) glds16(src + q * 1024, dst + q * 1024);
 }
 
+// ---- where a pair's LDS-DMA pieces are issued (all of it compile time) ----
+// A pair issues N = J + 6 pieces, always in this order:   A(P+1) x J | W(2P+2) x 3 | W(2P+3) x 3.
+// They go to POSITIONS of the pair's MFMA stream: behind the six MFMAs of a tile (SUB = 1: 2 NT positions per pair), and,
+// only where the pieces do not fit one per tile (passes of <= 5 tiles), also behind a tile's third MFMA (SUB = 2).  A
+// position takes CAP = ceil(N / positions) pieces; CAP <= kMaxGldsRun = 2 for every pass size, and 1 for 6 and 7 tiles.
+// So a wave never issues more than kMaxGldsRun LDS-DMAs in a row without MFMAs of its own between them, the loop's back
+// edge included (tests/test_gemm_s3_schedule_cpu.py reads that off the assembly).
+// Placement of the sequence over the positions (S3_GEMM_PLACE; probe builds may choose another for waves 4-7 with
+// S3_GEMM_PLACE_HI): 0 = front-loaded (piece i at position i / CAP), 1 = evenly spread, 2 = back-loaded.  The W(2P+3)
+// pieces are pushed into the second k-step where the placement would put them earlier: their slot is read at k-step 2P+1.
+#ifndef S3_GEMM_PLACE
+#define S3_GEMM_PLACE 0
+#endif
+#ifndef S3_GEMM_PLACE_HI
+#define S3_GEMM_PLACE_HI S3_GEMM_PLACE
+#endif
+#ifndef S3_GEMM_PRIO
+#define S3_GEMM_PRIO 0  // probe builds: 1 = one s_setprio 1 for waves 4-7 in front of the loop
+#endif
+constexpr int kMaxGldsRun = 2;
+template <int NT, int J, int PL>
+struct PairSched {
+  static constexpr int JA = S3_GEMM_ABLATE == 1 ? 0 : J;      // (ablated builds issue nothing and count nothing)
+  static constexpr int WL = S3_GEMM_ABLATE == 2 ? 0 : 3 * CT;
+  static constexpr int N = JA + 2 * WL;
+  static constexpr int SUB = N > 2 * NT ? 2 : 1;
+  static constexpr int S = 2 * NT * SUB;  // positions per pair; the first S / 2 belong to k-step 2P
+  static constexpr int CAP = N > S ? (N + S - 1) / S : 1;
+  static constexpr int pos(int i) {
+    int p = PL == 0 ? i / CAP : PL == 1 ? i * S / N : S - 1 - (N - 1 - i) / CAP;
+    if (i >= JA + WL) {
+      const int lo = S / 2 + (i - JA - WL) / CAP;
+      if (p < lo) p = lo;
+    }
+    return p;
+  }
+  static constexpr int count_at(int p) {
+    int c = 0;
+    for (int i = 0; i < N; ++i) c += pos(i) == p;
+    return c;
+  }
+  static constexpr int first_half() {  // pieces issued under k-step 2P
+    int c = 0;
+    for (int i = 0; i < N; ++i) c += pos(i) < S / 2;
+    return c;
+  }
+  static constexpr bool valid() {
+    for (int i = 0; i < N; ++i) {
+      if (pos(i) < 0 || pos(i) >= S) return false;
+      if (i && pos(i) < pos(i - 1)) return false;     // issue order = position order
+      if (i >= JA + WL && pos(i) < S / 2) return false;  // W(2P+3) only after k-step 2P+1 has read its slot
+    }
+    for (int p = 0; p < S; ++p)
+      if (count_at(p) > kMaxGldsRun) return false;
+    if (S3_GEMM_ABLATE == 0 && first_half() == 0) return false;  // k-step 2P+1's wait would be vmcnt(0)
+    return true;
+  }
+  static_assert(valid(), "the pair's LDS-DMA schedule");
+};
+
 // One pass: NT row tiles x this wave's 16 columns over all KS k-steps.  J = LDS-DMA instructions per wave and pair for
 // the activations (the block's larger pass size decides it, so that the counts in flight do not change at a pass
 // boundary).  offc / offn: this wave's J source offsets (row base + part + this lane's unit) for this pass and the next.
-// In flight at the top of pair P (issue order): A(P) | W(2P) | W(2P+1) -- then W(2P+1)... see the waits below.
-template <class P, int NT, int J>
+//
+// What pair P (k-steps 2P and 2P+1) issues, spread over its tiles by PairSched, and why each piece is legal there:
+//   A(P+1)  -> the activation buffer that was read during pair P-1: every position lies behind pair P's barrier, which
+//              every wave passes only after its last read of pair P-1;
+//   W(2P+2) -> this wave's ring slot of k-step 2P: every position lies behind MFMAs of k-step 2P's first tile, and
+//              those were issued behind the wait for that k-step's weight reads (the fragments are in registers);
+//   W(2P+3) -> the slot of k-step 2P+1: positions of the second k-step only (PairSched::valid), for the same reason.
+// (The ring has two slots, so W(k+2) goes where W(k) was: with the weights only ONE k-step ahead, the wait for W(2P+2)
+// right behind the barrier would have nothing younger in flight and would have to be vmcnt(0).)
+// vmcnt retires in issue order.  In flight (issue order, oldest first) and what each counted wait leaves, WL = 3:
+//   before the barrier of pair P:   ... A(P) | W(2P) | W(2P+1)                      vmcnt(2 WL): A(P) has landed
+//   before k-step 2P's weights:     W(2P) | W(2P+1)                                 vmcnt(WL):   W(2P) has landed
+//   before k-step 2P+1's weights:   W(2P+1) | first_half() pieces of pair P         vmcnt(first_half()): W(2P+1) has landed
+// None of the three is 0 and none depends on the pass: J is the block's, the order A | W | W is every pass's, and
+// first_half() counts pieces of the pass that issues them.  The prologue issues A(P0) | W(2 P0) | W(2 P0 + 1).
+template <class P, int NT, int J, int PL>
 __device__ __forceinline__ void k_pass(const uint8_t* __restrict__ Xb, const uint8_t* __restrict__ wsrc, uint8_t* lds, uint32_t lds0,
                                        const uint32_t (&offc)[J], const uint32_t (&offn)[J], const uint32_t (&ldst)[J],
                                        uint32_t frag_base, uint32_t wave, f32x4 (&acc)[NT][CT], f32x4 (&accs)[NT][CT], Pipe& pp,
                                        int kp0, int kp1) {
-  constexpr int WL = 3 * CT;
+  using SC = PairSched<NT, J, PL>;
+  static_assert(CT == 1, "the positions of PairSched are those of one column tile's MFMAs");
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t bring = kLdsB + wave * 2 * kBSlot;  // this wave's weight ring
   for (int kp = kp0; kp < kp1; ++kp) {  // (split-K: this block's slice of the pairs)
     const uint32_t abuf = (pp.g & 1) * kABuf;
-    // ---- pair kp's lines have landed (issued one pair ago; younger: the weights of k-step s, issued since); everybody
-    // is done with the other buffer
-    wait_vm<WL>();
+    // ---- pair kp's lines have landed (younger: two k-steps of weights); everybody is done with the other buffer
+    wait_vm<2 * SC::WL>();
     __builtin_amdgcn_s_barrier();
-    {  // weights of k-step s + 1 (its slot was read last at k-step s - 1), then the next pair's lines
-      int k1 = 2 * kp + 1;
-      issue_weights<P>(wsrc, lds, bring, k1, (pp.s + 1) & 1, lane);
-      int k2 = kp + 1;
-      const bool nextp = k2 >= kp1;  // (uniform)
-      if (nextp) k2 = kp0;
-      const uint8_t* src = Xb + P::pair_off(k2);
-      const uint32_t dst = ((pp.g + 1) & 1) * kABuf;
-      if constexpr (S3_GEMM_ABLATE != 1) {
-#pragma unroll
-        for (int j = 0; j < J; ++j)
-          glds16(src + (nextp ? offn[j] : offc[j]), lds + (ldst[j] >= (uint32_t)kLdsSpare ? ldst[j] : dst + ldst[j]));
+    // sources and destinations of what this pair issues (all wave-uniform but the lane's 16 bytes)
+    int k2 = kp + 1;
+    const bool nextp = k2 >= kp1;  // (uniform) the next pass's rows, the same weights again
+    if (nextp) k2 = kp0;
+    const uint8_t* asrc = Xb + P::pair_off(k2);
+    const uint32_t adst = ((pp.g + 1) & 1) * kABuf;
+    const uint8_t* wsrc2 = wsrc + (size_t)(2 * k2) * (kStageU4 * 16) + lane * 16;  // W(2P+2); W(2P+3) is one k-step further
+    uint8_t* const wdst0 = lds + bring + (pp.s & 1) * kBSlot;                       // the slot of k-step 2P
+    uint8_t* const wdst1 = lds + bring + ((pp.s + 1) & 1) * kBSlot;                 // the slot of k-step 2P+1
+    auto issue_at = [&](auto pt) {  // the pieces of position PT, fenced; nothing where the position is empty
+      constexpr int PT = decltype(pt)::value;
+      if constexpr (SC::count_at(PT) > 0) {
+        static_for<SC::N>([&](auto ii) {
+          constexpr int I = decltype(ii)::value;
+          if constexpr (SC::pos(I) == PT) {
+            if constexpr (I < SC::JA) {
+              glds16(asrc + (nextp ? offn[I] : offc[I]), lds + (ldst[I] >= (uint32_t)kLdsSpare ? ldst[I] : adst + ldst[I]));
+            } else if constexpr (I < SC::JA + SC::WL) {
+              glds16(wsrc2 + (I - SC::JA) * 1024, wdst0 + (I - SC::JA) * 1024);
+            } else {
+              glds16(wsrc2 + kStageU4 * 16 + (I - SC::JA - SC::WL) * 1024, wdst1 + (I - SC::JA - SC::WL) * 1024);
+            }
+          }
+        });
+        __builtin_amdgcn_sched_barrier(0);
       }
-    }
+    };
     static_for<2>([&](auto hh) {
       constexpr int H = decltype(hh)::value;
-      if constexpr (H == 1) {  // weights of k-step s + 1 = the next pair's first (slot read last at k-step s - 1)
-        int k2 = 2 * kp + 2;
-        if (k2 >= 2 * kp1) k2 = 2 * kp0;
-        issue_weights<P>(wsrc, lds, bring, k2, (pp.s + 1) & 1, lane);
-      }
-      wait_vm<J + WL>();  // the weights of k-step s (younger: the next pair's lines and one k-step of weights)
+      // the weights of this k-step (younger, H = 0: the other k-step's weights; H = 1: what k-step 2P issued)
+      wait_vm<H == 0 ? SC::WL : SC::first_half()>();
       const uint32_t wa = lds0 + bring + (pp.s & 1) * kBSlot + lane * 16;
       u32x4 wq[CT][3];
       static_for<CT>([&](auto jj) {
@@ -279,16 +370,18 @@ __device__ __forceinline__ void k_pass(const uint8_t* __restrict__ Xb, const uin
                      x2 = __builtin_bit_cast(bf16x8, x[C][2]);
         // the five small products have an accumulator of their own (added once per pass): the main one takes ONE
         // rounding per 32 k at the magnitude of the running sum
-#pragma unroll
-        for (int j = 0; j < CT; ++j) {
-          accs[T][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][2], x0, accs[T][j], 0, 0, 0);
-          accs[T][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][0], x2, accs[T][j], 0, 0, 0);
-          accs[T][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][1], x1, accs[T][j], 0, 0, 0);
-          accs[T][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][1], x0, accs[T][j], 0, 0, 0);
-          accs[T][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][0], x1, accs[T][j], 0, 0, 0);
-          acc[T][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][0], x0, acc[T][j], 0, 0, 0);
+        accs[T][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0][2], x0, accs[T][0], 0, 0, 0);
+        accs[T][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0][0], x2, accs[T][0], 0, 0, 0);
+        accs[T][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0][1], x1, accs[T][0], 0, 0, 0);
+        if constexpr (SC::SUB == 2) {  // (short passes only) a position behind the tile's third MFMA
+          if constexpr (SC::count_at((H * NT + T) * 2) > 0) __builtin_amdgcn_sched_barrier(0);
+          issue_at(IC<(H * NT + T) * 2>{});
         }
+        accs[T][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0][1], x0, accs[T][0], 0, 0, 0);
+        accs[T][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0][0], x1, accs[T][0], 0, 0, 0);
+        acc[T][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0][0], x0, acc[T][0], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
+        issue_at(IC<(H * NT + T) * SC::SUB + SC::SUB - 1>{});  // the position behind the tile's six MFMAs
       });
       pp.s += 1;
     });
@@ -346,8 +439,11 @@ __global__ __launch_bounds__(kGemmT, 1) void gemm_s3(const uint8_t* __restrict__
     asm volatile("" : "+v"(bv[j]));  // (returned before the first LDS-DMA is issued: see conv_img_s3.h)
   }
   Pipe pp{0u, 0u};
+  if constexpr (S3_GEMM_PRIO == 1) {
+    if (wave >= 4) __builtin_amdgcn_s_setprio(1);
+  }
 
-  auto run = [&](auto ntm) {
+  auto run =[&](auto ntm) {
     constexpr int NTM = decltype(ntm)::value, J = glds_per_wave(NTM);  // the block's passes have NTM or NTM - 1 tiles
     uint32_t offc[J], offn[J], ldst[J];
     // LDS-DMA instruction i = wave + 8 j of a pair: i = (tile * 3 + part) * 2 + row half; an instruction past the pass's
@@ -370,12 +466,13 @@ __global__ __launch_bounds__(kGemmT, 1) void gemm_s3(const uint8_t* __restrict__
     }
     set_off(offc, 0);
     set_off(offn, min(1, passes - 1));
-    // prologue: pair 0's lines, then the weights of k-step 0 (what the loop's first counted wait expects in flight)
+    // prologue: pair 0's lines, then the weights of its two k-steps (what the loop's counted waits expect in flight)
     {
       const uint8_t* src = Xb + P::pair_off(kp0);
 #pragma unroll
       for (int j = 0; j < J; ++j) glds16(src + offc[j], lds + ldst[j]);
       issue_weights<P>(wsrc, lds, kLdsB + wave * 2 * kBSlot, 2 * kp0, 0, lane);
+      issue_weights<P>(wsrc, lds, kLdsB + wave * 2 * kBSlot, 2 * kp0 + 1, 1, lane);
     }
     // one pass of NT tiles: accumulators (NT x CT column tiles x {main, small terms} x 4 registers -- sized by NT, not by
     // TMV: with all eight tiles' registers live the kernel spilled 1.4 KB per lane and wrote 100 MB of scratch per launch),
@@ -387,7 +484,14 @@ __global__ __launch_bounds__(kGemmT, 1) void gemm_s3(const uint8_t* __restrict__
       for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int j = 0; j < CT; ++j) acc[t][j] = bv[j], accs[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      k_pass<P, NT, J>(Xb, wsrc, lds, lds0, offc, offn, ldst, frag_base, wave, acc, accs, pp, kp0, kp1);
+      if constexpr (S3_GEMM_PLACE_HI != S3_GEMM_PLACE) {  // (probe builds) waves 4-7 place their pieces differently
+        if (wave >= 4)
+          k_pass<P, NT, J, S3_GEMM_PLACE_HI>(Xb, wsrc, lds, lds0, offc, offn, ldst, frag_base, wave, acc, accs, pp, kp0, kp1);
+        else
+          k_pass<P, NT, J, S3_GEMM_PLACE>(Xb, wsrc, lds, lds0, offc, offn, ldst, frag_base, wave, acc, accs, pp, kp0, kp1);
+      } else {
+        k_pass<P, NT, J, S3_GEMM_PLACE>(Xb, wsrc, lds, lds0, offc, offn, ldst, frag_base, wave, acc, accs, pp, kp0, kp1);
+      }
       // ---- epilogue: this lane's four channels (per column tile) of pixel li of every tile
       const int t0 = r0 + first_of(p);
 #pragma unroll

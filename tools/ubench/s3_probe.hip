@@ -2,6 +2,12 @@
 //   hipcc --offload-arch=gfx950 -O3 -I rela_amd/csrc tools/ubench/s3_probe.hip -o tools/ubench/s3_probe
 //   tools/ubench/s3_probe [N = 6554] [iters = 20]
 //   tools/ubench/s3_probe N iters 12 | 13     conv12_s3<false> | <true> alone: time and checksums
+//   tools/ubench/s3_probe N iters 30 [rounds] gemm_s3 alone: fc at N rows and the x-gates at N / 2 rows, alternated; checksums
+// Compile-time switches of gemm_s3's k-loop (csrc/gemm_s3.h), one binary per variant:
+//   -DS3_GEMM_ABLATE=1 | 2      no activation | no weight LDS-DMAs in the loop (timing only, garbage results)
+//   -DS3_GEMM_PLACE=0 | 1 | 2   the pair's LDS-DMA pieces front-loaded (the library's) | evenly spread | back-loaded
+//   -DS3_GEMM_PLACE_HI=p        waves 4-7 place theirs by p, waves 0-3 by S3_GEMM_PLACE
+//   -DS3_GEMM_PRIO=1            one s_setprio 1 for waves 4-7 in front of the loop
 // For conv2 / conv3 / fc of the AtariFFNet trunk at N samples: runs the 6- and 9-product kernels on random ReLU-like
 // activations, compares sampled outputs with an f64 evaluation on the host and with a sequential f32 FMA chain (what
 // "f32 arithmetic" means for one dot product), and times the kernels with HIP events.  One JSON object per line.
@@ -301,9 +307,91 @@ static void time_conv12(int N, int iters) {
          (int)A1OUT, N, us[0], us[1], (unsigned long long)fnv1a(out, out_bytes), (unsigned long long)(A1OUT ? fnv1a(a1, a1_bytes) : 0));
 }
 
+// mode 30: gemm_s3 alone at the shapes the library launches it with -- fc (3136 -> 512, ReLU) at N rows and the recurrent
+// net's x-gates (3136 -> 2048, raw sums) at N / 2 rows -- on random ReLU-like activations and random weights, the two
+// alternated for `rounds` rounds of `iters` launches each; an FNV-1a checksum of each output to compare builds.
+template <class PS, int EPI>
+struct GemmCase {
+  int M = 0;
+  uint8_t* rec = nullptr;
+  uint4* wp = nullptr;
+  float *bias = nullptr, *out = nullptr;
+  void setup(int M_, uint32_t seed) {
+    M = M_;
+    const size_t xe = (size_t)M * 3136, we = (size_t)PS::OC * 3136;
+    uint32_t st = seed * 2654435761u + 12345u;
+    auto rnd = [&]() {  // xorshift32 -> (-1, 1)
+      st ^= st << 13, st ^= st >> 17, st ^= st << 5;
+      return (float)(int32_t)st * (1.0f / 2147483648.0f);
+    };
+    std::vector<float> X(xe), W(we), B(PS::OC);
+    for (auto& v : X) {
+      const float t = rnd();
+      v = t > 0.f ? t : 0.f;
+    }
+    for (auto& v : W) v = rnd() * 0.03f;
+    for (auto& v : B) v = rnd() * 0.1f;
+    float *dX, *dW;
+    CK(hipMalloc(&dX, xe * 4));
+    CK(hipMalloc(&dW, we * 4));
+    CK(hipMalloc(&rec, xe * 6 + 4096));
+    CK(hipMalloc(&wp, packed_u4<ProbFc>() / ProbFc::NCG * (PS::OC / 64) * 16));
+    CK(hipMalloc(&bias, PS::OC * 4));
+    CK(hipMalloc(&out, (size_t)M * PS::OC * 4));
+    CK(hipMemcpy(dX, X.data(), xe * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dW, W.data(), we * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(bias, B.data(), PS::OC * 4, hipMemcpyHostToDevice));
+    const int64_t pel = (int64_t)(PS::OC / 64) * 98 * TN * 64 * 8;
+    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((pel + 255) / 256)), dim3(256), 0, 0, 3, dW, reinterpret_cast<uint16_t*>(wp),
+                       PS::OC / 64, 98);
+    const int64_t px = (int64_t)M * 49, th = px * 16;
+    hipLaunchKernelGGL((s3::split_s3<64>), dim3((unsigned)((th + 255) / 256)), dim3(256), 0, 0, dX, rec, px);
+    CK(hipDeviceSynchronize());
+    CK(hipGetLastError());
+    CK(hipFree(dX));
+    CK(hipFree(dW));
+  }
+  void go() { s3::launch<PS, EPI>(rec, wp, bias, out, M, 0); }
+  float time_us(int iters, hipEvent_t e0, hipEvent_t e1) {
+    CK(hipEventRecord(e0, 0));
+    for (int i = 0; i < iters; ++i) go();
+    CK(hipEventRecord(e1, 0));
+    CK(hipEventSynchronize(e1));
+    float ms = 0;
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    return 1e3f * ms / iters;
+  }
+};
+
+static void time_gemms(int N, int iters, int rounds) {
+  GemmCase<s3::ProbFc, s3::kEpiRelu> fc;
+  GemmCase<s3::ProbFcT<2048>, s3::kEpiRaw> gx;
+  fc.setup(N, 1);
+  gx.setup(N / 2, 2);
+  hipEvent_t e0, e1;
+  CK(hipEventCreate(&e0));
+  CK(hipEventCreate(&e1));
+  for (int i = 0; i < 5; ++i) fc.go(), gx.go();
+  CK(hipDeviceSynchronize());
+  CK(hipGetLastError());
+  for (int r = 0; r < rounds; ++r) {
+    const float a = fc.time_us(iters, e0, e1), b = gx.time_us(iters, e0, e1);
+    printf("{\"probe\": \"gemm_s3\", \"ablate\": %d, \"round\": %d, \"fc_rows\": %d, \"fc_us\": %.2f, \"gates_rows\": %d, \"gates_us\": %.2f}\n",
+           S3_GEMM_ABLATE, r, fc.M, a, gx.M, b);
+    fflush(stdout);
+  }
+  CK(hipGetLastError());
+  printf("{\"probe\": \"gemm_s3\", \"ablate\": %d, \"fc_fnv\": \"%016llx\", \"gates_fnv\": \"%016llx\"}\n", S3_GEMM_ABLATE,
+         (unsigned long long)fnv1a(fc.out, (size_t)fc.M * 512 * 4), (unsigned long long)fnv1a(gx.out, (size_t)gx.M * 2048 * 4));
+}
+
 int main(int argc, char** argv) {
   const int N = argc > 1 ? atoi(argv[1]) : 6554;
   const int iters = argc > 2 ? atoi(argv[2]) : 20;
+  if (argc > 3 && atoi(argv[3]) == 30) {  // gemm_s3 alone: fc at N rows, x-gates at N / 2 rows, [rounds = 3]
+    time_gemms(N, iters, argc > 4 ? atoi(argv[4]) : 3);
+    return 0;
+  }
   if (argc > 3 && atoi(argv[3]) == 12) {  // conv12_s3<false>; 13: conv12_s3<true> (also writes a1_out)
     time_conv12<false>(N, iters);
     return 0;
