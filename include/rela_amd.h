@@ -685,6 +685,41 @@ int rela_debug_lstm_input_backward(int rows, int mode, const float* dg, const fl
  * (d_ha: of the last rela_apex_learner_loss).  Valid until the next rela_apex_learner_loss.                        */
 int rela_apex_learner_debug_head_grads(rela_apex_learner* l, float** d_ha, float** d_h, float** d_a3);
 
+/* Test tap: the sequence TD block of rela_r2d2_learner_loss (csrc/learner_r2d2.hip: seq_td_launch -- q_min_all, seq_select,
+ * seq_td_loss, seq_head_grad; R2D2Agent.td_err / loss / aggregate_priority and AtariLSTMNet.forward's greedy rule and
+ * duel) with the Q tables of the training rows as inputs of the call.  All pointers are device pointers; the call
+ * synchronises.  Rows are time-major training rows, row = i * batch + b, rows = (seq_len + multi_step) * batch; the
+ * caller passes the training part of the batch fields, already past the burn-in.
+ *   q_on, q_tg, legal          f32 [rows][A]   online Q, target Q, legal moves
+ *   act                        i64 [rows];  reward, bootstrap   f32 [rows]
+ *   seq_lens, weight           f32 [batch]   sequence lengths (burn-in included), importance weights
+ *   qa_on, qa_tg, dqa          out: f32 [rows]   Q_online[act], Q_target[greedy], d mean(loss * w) / d Q_online[act]
+ *   priority, loss_seq         out: f32 [batch]   eta-mixed priority, Huber sum per sequence
+ *   loss                       out: f32 [1]   mean(loss_seq * weight)
+ *   d_ha                       out: f32 [rows][32]   columns 0..A-1 = d loss / d fc_a, 31 = d loss / d fc_v, A..30 zero
+ * gamma_n: gamma ** multi_step; vr_eps: value rescaling of the target, <= 0 off; eta is converted as
+ * rela_r2d2_learner_create converts it.  1 <= batch <= 1,024 (seq_td_loss is one block, one thread per sequence),
+ * 1 <= A <= 31, 0 <= burn_in <= seq_len, 1 <= multi_step <= seq_len, rows <= 32,768.  Bad arguments, NULL pointers and an
+ * output that overlaps another buffer of the call are RELA_EINVAL before anything is launched.                        */
+int rela_debug_seq_loss_grad(int batch, int A, int seq_len, int burn_in, int multi_step, const float* q_on,
+                             const float* q_tg, const float* legal, const int64_t* act, const float* reward,
+                             const float* bootstrap, const float* seq_lens, const float* weight, float gamma_n,
+                             float vr_eps, double eta, float* qa_on, float* qa_tg, float* dqa, float* priority,
+                             float* loss_seq, float* loss, float* d_ha, void* stream);
+/* Test tap: the head backward at the top of rela_r2d2_learner_grad (csrc/learner_r2d2.hip: seq_head_backward): d_o, the
+ * two weight gradients (below 1,024 rows one GEMM, from 1,024 rows 32 split-K slices + head_wgrad_reduce: what the learner
+ * runs at that row count, there is no form switch), the column sum of d_ha and head_bias_grad.  No ReLU mask: o is the
+ * LSTM's output.  All pointers are device pointers; the call allocates its own scratch, synchronises and frees it.
+ *   d_ha     f32 [rows][32]    as rela_debug_seq_loss_grad leaves it; columns A..30 take no part
+ *   o        f32 [rows][512]   LSTM outputs of the training rows
+ *   fc_a_w, fc_v_w             [A][512], [1][512]   (state_dict layout)
+ *   d_o                        out: [rows][512]
+ *   g_fc_a_w .. g_fc_v_b       out: [A][512], [A], [1][512], [1]   (state_dict layout)
+ * 1 <= rows <= 32,768, 1 <= A <= 31.  Refusals as rela_debug_seq_loss_grad.                                          */
+int rela_debug_seq_head_backward(int rows, int A, const float* d_ha, const float* o, const float* fc_a_w,
+                                 const float* fc_v_w, float* d_o, float* g_fc_a_w, float* g_fc_a_b, float* g_fc_v_w,
+                                 float* g_fc_v_b, void* stream);
+
 /* ===================================================================================
  * R2D2 learner step  --  pyrela/main.py:206-251 with R2D2Agent.loss (pyrela/r2d2.py:189-206):
  * td_err (:122-187: burn-in unroll without gradient, state zeroed where terminal[burn_in-1], training
@@ -748,6 +783,12 @@ int rela_r2d2_learner_set_precision(rela_r2d2_learner* l, int mode);
  * h(reward[i] + bootstrap[i] * gamma ** n * h_inv(target_qa[i + n])).  Padding, the eta-mixed priority and the gradient
  * keep their logic.  Before the first rela_r2d2_learner_loss / _backward only (later: RELA_ESTATE). */
 int rela_r2d2_learner_set_value_rescale(rela_r2d2_learner* l, float eps);
+/* Debug / tests: the learner's own head buffers over the *rows time-major training rows of the last
+ * rela_r2d2_learner_loss: q_on, q_tg [rows][A], d_ha [rows][32], o_tr [rows][512] (the online LSTM's outputs), and d_o
+ * [rows][512] of the last rela_r2d2_learner_grad.  Valid until the next rela_r2d2_learner_loss; RELA_ESTATE before the
+ * first.  Mirrors rela_apex_learner_debug_head_grads.                                                                */
+int rela_r2d2_learner_debug_heads(rela_r2d2_learner* l, float** q_on, float** q_tg, float** d_ha, float** o_tr,
+                                  float** d_o, int* rows);
 
 /* ===================================================================================
  * Live per-kernel timing (HIP events on the launch stream) for bench.py's roofline line.

@@ -239,6 +239,8 @@ _sig("rela_debug_loss_grad", i32, [i32, i32, i32] + [vp] * 7 + [f32, f32] + [vp]
 _sig("rela_debug_head_fc_backward", i32, [i32, i32, i32, i32] + [vp] * 15)
 _sig("rela_debug_lstm_input_backward", i32, [i32, i32] + [vp] * 10)
 _sig("rela_apex_learner_debug_head_grads", i32, [vp, P(vp), P(vp), P(vp)])
+_sig("rela_debug_seq_loss_grad", i32, [i32] * 5 + [vp] * 8 + [f32, f32, f64] + [vp] * 8)
+_sig("rela_debug_seq_head_backward", i32, [i32, i32] + [vp] * 10)
 _sig("rela_r2d2_learner_create", i32, [P(vp), i32, i32, i32, f32, i32, i32, f64, i32, f32, f32, f32, i32])
 _sig("rela_r2d2_learner_destroy", None, [vp])
 _sig("rela_r2d2_learner_load", i32, [vp, P(LSTMNetParams), P(LSTMNetParams), i32, vp])
@@ -254,6 +256,7 @@ _sig("rela_r2d2_learner_stats_dev", vp, [vp])
 _sig("rela_r2d2_learner_check", i32, [vp, vp])
 _sig("rela_r2d2_learner_set_precision", i32, [vp, i32])
 _sig("rela_r2d2_learner_set_value_rescale", i32, [vp, f32])
+_sig("rela_r2d2_learner_debug_heads", i32, [vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(i32)])
 _sig("rela_prof_enable", i32, [i32])
 _sig("rela_prof_set_filter", i32, [C.c_char_p])
 _sig("rela_prof_summary_json", i32, [C.c_char_p, i64])

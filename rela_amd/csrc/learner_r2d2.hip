@@ -656,6 +656,7 @@ struct rela_r2d2_learner : LearnerCore {
   // batch of the last rela_r2d2_learner_loss, until rela_r2d2_learner_grad consumes it
   int pend_B = 0;
   const uint8_t* pend_obs = nullptr;
+  int last_B = 0;  // batch of the last rela_r2d2_learner_loss that ran through (rela_r2d2_learner_debug_heads)
 };
 
 namespace {
@@ -1136,6 +1137,67 @@ extern "C" int rela_r2d2_learner_check(rela_r2d2_learner* l, void* stream_) {
   return RELA_OK;
 }
 
+namespace {
+// The sequence TD block of rela_r2d2_learner_loss, from the Q tables of the training rows (time-major, rows = (seq + nstep)
+// * Bn) to priorities, loss and the head gradient d_ha; rela_debug_seq_loss_grad runs the same function.  The pointers of
+// legal / act / reward / boot start at the first training row.  census: the tap counts its four launches (the learner's
+// step does not: its census is a recorded one, tests/golden/r2d2_learner_parent_bits.json).
+void seq_td_launch(const float* q_on, const float* q_tg, const float* legal, const int64_t* act, const float* reward,
+                   const float* boot, const float* seq_len, const float* weight, int Bn, int A, int seq, int burn, int nstep,
+                   float gamma_n, float vr_eps, float eta, float one_minus_eta, float* qmin, float* qa_on, float* qa_tg,
+                   float* dqa, float* prio, float* loss_seq, float* loss, float* d_ha, bool census, hipStream_t s) {
+  const int rowsTr = (seq + nstep) * Bn;
+  ProfScope prof("learner_seq_td", s);
+  if (census) note_launch("q_min_all");
+  hipLaunchKernelGGL(q_min_all, dim3(1), dim3(1024), 0, s, q_on, (int64_t)rowsTr * A, qmin);
+  if (census) note_launch("seq_select");
+  hipLaunchKernelGGL(seq_select, dim3(ceil_div(rowsTr, 256)), dim3(256), 0, s, q_on, q_tg, legal, act, (const float*)qmin,
+                     rowsTr, A, qa_on, qa_tg);
+  if (census) note_launch("seq_td_loss");
+  hipLaunchKernelGGL(seq_td_loss, dim3(1), dim3(1024), 0, s, (const float*)qa_on, (const float*)qa_tg, reward, boot, seq_len,
+                     weight, Bn, seq, burn, nstep, gamma_n, vr_eps, eta, one_minus_eta, dqa, prio, loss_seq, loss);
+  if (census) note_launch("seq_head_grad");
+  hipLaunchKernelGGL(seq_head_grad, dim3(ceil_div((int64_t)rowsTr * 32, 256)), dim3(256), 0, s, (const float*)dqa, act, legal,
+                     rowsTr, A, d_ha);
+}
+
+// The head part of rela_r2d2_learner_grad over the time-major training rows (no ReLU on the LSTM's output): d_o, the two
+// weight gradients in the form of that row count, the column sum of d_ha and the two bias gradients;
+// rela_debug_seq_head_backward runs the same function.  part: kSeqHeadPartFloats, cpart: kColsumBlocks * 32, s32: 32 floats.
+// census: the tap also counts which weight-gradient form ran (the two GEMMs count themselves as gemm_lds either way).
+constexpr int kSplitHeads = 32;
+constexpr int kSeqHeadSplitRows = 1024;
+constexpr size_t kSeqHeadPartFloats = (size_t)kSplitHeads * 32 * 512;
+static_assert(kSeqHeadPartFloats <= kTrunkPartFloats, "part size");
+void seq_head_backward(int rowsTr, int A, const float* d_ha, const float* o_tr, const float* a_w, const float* v_w, float* d_o,
+                       float* g_a_w, float* g_a_b, float* g_v_w, float* g_v_b, float* part, float* cpart, float* s32,
+                       bool census, hipStream_t s) {
+  {
+    ProbHeadDgradSeq p{};
+    p.M = rowsTr, p.N = kHid, p.K = 32;
+    p.d_ha = d_ha, p.a_w = a_w, p.v_w = v_w, p.d_o = d_o, p.A = A;
+    launch_gemm<TileRows>(p, 1, s, "learner_dgrad_heads");
+  }
+  if (rowsTr >= kSeqHeadSplitRows) {  // split-K over 32 slices: 256 blocks instead of 8 (0.13 ms on 8 CUs at 5,312 rows)
+    ProbHeadWgradPart p{};
+    p.M = 32, p.N = kHid, p.K = rowsTr;
+    p.d_ha = d_ha, p.h = o_tr, p.part = part;
+    if (census) note_launch("head_wgrad (split-K)"), note_launch("head_wgrad_reduce");
+    launch_gemm<TileW32r>(p, kSplitHeads, s, "learner_wgrad_heads");
+    hipLaunchKernelGGL(head_wgrad_reduce, dim3(ceil_div(32 * 512, 256)), dim3(256), 0, s, (const float*)part, kSplitHeads, A,
+                       g_a_w, g_v_w);
+  } else {
+    ProbHeadWgrad p{};
+    p.M = 32, p.N = kHid, p.K = rowsTr;
+    p.d_ha = d_ha, p.h = o_tr, p.g_a_w = g_a_w, p.g_v_w = g_v_w, p.A = A;
+    if (census) note_launch("head_wgrad (one launch)");
+    launch_gemm<TileW32r>(p, 1, s, "learner_wgrad_heads");
+  }
+  colsum_launch(d_ha, rowsTr, 32, cpart, s32, s);
+  hipLaunchKernelGGL(head_bias_grad, dim3(1), dim3(32), 0, s, (const float*)s32, A, g_a_b, g_v_b);
+}
+}  // namespace
+
 extern "C" int rela_r2d2_learner_backward(rela_r2d2_learner* l, int batch, const void* const* rows_dev,
                                           const float* weight_dev, float* priority_dev, float* loss_dev,
                                           float* loss_seq_dev, void* stream_) {
@@ -1158,7 +1220,8 @@ extern "C" int rela_r2d2_learner_loss(rela_r2d2_learner* l, int batch, const voi
   DeviceGuard g(l->device);
   l->pend_B = 0;
   l->loss_called = true;
-  const int Bn = batch, A = l->A, T = l->T, burn = l->burn, Tt = T - burn, rowsTr = Tt * Bn;
+  l->last_B = 0;
+  const int Bn = batch, A = l->A, burn = l->burn;
   // RNNTransition batch, time-major (types.cc:140-182), in the order of the 10-field sequence schema
   const uint8_t* obs = static_cast<const uint8_t*>(rows_dev[0]);     // [T][B][4][84][84]
   const float* legal = static_cast<const float*>(rows_dev[2]);       // [T][B][A]
@@ -1177,22 +1240,15 @@ extern "C" int rela_r2d2_learner_loss(rela_r2d2_learner* l, int batch, const voi
   // target net first (no gradient, :158-159), then the online net, whose activations stay for the backward pass
   int rc = forward_both(l, Bn, obs, legal_tr, term, h0, c0, s);
   if (rc != RELA_OK) return rc;
-  {
-    ProfScope prof("learner_seq_td", s);
-    hipLaunchKernelGGL(q_min_all, dim3(1), dim3(1024), 0, s, (const float*)l->q_on, (int64_t)rowsTr * A, l->qmin);
-    hipLaunchKernelGGL(seq_select, dim3(ceil_div(rowsTr, 256)), dim3(256), 0, s, (const float*)l->q_on,
-                       (const float*)l->q_tg, legal_tr, act_tr, (const float*)l->qmin, rowsTr, A, l->qa_on, l->qa_tg);
-    hipLaunchKernelGGL(seq_td_loss, dim3(1), dim3(1024), 0, s, (const float*)l->qa_on, (const float*)l->qa_tg,
-                       reward + tr0, boot + tr0, seq_len, weight_dev, Bn, l->seq, burn, l->n, l->gamma_n, l->vr_eps, l->eta,
-                       l->one_minus_eta, l->dqa, priority_dev, l->loss_seq, l->loss);
-    hipLaunchKernelGGL(seq_head_grad, dim3(ceil_div((int64_t)rowsTr * 32, 256)), dim3(256), 0, s, (const float*)l->dqa,
-                       act_tr, legal_tr, rowsTr, A, l->d_ha);
-  }
+  seq_td_launch(l->q_on, l->q_tg, legal_tr, act_tr, reward + tr0, boot + tr0, seq_len, weight_dev, Bn, A, l->seq, burn, l->n,
+                l->gamma_n, l->vr_eps, l->eta, l->one_minus_eta, l->qmin, l->qa_on, l->qa_tg, l->dqa, priority_dev,
+                l->loss_seq, l->loss, l->d_ha, false, s);
   if (loss_dev) RELA_HIP(hipMemcpyAsync(loss_dev, l->loss, sizeof(float), hipMemcpyDeviceToDevice, s));
   if (loss_seq_dev)
     RELA_HIP(hipMemcpyAsync(loss_seq_dev, l->loss_seq, sizeof(float) * Bn, hipMemcpyDeviceToDevice, s));
   RELA_LAUNCH_CHECK();
   l->pend_B = Bn;
+  l->last_B = Bn;
   l->pend_obs = obs;
   return RELA_OK;
 }
@@ -1217,29 +1273,8 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
   // kernels and the conv data gradients stay what they are in mode 0
   const bool x6 = l->precision == 3;
   // heads: d_o, dW, db
-  {
-    ProbHeadDgradSeq p{};
-    p.M = rowsTr, p.N = kHid, p.K = 32;
-    p.d_ha = l->d_ha, p.a_w = P.a_w, p.v_w = P.v_w, p.d_o = l->d_o, p.A = A;
-    launch_gemm<TileRows>(p, 1, s, "learner_dgrad_heads");
-  }
-  if (rowsTr >= 1024) {  // split-K over 32 slices: 256 blocks instead of 8 (0.13 ms on 8 CUs at 5,312 rows)
-    constexpr int kSplitHeads = 32;
-    static_assert((size_t)kSplitHeads * 32 * 512 <= kTrunkPartFloats, "part size");
-    ProbHeadWgradPart p{};
-    p.M = 32, p.N = kHid, p.K = rowsTr;
-    p.d_ha = l->d_ha, p.h = o_tr, p.part = l->part;
-    launch_gemm<TileW32r>(p, kSplitHeads, s, "learner_wgrad_heads");
-    hipLaunchKernelGGL(head_wgrad_reduce, dim3(ceil_div(32 * 512, 256)), dim3(256), 0, s, (const float*)l->part,
-                       kSplitHeads, A, Gm[12], Gm[10]);
-  } else {
-    ProbHeadWgrad p{};
-    p.M = 32, p.N = kHid, p.K = rowsTr;
-    p.d_ha = l->d_ha, p.h = o_tr, p.g_a_w = Gm[12], p.g_v_w = Gm[10], p.A = A;
-    launch_gemm<TileW32r>(p, 1, s, "learner_wgrad_heads");
-  }
-  colsum_launch(l->d_ha, rowsTr, 32, l->cpart, l->s32, s);
-  hipLaunchKernelGGL(head_bias_grad, dim3(1), dim3(32), 0, s, (const float*)l->s32, A, Gm[13], Gm[11]);
+  seq_head_backward(rowsTr, A, l->d_ha, o_tr, P.a_w, P.v_w, l->d_o, Gm[12], Gm[13], Gm[10], Gm[11], l->part, l->cpart, l->s32,
+                    false, s);
   // BPTT over the training steps, newest first; the activated gates in gx become the gate gradients in place
   RELA_HIP(hipMemsetAsync(l->dc_rec, 0, blk * sizeof(float), s));
   const int cell_grid = ceil_div((int64_t)Bn * kHid, 256);
@@ -1379,6 +1414,92 @@ extern "C" int rela_debug_lstm_input_backward(int rows, int mode, const float* d
   if (rc != RELA_OK) return rc;
   RELA_HIP(launched);
   RELA_HIP(done);
+  return RELA_OK;
+}
+
+// Test tap: seq_td_launch on its own, with the Q tables of the training rows and the batch fields as inputs of the call.
+// eta as rela_r2d2_learner_create converts it.  qmin lives for this one call.
+extern "C" int rela_debug_seq_loss_grad(int batch, int A, int seq_len, int burn_in, int multi_step, const float* q_on,
+                                        const float* q_tg, const float* legal, const int64_t* act, const float* reward,
+                                        const float* bootstrap, const float* seq_lens, const float* weight, float gamma_n,
+                                        float vr_eps, double eta, float* qa_on, float* qa_tg, float* dqa, float* priority,
+                                        float* loss_seq, float* loss, float* d_ha, void* stream_) {
+  RELA_CHECK(batch >= 1 && batch <= 1024 && A >= 1 && A <= 31 && seq_len >= 1 && burn_in >= 0 && burn_in <= seq_len &&
+                 multi_step >= 1 && multi_step <= seq_len &&
+                 ((int64_t)seq_len + multi_step) * batch <= (int64_t)kTrunkMaxFrames,
+             RELA_EINVAL, "rela_debug_seq_loss_grad: bad arguments (batch %d, A %d, seq %d, burn %d, n %d)", batch, A, seq_len,
+             burn_in, multi_step);
+  RELA_CHECK(q_on && q_tg && legal && act && reward && bootstrap && seq_lens && weight && qa_on && qa_tg && dqa && priority &&
+                 loss_seq && loss && d_ha,
+             RELA_EINVAL, "rela_debug_seq_loss_grad: a pointer is NULL");
+  {
+    const size_t n = (size_t)(seq_len + multi_step) * batch, f = sizeof(float), b = (size_t)batch;
+    const TapBuf bufs[15] = {{q_on, n * A * f}, {q_tg, n * A * f}, {legal, n * A * f}, {act, n * sizeof(int64_t)},
+                             {reward, n * f},   {bootstrap, n * f}, {seq_lens, b * f},  {weight, b * f},
+                             {qa_on, n * f},    {qa_tg, n * f},     {dqa, n * f},       {priority, b * f},
+                             {loss_seq, b * f}, {loss, f},          {d_ha, n * 32 * f}};
+    RELA_CHECK(!tap_output_overlaps(bufs, 15, 8), RELA_EINVAL,
+               "rela_debug_seq_loss_grad: an output buffer overlaps another buffer of the call");
+  }
+  hipStream_t s = (hipStream_t)stream_;
+  struct Scratch {
+    DevBuffers mem;
+    ~Scratch() { mem.free_all(); }
+  } sc;
+  float* qmin = nullptr;
+  if (int rc = sc.mem.alloc(&qmin, 4, false)) return rc;
+  seq_td_launch(q_on, q_tg, legal, act, reward, bootstrap, seq_lens, weight, batch, A, seq_len, burn_in, multi_step, gamma_n,
+                vr_eps, (float)eta, (float)(1.0 - eta), qmin, qa_on, qa_tg, dqa, priority, loss_seq, loss, d_ha, true, s);
+  const hipError_t launched = hipGetLastError();
+  const hipError_t done = hipStreamSynchronize(s);  // (the scratch goes away with `sc`)
+  RELA_HIP(launched);
+  RELA_HIP(done);
+  return RELA_OK;
+}
+
+// Test tap: seq_head_backward on its own, in the weight-gradient form of its row count.
+extern "C" int rela_debug_seq_head_backward(int rows, int A, const float* d_ha, const float* o, const float* fc_a_w,
+                                            const float* fc_v_w, float* d_o, float* g_fc_a_w, float* g_fc_a_b,
+                                            float* g_fc_v_w, float* g_fc_v_b, void* stream_) {
+  RELA_CHECK(rows >= 1 && rows <= kTrunkMaxFrames && A >= 1 && A <= 31, RELA_EINVAL,
+             "rela_debug_seq_head_backward: bad arguments (rows %d, A %d)", rows, A);
+  RELA_CHECK(d_ha && o && fc_a_w && fc_v_w && d_o && g_fc_a_w && g_fc_a_b && g_fc_v_w && g_fc_v_b, RELA_EINVAL,
+             "rela_debug_seq_head_backward: a pointer is NULL");
+  {
+    const size_t n = (size_t)rows, f = sizeof(float), a = (size_t)A;
+    const TapBuf bufs[9] = {{d_ha, n * 32 * f},  {o, n * kHid * f},        {fc_a_w, a * kHid * f},
+                            {fc_v_w, kHid * f},  {d_o, n * kHid * f},      {g_fc_a_w, a * kHid * f},
+                            {g_fc_a_b, a * f},   {g_fc_v_w, kHid * f},     {g_fc_v_b, f}};
+    RELA_CHECK(!tap_output_overlaps(bufs, 9, 4), RELA_EINVAL,
+               "rela_debug_seq_head_backward: an output buffer overlaps another buffer of the call");
+  }
+  hipStream_t s = (hipStream_t)stream_;
+  struct Scratch {
+    DevBuffers mem;
+    ~Scratch() { mem.free_all(); }
+  } sc;
+  float *part = nullptr, *cpart = nullptr, *s32 = nullptr;
+  if (int rc = sc.mem.alloc(&part, kSeqHeadPartFloats, false)) return rc;
+  if (int rc = sc.mem.alloc(&cpart, (size_t)kColsumBlocks * 32, false)) return rc;
+  if (int rc = sc.mem.alloc(&s32, 32, false)) return rc;
+  seq_head_backward(rows, A, d_ha, o, fc_a_w, fc_v_w, d_o, g_fc_a_w, g_fc_a_b, g_fc_v_w, g_fc_v_b, part, cpart, s32, true, s);
+  const hipError_t launched = hipGetLastError();
+  const hipError_t done = hipStreamSynchronize(s);  // (the scratch goes away with `sc`)
+  RELA_HIP(launched);
+  RELA_HIP(done);
+  return RELA_OK;
+}
+
+// Debug / tests: the learner's own head buffers of the last rela_r2d2_learner_loss / _grad over its rows training rows
+// (time-major): q_on, q_tg [rows][A], d_ha [rows][32], o_tr = the online LSTM's outputs [rows][512], d_o [rows][512] (of the
+// last _grad).  Valid until the next rela_r2d2_learner_loss.
+extern "C" int rela_r2d2_learner_debug_heads(rela_r2d2_learner* l, float** q_on, float** q_tg, float** d_ha, float** o_tr,
+                                             float** d_o, int* rows) {
+  RELA_CHECK(l && q_on && q_tg && d_ha && o_tr && d_o && rows, RELA_EINVAL, "rela_r2d2_learner_debug_heads: bad arguments");
+  RELA_CHECK(l->last_B > 0, RELA_ESTATE, "rela_r2d2_learner_debug_heads: no rela_r2d2_learner_loss yet");
+  *q_on = l->q_on, *q_tg = l->q_tg, *d_ha = l->d_ha, *d_o = l->d_o;
+  *o_tr = l->Hs[0] + (size_t)(l->burn + 1) * l->last_B * kHid;
+  *rows = (l->T - l->burn) * l->last_B;
   return RELA_OK;
 }
 

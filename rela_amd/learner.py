@@ -337,6 +337,17 @@ class HipR2D2Learner(_HipLearner):
         """Synchronises and raises if a grid barrier of the persistent recurrent kernels gave up since the last check."""
         self._call("check", self._stream())
 
+    def debug_heads(self):
+        """f32 views of the learner's own head buffers over the time-major training rows of the last loss(): q_on, q_tg
+        [rows,A], d_ha [rows,32], o_tr [rows,512] (the online LSTM's outputs) and d_o [rows,512] of the last grad(); valid
+        until the next loss()."""
+        C = self._C
+        p = [C.c_void_p() for _ in range(5)]
+        rows = C.c_int()
+        self._call("debug_heads", *[C.byref(x) for x in p], C.byref(rows))
+        n, A = rows.value, self.num_action
+        return [self._view(x.value, sh) for x, sh in zip(p, [(n, A), (n, A), (n, 32), (n, 512), (n, 512)])]
+
     def backward(self, batch, weight):
         """batch: RNNTransition-shaped (time-major [T, B, ...] cuda tensors: obs{s, eps, legal_move}, h0{h0, c0},
         action{a}, reward, terminal, bootstrap, seq_len); weight: cuda f32[B].
