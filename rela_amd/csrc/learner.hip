@@ -109,29 +109,25 @@ struct HeadFcBwd {
   float *d_h, *d_a3;            // out: [Bn][512] masked by h > 0, [Bn][49][64] masked by a3 > 0
   float *g_a_w, *g_v_w, *g_fc_w, *g_fc_b;  // out: gradients, state_dict layout
   float* s32;                   // the column sums of d_ha, for head_bias_grad after the queued sums have run
-  bool g3 = false, g6 = false;  // the GEMMs on bf16 MFMA with two-part (bf16x2) / three-part (f32x3) operands, else f32
+  GemmArith arith;              // of the four GEMMs (ApexBwdPlan::heads_fc, learner_plan.h)
   hipEvent_t ev_dh = nullptr;   // (two lanes) d_h is ready
 };
 // s: the data-gradient chain; sw: the lane of the weight gradients (== s: one lane).  The two bias gradients' column
 // sums are queued on `sums` for the launch pair at the end of trunk_backward.
-void head_fc_backward(const HeadFcBwd& t, hipStream_t s, hipStream_t sw, ColsumJobs* sums) {
+int head_fc_backward(const HeadFcBwd& t, hipStream_t s, hipStream_t sw, ColsumJobs* sums) {
   const int Bn = t.Bn;
   // heads: d_h, dWh, db
   {
     ProbHeadDgrad p{};
     p.M = Bn, p.N = 512, p.K = 32;
     p.d_ha = t.d_ha, p.a_w = t.a_w, p.v_w = t.v_w, p.h = t.h, p.d_h = t.d_h, p.A = t.A;
-    if (t.g3) (void)gemm3::launch_gemm<Tile3Dgrad>(p, 1, s, "learner_dgrad_heads");
-    else if (t.g6) (void)gemm3::launch_gemm<Tile6Dgrad>(p, 1, s, "learner_dgrad_heads");
-    else launch_gemm<TileDgrad>(p, 1, s, "learner_dgrad_heads");
+    if (int rc = launch_gemm_as<SetDgrad>(t.arith, p, 1, s, "learner_dgrad_heads")) return rc;
   }
   {
     ProbHeadWgrad p{};
     p.M = 32, p.N = 512, p.K = Bn;
     p.d_ha = t.d_ha, p.h = t.h, p.g_a_w = t.g_a_w, p.g_v_w = t.g_v_w, p.A = t.A;
-    if (t.g3) (void)gemm3::launch_gemm<Tile3W32>(p, 1, sw, "learner_wgrad_heads");
-    else if (t.g6) (void)gemm3::launch_gemm<Tile6W32>(p, 1, sw, "learner_wgrad_heads");
-    else launch_gemm<TileW32>(p, 1, sw, "learner_wgrad_heads");
+    if (int rc = launch_gemm_as<SetW32>(t.arith, p, 1, sw, "learner_wgrad_heads")) return rc;
   }
   sums->add(t.d_ha, Bn, 32, t.s32);
   if (sw != s) lane_dep(t.ev_dh, s, sw);  // d_h is ready
@@ -140,19 +136,16 @@ void head_fc_backward(const HeadFcBwd& t, hipStream_t s, hipStream_t sw, ColsumJ
     ProbFcDgrad p{};
     p.M = Bn, p.N = 3136, p.K = 512;
     p.d_h = t.d_h, p.wfcp = t.wfcp, p.a3 = t.a3, p.d_a3 = t.d_a3;
-    if (t.g3) (void)gemm3::launch_gemm<Tile3Dgrad>(p, 1, s, "learner_dgrad_fc");
-    else if (t.g6) (void)gemm3::launch_gemm<Tile6Dgrad>(p, 1, s, "learner_dgrad_fc");
-    else launch_gemm<TileDgrad>(p, 1, s, "learner_dgrad_fc");
+    if (int rc = launch_gemm_as<SetDgrad>(t.arith, p, 1, s, "learner_dgrad_fc")) return rc;
   }
   {
     ProbFcWgrad p{};
     p.M = 512, p.N = 3136, p.K = Bn;
     p.d_h = t.d_h, p.a3 = t.a3, p.g_fc_w = t.g_fc_w;
-    if (t.g3) (void)gemm3::launch_gemm<Tile3Wfc>(p, 1, sw, "learner_wgrad_fc");
-    else if (t.g6) (void)gemm3::launch_gemm<Tile6Wfc>(p, 1, sw, "learner_wgrad_fc");
-    else launch_gemm<TileWfc>(p, 1, sw, "learner_wgrad_fc");
+    if (int rc = launch_gemm_as<SetWfc>(t.arith, p, 1, sw, "learner_wgrad_fc")) return rc;
   }
   sums->add(t.d_h, Bn, 512, t.g_fc_b);
+  return RELA_OK;
 }
 }  // namespace
 
@@ -411,9 +404,8 @@ extern "C" int rela_apex_learner_grad(rela_apex_learner* l, void* stream_) {
   for (int i = 0; i < kFFNetSegs; ++i) Gm[i] = l->G + l->off[i];
 
   ColsumJobs sums;  // the five bias gradients: queued here, one launch pair at the end of trunk_backward
-  const bool g3 = rela_ffnet_precision(l->online) == 1 && gemm_bf16x3_on();  // bf16x2: the GEMMs on bf16 MFMA too
-  const bool g6 = rela_ffnet_precision(l->online) == 2;  // f32x3: ... with three-part operands (f32 accuracy)
   const bool lanes = l->side != nullptr;
+  const ApexBwdPlan plan = plan_apex_backward(rela_ffnet_precision(l->online), lanes);
   hipStream_t sw = lanes ? l->side : s;  // the weight-gradient lane
   if (lanes) lane_dep(l->ev[2], s, sw);  // d_ha and the forward's activations are ready
 
@@ -421,23 +413,22 @@ extern "C" int rela_apex_learner_grad(rela_apex_learner* l, void* stream_) {
     HeadFcBwd t{};
     t.Bn = Bn, t.A = A, t.d_ha = l->d_ha, t.h = w.h, t.a3 = w.a3, t.a_w = P.a_w, t.v_w = P.v_w, t.wfcp = l->wfcp;
     t.d_h = l->d_h, t.d_a3 = l->d_a3, t.g_a_w = Gm[10], t.g_v_w = Gm[8], t.g_fc_w = Gm[6], t.g_fc_b = Gm[7], t.s32 = l->s32;
-    t.g3 = g3, t.g6 = g6, t.ev_dh = l->ev[3];
-    head_fc_backward(t, s, sw, &sums);
+    t.arith = plan.heads_fc, t.ev_dh = l->ev[3];
+    if (int rc = head_fc_backward(t, s, sw, &sums)) return rc;
   }
   {
     TrunkBwd t{};
     t.Bn = Bn, t.obs = obs, t.a1 = w.a1, t.a2 = w.a2, t.d_a3 = l->d_a3, t.d_a2 = l->d_a2, t.d_a1 = l->d_a1;
     t.part = l->part, t.cpart = l->cpart, t.w2p = l->w2p, t.w3p = l->w3p;
     t.g_c1w = Gm[0], t.g_c1b = Gm[1], t.g_c2w = Gm[2], t.g_c2b = Gm[3], t.g_c3w = Gm[4], t.g_c3b = Gm[5];
-    t.fast = rela_ffnet_precision(l->online) == 1;
-    t.emu = g6;
+    t.plan = plan.trunk.plan(Bn);
     if (lanes) {
       t.side = sw, t.ev_da3 = l->ev[4], t.ev_da2 = l->ev[5], t.ev_side = l->ev[6];
       t.part_side = l->part_side, t.cpart_side = l->cpart_side;
-      if (t.fast) t.frag2 = l->frag2, t.frag3 = l->frag3;
+      if (t.plan.dgrad_bf16) t.frag2 = l->frag2, t.frag3 = l->frag3;
       t.s32 = l->s32, t.A = A, t.g_a_b = Gm[11], t.g_v_b = Gm[9];
     }
-    trunk_backward(t, s, &sums);
+    if (int rc = trunk_backward(t, s, &sums)) return rc;
     if (!lanes) hipLaunchKernelGGL(head_bias_grad, dim3(1), dim3(32), 0, s, (const float*)l->s32, A, Gm[11], Gm[9]);
   }
   RELA_LAUNCH_CHECK();
@@ -485,18 +476,17 @@ extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fa
   t.Bn = frames, t.obs = obs, t.a1 = a1, t.a2 = a2, t.d_a3 = d_a3, t.d_a2 = d_a2, t.d_a1 = d_a1;
   t.w2p = w2p, t.w3p = w3p;
   t.g_c1w = g_c1w, t.g_c1b = g_c1b, t.g_c2w = g_c2w, t.g_c2b = g_c2b, t.g_c3w = g_c3w, t.g_c3b = g_c3b;
-  t.fast = mode == 1;
-  if (fast_wgrad_min_frames > 0) t.fast_wgrad_min_frames = fast_wgrad_min_frames;
+  t.plan = plan_apex_backward(mode, lanes != 0)
+               .trunk.plan(frames, fast_wgrad_min_frames > 0 ? fast_wgrad_min_frames : kFastWgradMinFrames);
   if (int rc = sc.mem.alloc(&t.part, kTrunkPartFloats, false)) return rc;
   if (int rc = sc.mem.alloc(&t.cpart, cpart_floats, false)) return rc;
-  t.emu = mode == 2;
   if (lanes) {  // as rela_apex_learner_grad fills it; else one lane, as the R2D2 learner (and RELA_LEARNER_LANES=1)
     RELA_HIP(hipStreamCreateWithFlags(&sc.side, hipStreamNonBlocking));
     for (hipEvent_t& e : sc.ev) RELA_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     t.side = sc.side, t.ev_da3 = sc.ev[0], t.ev_da2 = sc.ev[1], t.ev_side = sc.ev[2];
     if (int rc = sc.mem.alloc(&t.part_side, kTrunkPartFloats, false)) return rc;
     if (int rc = sc.mem.alloc(&t.cpart_side, cpart_floats, false)) return rc;
-    if (t.fast) {  // the data-gradient weight fragments packed ahead, as repack() does
+    if (t.plan.dgrad_bf16) {  // the data-gradient weight fragments packed ahead, as repack() does
       uint8_t *frag2 = nullptr, *frag3 = nullptr;
       if (int rc = sc.mem.alloc(&frag2, dgfast::kFrag2Bytes, false)) return rc;
       if (int rc = sc.mem.alloc(&frag3, dgfast::kFrag3Bytes, false)) return rc;
@@ -504,11 +494,12 @@ extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fa
       t.frag2 = frag2, t.frag3 = frag3;
     }
   }
-  trunk_backward(t, s);
+  const int rc = trunk_backward(t, s);
   const hipError_t launched = hipGetLastError();
   // (the scratch goes away with `sc`: both lanes must be done with it whatever happened)
   const hipError_t done = hipStreamSynchronize(s);
   if (sc.side) (void)hipStreamSynchronize(sc.side);
+  if (rc != RELA_OK) return rc;
   RELA_HIP(launched);
   RELA_HIP(done);
   return RELA_OK;
@@ -563,16 +554,19 @@ extern "C" int rela_debug_head_fc_backward(int batch, int A, int mode, int lanes
   HeadFcBwd t{};
   t.Bn = batch, t.A = A, t.d_ha = d_ha, t.h = h, t.a3 = a3, t.a_w = fc_a_w, t.v_w = fc_v_w, t.wfcp = wfcp;
   t.d_h = d_h, t.d_a3 = d_a3, t.g_a_w = g_fc_a_w, t.g_v_w = g_fc_v_w, t.g_fc_w = g_fc_w, t.g_fc_b = g_fc_b, t.s32 = s32;
-  t.g3 = mode == 1 && gemm_bf16x3_on(), t.g6 = mode == 2, t.ev_dh = sc.ev[1];
+  t.arith = plan_apex_backward(mode, lanes != 0).heads_fc, t.ev_dh = sc.ev[1];
   ColsumJobs sums;
-  head_fc_backward(t, s, sw, &sums);
-  colsum_multi_launch(sums, cpart, sw);
-  hipLaunchKernelGGL(head_bias_grad, dim3(1), dim3(32), 0, sw, (const float*)s32, A, g_fc_a_b, g_fc_v_b);
+  const int rc = head_fc_backward(t, s, sw, &sums);
+  if (rc == RELA_OK) {
+    colsum_multi_launch(sums, cpart, sw);
+    hipLaunchKernelGGL(head_bias_grad, dim3(1), dim3(32), 0, sw, (const float*)s32, A, g_fc_a_b, g_fc_v_b);
+  }
   if (lanes) lane_dep(sc.ev[2], sw, s);
   const hipError_t launched = hipGetLastError();
   // (the scratch goes away with `sc`: both lanes must be done with it whatever happened)
   const hipError_t done = hipStreamSynchronize(s);
   if (sc.side) (void)hipStreamSynchronize(sc.side);
+  if (rc != RELA_OK) return rc;
   RELA_HIP(launched);
   RELA_HIP(done);
   return RELA_OK;

@@ -1,18 +1,20 @@
 // learner_common.h -- pieces shared by the two hand-written learner steps (learner.hip: Ape-X /
-// AtariFFNet; learner_r2d2.hip: R2D2 / AtariLSTMNet): the gemm_lds problem descriptions of the conv trunk's
-// backward pass, split-K reduction, column sums, global-norm clipping and the optimisers, and -- host side, at the
+// AtariFFNet; learner_r2d2.hip: R2D2 / AtariLSTMNet): the tiles of their GEMMs and the one dispatch that obeys the
+// backward plan (learner_plan.h), the gemm_lds problem descriptions of the conv trunk's backward pass, split-K reduction, column sums, global-norm clipping and the optimisers, and -- host side, at the
 // end -- LearnerCore, the base of rela_apex_learner and rela_r2d2_learner: the flat parameter / gradient /
 // optimiser-state store and what the entry points do with it (its device buffers belong to a DevBuffers, common.h).
 // Everything sits in an anonymous namespace: each translation unit gets its own copy of the kernels.
 #pragma once
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
 #include "ffnet_layout.h"
 #include "gemm_lds.h"
 #include "gemm_bf16x3.h"
+#include "learner_plan.h"
 #include "param_layout.h"
 #include "prof.h"
 #include "value_rescale.h"
@@ -27,37 +29,79 @@ namespace {
 
 using namespace gemm;
 
+// ---- the tiles of the learners' GEMMs, by shape and arithmetic --------------------------------------------------------
+// A shape's f32 tile runs on gemm_lds (f32 MFMA).  The two-part tile runs on the bf16 matrix cores (gemm_bf16x3.h: operands
+// split into bf16 hi + lo on the way into LDS, three MFMAs per product): the learners' bf16x2 mode.  The three-part tile
+// (PARTS = 3, six products) has f32 accuracy on the bf16 MFMA: the f32x3 modes.
 using TileDgrad = TileCfg<128, 64, 4, 2, false>;  // M = batch rows, A k-contiguous
+using Tile3Dgrad = gemm3::TileCfg<128, 64, 4, 2, false>;
+using Tile6Dgrad = gemm3::TileCfg<128, 64, 4, 2, false, 3>;
 using TileWfc = TileCfg<128, 64, 4, 2, true>;     // fc weight gradient (M = 512 units)
-using TileW64 = TileCfg<64, 64, 2, 4, true>;      // conv2 / conv3 weight gradients (M = 64 channels)
+using Tile3Wfc = gemm3::TileCfg<128, 64, 4, 2, true>;
+using Tile6Wfc = gemm3::TileCfg<128, 64, 4, 2, true, 3>;
+// conv2 / conv3 weight gradients (M = 64 channels).  The 64 x 64 tiles stay at S = 1 (stages of one chunk per barrier): at
+// S = 2 the f32 tile measured 4 us (512 frames) and 3 - 11 us (5,312) BEHIND; the three-part tile then fits one block on a CU
+// instead of two and conv2 / conv3 measured 8 / 7 us behind.
+using TileW64 = TileCfg<64, 64, 2, 4, true>;
+using Tile3W64 = gemm3::TileCfg<64, 64, 2, 4, true>;
+using Tile6W64 = gemm3::TileCfg<64, 64, 2, 4, true, 3>;
 using TileW32 = TileCfg<32, 64, 2, 4, true>;      // head weight gradients (M = 32)
-// conv1's weight gradient: stages of FOUR chunks per barrier (gemm_lds.h, S; 128 KB of dynamic LDS, one block per CU as
-// before: 256 blocks).  Measured alone at 512 / 5,312 frames: S = 1 60 / 627 us, S = 2 53 / 590, S = 4 54 / 553.
-// conv2 / conv3 (TileW64) stay at S = 1: at S = 2 they measured 4 us (512 frames) and 3 - 11 us (5,312) BEHIND.
+using Tile3W32 = gemm3::TileCfg<32, 64, 2, 4, true>;
+using Tile6W32 = gemm3::TileCfg<32, 64, 2, 4, true, 3>;
+// conv1's weight gradient in f32: stages of FOUR chunks per barrier (gemm_lds.h, S; 128 KB of dynamic LDS, one block per CU
+// as before: 256 blocks).  Measured alone at 512 / 5,312 frames: S = 1 60 / 627 us, S = 2 53 / 590, S = 4 54 / 553.
 using TileW1 = TileCfg<32, 64, 2, 4, true, 4>;
-// conv3's / conv2's data gradients (N = 64 / 32 input channels): 64 rows per block measured ahead of 128 (and of 256 for
-// conv2) at 512 frames -- K is only 576 / 256, so more and smaller blocks hide more of each block's fixed costs
+// ... in three parts: the B operand is the u8 frame, exact in ONE bf16 part -- its mid and lo parts would be zeros --
+// at a stage of TWO chunks: 45 -> 37 us alone at 512 frames.  S = 4 measured 36 us but takes 112 KB of LDS and 138
+// registers: a second block no longer fits the CU (tests/test_trunk_backward_resources_cpu.py); S = 2 keeps 56 KB, 72 registers.
+// (The bf16x2 mode runs wgrad_conv1_bf16.h instead.)
+using Tile6W32U8 = gemm3::SinglePartB<gemm3::TileCfg<32, 64, 2, 4, true, 3, 2>>;
+// conv3's / conv2's data gradients (N = 64 / 32 input channels), f32 in every mode: 64 rows per block measured ahead of 128
+// (and of 256 for conv2) at 512 frames -- K is only 576 / 256, so more and smaller blocks hide more of each block's fixed costs
 using TileDgrad3 = TileCfg<64, 64, 2, 4, false>;
 using TileDgrad2 = TileCfg<64, 32, 4, 2, false>;
-// the same shapes on the bf16 matrix cores (gemm_bf16x3.h: operands split into bf16 hi + lo on the way into LDS, three
-// MFMAs per product): the learners' bf16x2 mode.
-using Tile3Dgrad = gemm3::TileCfg<128, 64, 4, 2, false>;
-using Tile3Wfc = gemm3::TileCfg<128, 64, 4, 2, true>;
-using Tile3W64 = gemm3::TileCfg<64, 64, 2, 4, true>;
-using Tile3W32 = gemm3::TileCfg<32, 64, 2, 4, true>;
-inline bool gemm_bf16x3_on() { return true; }
-// ... and with every operand as THREE bf16 parts, six products (gemm_bf16x3.h, PARTS = 3): f32 accuracy on the bf16 MFMA --
-// the learners' f32x3 mode
-using Tile6Dgrad = gemm3::TileCfg<128, 64, 4, 2, false, 3>;
-using Tile6Wfc = gemm3::TileCfg<128, 64, 4, 2, true, 3>;
-using Tile6W64 = gemm3::TileCfg<64, 64, 2, 4, true, 3>;
-using Tile6W32 = gemm3::TileCfg<32, 64, 2, 4, true, 3>;
-// conv1's weight gradient: the B operand is the u8 frame, exact in ONE bf16 part -- its mid and lo parts would be zeros
-// ... at a stage of TWO chunks: 45 -> 37 us alone at 512 frames.  S = 4 measured 36 us but takes 112 KB of LDS and 138
-// registers: a second block no longer fits the CU (tests/test_trunk_backward_resources_cpu.py); S = 2 keeps 56 KB, 72 registers.
-// The 64 x 64 tiles stay at S = 1: at S = 2 one block fits a CU instead of two and conv2 / conv3 measured 8 / 7 us behind.
-using Tile6W32U8 = gemm3::SinglePartB<gemm3::TileCfg<32, 64, 2, 4, true, 3, 2>>;
+// the R2D2 learner's (learner_r2d2.hip)
+using TileRows = TileCfg<128, 64, 4, 2, false>;  // M = many rows, A k-contiguous
+using TileRec = TileCfg<64, 64, 2, 4, false>;    // M = batch rows of one time step
+using TileWg = TileCfg<128, 64, 4, 2, true>;     // weight gradients, M = 2048 gate rows
+using TileW32r = TileCfg<32, 64, 2, 4, true>;    // head weight gradients (M = 32)
+// The backward GEMMs of its mode 3 (f32x3_bwd).  64 x 64 tiles (100 registers, 60 KB of LDS: two blocks per CU) measured
+// ahead of the 128 x 64 tiles of TileRows / TileWg (172 registers, 84 KB: one block) at 5,312 training rows: dW_ih 0.66 ->
+// 0.58 ms, dW_hh 0.15 -> 0.10, d_a3 0.61 -> 0.58.  The conv weight gradients run one block per CU at their f32 split counts
+// (conv3 0.28 ms against 0.24 in f32), two at twice the splits (learner_plan.h: kX6SplitMul).
+using Tile6Rows = gemm3::TileCfg<64, 64, 2, 4, false, 3>;
+using Tile6Wg = Tile6W64;
 
+// The tiles of one GEMM shape: f32 | two-part | three-part.  void: that arithmetic never reaches the shape -- no kernel is
+// instantiated for it, and a plan that asks for it is an internal error.
+template <class F32, class X2, class X3>
+struct TileSet {
+  using f32 = F32;
+  using x2 = X2;
+  using x3 = X3;
+};
+using SetDgrad = TileSet<TileDgrad, Tile3Dgrad, Tile6Dgrad>;  // dgrad rows (heads, fc)
+using SetWfc = TileSet<TileWfc, Tile3Wfc, Tile6Wfc>;          // fc weight gradient
+using SetW64 = TileSet<TileW64, Tile3W64, Tile6W64>;          // 64-channel weight gradients (conv2, conv3)
+using SetW32 = TileSet<TileW32, Tile3W32, Tile6W32>;          // 32-row head weight gradients
+using SetW1 = TileSet<TileW1, void, Tile6W32U8>;              // conv1 weight gradient
+using SetWg = TileSet<TileWg, void, Tile6Wg>;                 // R2D2: dW_hh, dW_ih
+using SetRows = TileSet<TileRows, void, Tile6Rows>;           // R2D2: the input-side data gradient
+using SetSeqHeadRows = TileSet<TileRows, void, void>;         // R2D2: the heads' data gradient and ...
+using SetSeqHeadW32 = TileSet<TileW32r, void, void>;          // ... weight gradients (measured slower in three parts)
+
+// the one way a learner GEMM is launched: the slot of `arith` in the shape's set (split-K, stream, names as launch_gemm)
+template <class Set, class P>
+int launch_gemm_as(GemmArith arith, const P& p, int splits, hipStream_t s, const char* name) {
+  if constexpr (!std::is_void_v<typename Set::f32>)
+    if (arith == kArithF32) return launch_gemm<typename Set::f32>(p, splits, s, name), RELA_OK;
+  if constexpr (!std::is_void_v<typename Set::x2>)
+    if (arith == kArithBf16x2) return gemm3::launch_gemm<typename Set::x2>(p, splits, s, name);
+  if constexpr (!std::is_void_v<typename Set::x3>)
+    if (arith == kArithF32x3) return gemm3::launch_gemm<typename Set::x3>(p, splits, s, name);
+  set_last_error("%s: no tile for arithmetic %d (internal error: the plan and the tile sets disagree)", name, (int)arith);
+  return RELA_ESTATE;
+}
 
 // d_h[b][u] = relu'(h) * sum_k d_ha[b][k] * Wh[k][u]      Wh rows: 0..A-1 = fc_a.weight, 31 = fc_v.weight
 struct ProbHeadDgrad : ProbBase {
@@ -601,19 +645,18 @@ __global__ void adam_update(float* __restrict__ p, const float* __restrict__ g, 
 
 
 // ---- backward pass of the conv trunk (net.{0,2,4}), shared by both learners ---------------------
-constexpr int kSplitW3 = 28, kSplitW2 = 27, kSplitW1 = 64;
+// (which kernels run, their split counts and thresholds: plan_trunk_backward, learner_plan.h)
 // the largest partial buffer: conv3's split-K tiles, or one tile per block of the bf16 conv1 ([32][256]) / conv2
 // ([64][512]) gradients
 constexpr size_t kTrunkPartFloats = (size_t)w3fast::kMaxBlocks * 64 * 576;
 static_assert(kTrunkPartFloats * 4 >= dgfast::kFrag3Bytes && kTrunkPartFloats * 4 >= dgfast::kFrag2Bytes, "frag scratch");
-static_assert(kTrunkPartFloats >= (size_t)kSplitW3 * 8 * 64 * 576, "part size (split multiplier up to 8)");
+static_assert(kTrunkPartFloats >= (size_t)kSplitW3 * kMaxSplitMul * 64 * 576, "part size (split multiplier up to kMaxSplitMul)");
 static_assert(kTrunkPartFloats >= (size_t)kSplitW3 * 64 * 576 && kTrunkPartFloats >= (size_t)w1fast::kMaxBlocks * 32 * 256 &&
                   kTrunkPartFloats >= (size_t)w2fast::kMaxBlocks * 64 * 512,
               "part size");
 static_assert(kSplitW3 * 64 * 576 >= kSplitW2 * 64 * 512 && kSplitW3 * 64 * 576 >= kSplitW1 * 32 * 256, "part size");
-constexpr int kMaxSplitMul = 8;  // of TrunkBwd::emu_split_mul: what the assertions above leave room for
+static_assert(kWgrad1Blocks == w1fast::kMaxBlocks && kWgrad1BlocksTwoLanes <= w1fast::kMaxBlocks, "the plan's block caps");
 
-constexpr int kFastWgradMinFrames = 2048;
 // the most frames of one trunk_backward call: the data gradients put frames * 100 / 64 (conv2) and frames * 81 / 64
 // (conv3) tiles on the grid's y axis
 constexpr int kTrunkMaxFrames = 32768;
@@ -629,17 +672,11 @@ struct TrunkBwd {
   float* cpart;        // scratch, kColsumBlocks * 512
   const float *w2p, *w3p;  // conv2 / conv3 weights in dgrad k order (permute_weight_at, ffnet_layout.h)
   float *g_c1w, *g_c1b, *g_c2w, *g_c2b, *g_c3w, *g_c3b;  // gradients, state_dict layout
-  bool fast = false;   // the learner's bf16x2 mode: conv1's weight gradient on bf16 MFMA
-  // the f32x3 mode: the weight-gradient GEMMs below (contraction over batch x positions) on the bf16 MFMA with three-part
-  // operands, f32 accuracy (r4 at 512 frames, us f32 -> three-part: conv3 49 -> 35, conv2 63 -> 52, conv1 110 -> 102)
-  bool emu = false;
-  // (with emu) multipliers on the split counts of conv1's / conv2's / conv3's three-part weight gradients: conv1 at every
-  // frame count, conv2 / conv3 above 1,024 frames (below, their splits are tripled already).  Another split count is another
-  // association of the sum, so both learners' existing modes keep 1; the R2D2 learner's mode 3 sets its own.
-  int emu_split_mul[3] = {1, 1, 1};
-  // frames from which `fast` runs conv2's / conv3's weight gradients on wgrad_conv{2,3}_bf16 (both learners keep the
-  // default; rela_debug_trunk_backward lowers it so that small ragged frame counts reach those kernels)
-  int fast_wgrad_min_frames = kFastWgradMinFrames;
+  // What runs: the learner's TrunkArith for Bn frames (learner_plan.h).  bf16x2: the weight gradients on the dedicated bf16
+  // kernels (conv2 / conv3 from kFastWgradMinFrames frames), the data gradients on dgrad_conv_bf16.h.  f32x3: the weight-gradient
+  // GEMMs (contraction over batch x positions) on the bf16 MFMA with three-part operands, f32 accuracy (r4 at 512 frames, us
+  // f32 -> three-part: conv3 49 -> 35, conv2 63 -> 52, conv1 110 -> 102).
+  TrunkBwdPlan plan;
   // Two-lane form (the Ape-X learner): conv3's and conv2's weight gradients, and the column sums of every tensor that
   // exists by then (the caller's pending jobs, d_a3, d_a2), run on `side` next to the data-gradient chain on the
   // caller's stream; the caller's stream waits for the side lane before trunk_backward returns.  Every kernel computes
@@ -679,43 +716,43 @@ inline void colsum_launch(const float* src, int64_t rows, int C, float* cpart, f
   hipLaunchKernelGGL(colsum_final, dim3(C / 4), dim3(kColsumBlocks), 0, s, (const float*)cpart, C, out);
 }
 
+// One conv weight gradient as its WgradPlan says: the dedicated bf16 kernel (`fast`: (int* blocks) -> its launch) or the
+// split-K GEMM of Problem `p` in the plan's arithmetic, into partial tiles p.part [slices][p.M][p.N]; then reduce_splits sums
+// the slices in order into `out` (state_dict layout, `red`: kRedConv1 / 2 / 3).
+template <class Set, class P, class Fast>
+int conv_wgrad(const WgradPlan& w, const P& p, Fast fast, int red, float* out, hipStream_t s, const char* name) {
+  int slices = w.splits;
+  if (w.bf16_kernel) {
+    ProfScope prof(name, s);
+    (void)fast(&slices);
+  } else if (int rc = launch_gemm_as<Set>(w.arith, p, slices, s, name)) {
+    return rc;
+  }
+  hipLaunchKernelGGL(reduce_splits, dim3(ceil_div(p.M * p.N, 256)), dim3(256), 0, s, (const float*)p.part, slices, p.M, p.N,
+                     red, out);
+  return RELA_OK;
+}
+
 // `jobs`: the caller's pending column sums; the three bias gradients of the trunk are queued behind them and the
 // whole queue goes out in one launch pair at the end (t.cpart: kColsumBlocks * (sum of all queued C) floats)
-inline void trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending = nullptr) {
+inline int trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending = nullptr) {
   const int Bn = t.Bn;
+  const TrunkBwdPlan& plan = t.plan;
   ColsumJobs own;
   ColsumJobs& jobs = pending ? *pending : own;
   const bool lanes = t.side != nullptr;
   hipStream_t sw = lanes ? t.side : s;  // the lane of conv3's / conv2's weight gradients
   float* partw = lanes ? t.part_side : t.part;
   if (lanes) lane_dep(t.ev_da3, s, sw);  // d_a3 (and everything the pending jobs read) is ready
-  // conv2 / conv3 on bf16 MFMA only for many frames (R2D2: T * B): at 512 frames their per-block fixed costs (LDS
-  // zero fill, 256 partial tiles of 128 / 144 KB for reduce_splits) cancel the gain (Ape-X: step 0.83 -> 0.91 ms)
-  const bool fast23 = t.fast && Bn >= t.fast_wgrad_min_frames;
-  if (fast23) {  // conv3's weight gradient on bf16 MFMA (wgrad_conv3_bf16.h)
-    int blocks = 0;
-    {
-      ProfScope prof("learner_wgrad_conv3", sw);
-      (void)w3fast::launch(t.a2, t.d_a3, Bn, partw, sw, &blocks);
-    }
-    hipLaunchKernelGGL(reduce_splits, dim3(ceil_div(64 * 576, 256)), dim3(256), 0, sw, (const float*)partw, blocks, 64,
-                       576, kRedConv3, t.g_c3w);
-  } else {  // conv3: dW3, db3, d_a2
+  {  // conv3: dW3, db3, d_a2
     ProbW3 p{};
     p.M = 64, p.N = 576, p.K = Bn * 49;
     p.d_out = t.d_a3, p.in = t.a2, p.part = partw;
-    // (a few hundred frames: 3 x the splits = 3-4 blocks per CU instead of one; a block alone on its CU waits out
-    // every chunk's load latency with two waves per SIMD)
-    static const int mul = 3  /* (<= 8: what kTrunkPartFloats holds; flat between 2 and 4 in the r3 sweep) */;
-    const int split3 = Bn <= 1024 ? kSplitW3 * mul : kSplitW3 * (t.emu ? t.emu_split_mul[2] : 1);
-    if (t.fast && gemm_bf16x3_on()) (void)gemm3::launch_gemm<Tile3W64>(p, split3, sw, "learner_wgrad_conv3");
-    else if (t.emu) (void)gemm3::launch_gemm<Tile6W64>(p, split3, sw, "learner_wgrad_conv3");
-    else launch_gemm<TileW64>(p, split3, sw, "learner_wgrad_conv3");
-    hipLaunchKernelGGL(reduce_splits, dim3(ceil_div(64 * 576, 256)), dim3(256), 0, sw, (const float*)partw, split3, 64,
-                       576, kRedConv3, t.g_c3w);
+    auto fast = [&](int* blocks) { return w3fast::launch(t.a2, t.d_a3, Bn, partw, sw, blocks); };
+    if (int rc = conv_wgrad<SetW64>(plan.w3, p, fast, kRedConv3, t.g_c3w, sw, "learner_wgrad_conv3")) return rc;
   }
   jobs.add(t.d_a3, (int64_t)Bn * 49, 64, t.g_c3b);
-  if (t.fast) {  // transposed convolution on bf16 MFMA, ReLU mask fused, no column buffer (dgrad_conv_bf16.h)
+  if (plan.dgrad_bf16) {  // transposed convolution on bf16 MFMA, ReLU mask fused, no column buffer (dgrad_conv_bf16.h)
     ProfScope prof("learner_dgrad_conv3", s);
     (void)dgfast::launch_conv3(t.d_a3, t.w3p, t.a2, t.d_a2, Bn, t.part, s, t.frag3);
   } else {
@@ -725,25 +762,12 @@ inline void trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending
     launch_gemm<TileDgrad3>(p, 1, s, "learner_dgrad_conv3");
   }
   if (lanes) lane_dep(t.ev_da2, s, sw);  // d_a2 is ready
-  if (fast23) {  // conv2's weight gradient on bf16 MFMA (wgrad_conv2_bf16.h)
-    int blocks = 0;
-    {
-      ProfScope prof("learner_wgrad_conv2", sw);
-      (void)w2fast::launch(t.a1, t.d_a2, Bn, partw, sw, &blocks);
-    }
-    hipLaunchKernelGGL(reduce_splits, dim3(ceil_div(64 * 512, 256)), dim3(256), 0, sw, (const float*)partw, blocks, 64,
-                       512, kRedConv2, t.g_c2w);
-  } else {  // conv2: dW2, db2, d_a1
+  {  // conv2: dW2, db2, d_a1
     ProbW2 p{};
     p.M = 64, p.N = 512, p.K = Bn * 81;
     p.d_out = t.d_a2, p.in = t.a1, p.part = partw;
-    static const int mul = 3  /* (<= 8: what kTrunkPartFloats holds; flat between 2 and 4 in the r3 sweep) */;
-    const int split2 = Bn <= 1024 ? kSplitW2 * mul : kSplitW2 * (t.emu ? t.emu_split_mul[1] : 1);
-    if (t.fast && gemm_bf16x3_on()) (void)gemm3::launch_gemm<Tile3W64>(p, split2, sw, "learner_wgrad_conv2");
-    else if (t.emu) (void)gemm3::launch_gemm<Tile6W64>(p, split2, sw, "learner_wgrad_conv2");
-    else launch_gemm<TileW64>(p, split2, sw, "learner_wgrad_conv2");
-    hipLaunchKernelGGL(reduce_splits, dim3(ceil_div(64 * 512, 256)), dim3(256), 0, sw, (const float*)partw, split2, 64,
-                       512, kRedConv2, t.g_c2w);
+    auto fast = [&](int* blocks) { return w2fast::launch(t.a1, t.d_a2, Bn, partw, sw, blocks); };
+    if (int rc = conv_wgrad<SetW64>(plan.w2, p, fast, kRedConv2, t.g_c2w, sw, "learner_wgrad_conv2")) return rc;
   }
   jobs.add(t.d_a2, (int64_t)Bn * 81, 64, t.g_c2b);
   if (lanes) {  // the side lane ends here: the column sums of everything but d_a1, then the head biases
@@ -751,7 +775,7 @@ inline void trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending
     if (t.s32) hipLaunchKernelGGL(head_bias_grad, dim3(1), dim3(32), 0, sw, t.s32, t.A, t.g_a_b, t.g_v_b);
     jobs.n = 0;
   }
-  if (t.fast) {
+  if (plan.dgrad_bf16) {
     ProfScope prof("learner_dgrad_conv2", s);
     (void)dgfast::launch_conv2(t.d_a2, t.w2p, t.a1, t.d_a1, Bn, t.part, s, t.frag2);
   } else {
@@ -760,29 +784,17 @@ inline void trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending
     p.d_out = t.d_a2, p.wp = t.w2p, p.a1 = t.a1, p.d_a1 = t.d_a1;
     launch_gemm<TileDgrad2>(p, 1, s, "learner_dgrad_conv2");
   }
-  if (t.fast) {  // conv1 on bf16 MFMA (wgrad_conv1_bf16.h): exact u8 frames x (hi + lo) gradients
-    int blocks = 0;
-    {
-      ProfScope prof("learner_wgrad_conv1", s);
-      (void)w1fast::launch(t.obs, t.d_a1, Bn, t.part, s, &blocks, lanes ? 128 : w1fast::kMaxBlocks);
-    }
-    hipLaunchKernelGGL(reduce_splits, dim3(ceil_div(32 * 256, 256)), dim3(256), 0, s, (const float*)t.part, blocks, 32,
-                       256, kRedConv1, t.g_c1w);
-  } else {  // conv1: dW1, db1 (no gradient flows into the frames)
+  {  // conv1: dW1, db1 (no gradient flows into the frames)
     ProbW1 p{};
     p.M = 32, p.N = 256, p.K = Bn * 400;
     p.d_out = t.d_a1, p.obs = t.obs, p.part = t.part;
-    // (kSplitW1 splits at every frame count: 3-4 x the splits at <= 1,024 frames, as conv3 / conv2 above, measured 105 ->
-    // 69-75 us at 512 frames, but another split changes the association of g_c1w and with it the bits of a step)
-    const int split1 = kSplitW1 * (t.emu ? t.emu_split_mul[0] : 1);
-    if (t.emu) (void)gemm3::launch_gemm<Tile6W32U8>(p, split1, s, "learner_wgrad_conv1");
-    else launch_gemm<TileW1>(p, split1, s, "learner_wgrad_conv1");
-    hipLaunchKernelGGL(reduce_splits, dim3(ceil_div(32 * 256, 256)), dim3(256), 0, s, (const float*)t.part, split1, 32,
-                       256, kRedConv1, t.g_c1w);
+    auto fast = [&](int* blocks) { return w1fast::launch(t.obs, t.d_a1, Bn, t.part, s, blocks, plan.w1_max_blocks); };
+    if (int rc = conv_wgrad<SetW1>(plan.w1, p, fast, kRedConv1, t.g_c1w, s, "learner_wgrad_conv1")) return rc;
   }
   jobs.add(t.d_a1, (int64_t)Bn * 400, 32, t.g_c1b);
   colsum_multi_launch(jobs, t.cpart, s);
   if (lanes) lane_dep(t.ev_side, sw, s);
+  return RELA_OK;
 }
 
 // ---- clip_grad_norm_ + optimiser over flat parameter / gradient / state buffers -------------------

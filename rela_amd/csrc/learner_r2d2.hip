@@ -29,20 +29,7 @@ constexpr int kHid = 512, kGates = 2048, kFeat = 3136;
 constexpr int kRecSplitF = 4;  // split-K of the recurrent forward GEMM (K = 512)
 constexpr int kRecSplitB = 8;  // split-K of the recurrent backward GEMM (K = 2048)
 
-using TileRows = TileCfg<128, 64, 4, 2, false>;  // M = many rows, A k-contiguous
-using TileRec = TileCfg<64, 64, 2, 4, false>;    // M = batch rows of one time step
-using TileWg = TileCfg<128, 64, 4, 2, true>;     // weight gradients, M = 2048 gate rows
-using TileW32r = TileCfg<32, 64, 2, 4, true>;    // head weight gradients (M = 32)
-// The backward GEMMs of mode 3 (f32x3_bwd): every operand as three bf16 parts (gemm_bf16x3.h, PARTS = 3), f32 accuracy on
-// the bf16 matrix cores.  64 x 64 tiles (100 registers, 60 KB of LDS: two blocks per CU) measured ahead of the 128 x 64
-// tiles of TileRows / TileWg (172 registers, 84 KB: one block) at 5,312 training rows: dW_ih 0.66 -> 0.58 ms, dW_hh 0.15 ->
-// 0.10, d_a3 0.61 -> 0.58.  The conv weight gradients run one block per CU at their f32 split counts (conv3 0.28 ms against
-// 0.24 in f32); twice the splits: conv1 0.35 -> 0.28 ms, conv2 0.31 -> 0.25, conv3 0.28 -> 0.15 (four times: the same).
-// The heads' two GEMMs (K = 32, M = 32) are 11 / 10 us in three parts against 10 / 8 us and stay on gemm_lds.
-using Tile6Rows = gemm3::TileCfg<64, 64, 2, 4, false, 3>;
-using Tile6Wg = Tile6W64;
-constexpr int kX6SplitMul[3] = {2, 2, 2};  // conv1, conv2, conv3 (TrunkBwd::emu_split_mul)
-static_assert(kX6SplitMul[0] <= kMaxSplitMul && kX6SplitMul[1] <= kMaxSplitMul && kX6SplitMul[2] <= kMaxSplitMul, "part size");
+// (the tiles of this file's GEMMs: learner_common.h, next to the Ape-X learner's; what the backward runs: learner_plan.h)
 
 // GX[r][g] = bias[g] + sum_k a3[r][k] * wihT[k][g]
 struct ProbGateX : ProbBase {
@@ -723,33 +710,33 @@ int refresh_weight_records(rela_r2d2_learner* l, int which, hipStream_t s) {
 }
 
 // The LSTM's input side over all training rows at once, between the BPTT and trunk_backward: dW_hh, dW_ih, the gate
-// column sum (both bias gradients) and the masked d_a3.  precision as rela_r2d2_learner_set_precision: 1 runs the rec64
-// path (gemm_bf16s.h), 3 the Problems of mode 0 on gemm_bf16x3 with three-part operands, 0 and 2 gemm_lds.
+// column sum (both bias gradients) and the masked d_a3.  rec64 (R2d2BwdPlan::lstm_in_rec64, learner_plan.h): the rec64 path
+// (gemm_bf16s.h); else the three GEMMs in `arith` (R2d2BwdPlan::lstm_in): gemm_lds, or the same Problems on gemm_bf16x3 with
+// three-part operands.
 struct LstmInBwd {
   int rowsTr;
-  int precision;
+  bool rec64;
+  GemmArith arith;
   const float* dg;     // [rowsTr][2048] gate gradients
   const float* hprev;  // [rowsTr][512] h_{t-1} of every training row
   const float* a3;     // [rowsTr][49][64] relu(conv3), channel-last: operand of dW_ih and the mask of d_a3
-  const float* wihp;   // (precision != 1) W_ih in k order, k = pos * 64 + c
-  const uint8_t* wTrec;          // (precision 1) W_ih^T as rec64 [3136][32 chunks]
-  uint8_t *arec, *trec;          // (precision 1) scratch: rowsTr * 2048 * 4 and (2048 + 3136) * ceil(rowsTr / 64) * 256 bytes
+  const float* wihp;   // (GEMMs) W_ih in k order, k = pos * 64 + c
+  const uint8_t* wTrec;          // (rec64) W_ih^T as rec64 [3136][32 chunks]
+  uint8_t *arec, *trec;          // (rec64) scratch: rowsTr * 2048 * 4 and (2048 + 3136) * ceil(rowsTr / 64) * 256 bytes
   float* cpart;                  // scratch, kColsumBlocks * 2048
   float *g_w_ih, *g_w_hh, *g_b_ih, *g_b_hh;  // state_dict layout
   float* d_a3;                   // [rowsTr][49][64]
 };
 int lstm_input_backward(const LstmInBwd& t, hipStream_t s) {
   const int rowsTr = t.rowsTr;
-  const bool x6 = t.precision == 3;
   const float *DG = t.dg, *hprev = t.hprev, *a3_tr = t.a3;
-  if (t.precision != 1) {
+  if (!t.rec64) {
     ProbWhh p{};
     p.M = kGates, p.N = kHid, p.K = rowsTr;
     p.dg = DG, p.hprev = hprev, p.out = t.g_w_hh;
-    if (x6) (void)gemm3::launch_gemm<Tile6Wg>(p, 1, s, "learner_wgrad_lstm_hh");
-    else launch_gemm<TileWg>(p, 1, s, "learner_wgrad_lstm_hh");
+    if (int rc = launch_gemm_as<SetWg>(t.arith, p, 1, s, "learner_wgrad_lstm_hh")) return rc;
   }
-  if (t.precision == 1) {
+  if (t.rec64) {
     // dW_ih[g][c*49+pos] = sum_r dg[r][g] * a3[r][pos*64+c]: both operands transposed into rec64 rows of 64 r each
     // (a3's columns land in weight_ih_l0's own column order, so the result is stored row-major as it is)
     using namespace gemm16;
@@ -775,12 +762,11 @@ int lstm_input_backward(const LstmInBwd& t, hipStream_t s) {
     ProbWih p{};
     p.M = kGates, p.N = kFeat, p.K = rowsTr;
     p.dg = DG, p.a3 = a3_tr, p.out = t.g_w_ih;
-    if (x6) (void)gemm3::launch_gemm<Tile6Wg>(p, 1, s, "learner_wgrad_lstm_ih");
-    else launch_gemm<TileWg>(p, 1, s, "learner_wgrad_lstm_ih");
+    if (int rc = launch_gemm_as<SetWg>(t.arith, p, 1, s, "learner_wgrad_lstm_ih")) return rc;
   }
   colsum_launch(DG, rowsTr, kGates, t.cpart, t.g_b_ih, s);  // bias_ih_l0 and bias_hh_l0 see the same gradient
   RELA_HIP(hipMemcpyAsync(t.g_b_hh, t.g_b_ih, sizeof(float) * kGates, hipMemcpyDeviceToDevice, s));
-  if (t.precision == 1) {
+  if (t.rec64) {
     using namespace gemm16;
     {
       ProfScope prof("learner_lstm_split_rows", s);
@@ -794,8 +780,7 @@ int lstm_input_backward(const LstmInBwd& t, hipStream_t s) {
     ProbIhDgrad p{};
     p.M = rowsTr, p.N = kFeat, p.K = kGates;
     p.dg = DG, p.wihp = t.wihp, p.a3 = a3_tr, p.d_a3 = t.d_a3;
-    if (x6) (void)gemm3::launch_gemm<Tile6Rows>(p, 1, s, "learner_dgrad_lstm_ih");
-    else launch_gemm<TileRows>(p, 1, s, "learner_dgrad_lstm_ih");
+    if (int rc = launch_gemm_as<SetRows>(t.arith, p, 1, s, "learner_dgrad_lstm_ih")) return rc;
   }
   return RELA_OK;
 }
@@ -814,10 +799,9 @@ int forward_pre(rela_r2d2_learner* l, int which, int Bn, const uint8_t* obs, con
   // bf16x2 (r3): BOTH trunks on split-bf16 MFMA.  The online pass leaves a1 / a2 / a3 of the training frames for the
   // backward kernels: its conv1 records are copied out (they never leave LDS otherwise), a3's records feed the gate GEMM
   // directly, then the training rows are turned back into f32 in place (below) -- the backward differentiates the
-  // forward that really ran, ReLU pattern included.  RELA_R2D2_ONLINE_F32=1 keeps the online trunk in f32 (r2).
-  constexpr bool online_f32 = false;  // (r2's f32 online trunk in bf16x2 mode: an A/B switch until r4)
+  // forward that really ran, ReLU pattern included.
   const bool fast_target = which == 1 && l->precision == 1;
-  const bool fast_online = which == 0 && l->precision == 1 && !online_f32 && rowsAll >= 128;
+  const bool fast_online = which == 0 && l->precision == 1 && rowsAll >= 128;
   bool a3_records = false;  // a fast trunk hands a3 over as the split records the gate GEMM reads
   int rc;
   if (fast_online) {
@@ -1162,39 +1146,38 @@ void seq_td_launch(const float* q_on, const float* q_tg, const float* legal, con
 }
 
 // The head part of rela_r2d2_learner_grad over the time-major training rows (no ReLU on the LSTM's output): d_o, the two
-// weight gradients in the form of that row count, the column sum of d_ha and the two bias gradients;
-// rela_debug_seq_head_backward runs the same function.  part: kSeqHeadPartFloats, cpart: kColsumBlocks * 32, s32: 32 floats.
-// census: the tap also counts which weight-gradient form ran (the two GEMMs count themselves as gemm_lds either way).
-constexpr int kSplitHeads = 32;
-constexpr int kSeqHeadSplitRows = 1024;
+// weight gradients in the form the plan has for that row count (learner_plan.h), the column sum of d_ha and the two bias
+// gradients; rela_debug_seq_head_backward runs the same function.  part: kSeqHeadPartFloats, cpart: kColsumBlocks * 32, s32: 32
+// floats.  census: the tap also counts which weight-gradient form ran (the two GEMMs count themselves as gemm_lds either way).
 constexpr size_t kSeqHeadPartFloats = (size_t)kSplitHeads * 32 * 512;
 static_assert(kSeqHeadPartFloats <= kTrunkPartFloats, "part size");
-void seq_head_backward(int rowsTr, int A, const float* d_ha, const float* o_tr, const float* a_w, const float* v_w, float* d_o,
-                       float* g_a_w, float* g_a_b, float* g_v_w, float* g_v_b, float* part, float* cpart, float* s32,
-                       bool census, hipStream_t s) {
+int seq_head_backward(const R2d2BwdPlan& plan, int rowsTr, int A, const float* d_ha, const float* o_tr, const float* a_w,
+                      const float* v_w, float* d_o, float* g_a_w, float* g_a_b, float* g_v_w, float* g_v_b, float* part,
+                      float* cpart, float* s32, bool census, hipStream_t s) {
   {
     ProbHeadDgradSeq p{};
     p.M = rowsTr, p.N = kHid, p.K = 32;
     p.d_ha = d_ha, p.a_w = a_w, p.v_w = v_w, p.d_o = d_o, p.A = A;
-    launch_gemm<TileRows>(p, 1, s, "learner_dgrad_heads");
+    if (int rc = launch_gemm_as<SetSeqHeadRows>(plan.heads, p, 1, s, "learner_dgrad_heads")) return rc;
   }
-  if (rowsTr >= kSeqHeadSplitRows) {  // split-K over 32 slices: 256 blocks instead of 8 (0.13 ms on 8 CUs at 5,312 rows)
+  if (plan.head_wgrad_splits > 1) {  // split-K over 32 slices: 256 blocks instead of 8 (0.13 ms on 8 CUs at 5,312 rows)
     ProbHeadWgradPart p{};
     p.M = 32, p.N = kHid, p.K = rowsTr;
     p.d_ha = d_ha, p.h = o_tr, p.part = part;
     if (census) note_launch("head_wgrad (split-K)"), note_launch("head_wgrad_reduce");
-    launch_gemm<TileW32r>(p, kSplitHeads, s, "learner_wgrad_heads");
-    hipLaunchKernelGGL(head_wgrad_reduce, dim3(ceil_div(32 * 512, 256)), dim3(256), 0, s, (const float*)part, kSplitHeads, A,
-                       g_a_w, g_v_w);
+    if (int rc = launch_gemm_as<SetSeqHeadW32>(plan.heads, p, plan.head_wgrad_splits, s, "learner_wgrad_heads")) return rc;
+    hipLaunchKernelGGL(head_wgrad_reduce, dim3(ceil_div(32 * 512, 256)), dim3(256), 0, s, (const float*)part,
+                       plan.head_wgrad_splits, A, g_a_w, g_v_w);
   } else {
     ProbHeadWgrad p{};
     p.M = 32, p.N = kHid, p.K = rowsTr;
     p.d_ha = d_ha, p.h = o_tr, p.g_a_w = g_a_w, p.g_v_w = g_v_w, p.A = A;
     if (census) note_launch("head_wgrad (one launch)");
-    launch_gemm<TileW32r>(p, 1, s, "learner_wgrad_heads");
+    if (int rc = launch_gemm_as<SetSeqHeadW32>(plan.heads, p, 1, s, "learner_wgrad_heads")) return rc;
   }
   colsum_launch(d_ha, rowsTr, 32, cpart, s32, s);
   hipLaunchKernelGGL(head_bias_grad, dim3(1), dim3(32), 0, s, (const float*)s32, A, g_a_b, g_v_b);
+  return RELA_OK;
 }
 }  // namespace
 
@@ -1268,13 +1251,11 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
   const size_t blk = (size_t)Bn * kHid;
   float *H = l->Hs[0], *Cc = l->Cs[0];
   const float* o_tr = H + (size_t)(burn + 1) * blk;  // LSTM outputs of the training steps
-  // mode 3: the large GEMMs over all training rows at once (dW_hh, dW_ih, d_a3, the conv weight gradients), with the
-  // Problems of mode 0, on gemm_bf16x3 with three-part operands (f32 accuracy); the heads' GEMMs, the recurrence, the cell
-  // kernels and the conv data gradients stay what they are in mode 0
-  const bool x6 = l->precision == 3;
+  const R2d2BwdPlan plan = plan_r2d2_backward(l->precision, rowsTr);
   // heads: d_o, dW, db
-  seq_head_backward(rowsTr, A, l->d_ha, o_tr, P.a_w, P.v_w, l->d_o, Gm[12], Gm[13], Gm[10], Gm[11], l->part, l->cpart, l->s32,
-                    false, s);
+  if (int rc = seq_head_backward(plan, rowsTr, A, l->d_ha, o_tr, P.a_w, P.v_w, l->d_o, Gm[12], Gm[13], Gm[10], Gm[11], l->part,
+                                 l->cpart, l->s32, false, s))
+    return rc;
   // BPTT over the training steps, newest first; the activated gates in gx become the gate gradients in place
   RELA_HIP(hipMemsetAsync(l->dc_rec, 0, blk * sizeof(float), s));
   const int cell_grid = ceil_div((int64_t)Bn * kHid, 256);
@@ -1309,7 +1290,7 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
   }
   {
     LstmInBwd t{};
-    t.rowsTr = rowsTr, t.precision = l->precision;
+    t.rowsTr = rowsTr, t.rec64 = plan.lstm_in_rec64, t.arith = plan.lstm_in;
     t.dg = ga_tr;                          // [rowsTr][2048]
     t.hprev = H + (size_t)burn * blk;      // h_{t-1} of training step t = H[burn + t]
     t.a3 = l->a3 + tr0 * kA3;
@@ -1324,10 +1305,8 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
     t.d_a2 = l->d_a2, t.d_a1 = l->d_a1, t.part = l->part, t.cpart = l->cpart;
     t.w2p = l->w2p, t.w3p = l->w3p;
     t.g_c1w = Gm[0], t.g_c1b = Gm[1], t.g_c2w = Gm[2], t.g_c2b = Gm[3], t.g_c3w = Gm[4], t.g_c3b = Gm[5];
-    t.fast = l->precision == 1;
-    t.emu = x6;  // conv1 / conv2 / conv3 weight gradients on three-part operands, one lane
-    for (int i = 0; i < 3; ++i) t.emu_split_mul[i] = kX6SplitMul[i];
-    trunk_backward(t, s);
+    t.plan = plan.trunk.plan(rowsTr);  // one lane
+    if (int rc = trunk_backward(t, s)) return rc;
   }
   RELA_LAUNCH_CHECK();
   return RELA_OK;
@@ -1382,8 +1361,9 @@ extern "C" int rela_debug_lstm_input_backward(int rows, int mode, const float* d
     DevBuffers mem;
     ~Scratch() { mem.free_all(); }
   } sc;
+  const R2d2BwdPlan plan = plan_r2d2_backward(mode, rows);
   LstmInBwd t{};
-  t.rowsTr = rows, t.precision = mode, t.dg = dg, t.hprev = hprev, t.a3 = a3;
+  t.rowsTr = rows, t.rec64 = plan.lstm_in_rec64, t.arith = plan.lstm_in, t.dg = dg, t.hprev = hprev, t.a3 = a3;
   t.g_w_ih = g_w_ih, t.g_w_hh = g_w_hh, t.g_b_ih = g_b_ih, t.g_b_hh = g_b_hh, t.d_a3 = d_a3;
   // pack_lstm_learner also transposes W_hh and sums the biases: zeros stand in for them, their outputs are not read
   float *wihT = nullptr, *wihp = nullptr, *zeros = nullptr, *whhT = nullptr, *bsum = nullptr;
@@ -1396,7 +1376,7 @@ extern "C" int rela_debug_lstm_input_backward(int rows, int mode, const float* d
   RELA_HIP(hipMemsetAsync(zeros, 0, sizeof(float) * kGates * kHid, s));
   if (int rc = launch_pack_lstm(w_ih, zeros, zeros, zeros, wihT, wihp, whhT, bsum, s)) return rc;
   t.wihp = wihp;
-  if (mode == 1) {  // as refresh_weight_records (online net) and the learner's sizes of arec / trec, for `rows` rows
+  if (t.rec64) {  // as refresh_weight_records (online net) and the learner's sizes of arec / trec, for `rows` rows
     using namespace gemm16;
     uint8_t* wTrec = nullptr;
     const size_t chunks = ((size_t)rows + 63) / 64;
@@ -1482,9 +1462,12 @@ extern "C" int rela_debug_seq_head_backward(int rows, int A, const float* d_ha, 
   if (int rc = sc.mem.alloc(&part, kSeqHeadPartFloats, false)) return rc;
   if (int rc = sc.mem.alloc(&cpart, (size_t)kColsumBlocks * 32, false)) return rc;
   if (int rc = sc.mem.alloc(&s32, 32, false)) return rc;
-  seq_head_backward(rows, A, d_ha, o, fc_a_w, fc_v_w, d_o, g_fc_a_w, g_fc_a_b, g_fc_v_w, g_fc_v_b, part, cpart, s32, true, s);
+  // (the heads run the same in every precision mode: mode 0's plan)
+  const int rc = seq_head_backward(plan_r2d2_backward(0, rows), rows, A, d_ha, o, fc_a_w, fc_v_w, d_o, g_fc_a_w, g_fc_a_b,
+                                   g_fc_v_w, g_fc_v_b, part, cpart, s32, true, s);
   const hipError_t launched = hipGetLastError();
   const hipError_t done = hipStreamSynchronize(s);  // (the scratch goes away with `sc`)
+  if (rc != RELA_OK) return rc;
   RELA_HIP(launched);
   RELA_HIP(done);
   return RELA_OK;

@@ -481,7 +481,7 @@ def caught(margins):
 HEAD_KEYS = ("d_o", "g_fc_a_w", "g_fc_a_b", "g_fc_v_w", "g_fc_v_b")
 HEAD_ROWS = (1, 5, 33, 129, 1023, 1024, 1025, 2051)
 HEAD_CASES = [(rows, A) for rows in HEAD_ROWS for A in (A_LIST if rows in (33, 1024) else (18,))]
-SPLIT_ROWS, SPLIT_SLICES = 1024, 32  # csrc/learner_r2d2.hip: kSeqHeadSplitRows, kSplitHeads
+SPLIT_ROWS, SPLIT_SLICES = 1024, 32  # csrc/learner_plan.h: kSeqHeadSplitRows, kSplitHeads
 
 
 def head_shapes(rows, A):

@@ -12,33 +12,18 @@ csrc/learner.hip and csrc/learner_r2d2.hip are compiled device-only to assembly 
 -Rpass-analysis=kernel-resource-usage, as tests/test_learner_gemm_waits_cpu.py does.  Only MFMA and barrier counts inside
 the blocks the compiler marks as a loop, and the resource remarks, are read.
 """
-import os
 import re
-import shutil
 import subprocess
 
 import pytest
+
+from kernel_resources import device_only_cmd, parse_remarks
 
 SOURCES = ("learner.hip", "learner_r2d2.hip")
 # (substrings of the mangled name) -> (S, MFMAs per barrier of the S = 1 kernel)
 STAGED = {("8gemm_ldsI", "6ProbW1E"): (4, 8), ("11gemm_bf16x3I", "11SinglePartBI", "6ProbW1E"): (2, 3)}
 # the stage depth is TileCfg's last template argument: ..., true, S> for gemm_lds, ..., true, 3 parts, S> for gemm_bf16x3
 STAGE_ARG = {"8gemm_ldsI": r"Lb[01]ELi%dEE", "11gemm_bf16x3I": r"Lb[01]ELi\dELi%dEE"}
-
-
-def parse_remarks(stderr):
-    """-> {mangled kernel name: {remark key: int}}"""
-    out, name = {}, None
-    for line in stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.search(r"remark:\s+(.+?): (\d+) \[-Rpass-analysis", line)
-        if m and name:
-            out[name][m.group(1)] = int(m.group(2))
-    return out
 
 
 def parse_loops(asm):
@@ -72,18 +57,12 @@ def parse_loops(asm):
 @pytest.fixture(scope="module")
 def compiled(tmp_path_factory):
     """{source: ({kernel: loop counts}, {kernel: resource remarks})} of the gemm_bf16x3 / gemm_lds kernels"""
-    from rela_amd import build as b
-
-    hipcc = b.HIPCC if os.path.exists(b.HIPCC) else shutil.which("hipcc")
-    if not hipcc:
-        pytest.skip("no hipcc here")
     tmp = tmp_path_factory.mktemp("gemmstage")
     jobs = {}
     for src in SOURCES:
         asm = str(tmp / (src[:-4] + ".s"))
-        cmd = [hipcc] + b.HIP_FLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-S",
-                                       os.path.join(b.CSRC, src), "-o", asm]
-        jobs[src] = (asm, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+        jobs[src] = (asm, subprocess.Popen(device_only_cmd(src, asm, "-S"), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                                           text=True))
     out = {}
     for src, (asm, proc) in jobs.items():
         _, err = proc.communicate()

@@ -425,7 +425,7 @@ def test_learner_errors():
 
 
 @pytest.mark.parametrize("precision", ["f32", "f32x3", "bf16x2"])
-@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLD, "learner_*.json"))), ids=os.path.basename)
+@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLD, "learner_apex_*.json"))), ids=os.path.basename)
 def test_learner_step_matches_the_reference_golden(path, precision):
     """One learner step against vectors recorded from the REAL reference on CPU
     (tests/golden/make_golden.py learner_cases: pyrela/apex.py loss -> backward -> clip_grad_norm_ ->

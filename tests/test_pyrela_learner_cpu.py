@@ -1,5 +1,5 @@
 """CPU checks of the PyTorch learner path (`--hip_learner 0`, rela_amd/pyrela/apex.py) against the vectors
-recorded from the REAL reference's learner step (tests/golden/learner_*.json, make_golden.py learner)."""
+recorded from the REAL reference's learner step (tests/golden/learner_apex_*.json, make_golden.py learner)."""
 import glob
 import json
 import os
@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 GOLD = os.path.join(HERE, "golden")
 
 
-@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLD, "learner_*.json"))), ids=os.path.basename)
+@pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLD, "learner_apex_*.json"))), ids=os.path.basename)
 def test_autograd_learner_step_matches_reference_golden(path):
     import torch
     from types import SimpleNamespace

@@ -11,14 +11,11 @@ SIMD (a block is 2: the tiles were chosen for two blocks per CU).  Only the rema
 
 Arguments: rela_amd/pyrela/main.py's --learner_precision and its two refusals.
 """
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from kernel_resources import kernel_resources
 
 # mangled: gemm_bf16x3<TileCfg<BM, BN, WM, WN, AMC, 3, S>, Problem>
 THREE_PART = re.compile(r"11gemm_bf16x3I.*7TileCfgILi\d+ELi\d+ELi\d+ELi\d+ELb[01]ELi3ELi\d+EE")
@@ -28,28 +25,7 @@ NEW_PROBLEMS = ("7ProbWhhE", "7ProbWihE", "11ProbIhDgradE")
 @pytest.fixture(scope="module")
 def resources(tmp_path_factory):
     """{mangled kernel name: {remark key: int}} of csrc/learner_r2d2.hip's kernels"""
-    from rela_amd import build as b
-
-    hipcc = b.HIPCC if os.path.exists(b.HIPCC) else shutil.which("hipcc")
-    if not hipcc:
-        pytest.skip("no hipcc here")
-    obj = str(tmp_path_factory.mktemp("r2d2res") / "learner_r2d2_dev.o")
-    cmd = [hipcc] + b.HIP_FLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-                                   os.path.join(b.CSRC, "learner_r2d2.hip"), "-o", obj]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    out = {}
-    name = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.search(r"remark:\s+(.+?): (\d+) \[-Rpass-analysis", line)
-        if m and name:
-            out[name][m.group(1)] = int(m.group(2))
-    return out
+    return kernel_resources("learner_r2d2.hip", tmp_path_factory.mktemp("r2d2res"))
 
 
 def test_three_part_gemms_have_no_scratch_and_no_spills(resources):

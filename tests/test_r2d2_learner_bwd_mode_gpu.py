@@ -14,7 +14,7 @@ Shapes (A, B, seq, burn, n):
   (18, 33, 12, 6, 3)   693 frames, 495 training rows: ragged, the three-part forwards run too
   (6, 130, 3, 1, 1)    650 frames, 520 training rows: B > 128 takes the per-step recurrence
   (6, 33, 30, 0, 2)    1,056 frames, 1,056 training rows: above 1,024, where conv2's / conv3's weight gradients run at twice
-                       mode 0's split-K slices (54 / 56: TrunkBwd::emu_split_mul)
+                       mode 0's split-K slices (54 / 56: kX6SplitMul, csrc/learner_plan.h)
 
 Modes 0, 1 and 2 must not move a bit: sha256 of the flat gradient buffer, the loss and the priorities of the first two
 shapes are compared with tests/golden/r2d2_learner_parent_bits.json, recorded on an MI355X with this file's `compute()`

@@ -19,7 +19,7 @@ import trunk_bwd_ref as R
 pytestmark = pytest.mark.gpu
 
 MODES = {"f32": 0, "bf16x2": 1, "f32x3": 2}
-FAST_WGRAD_MIN_FRAMES = 2048  # csrc/learner_common.h: kFastWgradMinFrames
+FAST_WGRAD_MIN_FRAMES = 2048  # csrc/learner_plan.h: kFastWgradMinFrames
 OUT_SHAPES = {"g_c1w": (32, 4, 8, 8), "g_c1b": (32,), "g_c2w": (64, 32, 4, 4), "g_c2b": (64,), "g_c3w": (64, 64, 3, 3),
               "g_c3b": (64,)}
 

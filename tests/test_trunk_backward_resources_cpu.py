@@ -10,14 +10,9 @@ device-only with build.py's HIP_FLAGS plus -Rpass-analysis=kernel-resource-usage
 remarks must say `ScratchSize [bytes/lane]: 0`, `VGPRs Spill: 0`, an occupancy of at least 4 waves per SIMD (a block is
 2 waves per SIMD) and at most 80 KB of static LDS per block (two blocks in a CU's 160 KB).  Only the remarks are read.
 """
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from kernel_resources import kernel_resources
 
 # substrings of the mangled kernel names: gemm_lds<.., ProbDgrad3>, gemm_lds<.., ProbDgrad2>, gemm_bf16x3<SinglePartB<..>, ProbW1>
 KERNELS = {"dgrad_conv3": ("8gemm_ldsI", "10ProbDgrad3E"), "dgrad_conv2": ("8gemm_ldsI", "10ProbDgrad2E"),
@@ -27,28 +22,7 @@ KERNELS = {"dgrad_conv3": ("8gemm_ldsI", "10ProbDgrad3E"), "dgrad_conv2": ("8gem
 @pytest.fixture(scope="module")
 def resources(tmp_path_factory):
     """{mangled kernel name: {remark key: int}} of csrc/learner.hip's kernels"""
-    from rela_amd import build as b
-
-    hipcc = b.HIPCC if os.path.exists(b.HIPCC) else shutil.which("hipcc")
-    if not hipcc:
-        pytest.skip("no hipcc here")
-    obj = str(tmp_path_factory.mktemp("tbres") / "learner_dev.o")
-    cmd = [hipcc] + b.HIP_FLAGS + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-                                   os.path.join(b.CSRC, "learner.hip"), "-o", obj]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    out = {}
-    name = None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.search(r"remark:\s+(.+?): (\d+) \[-Rpass-analysis", line)
-        if m and name:
-            out[name][m.group(1)] = int(m.group(2))
-    return out
+    return kernel_resources("learner.hip", tmp_path_factory.mktemp("tbres"))
 
 
 @pytest.mark.parametrize("kernel", sorted(KERNELS))
