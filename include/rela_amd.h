@@ -684,6 +684,26 @@ int rela_debug_lstm_input_backward(int rows, int mode, const float* dg, const fl
 /* Debug / tests: the learner's own d_ha [B][32], d_h [B][512] and d_a3 [B][49][64] of the last rela_apex_learner_grad
  * (d_ha: of the last rela_apex_learner_loss).  Valid until the next rela_apex_learner_loss.                        */
 int rela_apex_learner_debug_head_grads(rela_apex_learner* l, float** d_ha, float** d_h, float** d_a3);
+/* Test tap: the step of both learners that turns gradients into weights (csrc/learner_common.h: optimizer_apply --
+ * sumsq_partial, clip_coef, then rmsprop_update or adam_update) on the caller's flat buffers.  p, g, s1, s2 and stats_out
+ * are device pointers; the call brings its own partial sums, abort word and skip counter, synchronises and frees them.
+ *   optimizer        0 RMSprop (alpha 0.99; s1 = square average, s2 untouched), 1 Adam (betas 0.9 / 0.999; s1, s2 = m, v)
+ *   lr, eps, clip    as rela_*_learner_create takes them (clip = max_norm of clip_grad_norm_)
+ *   adam_steps_done  Adam steps already taken: this call's bias corrections are those of step adam_steps_done + 1
+ *   p, s1, s2        in / out: f32 [n];   g   f32 [n]
+ *   stats_out        out: f32 [2] on the device: the gradient norm, the clip coefficient (-1: the update was skipped)
+ *   abort            1: the abort word is set, as the R2D2 learner's timeout word would be: the norm is still written, the
+ *                    coefficient is -1, p / s1 / s2 stay as they are and the skip counter goes up by one
+ *   skipped_out      out (host, may be NULL): the skip counter after the call
+ * n > 0, n % 4 == 0 and p, g, s1, s2 16-byte aligned, else RELA_EINVAL: that is what the learners' flat buffers give (every
+ * segment is padded to 4 floats).  The update kernels cover n / 4 float4, so with another n the norm would count elements
+ * that are never updated.  Launch census: sumsq_partial, clip_coef and the update kernel, one each.                  */
+int rela_debug_optimizer_apply(int optimizer, float lr, float eps, float clip, int64_t adam_steps_done, int64_t n, float* p,
+                               const float* g, float* s1, float* s2, float* stats_out, int abort, unsigned* skipped_out,
+                               void* stream);
+/* Debug / tests: the optimiser state of the flat store (device pointers, the layout and length of rela_apex_learner_flat,
+ * pads included: RMSprop's square average in s1; Adam's m in s1, v in s2) and the host's Adam step number.          */
+int rela_apex_learner_debug_optim(rela_apex_learner* l, float** s1_dev, float** s2_dev, int64_t* adam_t);
 
 /* Test tap: the sequence TD block of rela_r2d2_learner_loss (csrc/learner_r2d2.hip: seq_td_launch -- q_min_all, seq_select,
  * seq_td_loss, seq_head_grad; R2D2Agent.td_err / loss / aggregate_priority and AtariLSTMNet.forward's greedy rule and
@@ -762,7 +782,8 @@ int rela_r2d2_learner_flat(rela_r2d2_learner* l, float** params_dev, float** gra
 const float* rela_r2d2_learner_stats_dev(const rela_r2d2_learner* l); /* grad norm, clip coefficient */
 /* The T recurrent steps run as ONE persistent launch per pass with a bounded grid barrier between steps (no reference
  * counterpart: autograd launches per step).  Synchronises `stream` and returns RELA_ESTATE if a barrier of any call
- * since the last check gave up (never observed; the results of that call are then invalid). */
+ * since the last check gave up (never observed; the results of that call are then invalid).  The applies since then
+ * were skipped and counted on the device; the check takes them off the Adam step number again. */
 int rela_r2d2_learner_check(rela_r2d2_learner* l, void* stream);
 /* 1: the TARGET net's conv trunk (no gradient) runs on split-bf16 MFMA (rela_lstmnet_set_precision) and so do the GEMMs
  * of the LSTM's input side (gate GEMM of both nets, its data and weight gradients, dW_hh), the conv weight gradients
@@ -789,6 +810,13 @@ int rela_r2d2_learner_set_value_rescale(rela_r2d2_learner* l, float eps);
  * first.  Mirrors rela_apex_learner_debug_head_grads.                                                                */
 int rela_r2d2_learner_debug_heads(rela_r2d2_learner* l, float** q_on, float** q_tg, float** d_ha, float** o_tr,
                                   float** d_o, int* rows);
+/* Debug / tests: as rela_apex_learner_debug_optim.  adam_t counts the applies launched; rela_r2d2_learner_check takes the
+ * ones the device skipped off it again.                                                                             */
+int rela_r2d2_learner_debug_optim(rela_r2d2_learner* l, float** s1_dev, float** s2_dev, int64_t* adam_t);
+/* Debug / tests: a stream-ordered store of the timeout word and nothing else.  While the word is non-zero call only
+ * rela_r2d2_learner_apply (which skips its update on the device) and rela_r2d2_learner_check (which reports and clears
+ * it): the persistent recurrent kernels of _loss / _grad / _backward read the word and leave at once.               */
+int rela_r2d2_learner_debug_set_timeout_word(rela_r2d2_learner* l, unsigned word, void* stream);
 
 /* ===================================================================================
  * Live per-kernel timing (HIP events on the launch stream) for bench.py's roofline line.

@@ -239,6 +239,8 @@ _sig("rela_debug_loss_grad", i32, [i32, i32, i32] + [vp] * 7 + [f32, f32] + [vp]
 _sig("rela_debug_head_fc_backward", i32, [i32, i32, i32, i32] + [vp] * 15)
 _sig("rela_debug_lstm_input_backward", i32, [i32, i32] + [vp] * 10)
 _sig("rela_apex_learner_debug_head_grads", i32, [vp, P(vp), P(vp), P(vp)])
+_sig("rela_debug_optimizer_apply", i32, [i32, f32, f32, f32, i64, i64] + [vp] * 5 + [i32, P(C.c_uint), vp])
+_sig("rela_apex_learner_debug_optim", i32, [vp, P(vp), P(vp), P(i64)])
 _sig("rela_debug_seq_loss_grad", i32, [i32] * 5 + [vp] * 8 + [f32, f32, f64] + [vp] * 8)
 _sig("rela_debug_seq_head_backward", i32, [i32, i32] + [vp] * 10)
 _sig("rela_r2d2_learner_create", i32, [P(vp), i32, i32, i32, f32, i32, i32, f64, i32, f32, f32, f32, i32])
@@ -257,6 +259,8 @@ _sig("rela_r2d2_learner_check", i32, [vp, vp])
 _sig("rela_r2d2_learner_set_precision", i32, [vp, i32])
 _sig("rela_r2d2_learner_set_value_rescale", i32, [vp, f32])
 _sig("rela_r2d2_learner_debug_heads", i32, [vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(i32)])
+_sig("rela_r2d2_learner_debug_optim", i32, [vp, P(vp), P(vp), P(i64)])
+_sig("rela_r2d2_learner_debug_set_timeout_word", i32, [vp, C.c_uint, vp])
 _sig("rela_prof_enable", i32, [i32])
 _sig("rela_prof_set_filter", i32, [C.c_char_p])
 _sig("rela_prof_summary_json", i32, [C.c_char_p, i64])

@@ -579,6 +579,43 @@ extern "C" int rela_apex_learner_debug_head_grads(rela_apex_learner* l, float** 
   return RELA_OK;
 }
 
+// Test tap: optimizer_apply (learner_common.h) itself on the caller's flat buffers: the norm, the clip coefficient and one
+// RMSprop / Adam update.  The OptimState, the 256 partial sums, the abort word and the skip counter live for this one call.
+extern "C" int rela_debug_optimizer_apply(int optimizer, float lr, float eps, float clip, int64_t adam_steps_done, int64_t n,
+                                          float* p, const float* g, float* s1, float* s2, float* stats_out, int abort,
+                                          unsigned* skipped_out, void* stream_) {
+  RELA_CHECK((optimizer == 0 || optimizer == 1) && adam_steps_done >= 0 && n > 0 && n % 4 == 0 && (abort == 0 || abort == 1),
+             RELA_EINVAL, "rela_debug_optimizer_apply: bad arguments (optimizer %d, steps done %lld, n %lld, abort %d)",
+             optimizer, (long long)adam_steps_done, (long long)n, abort);
+  RELA_CHECK(p && g && s1 && s2 && stats_out, RELA_EINVAL, "rela_debug_optimizer_apply: a pointer is NULL");
+  for (const void* b : {(const void*)p, (const void*)g, (const void*)s1, (const void*)s2})
+    RELA_CHECK(((uintptr_t)b & 15) == 0, RELA_EINVAL, "rela_debug_optimizer_apply: a buffer is not 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream_;
+  struct Scratch {
+    DevBuffers mem;
+    ~Scratch() { mem.free_all(); }
+  } sc;
+  double* npart = nullptr;
+  unsigned* words = nullptr;  // [0] the abort word, [1] the skip counter
+  if (int rc = sc.mem.alloc(&npart, kNormBlocks, false)) return rc;
+  if (int rc = sc.mem.alloc(&words, 2, true)) return rc;
+  if (abort) RELA_HIP(hipMemsetD32Async((hipDeviceptr_t)words, 1, 1, s));
+  OptimState o;
+  o.optimizer = optimizer, o.lr = lr, o.eps = eps, o.clip = clip, o.adam_t = adam_steps_done;
+  optimizer_apply(o, p, g, s1, s2, n, npart, stats_out, s, words, words + 1, true);
+  const hipError_t launched = hipGetLastError();
+  const hipError_t done = hipStreamSynchronize(s);  // (the scratch goes away with `sc`)
+  RELA_HIP(launched);
+  RELA_HIP(done);
+  if (skipped_out) RELA_HIP(hipMemcpy(skipped_out, words + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
+  return RELA_OK;
+}
+
+extern "C" int rela_apex_learner_debug_optim(rela_apex_learner* l, float** s1_dev, float** s2_dev, int64_t* adam_t) {
+  RELA_CHECK(l, RELA_EINVAL, "rela_apex_learner_debug_optim: bad arguments");
+  return l->debug_optim("rela_apex_learner_debug_optim", s1_dev, s2_dev, adam_t);
+}
+
 extern "C" int rela_apex_learner_apply(rela_apex_learner* l, void* stream_) {
   RELA_CHECK(l && l->loaded, RELA_ESTATE, "rela_apex_learner_apply: parameters were never loaded");
   hipStream_t s = (hipStream_t)stream_;

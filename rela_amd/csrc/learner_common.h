@@ -585,8 +585,12 @@ __global__ __launch_bounds__(256) void sumsq_partial(const float* __restrict__ g
 // out[0] = total 2-norm, out[1] = min(1, max_norm / (norm + 1e-6))   (torch clip_grad_norm_)
 // `abort_word` (may be NULL): a device word that is non-zero when the gradients of this step must not be applied (the
 // R2D2 learner's grid-barrier timeout word): the coefficient becomes -1 and the update kernels leave everything alone.
+// `skipped` (may be NULL): a device counter of the applies skipped that way, which the host takes off its Adam step
+// number (rela_r2d2_learner_check); this thread is its only writer and the launches are stream-ordered.
+// A NaN norm gives a NaN coefficient (torch's clamp propagates it): the update kernels then make every weight NaN.
 __global__ __launch_bounds__(256) void clip_coef(const double* __restrict__ part, int nblk, float max_norm,
-                                                 float* __restrict__ out, const unsigned* __restrict__ abort_word) {
+                                                 float* __restrict__ out, const unsigned* __restrict__ abort_word,
+                                                 unsigned* __restrict__ skipped) {
   // one block of 256 threads: fixed-order tree over the (at most 256) partial sums (a single thread walking them took
   // 20 us of every learner step)
   __shared__ double red[256];
@@ -601,8 +605,11 @@ __global__ __launch_bounds__(256) void clip_coef(const double* __restrict__ part
   const float norm = (float)sqrt(s);
   out[0] = norm;
   const float c = max_norm / (norm + 1e-6f);
-  out[1] = c < 1.0f ? c : 1.0f;
-  if (abort_word && *abort_word != 0) out[1] = -1.0f;
+  out[1] = c >= 1.0f ? 1.0f : c;
+  if (abort_word && *abort_word != 0) {
+    out[1] = -1.0f;
+    if (skipped) *skipped += 1;
+  }
 }
 // torch.optim.RMSprop (momentum 0, not centred): sq = alpha*sq + (1-alpha)*g*g; p -= lr * g / (sqrt(sq) + eps)
 // (four elements per thread: 16-byte accesses; n4 = ceil(n / 4), the flat buffers are padded to 4 floats)
@@ -803,11 +810,20 @@ struct OptimState {
   float lr = 0.f, eps = 0.f, clip = 0.f;
   int64_t adam_t = 0;
 };
+// adam_t counts every Adam apply launched; one that the device skipped (abort_word) adds one to *skipped, which the
+// owner of abort_word takes off adam_t again once it has read the word.  census: rela_debug_optimizer_apply counts its
+// three launches (the learners' steps do not: their censuses are recorded ones).
 inline void optimizer_apply(OptimState& o, float* P, const float* G, float* S1, float* S2, int64_t n, double* npart,
-                            float* norm, hipStream_t s, const unsigned* abort_word = nullptr) {
+                            float* norm, hipStream_t s, const unsigned* abort_word = nullptr, unsigned* skipped = nullptr,
+                            bool census = false) {
   ProfScope prof("learner_optimizer", s);
   hipLaunchKernelGGL(sumsq_partial, dim3(kNormBlocks), dim3(256), 0, s, G, n, npart);
-  hipLaunchKernelGGL(clip_coef, dim3(1), dim3(256), 0, s, (const double*)npart, kNormBlocks, o.clip, norm, abort_word);
+  hipLaunchKernelGGL(clip_coef, dim3(1), dim3(256), 0, s, (const double*)npart, kNormBlocks, o.clip, norm, abort_word,
+                     skipped);
+  if (census) {
+    note_launch("sumsq_partial"), note_launch("clip_coef");
+    note_launch(o.optimizer == 0 ? "rmsprop_update" : "adam_update");
+  }
   if (o.optimizer == 0) {
     hipLaunchKernelGGL(rmsprop_update, dim3(ceil_div(n / 4, 256)), dim3(256), 0, s, P, G, S1, n / 4, o.lr, 0.99f, o.eps,
                        (const float*)norm);
@@ -892,8 +908,13 @@ struct LearnerCore {
     vr_eps = eps > 0.f ? eps : 0.f;
     return RELA_OK;
   }
-  void apply(hipStream_t s, const unsigned* abort_word = nullptr) {
-    optimizer_apply(opt, P, G, S1, S2, off[nseg], npart, norm, s, abort_word);
+  void apply(hipStream_t s, const unsigned* abort_word = nullptr, unsigned* skipped = nullptr) {
+    optimizer_apply(opt, P, G, S1, S2, off[nseg], npart, norm, s, abort_word, skipped);
+  }
+  int debug_optim(const char* who, float** s1_dev, float** s2_dev, int64_t* adam_t) const {
+    RELA_CHECK(s1_dev && s2_dev && adam_t, RELA_EINVAL, "%s: bad arguments", who);
+    *s1_dev = S1, *s2_dev = S2, *adam_t = opt.adam_t;
+    return RELA_OK;
   }
 };
 

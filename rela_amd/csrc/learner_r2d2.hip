@@ -618,7 +618,7 @@ struct rela_r2d2_learner : LearnerCore {
   float* gxs[2] = {nullptr, nullptr};  // per net [T*B][2048]: GX; the online one -> activated gates -> dgates
   float *Hs[2] = {nullptr, nullptr}, *Cs[2] = {nullptr, nullptr};     // [(T+1)*B][512] per net
   float* rec_part = nullptr;                                          // split-K partials of the recurrent GEMMs
-  unsigned* rec_bar = nullptr;                                        // [0] timeout word, [4 ..] per-step arrival counters
+  unsigned* rec_bar = nullptr;  // [0] timeout word, [1] applies skipped since (clip_coef), [4 ..] per-step arrival counters
   unsigned* rec_chain_bar = nullptr;                                  // lstm_rec_chain: [8 chains][Tpad]
   bool rec_chains_fit = true;                                         // its 256 blocks are resident at once (checked at create)
   bool rec_persist = true;
@@ -1106,12 +1106,15 @@ extern "C" int rela_r2d2_learner_check(rela_r2d2_learner* l, void* stream_) {
   RELA_CHECK(l, RELA_EINVAL, "rela_r2d2_learner_check: null learner");
   DeviceGuard g(l->device);
   RELA_HIP(hipStreamSynchronize((hipStream_t)stream_));
-  unsigned tmo = 0;
-  RELA_HIP(hipMemcpy(&tmo, l->rec_bar, sizeof(unsigned), hipMemcpyDeviceToHost));
+  unsigned words[2] = {0, 0};  // the timeout word, the applies skipped since it was set
+  RELA_HIP(hipMemcpy(words, l->rec_bar, sizeof(words), hipMemcpyDeviceToHost));
+  const unsigned tmo = words[0];
   if (tmo != 0) {
-    RELA_HIP(hipMemset(l->rec_bar, 0, sizeof(unsigned)));
-    // every apply() since the timeout was skipped on the device (clip_coef saw the word); from here on this learner
-    // runs the recurrences as per-step launches, which need no co-residency
+    RELA_HIP(hipMemset(l->rec_bar, 0, sizeof(words)));
+    // every apply() since the timeout was skipped on the device (clip_coef saw the word and counted the apply): those
+    // took no Adam step, so the step number that optimizer_apply advanced on the host goes back by as many; from here on
+    // this learner runs the recurrences as per-step launches, which need no co-residency
+    if (l->opt.optimizer == 1) l->opt.adam_t = std::max<int64_t>(0, l->opt.adam_t - (int64_t)words[1]);
     l->rec_persist = false;
     set_last_error("rela_r2d2_learner_check: the grid barrier of a persistent recurrent kernel timed out at step %u: the "
                    "results of that call are invalid, no optimiser update was applied since, and this learner now uses "
@@ -1492,7 +1495,24 @@ extern "C" int rela_r2d2_learner_apply(rela_r2d2_learner* l, void* stream_) {
   DeviceGuard g(l->device);
   // (a grid-barrier timeout of this step's persistent kernels leaves stale gradients: the update is skipped on the
   // device, rela_r2d2_learner_check reports it and switches to the per-step launches)
-  l->apply(s, l->rec_bar);
+  l->apply(s, l->rec_bar, l->rec_bar + 1);
   RELA_LAUNCH_CHECK();
   return repack_r2d2(l, true, false, s);
+}
+
+// Debug / tests: the optimiser state of the flat store (S1, S2: the layout of rela_r2d2_learner_flat, pads included) and
+// the host's Adam step number.
+extern "C" int rela_r2d2_learner_debug_optim(rela_r2d2_learner* l, float** s1_dev, float** s2_dev, int64_t* adam_t) {
+  RELA_CHECK(l, RELA_EINVAL, "rela_r2d2_learner_debug_optim: bad arguments");
+  return l->debug_optim("rela_r2d2_learner_debug_optim", s1_dev, s2_dev, adam_t);
+}
+
+// Debug / tests: a stream-ordered store of the timeout word and nothing else.  While it is non-zero only
+// rela_r2d2_learner_apply (which then skips its update) and rela_r2d2_learner_check (which clears it) may run: the
+// persistent recurrent kernels of loss / grad read the word and would leave at once.
+extern "C" int rela_r2d2_learner_debug_set_timeout_word(rela_r2d2_learner* l, unsigned word, void* stream_) {
+  RELA_CHECK(l, RELA_EINVAL, "rela_r2d2_learner_debug_set_timeout_word: bad arguments");
+  DeviceGuard g(l->device);
+  RELA_HIP(hipMemsetD32Async((hipDeviceptr_t)l->rec_bar, (int)word, 1, (hipStream_t)stream_));
+  return RELA_OK;
 }

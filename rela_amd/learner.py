@@ -154,6 +154,15 @@ class _HipLearner:
         """cuda f32[2]: gradient norm before clipping, clip coefficient of the last apply()."""
         return self._view(getattr(self._capi.lib, self._PREFIX + "stats_dev")(self.h), (2,))
 
+    def debug_optim(self):
+        """(S1, S2, adam_t): flat f32 views of the optimiser state in the layout of flat(), pads included (RMSprop's
+        square average in S1; Adam's m in S1 and v in S2), and the host's Adam step number."""
+        C = self._C
+        s1, s2, t, n = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_int64()
+        self._call("debug_optim", C.byref(s1), C.byref(s2), C.byref(t))
+        self._call("flat", None, None, C.byref(n))
+        return self._view(s1.value, (n.value,)), self._view(s2.value, (n.value,)), t.value
+
     _PRECISIONS = {"f32": 0, "bf16x2": 1, "f32x3": 2}
 
     def _set_precision(self, mode):
