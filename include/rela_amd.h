@@ -569,6 +569,28 @@ int rela_apex_learner_load(rela_apex_learner* l, const rela_ffnet_params* online
                            const rela_ffnet_params* target, int params_on_device, void* stream);
 /* ApexAgent.sync_target_with_online  apex.py:26-27 */
 int rela_apex_learner_sync_target(rela_apex_learner* l, void* stream);
+/* Update rules beyond the reference's (which has torch's defaults, a fixed learning rate and the whole copy above); with none
+ * of them called the learner launches what it launched before, with the same arguments.
+ * _soft_update_target: the Polyak update target += tau * (online - target) over the flat buffer (float32, in that order),
+ *   then the target re-pack of _sync_target.  0 < tau <= 1 (else RELA_EINVAL); tau == 1 is _sync_target, bit for bit.
+ *   RELA_ESTATE before the first load.
+ * _set_lr / _lr: the learning rate of the NEXT apply; lr finite and >= 0 (else RELA_EINVAL), any time after create.  Touches
+ *   neither the optimiser state nor the Adam step number.
+ * _set_rmsprop: RMSprop's decay alpha, 0 < alpha < 1 (default 0.99), and centered in {0, 1} (default 0): 1 keeps the gradient
+ *   average in the second state buffer and divides by sqrt(max(square average - average^2, 0)) + eps.  The clamp at 0 is
+ *   a departure from torch.optim.RMSprop(centered=True), whose float32 form takes the root of a difference that rounding makes
+ *   negative and turns the weight into NaN (csrc/learner_common.h: rmsprop_centered_update).  RELA_EINVAL on an Adam learner.
+ * _set_adam_betas: 0 <= b1 < 1, 0 < b2 < 1 (defaults 0.9 / 0.999); the bias corrections use them.  RELA_EINVAL on an RMSprop
+ *   learner.
+ * The two option setters are accepted only while the optimiser state is the zero state: after create or a load and before the
+ * first apply since then (later: RELA_ESTATE).  Every rela_*_learner_apply call counts, also one of the R2D2 learner that the
+ * device then skips on the timeout word (the host cannot know at that point): the options stay locked until the next load.
+ * A load resets the state and the step number and keeps options and lr. */
+int rela_apex_learner_soft_update_target(rela_apex_learner* l, float tau, void* stream);
+int rela_apex_learner_set_lr(rela_apex_learner* l, float lr);
+int rela_apex_learner_lr(rela_apex_learner* l, float* out);
+int rela_apex_learner_set_rmsprop(rela_apex_learner* l, float alpha, int centered);
+int rela_apex_learner_set_adam_betas(rela_apex_learner* l, float b1, float b2);
 /* 0 = exact f32 (default).  1 = the two gradient-free forwards of td_err (online and target net on next_obs,
  * apex.py:38-42) on the split-bf16 MFMA trunk (rela_ffnet_set_precision), conv1's weight gradient and the conv2 /
  * conv3 data gradients on bf16 MFMA (hi + lo operands, f32 accumulation).  The online(obs) pass, whose activations
@@ -701,6 +723,17 @@ int rela_apex_learner_debug_head_grads(rela_apex_learner* l, float** d_ha, float
 int rela_debug_optimizer_apply(int optimizer, float lr, float eps, float clip, int64_t adam_steps_done, int64_t n, float* p,
                                const float* g, float* s1, float* s2, float* stats_out, int abort, unsigned* skipped_out,
                                void* stream);
+/* Test tap: rela_debug_optimizer_apply with the options of rela_*_learner_set_rmsprop / _set_adam_betas (their ranges, else
+ * RELA_EINVAL; every other argument and refusal as above).  optimizer 0 with centered 1: s1 = square average, s2 = gradient
+ * average, and the update kernel of the census is rmsprop_centered_update.  With alpha 0.99, centered 0 and betas 0.9 / 0.999
+ * it is rela_debug_optimizer_apply.                                                                                    */
+int rela_debug_optimizer_apply_opts(int optimizer, float lr, float eps, float clip, int64_t adam_steps_done, int64_t n, float* p,
+                                    const float* g, float* s1, float* s2, float* stats_out, int abort, unsigned* skipped_out,
+                                    float alpha, int centered, float b1, float b2, void* stream);
+/* Test tap: the kernel of rela_*_learner_soft_update_target on the caller's device buffers: pt[i] += tau * (p[i] - pt[i]),
+ * i < n; p is read only.  n > 0, n % 4 == 0, 0 < tau <= 1 (tau == 1 runs the kernel too), pt and p 16-byte aligned, else
+ * RELA_EINVAL.  The call synchronises.  Launch census: one target_lerp.                                               */
+int rela_debug_target_lerp(int64_t n, float tau, float* pt, const float* p, void* stream);
 /* Debug / tests: the optimiser state of the flat store (device pointers, the layout and length of rela_apex_learner_flat,
  * pads included: RMSprop's square average in s1; Adam's m in s1, v in s2) and the host's Adam step number.          */
 int rela_apex_learner_debug_optim(rela_apex_learner* l, float** s1_dev, float** s2_dev, int64_t* adam_t);
@@ -759,6 +792,13 @@ void rela_r2d2_learner_destroy(rela_r2d2_learner* l);
 int rela_r2d2_learner_load(rela_r2d2_learner* l, const rela_lstmnet_params* online,
                            const rela_lstmnet_params* target, int params_on_device, void* stream);
 int rela_r2d2_learner_sync_target(rela_r2d2_learner* l, void* stream); /* r2d2.py:54-55 */
+/* as rela_apex_learner_soft_update_target / _set_lr / _lr / _set_rmsprop / _set_adam_betas.  The timeout word of
+ * rela_r2d2_learner_check does not gate the soft update: the online weights it reads are the ones no skipped apply touched. */
+int rela_r2d2_learner_soft_update_target(rela_r2d2_learner* l, float tau, void* stream);
+int rela_r2d2_learner_set_lr(rela_r2d2_learner* l, float lr);
+int rela_r2d2_learner_lr(rela_r2d2_learner* l, float* out);
+int rela_r2d2_learner_set_rmsprop(rela_r2d2_learner* l, float alpha, int centered);
+int rela_r2d2_learner_set_adam_betas(rela_r2d2_learner* l, float b1, float b2);
 /* loss + backward on one sampled batch.  rows_dev: the ten RNNTransition fields, time-major, in the order of
  * the sequence schema (s, eps, legal_move, a, reward, terminal, bootstrap, h0, c0, seq_len) as
  * rela_replay_sample fills them; weight_dev f32[batch].  Leaves the gradient of mean(loss * weight) in the flat

@@ -240,6 +240,15 @@ _sig("rela_debug_head_fc_backward", i32, [i32, i32, i32, i32] + [vp] * 15)
 _sig("rela_debug_lstm_input_backward", i32, [i32, i32] + [vp] * 10)
 _sig("rela_apex_learner_debug_head_grads", i32, [vp, P(vp), P(vp), P(vp)])
 _sig("rela_debug_optimizer_apply", i32, [i32, f32, f32, f32, i64, i64] + [vp] * 5 + [i32, P(C.c_uint), vp])
+_sig("rela_debug_optimizer_apply_opts", i32,
+     [i32, f32, f32, f32, i64, i64] + [vp] * 5 + [i32, P(C.c_uint), f32, i32, f32, f32, vp])
+_sig("rela_debug_target_lerp", i32, [i64, f32, vp, vp, vp])
+for _prefix in ("rela_apex_learner_", "rela_r2d2_learner_"):
+    _sig(_prefix + "soft_update_target", i32, [vp, f32, vp])
+    _sig(_prefix + "set_lr", i32, [vp, f32])
+    _sig(_prefix + "lr", i32, [vp, P(f32)])
+    _sig(_prefix + "set_rmsprop", i32, [vp, f32, i32])
+    _sig(_prefix + "set_adam_betas", i32, [vp, f32, f32])
 _sig("rela_apex_learner_debug_optim", i32, [vp, P(vp), P(vp), P(i64)])
 _sig("rela_debug_seq_loss_grad", i32, [i32] * 5 + [vp] * 8 + [f32, f32, f64] + [vp] * 8)
 _sig("rela_debug_seq_head_backward", i32, [i32, i32] + [vp] * 10)

@@ -262,6 +262,35 @@ extern "C" int rela_apex_learner_sync_target(rela_apex_learner* l, void* stream_
   return repack(l, false, true, s);
 }
 
+extern "C" int rela_apex_learner_soft_update_target(rela_apex_learner* l, float tau, void* stream_) {
+  RELA_CHECK(l, RELA_EINVAL, "rela_apex_learner_soft_update_target: bad arguments");
+  if (int rc = l->check_soft_update("rela_apex_learner_soft_update_target", tau)) return rc;
+  hipStream_t s = (hipStream_t)stream_;
+  DeviceGuard g(l->device);
+  if (int rc = l->soft_update_target(tau, s)) return rc;
+  return repack(l, false, true, s);
+}
+
+extern "C" int rela_apex_learner_set_lr(rela_apex_learner* l, float lr) {
+  RELA_CHECK(l, RELA_EINVAL, "rela_apex_learner_set_lr: bad arguments");
+  return l->set_lr("rela_apex_learner_set_lr", lr);
+}
+
+extern "C" int rela_apex_learner_lr(rela_apex_learner* l, float* out) {
+  RELA_CHECK(l, RELA_EINVAL, "rela_apex_learner_lr: bad arguments");
+  return l->get_lr("rela_apex_learner_lr", out);
+}
+
+extern "C" int rela_apex_learner_set_rmsprop(rela_apex_learner* l, float alpha, int centered) {
+  RELA_CHECK(l, RELA_EINVAL, "rela_apex_learner_set_rmsprop: bad arguments");
+  return l->set_rmsprop("rela_apex_learner_set_rmsprop", alpha, centered);
+}
+
+extern "C" int rela_apex_learner_set_adam_betas(rela_apex_learner* l, float b1, float b2) {
+  RELA_CHECK(l, RELA_EINVAL, "rela_apex_learner_set_adam_betas: bad arguments");
+  return l->set_adam_betas("rela_apex_learner_set_adam_betas", b1, b2);
+}
+
 extern "C" int rela_apex_learner_params(rela_apex_learner* l, rela_ffnet_params* online_out,
                                         rela_ffnet_params* target_out) {
   RELA_CHECK(l, RELA_EINVAL, "rela_apex_learner_params: bad arguments");
@@ -581,15 +610,16 @@ extern "C" int rela_apex_learner_debug_head_grads(rela_apex_learner* l, float** 
 
 // Test tap: optimizer_apply (learner_common.h) itself on the caller's flat buffers: the norm, the clip coefficient and one
 // RMSprop / Adam update.  The OptimState, the 256 partial sums, the abort word and the skip counter live for this one call.
-extern "C" int rela_debug_optimizer_apply(int optimizer, float lr, float eps, float clip, int64_t adam_steps_done, int64_t n,
-                                          float* p, const float* g, float* s1, float* s2, float* stats_out, int abort,
-                                          unsigned* skipped_out, void* stream_) {
+// (`who`: rela_debug_optimizer_apply, whose options are OptimState's defaults, or rela_debug_optimizer_apply_opts)
+static int debug_optimizer_apply(const char* who, const OptimState& options, int optimizer, float lr, float eps, float clip,
+                                 int64_t adam_steps_done, int64_t n, float* p, const float* g, float* s1, float* s2,
+                                 float* stats_out, int abort, unsigned* skipped_out, void* stream_) {
   RELA_CHECK((optimizer == 0 || optimizer == 1) && adam_steps_done >= 0 && n > 0 && n % 4 == 0 && (abort == 0 || abort == 1),
-             RELA_EINVAL, "rela_debug_optimizer_apply: bad arguments (optimizer %d, steps done %lld, n %lld, abort %d)",
-             optimizer, (long long)adam_steps_done, (long long)n, abort);
-  RELA_CHECK(p && g && s1 && s2 && stats_out, RELA_EINVAL, "rela_debug_optimizer_apply: a pointer is NULL");
+             RELA_EINVAL, "%s: bad arguments (optimizer %d, steps done %lld, n %lld, abort %d)", who, optimizer,
+             (long long)adam_steps_done, (long long)n, abort);
+  RELA_CHECK(p && g && s1 && s2 && stats_out, RELA_EINVAL, "%s: a pointer is NULL", who);
   for (const void* b : {(const void*)p, (const void*)g, (const void*)s1, (const void*)s2})
-    RELA_CHECK(((uintptr_t)b & 15) == 0, RELA_EINVAL, "rela_debug_optimizer_apply: a buffer is not 16-byte aligned");
+    RELA_CHECK(((uintptr_t)b & 15) == 0, RELA_EINVAL, "%s: a buffer is not 16-byte aligned", who);
   hipStream_t s = (hipStream_t)stream_;
   struct Scratch {
     DevBuffers mem;
@@ -600,7 +630,7 @@ extern "C" int rela_debug_optimizer_apply(int optimizer, float lr, float eps, fl
   if (int rc = sc.mem.alloc(&npart, kNormBlocks, false)) return rc;
   if (int rc = sc.mem.alloc(&words, 2, true)) return rc;
   if (abort) RELA_HIP(hipMemsetD32Async((hipDeviceptr_t)words, 1, 1, s));
-  OptimState o;
+  OptimState o = options;
   o.optimizer = optimizer, o.lr = lr, o.eps = eps, o.clip = clip, o.adam_t = adam_steps_done;
   optimizer_apply(o, p, g, s1, s2, n, npart, stats_out, s, words, words + 1, true);
   const hipError_t launched = hipGetLastError();
@@ -608,6 +638,43 @@ extern "C" int rela_debug_optimizer_apply(int optimizer, float lr, float eps, fl
   RELA_HIP(launched);
   RELA_HIP(done);
   if (skipped_out) RELA_HIP(hipMemcpy(skipped_out, words + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
+  return RELA_OK;
+}
+
+extern "C" int rela_debug_optimizer_apply(int optimizer, float lr, float eps, float clip, int64_t adam_steps_done, int64_t n,
+                                          float* p, const float* g, float* s1, float* s2, float* stats_out, int abort,
+                                          unsigned* skipped_out, void* stream_) {
+  return debug_optimizer_apply("rela_debug_optimizer_apply", OptimState(), optimizer, lr, eps, clip, adam_steps_done, n, p, g,
+                               s1, s2, stats_out, abort, skipped_out, stream_);
+}
+
+// Test tap: as rela_debug_optimizer_apply, with the options of rela_*_learner_set_rmsprop / _set_adam_betas
+extern "C" int rela_debug_optimizer_apply_opts(int optimizer, float lr, float eps, float clip, int64_t adam_steps_done,
+                                               int64_t n, float* p, const float* g, float* s1, float* s2, float* stats_out,
+                                               int abort, unsigned* skipped_out, float alpha, int centered, float b1, float b2,
+                                               void* stream_) {
+  RELA_CHECK(rmsprop_options_ok(alpha, centered) && adam_betas_ok(b1, b2), RELA_EINVAL,
+             "rela_debug_optimizer_apply_opts: bad options (alpha %g, centered %d, betas %g / %g)", (double)alpha, centered,
+             (double)b1, (double)b2);
+  OptimState options;
+  options.alpha = alpha, options.centered = centered != 0, options.b1 = b1, options.b2 = b2;
+  return debug_optimizer_apply("rela_debug_optimizer_apply_opts", options, optimizer, lr, eps, clip, adam_steps_done, n, p, g,
+                               s1, s2, stats_out, abort, skipped_out, stream_);
+}
+
+// Test tap: target_lerp (learner_common.h), the kernel of rela_*_learner_soft_update_target, on the caller's flat buffers
+extern "C" int rela_debug_target_lerp(int64_t n, float tau, float* pt, const float* p, void* stream_) {
+  RELA_CHECK(n > 0 && n % 4 == 0 && tau > 0.f && tau <= 1.f, RELA_EINVAL, "rela_debug_target_lerp: bad arguments (n %lld, tau %g)",
+             (long long)n, (double)tau);
+  RELA_CHECK(pt && p, RELA_EINVAL, "rela_debug_target_lerp: a pointer is NULL");
+  RELA_CHECK((((uintptr_t)pt | (uintptr_t)p) & 15) == 0, RELA_EINVAL, "rela_debug_target_lerp: a buffer is not 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream_;
+  note_launch("target_lerp");
+  hipLaunchKernelGGL(target_lerp, dim3(ceil_div(n / 4, 256)), dim3(256), 0, s, pt, p, n / 4, tau);
+  const hipError_t launched = hipGetLastError();
+  const hipError_t done = hipStreamSynchronize(s);
+  RELA_HIP(launched);
+  RELA_HIP(done);
   return RELA_OK;
 }
 

@@ -629,6 +629,42 @@ __global__ void rmsprop_update(float* __restrict__ p, const float* __restrict__ 
   reinterpret_cast<float4*>(sq)[i] = sv;
   reinterpret_cast<float4*>(p)[i] = pv;
 }
+// torch.optim.RMSprop(centered=True) (momentum 0): sq as above, av = alpha*av + (1-alpha)*g (the gradient average), and the
+// step divides by sqrt(sq - av*av) + eps.  One departure from torch, on purpose: sq - av*av is clamped at 0 before the square
+// root.  In float32 the difference goes negative once alpha^k has dropped below the rounding unit (an element whose gradient
+// barely changes: sq and av*av then agree to the last bit or two), and torch's float32 sqrt of it makes the weight NaN for good.
+// The clamp is a comparison, not fmaxf: a NaN variance stays NaN, so a NaN gradient still shows in its weight.
+__global__ void rmsprop_centered_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sq,
+                                        float* __restrict__ av, int64_t n4, float lr, float alpha, float eps,
+                                        const float* __restrict__ coef) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const float cf = coef[1];
+  if (i >= n4 || cf < 0.f) return;
+  const float4 gv = reinterpret_cast<const float4*>(g)[i];
+  float4 sv = reinterpret_cast<float4*>(sq)[i], mv = reinterpret_cast<float4*>(av)[i], pv = reinterpret_cast<float4*>(p)[i];
+  auto upd = [&](float gi, float& s, float& m, float& pi) {
+    gi = gi * cf;
+    s = alpha * s + (1.0f - alpha) * gi * gi;
+    m = alpha * m + (1.0f - alpha) * gi;
+    float v = s - m * m;
+    v = v < 0.0f ? 0.0f : v;
+    pi -= lr * (gi / (sqrtf(v) + eps));
+  };
+  upd(gv.x, sv.x, mv.x, pv.x), upd(gv.y, sv.y, mv.y, pv.y), upd(gv.z, sv.z, mv.z, pv.z), upd(gv.w, sv.w, mv.w, pv.w);
+  reinterpret_cast<float4*>(sq)[i] = sv;
+  reinterpret_cast<float4*>(av)[i] = mv;
+  reinterpret_cast<float4*>(p)[i] = pv;
+}
+// soft (Polyak) target update over the flat buffers: pt = pt + tau * (p - pt); the pads stay +0 (0 + tau * (0 - 0))
+__global__ void target_lerp(float* __restrict__ pt, const float* __restrict__ p, int64_t n4, float tau) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  const float4 pv = reinterpret_cast<const float4*>(p)[i];
+  float4 tv = reinterpret_cast<float4*>(pt)[i];
+  tv.x = tv.x + tau * (pv.x - tv.x), tv.y = tv.y + tau * (pv.y - tv.y);
+  tv.z = tv.z + tau * (pv.z - tv.z), tv.w = tv.w + tau * (pv.w - tv.w);
+  reinterpret_cast<float4*>(pt)[i] = tv;
+}
 // torch.optim.Adam (no amsgrad, no weight decay); bias corrections computed on the host per step
 __global__ void adam_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m1,
                             float* __restrict__ m2, int64_t n4, float lr, float b1, float b2, float eps, float bc1,
@@ -806,10 +842,17 @@ inline int trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending 
 
 // ---- clip_grad_norm_ + optimiser over flat parameter / gradient / state buffers -------------------
 struct OptimState {
-  int optimizer = 0;  // 0 RMSprop (torch defaults alpha 0.99), 1 Adam (betas 0.9 / 0.999)
+  int optimizer = 0;  // 0 RMSprop, 1 Adam
   float lr = 0.f, eps = 0.f, clip = 0.f;
   int64_t adam_t = 0;
+  // torch's defaults; *_learner_set_rmsprop / _set_adam_betas change them while the state is the zero state
+  float alpha = 0.99f;    // RMSprop's decay
+  bool centered = false;  // RMSprop: S2 = the gradient average, rmsprop_centered_update (else S2 is never touched)
+  float b1 = 0.9f, b2 = 0.999f;  // Adam's betas
 };
+// the ranges of the option setters and of rela_debug_optimizer_apply_opts (a NaN fails every comparison)
+inline bool rmsprop_options_ok(float alpha, int centered) { return alpha > 0.f && alpha < 1.f && (centered == 0 || centered == 1); }
+inline bool adam_betas_ok(float b1, float b2) { return b1 >= 0.f && b1 < 1.f && b2 > 0.f && b2 < 1.f; }
 // adam_t counts every Adam apply launched; one that the device skipped (abort_word) adds one to *skipped, which the
 // owner of abort_word takes off adam_t again once it has read the word.  census: rela_debug_optimizer_apply counts its
 // three launches (the learners' steps do not: their censuses are recorded ones).
@@ -822,14 +865,17 @@ inline void optimizer_apply(OptimState& o, float* P, const float* G, float* S1, 
                      skipped);
   if (census) {
     note_launch("sumsq_partial"), note_launch("clip_coef");
-    note_launch(o.optimizer == 0 ? "rmsprop_update" : "adam_update");
+    note_launch(o.optimizer != 0 ? "adam_update" : o.centered ? "rmsprop_centered_update" : "rmsprop_update");
   }
-  if (o.optimizer == 0) {
-    hipLaunchKernelGGL(rmsprop_update, dim3(ceil_div(n / 4, 256)), dim3(256), 0, s, P, G, S1, n / 4, o.lr, 0.99f, o.eps,
+  if (o.optimizer == 0 && o.centered) {
+    hipLaunchKernelGGL(rmsprop_centered_update, dim3(ceil_div(n / 4, 256)), dim3(256), 0, s, P, G, S1, S2, n / 4, o.lr,
+                       o.alpha, o.eps, (const float*)norm);
+  } else if (o.optimizer == 0) {
+    hipLaunchKernelGGL(rmsprop_update, dim3(ceil_div(n / 4, 256)), dim3(256), 0, s, P, G, S1, n / 4, o.lr, o.alpha, o.eps,
                        (const float*)norm);
   } else {
     o.adam_t += 1;
-    const float b1 = 0.9f, b2 = 0.999f;
+    const float b1 = o.b1, b2 = o.b2;
     const float bc1 = 1.0f - (float)pow((double)b1, (double)o.adam_t);
     const float bc2s = (float)sqrt(1.0 - pow((double)b2, (double)o.adam_t));
     hipLaunchKernelGGL(adam_update, dim3(ceil_div(n / 4, 256)), dim3(256), 0, s, P, G, S1, S2, n / 4, o.lr, b1, b2, o.eps,
@@ -849,6 +895,7 @@ struct LearnerCore {
   float vr_eps = 0.f;        // value rescaling of the TD target (set_value_rescale), 0 = off
   bool loss_called = false;  // ... which is fixed from the first loss on
   OptimState opt;
+  bool applied = false;  // an apply was launched since create / the last load: S1 / S2 are no longer the zero state
   int nseg = 0;
   int64_t cnt[kLstmNetSegs] = {0};      // elements per tensor
   int64_t off[kLstmNetSegs + 1] = {0};  // segment offsets, off[nseg] = total
@@ -885,10 +932,53 @@ struct LearnerCore {
     RELA_HIP(hipMemsetAsync(S1, 0, nb, s));
     RELA_HIP(hipMemsetAsync(S2, 0, nb, s));
     opt.adam_t = 0;
+    applied = false;  // (the options and the learning rate stay)
     return RELA_OK;
   }
   int copy_online_to_target(hipStream_t s) {  // apex.py:27
     RELA_HIP(hipMemcpyAsync(PT, P, sizeof(float) * (size_t)off[nseg], hipMemcpyDeviceToDevice, s));
+    return RELA_OK;
+  }
+  // Polyak update of the target net: PT += tau * (P - PT) over the whole flat buffer; tau == 1 is the copy, bit for bit
+  int soft_update_target(float tau, hipStream_t s) {
+    if (tau == 1.0f) return copy_online_to_target(s);
+    const int64_t n4 = off[nseg] / 4;
+    hipLaunchKernelGGL(target_lerp, dim3(ceil_div(n4, 256)), dim3(256), 0, s, PT, (const float*)P, n4, tau);
+    RELA_LAUNCH_CHECK();
+    return RELA_OK;
+  }
+  // the checks of rela_*_learner_soft_update_target; the caller then selects the device, calls soft_update_target and re-packs
+  int check_soft_update(const char* who, float tau) const {
+    RELA_CHECK(tau > 0.f && tau <= 1.f, RELA_EINVAL, "%s: tau must be in (0, 1] (got %g)", who, (double)tau);
+    RELA_CHECK(loaded, RELA_ESTATE, "%s: parameters were never loaded", who);
+    return RELA_OK;
+  }
+  int set_lr(const char* who, float lr) {
+    RELA_CHECK(lr >= 0.f && lr <= 3.402823466e+38f, RELA_EINVAL, "%s: lr must be finite and >= 0 (got %g)", who, (double)lr);
+    opt.lr = lr;  // the next apply passes it to its update kernel; no state, no step number
+    return RELA_OK;
+  }
+  int get_lr(const char* who, float* out) const {
+    RELA_CHECK(out, RELA_EINVAL, "%s: bad arguments", who);
+    *out = opt.lr;
+    return RELA_OK;
+  }
+  // The two option setters: only while S1 / S2 are the zero state (after create or a load, before the first apply since):
+  // S2 changes its meaning with `centered`, and a decay that changes under a running average has no counterpart in torch.
+  int set_rmsprop(const char* who, float alpha, int centered) {
+    RELA_CHECK(opt.optimizer == 0, RELA_EINVAL, "%s: this learner's optimiser is Adam, not RMSprop", who);
+    RELA_CHECK(rmsprop_options_ok(alpha, centered), RELA_EINVAL, "%s: alpha must be in (0, 1) and centered 0 or 1 (got %g, %d)",
+               who, (double)alpha, centered);
+    RELA_CHECK(!applied, RELA_ESTATE, "%s: call it before the first apply after create or load", who);
+    opt.alpha = alpha, opt.centered = centered != 0;
+    return RELA_OK;
+  }
+  int set_adam_betas(const char* who, float b1, float b2) {
+    RELA_CHECK(opt.optimizer == 1, RELA_EINVAL, "%s: this learner's optimiser is RMSprop, not Adam", who);
+    RELA_CHECK(adam_betas_ok(b1, b2), RELA_EINVAL, "%s: betas must be in [0, 1) and (0, 1) (got %g, %g)", who, (double)b1,
+               (double)b2);
+    RELA_CHECK(!applied, RELA_ESTATE, "%s: call it before the first apply after create or load", who);
+    opt.b1 = b1, opt.b2 = b2;
     return RELA_OK;
   }
   // params_out: the net's params struct; its nseg pointers into the flat buffer at `base`
@@ -910,6 +1000,7 @@ struct LearnerCore {
   }
   void apply(hipStream_t s, const unsigned* abort_word = nullptr, unsigned* skipped = nullptr) {
     optimizer_apply(opt, P, G, S1, S2, off[nseg], npart, norm, s, abort_word, skipped);
+    applied = true;  // (also when the device skips it on the abort word: the host cannot know yet)
   }
   int debug_optim(const char* who, float** s1_dev, float** s2_dev, int64_t* adam_t) const {
     RELA_CHECK(s1_dev && s2_dev && adam_t, RELA_EINVAL, "%s: bad arguments", who);

@@ -1064,6 +1064,36 @@ extern "C" int rela_r2d2_learner_sync_target(rela_r2d2_learner* l, void* stream_
   return repack_r2d2(l, false, true, s);
 }
 
+// (the timeout word does not gate it: the online weights it reads are the ones no skipped apply has touched)
+extern "C" int rela_r2d2_learner_soft_update_target(rela_r2d2_learner* l, float tau, void* stream_) {
+  RELA_CHECK(l, RELA_EINVAL, "rela_r2d2_learner_soft_update_target: bad arguments");
+  if (int rc = l->check_soft_update("rela_r2d2_learner_soft_update_target", tau)) return rc;
+  hipStream_t s = (hipStream_t)stream_;
+  DeviceGuard g(l->device);
+  if (int rc = l->soft_update_target(tau, s)) return rc;
+  return repack_r2d2(l, false, true, s);
+}
+
+extern "C" int rela_r2d2_learner_set_lr(rela_r2d2_learner* l, float lr) {
+  RELA_CHECK(l, RELA_EINVAL, "rela_r2d2_learner_set_lr: bad arguments");
+  return l->set_lr("rela_r2d2_learner_set_lr", lr);
+}
+
+extern "C" int rela_r2d2_learner_lr(rela_r2d2_learner* l, float* out) {
+  RELA_CHECK(l, RELA_EINVAL, "rela_r2d2_learner_lr: bad arguments");
+  return l->get_lr("rela_r2d2_learner_lr", out);
+}
+
+extern "C" int rela_r2d2_learner_set_rmsprop(rela_r2d2_learner* l, float alpha, int centered) {
+  RELA_CHECK(l, RELA_EINVAL, "rela_r2d2_learner_set_rmsprop: bad arguments");
+  return l->set_rmsprop("rela_r2d2_learner_set_rmsprop", alpha, centered);
+}
+
+extern "C" int rela_r2d2_learner_set_adam_betas(rela_r2d2_learner* l, float b1, float b2) {
+  RELA_CHECK(l, RELA_EINVAL, "rela_r2d2_learner_set_adam_betas: bad arguments");
+  return l->set_adam_betas("rela_r2d2_learner_set_adam_betas", b1, b2);
+}
+
 extern "C" int rela_r2d2_learner_params(rela_r2d2_learner* l, rela_lstmnet_params* online_out,
                                         rela_lstmnet_params* target_out) {
   RELA_CHECK(l, RELA_EINVAL, "rela_r2d2_learner_params: bad arguments");

@@ -131,6 +131,37 @@ class _HipLearner:
     def sync_target_with_online(self):
         self._call("sync_target", self._stream())
 
+    def soft_update_target(self, tau):
+        """Polyak update of the target net: target += tau * (online - target), 0 < tau <= 1 (1: the whole copy)."""
+        self._call("soft_update_target", float(tau), self._stream())
+
+    def set_lr(self, lr):
+        """The learning rate of the next apply(); touches neither the optimiser state nor the Adam step number."""
+        self._call("set_lr", float(lr))
+
+    @property
+    def lr(self):
+        out = self._C.c_float()
+        self._call("lr", self._C.byref(out))
+        return out.value
+
+    def set_rmsprop(self, alpha=0.99, centered=False):
+        """RMSprop's decay and the centred form (variance = square average - average^2, clamped at 0: DESIGN 4.6).
+        Before the first apply() after the constructor or a load only; refused on an Adam learner."""
+        self._call("set_rmsprop", float(alpha), int(bool(centered)))
+
+    def set_adam_betas(self, b1, b2):
+        """Adam's betas; timing as set_rmsprop; refused on an RMSprop learner."""
+        self._call("set_adam_betas", float(b1), float(b2))
+
+    def _set_options(self, alpha, centered, betas):
+        """the constructors' alpha= / centered= / betas=: nothing is called for what was left at its default (so an Adam
+        learner is never asked for RMSprop's defaults, which it would refuse)"""
+        if float(alpha) != 0.99 or centered:
+            self.set_rmsprop(alpha, centered)
+        if tuple(float(b) for b in betas) != (0.9, 0.999):
+            self.set_adam_betas(*betas)
+
     def state_dict(self, which="online"):
         """Zero-copy views of the flat parameter buffer as a state_dict ("online" | "target" | "grads")."""
         p = self._struct(which)
@@ -224,9 +255,10 @@ class HipApexLearner(_HipLearner):
               "bootstrap")
 
     def __init__(self, num_action, max_batch, multi_step, gamma, optimizer="rmsprop", lr=6.25e-5, eps=1.5e-4,
-                 grad_clip=40.0, device="cuda:0"):
+                 grad_clip=40.0, device="cuda:0", alpha=0.99, centered=False, betas=(0.9, 0.999)):
         self._create(device, num_action, max_batch, multi_step, gamma, {"rmsprop": 0, "adam": 1}[optimizer], lr, eps,
                      grad_clip)
+        self._set_options(alpha, centered, betas)
 
     @classmethod
     def from_agent(cls, agent, max_batch, **kw):
@@ -313,10 +345,11 @@ class HipR2D2Learner(_HipLearner):
                         (2048,), (2048,), (1, 512), (1,), (A, 512), (A,))
 
     def __init__(self, num_action, max_batch, multi_step, gamma, seq_len, burn_in, eta, optimizer="adam", lr=6.25e-5,
-                 eps=1.5e-4, grad_clip=40.0, device="cuda:0"):
+                 eps=1.5e-4, grad_clip=40.0, device="cuda:0", alpha=0.99, centered=False, betas=(0.9, 0.999)):
         self.seq_len, self.burn_in, self.multi_step = seq_len, burn_in, multi_step
         self._create(device, num_action, max_batch, multi_step, gamma, seq_len, burn_in, float(eta),
                      {"rmsprop": 0, "adam": 1}[optimizer], lr, eps, grad_clip)
+        self._set_options(alpha, centered, betas)
         self._loss_seq = torch.empty(max_batch, dtype=torch.float32, device=self.device)
 
     @classmethod

@@ -30,6 +30,12 @@ def masked_greedy(q: torch.Tensor, legal: torch.Tensor) -> torch.Tensor:
     return shifted.argmax(1)
 
 
+def polyak_update(target_net: nn.Module, online_net: nn.Module, tau: float):
+    """pt = pt + tau * (p - pt) per parameter, in place, in that order; call under torch.no_grad()"""
+    for pt, p in zip(target_net.parameters(), online_net.parameters()):
+        pt.add_((p - pt) * tau)
+
+
 class ApexAgent(nn.Module):
     def __init__(self, net_cons, multi_step: int, gamma: float, value_rescale: float = 0.0):
         super().__init__()
@@ -48,6 +54,12 @@ class ApexAgent(nn.Module):
 
     def sync_target_with_online(self):
         self.target_net.load_state_dict(self.online_net.state_dict())
+
+    @torch.no_grad()
+    def soft_update_target(self, tau: float):
+        """Polyak update target += tau * (online - target), the learners' formula (csrc/learner_common.h: target_lerp);
+        no reference counterpart"""
+        polyak_update(self.target_net, self.online_net, tau)
 
     def greedy_act(self, obs: Dict[str, torch.Tensor]) -> torch.Tensor:
         with torch.no_grad():

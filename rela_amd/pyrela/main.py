@@ -83,7 +83,76 @@ def parse_args(argv=None):
                    help="arithmetic of the HIP learner step (set_precision of rela_amd/learner.py): f32 = exact f32; bf16x2 "
                         "= two-part bf16 on the gradient-free forwards; f32x3 = f32-accurate three-part bf16 forwards; "
                         "f32x3_bwd (r2d2 only) = f32x3 plus the backward GEMMs on three-part bf16 operands")
+    # update rules beyond the reference's (torch's defaults, a fixed lr, the whole target copy); the defaults give its runs
+    p.add_argument("--rmsprop_alpha", type=float, default=0.99, help="RMSprop's decay (apex; Ape-X as published: 0.95)")
+    p.add_argument("--rmsprop_centered", type=int, default=0, help="1: centred RMSprop (apex; Ape-X as published)")
+    p.add_argument("--adam_beta1", type=float, default=0.9, help="Adam's beta1 (r2d2)")
+    p.add_argument("--adam_beta2", type=float, default=0.999, help="Adam's beta2 (r2d2)")
+    p.add_argument("--lr_warmup_updates", type=int, default=0, help="linear warm-up of the learning rate over so many updates")
+    p.add_argument("--lr_final", type=float, default=None, help="learning rate after the decay (default: --lr)")
+    p.add_argument("--lr_decay_updates", type=int, default=0,
+                   help="linear decay from --lr to --lr_final over so many updates after the warm-up; 0 = none")
+    p.add_argument("--target_tau", type=float, default=0.0,
+                   help="> 0: soft target updates target += tau * (online - target) every --target_update_freq updates after "
+                        "one whole copy at update 0; --num_update_between_sync is then ignored")
+    p.add_argument("--target_update_freq", type=int, default=1)
     return p.parse_args(argv)
+
+
+class UpdateRules:
+    """The update-rule flags of a run, checked against --algo: the optimiser options (as keywords of torch's optimiser and
+    of the HIP learner), the learning-rate schedule and how the target net moves.  Both loops (train, train_multi) drive
+    either a HIP learner or the agent with its torch optimiser through it; the defaults live in parse_args alone, and with
+    them nothing new is called."""
+
+    def __init__(self, args, quiet=False):
+        self.rmsprop = args.algo != "r2d2"  # pyrela/main.py:120,124: RMSprop for apex, Adam for r2d2
+        self.alpha, self.centered = float(args.rmsprop_alpha), bool(args.rmsprop_centered)
+        self.betas = (float(args.adam_beta1), float(args.adam_beta2))
+        if self.rmsprop and self.betas != (0.9, 0.999):
+            raise SystemExit("--adam_beta1 / --adam_beta2 are Adam's (--algo r2d2): --algo apex trains with RMSprop")
+        if not self.rmsprop and (self.alpha != 0.99 or self.centered):
+            raise SystemExit("--rmsprop_alpha / --rmsprop_centered are RMSprop's (--algo apex): --algo r2d2 trains with Adam")
+        if not 0 < self.alpha < 1 or not 0 <= self.betas[0] < 1 or not 0 < self.betas[1] < 1:
+            raise SystemExit("--rmsprop_alpha and --adam_beta2 must lie in (0, 1), --adam_beta1 in [0, 1)")
+        self.lr, self.warmup, self.decay = args.lr, int(args.lr_warmup_updates), int(args.lr_decay_updates)
+        self.lr_final = args.lr_final  # (None: --lr)
+        self.tau, self.freq = float(args.target_tau), int(args.target_update_freq)
+        if not 0 <= self.tau <= 1 or self.freq < 1 or self.warmup < 0 or self.decay < 0:
+            raise SystemExit("--target_tau must lie in [0, 1], --target_update_freq be >= 1, the update counts >= 0")
+        self.sync_every = args.num_update_between_sync
+        self.lr_now = args.lr
+        if self.tau > 0 and not quiet:
+            print("--target_tau %g: soft target updates every %d updates; --num_update_between_sync %d is ignored" % (
+                self.tau, self.freq, self.sync_every))
+
+    def torch_kw(self):
+        """keywords of torch.optim.RMSprop / Adam"""
+        return dict(alpha=self.alpha, centered=self.centered) if self.rmsprop else dict(betas=self.betas)
+
+    def learner_kw(self):
+        """keywords of HipApexLearner / HipR2D2Learner (rela_amd/learner.py)"""
+        return dict(alpha=self.alpha, centered=self.centered) if self.rmsprop else dict(betas=self.betas)
+
+    def before_update(self, num_update, learner, agent, optim):
+        """what precedes the step of update `num_update`: the target net's move and the learning rate of that step (set
+        only when the schedule changes it)"""
+        net = learner if learner is not None else agent
+        if self.tau > 0:
+            if num_update == 0:
+                net.sync_target_with_online()
+            elif num_update % self.freq == 0:
+                net.soft_update_target(self.tau)
+        elif num_update % self.sync_every == 0:
+            net.sync_target_with_online()
+        lr = utils.lr_at(num_update, self.lr, self.warmup, self.lr_final, self.decay)
+        if lr != self.lr_now:
+            self.lr_now = lr
+            if learner is not None:
+                learner.set_lr(lr)
+            else:
+                for group in optim.param_groups:
+                    group["lr"] = lr
 
 
 def learner_precision(args):
@@ -104,6 +173,7 @@ def train(args, on_epoch=None):
     if args.algo not in ("apex", "r2d2"):
         raise SystemExit("--algo must be apex or r2d2")
     precision = learner_precision(args)
+    rules = UpdateRules(args)
     torch.manual_seed(args.seed + 2)
     torch.cuda.manual_seed(args.seed + 3)
     pprint.pprint(vars(args))
@@ -113,19 +183,20 @@ def train(args, on_epoch=None):
         agent = R2D2Agent(lambda dev: AtariLSTMNet(dev, num_action), args.train_device, args.multi_step, args.gamma,
                           args.eta, args.seq_len, args.seq_burn_in, args.same_hid,
                           getattr(args, "value_rescale", 0.0)).to(args.train_device)
-        optim = torch.optim.Adam(agent.online_net.parameters(), lr=args.lr, eps=args.eps)
+        optim = torch.optim.Adam(agent.online_net.parameters(), lr=args.lr, eps=args.eps, **rules.torch_kw())
         replay_class = rela.RNNPrioritizedReplay
     else:  # :110-122
         agent = ApexAgent(lambda: AtariFFNet(num_action), args.multi_step, args.gamma,
                           getattr(args, "value_rescale", 0.0)).to(args.train_device)
-        optim = torch.optim.RMSprop(agent.online_net.parameters(), lr=args.lr, eps=args.eps)
+        optim = torch.optim.RMSprop(agent.online_net.parameters(), lr=args.lr, eps=args.eps, **rules.torch_kw())
         replay_class = rela.FFPrioritizedReplay
     learner = None
     if getattr(args, "hip_learner", 1):  # hand-written HIP learner step (csrc/learner.hip, csrc/learner_r2d2.hip)
         from rela_amd.learner import HipApexLearner, HipR2D2Learner
 
         cls = HipR2D2Learner if args.algo == "r2d2" else HipApexLearner
-        learner = cls.from_agent(agent, args.batchsize, lr=args.lr, eps=args.eps, grad_clip=args.grad_clip)
+        learner = cls.from_agent(agent, args.batchsize, lr=args.lr, eps=args.eps, grad_clip=args.grad_clip,
+                                 **rules.learner_kw())
         if precision != "f32":
             learner.set_precision(precision)
 
@@ -162,11 +233,7 @@ def train(args, on_epoch=None):
         watch = _LearnerWatch(learner, args.train_device)
         for batch_idx in range(args.epoch_len):
             num_update = batch_idx + epoch * args.epoch_len
-            if num_update % args.num_update_between_sync == 0:
-                if learner is not None:
-                    learner.sync_target_with_online()
-                else:
-                    agent.sync_target_with_online()
+            rules.before_update(num_update, learner, agent, optim)
             if num_update % args.actor_sync_freq == 0:
                 watch.poll()
                 if learner is not None:  # ModelLocker reads the Python model: hand it the current weights
@@ -194,7 +261,7 @@ def train(args, on_epoch=None):
             " (%d steps skipped after a learner timeout)" % watch.skipped) if watch.skipped else ""))
         rates = tach.lap(actors, replay_buffer, args.epoch_len * args.batchsize)
         history.append(dict(epoch=epoch, seconds=dt, train=rates[0], act=rates[1], buffer_add=rates[2],
-                            loss=mean_loss, skipped_steps=watch.skipped))
+                            loss=mean_loss, skipped_steps=watch.skipped, lr=rules.lr_now))
         if getattr(args, "num_eval_game", 0) > 0:  # main.py:264-278
             from rela_amd.pyrela.eval import evaluate
 
@@ -305,7 +372,9 @@ def _multi_worker(rank, world, args, port, results):
         to_namespace, learner_cls = ff_batch_namespace, HipApexLearner
     assert args.batchsize % G == 0 and args.num_thread % G == 0
     if rank == 0:
-        learner = learner_cls.from_agent(agent, args.batchsize, lr=args.lr, eps=args.eps, grad_clip=args.grad_clip)
+        rules = UpdateRules(args)
+        learner = learner_cls.from_agent(agent, args.batchsize, lr=args.lr, eps=args.eps, grad_clip=args.grad_clip,
+                                         **rules.learner_kw())
         if learner_precision(args) != "f32":
             learner.set_precision(learner_precision(args))
         # scheduled exchange: command words (a host synchronisation on every rank) only with the weight publish every
@@ -322,8 +391,7 @@ def _multi_worker(rank, world, args, port, results):
             watch = _LearnerWatch(learner, my_device)
             for batch_idx in range(args.epoch_len):
                 num_update = batch_idx + epoch * args.epoch_len
-                if num_update % args.num_update_between_sync == 0:
-                    learner.sync_target_with_online()
+                rules.before_update(num_update, learner, None, None)
                 if num_update % args.actor_sync_freq == 0:  # ONE broadcast per flat buffer instead of load_state_dict
                     watch.poll()
                     if native:  # (the actors read the mapped buffers themselves)
@@ -341,7 +409,7 @@ def _multi_worker(rank, world, args, port, results):
             mean_loss = watch.mean_loss()
             dt = time.time() - t0
             history.append(dict(epoch=epoch, seconds=dt, train=args.epoch_len * args.batchsize / dt,
-                                loss=mean_loss, skipped_steps=watch.skipped))
+                                loss=mean_loss, skipped_steps=watch.skipped, lr=rules.lr_now))
             print("epoch: %d, time: %.1fs, loss: %.5f, train: %.1f samples/s" % (
                 epoch, dt, history[-1]["loss"], history[-1]["train"]), flush=True)
         replay.stop()
@@ -463,6 +531,7 @@ def train_multi(args):
     if args.algo not in ("apex", "r2d2"):
         raise SystemExit("--algo must be apex or r2d2")
     learner_precision(args)  # (refused here, before any process is spawned)
+    UpdateRules(args, quiet=True)  # (likewise; the learner's rank builds and announces its own)
     if args.algo == "r2d2" and os.environ.get("RELA_REPLAY_DEDUP"):
         # the learner process would read the partitions' rows through IPC, and a sequence partition with de-duplicated
         # stacks holds references, not frames: the library refuses to export it (rela_replay_export_chunks)

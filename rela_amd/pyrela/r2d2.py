@@ -9,7 +9,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from .apex import value_rescale_h, value_rescale_h_inv
+from .apex import polyak_update, value_rescale_h, value_rescale_h_inv
 
 
 class R2D2Agent(nn.Module):
@@ -35,6 +35,11 @@ class R2D2Agent(nn.Module):
 
     def sync_target_with_online(self):
         self.target_net.load_state_dict(self.online_net.state_dict())
+
+    @torch.no_grad()
+    def soft_update_target(self, tau: float):
+        """as ApexAgent.soft_update_target"""
+        polyak_update(self.target_net, self.online_net, tau)
 
     @torch.no_grad()
     def act(self, obs, hid):

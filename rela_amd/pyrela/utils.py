@@ -14,6 +14,21 @@ def generate_eps(base_eps, alpha, num_actor):
     return [base_eps ** (1 + i / (num_actor - 1) * alpha) for i in range(num_actor)]
 
 
+def lr_at(num_update, lr, warmup=0, lr_final=None, decay_updates=0):
+    """The learning rate of update `num_update` (0-based; no reference counterpart): linear warm-up from lr / warmup at
+    update 0 to lr at update warmup - 1, then linear from lr (at update warmup) to lr_final over decay_updates updates,
+    lr_final afterwards.  decay_updates = 0 (or lr_final None): no decay, lr after the warm-up.  A pure function of the
+    update number, so replicated learners agree without an exchange.  warmup = decay_updates = 0 returns lr itself."""
+    if num_update < warmup:
+        return lr * ((num_update + 1) / warmup)  # (warmup / warmup is exactly 1: the ramp ends on lr itself)
+    if lr_final is None or decay_updates <= 0:
+        return lr
+    k = num_update - max(warmup, 0)
+    if k >= decay_updates:
+        return lr_final
+    return lr + (lr_final - lr) * (k / decay_updates)
+
+
 def total_acts(actors):
     return sum(a.num_act() for a in actors)
 
