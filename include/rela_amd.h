@@ -327,6 +327,24 @@ int rela_ffnet_debug_fc_stamps(const rela_ffnet* net, int n, const uint8_t* a3_r
                                void* stream);
 /* bytes of scratch rela_ffnet_forward needs for a batch of n */
 int64_t rela_ffnet_workspace_bytes(const rela_ffnet* net, int n);
+/* Test tap (host only: no launch, no synchronisation): where a forward of n rows at the net's current precision leaves
+ * every layer's output inside the CALLER's workspace, and which kernels its plan runs.  Offsets are bytes from the
+ * workspace's start, -1 for a field the net does not have; kinds are csrc/ffnet_plan.h's TrunkKind / FcKind (fc = -1 in
+ * an AtariLSTMNet).  The format of a1 / a2 / a3 says how the bytes at their offsets read:
+ *   RELA_WS_F32        channel-last f32 [n][pixels][C] at a1 / a2 / a3
+ *   RELA_WS_SPLIT_BF16 [n][pixels][hi C | lo C] bf16 at a2 / a3 (the f32 tensor's bytes), value = hi + lo
+ *   RELA_WS_SPLIT3     [n][pixels][part 0 C | part 1 C | part 2 C] bf16 at rec2 / rec3, value = p0 + p1 + p2
+ * fc_slices: partial tiles [fc_slices][n][512] f32 at fc_part where > 1 (h = relu(bias + their sum in slice order));
+ * fc_per: the positions of a3 (of 49) one slice of the split-K fc_bf16s contracts over, 0 for every other fc.
+ * gx (AtariLSTMNet): [n][2048] f32 raw sums of the x part of the gates, column = 4 * unit + gate, where x_in_gx. */
+enum { RELA_WS_NOT_WRITTEN = 0, RELA_WS_F32 = 1, RELA_WS_SPLIT_BF16 = 2, RELA_WS_SPLIT3 = 3 };
+typedef struct {
+  int64_t a1, a2, a3, h, ha, gx, fc_part, rec2, rec3;
+  int32_t precision, trunk, fc, fc_slices, fc_per;
+  int32_t a1_format, a2_format, a3_format;
+  int32_t a3_records, x_in_gx;
+} rela_debug_workspace_view;
+int rela_ffnet_debug_workspace(const rela_ffnet* net, int n, rela_debug_workspace_view* view);
 
 /* AtariFFNet.forward  net.py:42-55: q[n,A] (device f32) from s u8[n,4,84,84], legal f32[n,A] */
 int rela_ffnet_forward(const rela_ffnet* net, int n, const uint8_t* s_dev, const float* legal_dev,
@@ -384,6 +402,9 @@ int rela_lstmnet_precision(const rela_lstmnet* net);
 int rela_lstmnet_num_action(const rela_lstmnet* net);
 uint64_t rela_lstmnet_version(const rela_lstmnet* net); /* as rela_ffnet_version */
 int64_t rela_lstmnet_workspace_bytes(const rela_lstmnet* net, int n);
+/* as rela_ffnet_debug_workspace, for one rela_lstmnet_step of n rows: a1 | a2 | a3 | ha | gx, then the split3 records
+ * (h = fc_part = -1, fc = -1; a3_records: a3 stays in records for the gate GEMM's x part, which then goes to gx) */
+int rela_lstmnet_debug_workspace(const rela_lstmnet* net, int n, rela_debug_workspace_view* view);
 
 /* One time step for n rows: what AtariLSTMNet.act (net.py:110-124) and .forward with seq = 1
  * (:140-163) compute.  h_in/c_in/h_out/c_out are f32[n,512] (in and out may not alias);

@@ -65,6 +65,13 @@ class FFNetParams(C.Structure):
                                   "v_w", "v_b", "a_w", "a_b")]
 
 
+class DebugWorkspaceView(C.Structure):  # rela_debug_workspace_view
+    NOT_WRITTEN, F32, SPLIT_BF16, SPLIT3 = 0, 1, 2, 3  # a1 / a2 / a3 formats
+    _fields_ = ([(n, C.c_int64) for n in ("a1", "a2", "a3", "h", "ha", "gx", "fc_part", "rec2", "rec3")] +
+                [(n, C.c_int32) for n in ("precision", "trunk", "fc", "fc_slices", "fc_per", "a1_format", "a2_format",
+                                          "a3_format", "a3_records", "x_in_gx")])
+
+
 MISSING = []  # symbols of include/rela_amd.h the loaded library lacks (tests assert this is empty)
 
 
@@ -171,6 +178,8 @@ _sig("rela_lstmnet_debug_layout", i32, [vp, i32, P(C.c_char_p), P(i64), P(i32), 
 _sig("rela_lstmnet_set_precision", i32, [vp, i32])
 _sig("rela_lstmnet_precision", i32, [vp])
 _sig("rela_ffnet_workspace_bytes", i64, [vp, i32])
+_sig("rela_ffnet_debug_workspace", i32, [vp, i32, P(DebugWorkspaceView)])
+_sig("rela_lstmnet_debug_workspace", i32, [vp, i32, P(DebugWorkspaceView)])
 _sig("rela_ffnet_forward", i32, [vp, i32, vp, vp, vp, vp, i64, vp])
 _sig("rela_lstmnet_create", i32, [P(vp), i32, i32])
 _sig("rela_lstmnet_destroy", None, [vp])

@@ -2294,6 +2294,28 @@ int rela_amd::ffnet_forward_mode(const rela_ffnet* n, int N, const uint8_t* s_de
   return RELA_OK;
 }
 
+// Test tap: the workspace offsets and the plan of a forward of N rows at the net's precision, from the helpers the
+// forward itself calls (host only)
+extern "C" int rela_ffnet_debug_workspace(const rela_ffnet* n, int N, rela_debug_workspace_view* v) {
+  RELA_CHECK(n && v && N >= 1, RELA_EINVAL, "rela_ffnet_debug_workspace: bad arguments");
+  char* const ws = reinterpret_cast<char*>((uintptr_t)1 << 30);  // (never dereferenced: offsets only)
+  auto off = [&](const void* p) { return (int64_t)(static_cast<const char*>(p) - ws); };
+  const FFNetWs w = ffnet_ws(ws, N);
+  const FfnetPlan plan = plan_ffnet_forward(kModeNet, n->precision, N, n->max_rows);
+  *v = rela_debug_workspace_view{};
+  v->a1 = off(w.a1), v->a2 = off(w.a2), v->a3 = off(w.a3), v->h = off(w.h), v->ha = off(w.ha), v->gx = -1;
+  v->fc_part = off(fc_part_ptr(ws, w.ha, N));
+  v->rec2 = ws_records_offset(N), v->rec3 = v->rec2 + (int64_t)N * kRec2Bytes;
+  v->precision = plan.precision, v->trunk = plan.trunk, v->fc = plan.fc, v->fc_per = plan.fc_per;
+  v->fc_slices = (plan.fc == kFcS3 || plan.fc == kFcS3SplitK) ? s3::plan<s3::ProbFc>(N, plan.fc == kFcS3SplitK).slices : plan.fc_slices;
+  const int fmt = plan.trunk == kTrunkF32 ? RELA_WS_F32 : (plan.trunk == kTrunkBf16 ? RELA_WS_SPLIT_BF16 : RELA_WS_SPLIT3);
+  v->a1_format = plan.trunk == kTrunkF32 || (plan.trunk == kTrunkS3 && plan.keep_f32) ? RELA_WS_F32 : RELA_WS_NOT_WRITTEN;
+  v->a2_format = fmt;
+  v->a3_format = plan.trunk == kTrunkBf16 && plan.unsplit_a3 ? RELA_WS_F32 : fmt;
+  v->a3_records = v->a3_format != RELA_WS_F32, v->x_in_gx = 0;
+  return RELA_OK;
+}
+
 // ---- the Ape-X learner's three forwards in split-bf16, one launch per layer (csrc/learner.hip) ----------------
 namespace rela_amd {
 namespace {
@@ -2431,6 +2453,29 @@ using ProbGateX3 = s3::ProbFcT<2048>;
 inline int64_t lstm_ws_records_offset(int batch) {
   return (((int64_t)sizeof(float) * kLstmWsFloats * (batch > 0 ? batch : 0) + 256) + 255) & ~(int64_t)255;
 }
+// the workspace of one rela_lstmnet_step of N rows and what the step runs at `precision` (the step and its test tap)
+struct LstmStepWs {
+  float *a1, *a2, *a3, *ha, *gx;
+  uint8_t *rec2, *rec3;
+  LstmTrunkPlan tp;
+  bool x_in_gx;  // the x part of the gates is a GEMM of its own over a3's records -> gx (raw sums, permuted gate columns)
+};
+inline LstmStepWs lstm_step_ws(void* ws, int N, int precision) {
+  LstmStepWs w;
+  w.a1 = static_cast<float*>(ws);
+  w.a2 = w.a1 + kA1 * N;
+  w.a3 = w.a2 + kA2 * N;
+  w.ha = w.a3 + kA3 * N;
+  w.gx = w.ha + kHA * N;
+  w.rec2 = static_cast<uint8_t*>(ws) + lstm_ws_records_offset(N);
+  w.rec3 = w.rec2 + (int64_t)N * kRec2Bytes;
+  // bf16x2 mode from kFastMinN rows up: a3 stays in split records, the x part of the gates is one split-bf16 GEMM
+  // (gemm_bf16s.h: 41 GFLOP at 3,200 rows) and the f32 MFMA kernel only adds h x W_hh (K = 512) and runs the cell
+  const bool fast_gates = precision == 1 && N >= kFastMinN;
+  w.tp = plan_lstm_trunk(precision == 1, precision == 2, /*has_rec_scratch=*/true, N, fast_gates);
+  w.x_in_gx = w.tp.trunk == kTrunkS3 || (w.tp.trunk == kTrunkBf16 && w.tp.a3_records);
+  return w;
+}
 const char* const kLstmActorNames[3] = {"conv1_bf16x3", "conv2_mfma", "conv3_mfma"};
 // the trunk of an AtariLSTMNet: the fused conv1 -> conv2 launches run under conv2's label
 inline TrunkLabels lstm_trunk_labels(const char* const* names) { return {names[0], names[1], names[2], names[1]}; }
@@ -2508,34 +2553,25 @@ extern "C" int rela_lstmnet_step(const rela_lstmnet* n, int N, const uint8_t* s_
   RELA_CHECK(((uintptr_t)s_dev & 15) == 0 && ((uintptr_t)ws & 15) == 0 && ((uintptr_t)h_in & 15) == 0, RELA_EINVAL,
              "rela_lstmnet_step: s_dev, h_in and workspace must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream_;
-  float* a1 = static_cast<float*>(ws);
-  float* a2 = a1 + kA1 * N;
-  float* a3 = a2 + kA2 * N;
-  float* ha = a3 + kA3 * N;
-  float* gx = ha + kHA * N;
+  const LstmStepWs w = lstm_step_ws(ws, N, n->precision);
+  float *const a1 = w.a1, *const a2 = w.a2, *const a3 = w.a3, *const ha = w.ha, *const gx = w.gx;
+  uint8_t *const rec2 = w.rec2, *const rec3 = w.rec3;
+  const LstmTrunkPlan tp = w.tp;
   const FFNetDev& d = n->d;
-  // bf16x2 mode from kFastMinN rows up: a3 stays in split records, the x part of the gates is one split-bf16 GEMM
-  // (gemm_bf16s.h: 41 GFLOP at 3,200 rows) and the f32 MFMA kernel only adds h x W_hh (K = 512) and runs the cell
-  const bool fast_gates = n->precision == 1 && N >= kFastMinN;
-  uint8_t* rec2 = static_cast<uint8_t*>(ws) + lstm_ws_records_offset(N);
-  uint8_t* rec3 = rec2 + (int64_t)N * kRec2Bytes;
-  const LstmTrunkPlan tp = plan_lstm_trunk(n->precision == 1, n->precision == 2, /*has_rec_scratch=*/true, N, fast_gates);
   TrunkOpts opts;
   opts.leave_a3_records = tp.a3_records;
   launch_trunk(d, tp.trunk, N, s_dev, a1, a2, a3, rec2, rec3, opts, lstm_trunk_labels(kLstmActorNames), s);
   // the x part of the gates (3136 -> 2048) over a3's records -> gx (raw sums, permuted gate columns), where the trunk
   // left records: as a three-part GEMM (f32x3) or a split-bf16 one (bf16x2)
-  bool x_in_gx = false;
+  const bool x_in_gx = w.x_in_gx;
   if (tp.trunk == kTrunkS3) {
     ProfScope prof("lstm_gates_x_f32x3", s);
     note_launch("gemm_s3<gates_x>");
     s3::launch<ProbGateX3, s3::kEpiRaw>(rec3, n->d.Wx3, nullptr, gx, N, s);
-    x_in_gx = true;
-  } else if (tp.trunk == kTrunkBf16 && tp.a3_records) {
+  } else if (x_in_gx) {
     int rc = gemm16::launch_rec64_nt(reinterpret_cast<const uint8_t*>(a3), n->d.Wrec, N, 2048, 49, gemm16::EpiPlain{gx, 2048}, s,
                                      "lstm_gates_x_bf16");
     if (rc != RELA_OK) return rc;
-    x_in_gx = true;
   }
   {
     ProfScope prof("lstm_gates_mfma", s);
@@ -2561,6 +2597,23 @@ extern "C" int rela_lstmnet_step(const rela_lstmnet* n, int N, const uint8_t* s_
     }
   }
   RELA_LAUNCH_CHECK();
+  return RELA_OK;
+}
+
+extern "C" int rela_lstmnet_debug_workspace(const rela_lstmnet* n, int N, rela_debug_workspace_view* v) {
+  RELA_CHECK(n && v && N >= 1, RELA_EINVAL, "rela_lstmnet_debug_workspace: bad arguments");
+  char* const ws = reinterpret_cast<char*>((uintptr_t)1 << 30);  // (never dereferenced: offsets only)
+  auto off = [&](const void* p) { return (int64_t)(static_cast<const char*>(p) - ws); };
+  const LstmStepWs w = lstm_step_ws(ws, N, n->precision);
+  *v = rela_debug_workspace_view{};
+  v->a1 = off(w.a1), v->a2 = off(w.a2), v->a3 = off(w.a3), v->h = -1, v->ha = off(w.ha), v->gx = off(w.gx), v->fc_part = -1;
+  v->rec2 = off(w.rec2), v->rec3 = off(w.rec3);
+  v->precision = n->precision, v->trunk = w.tp.trunk, v->fc = -1, v->fc_slices = 0, v->fc_per = 0;
+  const int fmt = w.tp.trunk == kTrunkF32 ? RELA_WS_F32 : (w.tp.trunk == kTrunkBf16 ? RELA_WS_SPLIT_BF16 : RELA_WS_SPLIT3);
+  v->a1_format = w.tp.trunk == kTrunkF32 ? RELA_WS_F32 : RELA_WS_NOT_WRITTEN;
+  v->a2_format = fmt;
+  v->a3_format = w.tp.trunk == kTrunkBf16 && !w.tp.a3_records ? RELA_WS_F32 : fmt;
+  v->a3_records = w.tp.a3_records, v->x_in_gx = w.x_in_gx;
   return RELA_OK;
 }
 
