@@ -62,6 +62,43 @@ int rela_atari_features_indexed(const uint8_t* screens_dev, const uint8_t* palet
                                 uint8_t* planes_dev, void* stream);
 
 /* ===================================================================================
+ * Device-resident Catch env  --  csrc/catch_env.hip over csrc/catch_game.h (the game, in integer arithmetic: a falling,
+ * drifting ball, a paddle moved by action % 3 - 1, +1 / -1 per landing, episodes of episode_len steps; observation
+ * [4][84][84] u8, plane 3 the newest, sliding by one plane per step, a reset repeating the first frame four times).
+ * `rows` games live in HBM; row r plays the game seeded seed + r, exactly as the host env synth_atari.CatchEnv(seed + r)
+ * does.  Every call is asynchronous on `stream` and successive calls on one object must be ordered (one stream, or
+ * rela_stream_wait_stream).  Observation buffers are [rows][4][84][84] u8 in device memory, 16-byte aligned -- in
+ * practice rela_*_actor_obs_slot().
+ *
+ * _create: RELA_ENODEV without a GPU; RELA_EINVAL for rows < 1, num_action < 3 or episode_len < 1.  No frame exists
+ *   before the first _reset.
+ * _reset: reset() of every row (the LCG stream continues) and its stack.
+ * _step: steps every row with action_dev[row] (i64), writes reward_dev (f32: exactly -1, 0 or +1) and terminal_dev (u8)
+ *   and, in the same launch (census: catch_step_render), the NEXT observation of every row to obs_dev.  The semantics are
+ *   VectorEnv::reset followed by act: a row whose episode ends reports terminal = 1 with the step's reward, and the
+ *   observation written for it is already the first of its next episode.  An action outside [0, num_action) is not an
+ *   error: the row stays exactly as it is (reward 0, terminal 0, the same observation) and its bad_actions counter
+ *   goes up by one.
+ *   obs_dev == NULL: the step alone (census: catch_step); _render then writes the current stacks (census: catch_render).
+ *   An actor shard WITH a replay needs this split: during post_step() all n + 1 history slots are live -- the slot of
+ *   the next observation still holds the oldest stack of the transition being inserted -- and post_step() takes the
+ *   reward: step, post_step, then render into the shard's obs_slot.
+ * _stats_dev: [4][rows] int32, per row: episodes finished, sum of their returns, the last one's return and length.
+ *   Each row writes only its own entries.
+ * _debug_state: [rows][8] int32 to the host -- LCG state bits, px, bx, by, dx, steps, ep_return, bad_actions; the call
+ *   synchronises the device.
+ * =================================================================================== */
+typedef struct rela_catch rela_catch;
+int rela_catch_create(rela_catch** out, int rows, int num_action, int episode_len, uint64_t seed, int device);
+void rela_catch_destroy(rela_catch* c);
+int rela_catch_reset(rela_catch* c, uint8_t* obs_dev, void* stream);
+int rela_catch_step(rela_catch* c, const int64_t* action_dev, uint8_t* obs_dev, float* reward_dev, uint8_t* terminal_dev,
+                    void* stream);
+int rela_catch_render(rela_catch* c, uint8_t* obs_dev, void* stream);
+const int32_t* rela_catch_stats_dev(const rela_catch* c);
+int rela_catch_debug_state(rela_catch* c, int32_t* host_dst);
+
+/* ===================================================================================
  * Prioritized replay  --  rela/prioritized_replay.h:173-348 (PrioritizedReplay<T>) over
  * :14-171 (ConcurrentQueue<T>), bound in rela/pybind.cc:37-59.
  *

@@ -95,6 +95,13 @@ _sig("rela_stream_wait_stream", i32, [vp, vp, i32])
 _sig("rela_memcpy_h2d_async", i32, [vp, vp, i64, vp, i32])
 _sig("rela_atari_features", i32, [vp, i32, i32, i32, vp, vp])
 _sig("rela_atari_features_indexed", i32, [vp, vp, i32, i32, i32, vp, vp])
+_sig("rela_catch_create", i32, [P(vp), i32, i32, i32, u64, i32])
+_sig("rela_catch_destroy", None, [vp])
+_sig("rela_catch_reset", i32, [vp, vp, vp])
+_sig("rela_catch_step", i32, [vp, vp, vp, vp, vp, vp])
+_sig("rela_catch_render", i32, [vp, vp, vp])
+_sig("rela_catch_stats_dev", vp, [vp])
+_sig("rela_catch_debug_state", i32, [vp, vp])
 _sig("rela_replay_set_decoupled_insert", i32, [vp, i32])
 _sig("rela_replay_export_ipc", i32, [vp, vp])
 _sig("rela_replay_import_ipc", i32, [P(vp), vp, i32])

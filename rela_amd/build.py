@@ -66,7 +66,8 @@ def build_pybind(verbose=False, force=False):
     libs = ["-L" + os.path.join(tdir, "lib"), "-ltorch", "-ltorch_cpu", "-lc10", "-ltorch_python",
             "-Wl,-rpath," + os.path.join(tdir, "lib")]
     hdrs = glob.glob(os.path.join(PYBIND_DIR, "include", "rela", "*.h")) + [os.path.join(ROOT, "include", "rela_amd.h"),
-                                                                             os.path.join(CSRC, "atari_screen.h")]
+                                                                             os.path.join(CSRC, "atari_screen.h"),
+                                                                             os.path.join(CSRC, "catch_game.h")]
     jobs = []
     outs = []
     for name, src, extra in (("rela", "rela_module.cc", ["-L" + PKG, "-lrela_amd", "-Wl,-rpath,$ORIGIN/.."]),

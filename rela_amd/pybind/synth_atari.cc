@@ -32,6 +32,8 @@
 #else
 #define RELA_HAS_SCREEN 0
 #endif
+// the Catch game, the same header the device env compiles (csrc/catch_env.hip); plain C++, so the oracle's build has it too
+#include "../csrc/catch_game.h"
 
 namespace py = pybind11;
 
@@ -186,6 +188,71 @@ class NullAtariEnv : public rela::Env RELA_FRAME_ROW_BASE {
   uint32_t state_;
   int steps_ = 0;
   bool terminal_ = true;
+  torch::Tensor eps_, legal_, frame_;
+};
+
+// Catch (csrc/catch_game.h): the one env here with something to learn -- a uniformly random policy scores about
+// -7 per 200 steps, walking the paddle towards bx - 4 catches every ball (+10).  The host twin of the device env
+// (csrc/catch_env.hip: row r of rela_catch_create(seed) is CatchEnv(seed + r)), a plain rela::Env whose stack slides.
+class CatchEnv : public rela::Env RELA_FRAME_ROW_BASE {
+ public:
+  CatchEnv(int seed, float eps, int numAction, int episodeLen) : numAction_(numAction), episodeLen_(episodeLen) {
+    if (numAction < 3 || episodeLen < 1) throw std::invalid_argument("CatchEnv: num_action >= 3 and episode_len >= 1");
+    game_ = catch_game::Game();
+    game_.seed(seed);
+    eps_ = torch::full({1}, eps, torch::kFloat32);
+    legal_ = torch::ones({numAction}, torch::kFloat32);
+    frame_ = torch::zeros({4, 84, 84}, torch::kUInt8);
+  }
+
+  int numAction() const { return numAction_; }
+  float getEpisodeReward() const { return episodeReward_; }
+
+  rela::TensorDict reset() final {
+    terminal_ = false;
+    episodeReward_ = 0.f;
+    game_.reset();
+    catch_game::render(game_, frame_.data_ptr<uint8_t>());
+    return observation();
+  }
+
+  std::tuple<rela::TensorDict, float, bool> step(const rela::TensorDict& action) final {
+    const auto& at = action.at("a");
+    const int64_t a = (at.device().is_cpu() && at.scalar_type() == torch::kInt64 && at.numel() == 1)
+                          ? *at.data_ptr<int64_t>()
+                          : at.item<int64_t>();
+    if (a < 0 || a >= numAction_) throw std::out_of_range("CatchEnv: action out of range");
+    bool terminal = false;
+    const float reward = (float)game_.step(catch_game::move_of(a), episodeLen_, &terminal);
+    terminal_ = terminal;
+    episodeReward_ += reward;
+    catch_game::render(game_, frame_.data_ptr<uint8_t>());
+    return std::make_tuple(observation(), reward, terminal_);
+  }
+
+  bool terminated() const final { return terminal_; }
+
+  // [8] int32: LCG state bits, px, bx, by, dx, steps, ep_return, 0 -- the columns of rela_catch_debug_state (tests)
+  torch::Tensor state() const {
+    auto t = torch::zeros({8}, torch::kInt32);
+    int32_t* p = t.data_ptr<int32_t>();
+    p[0] = (int32_t)game_.lcg;
+    p[1] = game_.px, p[2] = game_.bx, p[3] = game_.by, p[4] = game_.dx, p[5] = game_.steps, p[6] = game_.ep_return;
+    return t;
+  }
+
+#if RELA_HAS_FRAME_ROW
+  void bindFrameRow(uint8_t* row) final { frame_ = torch::from_blob(row, {4, 84, 84}, torch::kUInt8); }
+  bool slidingStack() const final { return true; }
+#endif
+
+ private:
+  rela::TensorDict observation() const { return {{"s", frame_}, {"eps", eps_}, {"legal_move", legal_}}; }
+
+  catch_game::Game game_;
+  const int numAction_, episodeLen_;
+  bool terminal_ = true;
+  float episodeReward_ = 0.f;
   torch::Tensor eps_, legal_, frame_;
 };
 
@@ -401,6 +468,14 @@ PYBIND11_MODULE(synth_atari, m) {
       .def("reset", &NullAtariEnv::reset)
       .def("step", &NullAtariEnv::step)
       .def("terminated", &NullAtariEnv::terminated);
+  py::class_<CatchEnv, rela::Env, std::shared_ptr<CatchEnv>>(m, "CatchEnv")
+      .def(py::init<int, float, int, int>(), py::arg("seed"), py::arg("eps"), py::arg("num_action"), py::arg("episode_len"))
+      .def("num_action", &CatchEnv::numAction)
+      .def("reset", &CatchEnv::reset)
+      .def("step", &CatchEnv::step)
+      .def("terminated", &CatchEnv::terminated)
+      .def("get_episode_reward", &CatchEnv::getEpisodeReward)
+      .def("state", &CatchEnv::state);
 #if RELA_HAS_SCREEN
   py::class_<SyntheticScreenEnv, rela::Env, std::shared_ptr<SyntheticScreenEnv>>(m, "SyntheticScreenEnvHost")
       .def("num_action", &SyntheticScreenEnv::numAction)

@@ -1,7 +1,7 @@
 """Builds T threads x K synthetic envs wired to actors (counterpart of pyrela/create_atari.py:64-98).
 
 Real ALE is unreachable in this pipeline (no submodule, no ROMs), so `game` only selects the
-action count; everything else -- per-env seed = seed + thread*K + game (create_atari.py:84),
+action count and, as "catch", the one learnable env (synth_atari.CatchEnv); everything else -- per-env seed = seed + thread*K + game (create_atari.py:84),
 per-env eps from the Ape-X schedule, VectorEnv -> BasicThreadLoop -> Context -- is as upstream.
 """
 import os
@@ -22,7 +22,11 @@ def get_num_action(game_name):
     return NUM_ACTION
 
 
-def create_game(seed, eps, episode_len):
+def create_game(seed, eps, episode_len, game=None):
+    # game == "catch": the learnable env (csrc/catch_game.h; its stack slides, so RELA_REPLAY_DEDUP=plane accepts it);
+    # every other name keeps selecting a synthetic env through the environment variables below
+    if game == "catch":
+        return synth_atari.CatchEnv(seed, eps, NUM_ACTION, episode_len)
     # RELA_SYNTH_ENV=null: the zero-cost env (constant frames, reward 0): the runtime's own ceiling
     if os.environ.get("RELA_SYNTH_ENV") == "null":
         return synth_atari.NullAtariEnv(eps, NUM_ACTION, episode_len, seed)
@@ -49,16 +53,16 @@ def create_game(seed, eps, episode_len):
     return synth_atari.SyntheticAtariEnv(seed, eps, NUM_ACTION, episode_len, sliding)
 
 
-def create_train_env(seed, eps, episode_len, num_thread, num_game_per_thread, actor_creator):
+def create_train_env(seed, eps, episode_len, num_thread, num_game_per_thread, actor_creator, game=None):
     context = rela.Context()
     games, actors = [], []
     for t in range(num_thread):
         vec = rela.VectorEnv()
         for g in range(num_game_per_thread):
             idx = t * num_game_per_thread + g
-            game = create_game(seed + idx, eps[idx], episode_len)
-            games.append(game)
-            vec.append(game)
+            env = create_game(seed + idx, eps[idx], episode_len, game)
+            games.append(env)
+            vec.append(env)
         actor = actor_creator(t)
         actors.append(actor)
         context.push_env_thread(rela.BasicThreadLoop(actor, vec, False))

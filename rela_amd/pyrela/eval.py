@@ -12,14 +12,14 @@ from rela_amd.pyrela import create_env
 rela = create_env.rela
 
 
-def evaluate(num_thread, model_locker, actor_cls, seed, episode_len, eval_eps=0.0):
+def evaluate(num_thread, model_locker, actor_cls, seed, episode_len, eval_eps=0.0, game=None):
     context = rela.Context()
     games = []
     for i in range(num_thread):
-        game = create_env.create_game(seed + i, eval_eps, episode_len)
-        games.append(game)
+        game_env = create_env.create_game(seed + i, eval_eps, episode_len, game)
+        games.append(game_env)
         env = rela.VectorEnv()
-        env.append(game)
+        env.append(game_env)
         context.push_env_thread(rela.BasicThreadLoop(actor_cls(model_locker), env, True))
     context.start()
     while not context.terminated():

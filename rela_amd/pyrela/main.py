@@ -4,7 +4,7 @@ Flag names, defaults and the loop shape follow pyrela/main.py:23-82,197-251: act
 replay from C++ threads, the learner samples / steps / updates priorities, actor weights are
 re-published every --actor_sync_freq updates, the target net every --num_update_between_sync.
 Differences, all on purpose:
-  * envs are synthetic (create_env.py); --game only names the run;
+  * envs are synthetic (create_env.py); --game only names the run, except "catch", the learnable env (csrc/catch_game.h);
   * the priority stays on the GPU between loss() and update_priority() (no per-step host sync);
   * several --act_device values: by default one PROCESS per device (train_multi, rela_amd/parallel.py);
     --single_process 1 keeps the reference's own wiring (main.py:131-136,155,166): one ModelLocker per act device in
@@ -219,7 +219,8 @@ def train(args, on_epoch=None):
                                              args.gamma, replay_buffer)
     print("creating train env")
     context, games, actors = create_env.create_train_env(args.seed, explore_eps, args.episode_len, args.num_thread,
-                                                         args.num_game_per_thread, make_actor)
+                                                         args.num_game_per_thread, make_actor,
+                                                         game=getattr(args, "game", None))
     context.start()
     while replay_buffer.size() < args.burn_in_frames:
         print("warming up replay buffer:", replay_buffer.size())
@@ -271,7 +272,8 @@ def train(args, on_epoch=None):
                 agent.target_net.load_state_dict(learner.state_dict("target"))
             eval_locker.update_model(agent)
             actor_cls = rela.R2D2Actor if args.algo == "r2d2" else rela.DQNActor
-            score = evaluate(args.num_eval_game, eval_locker, actor_cls, epoch * args.num_eval_game + 1, args.episode_len, 0)
+            score = evaluate(args.num_eval_game, eval_locker, actor_cls, epoch * args.num_eval_game + 1, args.episode_len, 0,
+                             game=getattr(args, "game", None))
             print("epoch %d, eval score: %f" % (epoch, score))
             history[-1]["eval_score"] = score
             context.resume()
@@ -436,7 +438,7 @@ def _multi_worker(rank, world, args, port, results):
         else:
             make_actor = lambda i: rela.DQNActor(locker, args.multi_step, K, args.gamma, part)
         context, games, actors = create_env.create_train_env(args.seed + 7919 * g, eps, args.episode_len, len(threads), K,
-                                                             make_actor)
+                                                             make_actor, game=getattr(args, "game", None))
         context.start()
         while part.size() < max(args.burn_in_frames // G, args.batchsize // G):
             time.sleep(0.05)
