@@ -2,7 +2,7 @@
 // arithmetic: conv1's output a1 (400 pixels x 32 channels) never reaches HBM (r4: conv1_bf16x3 wrote 328 MB per 6,400
 // frames and gemm_f32emu<conv2> read 395 MB back).
 //
-//   conv1  u8 frames x 24-bit fixed-point weights on the INT8 matrix cores, exactly as conv12_i8 (ffnet.hip): the pixels
+//   conv1  u8 frames x 24-bit fixed-point weights on the INT8 matrix cores, exactly as conv12_i8 (conv12_i8.h): the pixels
 //          x - 128 as int8, every weight as three balanced base-256 digits relative to its channel's largest, three
 //          exact i32 sums per output, one f32 scale + bias (pack_conv1_i8).  Whole frame in LDS as [plane][4x4 cell].
 //   a1     ReLU, split into the three bf16 parts (split3 record, 192 B per pixel) in conv1's epilogue, stored into the
@@ -439,6 +439,19 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
       dst[i] = *reinterpret_cast<const uint4*>(otile + px * F::OROW + u * 16);
     }
   }
+}
+
+// frames u8 [N][4][84][84] -> a2 as split3 records at rec2; a1 != NULL: a1 as channel-last f32 too (A1OUT)
+inline void launch_conv12(const uint8_t* frames, const uint4* W1d, const float* s1q, const float* b1q, const uint4* B2e,
+                          const float* b2, uint8_t* rec2, float* a1, int N, hipStream_t s, int blocks) {
+  const auto kernel = a1 ? conv12_s3<true> : conv12_s3<false>;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(Conv12S::kT), Conv12S::LDS_TOTAL, s, frames, W1d, s1q, b1q, B2e, b2, rec2, a1, N);
+}
+// both instantiations' opt-in to their dynamic LDS (once per process, before the first launch)
+inline int opt_in_lds_conv12() {
+  for (const void* k : {reinterpret_cast<const void*>(&conv12_s3<false>), reinterpret_cast<const void*>(&conv12_s3<true>)})
+    RELA_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, Conv12S::LDS_TOTAL));
+  return RELA_OK;
 }
 
 }  // namespace s3

@@ -31,7 +31,7 @@ conv1 of the two record trunks runs on the int8 matrix cores with 24-bit fixed-p
 bit-exact one of tests/test_conv1_i8_gpu.py (expected_records), imported unchanged.  Those trunks do not store a1, so
 their check spans obs -> a2 with the propagated bound  E(a2) = |W2| . E(a1) + b2 u S2,  E(a1) = b1 u S1.
 
-THE LSTM CELL (gemm_mfma's kEpiLstmCell epilogue, csrc/ffnet.hip).  From the pre-activations z = (i, f, g, o):
+THE LSTM CELL (gemm_mfma's kEpiLstmCell epilogue, csrc/gemm_f32.h).  From the pre-activations z = (i, f, g, o):
     c' = sig(f) * c + sig(i) * tanh(g)         10 float32 operations: 2 x (expf, add, divide), tanhf, 2 multiplies, 1 add
     h' = sig(o) * tanh(c')                      5 float32 operations: expf, add, divide, tanhf, multiply
 The bound propagates E(z) through the cell with the derivatives taken in float64 and adds one rounding (u) per float32

@@ -1,4 +1,4 @@
-"""conv1 of the split-bf16 mode on the int8 matrix cores (csrc/ffnet.hip: conv12_i8): the kernel's arithmetic is
+"""conv1 of the split-bf16 mode on the int8 matrix cores (csrc/conv12_i8.h: conv12_i8): the kernel's arithmetic is
 integer up to one fixed sequence of f32 operations, so conv1's records can be checked BIT FOR BIT against a numpy
 restatement -- digits of the 24-bit fixed-point weights, exact i64 sums, then
     u = f32(S_hi) * 65536 + f32(S_mid * 256 + S_lo);  y = u * s_c + b'_c;  relu;  bf16 hi (RNE), bf16 lo of y - hi

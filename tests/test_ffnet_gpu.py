@@ -1,5 +1,5 @@
-"""GPU parity tests of the hand-written AtariFFNet forward (rela_amd/csrc/ffnet.hip), through the
-C ABI.  fp32 tolerance 1e-4 abs + 1e-4 rel on Q-values (the reference's library convolutions
+"""GPU parity tests of the hand-written AtariFFNet forward (rela_amd/csrc/ffnet.hip and the kernel
+headers it includes), through the C ABI.  fp32 tolerance 1e-4 abs + 1e-4 rel on Q-values (the reference's library convolutions
 sum in a different order; our MFMA path is an exact fp32 fmaf chain)."""
 import ctypes as C
 import glob
