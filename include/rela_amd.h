@@ -637,7 +637,7 @@ int rela_apex_learner_sync_target(rela_apex_learner* l, void* stream);
  * _set_rmsprop: RMSprop's decay alpha, 0 < alpha < 1 (default 0.99), and centered in {0, 1} (default 0): 1 keeps the gradient
  *   average in the second state buffer and divides by sqrt(max(square average - average^2, 0)) + eps.  The clamp at 0 is
  *   a departure from torch.optim.RMSprop(centered=True), whose float32 form takes the root of a difference that rounding makes
- *   negative and turns the weight into NaN (csrc/learner_common.h: rmsprop_centered_update).  RELA_EINVAL on an Adam learner.
+ *   negative and turns the weight into NaN (csrc/learner_common.hip: rmsprop_centered_update).  RELA_EINVAL on an Adam learner.
  * _set_adam_betas: 0 <= b1 < 1, 0 < b2 < 1 (defaults 0.9 / 0.999); the bias corrections use them.  RELA_EINVAL on an RMSprop
  *   learner.
  * The two option setters are accepted only while the optimiser state is the zero state: after create or a load and before the
@@ -693,7 +693,7 @@ const float* rela_apex_learner_stats_dev(const rela_apex_learner* l);
  * gradients were computed with).  Valid until the next rela_apex_learner_loss.                  */
 int rela_apex_learner_debug_activations(rela_apex_learner* l, float** a1, float** a2, float** a3, float** h, int* batch);
 
-/* Test tap: the backward pass of the conv trunk (csrc/learner_common.h: trunk_backward, shared by both learners) as one
+/* Test tap: the backward pass of the conv trunk (csrc/learner_common.hip: trunk_backward, shared by both learners) as one
  * call whose inputs are the forward's activations, so their > 0 patterns -- the ReLU masks -- are data of the call.
  * All pointers are device pointers; the call allocates its own scratch, synchronises and frees it.
  *   obs      u8  [frames][4][84][84]
@@ -713,7 +713,7 @@ int rela_debug_trunk_backward(int frames, int mode, int lanes, int fast_wgrad_mi
                               float* g_c3b, float* d_a2, float* d_a1, void* stream);
 
 /* Test tap: what rela_apex_learner_loss launches after its three forwards -- TD error, priorities, loss and the head
- * gradient d_ha (csrc/learner_common.h: learner_td_loss_grad, or td_kernel + learner_loss_grad) -- with the Q tables as
+ * gradient d_ha (csrc/learner.hip: learner_td_loss_grad, or td_kernel + learner_loss_grad) -- with the Q tables as
  * inputs of the call.  All pointers are device pointers; the call synchronises.
  *   q, qno, qnt      f32 [batch][A]   online(obs), online(next_obs), target(next_obs)
  *   nlegal, legal    f32 [batch][A]   legal moves of next_obs / obs
@@ -764,7 +764,7 @@ int rela_debug_lstm_input_backward(int rows, int mode, const float* dg, const fl
 /* Debug / tests: the learner's own d_ha [B][32], d_h [B][512] and d_a3 [B][49][64] of the last rela_apex_learner_grad
  * (d_ha: of the last rela_apex_learner_loss).  Valid until the next rela_apex_learner_loss.                        */
 int rela_apex_learner_debug_head_grads(rela_apex_learner* l, float** d_ha, float** d_h, float** d_a3);
-/* Test tap: the step of both learners that turns gradients into weights (csrc/learner_common.h: optimizer_apply --
+/* Test tap: the step of both learners that turns gradients into weights (csrc/learner_common.hip: optimizer_apply --
  * sumsq_partial, clip_coef, then rmsprop_update or adam_update) on the caller's flat buffers.  p, g, s1, s2 and stats_out
  * are device pointers; the call brings its own partial sums, abort word and skip counter, synchronises and frees them.
  *   optimizer        0 RMSprop (alpha 0.99; s1 = square average, s2 untouched), 1 Adam (betas 0.9 / 0.999; s1, s2 = m, v)

@@ -25,8 +25,161 @@
 // The gradient buffer is exposed (rela_apex_learner_flat) so data-parallel learners all-reduce
 // it between rela_apex_learner_backward and rela_apex_learner_apply.
 #include "learner_common.h"
+#include "value_rescale.h"
 
 using namespace rela_amd;
+
+namespace rela_amd {
+namespace {
+
+// ---- the Problems of this learner's own GEMMs (heads and fc; the tiles: learner_common.h) -----------------------------
+// d_h[b][u] = relu'(h) * sum_k d_ha[b][k] * Wh[k][u]      Wh rows: 0..A-1 = fc_a.weight, 31 = fc_v.weight
+struct ProbHeadDgrad : ProbBase {
+  const float *d_ha, *a_w, *v_w, *h;
+  float* d_h;
+  int A;
+  __device__ float4 fetchA(int m, int k) const { return ld4(d_ha + (size_t)min(m, M - 1) * 32 + k); }
+  __device__ float4 fixA(float4 v, int m, int) const { return keep4(m < M, v); }
+  __device__ float4 fetchB(int k, int n) const {  // (rows A .. 30 fetch fc_v's row and are zeroed)
+    const float* row = k < A ? a_w + (size_t)k * 512 : v_w;
+    return ld4(row + n);
+  }
+  __device__ float4 fixB(float4 v, int k, int) const { return keep4(k < A || k == 31, v); }
+  __device__ void store(int, int m, int n, float v) const {
+    const size_t i = (size_t)m * 512 + n;
+    d_h[i] = h[i] > 0.f ? v : 0.f;
+  }
+};
+
+// d_a3[b][j] = relu'(a3) * sum_u d_h[b][u] * Wfc'[u][j]     j = pos*64 + c (channel-last)
+struct ProbFcDgrad : ProbBase {
+  const float *d_h, *wfcp, *a3;
+  float* d_a3;
+  __device__ float4 fetchA(int m, int k) const { return ld4(d_h + (size_t)min(m, M - 1) * 512 + k); }
+  __device__ float4 fixA(float4 v, int m, int) const { return keep4(m < M, v); }
+  __device__ float4 fetchB(int k, int n) const { return ld4(wfcp + (size_t)k * 3136 + n); }
+  __device__ void store(int, int m, int n, float v) const {
+    const size_t i = (size_t)m * 3136 + n;
+    d_a3[i] = a3[i] > 0.f ? v : 0.f;
+  }
+};
+
+// dWfc[u][c*49+pos] = sum_b d_h[b][u] * a3[b][pos*64+c]   (written in state_dict order, net.py:49)
+struct ProbFcWgrad : ProbBase {
+  const float *d_h, *a3;
+  float* g_fc_w;
+  __device__ float4 fetchA(int b, int m) const { return ld4(d_h + (size_t)min(b, K - 1) * 512 + m); }
+  __device__ float4 fetchB(int b, int n) const { return ld4(a3 + (size_t)min(b, K - 1) * 3136 + n); }
+  __device__ float4 fixA(float4 v, int b, int) const { return keep4(b < K, v); }
+  __device__ float4 fixB(float4 v, int b, int) const { return keep4(b < K, v); }
+  __device__ void store(int, int m, int n, float v) const {
+    const int pos = n >> 6, c = n & 63;
+    g_fc_w[(size_t)m * 3136 + c * 49 + pos] = v;
+  }
+};
+
+// ---- loss: smooth_l1(err) * w, mean over the batch (apex.py:87, main.py:228), and its gradient
+// through the dueling head  q = v + a*legal - mean_A(a*legal)  (net.py:33-39) --------------------
+__global__ __launch_bounds__(kLT) void learner_loss_grad(const float* __restrict__ td, const float* __restrict__ w,
+                                                         const int64_t* __restrict__ act,
+                                                         const float* __restrict__ legal, int Bn, int A,
+                                                         float* __restrict__ d_ha, float* __restrict__ loss_out) {
+  __shared__ float red[kLT];
+  float lsum = 0.f;
+  const float inv_b = 1.0f / (float)Bn, inv_a = 1.0f / (float)A;
+  for (int i = threadIdx.x; i < Bn; i += kLT) {
+    const float e = td[i], ae = fabsf(e);
+    lsum += (ae < 1.0f ? 0.5f * e * e : ae - 0.5f) * w[i];
+    // err = target - q[a]:  d mean(loss*w) / d q[a] = -w * clamp(err, -1, 1) / B
+    const float g = -(w[i] * fminf(fmaxf(e, -1.0f), 1.0f)) * inv_b;
+    const int a = (int)act[i];
+    float* row = d_ha + (size_t)i * 32;
+    for (int k = 0; k < 32; ++k) {
+      float v = 0.f;
+      if (k < A) v = legal[(size_t)i * A + k] * (g * ((k == a ? 1.0f : 0.0f) - inv_a));
+      if (k == 31) v = g;
+      row[k] = v;
+    }
+  }
+  red[threadIdx.x] = lsum;
+  __syncthreads();
+  for (int o = kLT / 2; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss_out[0] = red[0] * inv_b;
+}
+
+// td_err (apex.py:30-45: batch-global q.min() of greedy_act(next_obs), double-DQN target, un-fused arithmetic as
+// agent_ops.hip's td_kernel) + the loss kernel above in ONE single-workgroup launch (two latency-bound launches
+// before: 15 + 19 us).  Same arithmetic in the same order, so priorities, loss and d_ha are bit-identical.
+__global__ __launch_bounds__(1024) void learner_td_loss_grad(int Bn, int A, const float* __restrict__ q,
+                                                             const float* __restrict__ qno, const float* __restrict__ qnt,
+                                                             const float* __restrict__ nlegal,
+                                                             const int64_t* __restrict__ act,
+                                                             const float* __restrict__ reward,
+                                                             const float* __restrict__ bootstrap, float gamma_n,
+                                                             float vr_eps, const float* __restrict__ w,
+                                                             const float* __restrict__ legal,
+                                                             float* __restrict__ td, float* __restrict__ prio,
+                                                             float* __restrict__ d_ha, float* __restrict__ loss_out) {
+  __shared__ float red[1024];
+  float m = INFINITY;
+  for (int i = threadIdx.x; i < Bn * A; i += 1024) m = fminf(m, qno[i]);
+  red[threadIdx.x] = m;
+  __syncthreads();
+  for (int off = 512; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) red[threadIdx.x] = fminf(red[threadIdx.x], red[threadIdx.x + off]);
+    __syncthreads();
+  }
+  const float qmin = red[0];
+  __syncthreads();
+  float lsum = 0.f;
+  const float inv_b = 1.0f / (float)Bn, inv_a = 1.0f / (float)A;
+  for (int i = threadIdx.x; i < Bn; i += 1024) {
+    int na = 0;
+    float bv = -INFINITY;
+#pragma unroll 6  // (the loads of several actions in flight: one at a time this loop was most of the kernel's 19 us)
+    for (int j = 0; j < A; ++j) {  // greedy_act(next_obs): first maximal index of (1 + q - qmin) * legal (apex.py:51)
+      const float lq = __fmul_rn(__fsub_rn(__fadd_rn(1.0f, qno[(size_t)i * A + j]), qmin), nlegal[(size_t)i * A + j]);
+      if (lq > bv) bv = lq, na = j;
+    }
+    const int a = (int)act[i];
+    const float qa = q[(size_t)i * A + a];
+    const float bq = qnt[(size_t)i * A + na];
+    float tgt;  // detached: with value rescaling (value_rescale.h) only the target changes, the Huber seed below keeps its formula
+    if (vr_eps > 0.0f)
+      tgt = rela_vr::h(__fadd_rn(reward[i], __fmul_rn(__fmul_rn(bootstrap[i], gamma_n), rela_vr::h_inv(bq, vr_eps))), vr_eps);
+    else
+      tgt = __fadd_rn(reward[i], __fmul_rn(__fmul_rn(bootstrap[i], gamma_n), bq));
+    const float e = __fsub_rn(tgt, qa), ae = fabsf(e);
+    td[i] = e;
+    prio[i] = ae;
+    lsum += (ae < 1.0f ? 0.5f * e * e : ae - 0.5f) * w[i];
+    const float g = -(w[i] * fminf(fmaxf(e, -1.0f), 1.0f)) * inv_b;
+    float4* row = reinterpret_cast<float4*>(d_ha + (size_t)i * 32);
+    float v[32];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) {
+      v[k] = 0.f;
+      if (k < A) v[k] = legal[(size_t)i * A + k] * (g * ((k == a ? 1.0f : 0.0f) - inv_a));
+      if (k == 31) v[k] = g;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) row[k] = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
+  }
+  // the same tree as learner_loss_grad's kLT = 512 lanes when Bn <= 512: lanes >= 512 hold zeros and fold in first
+  red[threadIdx.x] = lsum;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) loss_out[0] = red[0] * inv_b;
+}
+
+}  // namespace
+}  // namespace rela_amd
 
 // flat parameter layout: rela_ffnet_params order (LearnerCore, learner_common.h)
 static_assert(sizeof(rela_ffnet_params) == kFFNetSegs * sizeof(float*), "rela_ffnet_params is kFFNetSegs pointers");
@@ -67,7 +220,7 @@ int repack(rela_apex_learner* l, bool online, bool target, hipStream_t s) {
     extra.w2p = l->w2p, extra.w3p = l->w3p, extra.wfcp = l->wfcp;
     int rc = ffnet_load_extra(l->online, &p, s, extra);
     if (rc != RELA_OK) return rc;
-    if (l->frag2) dgfast::pack_frags(l->w2p, l->w3p, l->frag2, l->frag3, s);
+    if (l->frag2) pack_dgrad_frags(l->w2p, l->w3p, l->frag2, l->frag3, s);
   }
   if (target) {
     const rela_ffnet_params p = params_at(l, l->PT);
@@ -123,12 +276,7 @@ int head_fc_backward(const HeadFcBwd& t, hipStream_t s, hipStream_t sw, ColsumJo
     p.d_ha = t.d_ha, p.a_w = t.a_w, p.v_w = t.v_w, p.h = t.h, p.d_h = t.d_h, p.A = t.A;
     if (int rc = launch_gemm_as<SetDgrad>(t.arith, p, 1, s, "learner_dgrad_heads")) return rc;
   }
-  {
-    ProbHeadWgrad p{};
-    p.M = 32, p.N = 512, p.K = Bn;
-    p.d_ha = t.d_ha, p.h = t.h, p.g_a_w = t.g_a_w, p.g_v_w = t.g_v_w, p.A = t.A;
-    if (int rc = launch_gemm_as<SetW32>(t.arith, p, 1, sw, "learner_wgrad_heads")) return rc;
-  }
+  if (int rc = launch_head_wgrad(t.arith, Bn, t.A, t.d_ha, t.h, t.g_a_w, t.g_v_w, sw)) return rc;
   sums->add(t.d_ha, Bn, 32, t.s32);
   if (sw != s) lane_dep(t.ev_dh, s, sw);  // d_h is ready
   // fc: d_a3, dWfc, db
@@ -191,8 +339,8 @@ int build_learner(rela_apex_learner* l, int num_action, int max_batch, int multi
     for (hipEvent_t& e : l->ev) RELA_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     if (int rc = m.alloc(&l->part_side, kTrunkPartFloats, false)) return rc;
     if (int rc = m.alloc(&l->cpart_side, cpart_floats, false)) return rc;
-    if (int rc = m.alloc(&l->frag2, dgfast::kFrag2Bytes, false)) return rc;
-    if (int rc = m.alloc(&l->frag3, dgfast::kFrag3Bytes, false)) return rc;
+    if (int rc = m.alloc(&l->frag2, kFrag2Bytes, false)) return rc;
+    if (int rc = m.alloc(&l->frag3, kFrag3Bytes, false)) return rc;
   }
   return RELA_OK;
 }
@@ -458,79 +606,9 @@ extern "C" int rela_apex_learner_grad(rela_apex_learner* l, void* stream_) {
       t.s32 = l->s32, t.A = A, t.g_a_b = Gm[11], t.g_v_b = Gm[9];
     }
     if (int rc = trunk_backward(t, s, &sums)) return rc;
-    if (!lanes) hipLaunchKernelGGL(head_bias_grad, dim3(1), dim3(32), 0, s, (const float*)l->s32, A, Gm[11], Gm[9]);
+    if (!lanes) launch_head_bias_grad(l->s32, A, Gm[11], Gm[9], s);
   }
   RELA_LAUNCH_CHECK();
-  return RELA_OK;
-}
-
-// Test tap: trunk_backward (learner_common.h) on its own, with the activations and the masked d_a3 as inputs of the call.
-// Everything the learners keep across steps (scratch, the permuted weight copies, the side lane) lives for this one call.
-namespace {
-// one of the dgrad operand copies on its own, as a pack list of one segment (the learners' re-pack makes them in its launch)
-int permute_weight(int mode, const float* src, float* dst, hipStream_t s) {
-  return pack_one(kPackPermute, src, nullptr, dst, mode, 0, kPermFloats[mode], s);
-}
-struct TrunkTapScratch {
-  DevBuffers mem;
-  hipStream_t side = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  ~TrunkTapScratch() {
-    mem.free_all();
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (side) (void)hipStreamDestroy(side);
-  }
-};
-}  // namespace
-
-extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fast_wgrad_min_frames, const uint8_t* obs,
-                                         const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
-                                         const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b,
-                                         float* g_c3w, float* g_c3b, float* d_a2, float* d_a1, void* stream_) {
-  RELA_CHECK(frames >= 1 && frames <= kTrunkMaxFrames && mode >= 0 && mode <= 2 && (lanes == 0 || lanes == 1), RELA_EINVAL,
-             "rela_debug_trunk_backward: bad arguments (frames %d, mode %d, lanes %d)", frames, mode, lanes);
-  RELA_CHECK(obs && a1 && a2 && d_a3 && conv2_w && conv3_w && g_c1w && g_c1b && g_c2w && g_c2b && g_c3w && g_c3b && d_a2 &&
-                 d_a1,
-             RELA_EINVAL, "rela_debug_trunk_backward: a pointer is NULL");
-  hipStream_t s = (hipStream_t)stream_;
-  TrunkTapScratch sc;
-  const size_t cpart_floats = (size_t)kColsumBlocks * (32 + 512 + 64 + 64 + 32);  // as the learners size it
-  float *w2p = nullptr, *w3p = nullptr;
-  if (int rc = sc.mem.alloc(&w2p, kPermFloats[kPermConv2], false)) return rc;
-  if (int rc = sc.mem.alloc(&w3p, kPermFloats[kPermConv3], false)) return rc;
-  if (int rc = permute_weight(kPermConv2, conv2_w, w2p, s)) return rc;
-  if (int rc = permute_weight(kPermConv3, conv3_w, w3p, s)) return rc;
-  TrunkBwd t{};
-  t.Bn = frames, t.obs = obs, t.a1 = a1, t.a2 = a2, t.d_a3 = d_a3, t.d_a2 = d_a2, t.d_a1 = d_a1;
-  t.w2p = w2p, t.w3p = w3p;
-  t.g_c1w = g_c1w, t.g_c1b = g_c1b, t.g_c2w = g_c2w, t.g_c2b = g_c2b, t.g_c3w = g_c3w, t.g_c3b = g_c3b;
-  t.plan = plan_apex_backward(mode, lanes != 0)
-               .trunk.plan(frames, fast_wgrad_min_frames > 0 ? fast_wgrad_min_frames : kFastWgradMinFrames);
-  if (int rc = sc.mem.alloc(&t.part, kTrunkPartFloats, false)) return rc;
-  if (int rc = sc.mem.alloc(&t.cpart, cpart_floats, false)) return rc;
-  if (lanes) {  // as rela_apex_learner_grad fills it; else one lane, as the R2D2 learner (and RELA_LEARNER_LANES=1)
-    RELA_HIP(hipStreamCreateWithFlags(&sc.side, hipStreamNonBlocking));
-    for (hipEvent_t& e : sc.ev) RELA_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    t.side = sc.side, t.ev_da3 = sc.ev[0], t.ev_da2 = sc.ev[1], t.ev_side = sc.ev[2];
-    if (int rc = sc.mem.alloc(&t.part_side, kTrunkPartFloats, false)) return rc;
-    if (int rc = sc.mem.alloc(&t.cpart_side, cpart_floats, false)) return rc;
-    if (t.plan.dgrad_bf16) {  // the data-gradient weight fragments packed ahead, as repack() does
-      uint8_t *frag2 = nullptr, *frag3 = nullptr;
-      if (int rc = sc.mem.alloc(&frag2, dgfast::kFrag2Bytes, false)) return rc;
-      if (int rc = sc.mem.alloc(&frag3, dgfast::kFrag3Bytes, false)) return rc;
-      dgfast::pack_frags(w2p, w3p, frag2, frag3, s);
-      t.frag2 = frag2, t.frag3 = frag3;
-    }
-  }
-  const int rc = trunk_backward(t, s);
-  const hipError_t launched = hipGetLastError();
-  // (the scratch goes away with `sc`: both lanes must be done with it whatever happened)
-  const hipError_t done = hipStreamSynchronize(s);
-  if (sc.side) (void)hipStreamSynchronize(sc.side);
-  if (rc != RELA_OK) return rc;
-  RELA_HIP(launched);
-  RELA_HIP(done);
   return RELA_OK;
 }
 
@@ -588,7 +666,7 @@ extern "C" int rela_debug_head_fc_backward(int batch, int A, int mode, int lanes
   const int rc = head_fc_backward(t, s, sw, &sums);
   if (rc == RELA_OK) {
     colsum_multi_launch(sums, cpart, sw);
-    hipLaunchKernelGGL(head_bias_grad, dim3(1), dim3(32), 0, sw, (const float*)s32, A, g_fc_a_b, g_fc_v_b);
+    launch_head_bias_grad(s32, A, g_fc_a_b, g_fc_v_b, sw);
   }
   if (lanes) lane_dep(sc.ev[2], sw, s);
   const hipError_t launched = hipGetLastError();
@@ -605,76 +683,6 @@ extern "C" int rela_apex_learner_debug_head_grads(rela_apex_learner* l, float** 
   RELA_CHECK(l && d_ha && d_h && d_a3, RELA_EINVAL, "rela_apex_learner_debug_head_grads: bad arguments");
   RELA_CHECK(l->last_B > 0, RELA_ESTATE, "rela_apex_learner_debug_head_grads: no rela_apex_learner_loss yet");
   *d_ha = l->d_ha, *d_h = l->d_h, *d_a3 = l->d_a3;
-  return RELA_OK;
-}
-
-// Test tap: optimizer_apply (learner_common.h) itself on the caller's flat buffers: the norm, the clip coefficient and one
-// RMSprop / Adam update.  The OptimState, the 256 partial sums, the abort word and the skip counter live for this one call.
-// (`who`: rela_debug_optimizer_apply, whose options are OptimState's defaults, or rela_debug_optimizer_apply_opts)
-static int debug_optimizer_apply(const char* who, const OptimState& options, int optimizer, float lr, float eps, float clip,
-                                 int64_t adam_steps_done, int64_t n, float* p, const float* g, float* s1, float* s2,
-                                 float* stats_out, int abort, unsigned* skipped_out, void* stream_) {
-  RELA_CHECK((optimizer == 0 || optimizer == 1) && adam_steps_done >= 0 && n > 0 && n % 4 == 0 && (abort == 0 || abort == 1),
-             RELA_EINVAL, "%s: bad arguments (optimizer %d, steps done %lld, n %lld, abort %d)", who, optimizer,
-             (long long)adam_steps_done, (long long)n, abort);
-  RELA_CHECK(p && g && s1 && s2 && stats_out, RELA_EINVAL, "%s: a pointer is NULL", who);
-  for (const void* b : {(const void*)p, (const void*)g, (const void*)s1, (const void*)s2})
-    RELA_CHECK(((uintptr_t)b & 15) == 0, RELA_EINVAL, "%s: a buffer is not 16-byte aligned", who);
-  hipStream_t s = (hipStream_t)stream_;
-  struct Scratch {
-    DevBuffers mem;
-    ~Scratch() { mem.free_all(); }
-  } sc;
-  double* npart = nullptr;
-  unsigned* words = nullptr;  // [0] the abort word, [1] the skip counter
-  if (int rc = sc.mem.alloc(&npart, kNormBlocks, false)) return rc;
-  if (int rc = sc.mem.alloc(&words, 2, true)) return rc;
-  if (abort) RELA_HIP(hipMemsetD32Async((hipDeviceptr_t)words, 1, 1, s));
-  OptimState o = options;
-  o.optimizer = optimizer, o.lr = lr, o.eps = eps, o.clip = clip, o.adam_t = adam_steps_done;
-  optimizer_apply(o, p, g, s1, s2, n, npart, stats_out, s, words, words + 1, true);
-  const hipError_t launched = hipGetLastError();
-  const hipError_t done = hipStreamSynchronize(s);  // (the scratch goes away with `sc`)
-  RELA_HIP(launched);
-  RELA_HIP(done);
-  if (skipped_out) RELA_HIP(hipMemcpy(skipped_out, words + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
-  return RELA_OK;
-}
-
-extern "C" int rela_debug_optimizer_apply(int optimizer, float lr, float eps, float clip, int64_t adam_steps_done, int64_t n,
-                                          float* p, const float* g, float* s1, float* s2, float* stats_out, int abort,
-                                          unsigned* skipped_out, void* stream_) {
-  return debug_optimizer_apply("rela_debug_optimizer_apply", OptimState(), optimizer, lr, eps, clip, adam_steps_done, n, p, g,
-                               s1, s2, stats_out, abort, skipped_out, stream_);
-}
-
-// Test tap: as rela_debug_optimizer_apply, with the options of rela_*_learner_set_rmsprop / _set_adam_betas
-extern "C" int rela_debug_optimizer_apply_opts(int optimizer, float lr, float eps, float clip, int64_t adam_steps_done,
-                                               int64_t n, float* p, const float* g, float* s1, float* s2, float* stats_out,
-                                               int abort, unsigned* skipped_out, float alpha, int centered, float b1, float b2,
-                                               void* stream_) {
-  RELA_CHECK(rmsprop_options_ok(alpha, centered) && adam_betas_ok(b1, b2), RELA_EINVAL,
-             "rela_debug_optimizer_apply_opts: bad options (alpha %g, centered %d, betas %g / %g)", (double)alpha, centered,
-             (double)b1, (double)b2);
-  OptimState options;
-  options.alpha = alpha, options.centered = centered != 0, options.b1 = b1, options.b2 = b2;
-  return debug_optimizer_apply("rela_debug_optimizer_apply_opts", options, optimizer, lr, eps, clip, adam_steps_done, n, p, g,
-                               s1, s2, stats_out, abort, skipped_out, stream_);
-}
-
-// Test tap: target_lerp (learner_common.h), the kernel of rela_*_learner_soft_update_target, on the caller's flat buffers
-extern "C" int rela_debug_target_lerp(int64_t n, float tau, float* pt, const float* p, void* stream_) {
-  RELA_CHECK(n > 0 && n % 4 == 0 && tau > 0.f && tau <= 1.f, RELA_EINVAL, "rela_debug_target_lerp: bad arguments (n %lld, tau %g)",
-             (long long)n, (double)tau);
-  RELA_CHECK(pt && p, RELA_EINVAL, "rela_debug_target_lerp: a pointer is NULL");
-  RELA_CHECK((((uintptr_t)pt | (uintptr_t)p) & 15) == 0, RELA_EINVAL, "rela_debug_target_lerp: a buffer is not 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream_;
-  note_launch("target_lerp");
-  hipLaunchKernelGGL(target_lerp, dim3(ceil_div(n / 4, 256)), dim3(256), 0, s, pt, p, n / 4, tau);
-  const hipError_t launched = hipGetLastError();
-  const hipError_t done = hipStreamSynchronize(s);
-  RELA_HIP(launched);
-  RELA_HIP(done);
   return RELA_OK;
 }
 

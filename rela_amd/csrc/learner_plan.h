@@ -1,5 +1,5 @@
 // Which kernels the backward pass of a learner step runs (csrc/learner.hip, learner_r2d2.hip, the shared conv trunk in
-// learner_common.h): the arithmetic of every GEMM, the split-K counts and the frame / row thresholds, as pure host
+// learner_common.hip): the arithmetic of every GEMM, the split-K counts and the frame / row thresholds, as pure host
 // functions of the learner's precision mode.  No HIP in here: learner_common.h includes this header, and
 // tests/cpu_shims/learner_plan_host.cpp compiles it with a plain C++ compiler so that the decision table is checked where
 // there is no GPU (tests/test_learner_plan_host.py).  The two *_grad entry points and the four backward taps take their

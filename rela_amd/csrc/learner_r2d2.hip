@@ -15,10 +15,11 @@
 //   backward  d(mean(loss * w)) through the heads, BPTT over the seq_len + multi_step training steps
 //             (dh_{t-1} = dgates_t x W_hh, split-K), then batched over all training rows:
 //             dW_hh = DG^T x H_prev, dW_ih = DG^T x a3, d_a3 = DG x W_ih (ReLU mask) and the shared conv-trunk
-//             backward of learner_common.h.  Every contraction is an instance of gemm_lds (f32 MFMA).
+//             backward of learner_common.hip.  Every contraction is an instance of gemm_lds (f32 MFMA).
 //   update    clip_grad_norm_ + Adam (pyrela/main.py:124-126,233-238) on flat buffers in state_dict order.
 #include "gemm_bf16s.h"
 #include "learner_common.h"
+#include "value_rescale.h"
 
 using namespace rela_amd;
 
@@ -29,7 +30,22 @@ constexpr int kHid = 512, kGates = 2048, kFeat = 3136;
 constexpr int kRecSplitF = 4;  // split-K of the recurrent forward GEMM (K = 512)
 constexpr int kRecSplitB = 8;  // split-K of the recurrent backward GEMM (K = 2048)
 
-// (the tiles of this file's GEMMs: learner_common.h, next to the Ape-X learner's; what the backward runs: learner_plan.h)
+// ---- the tiles of this file's GEMMs (TileSet and the Ape-X learner's: learner_common.h; what the backward runs:
+// learner_plan.h) ---------------------------------------------------------------------------------------------------------
+using TileRows = TileCfg<128, 64, 4, 2, false>;  // M = many rows, A k-contiguous
+using TileRec = TileCfg<64, 64, 2, 4, false>;    // M = batch rows of one time step
+using TileWg = TileCfg<128, 64, 4, 2, true>;     // weight gradients, M = 2048 gate rows
+using TileW32r = TileCfg<32, 64, 2, 4, true>;    // head weight gradients (M = 32)
+// The backward GEMMs of its mode 3 (f32x3_bwd).  64 x 64 tiles (100 registers, 60 KB of LDS: two blocks per CU) measured
+// ahead of the 128 x 64 tiles of TileRows / TileWg (172 registers, 84 KB: one block) at 5,312 training rows: dW_ih 0.66 ->
+// 0.58 ms, dW_hh 0.15 -> 0.10, d_a3 0.61 -> 0.58.  The conv weight gradients run one block per CU at their f32 split counts
+// (conv3 0.28 ms against 0.24 in f32), two at twice the splits (learner_plan.h: kX6SplitMul).
+using Tile6Rows = gemm3::TileCfg<64, 64, 2, 4, false, 3>;
+using Tile6Wg = Tile6W64;
+using SetWg = TileSet<TileWg, void, Tile6Wg>;          // dW_hh, dW_ih
+using SetRows = TileSet<TileRows, void, Tile6Rows>;    // the input-side data gradient
+using SetSeqHeadRows = TileSet<TileRows, void, void>;  // the heads' data gradient and ...
+using SetSeqHeadW32 = TileSet<TileW32r, void, void>;   // ... split-K weight gradient (measured slower in three parts)
 
 // GX[r][g] = bias[g] + sum_k a3[r][k] * wihT[k][g]
 struct ProbGateX : ProbBase {
@@ -107,6 +123,30 @@ struct ProbHeadDgradSeq : ProbBase {
   __device__ float4 fixB(float4 v, int k, int) const { return keep4(k < A || k == 31, v); }
   __device__ void store(int, int m, int n, float v) const { d_o[(size_t)m * kHid + n] = v; }
 };
+// dWh[k][u] = sum_r d_ha[r][k] * o[r][u] over many rows (5,312 training rows), split over blockIdx.z into partial tiles
+// part[z][32][512] that head_wgrad_reduce sums in z order (one 32 x 512 output: without the split the GEMM is 8 blocks;
+// in one launch: launch_head_wgrad, learner_common.h)
+struct ProbHeadWgradPart : ProbBase {
+  const float *d_ha, *h;
+  float* part;
+  __device__ float4 fetchA(int b, int m) const { return ld4(d_ha + (size_t)min(b, K - 1) * 32 + m); }
+  __device__ float4 fetchB(int b, int n) const { return ld4(h + (size_t)min(b, K - 1) * 512 + n); }
+  __device__ float4 fixA(float4 v, int b, int) const { return keep4(b < K, v); }
+  __device__ float4 fixB(float4 v, int b, int) const { return keep4(b < K, v); }
+  __device__ void store(int z, int m, int n, float v) const { part[((size_t)z * 32 + m) * 512 + n] = v; }
+};
+__global__ void head_wgrad_reduce(const float* __restrict__ part, int splits, int A, float* __restrict__ g_a_w,
+                                  float* __restrict__ g_v_w) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= 32 * 512) return;
+  const int m = idx >> 9, n = idx & 511;
+  if (m >= A && m != 31) return;
+  float s = 0.f;
+#pragma unroll 8
+  for (int z = 0; z < splits; ++z) s += part[(size_t)z * (32 * 512) + idx];
+  if (m < A) g_a_w[(size_t)m * 512 + n] = s;
+  else g_v_w[n] = s;
+}
 
 // ---- weight copies in the orders the GEMM loaders read ------------------------------------------
 // wihT[k = pos*64+c][g] and wihp[g][k = pos*64+c]  <-  weight_ih_l0[g][c*49+pos]; whhT[k][g] <- weight_hh_l0[g][k]
@@ -1202,14 +1242,14 @@ int seq_head_backward(const R2d2BwdPlan& plan, int rowsTr, int A, const float* d
     hipLaunchKernelGGL(head_wgrad_reduce, dim3(ceil_div(32 * 512, 256)), dim3(256), 0, s, (const float*)part,
                        plan.head_wgrad_splits, A, g_a_w, g_v_w);
   } else {
-    ProbHeadWgrad p{};
-    p.M = 32, p.N = kHid, p.K = rowsTr;
-    p.d_ha = d_ha, p.h = o_tr, p.g_a_w = g_a_w, p.g_v_w = g_v_w, p.A = A;
     if (census) note_launch("head_wgrad (one launch)");
-    if (int rc = launch_gemm_as<SetSeqHeadW32>(plan.heads, p, 1, s, "learner_wgrad_heads")) return rc;
+    RELA_CHECK(plan.heads == kArithF32, RELA_ESTATE,  // (as SetSeqHeadW32: only the f32 tile, measured slower in three parts)
+               "%s: no tile for arithmetic %d (internal error: the plan and the tile sets disagree)", "learner_wgrad_heads",
+               (int)plan.heads);
+    if (int rc = launch_head_wgrad(plan.heads, rowsTr, A, d_ha, o_tr, g_a_w, g_v_w, s)) return rc;
   }
   colsum_launch(d_ha, rowsTr, 32, cpart, s32, s);
-  hipLaunchKernelGGL(head_bias_grad, dim3(1), dim3(32), 0, s, (const float*)s32, A, g_a_b, g_v_b);
+  launch_head_bias_grad(s32, A, g_a_b, g_v_b, s);
   return RELA_OK;
 }
 }  // namespace

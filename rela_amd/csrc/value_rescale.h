@@ -1,7 +1,7 @@
 // value_rescale.h -- the invertible value rescaling of R2D2 (Kapturowski et al., ICLR 2019, after Pohlen et al. 2018)
 //   h(x)     = sign(x) * (sqrt(|x| + 1) - 1) + eps * x
 //   h_inv(x) = sign(x) * (((sqrt(1 + 4 eps (|x| + 1 + eps)) - 1) / (2 eps))^2 - 1)
-// as ONE fixed float32 recipe, shared by every kernel that forms a TD target (agent_ops.hip: td_kernel, learner_common.h:
+// as ONE fixed float32 recipe, shared by every kernel that forms a TD target (agent_ops.hip: td_kernel, learner.hip:
 // learner_td_loss_grad, learner_r2d2.hip: seq_td_loss) and by the host restatement (tests/cpu_shims/value_rescale_host.cpp),
 // which are therefore bit-identical.  The reference has no counterpart (it clips rewards in its env instead).
 //

@@ -30,7 +30,7 @@
 
 namespace rela_amd {
 namespace w1fast {
-namespace {  // (included by both learners' translation units)
+namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

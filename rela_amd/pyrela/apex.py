@@ -57,7 +57,7 @@ class ApexAgent(nn.Module):
 
     @torch.no_grad()
     def soft_update_target(self, tau: float):
-        """Polyak update target += tau * (online - target), the learners' formula (csrc/learner_common.h: target_lerp);
+        """Polyak update target += tau * (online - target), the learners' formula (csrc/learner_common.hip: target_lerp);
         no reference counterpart"""
         polyak_update(self.target_net, self.online_net, tau)
 

@@ -1,4 +1,4 @@
-"""optimizer_apply (csrc/learner_common.h: sumsq_partial, clip_coef, rmsprop_update / adam_update) restated twice, and the
+"""optimizer_apply (csrc/learner_common.hip: sumsq_partial, clip_coef, rmsprop_update / adam_update) restated twice, and the
 tables by role that tests/test_optimizer_gpu.py runs through rela_debug_optimizer_apply:
   step_f64    torch's clip_grad_norm_ + RMSprop (alpha 0.99, no momentum, not centred) / Adam (betas 0.9 / 0.999, no
               amsgrad) in float64, parameterised by the constants: TORCH_CONSTS, or KERNEL_CONSTS, the float32 values the

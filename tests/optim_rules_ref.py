@@ -1,4 +1,4 @@
-"""The learners' configurable update rules (csrc/learner_common.h: optimizer_apply with OptimState's alpha / centered / b1 / b2,
+"""The learners' configurable update rules (csrc/learner_common.hip: optimizer_apply with OptimState's alpha / centered / b1 / b2,
 rmsprop_centered_update, target_lerp; pyrela/utils.py: lr_at) restated twice, the way tests/optim_ref.py restates the defaults:
   step_f64    clip_grad_norm_ + RMSprop (any alpha, centred or not) / Adam (any betas) in float64, parameterised by the
               constants: torch_consts(...), or kernel_consts(...), the float32 values the kernels compute with;

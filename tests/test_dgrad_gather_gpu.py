@@ -1,4 +1,4 @@
-"""conv3's / conv2's data gradients in the f32 and f32x3 modes (csrc/learner_common.h: ProbDgrad3, ProbDgrad2 on gemm_lds):
+"""conv3's / conv2's data gradients in the f32 and f32x3 modes (csrc/learner_common.hip: ProbDgrad3, ProbDgrad2 on gemm_lds):
 the transposed convolutions as gather-form GEMMs over the layer's input pixels, 64 rows per block; conv2's four parity
 classes are the four N tiles of one launch, each over the 100 pixels per frame of its class.
 
@@ -22,7 +22,7 @@ from test_trunk_backward_gpu import exact_case, expected_census, run_tap
 
 pytestmark = pytest.mark.gpu
 
-BM = 64  # csrc/learner_common.h: TileDgrad3::BM and TileDgrad2::BM
+BM = 64  # csrc/learner_common.hip: TileDgrad3::BM and TileDgrad2::BM
 FRAMES = (1, 16, 17, 64, 65)
 assert (81 * 64) % BM == 0 and (100 * 16) % BM == 0
 CASES = [(mode, lanes, n) for n in FRAMES for mode in ("f32", "f32x3") for lanes in (0, 1)]

@@ -1,5 +1,5 @@
 """Everything between the Q tables and d_a3 in the Ape-X learner, one call at a time (include/rela_amd.h):
-  rela_debug_loss_grad          learner_td_loss_grad, or td_kernel + learner_loss_grad (csrc/learner_common.h)
+  rela_debug_loss_grad          learner_td_loss_grad, or td_kernel + learner_loss_grad (csrc/learner.hip)
   rela_debug_head_fc_backward   the four head / fc GEMMs of csrc/learner.hip: head_fc_backward in their three tile families
                                 (gemm_lds f32, gemm_bf16x3 with two and with three parts), the column sums of d_ha and d_h
                                 through the learner's multi-job launcher, head_bias_grad

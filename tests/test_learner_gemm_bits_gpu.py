@@ -14,7 +14,7 @@ is counted once whatever the order.  Every case runs the three precision modes' 
 
 Shapes: the smallest where the new code can go wrong.  A chunk is 32 k, the register ring of gemm_bf16x3 is 4 chunks.
   trunk, K = 400 f (conv1), 81 f (conv2), 49 f (conv3) rows of f frames, split over 64 / 81 / 84 K slices
-  (csrc/learner_common.h: kSplitW1, 3 x kSplitW2, 3 x kSplitW3), slice = ceil(chunks / splits) chunks:
+  (csrc/learner_plan.h: kSplitW1, 3 x kSplitW2, 3 x kSplitW3), slice = ceil(chunks / splits) chunks:
     1, 2    13 and 25 (conv1), 3 and 6 (conv2), 2 and 4 (conv3) chunks: one chunk per slice, most slices empty and
             writing zeros, every ring refill clamps, partial last chunks (400, 81, 49, 162, 98 mod 32 != 0);
     5       63 chunks of conv1 in 64 slices: one empty slice; conv2 / conv3 end on partial chunks (405, 245);

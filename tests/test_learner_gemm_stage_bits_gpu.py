@@ -10,7 +10,7 @@ So every output of the two one-call taps is compared by sha256 with tests/golden
 on an MI355X with this file's `compute()` from a checkout of the commit named in it: the parent of the stage depth
 (S = 1 everywhere).  Inputs are random at the scale of a trained agent (gain 4.6), so any reassociation flips bits.
 
-The instantiation with S > 1 (csrc/learner_common.h: TileW1, Tile6W32U8) is conv1's weight gradient; the 64 x 64 tiles of
+The instantiation with S > 1 (csrc/learner_common.hip: TileW1, Tile6W32U8) is conv1's weight gradient; the 64 x 64 tiles of
 conv2 / conv3 were measured at S = 2 with these same cases (and passed them) but are slower there and stay at S = 1.  The
 frame counts cover all three, so that a stage depth given to conv2 / conv3 later meets its slice ends here:
   conv1 (ProbW1),  K = 400 f, kSplitW1 = 64 slices,            S = 4 in f32 (gemm_lds), S = 2 in f32x3 (gemm_bf16x3)

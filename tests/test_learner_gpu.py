@@ -116,7 +116,7 @@ MERGED_MIN_B, MERGED_MAX_B = 128, 1023  # batches the merged split-bf16 forward 
 
 
 def _assert_fast_learner_kernels(counts, B):
-    """The kernels a bf16x2 learner step of B rows must launch (csrc/learner.hip, ffnet.hip, learner_common.h): from
+    """The kernels a bf16x2 learner step of B rows must launch (csrc/learner.hip, ffnet.hip, learner_common.hip): from
     128 rows the three forwards of td_err as ONE split-bf16 launch per layer (conv12_i8_jobs, conv3_bf16s_jobs,
     fc_bf16s split-K) and no f32 trunk kernel at all; at every size conv1's weight gradient and the conv2 / conv3 data
     gradients on bf16 MFMA -- so a silent fall-back to the f32 kernels cannot pass for a test of the fast ones."""
@@ -187,7 +187,7 @@ def test_learner_fast_mode_within_stated_tolerance(B):
     learner.close()
 
 
-FAST_WGRAD_MIN_FRAMES = 2048  # csrc/learner_common.h: from here conv2's / conv3's weight gradients run on bf16 MFMA too
+FAST_WGRAD_MIN_FRAMES = 2048  # csrc/learner_plan.h: from here conv2's / conv3's weight gradients run on bf16 MFMA too
 
 
 @pytest.mark.parametrize("B", [512, 200, 2051])

@@ -1,4 +1,4 @@
-"""The learners' configurable update rules on the GPU (include/rela_amd.h, csrc/learner_common.h):
+"""The learners' configurable update rules on the GPU (include/rela_amd.h, csrc/learner_common.h and .hip):
   rela_debug_optimizer_apply_opts   optimizer_apply with alpha / centered / betas: rmsprop_centered_update, and the two
                                     existing update kernels with other constants
   rela_debug_target_lerp            target_lerp, the kernel of the soft target update

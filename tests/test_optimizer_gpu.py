@@ -1,4 +1,4 @@
-"""The step of both learners that turns gradients into weights, one call at a time (include/rela_amd.h, csrc/learner_common.h):
+"""The step of both learners that turns gradients into weights, one call at a time (include/rela_amd.h, csrc/learner_common.hip):
   rela_debug_optimizer_apply     optimizer_apply: sumsq_partial, clip_coef, rmsprop_update / adam_update
 against tests/optim_ref.py: the float32 restatement in the kernels' order BIT FOR BIT, the float64 form within the bound counted
 from the roundings, on tables by role:

@@ -1,12 +1,13 @@
 """CPU checks of the R2D2 learner's "f32x3_bwd" mode (tests/test_r2d2_learner_bwd_mode_gpu.py has the GPU half).
 
 Resources: mode 3 instantiates gemm_bf16x3 (csrc/gemm_bf16x3.h) with three-part 64 x 64 tiles for three Problems of
-csrc/learner_r2d2.hip -- ProbWhh, ProbWih, ProbIhDgrad -- next to the conv weight gradients' three.  A block holds four
+csrc/learner_r2d2.hip -- ProbWhh, ProbWih, ProbIhDgrad -- next to the conv weight gradients' three, which both learners
+run from csrc/learner_common.hip.  A block holds four
 register sets of staged loads next to two accumulators per 16 x 16 tile and runs with a second block on its CU; a spill would
 put scratch traffic inside the chunk loop without any test of the results noticing.  So the compiler's own account is asserted
-(as tests/test_trunk_backward_resources_cpu.py does for csrc/learner.hip): csrc/learner_r2d2.hip is compiled device-only
-with build.py's HIP_FLAGS plus -Rpass-analysis=kernel-resource-usage, and every three-part gemm_bf16x3 kernel of the file
-must report `ScratchSize [bytes/lane]: 0`, `VGPRs Spill: 0`, `SGPRs Spill: 0` and an occupancy of at least 4 waves per
+(as tests/test_trunk_backward_resources_cpu.py does for csrc/learner_common.hip): both files are compiled device-only
+with build.py's HIP_FLAGS plus -Rpass-analysis=kernel-resource-usage, and every three-part gemm_bf16x3 kernel of
+learner_r2d2.hip and the three conv weight gradients of learner_common.hip must report `ScratchSize [bytes/lane]: 0`, `VGPRs Spill: 0`, `SGPRs Spill: 0` and an occupancy of at least 4 waves per
 SIMD (a block is 2: the tiles were chosen for two blocks per CU).  Only the remarks are read.
 
 Arguments: rela_amd/pyrela/main.py's --learner_precision and its two refusals.
@@ -22,16 +23,27 @@ THREE_PART = re.compile(r"11gemm_bf16x3I.*7TileCfgILi\d+ELi\d+ELi\d+ELi\d+ELb[01
 NEW_PROBLEMS = ("7ProbWhhE", "7ProbWihE", "11ProbIhDgradE")
 
 
+# the conv weight gradients (conv3, conv2: ProbConvWgrad; conv1: ProbW1), compiled in csrc/learner_common.hip
+CONV_WGRADS = ("13ProbConvWgradI", "6ProbW1E")
+
+
 @pytest.fixture(scope="module")
 def resources(tmp_path_factory):
-    """{mangled kernel name: {remark key: int}} of csrc/learner_r2d2.hip's kernels"""
-    return kernel_resources("learner_r2d2.hip", tmp_path_factory.mktemp("r2d2res"))
+    """{mangled kernel name: {remark key: int}} of the three-part gemm_bf16x3 kernels an R2D2 step can launch: all of
+    csrc/learner_r2d2.hip's, and the conv weight gradients' of csrc/learner_common.hip"""
+    tmp = tmp_path_factory.mktemp("r2d2res")
+    own = {n: v for n, v in kernel_resources("learner_r2d2.hip", tmp).items() if THREE_PART.search(n)}
+    trunk = {n: v for n, v in kernel_resources("learner_common.hip", tmp).items()
+             if THREE_PART.search(n) and any(p in n for p in CONV_WGRADS)}
+    assert own and not set(own) & set(trunk)
+    return {**own, **trunk}
 
 
 def test_three_part_gemms_have_no_scratch_and_no_spills(resources):
-    mine = {n: v for n, v in resources.items() if THREE_PART.search(n)}
+    mine = resources
     for prob in NEW_PROBLEMS:
         assert sum(prob in n for n in mine) == 1, (prob, sorted(mine))
+    assert sum(any(p in n for p in CONV_WGRADS) for n in mine) == 3, sorted(mine)  # conv3, conv2, conv1
     for name, v in sorted(mine.items()):
         print(name, v)
         assert v["ScratchSize [bytes/lane]"] == 0, (name, v)

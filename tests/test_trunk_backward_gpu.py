@@ -1,4 +1,4 @@
-"""The backward pass of the conv trunk (csrc/learner_common.h: trunk_backward -- wgrad_conv{1,2,3}_bf16, dgrad_conv{2,3}_bf16,
+"""The backward pass of the conv trunk (csrc/learner_common.hip: trunk_backward -- wgrad_conv{1,2,3}_bf16, dgrad_conv{2,3}_bf16,
 the f32 / three-part split-K GEMMs with col2im2/3, reduce_splits, the column sums) one call at a time, through
 rela_debug_trunk_backward, against the float64 reference of the same call (tests/trunk_bwd_ref.py).  The activations are
 inputs of the call, so the ReLU masks are data and the only error left is the kernels' arithmetic:

@@ -1,4 +1,4 @@
-"""Float64 reference of ONE call of the conv trunk's backward pass (csrc/learner_common.h: trunk_backward, reached through
+"""Float64 reference of ONE call of the conv trunk's backward pass (csrc/learner_common.hip: trunk_backward, reached through
 rela_debug_trunk_backward), with the forward's activations as inputs, so the ReLU masks are data:
 
   d_a2  = [a2 > 0] * convT(d_a3, W3)            g_c3w = d_a3 (x) patches(a2)          g_c3b = sum d_a3
