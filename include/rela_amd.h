@@ -176,6 +176,13 @@ int rela_replay_write_rows(rela_replay* r, int first_slot, int offset, int count
 int rela_replay_write_rows_gather(rela_replay* r, int first_slot, int count,
                                   const int32_t* dst_offset_dev, const void* const* bases_dev,
                                   const int32_t* const* src_index_dev, void* stream);
+/* write, by the producer itself: a producer whose own kernel on `stream` stores field `field` of the reserved block
+ * [first_slot, +count) -- plain fields only, not a sequence or de-duplicated stack field -- gets the field's base and
+ * the ring length (row first_slot + i at base + ((first_slot + i) mod ring) * row_bytes) and, on `stream`, the waits a
+ * row copy into these slots takes: the gathers of samples that evicted them.  It passes NULL for that field to
+ * rela_replay_write_rows; the commit on the same stream orders the rows before the block becomes visible.        */
+int rela_replay_direct_rows(rela_replay* r, int first_slot, int count, int field, void** base_dev, int* ring,
+                            int64_t* row_bytes, void* stream);
 int rela_replay_commit_add(rela_replay* r, int first_slot, int n, const float* priority_dev,
                            void* stream);
 /* The same commit for n = G*group_rows slots that stand for G consecutive reference blocks of
@@ -382,6 +389,12 @@ typedef struct {
   int32_t a3_records, x_in_gx;
 } rela_debug_workspace_view;
 int rela_ffnet_debug_workspace(const rela_ffnet* net, int n, rela_debug_workspace_view* view);
+/* Test tap: rela_ffnet_forward that also stores its n input frames (28,224 bytes each) into a ring of `ring` frame
+ * rows at rows_dev, frame i into row (first + i) mod ring (n <= ring), as the Ape-X shard's target forward does into
+ * the replay.  Only a forward whose trunk is conv12_s3 stores them: *copied says whether it did.              */
+int rela_ffnet_debug_forward_store_frames(const rela_ffnet* net, int n, const uint8_t* s_dev, const float* legal_dev,
+                                          float* q_dev, void* workspace_dev, int64_t workspace_bytes, void* rows_dev,
+                                          int first, int ring, int* copied, void* stream);
 
 /* AtariFFNet.forward  net.py:42-55: q[n,A] (device f32) from s u8[n,4,84,84], legal f32[n,A] */
 int rela_ffnet_forward(const rela_ffnet* net, int n, const uint8_t* s_dev, const float* legal_dev,
@@ -539,6 +552,11 @@ int64_t rela_apex_actor_num_act(const rela_apex_actor* a); /* numAct()  dqn_acto
  * on = 1 (default): reuse both; 2: only the one of next_obs; 0: always recompute, i.e. the reference's
  * 4 forwards per step */
 int rela_apex_actor_set_reuse(rela_apex_actor* a, int on);
+/* on = 1 (default): where the target net's forward of post_step runs conv12_s3 (f32x3, 512 rows and up) and the
+ * shard enters the replay as one block of plain rows, that forward stores next_obs into the block's rows itself
+ * (rela_replay_direct_rows) and the insert copies one field less; 0: every field is copied by the insert.  The
+ * replay's contents are the same bytes either way.                                                            */
+int rela_apex_actor_set_fused_insert(rela_apex_actor* a, int on);
 /* Invertible value rescaling of the priority's TD target (R2D2 as published, Kapturowski et al. 2019; the reference
  * leaves it out and clips rewards in its env instead, so ApexAgent.td_err apex.py:30-45 has no such step):
  * target = h(reward + bootstrap * gamma ** n * h_inv(target_q)), h(x) = sign(x) (sqrt(|x| + 1) - 1) + eps x, in the

@@ -147,6 +147,7 @@ _sig("rela_replay_dedup_steps", i32, [vp])
 _sig("rela_replay_begin_add", i32, [vp, i32, i32, P(i32)])
 _sig("rela_replay_write_rows", i32, [vp, i32, i32, i32, P(vp), vp])
 _sig("rela_replay_write_rows_gather", i32, [vp, i32, i32, vp, P(vp), P(vp), vp])
+_sig("rela_replay_direct_rows", i32, [vp, i32, i32, i32, P(vp), P(i32), P(i64), vp])
 _sig("rela_replay_commit_add", i32, [vp, i32, i32, vp, vp])
 _sig("rela_replay_commit_add_grouped", i32, [vp, i32, i32, i32, vp, vp])
 _sig("rela_replay_abort_add", i32, [vp, i32, i32])
@@ -186,6 +187,7 @@ _sig("rela_lstmnet_set_precision", i32, [vp, i32])
 _sig("rela_lstmnet_precision", i32, [vp])
 _sig("rela_ffnet_workspace_bytes", i64, [vp, i32])
 _sig("rela_ffnet_debug_workspace", i32, [vp, i32, P(DebugWorkspaceView)])
+_sig("rela_ffnet_debug_forward_store_frames", i32, [vp, i32, vp, vp, vp, vp, i64, vp, i32, i32, P(i32), vp])
 _sig("rela_lstmnet_debug_workspace", i32, [vp, i32, P(DebugWorkspaceView)])
 _sig("rela_ffnet_forward", i32, [vp, i32, vp, vp, vp, vp, i64, vp])
 _sig("rela_lstmnet_create", i32, [P(vp), i32, i32])
@@ -214,6 +216,7 @@ _sig("rela_apex_actor_post_step", i32, [vp, vp, vp, i32, vp, vp, i32, P(i32), vp
 _sig("rela_apex_actor_set_dedup", i32, [vp, i32])
 _sig("rela_apex_actor_num_act", i64, [vp])
 _sig("rela_apex_actor_set_reuse", i32, [vp, i32])
+_sig("rela_apex_actor_set_fused_insert", i32, [vp, i32])
 _sig("rela_apex_actor_set_value_rescale", i32, [vp, f32])
 _sig("rela_apex_actor_last_q_dev", vp, [vp])
 _sig("rela_apex_actor_last_priority_dev", vp, [vp])

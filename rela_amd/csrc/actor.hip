@@ -11,6 +11,7 @@
 #include <cmath>
 
 #include "actor_shard.h"
+#include "ffnet_layout.h"
 
 using namespace rela_amd;
 
@@ -84,6 +85,11 @@ extern "C" int rela_apex_actor_screens_to_stacks(rela_apex_actor* a, const uint8
 }
 extern "C" int rela_apex_actor_set_reuse(rela_apex_actor* a, int on) {
   return shard_set_reuse(a, on, "rela_apex_actor_set_reuse");
+}
+extern "C" int rela_apex_actor_set_fused_insert(rela_apex_actor* a, int on) {
+  RELA_CHECK(a && (on == 0 || on == 1), RELA_EINVAL, "rela_apex_actor_set_fused_insert: 0 (off) or 1 (on)");
+  a->fused_insert = on != 0;
+  return RELA_OK;
 }
 extern "C" int rela_apex_actor_set_value_rescale(rela_apex_actor* a, float eps) {
   return shard_set_value_rescale(a, eps, "rela_apex_actor_set_value_rescale");
@@ -195,18 +201,6 @@ extern "C" int rela_apex_actor_post_step(rela_apex_actor* a, const float* reward
     if (rc != RELA_OK) return rc;
     q_online_n = a->q + 2 * QA;
   }
-  rc = rela_ffnet_forward(target, a->R, obs_n, legal_n, a->q + 3 * QA, a->ws, a->ws_bytes, s);  // :42
-  if (rc != RELA_OK) return rc;
-  const int64_t* act_t = a->act + (size_t)first * a->R;
-  rc = td_from_q(a->R, a->A, a->K, q_online_t, q_online_n, a->q + 3 * QA, legal_n, act_t, a->out_r, a->out_b, a->gamma_n,
-                 a->vr_eps, nullptr, a->prio, s);
-  if (rc != RELA_OK) return rc;
-  // FFTransition rows (types.h:18-51): obs{s,eps,legal_move}, next_obs{...}, action{a}, reward, terminal, bootstrap
-  const void* rows[10] = {obs_t, obs_n, eps_t, eps_n, legal_t, legal_n, act_t, a->out_r, a->out_t, a->out_b};
-  if (a->dd_ups > 0) {
-    rows[0] = a->ref_hist + (size_t)first * a->R * a->dd_ups;
-    rows[1] = a->ref_hist + (size_t)last * a->R * a->dd_ups;
-  }
   // One reference block per group of K rows (each batched actor thread's own add, :189).  The whole shard
   // is reserved at once when that can always be satisfied; a blocking append of more than ring - capacity
   // rows never can (sample() evicts down to capacity only), so a shard that large goes in pieces of whole
@@ -216,6 +210,50 @@ extern "C" int rela_apex_actor_post_step(rela_apex_actor* a, const float* reward
   if (rc != RELA_OK) return rc;
   const int fit = ((ring - cap) / a->K) * a->K;
   const int piece = a->R <= ring - cap ? a->R : (fit > a->K ? fit : a->K);
+  // Fused insert: the target forward reads every byte of obs_n, the very rows the insert copies into the replay's
+  // next_obs field.  Where its trunk is conv12_s3 (f32x3, 512 rows and up) and the shard goes in as ONE block of plain
+  // rows, the block is reserved here already and the forward stores the frames into its rows from the registers it stages
+  // them in (conv12_s3_copy): one replay_scatter_rows launch and one read of R frames less per tick.  The rows are
+  // written on `s`, behind the waits rela_replay_direct_rows puts there and ahead of the event commit_add records on `s`.
+  // Anything else -- de-duplicated stacks, a shard in pieces, another trunk, a reservation that would block -- takes the
+  // path below unchanged.
+  int fused_slot = -1, fused_copied = 0;
+  if (a->fused_insert && a->dd_ups == 0 && piece == a->R && ffnet_forward_stores_frames(target, a->R)) {
+    rc = rela_replay_begin_add(a->replay, a->R, nonblocking, &fused_slot);
+    if (rc == RELA_EWOULDBLOCK) fused_slot = -1;
+    else if (rc != RELA_OK) return rc;
+  }
+  if (fused_slot >= 0) {
+    void* base = nullptr;
+    int rows_ring = 0;
+    int64_t row_bytes = 0;
+    rc = rela_replay_direct_rows(a->replay, fused_slot, a->R, 1, &base, &rows_ring, &row_bytes, s);
+    if (rc == RELA_OK && row_bytes != kObs) {
+      set_last_error("rela_apex_actor_post_step: the replay's next_obs rows have %lld bytes, a frame stack %lld",
+                     (long long)row_bytes, (long long)kObs);
+      rc = RELA_EINVAL;
+    }
+    if (rc == RELA_OK)
+      rc = ffnet_forward_store_frames(target, a->R, obs_n, legal_n, a->q + 3 * QA, a->ws, a->ws_bytes, s,
+                                      FrameRows{static_cast<uint8_t*>(base), fused_slot, rows_ring}, &fused_copied);  // :42
+  } else {
+    rc = rela_ffnet_forward(target, a->R, obs_n, legal_n, a->q + 3 * QA, a->ws, a->ws_bytes, s);  // :42
+  }
+  const int64_t* act_t = a->act + (size_t)first * a->R;
+  if (rc == RELA_OK)
+    rc = td_from_q(a->R, a->A, a->K, q_online_t, q_online_n, a->q + 3 * QA, legal_n, act_t, a->out_r, a->out_b, a->gamma_n,
+                   a->vr_eps, nullptr, a->prio, s);
+  if (rc != RELA_OK) {
+    if (fused_slot >= 0) (void)rela_replay_abort_add(a->replay, fused_slot, a->R);
+    return rc;
+  }
+  // FFTransition rows (types.h:18-51): obs{s,eps,legal_move}, next_obs{...}, action{a}, reward, terminal, bootstrap
+  const void* rows[10] = {obs_t, obs_n, eps_t, eps_n, legal_t, legal_n, act_t, a->out_r, a->out_t, a->out_b};
+  if (a->dd_ups > 0) {
+    rows[0] = a->ref_hist + (size_t)first * a->R * a->dd_ups;
+    rows[1] = a->ref_hist + (size_t)last * a->R * a->dd_ups;
+  }
+  // (the blocks: `piece` rows each, above; a fused insert's one block is reserved already and has its next_obs rows)
   const int64_t stack_rb = a->dd_ups > 0 ? (int64_t)sizeof(int32_t) * a->dd_ups : kObs;
   const int64_t rb[10] = {stack_rb, stack_rb, 4, 4, 4 * a->A, 4 * a->A, 8, 4, 1, 4};
   int dropped = dd_drop ? 1 : 0;
@@ -223,13 +261,17 @@ extern "C" int rela_apex_actor_post_step(rela_apex_actor* a, const float* reward
     const int cnt = a->R - off < piece ? a->R - off : piece;
     const void* prow[10];
     for (int f = 0; f < 10; ++f) prow[f] = static_cast<const uint8_t*>(rows[f]) + (int64_t)off * rb[f];
-    int slot = 0;
-    rc = rela_replay_begin_add(a->replay, cnt, nonblocking, &slot);
-    if (rc == RELA_EWOULDBLOCK) {
-      dropped = 1;
-      continue;
+    int slot = fused_slot;
+    if (fused_slot >= 0) {  // (piece == R: this is the only block)
+      if (fused_copied) prow[1] = nullptr;
+    } else {
+      rc = rela_replay_begin_add(a->replay, cnt, nonblocking, &slot);
+      if (rc == RELA_EWOULDBLOCK) {
+        dropped = 1;
+        continue;
+      }
+      if (rc != RELA_OK) break;
     }
-    if (rc != RELA_OK) break;
     if (a->dd_ups > 0) (void)rela_replay_set_block_min_unit(a->replay, slot, cnt, dd_min_seq);
     rc = rela_replay_write_rows(a->replay, slot, 0, cnt, prow, s);
     if (rc == RELA_OK) rc = rela_replay_commit_add_grouped(a->replay, slot, cnt, a->K, a->prio + off, s);

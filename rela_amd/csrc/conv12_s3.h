@@ -79,11 +79,16 @@ struct Conv12S {
 
 // W1d / scale1 / bias1q: pack_conv1_i8 ([digit][ct 2][tap 4][lane] x 16 int8); B2: pack_f32emu_at mode 1
 // ([ks][u][part][lane] x 8 bf16); out: a2 records [N][81] x 384 B; A1OUT: a1 also as f32 [N][400][32] (a1_out).
-template <bool A1OUT>
-__global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ in, const uint4* __restrict__ W1d,
-                                                    const float* __restrict__ scale1, const float* __restrict__ bias1q,
-                                                    const uint4* __restrict__ B2, const float* __restrict__ bias2,
-                                                    uint8_t* __restrict__ out, float* __restrict__ a1_out, int N) {
+// COPY (conv12_s3_copy, the Ape-X shard's target forward): every 16-byte row piece a thread stages is ALSO stored, from
+// the registers it was loaded into, to the frame's row of a ring of frame rows: frame fr -> copy_dst + ((copy_first + fr)
+// wrapped once at copy_ring) * IN_ELEMS.  The units cover all 84 bytes of all 84 rows of the 4 planes (bytes 68 .. 79 of a
+// row and the clamped last unit twice, with the same values), so the row is the frame, byte for byte.
+template <bool A1OUT, bool COPY>
+__device__ __forceinline__ void conv12_s3_body(const uint8_t* __restrict__ in, const uint4* __restrict__ W1d,
+                                               const float* __restrict__ scale1, const float* __restrict__ bias1q,
+                                               const uint4* __restrict__ B2, const float* __restrict__ bias2,
+                                               uint8_t* __restrict__ out, float* __restrict__ a1_out, int N,
+                                               uint8_t* __restrict__ copy_dst, int copy_first, int copy_ring) {
   using F = Conv12S;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_c12[];
   uint8_t* t1 = smem_c12;
@@ -148,6 +153,16 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
     const uint8_t* fb = in + (size_t)fr * F::IN_ELEMS;  // uniform frame base + 32-bit offset + the row as immediate
 #pragma unroll
     for (int r = 0; r < 4; ++r) sq[j][r] = *reinterpret_cast<const u32x4_a4*>(fb + (size_t)ugoff[j] + r * 84);
+  };
+  // COPY: frame fr's row of the destination ring (uniform: copy_first + fr < 2 copy_ring, one compare and subtract) ...
+  auto copy_row = [&](int fr) __attribute__((always_inline)) -> uint8_t* {
+    int sl = copy_first + fr;
+    if (sl >= copy_ring) sl -= copy_ring;
+    return copy_dst + (size_t)sl * F::IN_ELEMS;
+  };
+  // ... and row r of unit j into it, at the place it was loaded from (uniform base + the same 32-bit offset + immediate)
+  auto g_copy4 = [&](uint8_t* cb, int j, int r) __attribute__((always_inline)) {
+    *reinterpret_cast<u32x4_a4*>(cb + (size_t)ugoff[j] + r * 84) = sq[j][r];
   };
   auto s_store4 = [&](int j, int k) __attribute__((always_inline)) {  // cell X0 + k of unit j; x -> x - 128: flip the sign bits
     *reinterpret_cast<uint4*>(t1 + uloff[j] + k * 16) = make_uint4(sq[j][0][k] ^ 0x80808080u, sq[j][1][k] ^ 0x80808080u,
@@ -276,6 +291,13 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
   for (int j = 0; j < F::UIT; ++j)
 #pragma unroll
     for (int k = 0; k < 4; ++k) s_store4(j, k);
+  if constexpr (COPY) {
+    uint8_t* cb = copy_row(n);
+#pragma unroll
+    for (int j = 0; j < F::UIT; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) g_copy4(cb, j, r);
+  }
   __syncthreads();
 
   auto copy_hook = [&](auto idx_tag) {
@@ -362,6 +384,9 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
   int filled = 0;  // the ring's slots in use (uniform)
   for (; n < N; n += nblk) {
     const int nn = (n + nblk < N) ? n + nblk : n;  // (the last round re-stages its own frame)
+    // (COPY: ... and stores it again, the same bytes to the same row; no branch inside conv2's instruction stream)
+    uint8_t* cbn = nullptr;
+    if constexpr (COPY) cbn = copy_row(nn);
     pin_weights();
     conv1_pass(IC<0>{}, IC<5>{}, copy_hook);
     conv1_pass(IC<5>{}, IC<4>{}, no_hook);
@@ -401,11 +426,13 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
         if constexpr (IDX + D < TOT) a_issue(IC<IDX + D>{}, SLOT);
         if constexpr (IDX == 2) *reinterpret_cast<uint4*>(smem_c12 + pdst + filled * F::SLOT_BYTES) = patch;
         // the next frame's two units: loaded behind items 1 and 13, their eight cells stored (sign bits flipped) behind
-        // items 40, 44, ..., 68
+        // items 40, 44, ..., 68 (COPY: one of the unit's four rows goes to the destination row with each cell, so the
+        // staged registers live exactly as long as before)
         static_for<4 * F::UIT>([&](auto jj) {
           constexpr int JJ = decltype(jj)::value;
           if constexpr (JJ < F::UIT && IDX == 1 + 12 * JJ && !kNoStage) g_load4(nn, JJ);
           if constexpr (IDX == TOT / 2 + 4 * JJ && !kNoStage) s_store4(JJ >> 2, JJ & 3);
+          if constexpr (COPY && IDX == TOT / 2 + 4 * JJ && !kNoStage) g_copy4(cbn, JJ >> 2, JJ & 3);
         });
         if constexpr (KS == F::KS2 - 1 && kNoEpi2) asm volatile("" ::"v"(acc), "v"(accs));
         if constexpr (KS == F::KS2 - 1 && !kNoEpi2) {  // tile T complete: ReLU, split, its record slice into O
@@ -441,15 +468,39 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
   }
 }
 
+template <bool A1OUT>
+__global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ in, const uint4* __restrict__ W1d,
+                                                    const float* __restrict__ scale1, const float* __restrict__ bias1q,
+                                                    const uint4* __restrict__ B2, const float* __restrict__ bias2,
+                                                    uint8_t* __restrict__ out, float* __restrict__ a1_out, int N) {
+  conv12_s3_body<A1OUT, false>(in, W1d, scale1, bias1q, B2, bias2, out, a1_out, N, nullptr, 0, 0);
+}
+// conv12_s3<false> that also stores frame fr to row (copy_first + fr) mod copy_ring of copy_dst (N <= copy_ring)
+__global__ __launch_bounds__(256, 1) void conv12_s3_copy(const uint8_t* __restrict__ in, const uint4* __restrict__ W1d,
+                                                         const float* __restrict__ scale1, const float* __restrict__ bias1q,
+                                                         const uint4* __restrict__ B2, const float* __restrict__ bias2,
+                                                         uint8_t* __restrict__ out, int N, uint8_t* __restrict__ copy_dst,
+                                                         int copy_first, int copy_ring) {
+  conv12_s3_body<false, true>(in, W1d, scale1, bias1q, B2, bias2, out, nullptr, N, copy_dst, copy_first, copy_ring);
+}
+
 // frames u8 [N][4][84][84] -> a2 as split3 records at rec2; a1 != NULL: a1 as channel-last f32 too (A1OUT)
 inline void launch_conv12(const uint8_t* frames, const uint4* W1d, const float* s1q, const float* b1q, const uint4* B2e,
                           const float* b2, uint8_t* rec2, float* a1, int N, hipStream_t s, int blocks) {
   const auto kernel = a1 ? conv12_s3<true> : conv12_s3<false>;
   hipLaunchKernelGGL(kernel, dim3(blocks), dim3(Conv12S::kT), Conv12S::LDS_TOTAL, s, frames, W1d, s1q, b1q, B2e, b2, rec2, a1, N);
 }
-// both instantiations' opt-in to their dynamic LDS (once per process, before the first launch)
+// ... and every frame to its row of the ring of frame rows at copy_dst (0 <= copy_first < copy_ring, N <= copy_ring)
+inline void launch_conv12_copy(const uint8_t* frames, const uint4* W1d, const float* s1q, const float* b1q, const uint4* B2e,
+                               const float* b2, uint8_t* rec2, int N, hipStream_t s, int blocks, uint8_t* copy_dst,
+                               int copy_first, int copy_ring) {
+  hipLaunchKernelGGL(conv12_s3_copy, dim3(blocks), dim3(Conv12S::kT), Conv12S::LDS_TOTAL, s, frames, W1d, s1q, b1q, B2e, b2, rec2,
+                     N, copy_dst, copy_first, copy_ring);
+}
+// the three kernels' opt-in to their dynamic LDS (once per process, before the first launch)
 inline int opt_in_lds_conv12() {
-  for (const void* k : {reinterpret_cast<const void*>(&conv12_s3<false>), reinterpret_cast<const void*>(&conv12_s3<true>)})
+  for (const void* k : {reinterpret_cast<const void*>(&conv12_s3<false>), reinterpret_cast<const void*>(&conv12_s3<true>),
+                        reinterpret_cast<const void*>(&conv12_s3_copy)})
     RELA_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, Conv12S::LDS_TOTAL));
   return RELA_OK;
 }

@@ -101,6 +101,7 @@ struct TrunkLabels {  // per-kernel timing labels (prof.h); conv12: the launch t
 struct TrunkOpts {
   bool keep_f32 = false;          // kTrunkS3: a1 is ALSO written as channel-last f32 (a2 / a3: unsplit_s3_a23, the caller's)
   bool leave_a3_records = false;  // kTrunkBf16: a3 stays in split records instead of going back to f32 in place
+  const FrameRows* store_frames = nullptr;  // kTrunkS3 without keep_f32: the frames also go to these rows (conv12_s3_copy)
 };
 // kTrunkF32:  a1 / a2 / a3 channel-last f32
 // kTrunkBf16: a1 is NOT produced; a2 / a3 hold split-bf16 records in the f32 tensors' places (same bytes)
@@ -113,7 +114,13 @@ void launch_trunk(const FFNetDev& d, TrunkKind kind, int N, const uint8_t* s_dev
       {
         ProfScope prof(l.conv12, s);
         note_launch("conv12_s3");
-        s3::launch_conv12(s_dev, d.W1d, d.s1q, d.b1q, d.B2e, d.b2, rec2, o.keep_f32 ? a1 : nullptr, N, s, persistent_blocks(N));
+        if (o.store_frames) {
+          note_launch("conv12_s3_copy");  // (counted under both names: it is a conv12_s3 launch that also copies)
+          s3::launch_conv12_copy(s_dev, d.W1d, d.s1q, d.b1q, d.B2e, d.b2, rec2, N, s, persistent_blocks(N), o.store_frames->base,
+                                 o.store_frames->first, o.store_frames->ring);
+        } else {
+          s3::launch_conv12(s_dev, d.W1d, d.s1q, d.b1q, d.B2e, d.b2, rec2, o.keep_f32 ? a1 : nullptr, N, s, persistent_blocks(N));
+        }
       }
       ProfScope prof(l.conv3, s);
       note_launch("conv3_img_s3");
@@ -504,6 +511,8 @@ int rela_amd::ffnet_load_extra(rela_ffnet* n, const rela_ffnet_params* p, void* 
   return ffnet_load_impl(n, p, 1, stream_, extra);
 }
 
+static int forward_impl(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev, float* q_dev, void* ws,
+                        int64_t ws_bytes, void* stream_, int mode, int rows_limit, const FrameRows* store, int* copied);
 extern "C" int rela_ffnet_forward(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev,
                                   float* q_dev, void* ws, int64_t ws_bytes, void* stream_) {
   return rela_amd::ffnet_forward_mode(n, N, s_dev, legal_dev, q_dev, ws, ws_bytes, stream_, kModeNet);
@@ -511,6 +520,31 @@ extern "C" int rela_ffnet_forward(const rela_ffnet* n, int N, const uint8_t* s_d
 
 int rela_amd::ffnet_forward_mode(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev, float* q_dev,
                                  void* ws, int64_t ws_bytes, void* stream_, int mode, int rows_limit) {
+  return forward_impl(n, N, s_dev, legal_dev, q_dev, ws, ws_bytes, stream_, mode, rows_limit, nullptr, nullptr);
+}
+
+bool rela_amd::ffnet_forward_stores_frames(const rela_ffnet* n, int N) {
+  return n && N >= 1 && plan_ffnet_forward(kModeNet, n->precision, N, n->max_rows).trunk == kTrunkS3;
+}
+int rela_amd::ffnet_forward_store_frames(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev, float* q_dev,
+                                         void* ws, int64_t ws_bytes, void* stream_, const FrameRows& rows, int* copied) {
+  RELA_CHECK(copied && rows.base && ((uintptr_t)rows.base & 3) == 0 && rows.first >= 0 && rows.first < rows.ring && N <= rows.ring,
+             RELA_EINVAL, "ffnet_forward_store_frames: bad frame rows (first %d, ring %d, %d frames)", rows.first, rows.ring, N);
+  return forward_impl(n, N, s_dev, legal_dev, q_dev, ws, ws_bytes, stream_, kModeNet, -1, &rows, copied);
+}
+
+// Test tap: ffnet_forward_store_frames over a caller's ring of frame rows
+extern "C" int rela_ffnet_debug_forward_store_frames(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev,
+                                                     float* q_dev, void* ws, int64_t ws_bytes, void* rows_dev, int first,
+                                                     int ring, int* copied, void* stream_) {
+  return rela_amd::ffnet_forward_store_frames(n, N, s_dev, legal_dev, q_dev, ws, ws_bytes, stream_,
+                                              FrameRows{static_cast<uint8_t*>(rows_dev), first, ring}, copied);
+}
+
+// store != NULL: a kTrunkS3 plan also stores the frames into *store and sets *copied, any other plan clears it
+static int forward_impl(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev, float* q_dev, void* ws,
+                        int64_t ws_bytes, void* stream_, int mode, int rows_limit, const FrameRows* store, int* copied) {
+  if (copied) *copied = 0;
   RELA_CHECK(n && n->loaded, RELA_ESTATE, "rela_ffnet_forward: parameters were never loaded");
   const int max_rows = rows_limit < 0 ? n->max_rows : rows_limit;
   RELA_CHECK(N >= 1 && s_dev && legal_dev && q_dev && ws, RELA_EINVAL, "rela_ffnet_forward: bad arguments");
@@ -542,6 +576,10 @@ int rela_amd::ffnet_forward_mode(const rela_ffnet* n, int N, const uint8_t* s_de
   TrunkOpts opts;
   opts.keep_f32 = plan.keep_f32;
   opts.leave_a3_records = !plan.unsplit_a3;
+  if (store && plan.trunk == kTrunkS3 && !plan.keep_f32) {
+    opts.store_frames = store;
+    *copied = 1;
+  }
   launch_trunk(d, plan.trunk, N, s_dev, w.a1, w.a2, w.a3, rec2, rec3, opts, {names[0], names[1], names[2], name12}, s);
 
   float* const part = fc_part_ptr(ws, w.ha, N);  // (the split-K fcs' partial tiles)

@@ -73,6 +73,19 @@ void ffnet_set_max_rows(rela_ffnet* n, int rows);
 // last load did not pack.
 int ffnet_forward_mode(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev, float* q_dev, void* ws,
                        int64_t ws_bytes, void* stream, int mode, int rows_limit = -1);
+// A ring of `ring` frame rows (kFrameBytes each, 4-byte aligned) at `base`: row (first + i) mod ring takes frame i.
+constexpr int64_t kFrameBytes = 4 * 84 * 84;
+struct FrameRows {
+  uint8_t* base;
+  int first, ring;
+};
+// rela_ffnet_forward (the net's own precision) that ALSO stores its N input frames into `rows` (N <= rows.ring), from the
+// registers conv12_s3_copy stages them in -- the Ape-X shard's target forward, which so writes next_obs into the replay
+// (actor.hip).  Only a kTrunkS3 plan can: *copied says whether the frames were stored; 0 = an ordinary forward ran and
+// the caller copies them itself.  ffnet_forward_stores_frames: what *copied will be, for a caller that must know before.
+bool ffnet_forward_stores_frames(const rela_ffnet* n, int N);
+int ffnet_forward_store_frames(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev, float* q_dev, void* ws,
+                               int64_t ws_bytes, void* stream, const FrameRows& rows, int* copied);
 // The Ape-X learner's three forwards of td_err (apex.py:30-45) in split-bf16 with one launch per layer: online over
 // [s ; s'] (2 B rows) and target over s' (B rows).  ws_on: ffnet_ws layout for 2 B rows, ws_tg for B rows; a1 (rows < B),
 // a2, a3 come out as split records; ffnet_learner_unsplit turns the rows < B into f32 in place for the backward pass.

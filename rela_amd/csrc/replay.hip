@@ -1069,6 +1069,7 @@ extern "C" int rela_replay_write_rows(rela_replay* r, int first_slot, int offset
     const int v16 = vec16_ok(rows_dev[f], r->fields[f].base, rb);
     {
       ProfScope prof("replay_scatter_rows", r->copy_stream);
+      note_launch("replay_scatter_rows");
       hipLaunchKernelGGL(replay_scatter_rows, dim3(grid_x(v16 ? (rb >> 4) : rb), std::min(count, 32768)), dim3(kThreads), 0,
                          r->copy_stream, (const uint8_t*)rows_dev[f], r->fields[f].base, rb, count, r->ring, start, v16);
     }
@@ -1101,6 +1102,7 @@ extern "C" int rela_replay_write_rows_gather(rela_replay* r, int first_slot, int
     const int v16 = vec16_ok(bases_dev[f], r->fields[f].base, rb);
     {
       ProfScope prof("replay_scatter_rows", r->copy_stream);
+      note_launch("replay_scatter_rows");
       hipLaunchKernelGGL(replay_scatter_rows_indexed, dim3(grid_x(v16 ? (rb >> 4) : rb), std::min(count, 32768)),
                          dim3(kThreads), 0, r->copy_stream, (const uint8_t*)bases_dev[f], src_index_dev[f], dst_offset_dev,
                          r->fields[f].base, rb, count, r->ring, first_slot, v16);
@@ -1108,6 +1110,36 @@ extern "C" int rela_replay_write_rows_gather(rela_replay* r, int first_slot, int
   }
   RELA_LAUNCH_CHECK();
   return copy_end(r, producer);
+}
+
+// A producer that writes field `field` of its reserved block [first_slot, first_slot + count) ITSELF, from a kernel on its
+// own stream (the Ape-X shard's target forward stores next_obs so, conv12_s3_copy): the field's base and the ring length;
+// row first_slot + i lives at base + ((first_slot + i) mod ring) * row_bytes.  The producer's stream gets the waits
+// copy_begin gives the copy stream: the gathers of every sample that evicted one of these slots and may still be reading
+// it (the slots are the producer's alone until commit, so no later eviction can touch them).  The producer then passes
+// NULL for this field to rela_replay_write_rows.  Ordering of the rows against the block's publication: commit_add records
+// ev_in (in-order form) or ev_cin (decoupled form) on the producer's stream BEHIND the kernel that wrote them, and the
+// replay / copy stream waits for that event before the append, so every reader of the published block (sample's gathers
+// run on the replay stream behind the append) sees the rows, exactly as it sees the rows write_rows copied.
+extern "C" int rela_replay_direct_rows(rela_replay* r, int first_slot, int count, int field, void** base_dev, int* ring,
+                                       int64_t* row_bytes, void* stream_) {
+  RELA_CHECK(r && count > 0 && first_slot >= 0 && first_slot < r->ring && count <= r->ring && base_dev && ring, RELA_EINVAL,
+             "rela_replay_direct_rows: bad arguments");
+  RELA_CHECK(field >= 0 && field < (int)r->fields.size() && r->sc.steps[(size_t)field] == 1 && !r->sc.is_stack(field), RELA_EINVAL,
+             "rela_replay_direct_rows: field %d is not a plain row field of this schema", field);
+  hipStream_t producer = (hipStream_t)stream_;
+  DeviceGuard g(r->device);
+  std::lock_guard<std::mutex> lk(r->m);
+  auto overlaps = [&](int a0, int an, int b0, int bn) {  // ring intervals [a0, a0 + an) and [b0, b0 + bn)
+    const int d = ((b0 - a0) % r->ring + r->ring) % r->ring;
+    return d < an || d + bn > r->ring;
+  };
+  for (auto& e : r->evictions)
+    if (overlaps(first_slot, count, e.start, e.count)) RELA_HIP(hipStreamWaitEvent(producer, e.done, 0));
+  *base_dev = r->fields[(size_t)field].base;
+  *ring = r->ring;
+  if (row_bytes) *row_bytes = r->sc.row_bytes[(size_t)field];
+  return RELA_OK;
 }
 
 // (caller holds r->m) blockAppend's arithmetic for the n slots from first_slot, on the replay's stream.  Large grouped

@@ -147,6 +147,11 @@ class ApexActorEngine:
         forwards of this tick and of n ticks ago; 2: only the one of this tick."""
         capi.check(capi.lib.rela_apex_actor_set_reuse(self.h, int(on)), "rela_apex_actor_set_reuse")
 
+    def set_fused_insert(self, on):
+        """True (default): the target forward of post_step stores next_obs into the replay's rows itself where it can
+        (f32x3, 512 rows and up, the shard as one block); False: the insert copies every field."""
+        capi.check(capi.lib.rela_apex_actor_set_fused_insert(self.h, int(bool(on))), "rela_apex_actor_set_fused_insert")
+
     def next_obs_slot(self):
         """The HBM slot the env layer writes the next observation batch into ([R,4,84,84] u8)."""
         ptr = capi.lib.rela_apex_actor_obs_slot(self.h)

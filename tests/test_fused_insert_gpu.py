@@ -1,0 +1,169 @@
+"""The Ape-X shard's fused insert (csrc/actor.hip, rela_apex_actor_set_fused_insert) stores the same replay.
+
+With the switch on (the default), where the target net's forward of post_step runs conv12_s3 (f32x3, 512 rows and up)
+and the shard enters the replay as one block of plain rows, the block is reserved before that forward and the forward
+writes next_obs into the block's rows itself (conv12_s3_copy, rela_replay_direct_rows); the insert then copies nine
+fields instead of ten.  Nothing a reader of the replay can see may change, so the same seeded tick sequence runs twice,
+switch on and off, and after every insert the block's rows of all ten fields (rela_replay_debug_read_rows, the ring's
+wrap followed), the priorities, the Q table of the tick's act(), the weights of the whole ring and sum_ are compared
+with exact equality -- as are the ids, rows and IS weights of every sample.  In the plain schema the stored next_obs
+rows are also compared with the frames acted on this tick and the obs rows with those of n ticks ago.
+
+Shapes: R = 512 and 513 rows are the smallest that reach conv12_s3, and 513 makes its blocks own one and two frames;
+K = 64 and 57 (513 = 9 x 57); n = 3; random frames.  The ring has 5 R + 100 slots (capacity 4 / 5 of it, so that
+ring - capacity >= R and the shard is one block): five inserts fill it to ring - 100, a sample then evicts the oldest
+slots down to the capacity, and the sixth insert starts ring - 100 slots in, WRAPS, and rewrites exactly the slots that
+sample has just evicted (its gathers may still be reading them: the forward waits for them on its own stream).  A
+seventh insert follows another sample.
+
+The census (note_launch) says which path ran: fused, exactly one replay_scatter_rows and one conv12_s3_copy per insert;
+every other case two replay_scatter_rows and no conv12_s3_copy -- f32 and bf16x2 nets (another trunk), R = 128 (below
+conv12_s3's 512 rows), and dedup="stack", whose stack fields are int32 references: there write_rows launches no
+replay_scatter_rows at all, with the switch on or off, and the census of the two runs is compared instead.  The
+decoupled insert form (rela_replay_set_decoupled_insert) runs once at R = 512.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+A, N_STEP = 18, 3
+FRAME = 4 * 84 * 84
+BATCH = 64
+
+_frames = {}
+
+
+def frames_of(R, ticks):
+    """[ticks][R][4][84][84] u8, seeded; made once per R and shared by the runs that compare against each other"""
+    if R not in _frames or _frames[R].shape[0] < ticks:
+        _frames[R] = np.random.default_rng(900 + R).integers(0, 256, (ticks, R, 4, 84, 84), dtype=np.uint8)
+    return _frames[R]
+
+
+def read_block(replay, field, first, count, ring):
+    from rela_amd import _capi as capi
+
+    rb = replay.row_bytes[field]
+    if replay.dedup and field < 2:  # a de-duplicated stack field holds int32 references, one per unit of the stack
+        rb = 4 * {"stack": 1, "plane": 4}[replay.dedup]
+    out = np.zeros((count, rb), np.uint8)
+    head = min(count, ring - first)
+    for dst0, slot, cnt in ((0, first, head), (head, 0, count - head)):
+        if cnt > 0:
+            part = out[dst0:dst0 + cnt]
+            capi.check(capi.lib.rela_replay_debug_read_rows(replay.h, field, slot, cnt, part.ctypes.data_as(C.c_void_p)),
+                       "debug_read_rows")
+    return out
+
+
+def run(R, K, precision, fused, ticks, *, dedup=None, decoupled=False, sample_after=()):
+    """-> (trace, per-insert census, first slot of every inserted block, ring)"""
+    import torch
+
+    from rela_amd import _capi as capi
+    from rela_amd.engine import ApexActorEngine, FFNetHandle
+    from rela_amd.replay import FFReplay
+    from synth import synth_params
+
+    dev = "cuda:0"
+    ring = 5 * R + 100
+    assert ring % 5 == 0
+    cap = ring * 4 // 5
+    on, tg = FFNetHandle(A, dev), FFNetHandle(A, dev)
+    on.load_state_dict({k: torch.from_numpy(v) for k, v in synth_params(A, 61).items()})
+    tg.load_state_dict({k: torch.from_numpy(v) for k, v in synth_params(A, 62).items()})
+    on.set_precision(precision)
+    tg.set_precision(precision)
+    replay = FFReplay(cap, 7, 0.6, 0.4, 0, A, dev, dedup=dedup, guard_units=(N_STEP + 8) * R if dedup else 0)
+    st = capi.ReplayState()
+    capi.check(capi.lib.rela_replay_debug_state(replay.h, C.byref(st), None, None, None), "debug_state")
+    assert st.ring == ring
+    capi.check(capi.lib.rela_replay_set_decoupled_insert(replay.h, int(decoupled)), "set_decoupled_insert")
+    eng = ApexActorEngine(R, K, A, N_STEP, 0.99, replay, [0.1] * R, dev, seed=5)
+    eng.set_fused_insert(fused)
+    frames = frames_of(R, ticks)
+    rng = np.random.default_rng(77)
+    trace, censuses, firsts = [], [], []
+    inserts = 0
+    for t in range(ticks):
+        eng.next_obs_slot().copy_(torch.from_numpy(frames[t]))
+        act = eng.act(on).cpu().numpy().copy()
+        q = eng.q[0].cpu().numpy().copy()
+        rew = torch.from_numpy(rng.integers(-1, 2, R).astype(np.float32)).to(dev)
+        term = torch.from_numpy((rng.uniform(size=R) < 0.1).astype(np.uint8)).to(dev)
+        first = replay.debug_state()["tail"]
+        with capi.launch_census() as census:
+            inserted = eng.post_step(rew, term, on, tg, nonblocking=True)
+        assert inserted == (t >= N_STEP), (t, capi.lib.rela_last_error())
+        if not inserted:
+            continue
+        inserts += 1
+        torch.cuda.synchronize()
+        censuses.append(dict(census.counts))
+        firsts.append(first)
+        rows = [read_block(replay, f, first, R, ring) for f in range(10)]
+        if dedup is None:  # the frames themselves: obs of n ticks ago, next_obs of this tick
+            assert np.array_equal(rows[0], frames[t - N_STEP].reshape(R, FRAME)), (t, "obs rows")
+            assert np.array_equal(rows[1], frames[t].reshape(R, FRAME)), (t, "next_obs rows")
+        w = np.zeros(ring, np.float32)
+        capi.check(capi.lib.rela_replay_debug_weights(replay.h, w.ctypes.data_as(C.c_void_p), None), "debug_weights")
+        state = replay.debug_state()
+        trace.append(("insert", t, first, [r.tobytes() for r in rows], eng.prio.cpu().numpy().tobytes(), q.tobytes(),
+                      act.tobytes(), w.tobytes(), state["sum"], state["size"], state["head"], state["tail"]))
+        if inserts in sample_after:
+            batch, weight = replay.sample(BATCH)
+            torch.cuda.synchronize()
+            ids = np.zeros(BATCH, np.int32)
+            capi.check(capi.lib.rela_replay_debug_state(replay.h, C.byref(st), ids.ctypes.data_as(C.c_void_p), None, None),
+                       "debug_state")
+            trace.append(("sample", ids.tobytes(), batch.obs["s"].cpu().numpy().tobytes(),
+                          batch.next_obs["s"].cpu().numpy().tobytes(), batch.action["a"].cpu().numpy().tobytes(),
+                          batch.reward.cpu().numpy().tobytes(), weight.cpu().numpy().tobytes(), st.head, st.size))
+            replay.update_priority(torch.from_numpy(rng.uniform(0.05, 3.0, BATCH).astype(np.float32)))
+    torch.cuda.synchronize()
+    eng.close()
+    replay.close()
+    on.close()
+    tg.close()
+    return trace, censuses, firsts, ring
+
+
+def assert_same(a, b):
+    assert len(a) == len(b) > 0
+    for x, y in zip(a, b):
+        assert x[:3] == y[:3] or x[0] == "sample"
+        assert len(x) == len(y)
+        for i, (u, v) in enumerate(zip(x, y)):
+            assert u == v, (x[0], x[1] if x[0] == "insert" else None, "item %d differs" % i)
+
+
+@pytest.mark.parametrize("R,K,decoupled", [(512, 64, False), (513, 57, False), (512, 64, True)])
+def test_fused_insert_stores_the_same_replay(R, K, decoupled):
+    ticks = N_STEP + 7
+    kw = dict(decoupled=decoupled, sample_after=(5, 6))
+    t_on, c_on, firsts, ring = run(R, K, "f32x3", True, ticks, **kw)
+    t_off, c_off, firsts_off, _ = run(R, K, "f32x3", False, ticks, **kw)
+    assert firsts == firsts_off
+    # the sixth block starts ring - 100 slots in, wraps, and lands on slots the sample before it evicted
+    assert firsts[5] == ring - 100 and firsts[5] + R > ring, firsts
+    for c in c_on:
+        assert c.get("replay_scatter_rows") == 1 and c.get("conv12_s3_copy") == 1 and c.get("conv12_s3") == 1, c
+    for c in c_off:
+        assert c.get("replay_scatter_rows") == 2 and "conv12_s3_copy" not in c and c.get("conv12_s3") == 1, c
+    assert_same(t_on, t_off)
+
+
+@pytest.mark.parametrize("R,K,precision,dedup", [(512, 64, "f32", None), (512, 64, "bf16x2", None), (512, 64, "f32x3", "stack"),
+                                                 (128, 64, "f32x3", None)])
+def test_other_cases_take_the_unfused_path(R, K, precision, dedup):
+    ticks = N_STEP + 2
+    t_on, c_on, _, _ = run(R, K, precision, True, ticks, dedup=dedup, sample_after=(2,))
+    t_off, c_off, _, _ = run(R, K, precision, False, ticks, dedup=dedup, sample_after=(2,))
+    assert c_on == c_off
+    for c in c_on:
+        assert "conv12_s3_copy" not in c, c
+        assert c.get("replay_scatter_rows", 0) == (0 if dedup else 2), c  # (dedup: the stack fields are small reference rows)
+    assert_same(t_on, t_off)
