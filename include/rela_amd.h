@@ -395,6 +395,13 @@ int rela_ffnet_debug_workspace(const rela_ffnet* net, int n, rela_debug_workspac
 int rela_ffnet_debug_forward_store_frames(const rela_ffnet* net, int n, const uint8_t* s_dev, const float* legal_dev,
                                           float* q_dev, void* workspace_dev, int64_t workspace_bytes, void* rows_dev,
                                           int first, int ring, int* copied, void* stream);
+/* ... and, under the same launch, passes the n frames at s2_dev (any frames, not the forward's input) through to row
+ * (first2 + i) mod ring of a second ring of `ring` rows at rows2_dev, which must not overlap the first -- the obs rows
+ * of the shard's insert.  *copied: the number of fields stored, 2 where the trunk is conv12_s3, else 0.          */
+int rela_ffnet_debug_forward_store_frames2(const rela_ffnet* net, int n, const uint8_t* s_dev, const float* legal_dev,
+                                           float* q_dev, void* workspace_dev, int64_t workspace_bytes, void* rows_dev,
+                                           int first, int ring, const uint8_t* s2_dev, void* rows2_dev, int first2,
+                                           int* copied, void* stream);
 
 /* AtariFFNet.forward  net.py:42-55: q[n,A] (device f32) from s u8[n,4,84,84], legal f32[n,A] */
 int rela_ffnet_forward(const rela_ffnet* net, int n, const uint8_t* s_dev, const float* legal_dev,
@@ -554,8 +561,10 @@ int64_t rela_apex_actor_num_act(const rela_apex_actor* a); /* numAct()  dqn_acto
 int rela_apex_actor_set_reuse(rela_apex_actor* a, int on);
 /* on = 1 (default): where the target net's forward of post_step runs conv12_s3 (f32x3, 512 rows and up) and the
  * shard enters the replay as one block of plain rows, that forward stores next_obs into the block's rows itself
- * (rela_replay_direct_rows) and the insert copies one field less; 0: every field is copied by the insert.  The
- * replay's contents are the same bytes either way.                                                            */
+ * (rela_replay_direct_rows) and the insert copies one field less; 2: under the same conditions that forward also
+ * passes obs, the frames acted on n ticks ago, through to the block's obs rows (conv12_s3_copy2), and the insert
+ * copies no frame rows at all; 0: every field is copied by the insert.  The replay's contents are the same bytes in
+ * every mode.                                                                                                   */
 int rela_apex_actor_set_fused_insert(rela_apex_actor* a, int on);
 /* Invertible value rescaling of the priority's TD target (R2D2 as published, Kapturowski et al. 2019; the reference
  * leaves it out and clips rewards in its env instead, so ApexAgent.td_err apex.py:30-45 has no such step):

@@ -188,6 +188,7 @@ _sig("rela_lstmnet_precision", i32, [vp])
 _sig("rela_ffnet_workspace_bytes", i64, [vp, i32])
 _sig("rela_ffnet_debug_workspace", i32, [vp, i32, P(DebugWorkspaceView)])
 _sig("rela_ffnet_debug_forward_store_frames", i32, [vp, i32, vp, vp, vp, vp, i64, vp, i32, i32, P(i32), vp])
+_sig("rela_ffnet_debug_forward_store_frames2", i32, [vp, i32, vp, vp, vp, vp, i64, vp, i32, i32, vp, vp, i32, P(i32), vp])
 _sig("rela_lstmnet_debug_workspace", i32, [vp, i32, P(DebugWorkspaceView)])
 _sig("rela_ffnet_forward", i32, [vp, i32, vp, vp, vp, vp, i64, vp])
 _sig("rela_lstmnet_create", i32, [P(vp), i32, i32])

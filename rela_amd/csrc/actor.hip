@@ -87,8 +87,8 @@ extern "C" int rela_apex_actor_set_reuse(rela_apex_actor* a, int on) {
   return shard_set_reuse(a, on, "rela_apex_actor_set_reuse");
 }
 extern "C" int rela_apex_actor_set_fused_insert(rela_apex_actor* a, int on) {
-  RELA_CHECK(a && (on == 0 || on == 1), RELA_EINVAL, "rela_apex_actor_set_fused_insert: 0 (off) or 1 (on)");
-  a->fused_insert = on != 0;
+  RELA_CHECK(a && on >= 0 && on <= 2, RELA_EINVAL, "rela_apex_actor_set_fused_insert: 0 (off), 1 (next_obs) or 2 (next_obs and obs)");
+  a->fused_insert = on;
   return RELA_OK;
 }
 extern "C" int rela_apex_actor_set_value_rescale(rela_apex_actor* a, float eps) {
@@ -215,8 +215,11 @@ extern "C" int rela_apex_actor_post_step(rela_apex_actor* a, const float* reward
   // rows, the block is reserved here already and the forward stores the frames into its rows from the registers it stages
   // them in (conv12_s3_copy): one replay_scatter_rows launch and one read of R frames less per tick.  The rows are
   // written on `s`, behind the waits rela_replay_direct_rows puts there and ahead of the event commit_add records on `s`.
+  // fused_insert == 2: the same launch passes obs_t through to the block's obs rows as well (conv12_s3_copy2; obs_t takes
+  // no part in that forward's arithmetic): the insert then launches no replay_scatter_rows at all.  obs_t is the history
+  // slot the NEXT act() overwrites; the forward reads it on `s` ahead of everything the next tick queues there.
   // Anything else -- de-duplicated stacks, a shard in pieces, another trunk, a reservation that would block -- takes the
-  // path below unchanged.
+  // path below unchanged; a field the forward reports it did not store is copied by write_rows.
   int fused_slot = -1, fused_copied = 0;
   if (a->fused_insert && a->dd_ups == 0 && piece == a->R && ffnet_forward_stores_frames(target, a->R)) {
     rc = rela_replay_begin_add(a->replay, a->R, nonblocking, &fused_slot);
@@ -233,9 +236,22 @@ extern "C" int rela_apex_actor_post_step(rela_apex_actor* a, const float* reward
                      (long long)row_bytes, (long long)kObs);
       rc = RELA_EINVAL;
     }
+    FrameRows fr{static_cast<uint8_t*>(base), fused_slot, rows_ring};
+    if (rc == RELA_OK && a->fused_insert == 2) {
+      void* base0 = nullptr;
+      int ring0 = 0;
+      rc = rela_replay_direct_rows(a->replay, fused_slot, a->R, 0, &base0, &ring0, &row_bytes, s);
+      if (rc == RELA_OK && (row_bytes != kObs || ring0 != rows_ring)) {
+        set_last_error("rela_apex_actor_post_step: the replay's obs rows have %lld bytes in a ring of %d, a frame stack %lld in %d",
+                       (long long)row_bytes, ring0, (long long)kObs, rows_ring);
+        rc = RELA_EINVAL;
+      }
+      fr.src2 = obs_t;
+      fr.base2 = static_cast<uint8_t*>(base0);
+      fr.first2 = fused_slot;
+    }
     if (rc == RELA_OK)
-      rc = ffnet_forward_store_frames(target, a->R, obs_n, legal_n, a->q + 3 * QA, a->ws, a->ws_bytes, s,
-                                      FrameRows{static_cast<uint8_t*>(base), fused_slot, rows_ring}, &fused_copied);  // :42
+      rc = ffnet_forward_store_frames(target, a->R, obs_n, legal_n, a->q + 3 * QA, a->ws, a->ws_bytes, s, fr, &fused_copied);  // :42
   } else {
     rc = rela_ffnet_forward(target, a->R, obs_n, legal_n, a->q + 3 * QA, a->ws, a->ws_bytes, s);  // :42
   }
@@ -263,7 +279,8 @@ extern "C" int rela_apex_actor_post_step(rela_apex_actor* a, const float* reward
     for (int f = 0; f < 10; ++f) prow[f] = static_cast<const uint8_t*>(rows[f]) + (int64_t)off * rb[f];
     int slot = fused_slot;
     if (fused_slot >= 0) {  // (piece == R: this is the only block)
-      if (fused_copied) prow[1] = nullptr;
+      if (fused_copied >= 1) prow[1] = nullptr;
+      if (fused_copied >= 2) prow[0] = nullptr;
     } else {
       rc = rela_replay_begin_add(a->replay, cnt, nonblocking, &slot);
       if (rc == RELA_EWOULDBLOCK) {

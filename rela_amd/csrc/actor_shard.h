@@ -40,8 +40,9 @@ struct ActorShardBase {
   std::vector<uint64_t> qh_version;
   int q_slot = -1;     // slot of the last act()
   int reuse_mode = 1;  // 0: recompute everything, 1: reuse both act() forwards, 2: only the one of s_t+n
-  // Ape-X shard (*_set_fused_insert): the target forward stores next_obs into the reserved replay rows itself
-  bool fused_insert = true;
+  // Ape-X shard (*_set_fused_insert): the target forward stores into the reserved replay rows itself: 1 next_obs, 2 next_obs
+  // and obs, 0 neither
+  int fused_insert = 2;
   float vr_eps = 0.f;  // value rescaling of the priority's TD target (*_set_value_rescale; value_rescale.h), 0 = off
   // sliding-stack and screen input of the observation slot
   uint8_t* restart = nullptr;       // [R] *_slide_stacks / *_screens_to_stacks: 1 = the row's stack restarts with its new plane

@@ -42,6 +42,8 @@ typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));  // a
 
 constexpr bool kNoCopyOut = C12_ABLATE == 1, kNoStage = C12_ABLATE == 2, kNoEpi1 = C12_ABLATE == 3, kNoEpi2 = C12_ABLATE == 4,
                kNoConv1 = C12_ABLATE == 5, kNoConv2 = C12_ABLATE == 6;
+// (conv12_s3_copy2's pass-through, timing only: 7 loads its pieces and stores nothing, 8 stores registers it never loaded)
+constexpr bool kNoPtStore = C12_ABLATE == 7, kNoPtLoad = C12_ABLATE == 8;
 
 struct Conv12S {
   static constexpr int kT = 256;
@@ -83,12 +85,20 @@ struct Conv12S {
 // the registers it was loaded into, to the frame's row of a ring of frame rows: frame fr -> copy_dst + ((copy_first + fr)
 // wrapped once at copy_ring) * IN_ELEMS.  The units cover all 84 bytes of all 84 rows of the 4 planes (bytes 68 .. 79 of a
 // row and the clamped last unit twice, with the same values), so the row is the frame, byte for byte.
-template <bool A1OUT, bool COPY>
+// COPY == 2 (conv12_s3_copy2: the same forward, which stores the insert's obs rows too): besides, frame fr of a SECOND
+// source in2 (N frames, the stride of `in`) passes through to row (copy2_first + fr) wrapped once at copy_ring of copy2_dst.
+// Its bytes take no part in the arithmetic: the thread's eight row pieces of the frame -- the same units, so again the whole
+// frame -- are loaded behind conv1's later items and stored behind conv2's early ones, the frame the block is computing,
+// through four rotating registers (pt): every piece has some 20 items of MFMAs between its load and its store, and every
+// wait the compiler places for them is a counted vmcnt (nothing of the staging's own loads is outstanding behind them).
+template <bool A1OUT, int COPY>
 __device__ __forceinline__ void conv12_s3_body(const uint8_t* __restrict__ in, const uint4* __restrict__ W1d,
                                                const float* __restrict__ scale1, const float* __restrict__ bias1q,
                                                const uint4* __restrict__ B2, const float* __restrict__ bias2,
                                                uint8_t* __restrict__ out, float* __restrict__ a1_out, int N,
-                                               uint8_t* __restrict__ copy_dst, int copy_first, int copy_ring) {
+                                               uint8_t* __restrict__ copy_dst, int copy_first, int copy_ring,
+                                               const uint8_t* __restrict__ in2, uint8_t* __restrict__ copy2_dst,
+                                               int copy2_first) {
   using F = Conv12S;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_c12[];
   uint8_t* t1 = smem_c12;
@@ -163,6 +173,20 @@ __device__ __forceinline__ void conv12_s3_body(const uint8_t* __restrict__ in, c
   // ... and row r of unit j into it, at the place it was loaded from (uniform base + the same 32-bit offset + immediate)
   auto g_copy4 = [&](uint8_t* cb, int j, int r) __attribute__((always_inline)) {
     *reinterpret_cast<u32x4_a4*>(cb + (size_t)ugoff[j] + r * 84) = sq[j][r];
+  };
+  // COPY == 2: piece P of the pass-through frame = row P & 3 of unit P >> 2, through register P & 3 (cb2: frame n's row)
+  u32x4_a4 pt[4] = {};
+  uint8_t* cb2 = nullptr;
+  auto pt_load = [&](auto p_tag) __attribute__((always_inline)) {
+    constexpr int P = decltype(p_tag)::value;
+    const uint8_t* fb = in2 + (size_t)n * F::IN_ELEMS;
+    if constexpr (!kNoPtLoad) pt[P & 3] = *reinterpret_cast<const u32x4_a4*>(fb + (size_t)ugoff[P >> 2] + (P & 3) * 84);
+  };
+  auto pt_store = [&](auto p_tag) __attribute__((always_inline)) {
+    constexpr int P = decltype(p_tag)::value;
+    const u32x4_a4 v = pt[P & 3];
+    if constexpr (!kNoPtStore) *reinterpret_cast<u32x4_a4*>(cb2 + (size_t)ugoff[P >> 2] + (P & 3) * 84) = v;
+    else asm volatile("" ::"v"(v));
   };
   auto s_store4 = [&](int j, int k) __attribute__((always_inline)) {  // cell X0 + k of unit j; x -> x - 128: flip the sign bits
     *reinterpret_cast<uint4*>(t1 + uloff[j] + k * 16) = make_uint4(sq[j][0][k] ^ 0x80808080u, sq[j][1][k] ^ 0x80808080u,
@@ -291,7 +315,7 @@ __device__ __forceinline__ void conv12_s3_body(const uint8_t* __restrict__ in, c
   for (int j = 0; j < F::UIT; ++j)
 #pragma unroll
     for (int k = 0; k < 4; ++k) s_store4(j, k);
-  if constexpr (COPY) {
+  if constexpr (COPY != 0) {
     uint8_t* cb = copy_row(n);
 #pragma unroll
     for (int j = 0; j < F::UIT; ++j)
@@ -310,7 +334,14 @@ __device__ __forceinline__ void conv12_s3_body(const uint8_t* __restrict__ in, c
       else o_write(IC<IDX / 2>{});
     }
   };
-  auto no_hook = [](auto) {};
+  // (conv1's second and third pass: nothing, but for) COPY == 2: the pass-through frame's pieces 0 .. 3 are loaded behind conv1's items 20, 28, 36 and 44 (second and third
+  // pass; the first holds the copy-out), stored behind conv2's items 4, 8, 12 and 16; pieces 4 .. 7 are loaded behind
+  // conv2's items 6, 10, 15 and 18 and stored behind 27, 31, 35 and 39, ahead of the staging's own stores (40 ..)
+  auto pass_hook = [&](auto idx_tag) {
+    constexpr int IDX = decltype(idx_tag)::value;
+    if constexpr (COPY == 2 && IDX >= 20 && (IDX - 20) % 8 == 0 && !kNoStage) pt_load(IC<(IDX - 20) / 8>{});
+  };
+  constexpr int kPtStore[8] = {4, 8, 12, 16, 27, 31, 35, 39}, kPtLoad[8] = {-1, -1, -1, -1, 6, 10, 15, 18};
   static_assert(2 * F::OIT <= 20, "copy-out slots inside conv1's first pass");
 
   uint32_t xbh[F::C2TILES];  // conv2's per-tile offsets into the a1 image (frame-invariant)
@@ -386,11 +417,16 @@ __device__ __forceinline__ void conv12_s3_body(const uint8_t* __restrict__ in, c
     const int nn = (n + nblk < N) ? n + nblk : n;  // (the last round re-stages its own frame)
     // (COPY: ... and stores it again, the same bytes to the same row; no branch inside conv2's instruction stream)
     uint8_t* cbn = nullptr;
-    if constexpr (COPY) cbn = copy_row(nn);
+    if constexpr (COPY != 0) cbn = copy_row(nn);
+    if constexpr (COPY == 2) {
+      int sl = copy2_first + n;
+      if (sl >= copy_ring) sl -= copy_ring;
+      cb2 = copy2_dst + (size_t)sl * F::IN_ELEMS;
+    }
     pin_weights();
     conv1_pass(IC<0>{}, IC<5>{}, copy_hook);
-    conv1_pass(IC<5>{}, IC<4>{}, no_hook);
-    conv1_pass(IC<9>{}, IC<4>{}, no_hook);
+    conv1_pass(IC<5>{}, IC<4>{}, pass_hook);
+    conv1_pass(IC<9>{}, IC<4>{}, pass_hook);
     if constexpr (kNoEpi1) asm volatile("" ::"v"(sc1), "v"(bv1));
     __syncthreads();  // T2 complete, T1 and O free
     // ---- conv2 from T2, tile by tile; the next frame's cells go into T1 in the second half
@@ -432,7 +468,9 @@ __device__ __forceinline__ void conv12_s3_body(const uint8_t* __restrict__ in, c
           constexpr int JJ = decltype(jj)::value;
           if constexpr (JJ < F::UIT && IDX == 1 + 12 * JJ && !kNoStage) g_load4(nn, JJ);
           if constexpr (IDX == TOT / 2 + 4 * JJ && !kNoStage) s_store4(JJ >> 2, JJ & 3);
-          if constexpr (COPY && IDX == TOT / 2 + 4 * JJ && !kNoStage) g_copy4(cbn, JJ >> 2, JJ & 3);
+          if constexpr (COPY != 0 && IDX == TOT / 2 + 4 * JJ && !kNoStage) g_copy4(cbn, JJ >> 2, JJ & 3);
+          if constexpr (COPY == 2 && IDX == kPtStore[JJ] && !kNoStage) pt_store(IC<JJ>{});
+          if constexpr (COPY == 2 && IDX == kPtLoad[JJ] && !kNoStage) pt_load(IC<JJ>{});
         });
         if constexpr (KS == F::KS2 - 1 && kNoEpi2) asm volatile("" ::"v"(acc), "v"(accs));
         if constexpr (KS == F::KS2 - 1 && !kNoEpi2) {  // tile T complete: ReLU, split, its record slice into O
@@ -473,7 +511,7 @@ __global__ __launch_bounds__(256, 1) void conv12_s3(const uint8_t* __restrict__ 
                                                     const float* __restrict__ scale1, const float* __restrict__ bias1q,
                                                     const uint4* __restrict__ B2, const float* __restrict__ bias2,
                                                     uint8_t* __restrict__ out, float* __restrict__ a1_out, int N) {
-  conv12_s3_body<A1OUT, false>(in, W1d, scale1, bias1q, B2, bias2, out, a1_out, N, nullptr, 0, 0);
+  conv12_s3_body<A1OUT, 0>(in, W1d, scale1, bias1q, B2, bias2, out, a1_out, N, nullptr, 0, 0, nullptr, nullptr, 0);
 }
 // conv12_s3<false> that also stores frame fr to row (copy_first + fr) mod copy_ring of copy_dst (N <= copy_ring)
 __global__ __launch_bounds__(256, 1) void conv12_s3_copy(const uint8_t* __restrict__ in, const uint4* __restrict__ W1d,
@@ -481,7 +519,20 @@ __global__ __launch_bounds__(256, 1) void conv12_s3_copy(const uint8_t* __restri
                                                          const uint4* __restrict__ B2, const float* __restrict__ bias2,
                                                          uint8_t* __restrict__ out, int N, uint8_t* __restrict__ copy_dst,
                                                          int copy_first, int copy_ring) {
-  conv12_s3_body<false, true>(in, W1d, scale1, bias1q, B2, bias2, out, nullptr, N, copy_dst, copy_first, copy_ring);
+  conv12_s3_body<false, 1>(in, W1d, scale1, bias1q, B2, bias2, out, nullptr, N, copy_dst, copy_first, copy_ring, nullptr, nullptr,
+                           0);
+}
+// ... and frame fr of in2 to row (copy2_first + fr) mod copy_ring of copy2_dst (the two destinations do not overlap).
+// Label and census name: conv12_s3_copy2.  The symbol is spelled conv12_s3_copies2 so that "conv12_s3_copy" keeps naming
+// exactly one kernel of this file (tests/test_conv12_copy_resources_cpu.py and tools/trace_insert_tail.py find it so).
+__global__ __launch_bounds__(256, 1) void conv12_s3_copies2(const uint8_t* __restrict__ in, const uint4* __restrict__ W1d,
+                                                            const float* __restrict__ scale1, const float* __restrict__ bias1q,
+                                                            const uint4* __restrict__ B2, const float* __restrict__ bias2,
+                                                            uint8_t* __restrict__ out, int N, uint8_t* __restrict__ copy_dst,
+                                                            int copy_first, int copy_ring, const uint8_t* __restrict__ in2,
+                                                            uint8_t* __restrict__ copy2_dst, int copy2_first) {
+  conv12_s3_body<false, 2>(in, W1d, scale1, bias1q, B2, bias2, out, nullptr, N, copy_dst, copy_first, copy_ring, in2, copy2_dst,
+                           copy2_first);
 }
 
 // frames u8 [N][4][84][84] -> a2 as split3 records at rec2; a1 != NULL: a1 as channel-last f32 too (A1OUT)
@@ -497,10 +548,17 @@ inline void launch_conv12_copy(const uint8_t* frames, const uint4* W1d, const fl
   hipLaunchKernelGGL(conv12_s3_copy, dim3(blocks), dim3(Conv12S::kT), Conv12S::LDS_TOTAL, s, frames, W1d, s1q, b1q, B2e, b2, rec2,
                      N, copy_dst, copy_first, copy_ring);
 }
-// the three kernels' opt-in to their dynamic LDS (once per process, before the first launch)
+// ... and the N frames at frames2 to their rows of the ring at copy2_dst (0 <= copy2_first < copy_ring, the same length)
+inline void launch_conv12_copy2(const uint8_t* frames, const uint4* W1d, const float* s1q, const float* b1q, const uint4* B2e,
+                                const float* b2, uint8_t* rec2, int N, hipStream_t s, int blocks, uint8_t* copy_dst,
+                                int copy_first, int copy_ring, const uint8_t* frames2, uint8_t* copy2_dst, int copy2_first) {
+  hipLaunchKernelGGL(conv12_s3_copies2, dim3(blocks), dim3(Conv12S::kT), Conv12S::LDS_TOTAL, s, frames, W1d, s1q, b1q, B2e, b2, rec2,
+                     N, copy_dst, copy_first, copy_ring, frames2, copy2_dst, copy2_first);
+}
+// the four kernels' opt-in to their dynamic LDS (once per process, before the first launch)
 inline int opt_in_lds_conv12() {
   for (const void* k : {reinterpret_cast<const void*>(&conv12_s3<false>), reinterpret_cast<const void*>(&conv12_s3<true>),
-                        reinterpret_cast<const void*>(&conv12_s3_copy)})
+                        reinterpret_cast<const void*>(&conv12_s3_copy), reinterpret_cast<const void*>(&conv12_s3_copies2)})
     RELA_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, Conv12S::LDS_TOTAL));
   return RELA_OK;
 }

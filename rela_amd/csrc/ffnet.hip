@@ -101,7 +101,8 @@ struct TrunkLabels {  // per-kernel timing labels (prof.h); conv12: the launch t
 struct TrunkOpts {
   bool keep_f32 = false;          // kTrunkS3: a1 is ALSO written as channel-last f32 (a2 / a3: unsplit_s3_a23, the caller's)
   bool leave_a3_records = false;  // kTrunkBf16: a3 stays in split records instead of going back to f32 in place
-  const FrameRows* store_frames = nullptr;  // kTrunkS3 without keep_f32: the frames also go to these rows (conv12_s3_copy)
+  // kTrunkS3 without keep_f32: the frames also go to these rows (conv12_s3_copy; with a second pair, conv12_s3_copy2)
+  const FrameRows* store_frames = nullptr;
 };
 // kTrunkF32:  a1 / a2 / a3 channel-last f32
 // kTrunkBf16: a1 is NOT produced; a2 / a3 hold split-bf16 records in the f32 tensors' places (same bytes)
@@ -114,7 +115,12 @@ void launch_trunk(const FFNetDev& d, TrunkKind kind, int N, const uint8_t* s_dev
       {
         ProfScope prof(l.conv12, s);
         note_launch("conv12_s3");
-        if (o.store_frames) {
+        if (o.store_frames && o.store_frames->src2) {
+          note_launch("conv12_s3_copy2");  // (counted under both names: it is a conv12_s3 launch that also copies two fields)
+          s3::launch_conv12_copy2(s_dev, d.W1d, d.s1q, d.b1q, d.B2e, d.b2, rec2, N, s, persistent_blocks(N), o.store_frames->base,
+                                  o.store_frames->first, o.store_frames->ring, o.store_frames->src2, o.store_frames->base2,
+                                  o.store_frames->first2);
+        } else if (o.store_frames) {
           note_launch("conv12_s3_copy");  // (counted under both names: it is a conv12_s3 launch that also copies)
           s3::launch_conv12_copy(s_dev, d.W1d, d.s1q, d.b1q, d.B2e, d.b2, rec2, N, s, persistent_blocks(N), o.store_frames->base,
                                  o.store_frames->first, o.store_frames->ring);
@@ -530,6 +536,13 @@ int rela_amd::ffnet_forward_store_frames(const rela_ffnet* n, int N, const uint8
                                          void* ws, int64_t ws_bytes, void* stream_, const FrameRows& rows, int* copied) {
   RELA_CHECK(copied && rows.base && ((uintptr_t)rows.base & 3) == 0 && rows.first >= 0 && rows.first < rows.ring && N <= rows.ring,
              RELA_EINVAL, "ffnet_forward_store_frames: bad frame rows (first %d, ring %d, %d frames)", rows.first, rows.ring, N);
+  if (rows.src2) {  // the second ring lies wholly before or behind the first
+    const uint8_t *b1 = rows.base, *b2 = rows.base2;
+    const int64_t len = (int64_t)rows.ring * kFrameBytes;
+    RELA_CHECK(b2 && (((uintptr_t)b2 | (uintptr_t)rows.src2) & 3) == 0 && rows.first2 >= 0 && rows.first2 < rows.ring &&
+                   (b2 + len <= b1 || b1 + len <= b2),
+               RELA_EINVAL, "ffnet_forward_store_frames: bad second frame rows (first %d, ring %d)", rows.first2, rows.ring);
+  }
   return forward_impl(n, N, s_dev, legal_dev, q_dev, ws, ws_bytes, stream_, kModeNet, -1, &rows, copied);
 }
 
@@ -540,8 +553,19 @@ extern "C" int rela_ffnet_debug_forward_store_frames(const rela_ffnet* n, int N,
   return rela_amd::ffnet_forward_store_frames(n, N, s_dev, legal_dev, q_dev, ws, ws_bytes, stream_,
                                               FrameRows{static_cast<uint8_t*>(rows_dev), first, ring}, copied);
 }
+// ... with the second pair: the n frames at s2_dev to row (first2 + i) mod ring of rows2_dev
+extern "C" int rela_ffnet_debug_forward_store_frames2(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev,
+                                                      float* q_dev, void* ws, int64_t ws_bytes, void* rows_dev, int first,
+                                                      int ring, const uint8_t* s2_dev, void* rows2_dev, int first2, int* copied,
+                                                      void* stream_) {
+  RELA_CHECK(s2_dev && rows2_dev, RELA_EINVAL, "rela_ffnet_debug_forward_store_frames2: no second source or destination");
+  return rela_amd::ffnet_forward_store_frames(
+      n, N, s_dev, legal_dev, q_dev, ws, ws_bytes, stream_,
+      FrameRows{static_cast<uint8_t*>(rows_dev), first, ring, s2_dev, static_cast<uint8_t*>(rows2_dev), first2}, copied);
+}
 
-// store != NULL: a kTrunkS3 plan also stores the frames into *store and sets *copied, any other plan clears it
+// store != NULL: a kTrunkS3 plan also stores the frames into *store and sets *copied to the number of fields (1, or 2 with
+// the second pair), any other plan clears it
 static int forward_impl(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev, float* q_dev, void* ws,
                         int64_t ws_bytes, void* stream_, int mode, int rows_limit, const FrameRows* store, int* copied) {
   if (copied) *copied = 0;
@@ -578,7 +602,7 @@ static int forward_impl(const rela_ffnet* n, int N, const uint8_t* s_dev, const 
   opts.leave_a3_records = !plan.unsplit_a3;
   if (store && plan.trunk == kTrunkS3 && !plan.keep_f32) {
     opts.store_frames = store;
-    *copied = 1;
+    *copied = store->src2 ? 2 : 1;
   }
   launch_trunk(d, plan.trunk, N, s_dev, w.a1, w.a2, w.a3, rec2, rec3, opts, {names[0], names[1], names[2], name12}, s);
 

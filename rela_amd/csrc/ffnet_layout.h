@@ -75,14 +75,21 @@ int ffnet_forward_mode(const rela_ffnet* n, int N, const uint8_t* s_dev, const f
                        int64_t ws_bytes, void* stream, int mode, int rows_limit = -1);
 // A ring of `ring` frame rows (kFrameBytes each, 4-byte aligned) at `base`: row (first + i) mod ring takes frame i.
 constexpr int64_t kFrameBytes = 4 * 84 * 84;
+// Optionally a second pair: the N frames at src2 (not the forward's input; kFrameBytes apart, 4-byte aligned) go to row
+// (first2 + i) mod ring of a second ring of the same length at base2, which does not overlap the first.
 struct FrameRows {
   uint8_t* base;
   int first, ring;
+  const uint8_t* src2 = nullptr;
+  uint8_t* base2 = nullptr;
+  int first2 = 0;
 };
 // rela_ffnet_forward (the net's own precision) that ALSO stores its N input frames into `rows` (N <= rows.ring), from the
 // registers conv12_s3_copy stages them in -- the Ape-X shard's target forward, which so writes next_obs into the replay
-// (actor.hip).  Only a kTrunkS3 plan can: *copied says whether the frames were stored; 0 = an ordinary forward ran and
-// the caller copies them itself.  ffnet_forward_stores_frames: what *copied will be, for a caller that must know before.
+// (actor.hip) -- and, where rows.src2 is set, passes those frames through to the second ring (conv12_s3_copy2: the obs
+// rows of the same insert).  Only a kTrunkS3 plan can: *copied says how many of the fields were stored, 0, 1 or 2 (the
+// first, or both); 0 = an ordinary forward ran, and the caller copies what was not stored itself.
+// ffnet_forward_stores_frames: whether *copied will be above 0, for a caller that must know before.
 bool ffnet_forward_stores_frames(const rela_ffnet* n, int N);
 int ffnet_forward_store_frames(const rela_ffnet* n, int N, const uint8_t* s_dev, const float* legal_dev, float* q_dev, void* ws,
                                int64_t ws_bytes, void* stream, const FrameRows& rows, int* copied);

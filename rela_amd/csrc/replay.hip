@@ -1121,6 +1121,12 @@ extern "C" int rela_replay_write_rows_gather(rela_replay* r, int first_slot, int
 // ev_in (in-order form) or ev_cin (decoupled form) on the producer's stream BEHIND the kernel that wrote them, and the
 // replay / copy stream waits for that event before the append, so every reader of the published block (sample's gathers
 // run on the replay stream behind the append) sees the rows, exactly as it sees the rows write_rows copied.
+// The shard calls this once per field it stores: next_obs (field 1), and obs (field 0) where the same forward passes obs_t
+// through (conv12_s3_copy2); the eviction waits of the second call are the first call's again, which costs nothing.
+// Ordering of the SOURCE of field 0: obs_t lives in the history slot the next act() overwrites.  The forward reads it on
+// the producer's stream, ahead of everything the next tick queues on that stream (the slot's refill and act() included),
+// so no event is needed for it -- where write_rows copied it on the copy stream, copy_end's ev_cout gave that order.  The
+// stores of both fields are ahead of the event commit_add records on the producer's stream.
 extern "C" int rela_replay_direct_rows(rela_replay* r, int first_slot, int count, int field, void** base_dev, int* ring,
                                        int64_t* row_bytes, void* stream_) {
   RELA_CHECK(r && count > 0 && first_slot >= 0 && first_slot < r->ring && count <= r->ring && base_dev && ring, RELA_EINVAL,

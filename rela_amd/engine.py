@@ -148,9 +148,10 @@ class ApexActorEngine:
         capi.check(capi.lib.rela_apex_actor_set_reuse(self.h, int(on)), "rela_apex_actor_set_reuse")
 
     def set_fused_insert(self, on):
-        """True (default): the target forward of post_step stores next_obs into the replay's rows itself where it can
-        (f32x3, 512 rows and up, the shard as one block); False: the insert copies every field."""
-        capi.check(capi.lib.rela_apex_actor_set_fused_insert(self.h, int(bool(on))), "rela_apex_actor_set_fused_insert")
+        """1 / True: the target forward of post_step stores next_obs into the replay's rows itself where it can (f32x3,
+        512 rows and up, the shard as one block); 2 (default): obs as well, so the insert copies no frame rows;
+        0 / False: the insert copies every field."""
+        capi.check(capi.lib.rela_apex_actor_set_fused_insert(self.h, int(on)), "rela_apex_actor_set_fused_insert")
 
     def next_obs_slot(self):
         """The HBM slot the env layer writes the next observation batch into ([R,4,84,84] u8)."""

@@ -73,7 +73,7 @@ print("kernels overlapping the copies, us per tick:")
 for k, v in sorted(overlappers.items(), key=lambda kv: -kv[1])[:8]:
     print("  %-50s %s" % (k, us(v / len(per_tick))))
 lo, hi = rows[tds[0]][0], rows[tds[-1]][1]
-for key in ("conv12_s3<false>", "conv12_s3_copy"):
+for key in ("conv12_s3<false>", "conv12_s3_copy", "conv12_s3_copies2"):  # (the last: the kernel labelled conv12_s3_copy2)
     d = [r[1] - r[0] for r in rows if key in r[2] and lo <= r[0] <= hi]
     d = [x for x in d if x > 0.5 * max(d)] if d else d  # (the tick's grid, not the learner's smaller batches)
     if d:
