@@ -1044,6 +1044,13 @@ int rela_runtime_set_replay_chunk_bytes(int64_t bytes);
 int rela_replay_export_chunks(rela_replay* r, rela_replay_chunk_desc* out, int* fds_out, int max_fds);
 int rela_replay_import_chunks(rela_replay_remote** out, const rela_replay_chunk_desc* desc, const int* fds, int nfds,
                               int device);
+/* Do chunks travel between two processes here?  Where hipMemImportFromShareableHandle refuses another process's
+ * descriptors (it can, with everything else about chunks working), partitions have to stay in plain mode, whose fields
+ * travel as IPC handles.  Only two processes can tell: one calls _export and sends the descriptor like a chunk's (and
+ * closes it), the other one calls _import on what it received -> *ok_out = 1 / 0.  rela_amd/parallel.py:
+ * chunks_cross_processes asks every owner / learner pair of a group before the partitions are created. */
+int rela_ipc_chunk_probe_export(int device, int* fd_out);
+int rela_ipc_chunk_probe_import(int device, int fd, int* ok_out);
 /* the same mapping for a device buffer this library allocated (e.g. rela_apex_learner_flat's parameter buffer): the
  * weight publish across processes -- actors load their nets straight from the learner's mapped buffer */
 int rela_ipc_export_buffer(const void* dev_ptr, unsigned char handle_out[64]);
@@ -1082,10 +1089,12 @@ int rela_ipc_allreduce_run(rela_ipc_allreduce* ar, void* stream);
 int rela_ipc_allreduce_mode(const rela_ipc_allreduce* ar); /* 1 = stream value operations, 0 = host synchronisation */
 void rela_ipc_allreduce_destroy(rela_ipc_allreduce* ar);
 /* A page of 32-bit words shared by the processes of one host and by their GPUs' command processors (r5; csrc/ipc_page.hip):
- * the control plane of the native partition exchange.  POSIX shared memory, registered with HIP in every process, so a
- * word can be written by a stream (after everything queued before it), waited for by a stream (>=: the command
- * processor waits, no CU spins, the host goes on), read by a kernel (rela_ipc_page_dev_ptr) and read / written / waited
- * for by host threads.  Step counters only grow, so a wait binds to a value: nothing to re-arm, nothing to acknowledge.
+ * the control plane of the native partition exchange.  Pinned host memory of the creator (hipHostMalloc), mapped by every
+ * other process through its IPC handle, so a word can be written by a stream (after everything queued before it), waited
+ * for by a stream (>=: the command processor waits, no CU spins, the host goes on), read by a kernel
+ * (rela_ipc_page_dev_ptr) and read / written / waited for by host threads: in place in the creator
+ * (rela_ipc_page_host_ptr; NULL elsewhere), through a private stream in a process that opened the page.
+ * Step counters only grow, so a wait binds to a value: nothing to re-arm, nothing to acknowledge.
  * rela_amd/parallel.py keeps, per partition g: sampled[g] (the owner's stream, after its gather-less sample), size[g]
  * (the partition's item count of that sample), consumed[g] (the learner's stream, after its gather and its priorities) --
  * the per-step gather of importance weights and scatter of priorities through torch.distributed are gone.       */

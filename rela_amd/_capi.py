@@ -128,6 +128,8 @@ _sig("rela_replay_set_chunk_bytes", i32, [vp, i64])
 _sig("rela_runtime_set_replay_chunk_bytes", i32, [i64])
 _sig("rela_replay_export_chunks", i32, [vp, vp, P(i32), i32])
 _sig("rela_replay_import_chunks", i32, [P(vp), vp, P(i32), i32, i32])
+_sig("rela_ipc_chunk_probe_export", i32, [i32, P(i32)])
+_sig("rela_ipc_chunk_probe_import", i32, [i32, i32, P(i32)])
 _sig("rela_replay_remote_close", None, [vp])
 _sig("rela_replay_remote_gather", i32, [vp, i32, vp, vp, vp, i32, i32, vp])
 _sig("rela_ipc_export_buffer", i32, [vp, vp])

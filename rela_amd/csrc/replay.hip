@@ -1633,7 +1633,8 @@ static int export_partition(rela_replay* r, rela_replay_ipc_desc* out, rela_repl
     if (!d.chunked && hipMemGetAddressRange(&base, &bytes, d.base) == hipSuccess && bytes > ((size_t)24 << 30)) {
       set_last_error("%s: field %d is one allocation of %.1f GB; HIP IPC imports above ~24 GB do not return on this "
                      "platform -- create the partition with rela_replay_set_chunk_bytes (or RELA_REPLAY_CHUNK_GB) and "
-                     "export it with rela_replay_export_chunks", who, f, (double)bytes / 1e9);
+                     "export it with rela_replay_export_chunks (where chunks do not travel between processes, "
+                     "rela_ipc_chunk_probe_*, only smaller partitions do)", who, f, (double)bytes / 1e9);
       return fail(RELA_EINVAL);
     }
     char what[32];
@@ -1823,5 +1824,33 @@ extern "C" int rela_ipc_close_buffer(void* dev_ptr, int device) {
   if (!dev_ptr) return RELA_OK;
   DeviceGuard g(device);
   RELA_HIP(hipIpcCloseMemHandle(dev_ptr));
+  return RELA_OK;
+}
+
+// Do chunks travel between two processes of this host?  Not on every platform: hipMemImportFromShareableHandle of a
+// descriptor ANOTHER process exported can fail with hipErrorInvalidValue where everything else about chunks works,
+// the import of a descriptor of the process's own included, so only two processes can tell.  One exports a chunk of its
+// own (the descriptor keeps the 2 MB alive until it is closed), the other one imports it and lets go of it again.
+extern "C" int rela_ipc_chunk_probe_export(int device, int* fd_out) {
+  RELA_CHECK(fd_out, RELA_EINVAL, "rela_ipc_chunk_probe_export: bad arguments");
+  DeviceGuard g(device);
+  RELA_CHECK(g.ok, RELA_ENODEV, "rela_ipc_chunk_probe_export: HIP device %d not available; there is no CPU path", device);
+  hipMemAllocationProp p = VmmRange::prop_for(device);
+  hipMemGenericAllocationHandle_t h{};
+  RELA_HIP(hipMemCreate(&h, (size_t)2 << 20, &p, 0));
+  const hipError_t e = hipMemExportToShareableHandle(fd_out, h, hipMemHandleTypePosixFileDescriptor, 0);
+  (void)hipMemRelease(h);
+  RELA_CHECK(e == hipSuccess, RELA_ENODEV, "rela_ipc_chunk_probe_export: hipMemExportToShareableHandle: %s", hipGetErrorString(e));
+  return RELA_OK;
+}
+extern "C" int rela_ipc_chunk_probe_import(int device, int fd, int* ok_out) {
+  RELA_CHECK(fd >= 0 && ok_out, RELA_EINVAL, "rela_ipc_chunk_probe_import: bad arguments");
+  DeviceGuard g(device);
+  RELA_CHECK(g.ok, RELA_ENODEV, "rela_ipc_chunk_probe_import: HIP device %d not available; there is no CPU path", device);
+  hipMemGenericAllocationHandle_t h{};
+  const hipError_t e = VmmRange::import_fd(&h, fd);
+  if (e == hipSuccess) (void)hipMemRelease(h);
+  (void)hipGetLastError();
+  *ok_out = e == hipSuccess ? 1 : 0;
   return RELA_OK;
 }

@@ -429,6 +429,52 @@ def _import_partition(capi, C, entry, dev_index):
     return rr
 
 
+def chunks_cross_processes(device, learner_rank=0, group=None):
+    """Collective over `group`, BEFORE the owners create their partitions: can the learner rank import a chunk of every
+    other rank (include/rela_amd.h: rela_ipc_chunk_probe_*)?  Where hipMemImportFromShareableHandle refuses another
+    process's descriptors, a chunked partition cannot leave its process; the owners then keep their partitions in plain
+    mode (no rela_replay_set_chunk_bytes), whose fields travel as IPC handles.  -> the same bool on every rank."""
+    import ctypes as C
+
+    from . import _capi as capi
+
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    dev_index = torch.device(device).index or 0
+    # `error`: a call of the probe that failed outright (not the refused import it asks about).  It travels through the
+    # second collective and is raised on EVERY rank after it, so no rank waits for one that has left.
+    ok, error, server = True, None, None
+    if rank != learner_rank:
+        fd = C.c_int(-1)
+        if capi.lib.rela_ipc_chunk_probe_export(dev_index, C.byref(fd)) == capi.OK:
+            server = _FdServer([fd.value])
+        else:
+            ok, error = False, "rank %d: rela_ipc_chunk_probe_export: %s" % (rank, capi.lib.rela_last_error().decode())
+    names = [None] * world
+    dist.all_gather_object(names, server.name if server else None, group=group)
+    if rank == learner_rank:
+        for r, name in enumerate(names):
+            if r == rank or not name:
+                continue
+            got, fds = C.c_int(0), []
+            try:
+                fds = _fetch_fds(name)
+                capi.check(capi.lib.rela_ipc_chunk_probe_import(dev_index, fds[0], C.byref(got)), "rela_ipc_chunk_probe_import")
+            except (OSError, AssertionError, capi.RelaError) as e:
+                error = error or "rank %d: importing the chunk of rank %d: %s" % (rank, r, e)
+            finally:
+                for fd in fds:
+                    os.close(fd)
+            ok = ok and bool(got.value)
+    votes = [None] * world
+    dist.all_gather_object(votes, (ok, error), group=group)
+    if server is not None:
+        server.join(10.0)
+    errors = [e for _, e in votes if e]
+    if errors:
+        raise RuntimeError("chunks_cross_processes: the probe itself failed: " + "; ".join(errors))
+    return all(v for v, _ in votes)
+
+
 # word indices in the shared control page (include/rela_amd.h: rela_ipc_page_*), one 64-byte line per partition and use
 _W_SAMPLED, _W_CONSUMED, _W_SIZE, _W_TEST = 0, 256, 512, 768
 

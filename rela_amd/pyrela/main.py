@@ -341,8 +341,8 @@ def _multi_worker(rank, world, args, port, results):
 
     from rela_amd.learner import HipApexLearner, HipR2D2Learner, ffnet_flat_layout, lstmnet_flat_layout
     from rela_amd.parallel import (NativePartitionedReplay, NativePartitionServer, PartitionedReplay, PartitionServer,
-                                   _ModuleNativePartition, ff_batch_namespace, ff_field_specs, rnn_batch_namespace,
-                                   rnn_field_specs)
+                                   _ModuleNativePartition, chunks_cross_processes, ff_batch_namespace, ff_field_specs,
+                                   rnn_batch_namespace, rnn_field_specs)
 
     native = getattr(args, "exchange", "native") == "native"
 
@@ -373,6 +373,20 @@ def _multi_worker(rank, world, args, port, results):
         layout, total = ffnet_flat_layout(num_action)
         to_namespace, learner_cls = ff_batch_namespace, HipApexLearner
     assert args.batchsize % G == 0 and args.num_thread % G == 0
+    # chunked partitions travel at any size, but not on every platform: asked once, before the partitions exist
+    chunked = native and chunks_cross_processes(my_device)
+    if native and not chunked:
+        # plain mode: one IPC handle per field, which the library exports up to ~24 GB (rela_replay_export_chunks).  The
+        # ring of a partition is 1.25 x its capacity; every rank computes the same figure and stops before anything runs.
+        row = max(int(torch.Size(sp.shape).numel()) * torch.empty((), dtype=sp.dtype).element_size() for sp in specs)
+        largest = row * (args.replay_buffer_size // G + args.replay_buffer_size // G // 4)
+        if largest > (24 << 30):
+            raise SystemExit("chunks of device memory do not travel between processes here, and a partition of %d slots "
+                             "has a field of %.1f GB, more than one IPC handle carries (~24 GB): use more act devices, a "
+                             "smaller --replay_buffer_size or --exchange packed" % (args.replay_buffer_size // G, largest / 1e9))
+        if rank == 0:
+            print("chunks of device memory do not travel between processes here: the partitions stay in plain mode "
+                  "(one IPC handle per field; the largest field is %.2f GB)" % (largest / 1e9), file=sys.stderr, flush=True)
     if rank == 0:
         rules = UpdateRules(args)
         learner = learner_cls.from_agent(agent, args.batchsize, lr=args.lr, eps=args.eps, grad_clip=args.grad_clip,
@@ -423,7 +437,7 @@ def _multi_worker(rank, world, args, port, results):
     else:
         g = rank - 1
         locker = rela.ModelLocker([agent, agent, agent], my_device)
-        if native:  # the learner maps this partition: fields as 8 GB chunks, which travel at any size (include/rela_amd.h)
+        if chunked:  # the learner maps this partition: fields as 8 GB chunks, which travel at any size (include/rela_amd.h)
             rela.set_replay_chunk_bytes(8 << 30)
         part = (rela.RNNPrioritizedReplay if r2d2 else rela.FFPrioritizedReplay)(
             args.replay_buffer_size // G, args.seed + g, args.priority_exponent, args.importance_exponent, args.prefetch)

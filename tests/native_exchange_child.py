@@ -11,7 +11,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from rela_amd.parallel import (NativePartitionedReplay, NativePartitionServer, ff_field_specs)
+from rela_amd.parallel import (NativePartitionedReplay, NativePartitionServer, chunks_cross_processes, ff_field_specs)
 from rela_amd.replay import FFReplay
 
 A, BATCH, BETA, ROUNDS = 18, 64, 0.4, 4
@@ -21,6 +21,8 @@ dist.init_process_group("gloo", rank=rank, world_size=world)
 dev = "cuda:0"
 torch.cuda.set_device(0)
 specs = ff_field_specs(A)
+# (where another process's chunks cannot be imported, both partitions travel as IPC handles, as in pyrela/main.py)
+chunked = chunks_cross_processes(dev)
 
 if rank == 0:
     from rela_amd.learner import HipApexLearner
@@ -60,7 +62,7 @@ if rank == 0:
     rep.close()
     print("LEARNER OK", flush=True)
 else:
-    if rank == 2:  # one partition with its frame-stack fields in 8 MB chunks (9 descriptors each), one with plain IPC handles
+    if rank == 2 and chunked:  # one partition with its frame-stack fields in 8 MB chunks (9 descriptors each), one with plain IPC handles
         from rela_amd import _capi as capi
 
         capi.check(capi.lib.rela_runtime_set_replay_chunk_bytes(8 << 20), "chunk bytes")

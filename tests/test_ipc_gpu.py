@@ -4,6 +4,7 @@ gathered by a kernel of THIS process straight out of the owner's memory -- on a 
 xGMI; with both processes on the one GPU of the test box the address arithmetic, the descriptor and the protocol are
 the same.  Two processes on cuda:0."""
 import ctypes as C
+import functools
 import json
 import os
 import subprocess
@@ -15,6 +16,34 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+@functools.lru_cache(maxsize=1)
+def _chunks_cross_processes():
+    """Does hipMemImportFromShareableHandle take a descriptor that ANOTHER process exported?  Not on every platform (it
+    answers hipErrorInvalidValue where creating, mapping, exporting and even importing one's own chunks work), and then no
+    chunked partition can leave its process.  Asked with raw HIP calls, nothing of the library: tools/vmm_probe.py on one
+    2 MB chunk, two fresh processes, under the runtime that torch loads and with the descriptor form that runtime takes."""
+    import torch
+
+    lib = os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so")
+    lib = lib if os.path.exists(lib) else "libamdhip64.so"
+    version = C.c_int()
+    assert C.CDLL(lib).hipRuntimeGetVersion(C.byref(version)) == 0
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", CHUNKS="1", CHUNK_GB=repr(2.0 / 1024), HIPLIB=lib,
+               BYREF="1" if version.value < 70200000 else "0")
+    out = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "tools", "vmm_probe.py")], capture_output=True,
+                         text=True, timeout=150, env=env)
+    assert out.returncode == 0, out.stdout[-1000:] + out.stderr[-2000:]
+    res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    # everything on the owner's side has to work: only the import in the other process may be missing
+    assert res["create_rc"] == [0] and res["map_rc"] == [0] and res["export_rc"] == [0] and res["importer"] != "timeout", res
+    return res["importer"]["import_rc"] == [0]
+
+
+def _needs_chunks_across_processes():
+    if not _chunks_cross_processes():
+        pytest.skip("hipMemImportFromShareableHandle does not take another process's descriptors here")
 
 
 def _payload_of(tags, width):
@@ -99,6 +128,8 @@ def test_remote_gather_reads_the_owners_partition(chunk_bytes):
     """chunk_bytes > 0 (r5): the 20 MB payload field, the 15 MB sequence field and the 40 KB tag field are chunks of physical
     memory behind one virtual range each in BOTH processes (10 + 8 + 1 chunks of 2 MB; 4 + 3 + 1 of 6 MB, the last ones
     partial), handed over as file descriptors on a Unix socket"""
+    if chunk_bytes:
+        _needs_chunks_across_processes()
     hit = _remote_gather_against_owner(chunk_bytes)
     assert not chunk_bytes or len(hit) >= 3, hit  # the samples came out of several chunks
 
@@ -109,6 +140,7 @@ def test_remote_gather_from_a_partition_hipipc_cannot_carry():
     exported, mapped by this process and sampled from all over: 1.2 x 2^20 rows inserted, so that live rows reach into the
     fifth chunk (32 GB up), and every chunk is read by one of the 4 x 64 draws.  (The 4 GB sequence field and the tag field
     are one chunk each: 7 descriptors.)"""
+    _needs_chunks_across_processes()
     cap = 1 << 20
     hit = _remote_gather_against_owner(8 << 30, cap=cap, width=28224, rounds=4, timeout=120, n=cap + cap // 5)
     assert hit == set(range(5)), hit
@@ -122,6 +154,7 @@ def test_remote_gather_from_a_deduplicated_partition(mode):
     regenerates: every sampled transition must be obs = the env's stack at its tick (tags in the newest plane), next_obs =
     the same env's stack n ticks later, action = what the owner stored -- while the owner's actors keep ticking between its
     sample and this process's read (new units stored ahead; the slots the sample evicted are held)."""
+    _needs_chunks_across_processes()
     import torch
 
     from ipc_dedup_owner_child import B, NSTEP, A, frames

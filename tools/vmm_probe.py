@@ -77,6 +77,10 @@ def child(conn, chunks, chunk):
         rcs.append(h.hipMemImportFromShareableHandle(C.byref(hd), os_handle, POSIX_FD))
         handles.append(hd)
     out["import_rc"] = sorted(set(rcs))
+    if any(rcs):  # nothing to map: no handle is mapped, no address of an unmapped range is read
+        out["map_rc"], out["data_ok"] = None, False
+        conn.send(out)
+        return
     base, rc = map_range(h, handles, chunk)
     out["map_rc"] = sorted(set(rc))
     ok = True
