@@ -683,8 +683,12 @@ int rela_apex_learner_set_adam_betas(rela_apex_learner* l, float b1, float b2);
  * 1e-4 of its largest entry of mode 0.  2 = f32x3 (rela_ffnet_set_precision): conv2 / conv3 of all three forwards (from
  * 512 rows) and the weight-gradient / fc / head GEMMs with three-part bf16 operands (csrc/gemm_bf16x3.h, PARTS = 3) --
  * f32 accuracy, mode 0's tolerances (tests/test_learner_gpu.py); conv1, the conv data gradients, loss, clip and
- * optimiser exactly as in mode 0. */
+ * optimiser exactly as in mode 0.  In every mode rela_apex_learner_set_dgrad_x3 moves the conv data gradients alone. */
 int rela_apex_learner_set_precision(rela_apex_learner* l, int mode);
+/* on = 1: the conv2 / conv3 data gradients of the backward pass on the bf16 MFMA with every operand in three bf16 parts
+ * (csrc/dgrad_conv_x3.h: transposed convolutions, f32 accuracy), whatever the precision mode chose for them; 0 (default):
+ * the mode's own kernels, bit for bit.  Before or after _load; from the next _loss / _backward.  Other values: RELA_EINVAL. */
+int rela_apex_learner_set_dgrad_x3(rela_apex_learner* l, int on);
 /* as rela_apex_actor_set_value_rescale, for the target of td_err (apex.py:43-44).  The target carries no gradient, so the
  * backward pass keeps its formula with the new error.  Before the first rela_apex_learner_loss / _backward only (later:
  * RELA_ESTATE); eps <= 0 (default): off. */
@@ -738,6 +742,12 @@ int rela_debug_trunk_backward(int frames, int mode, int lanes, int fast_wgrad_mi
                               const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
                               const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b, float* g_c3w,
                               float* g_c3b, float* d_a2, float* d_a1, void* stream);
+/* as rela_debug_trunk_backward, with the option of rela_*_learner_set_dgrad_x3 (0 or 1): with 1 the two data gradients run on
+ * csrc/dgrad_conv_x3.h in every mode, with the weight fragments packed ahead where lanes = 1 and per call where lanes = 0 */
+int rela_debug_trunk_backward_opts(int frames, int mode, int lanes, int fast_wgrad_min_frames, int dgrad_x3, const uint8_t* obs,
+                                   const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
+                                   const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b, float* g_c3w,
+                                   float* g_c3b, float* d_a2, float* d_a1, void* stream);
 
 /* Test tap: what rela_apex_learner_loss launches after its three forwards -- TD error, priorities, loss and the head
  * gradient d_ha (csrc/learner.hip: learner_td_loss_grad, or td_kernel + learner_loss_grad) -- with the Q tables as
@@ -923,8 +933,10 @@ int rela_r2d2_learner_check(rela_r2d2_learner* l, void* stream);
  * The heads' two GEMMs (K = 32 / M = 32) were measured slower in three parts and stay on the f32 MFMA, as do the
  * recurrent chains and per-step recurrent GEMMs, the cell kernels, the conv data gradients, column sums, loss, clip and
  * optimiser.  Every split-K sum is reduced in a fixed order: a step gives the same bits every time.
- * Other values: RELA_EINVAL. */
+ * Other values: RELA_EINVAL.  In every mode rela_r2d2_learner_set_dgrad_x3 moves the conv data gradients alone. */
 int rela_r2d2_learner_set_precision(rela_r2d2_learner* l, int mode);
+/* as rela_apex_learner_set_dgrad_x3 (this learner packs the weight fragments per call, into its scratch) */
+int rela_r2d2_learner_set_dgrad_x3(rela_r2d2_learner* l, int on);
 /* as rela_apex_learner_set_value_rescale, for the per-timestep target of td_err (r2d2.py:172-176):
  * h(reward[i] + bootstrap[i] * gamma ** n * h_inv(target_qa[i + n])).  Padding, the eta-mixed priority and the gradient
  * keep their logic.  Before the first rela_r2d2_learner_loss / _backward only (later: RELA_ESTATE). */

@@ -18,6 +18,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # (no silent FMA); kernels that want FMA/MFMA ask for it explicitly.
 HIP_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wall",
              "-Wno-unused-function"]
+# per source file: dgrad_conv_x3.hip is compiled without packed f32 arithmetic (plain v_add_f32 / v_sub_f32 beside its MFMAs)
+EXTRA_HIP_FLAGS = {"dgrad_conv_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _newer(target, sources):
@@ -34,7 +36,7 @@ def build_native(verbose=False, force=False):
     for s in srcs:
         o = os.path.join(CSRC, os.path.basename(s)[:-4] + ".o")
         if force or _newer(o, deps):
-            cmd = [HIPCC] + HIP_FLAGS + ["-c", s, "-o", o]
+            cmd = [HIPCC] + HIP_FLAGS + EXTRA_HIP_FLAGS.get(os.path.basename(s), []) + ["-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)
             subprocess.run(cmd, check=True)

@@ -204,6 +204,8 @@ struct rela_apex_learner : LearnerCore {
   hipEvent_t ev[8] = {nullptr};  // 0 forward done | 1 unsplit done | 2 d_ha | 3 d_h | 4 d_a3 | 5 d_a2 | 6 side lane done
   float *part_side = nullptr, *cpart_side = nullptr;
   uint8_t *frag2 = nullptr, *frag3 = nullptr;  // conv2 / conv3 data-gradient weight fragments, re-packed with the weights
+  uint8_t *frag2_x3 = nullptr, *frag3_x3 = nullptr;  // ... and the three-part ones, while dgrad_x3 is on
+  bool dgrad_x3 = false;  // rela_apex_learner_set_dgrad_x3
 };
 
 namespace {
@@ -221,6 +223,7 @@ int repack(rela_apex_learner* l, bool online, bool target, hipStream_t s) {
     int rc = ffnet_load_extra(l->online, &p, s, extra);
     if (rc != RELA_OK) return rc;
     if (l->frag2) pack_dgrad_frags(l->w2p, l->w3p, l->frag2, l->frag3, s);
+    if (l->dgrad_x3 && l->frag2_x3) pack_dgrad_x3_frags(l->w2p, l->w3p, l->frag2_x3, l->frag3_x3, s);
   }
   if (target) {
     const rela_ffnet_params p = params_at(l, l->PT);
@@ -341,6 +344,8 @@ int build_learner(rela_apex_learner* l, int num_action, int max_batch, int multi
     if (int rc = m.alloc(&l->cpart_side, cpart_floats, false)) return rc;
     if (int rc = m.alloc(&l->frag2, kFrag2Bytes, false)) return rc;
     if (int rc = m.alloc(&l->frag3, kFrag3Bytes, false)) return rc;
+    if (int rc = m.alloc(&l->frag2_x3, kFrag2X3Bytes, false)) return rc;
+    if (int rc = m.alloc(&l->frag3_x3, kFrag3X3Bytes, false)) return rc;
   }
   return RELA_OK;
 }
@@ -400,6 +405,21 @@ extern "C" int rela_apex_learner_set_precision(rela_apex_learner* l, int mode) {
   int rc = rela_ffnet_set_precision(l->online, mode);
   if (rc != RELA_OK) return rc;
   return rela_ffnet_set_precision(l->target, mode);
+}
+
+extern "C" int rela_apex_learner_set_dgrad_x3(rela_apex_learner* l, int on) {
+  RELA_CHECK(l && (on == 0 || on == 1), RELA_EINVAL, "rela_apex_learner_set_dgrad_x3: needs a learner and on = 0 or 1");
+  const bool was = l->dgrad_x3;
+  l->dgrad_x3 = on != 0;
+  if (l->dgrad_x3 && !was && l->loaded && l->frag2_x3) {  // the fragments repack() skipped while the option was off
+    DeviceGuard g(l->device);
+    // (a rare call: after whatever stream loaded the weights, before whatever stream the next backward is given)
+    RELA_HIP(hipDeviceSynchronize());
+    pack_dgrad_x3_frags(l->w2p, l->w3p, l->frag2_x3, l->frag3_x3, nullptr);
+    RELA_LAUNCH_CHECK();
+    RELA_HIP(hipStreamSynchronize(nullptr));
+  }
+  return RELA_OK;
 }
 
 extern "C" int rela_apex_learner_sync_target(rela_apex_learner* l, void* stream_) {
@@ -582,7 +602,7 @@ extern "C" int rela_apex_learner_grad(rela_apex_learner* l, void* stream_) {
 
   ColsumJobs sums;  // the five bias gradients: queued here, one launch pair at the end of trunk_backward
   const bool lanes = l->side != nullptr;
-  const ApexBwdPlan plan = plan_apex_backward(rela_ffnet_precision(l->online), lanes);
+  const ApexBwdPlan plan = plan_apex_backward(rela_ffnet_precision(l->online), lanes, l->dgrad_x3);
   hipStream_t sw = lanes ? l->side : s;  // the weight-gradient lane
   if (lanes) lane_dep(l->ev[2], s, sw);  // d_ha and the forward's activations are ready
 
@@ -603,6 +623,7 @@ extern "C" int rela_apex_learner_grad(rela_apex_learner* l, void* stream_) {
       t.side = sw, t.ev_da3 = l->ev[4], t.ev_da2 = l->ev[5], t.ev_side = l->ev[6];
       t.part_side = l->part_side, t.cpart_side = l->cpart_side;
       if (t.plan.dgrad_bf16) t.frag2 = l->frag2, t.frag3 = l->frag3;
+      if (t.plan.dgrad_x3) t.frag2_x3 = l->frag2_x3, t.frag3_x3 = l->frag3_x3;
       t.s32 = l->s32, t.A = A, t.g_a_b = Gm[11], t.g_v_b = Gm[9];
     }
     if (int rc = trunk_backward(t, s, &sums)) return rc;

@@ -104,6 +104,15 @@ constexpr size_t kTrunkPartFloats = (size_t)256 * 64 * 576;
 // across steps: pack_dgrad_frags when the weights change, TrunkBwd::frag2 / frag3
 constexpr size_t kFrag2Bytes = (size_t)4 * 2 * 8 * 2 * 64 * 16, kFrag3Bytes = (size_t)4 * 18 * 2 * 64 * 16;
 void pack_dgrad_frags(const float* w2p, const float* w3p, void* frag2, void* frag3, hipStream_t s);
+// the three-part data gradients (dgrad_conv_x3.h, compiled in dgrad_conv_x3.hip; TrunkBwdPlan::dgrad_x3): their weight
+// fragments (TrunkBwd::frag2_x3 / frag3_x3 for a caller that keeps them across steps) and the two launches, which pack the
+// fragments into `scratch` (>= kFrag2X3Bytes / kFrag3X3Bytes) themselves where `frags` is null
+constexpr size_t kFrag2X3Bytes = (size_t)4 * 2 * 8 * 3 * 64 * 16, kFrag3X3Bytes = (size_t)4 * 18 * 3 * 64 * 16;
+void pack_dgrad_x3_frags(const float* w2p, const float* w3p, void* frag2, void* frag3, hipStream_t s);
+int launch_dgrad_conv3_x3(const float* d_a3, const float* w3p, const float* a2, float* d_a2, int frames, void* scratch,
+                          hipStream_t s, const void* frags);
+int launch_dgrad_conv2_x3(const float* d_a2, const float* w2p, const float* a1, float* d_a1, int frames, void* scratch,
+                          hipStream_t s, const void* frags);
 
 // the most frames of one trunk_backward call: the data gradients put frames * 100 / 64 (conv2) and frames * 81 / 64
 // (conv3) tiles on the grid's y axis
@@ -121,7 +130,8 @@ struct TrunkBwd {
   // What runs: the learner's TrunkArith for Bn frames (learner_plan.h).  bf16x2: the weight gradients on the dedicated bf16
   // kernels (conv2 / conv3 from kFastWgradMinFrames frames), the data gradients on dgrad_conv_bf16.h.  f32x3: the weight-gradient
   // GEMMs (contraction over batch x positions) on the bf16 MFMA with three-part operands, f32 accuracy (r4 at 512 frames, us
-  // f32 -> three-part: conv3 49 -> 35, conv2 63 -> 52, conv1 110 -> 102).
+  // f32 -> three-part: conv3 49 -> 35, conv2 63 -> 52, conv1 110 -> 102).  plan.dgrad_x3 (an option beside the mode): the two
+  // data gradients on dgrad_conv_x3.h whatever the mode's own choice was.
   TrunkBwdPlan plan;
   // Two-lane form (the Ape-X learner): conv3's and conv2's weight gradients, and the column sums of every tensor that
   // exists by then (the caller's pending jobs, d_a3, d_a2), run on `side` next to the data-gradient chain on the
@@ -131,6 +141,7 @@ struct TrunkBwd {
   hipEvent_t ev_da3 = nullptr, ev_da2 = nullptr, ev_side = nullptr;
   float *part_side = nullptr, *cpart_side = nullptr;  // the side lane's own `part` / `cpart`
   const void *frag2 = nullptr, *frag3 = nullptr;  // dgrad weight fragments packed ahead (else per call, into `part`)
+  const void *frag2_x3 = nullptr, *frag3_x3 = nullptr;  // the same for plan.dgrad_x3
   const float* s32 = nullptr;                     // (side lane) head_bias_grad after the column sums
   float *g_a_b = nullptr, *g_v_b = nullptr;
   int A = 0;

@@ -520,7 +520,10 @@ int trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending) {
     if (int rc = conv_wgrad<SetW64>(plan.w3, p, fast, kRedConv3, t.g_c3w, sw, "learner_wgrad_conv3")) return rc;
   }
   jobs.add(t.d_a3, (int64_t)Bn * 49, 64, t.g_c3b);
-  if (plan.dgrad_bf16) {  // transposed convolution on bf16 MFMA, ReLU mask fused, no column buffer (dgrad_conv_bf16.h)
+  if (plan.dgrad_x3) {  // the same design with three-part operands, f32 accuracy (dgrad_conv_x3.h)
+    ProfScope prof("learner_dgrad_conv3", s);
+    if (int rc = launch_dgrad_conv3_x3(t.d_a3, t.w3p, t.a2, t.d_a2, Bn, t.part, s, t.frag3_x3)) return rc;
+  } else if (plan.dgrad_bf16) {  // transposed convolution on bf16 MFMA, ReLU mask fused, no column buffer (dgrad_conv_bf16.h)
     ProfScope prof("learner_dgrad_conv3", s);
     (void)dgfast::launch_conv3(t.d_a3, t.w3p, t.a2, t.d_a2, Bn, t.part, s, t.frag3);
   } else {
@@ -543,7 +546,10 @@ int trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending) {
     if (t.s32) launch_head_bias_grad(t.s32, t.A, t.g_a_b, t.g_v_b, sw);
     jobs.n = 0;
   }
-  if (plan.dgrad_bf16) {
+  if (plan.dgrad_x3) {
+    ProfScope prof("learner_dgrad_conv2", s);
+    if (int rc = launch_dgrad_conv2_x3(t.d_a2, t.w2p, t.a1, t.d_a1, Bn, t.part, s, t.frag2_x3)) return rc;
+  } else if (plan.dgrad_bf16) {
     ProfScope prof("learner_dgrad_conv2", s);
     (void)dgfast::launch_conv2(t.d_a2, t.w2p, t.a1, t.d_a1, Bn, t.part, s, t.frag2);
   } else {
@@ -605,15 +611,17 @@ using namespace rela_amd;
 
 // Test tap: trunk_backward on its own, with the activations and the masked d_a3 as inputs of the call.
 // Everything the learners keep across steps (scratch, the permuted weight copies, the side lane) lives for this one call.
-extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fast_wgrad_min_frames, const uint8_t* obs,
-                                         const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
-                                         const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b,
-                                         float* g_c3w, float* g_c3b, float* d_a2, float* d_a1, void* stream_) {
-  RELA_CHECK(frames >= 1 && frames <= kTrunkMaxFrames && mode >= 0 && mode <= 2 && (lanes == 0 || lanes == 1), RELA_EINVAL,
-             "rela_debug_trunk_backward: bad arguments (frames %d, mode %d, lanes %d)", frames, mode, lanes);
+// (`who`: rela_debug_trunk_backward, or rela_debug_trunk_backward_opts with the learners' dgrad_x3 option)
+static int debug_trunk_backward(const char* who, int frames, int mode, int lanes, int fast_wgrad_min_frames, int dgrad_x3,
+                                const uint8_t* obs, const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
+                                const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b, float* g_c3w,
+                                float* g_c3b, float* d_a2, float* d_a1, void* stream_) {
+  RELA_CHECK(frames >= 1 && frames <= kTrunkMaxFrames && mode >= 0 && mode <= 2 && (lanes == 0 || lanes == 1) &&
+                 (dgrad_x3 == 0 || dgrad_x3 == 1),
+             RELA_EINVAL, "%s: bad arguments (frames %d, mode %d, lanes %d, dgrad_x3 %d)", who, frames, mode, lanes, dgrad_x3);
   RELA_CHECK(obs && a1 && a2 && d_a3 && conv2_w && conv3_w && g_c1w && g_c1b && g_c2w && g_c2b && g_c3w && g_c3b && d_a2 &&
                  d_a1,
-             RELA_EINVAL, "rela_debug_trunk_backward: a pointer is NULL");
+             RELA_EINVAL, "%s: a pointer is NULL", who);
   hipStream_t s = (hipStream_t)stream_;
   TrunkTapScratch sc;
   const size_t cpart_floats = (size_t)kColsumBlocks * (32 + 512 + 64 + 64 + 32);  // as the learners size it
@@ -626,7 +634,7 @@ extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fa
   t.Bn = frames, t.obs = obs, t.a1 = a1, t.a2 = a2, t.d_a3 = d_a3, t.d_a2 = d_a2, t.d_a1 = d_a1;
   t.w2p = w2p, t.w3p = w3p;
   t.g_c1w = g_c1w, t.g_c1b = g_c1b, t.g_c2w = g_c2w, t.g_c2b = g_c2b, t.g_c3w = g_c3w, t.g_c3b = g_c3b;
-  t.plan = plan_apex_backward(mode, lanes != 0)
+  t.plan = plan_apex_backward(mode, lanes != 0, dgrad_x3 != 0)
                .trunk.plan(frames, fast_wgrad_min_frames > 0 ? fast_wgrad_min_frames : kFastWgradMinFrames);
   if (int rc = sc.mem.alloc(&t.part, kTrunkPartFloats, false)) return rc;
   if (int rc = sc.mem.alloc(&t.cpart, cpart_floats, false)) return rc;
@@ -643,6 +651,13 @@ extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fa
       pack_dgrad_frags(w2p, w3p, frag2, frag3, s);
       t.frag2 = frag2, t.frag3 = frag3;
     }
+    if (t.plan.dgrad_x3) {  // ... and the three-part ones
+      uint8_t *frag2 = nullptr, *frag3 = nullptr;
+      if (int rc = sc.mem.alloc(&frag2, kFrag2X3Bytes, false)) return rc;
+      if (int rc = sc.mem.alloc(&frag3, kFrag3X3Bytes, false)) return rc;
+      pack_dgrad_x3_frags(w2p, w3p, frag2, frag3, s);
+      t.frag2_x3 = frag2, t.frag3_x3 = frag3;
+    }
   }
   const int rc = trunk_backward(t, s);
   const hipError_t launched = hipGetLastError();
@@ -653,6 +668,24 @@ extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fa
   RELA_HIP(launched);
   RELA_HIP(done);
   return RELA_OK;
+}
+
+extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fast_wgrad_min_frames, const uint8_t* obs,
+                                         const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
+                                         const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b,
+                                         float* g_c3w, float* g_c3b, float* d_a2, float* d_a1, void* stream_) {
+  return debug_trunk_backward("rela_debug_trunk_backward", frames, mode, lanes, fast_wgrad_min_frames, 0, obs, a1, a2, d_a3,
+                              conv2_w, conv3_w, g_c1w, g_c1b, g_c2w, g_c2b, g_c3w, g_c3b, d_a2, d_a1, stream_);
+}
+
+// Test tap: as rela_debug_trunk_backward, with the option of rela_*_learner_set_dgrad_x3
+extern "C" int rela_debug_trunk_backward_opts(int frames, int mode, int lanes, int fast_wgrad_min_frames, int dgrad_x3,
+                                              const uint8_t* obs, const float* a1, const float* a2, const float* d_a3,
+                                              const float* conv2_w, const float* conv3_w, float* g_c1w, float* g_c1b,
+                                              float* g_c2w, float* g_c2b, float* g_c3w, float* g_c3b, float* d_a2, float* d_a1,
+                                              void* stream_) {
+  return debug_trunk_backward("rela_debug_trunk_backward_opts", frames, mode, lanes, fast_wgrad_min_frames, dgrad_x3, obs, a1,
+                              a2, d_a3, conv2_w, conv3_w, g_c1w, g_c1b, g_c2w, g_c2b, g_c3w, g_c3b, d_a2, d_a1, stream_);
 }
 
 // Test tap: optimizer_apply itself on the caller's flat buffers: the norm, the clip coefficient and one

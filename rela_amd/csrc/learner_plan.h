@@ -40,6 +40,7 @@ struct TrunkBwdPlan {
   WgradPlan w3, w2, w1;
   int w1_max_blocks;  // of wgrad_conv1_bf16
   bool dgrad_bf16;    // the data gradients on dgrad_conv_bf16.h, else the f32 GEMM (f32x3 too: exact f32, one launch)
+  bool dgrad_x3;      // ... unless this is set: both on dgrad_conv_x3.h (three-part bf16 operands, f32 accuracy), in every mode
 };
 
 // conv3 / conv2: `base` slices, tripled for few frames; above, times the multiplier of the three-part GEMM
@@ -53,8 +54,9 @@ inline WgradPlan plan_wgrad23(GemmArith arith, int frames, int fast_wgrad_min_fr
 // frame count, conv2 / conv3 above kSmallTrunkMaxFrames).  Another split count is another association of the sum, so the
 // modes that existed before the R2D2 learner's mode 3 keep 1.  fast_wgrad_min_frames: kFastWgradMinFrames in both learners;
 // rela_debug_trunk_backward lowers it so that small ragged frame counts reach wgrad_conv{2,3}_bf16.
+// dgrad_x3: the learners' option of that name (rela_*_learner_set_dgrad_x3); it changes nothing but the plan's member.
 inline TrunkBwdPlan plan_trunk_backward(GemmArith arith, int frames, int fast_wgrad_min_frames, const int split_mul[3],
-                                        bool two_lanes) {
+                                        bool two_lanes, bool dgrad_x3 = false) {
   TrunkBwdPlan p{};
   p.w3 = plan_wgrad23(arith, frames, fast_wgrad_min_frames, kSplitW3, split_mul[2]);
   p.w2 = plan_wgrad23(arith, frames, fast_wgrad_min_frames, kSplitW2, split_mul[1]);
@@ -62,6 +64,7 @@ inline TrunkBwdPlan plan_trunk_backward(GemmArith arith, int frames, int fast_wg
   else p.w1 = {false, arith, kSplitW1 * (arith == kArithF32x3 ? split_mul[0] : 1)};
   p.w1_max_blocks = two_lanes ? kWgrad1BlocksTwoLanes : kWgrad1Blocks;
   p.dgrad_bf16 = arith == kArithBf16x2;
+  p.dgrad_x3 = dgrad_x3;
   return p;
 }
 
@@ -70,8 +73,9 @@ struct TrunkArith {
   GemmArith arith;
   int split_mul[3];  // conv1, conv2, conv3
   bool two_lanes;
+  bool dgrad_x3 = false;
   TrunkBwdPlan plan(int frames, int fast_wgrad_min_frames = kFastWgradMinFrames) const {
-    return plan_trunk_backward(arith, frames, fast_wgrad_min_frames, split_mul, two_lanes);
+    return plan_trunk_backward(arith, frames, fast_wgrad_min_frames, split_mul, two_lanes, dgrad_x3);
   }
 };
 
@@ -80,15 +84,16 @@ struct ApexBwdPlan {
   GemmArith heads_fc;  // the four GEMMs of head_fc_backward
   TrunkArith trunk;
 };
-inline ApexBwdPlan plan_apex_backward(int precision, bool two_lanes) {
+inline ApexBwdPlan plan_apex_backward(int precision, bool two_lanes, bool dgrad_x3 = false) {
   const GemmArith arith = precision == 1 ? kArithBf16x2 : precision == 2 ? kArithF32x3 : kArithF32;
-  return {arith, {arith, {1, 1, 1}, two_lanes}};
+  return {arith, {arith, {1, 1, 1}, two_lanes, dgrad_x3}};
 }
 
 // ---- R2D2 (rela_r2d2_learner_set_precision: 0 f32 | 1 bf16x2 | 2 f32x3 | 3 f32x3_bwd) -------------------------------
 // Mode 2 is a forward mode: its backward is mode 0's.  Mode 3 moves the large GEMMs over all training rows at once (dW_hh,
 // dW_ih, d_a3, the conv weight gradients) to three-part operands; the heads' GEMMs (K = 32, M = 32: 11 / 10 us in three
-// parts against 10 / 8 us), the recurrence, the cell kernels and the conv data gradients stay what they are in mode 0.
+// parts against 10 / 8 us), the recurrence, the cell kernels and the conv data gradients stay what they are in mode 0
+// (the data gradients unless dgrad_x3 moves them to dgrad_conv_x3.h, in any mode).
 constexpr int kSplitHeads = 32;
 constexpr int kSeqHeadSplitRows = 1024;  // from here the head weight gradient is split-K: 256 blocks instead of 8
 // twice the splits in mode 3: conv1 0.35 -> 0.28 ms, conv2 0.31 -> 0.25, conv3 0.28 -> 0.15 at 5,312 rows (four times: the same)
@@ -102,7 +107,7 @@ struct R2d2BwdPlan {
   GemmArith lstm_in;
   TrunkArith trunk;       // one lane
 };
-inline R2d2BwdPlan plan_r2d2_backward(int precision, int rows) {
+inline R2d2BwdPlan plan_r2d2_backward(int precision, int rows, bool dgrad_x3 = false) {
   R2d2BwdPlan p{};
   p.heads = kArithF32;
   p.head_wgrad_splits = rows >= kSeqHeadSplitRows ? kSplitHeads : 1;
@@ -111,6 +116,7 @@ inline R2d2BwdPlan plan_r2d2_backward(int precision, int rows) {
   if (precision == 1) p.trunk = {kArithBf16x2, {1, 1, 1}, false};
   else if (precision == 3) p.trunk = {kArithF32x3, {kX6SplitMul, kX6SplitMul, kX6SplitMul}, false};
   else p.trunk = {kArithF32, {1, 1, 1}, false};
+  p.trunk.dgrad_x3 = dgrad_x3;
   return p;
 }
 

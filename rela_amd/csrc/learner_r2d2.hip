@@ -665,6 +665,7 @@ struct rela_r2d2_learner : LearnerCore {
   // 1: the target net's conv trunk (no gradient, activations never read back) and the three large GEMMs of the LSTM's
   //    input side (gate GEMM of both nets, its data and weight gradients) on split-bf16 MFMA (gemm_bf16s.h)
   int precision = 0;
+  bool dgrad_x3 = false;  // rela_r2d2_learner_set_dgrad_x3
   // rec64 operands of those GEMMs (hi | lo bf16 records, 4 bytes per element)
   uint8_t* wrec[2] = {nullptr, nullptr};  // W_ih [2048][49 chunks], k = pos * 64 + c       (gate GEMM, per net)
   uint8_t* wTrec = nullptr;               // W_ih^T [3136][32 chunks], online                 (data gradient)
@@ -1172,6 +1173,12 @@ extern "C" int rela_r2d2_learner_set_precision(rela_r2d2_learner* l, int mode) {
   return rela_lstmnet_set_precision(l->target, net_mode);
 }
 
+extern "C" int rela_r2d2_learner_set_dgrad_x3(rela_r2d2_learner* l, int on) {
+  RELA_CHECK(l && (on == 0 || on == 1), RELA_EINVAL, "rela_r2d2_learner_set_dgrad_x3: needs a learner and on = 0 or 1");
+  l->dgrad_x3 = on != 0;  // (the weight fragments are packed per call, into the trunk's scratch)
+  return RELA_OK;
+}
+
 extern "C" int rela_r2d2_learner_check(rela_r2d2_learner* l, void* stream_) {
   RELA_CHECK(l, RELA_EINVAL, "rela_r2d2_learner_check: null learner");
   DeviceGuard g(l->device);
@@ -1324,7 +1331,7 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
   const size_t blk = (size_t)Bn * kHid;
   float *H = l->Hs[0], *Cc = l->Cs[0];
   const float* o_tr = H + (size_t)(burn + 1) * blk;  // LSTM outputs of the training steps
-  const R2d2BwdPlan plan = plan_r2d2_backward(l->precision, rowsTr);
+  const R2d2BwdPlan plan = plan_r2d2_backward(l->precision, rowsTr, l->dgrad_x3);
   // heads: d_o, dW, db
   if (int rc = seq_head_backward(plan, rowsTr, A, l->d_ha, o_tr, P.a_w, P.v_w, l->d_o, Gm[12], Gm[13], Gm[10], Gm[11], l->part,
                                  l->cpart, l->s32, false, s))

@@ -201,6 +201,11 @@ class _HipLearner:
             raise ValueError("%s.set_precision: %r is not one of %s" % (type(self).__name__, mode, sorted(self._PRECISIONS)))
         self._call("set_precision", self._PRECISIONS[mode])
 
+    def set_dgrad_x3(self, on):
+        """The conv2 / conv3 data gradients of the backward pass on three-part bf16 operands (csrc/dgrad_conv_x3.h, f32
+        accuracy) in whatever precision mode is set; False (default): the mode's own kernels.  rela_*_learner_set_dgrad_x3."""
+        self._call("set_dgrad_x3", int(bool(on)))
+
     def grad(self):
         self._call("grad", self._stream())
 

@@ -31,6 +31,7 @@ rela = create_env.rela
 
 
 LEARNER_PRECISIONS = ("f32", "bf16x2", "f32x3", "f32x3_bwd")
+LEARNER_DGRADS = ("mode", "x3")  # --learner_dgrad
 
 
 def parse_args(argv=None):
@@ -83,6 +84,9 @@ def parse_args(argv=None):
                    help="arithmetic of the HIP learner step (set_precision of rela_amd/learner.py): f32 = exact f32; bf16x2 "
                         "= two-part bf16 on the gradient-free forwards; f32x3 = f32-accurate three-part bf16 forwards; "
                         "f32x3_bwd (r2d2 only) = f32x3 plus the backward GEMMs on three-part bf16 operands")
+    p.add_argument("--learner_dgrad", type=str, default="mode", choices=LEARNER_DGRADS,
+                   help="conv data gradients of the HIP learner step: mode = what --learner_precision runs; x3 = three-part "
+                        "bf16 transposed convolutions, f32 accuracy (set_dgrad_x3 of rela_amd/learner.py)")
     # update rules beyond the reference's (torch's defaults, a fixed lr, the whole target copy); the defaults give its runs
     p.add_argument("--rmsprop_alpha", type=float, default=0.99, help="RMSprop's decay (apex; Ape-X as published: 0.95)")
     p.add_argument("--rmsprop_centered", type=int, default=0, help="1: centred RMSprop (apex; Ape-X as published)")
@@ -169,10 +173,22 @@ def learner_precision(args):
     return mode
 
 
+def learner_dgrad_x3(args):
+    """--learner_dgrad as the learners' set_dgrad_x3 argument, checked against --hip_learner (without it: mode)."""
+    choice = getattr(args, "learner_dgrad", "mode")
+    if choice not in LEARNER_DGRADS:
+        raise SystemExit("--learner_dgrad must be one of %s" % ", ".join(LEARNER_DGRADS))
+    if choice == "x3" and not getattr(args, "hip_learner", 1):
+        raise SystemExit("--learner_dgrad x3 needs the HIP learner step (--hip_learner 1): the PyTorch autograd step has no "
+                         "such kernels")
+    return choice == "x3"
+
+
 def train(args, on_epoch=None):
     if args.algo not in ("apex", "r2d2"):
         raise SystemExit("--algo must be apex or r2d2")
     precision = learner_precision(args)
+    dgrad_x3 = learner_dgrad_x3(args)
     rules = UpdateRules(args)
     torch.manual_seed(args.seed + 2)
     torch.cuda.manual_seed(args.seed + 3)
@@ -199,6 +215,8 @@ def train(args, on_epoch=None):
                                  **rules.learner_kw())
         if precision != "f32":
             learner.set_precision(precision)
+        if dgrad_x3:
+            learner.set_dgrad_x3(True)
 
     # create eval locker here, as upstream (main.py:115-116): replicas on the host, device string "cpu"
     eval_locker = rela.ModelLocker([type(agent).clone(agent, "cpu")], "cpu")
@@ -393,6 +411,8 @@ def _multi_worker(rank, world, args, port, results):
                                          **rules.learner_kw())
         if learner_precision(args) != "f32":
             learner.set_precision(learner_precision(args))
+        if learner_dgrad_x3(args):
+            learner.set_dgrad_x3(True)
         # scheduled exchange: command words (a host synchronisation on every rank) only with the weight publish every
         # actor_sync_freq steps; the sample / update_priority pairs in between follow the announced cycle
         if native:  # partitions and flat buffers mapped through HIP IPC: rows and weights never enter a collective
@@ -547,6 +567,7 @@ def train_multi(args):
     if args.algo not in ("apex", "r2d2"):
         raise SystemExit("--algo must be apex or r2d2")
     learner_precision(args)  # (refused here, before any process is spawned)
+    learner_dgrad_x3(args)
     UpdateRules(args, quiet=True)  # (likewise; the learner's rank builds and announces its own)
     if args.algo == "r2d2" and os.environ.get("RELA_REPLAY_DEDUP"):
         # the learner process would read the partitions' rows through IPC, and a sequence partition with de-duplicated

@@ -1,0 +1,175 @@
+"""The learners' dgrad_x3 option: the conv2 / conv3 data gradients on three-part bf16 operands (csrc/dgrad_conv_x3.h), through
+rela_debug_trunk_backward_opts and through both learners.  Reference, data sets, error units and bounds are those of
+tests/trunk_bwd_ref.py (tests/test_trunk_bwd_ref_cpu.py proves the preconditions of the exact data); the measured units are
+in profiles/dgrad_x3_error_units.md."""
+import ctypes as C
+
+import pytest
+
+import trunk_bwd_ref as R
+from test_trunk_backward_gpu import MODES, OUT_SHAPES, exact_case, expected_census, to_device
+
+pytestmark = pytest.mark.gpu
+
+NEW_KERNELS = {"dgrad_conv3_x3": 1, "dgrad_conv2_x3": 1}
+# the kernels stride frames over min(frames, 256) blocks: one frame, blocks - 1, blocks, blocks + 1, two rounds + 1
+EXACT_CASES = ([(mode, lanes, n) for mode in ("f32", "f32x3") for lanes in (0, 1) for n in (1, 2, 255, 256, 257, 513)] +
+               [("bf16x2", 1, 257)])
+EXACT_CASES.sort(key=lambda c: c[2])  # (cases of one frame count share their inputs and reference)
+
+
+@pytest.fixture(autouse=True)
+def _global_rng_untouched():
+    import torch
+
+    with torch.random.fork_rng(devices=[0]):
+        yield
+
+
+def run_tap(inp, mode, lanes, dgrad_x3, min_frames=0):
+    """device inputs {obs, a1, a2, d_a3, w2, w3} -> ({key: f32 tensor}, census); outputs start as NaN"""
+    import torch
+
+    from rela_amd import _capi as capi
+
+    n = inp["obs"].shape[0]
+    shapes = dict(OUT_SHAPES, d_a2=(n, 81, 64), d_a1=(n, 400, 32))
+    out = {k: torch.full(s, float("nan"), dtype=torch.float32, device="cuda") for k, s in shapes.items()}
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    with capi.launch_census() as census:
+        capi.check(capi.lib.rela_debug_trunk_backward_opts(
+            n, MODES[mode], lanes, min_frames, dgrad_x3, *[ptr(inp[k]) for k in ("obs", "a1", "a2", "d_a3", "w2", "w3")],
+            *[ptr(out[k]) for k in R.KEYS], C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+            "rela_debug_trunk_backward_opts")
+    torch.cuda.synchronize()
+    return out, dict(census.counts)
+
+
+def census_with_x3(mode, frames):
+    """the old tap's census with the two data-gradient launches replaced"""
+    want = dict(expected_census(mode, frames, 0), **NEW_KERNELS)
+    old = {"dgrad_conv3_bf16": 1, "dgrad_conv2_bf16": 1} if mode == "bf16x2" else {"gemm_lds (f32)": 2}
+    return {k: v - old.get(k, 0) for k, v in want.items() if v - old.get(k, 0)}
+
+
+@pytest.mark.parametrize("mode,lanes,frames", EXACT_CASES, ids=["%s-lanes%d-%d" % c for c in EXACT_CASES])
+def test_exact_data_through_the_new_tap(mode, lanes, frames):
+    import torch
+
+    for name in ("dense", "sparse"):
+        inp, want = exact_case(name, frames)  # (asserts the preconditions on the reference)
+        got, counts = run_tap(inp, mode, lanes, 1)
+        assert counts == census_with_x3(mode, frames), (name, counts)
+        for key in R.DATA_SETS[name]["exact"]:
+            assert torch.equal(got[key], want[key]), (name, key, int((got[key] != want[key]).sum()))
+
+
+@pytest.mark.parametrize("frames,gain,lanes", [(3, 4.6, 1), (257, 1.0, 0), (513, 4.6, 1)])
+def test_random_data_error_in_units(frames, gain, lanes, record_property):
+    """|got - float64| / (2^-24 * sum|terms|) per output against R.BOUND_UNITS["f32x3"]: four times what the parent's f32
+    data gradients measured.  g_c3w / g_c3b are computed before any data gradient: the option must not move their bits."""
+    import torch
+
+    inp = to_device(R.random_inputs(frames, gain))
+    ref, ab = R.reference(device="cuda", **inp), R.reference_abs(device="cuda", **inp)
+    for mode in ("f32", "f32x3"):
+        got, counts = run_tap(inp, mode, lanes, 1)
+        off, _ = run_tap(inp, mode, lanes, 0)
+        assert counts == census_with_x3(mode, frames), (mode, counts)
+        units = {k: R.err_units(got[k], ref[k], ab[k], R.U_F32) for k in R.KEYS}
+        for k in R.KEYS:
+            record_property("err_units_%s_x3_%s" % (mode, k), units[k])
+        print(frames, gain, lanes, mode, "units", " ".join("%s=%.3g" % kv for kv in units.items()))
+        for k in R.KEYS:
+            assert units[k] <= R.BOUND_UNITS["f32x3"][k], (mode, k, units[k])
+        for k in ("g_c3w", "g_c3b"):
+            assert torch.equal(got[k].view(torch.int32), off[k].view(torch.int32)), (mode, k)
+
+
+def _bits_equal(a, b):
+    import torch
+
+    return torch.equal(a.contiguous().view(torch.int32).flatten(), b.contiguous().view(torch.int32).flatten())
+
+
+def _step(learner, batch, weight):
+    """-> (loss, priorities, gradients, census) of one backward()"""
+    import torch
+
+    from rela_amd import _capi as capi
+
+    with capi.launch_census() as census:
+        loss, prio = learner.backward(batch, weight)[:2]
+    torch.cuda.synchronize()
+    return loss.clone(), prio.clone(), {k: v.clone() for k, v in learner.state_dict("grads").items()}, dict(census.counts)
+
+
+def _upstream_keeps_its_bits(off, on):
+    """loss, priorities and every gradient outside net.0.* / net.2.* as with the option off; the new kernels once each"""
+    assert all(on[3].get(k) == 1 for k in NEW_KERNELS) and not any(k in off[3] for k in NEW_KERNELS), (off[3], on[3])
+    assert on[3]["gemm_lds (f32)"] == off[3]["gemm_lds (f32)"] - 2
+    assert _bits_equal(off[0], on[0]) and _bits_equal(off[1], on[1])
+    for key in off[2]:
+        assert key.startswith(("net.0.", "net.2.")) or _bits_equal(off[2][key], on[2][key]), key
+    assert float(on[2]["net.0.weight"].abs().max()) > 0
+
+
+def test_apex_learner_wiring():
+    """A = 6, B = 32, f32x3; the conv1 / conv2 gradients equal the tap (two lanes, option on) fed with the learner's own obs,
+    a1, a2, d_a3 and weights, bit for bit"""
+    import torch
+
+    from rela_amd.learner import HipApexLearner
+    from synth import synth_params
+    from test_learner_gpu import make_batch
+
+    A, B = 6, 32
+    sd, tg = ({k: torch.from_numpy(v) for k, v in synth_params(A, seed, 4.6).items()} for seed in (41, 42))
+    batch, weight = make_batch(B, A, 5)
+    res = {}
+    for on in (False, True):
+        learner = HipApexLearner(A, B, 3, 0.99)
+        learner.set_dgrad_x3(on)  # (before the load, whose re-pack makes the fragments)
+        learner.load_state_dicts(sd, tg)
+        learner.set_precision("f32x3")
+        res[on] = _step(learner, batch, weight)
+        if on:
+            w = learner.state_dict("online")
+            inp = {"obs": batch.obs["s"], "a1": learner.debug_activations()[0], "a2": learner.debug_activations()[1],
+                   "d_a3": learner.debug_head_grads()[2], "w2": w["net.2.weight"], "w3": w["net.4.weight"]}
+            tap, _ = run_tap(inp, "f32x3", 1, 1)
+        learner.close()
+    _upstream_keeps_its_bits(res[False], res[True])
+    for key, name in (("g_c1w", "net.0.weight"), ("g_c1b", "net.0.bias"), ("g_c2w", "net.2.weight"), ("g_c2b", "net.2.bias")):
+        assert _bits_equal(tap[key], res[True][2][name]), key
+
+
+def test_r2d2_learner_wiring():
+    """the smallest shape of tests/test_r2d2_learner_bwd_mode_gpu.py in f32x3_bwd"""
+    from test_r2d2_learner_bwd_mode_gpu import SMALL, _case, _learner
+
+    _, batch, weight = _case(SMALL)
+    res = {}
+    for on in (False, True):
+        learner = _learner(SMALL, "f32x3_bwd")
+        learner.set_dgrad_x3(on)  # (after the load)
+        res[on] = _step(learner, batch, weight)
+        learner.check()
+        learner.close()
+    _upstream_keeps_its_bits(res[False], res[True])
+
+
+def test_bad_arguments_are_refused():
+    from rela_amd import _capi as capi
+    from rela_amd.learner import HipApexLearner, HipR2D2Learner
+
+    for learner, setter in ((HipApexLearner(6, 4, 2, 0.99), capi.lib.rela_apex_learner_set_dgrad_x3),
+                            (HipR2D2Learner(6, 4, 2, 0.99, 7, 0, 0.9), capi.lib.rela_r2d2_learner_set_dgrad_x3)):
+        assert setter(learner.h, 2) == capi.EINVAL and b"_set_dgrad_x3" in capi.lib.rela_last_error()
+        assert setter(None, 1) == capi.EINVAL
+        assert setter(learner.h, 1) == capi.OK and setter(learner.h, 0) == capi.OK
+        learner.close()
+    obs = to_device(R.exact_inputs("dense", 2))["obs"]
+    p = C.c_void_p(obs.data_ptr())
+    for mode, x3 in ((0, 2), (0, -1), (3, 1), (3, 0)):
+        assert capi.lib.rela_debug_trunk_backward_opts(*([2, mode, 0, 0, x3] + [p] * 14 + [None])) == capi.EINVAL
