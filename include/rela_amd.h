@@ -798,6 +798,14 @@ int rela_debug_head_fc_backward(int batch, int A, int mode, int lanes, const flo
 int rela_debug_lstm_input_backward(int rows, int mode, const float* dg, const float* hprev, const float* a3,
                                    const float* w_ih, float* g_w_ih, float* g_w_hh, float* g_b_ih, float* g_b_hh,
                                    float* d_a3, void* stream);
+/* The same call with the learner's lstm_in_rec3 option (rela_r2d2_learner_set_lstm_in_rec3): 1 runs the three GEMMs on
+ * three-part records in any mode (split_cols_rec3 / split_rows_rec3 / gemm_rec3_nt; the call makes its own records), 0 is
+ * rela_debug_lstm_input_backward.  Other values: RELA_EINVAL, like the other refusals before anything is launched. */
+int rela_debug_lstm_input_backward_opts(int rows, int mode, int lstm_in_rec3, const float* dg, const float* hprev,
+                                        const float* a3, const float* w_ih, float* g_w_ih, float* g_w_hh, float* g_b_ih,
+                                        float* g_b_hh, float* d_a3, void* stream);
+/* Tests: the row tile of gemm_rec3_nt's large (small = 0) or small (1) form, for row counts around it. */
+int rela_debug_lstm_in_rec3_row_tile(int small);
 /* Debug / tests: the learner's own d_ha [B][32], d_h [B][512] and d_a3 [B][49][64] of the last rela_apex_learner_grad
  * (d_ha: of the last rela_apex_learner_loss).  Valid until the next rela_apex_learner_loss.                        */
 int rela_apex_learner_debug_head_grads(rela_apex_learner* l, float** d_ha, float** d_h, float** d_a3);
@@ -937,6 +945,12 @@ int rela_r2d2_learner_check(rela_r2d2_learner* l, void* stream);
 int rela_r2d2_learner_set_precision(rela_r2d2_learner* l, int mode);
 /* as rela_apex_learner_set_dgrad_x3 (this learner packs the weight fragments per call, into its scratch) */
 int rela_r2d2_learner_set_dgrad_x3(rela_r2d2_learner* l, int on);
+/* on = 1: the three large GEMMs of the LSTM's input-side backward (dW_ih, dW_hh, d_a3 with its ReLU mask) on three-part
+ * record GEMMs (csrc/gemm_rec3.h: every operand split once per step into records of three exact bf16 parts, six part
+ * products per product, f32 accuracy) in whatever precision mode is set; 0 (default): the mode's own kernels.  Before or
+ * after load; takes effect from the next rela_r2d2_learner_loss.  The first on = 1 allocates the records (W_ih^T and the
+ * row / column scratch of a full batch): RELA_ENOMEM if that fails.  Other values: RELA_EINVAL. */
+int rela_r2d2_learner_set_lstm_in_rec3(rela_r2d2_learner* l, int on);
 /* as rela_apex_learner_set_value_rescale, for the per-timestep target of td_err (r2d2.py:172-176):
  * h(reward[i] + bootstrap[i] * gamma ** n * h_inv(target_qa[i + n])).  Padding, the eta-mixed priority and the gradient
  * keep their logic.  Before the first rela_r2d2_learner_loss / _backward only (later: RELA_ESTATE). */

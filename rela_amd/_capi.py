@@ -262,6 +262,8 @@ _sig("rela_debug_trunk_backward_opts", i32, [i32, i32, i32, i32, i32] + [vp] * 1
 _sig("rela_debug_loss_grad", i32, [i32, i32, i32] + [vp] * 7 + [f32, f32] + [vp] * 7)
 _sig("rela_debug_head_fc_backward", i32, [i32, i32, i32, i32] + [vp] * 15)
 _sig("rela_debug_lstm_input_backward", i32, [i32, i32] + [vp] * 10)
+_sig("rela_debug_lstm_input_backward_opts", i32, [i32, i32, i32] + [vp] * 10)
+_sig("rela_debug_lstm_in_rec3_row_tile", i32, [i32])
 _sig("rela_apex_learner_debug_head_grads", i32, [vp, P(vp), P(vp), P(vp)])
 _sig("rela_debug_optimizer_apply", i32, [i32, f32, f32, f32, i64, i64] + [vp] * 5 + [i32, P(C.c_uint), vp])
 _sig("rela_debug_optimizer_apply_opts", i32,
@@ -291,6 +293,7 @@ _sig("rela_r2d2_learner_stats_dev", vp, [vp])
 _sig("rela_r2d2_learner_check", i32, [vp, vp])
 _sig("rela_r2d2_learner_set_precision", i32, [vp, i32])
 _sig("rela_r2d2_learner_set_dgrad_x3", i32, [vp, i32])
+_sig("rela_r2d2_learner_set_lstm_in_rec3", i32, [vp, i32])
 _sig("rela_r2d2_learner_set_value_rescale", i32, [vp, f32])
 _sig("rela_r2d2_learner_debug_heads", i32, [vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(i32)])
 _sig("rela_r2d2_learner_debug_optim", i32, [vp, P(vp), P(vp), P(i64)])

@@ -18,6 +18,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # (no silent FMA); kernels that want FMA/MFMA ask for it explicitly.
 HIP_FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-std=c++17", "-Wall",
              "-Wno-unused-function"]
+# (gemm_rec3.hip, the three-part record GEMM beside it, takes the common flags)
 # per source file: dgrad_conv_x3.hip is compiled without packed f32 arithmetic (plain v_add_f32 / v_sub_f32 beside its MFMAs)
 EXTRA_HIP_FLAGS = {"dgrad_conv_x3.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 

@@ -113,6 +113,17 @@ int launch_dgrad_conv3_x3(const float* d_a3, const float* w3p, const float* a2, 
                           hipStream_t s, const void* frags);
 int launch_dgrad_conv2_x3(const float* d_a2, const float* w2p, const float* a1, float* d_a1, int frames, void* scratch,
                           hipStream_t s, const void* frags);
+// the three-part record GEMM of the R2D2 learner's LSTM input backward (gemm_rec3.h, compiled in gemm_rec3.hip;
+// R2d2BwdPlan::lstm_in_rec3): f32 rows / columns -> records of kLstmRec3Bytes per 64 k (a3_order: split_cols_rec64's),
+// C[M][N] = A records [M][KC] x B records [N][KC] stored plain or under the ReLU mask of act[M][N], and the row tile of
+// the large / small form (for the tests' row counts)
+constexpr size_t kLstmRec3Bytes = 384;
+void split_rows_rec3(const float* src, int64_t R, int K, uint8_t* dst, hipStream_t s);
+void split_cols_rec3(const float* src, int64_t R, int C, bool a3_order, uint8_t* dst, hipStream_t s);
+int launch_rec3_nt_plain(const uint8_t* A, const uint8_t* B, int M, int N, int KC, float* out, hipStream_t s, const char* name);
+int launch_rec3_nt_relu_mask(const uint8_t* A, const uint8_t* B, int M, int N, int KC, float* out, const float* act, hipStream_t s,
+                             const char* name);
+int lstm_rec3_row_tile(bool small);
 
 // the most frames of one trunk_backward call: the data gradients put frames * 100 / 64 (conv2) and frames * 81 / 64
 // (conv3) tiles on the grid's y axis

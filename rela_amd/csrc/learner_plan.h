@@ -105,14 +105,17 @@ struct R2d2BwdPlan {
   int head_wgrad_splits;  // 1: one GEMM straight into the gradient | kSplitHeads: partial tiles + head_wgrad_reduce
   bool lstm_in_rec64;     // lstm_input_backward on the rec64 path (gemm_bf16s.h), else three GEMMs in:
   GemmArith lstm_in;
+  bool lstm_in_rec3;      // ... unless this is set: the three GEMMs on gemm_rec3.h (three-part records, f32 accuracy), in every mode
   TrunkArith trunk;       // one lane
 };
-inline R2d2BwdPlan plan_r2d2_backward(int precision, int rows, bool dgrad_x3 = false) {
+// lstm_in_rec3: the learner's option of that name (rela_r2d2_learner_set_lstm_in_rec3); it changes nothing but the plan's member.
+inline R2d2BwdPlan plan_r2d2_backward(int precision, int rows, bool dgrad_x3 = false, bool lstm_in_rec3 = false) {
   R2d2BwdPlan p{};
   p.heads = kArithF32;
   p.head_wgrad_splits = rows >= kSeqHeadSplitRows ? kSplitHeads : 1;
   p.lstm_in_rec64 = precision == 1;
   p.lstm_in = precision == 3 ? kArithF32x3 : kArithF32;
+  p.lstm_in_rec3 = lstm_in_rec3;
   if (precision == 1) p.trunk = {kArithBf16x2, {1, 1, 1}, false};
   else if (precision == 3) p.trunk = {kArithF32x3, {kX6SplitMul, kX6SplitMul, kX6SplitMul}, false};
   else p.trunk = {kArithF32, {1, 1, 1}, false};

@@ -671,6 +671,11 @@ struct rela_r2d2_learner : LearnerCore {
   uint8_t* wTrec = nullptr;               // W_ih^T [3136][32 chunks], online                 (data gradient)
   uint8_t *arec = nullptr, *trec = nullptr;  // activations / gate gradients by rows; transposed operands of dW_ih
   uint64_t wver[2] = {1, 1}, rec_ver[2] = {0, 0};  // weight version (repack) / version the records were made from
+  // rela_r2d2_learner_set_lstm_in_rec3: the LSTM input backward on three-part records (gemm_rec3.h).  Allocated when the
+  // option is first turned on: W_ih^T [3136][32 chunks] (online), and the row / column scratch, arec / trec x 1.5
+  bool lstm_in_rec3 = false;
+  uint8_t *wTrec3 = nullptr, *arec3 = nullptr, *trec3 = nullptr;
+  uint64_t rec3_ver = 0;
   // f32x3 (r5): the trunks on split3 records and the x part of the gates as a three-part GEMM (csrc/gemm_s3.h)
   uint8_t* s3rec = nullptr;          // rowsAll x (a2 + a3 records)
   uint8_t* wx3[2] = {nullptr, nullptr};  // W_ih of either net as three-part fragments (gate columns as stored)
@@ -750,13 +755,24 @@ int refresh_weight_records(rela_r2d2_learner* l, int which, hipStream_t s) {
   return RELA_OK;
 }
 
+// W_ih^T of the online net as three-part records for lstm_in_rec3, made from the packed f32 copy when that changed
+int refresh_weight_records3(rela_r2d2_learner* l, hipStream_t s) {
+  if (!l->lstm_in_rec3 || l->rec3_ver == l->wver[0]) return RELA_OK;
+  ProfScope prof("learner_lstm_split_w", s);
+  split_rows_rec3(l->wihT[0], kFeat, kGates, l->wTrec3, s);  // wihT [3136][2048] row-wise = W_ih^T
+  RELA_LAUNCH_CHECK();
+  l->rec3_ver = l->wver[0];
+  return RELA_OK;
+}
+
 // The LSTM's input side over all training rows at once, between the BPTT and trunk_backward: dW_hh, dW_ih, the gate
 // column sum (both bias gradients) and the masked d_a3.  rec64 (R2d2BwdPlan::lstm_in_rec64, learner_plan.h): the rec64 path
 // (gemm_bf16s.h); else the three GEMMs in `arith` (R2d2BwdPlan::lstm_in): gemm_lds, or the same Problems on gemm_bf16x3 with
-// three-part operands.
+// three-part operands.  rec3 (R2d2BwdPlan::lstm_in_rec3) takes the place of either: the rec64 path's launches on three-part
+// records (gemm_rec3.h), with wTrec / arec / trec in that format and 1.5 x the size.
 struct LstmInBwd {
   int rowsTr;
-  bool rec64;
+  bool rec64, rec3;
   GemmArith arith;
   const float* dg;     // [rowsTr][2048] gate gradients
   const float* hprev;  // [rowsTr][512] h_{t-1} of every training row
@@ -771,13 +787,31 @@ struct LstmInBwd {
 int lstm_input_backward(const LstmInBwd& t, hipStream_t s) {
   const int rowsTr = t.rowsTr;
   const float *DG = t.dg, *hprev = t.hprev, *a3_tr = t.a3;
-  if (!t.rec64) {
+  if (!t.rec64 && !t.rec3) {
     ProbWhh p{};
     p.M = kGates, p.N = kHid, p.K = rowsTr;
     p.dg = DG, p.hprev = hprev, p.out = t.g_w_hh;
     if (int rc = launch_gemm_as<SetWg>(t.arith, p, 1, s, "learner_wgrad_lstm_hh")) return rc;
   }
-  if (t.rec64) {
+  if (t.rec3) {
+    // the rec64 branch below on three-part records: dg^T is split once and serves both weight gradients
+    const int chunks = ceil_div(rowsTr, 64);
+    uint8_t* dgT = t.trec;
+    uint8_t* a3T = t.trec + (size_t)kGates * chunks * kLstmRec3Bytes;
+    {
+      ProfScope prof("learner_lstm_split_cols", s);
+      split_cols_rec3(DG, rowsTr, kGates, false, dgT, s);
+      split_cols_rec3(a3_tr, rowsTr, kFeat, true, a3T, s);
+    }
+    int rc = launch_rec3_nt_plain(dgT, a3T, kGates, kFeat, chunks, t.g_w_ih, s, "learner_wgrad_lstm_ih");
+    if (rc != RELA_OK) return rc;
+    {
+      ProfScope prof("learner_lstm_split_cols", s);
+      split_cols_rec3(hprev, rowsTr, kHid, false, a3T, s);  // (in a3^T's place, consumed by the launch above)
+    }
+    rc = launch_rec3_nt_plain(dgT, a3T, kGates, kHid, chunks, t.g_w_hh, s, "learner_wgrad_lstm_hh");
+    if (rc != RELA_OK) return rc;
+  } else if (t.rec64) {
     // dW_ih[g][c*49+pos] = sum_r dg[r][g] * a3[r][pos*64+c]: both operands transposed into rec64 rows of 64 r each
     // (a3's columns land in weight_ih_l0's own column order, so the result is stored row-major as it is)
     using namespace gemm16;
@@ -807,7 +841,14 @@ int lstm_input_backward(const LstmInBwd& t, hipStream_t s) {
   }
   colsum_launch(DG, rowsTr, kGates, t.cpart, t.g_b_ih, s);  // bias_ih_l0 and bias_hh_l0 see the same gradient
   RELA_HIP(hipMemcpyAsync(t.g_b_hh, t.g_b_ih, sizeof(float) * kGates, hipMemcpyDeviceToDevice, s));
-  if (t.rec64) {
+  if (t.rec3) {
+    {
+      ProfScope prof("learner_lstm_split_rows", s);
+      split_rows_rec3(DG, rowsTr, kGates, t.arec, s);
+    }
+    int rc = launch_rec3_nt_relu_mask(t.arec, t.wTrec, rowsTr, kFeat, kGates / 64, t.d_a3, a3_tr, s, "learner_dgrad_lstm_ih");
+    if (rc != RELA_OK) return rc;
+  } else if (t.rec64) {
     using namespace gemm16;
     {
       ProfScope prof("learner_lstm_split_rows", s);
@@ -855,6 +896,10 @@ int forward_pre(rela_r2d2_learner* l, int which, int Bn, const uint8_t* obs, con
                        (fast_target || x3) ? &a3_records : nullptr, x3 ? l->s3rec : nullptr, which == 0);
   }
   if (rc != RELA_OK) return rc;
+  if (which == 0) {
+    rc = refresh_weight_records3(l, s);
+    if (rc != RELA_OK) return rc;
+  }
   if (l->precision == 1) {
     using namespace gemm16;
     rc = refresh_weight_records(l, which, s);
@@ -1179,6 +1224,19 @@ extern "C" int rela_r2d2_learner_set_dgrad_x3(rela_r2d2_learner* l, int on) {
   return RELA_OK;
 }
 
+extern "C" int rela_r2d2_learner_set_lstm_in_rec3(rela_r2d2_learner* l, int on) {
+  RELA_CHECK(l && (on == 0 || on == 1), RELA_EINVAL, "rela_r2d2_learner_set_lstm_in_rec3: needs a learner and on = 0 or 1");
+  if (on && !l->wTrec3) {  // the first time: W_ih^T's records, and the scratch for the rows of a full batch
+    DeviceGuard g(l->device);
+    const size_t rowsAll = (size_t)l->T * l->Bmax, chunks = (rowsAll + 63) / 64;
+    if (int rc = l->mem.alloc(&l->arec3, rowsAll * (kGates / 64) * kLstmRec3Bytes, false)) return rc;
+    if (int rc = l->mem.alloc(&l->trec3, (size_t)(kGates + kFeat) * chunks * kLstmRec3Bytes, false)) return rc;
+    if (int rc = l->mem.alloc(&l->wTrec3, (size_t)kFeat * (kGates / 64) * kLstmRec3Bytes, false)) return rc;
+  }
+  l->lstm_in_rec3 = on != 0;  // (the weight records are made by the next rela_r2d2_learner_loss)
+  return RELA_OK;
+}
+
 extern "C" int rela_r2d2_learner_check(rela_r2d2_learner* l, void* stream_) {
   RELA_CHECK(l, RELA_EINVAL, "rela_r2d2_learner_check: null learner");
   DeviceGuard g(l->device);
@@ -1331,7 +1389,7 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
   const size_t blk = (size_t)Bn * kHid;
   float *H = l->Hs[0], *Cc = l->Cs[0];
   const float* o_tr = H + (size_t)(burn + 1) * blk;  // LSTM outputs of the training steps
-  const R2d2BwdPlan plan = plan_r2d2_backward(l->precision, rowsTr, l->dgrad_x3);
+  const R2d2BwdPlan plan = plan_r2d2_backward(l->precision, rowsTr, l->dgrad_x3, l->lstm_in_rec3);
   // heads: d_o, dW, db
   if (int rc = seq_head_backward(plan, rowsTr, A, l->d_ha, o_tr, P.a_w, P.v_w, l->d_o, Gm[12], Gm[13], Gm[10], Gm[11], l->part,
                                  l->cpart, l->s32, false, s))
@@ -1370,11 +1428,12 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
   }
   {
     LstmInBwd t{};
-    t.rowsTr = rowsTr, t.rec64 = plan.lstm_in_rec64, t.arith = plan.lstm_in;
+    t.rowsTr = rowsTr, t.rec3 = plan.lstm_in_rec3, t.rec64 = plan.lstm_in_rec64 && !t.rec3, t.arith = plan.lstm_in;
     t.dg = ga_tr;                          // [rowsTr][2048]
     t.hprev = H + (size_t)burn * blk;      // h_{t-1} of training step t = H[burn + t]
     t.a3 = l->a3 + tr0 * kA3;
     t.wihp = l->wihp, t.wTrec = l->wTrec, t.arec = l->arec, t.trec = l->trec, t.cpart = l->cpart;
+    if (t.rec3) t.wTrec = l->wTrec3, t.arec = l->arec3, t.trec = l->trec3;
     t.g_w_ih = Gm[6], t.g_w_hh = Gm[7], t.g_b_ih = Gm[8], t.g_b_hh = Gm[9], t.d_a3 = l->d_a3;
     int rc = lstm_input_backward(t, s);
     if (rc != RELA_OK) return rc;
@@ -1424,8 +1483,18 @@ bool tap_output_overlaps(const TapBuf* bufs, int n, int first_out) {
 extern "C" int rela_debug_lstm_input_backward(int rows, int mode, const float* dg, const float* hprev, const float* a3,
                                               const float* w_ih, float* g_w_ih, float* g_w_hh, float* g_b_ih, float* g_b_hh,
                                               float* d_a3, void* stream_) {
-  RELA_CHECK(rows >= 1 && rows <= kLstmTapMaxRows && mode >= 0 && mode <= 3, RELA_EINVAL,
-             "rela_debug_lstm_input_backward: bad arguments (rows %d, mode %d)", rows, mode);
+  return rela_debug_lstm_input_backward_opts(rows, mode, 0, dg, hprev, a3, w_ih, g_w_ih, g_w_hh, g_b_ih, g_b_hh, d_a3, stream_);
+}
+
+extern "C" int rela_debug_lstm_in_rec3_row_tile(int small) { return lstm_rec3_row_tile(small != 0); }
+
+// ... with the learner's lstm_in_rec3 option (0 / 1): it makes its own three-part records, as the rec64 path does below
+extern "C" int rela_debug_lstm_input_backward_opts(int rows, int mode, int lstm_in_rec3, const float* dg, const float* hprev,
+                                                   const float* a3, const float* w_ih, float* g_w_ih, float* g_w_hh,
+                                                   float* g_b_ih, float* g_b_hh, float* d_a3, void* stream_) {
+  RELA_CHECK(rows >= 1 && rows <= kLstmTapMaxRows && mode >= 0 && mode <= 3 && (lstm_in_rec3 == 0 || lstm_in_rec3 == 1),
+             RELA_EINVAL, "rela_debug_lstm_input_backward: bad arguments (rows %d, mode %d, lstm_in_rec3 %d)", rows, mode,
+             lstm_in_rec3);
   RELA_CHECK(dg && hprev && a3 && w_ih && g_w_ih && g_w_hh && g_b_ih && g_b_hh && d_a3, RELA_EINVAL,
              "rela_debug_lstm_input_backward: a pointer is NULL");
   {
@@ -1441,9 +1510,10 @@ extern "C" int rela_debug_lstm_input_backward(int rows, int mode, const float* d
     DevBuffers mem;
     ~Scratch() { mem.free_all(); }
   } sc;
-  const R2d2BwdPlan plan = plan_r2d2_backward(mode, rows);
+  const R2d2BwdPlan plan = plan_r2d2_backward(mode, rows, false, lstm_in_rec3 != 0);
   LstmInBwd t{};
-  t.rowsTr = rows, t.rec64 = plan.lstm_in_rec64, t.arith = plan.lstm_in, t.dg = dg, t.hprev = hprev, t.a3 = a3;
+  t.rowsTr = rows, t.rec3 = plan.lstm_in_rec3, t.rec64 = plan.lstm_in_rec64 && !t.rec3, t.arith = plan.lstm_in;
+  t.dg = dg, t.hprev = hprev, t.a3 = a3;
   t.g_w_ih = g_w_ih, t.g_w_hh = g_w_hh, t.g_b_ih = g_b_ih, t.g_b_hh = g_b_hh, t.d_a3 = d_a3;
   // pack_lstm_learner also transposes W_hh and sums the biases: zeros stand in for them, their outputs are not read
   float *wihT = nullptr, *wihp = nullptr, *zeros = nullptr, *whhT = nullptr, *bsum = nullptr;
@@ -1465,6 +1535,16 @@ extern "C" int rela_debug_lstm_input_backward(int rows, int mode, const float* d
     if (int rc = sc.mem.alloc(&t.trec, (size_t)(kGates + kFeat) * chunks * REC, false)) return rc;
     hipLaunchKernelGGL(split_rows_rec64, dim3(ceil_div((int64_t)kGates * kFeat / 8, 256)), dim3(256), 0, s,
                        (const float*)wihT, (int64_t)kFeat, kGates, wTrec);
+    RELA_LAUNCH_CHECK();
+    t.wTrec = wTrec;
+  }
+  if (t.rec3) {  // as refresh_weight_records3 and rela_r2d2_learner_set_lstm_in_rec3's sizes, for `rows` rows
+    uint8_t* wTrec = nullptr;
+    const size_t chunks = ((size_t)rows + 63) / 64;
+    if (int rc = sc.mem.alloc(&wTrec, (size_t)kFeat * (kGates / 64) * kLstmRec3Bytes, false)) return rc;
+    if (int rc = sc.mem.alloc(&t.arec, (size_t)rows * (kGates / 64) * kLstmRec3Bytes, false)) return rc;
+    if (int rc = sc.mem.alloc(&t.trec, (size_t)(kGates + kFeat) * chunks * kLstmRec3Bytes, false)) return rc;
+    split_rows_rec3(wihT, kFeat, kGates, wTrec, s);
     RELA_LAUNCH_CHECK();
     t.wTrec = wTrec;
   }

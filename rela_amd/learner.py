@@ -380,6 +380,12 @@ class HipR2D2Learner(_HipLearner):
         the cell kernels, the conv data gradients, the column sums, loss, clip and optimiser stay in exact f32."""
         self._set_precision(mode)
 
+    def set_lstm_in_rec3(self, on):
+        """The three large GEMMs of the LSTM's input-side backward (dW_ih, dW_hh, the masked d_a3) on three-part record
+        GEMMs (csrc/gemm_rec3.h, f32 accuracy: every operand split once per step) in whatever precision mode is set; False
+        (default): the mode's own kernels.  From the next step on.  rela_r2d2_learner_set_lstm_in_rec3."""
+        self._call("set_lstm_in_rec3", int(bool(on)))
+
     def check(self):
         """Synchronises and raises if a grid barrier of the persistent recurrent kernels gave up since the last check."""
         self._call("check", self._stream())

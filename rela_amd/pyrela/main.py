@@ -32,6 +32,7 @@ rela = create_env.rela
 
 LEARNER_PRECISIONS = ("f32", "bf16x2", "f32x3", "f32x3_bwd")
 LEARNER_DGRADS = ("mode", "x3")  # --learner_dgrad
+LEARNER_LSTM_INS = ("mode", "rec3")  # --learner_lstm_in
 
 
 def parse_args(argv=None):
@@ -87,6 +88,9 @@ def parse_args(argv=None):
     p.add_argument("--learner_dgrad", type=str, default="mode", choices=LEARNER_DGRADS,
                    help="conv data gradients of the HIP learner step: mode = what --learner_precision runs; x3 = three-part "
                         "bf16 transposed convolutions, f32 accuracy (set_dgrad_x3 of rela_amd/learner.py)")
+    p.add_argument("--learner_lstm_in", type=str, default="mode", choices=LEARNER_LSTM_INS,
+                   help="the LSTM's input-side backward GEMMs of the HIP R2D2 learner step: mode = what --learner_precision "
+                        "runs; rec3 = three-part record GEMMs, f32 accuracy (set_lstm_in_rec3 of rela_amd/learner.py)")
     # update rules beyond the reference's (torch's defaults, a fixed lr, the whole target copy); the defaults give its runs
     p.add_argument("--rmsprop_alpha", type=float, default=0.99, help="RMSprop's decay (apex; Ape-X as published: 0.95)")
     p.add_argument("--rmsprop_centered", type=int, default=0, help="1: centred RMSprop (apex; Ape-X as published)")
@@ -184,11 +188,25 @@ def learner_dgrad_x3(args):
     return choice == "x3"
 
 
+def learner_lstm_in_rec3(args):
+    """--learner_lstm_in as the R2D2 learner's set_lstm_in_rec3 argument, checked against --algo and --hip_learner."""
+    choice = getattr(args, "learner_lstm_in", "mode")
+    if choice not in LEARNER_LSTM_INS:
+        raise SystemExit("--learner_lstm_in must be one of %s" % ", ".join(LEARNER_LSTM_INS))
+    if choice == "rec3" and not getattr(args, "hip_learner", 1):
+        raise SystemExit("--learner_lstm_in rec3 needs the HIP learner step (--hip_learner 1): the PyTorch autograd step has "
+                         "no such kernels")
+    if choice == "rec3" and args.algo != "r2d2":
+        raise SystemExit("--learner_lstm_in rec3 is the R2D2 learner's option (--algo r2d2): the Ape-X net has no LSTM")
+    return choice == "rec3"
+
+
 def train(args, on_epoch=None):
     if args.algo not in ("apex", "r2d2"):
         raise SystemExit("--algo must be apex or r2d2")
     precision = learner_precision(args)
     dgrad_x3 = learner_dgrad_x3(args)
+    lstm_in_rec3 = learner_lstm_in_rec3(args)
     rules = UpdateRules(args)
     torch.manual_seed(args.seed + 2)
     torch.cuda.manual_seed(args.seed + 3)
@@ -217,6 +235,8 @@ def train(args, on_epoch=None):
             learner.set_precision(precision)
         if dgrad_x3:
             learner.set_dgrad_x3(True)
+        if lstm_in_rec3:
+            learner.set_lstm_in_rec3(True)
 
     # create eval locker here, as upstream (main.py:115-116): replicas on the host, device string "cpu"
     eval_locker = rela.ModelLocker([type(agent).clone(agent, "cpu")], "cpu")
@@ -413,6 +433,8 @@ def _multi_worker(rank, world, args, port, results):
             learner.set_precision(learner_precision(args))
         if learner_dgrad_x3(args):
             learner.set_dgrad_x3(True)
+        if learner_lstm_in_rec3(args):
+            learner.set_lstm_in_rec3(True)
         # scheduled exchange: command words (a host synchronisation on every rank) only with the weight publish every
         # actor_sync_freq steps; the sample / update_priority pairs in between follow the announced cycle
         if native:  # partitions and flat buffers mapped through HIP IPC: rows and weights never enter a collective
@@ -568,6 +590,7 @@ def train_multi(args):
         raise SystemExit("--algo must be apex or r2d2")
     learner_precision(args)  # (refused here, before any process is spawned)
     learner_dgrad_x3(args)
+    learner_lstm_in_rec3(args)
     UpdateRules(args, quiet=True)  # (likewise; the learner's rank builds and announces its own)
     if args.algo == "r2d2" and os.environ.get("RELA_REPLAY_DEDUP"):
         # the learner process would read the partitions' rows through IPC, and a sequence partition with de-duplicated

@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Per-kernel HIP-event timings of the isolated R2D2 learner step at C4's shape (B = 64, seq 80 / burn 40 / n 3).
 
-  ITERS=10 [PRECISION=bf16x2] python tools/time_r2d2_learner.py      -> one line: kernel -> ms per step
+  ITERS=10 [PRECISION=bf16x2] [DGRAD=x3] [LSTM_IN=rec3] python tools/time_r2d2_learner.py   -> one line: kernel -> ms per step
+  LSTM_IN_AB=5 ITERS=20 PRECISION=f32x3_bwd DGRAD=x3 python tools/time_r2d2_learner.py
+      -> lstm_in_rec3 off and on alternated in this one process, LSTM_IN_AB pairs: per leg the whole step (device events,
+         profiler off) and, from a second window with the profiler on, the LSTM input backward's scopes; then
+         median [min .. max] of both per leg (profiles/lstm_in_rec3_ab.md)
 """
 import ctypes as C
 import json
@@ -25,6 +29,51 @@ agent = _agent(A, N, 0.997, 0.9, SEQ, BURN, 71, 72, "cuda:0")
 batch, weight = _random_batch(rng, A, B, SEQ, BURN, N, "cuda:0")
 learner = HipR2D2Learner.from_agent(agent, B)
 learner.set_precision(os.environ.get("PRECISION", "f32"))
+if os.environ.get("DGRAD") == "x3":
+    learner.set_dgrad_x3(True)
+if os.environ.get("LSTM_IN") == "rec3":
+    learner.set_lstm_in_rec3(True)
+
+# the scopes of lstm_input_backward's GEMM path, and the W_ih^T record refresh of every step (the weights move every step)
+LSTM_IN_SCOPES = ("learner_lstm_split_cols", "learner_wgrad_lstm_ih", "learner_wgrad_lstm_hh", "learner_lstm_split_rows",
+                  "learner_dgrad_lstm_ih", "learner_lstm_split_w")
+
+
+def window(profile):
+    """ITERS steps -> (ms per step by device events, {scope: ms per step} if profile)"""
+    capi.lib.rela_prof_enable(int(profile))
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(ITERS):
+        learner.step(batch, weight)
+    t1.record()
+    learner.check()
+    capi.lib.rela_prof_enable(0)
+    buf = C.create_string_buffer(1 << 16)
+    capi.check(capi.lib.rela_prof_summary_json(buf, len(buf)), "prof")
+    return t0.elapsed_time(t1) / ITERS, {k: v["total_ms"] / ITERS for k, v in json.loads(buf.value.decode()).items()}
+
+
+if os.environ.get("LSTM_IN_AB"):
+    legs = {0: [], 1: []}
+    for pair in range(int(os.environ["LSTM_IN_AB"])):
+        for on in (0, 1):
+            learner.set_lstm_in_rec3(bool(on))
+            for _ in range(3):
+                learner.step(batch, weight)
+            learner.check()
+            step_ms, _ = window(False)
+            _, prof = window(True)
+            scopes = {k: round(prof.get(k, 0.0), 4) for k in LSTM_IN_SCOPES}
+            legs[on].append((step_ms, sum(scopes.values())))
+            print("pair %d lstm_in_rec3 %d step %.3f ms  lstm_in %.3f ms  %s" % (pair, on, step_ms, sum(scopes.values()), scopes),
+                  flush=True)
+    for on in (0, 1):
+        for what, col in (("whole step", 0), ("lstm input backward scopes", 1)):
+            v = sorted(x[col] for x in legs[on])
+            print("lstm_in_rec3 %d %-27s median %.3f [%.3f .. %.3f] ms" % (on, what, v[len(v) // 2], v[0], v[-1]), flush=True)
+    sys.exit(0)
+
 for _ in range(2):
     learner.step(batch, weight)
 learner.check()
