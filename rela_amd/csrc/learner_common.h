@@ -124,6 +124,10 @@ int launch_rec3_nt_plain(const uint8_t* A, const uint8_t* B, int M, int N, int K
 int launch_rec3_nt_relu_mask(const uint8_t* A, const uint8_t* B, int M, int N, int KC, float* out, const float* act, hipStream_t s,
                              const char* name);
 int lstm_rec3_row_tile(bool small);
+// the three-part conv1 / conv2 weight gradients (wgrad_conv_x3.h, compiled in wgrad_conv_x3.hip; TrunkBwdPlan::wgrad_x3):
+// `blocks` partial tiles part[block][32][256] / part[block][64][512] for reduce_splits (kRedConv1 / kRedConv2)
+int launch_wgrad_conv1_x3(const uint8_t* obs, const float* d_a1, int frames, float* part, int blocks, hipStream_t s);
+int launch_wgrad_conv2_x3(const float* a1, const float* d_a2, int frames, float* part, int blocks, hipStream_t s);
 
 // the most frames of one trunk_backward call: the data gradients put frames * 100 / 64 (conv2) and frames * 81 / 64
 // (conv3) tiles on the grid's y axis
@@ -142,7 +146,8 @@ struct TrunkBwd {
   // kernels (conv2 / conv3 from kFastWgradMinFrames frames), the data gradients on dgrad_conv_bf16.h.  f32x3: the weight-gradient
   // GEMMs (contraction over batch x positions) on the bf16 MFMA with three-part operands, f32 accuracy (r4 at 512 frames, us
   // f32 -> three-part: conv3 49 -> 35, conv2 63 -> 52, conv1 110 -> 102).  plan.dgrad_x3 (an option beside the mode): the two
-  // data gradients on dgrad_conv_x3.h whatever the mode's own choice was.
+  // data gradients on dgrad_conv_x3.h whatever the mode's own choice was.  plan.wgrad_x3 (likewise): conv1's / conv2's weight
+  // gradients on wgrad_conv_x3.h, on the lanes and into the `part` buffers of the kernels they replace.
   TrunkBwdPlan plan;
   // Two-lane form (the Ape-X learner): conv3's and conv2's weight gradients, and the column sums of every tensor that
   // exists by then (the caller's pending jobs, d_a3, d_a2), run on `side` next to the data-gradient chain on the

@@ -465,6 +465,18 @@ int conv_wgrad(const WgradPlan& w, const P& p, Fast fast, int red, float* out, h
   return RELA_OK;
 }
 
+// conv1's / conv2's weight gradient of the wgrad_x3 option: `launch` (wgrad_conv_x3.hip) leaves `blocks` partial tiles in
+// `part`, reduce_splits finishes them as it does for the kernels above
+template <class Launch>
+int conv_wgrad_x3(Launch launch, const float* part, int blocks, int M, int N, int red, float* out, hipStream_t s, const char* name) {
+  {
+    ProfScope prof(name, s);
+    if (int rc = launch()) return rc;
+  }
+  hipLaunchKernelGGL(reduce_splits, dim3(ceil_div(M * N, 256)), dim3(256), 0, s, part, blocks, M, N, red, out);
+  return RELA_OK;
+}
+
 }  // namespace
 
 void colsum_multi_launch(ColsumJobs& jobs, float* cpart, hipStream_t s) {
@@ -533,7 +545,10 @@ int trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending) {
     launch_gemm<TileDgrad3>(p, 1, s, "learner_dgrad_conv3");
   }
   if (lanes) lane_dep(t.ev_da2, s, sw);  // d_a2 is ready
-  {  // conv2: dW2, db2, d_a1
+  if (plan.wgrad_x3) {  // conv2: dW2 on wgrad_conv_x3.h
+    auto x3 = [&]() { return launch_wgrad_conv2_x3(t.a1, t.d_a2, Bn, partw, plan.w2_x3_blocks, sw); };
+    if (int rc = conv_wgrad_x3(x3, partw, plan.w2_x3_blocks, 64, 512, kRedConv2, t.g_c2w, sw, "learner_wgrad_conv2")) return rc;
+  } else {  // conv2: dW2, db2, d_a1
     ProbW2 p{};
     p.M = 64, p.N = 512, p.K = Bn * 81;
     p.d_out = t.d_a2, p.in = t.a1, p.part = partw;
@@ -558,7 +573,10 @@ int trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending) {
     p.d_out = t.d_a2, p.wp = t.w2p, p.a1 = t.a1, p.d_a1 = t.d_a1;
     launch_gemm<TileDgrad2>(p, 1, s, "learner_dgrad_conv2");
   }
-  {  // conv1: dW1, db1 (no gradient flows into the frames)
+  if (plan.wgrad_x3) {  // conv1: dW1 on wgrad_conv_x3.h
+    auto x3 = [&]() { return launch_wgrad_conv1_x3(t.obs, t.d_a1, Bn, t.part, plan.w1_x3_blocks, s); };
+    if (int rc = conv_wgrad_x3(x3, t.part, plan.w1_x3_blocks, 32, 256, kRedConv1, t.g_c1w, s, "learner_wgrad_conv1")) return rc;
+  } else {  // conv1: dW1, db1 (no gradient flows into the frames)
     ProbW1 p{};
     p.M = 32, p.N = 256, p.K = Bn * 400;
     p.d_out = t.d_a1, p.obs = t.obs, p.part = t.part;
@@ -611,14 +629,15 @@ using namespace rela_amd;
 
 // Test tap: trunk_backward on its own, with the activations and the masked d_a3 as inputs of the call.
 // Everything the learners keep across steps (scratch, the permuted weight copies, the side lane) lives for this one call.
-// (`who`: rela_debug_trunk_backward, or rela_debug_trunk_backward_opts with the learners' dgrad_x3 option)
+// (`who`: rela_debug_trunk_backward, or rela_debug_trunk_backward_opts / _opts2 with the learners' dgrad_x3 / wgrad_x3 options)
 static int debug_trunk_backward(const char* who, int frames, int mode, int lanes, int fast_wgrad_min_frames, int dgrad_x3,
-                                const uint8_t* obs, const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
+                                int wgrad_x3, const uint8_t* obs, const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
                                 const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b, float* g_c3w,
                                 float* g_c3b, float* d_a2, float* d_a1, void* stream_) {
   RELA_CHECK(frames >= 1 && frames <= kTrunkMaxFrames && mode >= 0 && mode <= 2 && (lanes == 0 || lanes == 1) &&
-                 (dgrad_x3 == 0 || dgrad_x3 == 1),
-             RELA_EINVAL, "%s: bad arguments (frames %d, mode %d, lanes %d, dgrad_x3 %d)", who, frames, mode, lanes, dgrad_x3);
+                 (dgrad_x3 == 0 || dgrad_x3 == 1) && (wgrad_x3 == 0 || wgrad_x3 == 1),
+             RELA_EINVAL, "%s: bad arguments (frames %d, mode %d, lanes %d, dgrad_x3 %d, wgrad_x3 %d)", who, frames, mode, lanes,
+             dgrad_x3, wgrad_x3);
   RELA_CHECK(obs && a1 && a2 && d_a3 && conv2_w && conv3_w && g_c1w && g_c1b && g_c2w && g_c2b && g_c3w && g_c3b && d_a2 &&
                  d_a1,
              RELA_EINVAL, "%s: a pointer is NULL", who);
@@ -634,7 +653,7 @@ static int debug_trunk_backward(const char* who, int frames, int mode, int lanes
   t.Bn = frames, t.obs = obs, t.a1 = a1, t.a2 = a2, t.d_a3 = d_a3, t.d_a2 = d_a2, t.d_a1 = d_a1;
   t.w2p = w2p, t.w3p = w3p;
   t.g_c1w = g_c1w, t.g_c1b = g_c1b, t.g_c2w = g_c2w, t.g_c2b = g_c2b, t.g_c3w = g_c3w, t.g_c3b = g_c3b;
-  t.plan = plan_apex_backward(mode, lanes != 0, dgrad_x3 != 0)
+  t.plan = plan_apex_backward(mode, lanes != 0, dgrad_x3 != 0, wgrad_x3 != 0)
                .trunk.plan(frames, fast_wgrad_min_frames > 0 ? fast_wgrad_min_frames : kFastWgradMinFrames);
   if (int rc = sc.mem.alloc(&t.part, kTrunkPartFloats, false)) return rc;
   if (int rc = sc.mem.alloc(&t.cpart, cpart_floats, false)) return rc;
@@ -674,7 +693,7 @@ extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fa
                                          const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
                                          const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b,
                                          float* g_c3w, float* g_c3b, float* d_a2, float* d_a1, void* stream_) {
-  return debug_trunk_backward("rela_debug_trunk_backward", frames, mode, lanes, fast_wgrad_min_frames, 0, obs, a1, a2, d_a3,
+  return debug_trunk_backward("rela_debug_trunk_backward", frames, mode, lanes, fast_wgrad_min_frames, 0, 0, obs, a1, a2, d_a3,
                               conv2_w, conv3_w, g_c1w, g_c1b, g_c2w, g_c2b, g_c3w, g_c3b, d_a2, d_a1, stream_);
 }
 
@@ -684,8 +703,18 @@ extern "C" int rela_debug_trunk_backward_opts(int frames, int mode, int lanes, i
                                               const float* conv2_w, const float* conv3_w, float* g_c1w, float* g_c1b,
                                               float* g_c2w, float* g_c2b, float* g_c3w, float* g_c3b, float* d_a2, float* d_a1,
                                               void* stream_) {
-  return debug_trunk_backward("rela_debug_trunk_backward_opts", frames, mode, lanes, fast_wgrad_min_frames, dgrad_x3, obs, a1,
+  return debug_trunk_backward("rela_debug_trunk_backward_opts", frames, mode, lanes, fast_wgrad_min_frames, dgrad_x3, 0, obs, a1,
                               a2, d_a3, conv2_w, conv3_w, g_c1w, g_c1b, g_c2w, g_c2b, g_c3w, g_c3b, d_a2, d_a1, stream_);
+}
+
+// Test tap: as rela_debug_trunk_backward_opts, with the option of rela_*_learner_set_wgrad_x3 as well
+extern "C" int rela_debug_trunk_backward_opts2(int frames, int mode, int lanes, int fast_wgrad_min_frames, int dgrad_x3,
+                                               int wgrad_x3, const uint8_t* obs, const float* a1, const float* a2,
+                                               const float* d_a3, const float* conv2_w, const float* conv3_w, float* g_c1w,
+                                               float* g_c1b, float* g_c2w, float* g_c2b, float* g_c3w, float* g_c3b, float* d_a2,
+                                               float* d_a1, void* stream_) {
+  return debug_trunk_backward("rela_debug_trunk_backward_opts2", frames, mode, lanes, fast_wgrad_min_frames, dgrad_x3, wgrad_x3,
+                              obs, a1, a2, d_a3, conv2_w, conv3_w, g_c1w, g_c1b, g_c2w, g_c2b, g_c3w, g_c3b, d_a2, d_a1, stream_);
 }
 
 // Test tap: optimizer_apply itself on the caller's flat buffers: the norm, the clip coefficient and one

@@ -666,6 +666,7 @@ struct rela_r2d2_learner : LearnerCore {
   //    input side (gate GEMM of both nets, its data and weight gradients) on split-bf16 MFMA (gemm_bf16s.h)
   int precision = 0;
   bool dgrad_x3 = false;  // rela_r2d2_learner_set_dgrad_x3
+  bool wgrad_x3 = false;  // rela_r2d2_learner_set_wgrad_x3
   // rec64 operands of those GEMMs (hi | lo bf16 records, 4 bytes per element)
   uint8_t* wrec[2] = {nullptr, nullptr};  // W_ih [2048][49 chunks], k = pos * 64 + c       (gate GEMM, per net)
   uint8_t* wTrec = nullptr;               // W_ih^T [3136][32 chunks], online                 (data gradient)
@@ -1218,6 +1219,12 @@ extern "C" int rela_r2d2_learner_set_precision(rela_r2d2_learner* l, int mode) {
   return rela_lstmnet_set_precision(l->target, net_mode);
 }
 
+extern "C" int rela_r2d2_learner_set_wgrad_x3(rela_r2d2_learner* l, int on) {
+  RELA_CHECK(l && (on == 0 || on == 1), RELA_EINVAL, "rela_r2d2_learner_set_wgrad_x3: needs a learner and on = 0 or 1");
+  l->wgrad_x3 = on != 0;
+  return RELA_OK;
+}
+
 extern "C" int rela_r2d2_learner_set_dgrad_x3(rela_r2d2_learner* l, int on) {
   RELA_CHECK(l && (on == 0 || on == 1), RELA_EINVAL, "rela_r2d2_learner_set_dgrad_x3: needs a learner and on = 0 or 1");
   l->dgrad_x3 = on != 0;  // (the weight fragments are packed per call, into the trunk's scratch)
@@ -1389,7 +1396,7 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
   const size_t blk = (size_t)Bn * kHid;
   float *H = l->Hs[0], *Cc = l->Cs[0];
   const float* o_tr = H + (size_t)(burn + 1) * blk;  // LSTM outputs of the training steps
-  const R2d2BwdPlan plan = plan_r2d2_backward(l->precision, rowsTr, l->dgrad_x3, l->lstm_in_rec3);
+  const R2d2BwdPlan plan = plan_r2d2_backward(l->precision, rowsTr, l->dgrad_x3, l->lstm_in_rec3, l->wgrad_x3);
   // heads: d_o, dW, db
   if (int rc = seq_head_backward(plan, rowsTr, A, l->d_ha, o_tr, P.a_w, P.v_w, l->d_o, Gm[12], Gm[13], Gm[10], Gm[11], l->part,
                                  l->cpart, l->s32, false, s))
@@ -1642,6 +1649,15 @@ extern "C" int rela_r2d2_learner_debug_heads(rela_r2d2_learner* l, float** q_on,
   RELA_CHECK(l->last_B > 0, RELA_ESTATE, "rela_r2d2_learner_debug_heads: no rela_r2d2_learner_loss yet");
   *q_on = l->q_on, *q_tg = l->q_tg, *d_ha = l->d_ha, *d_o = l->d_o;
   *o_tr = l->Hs[0] + (size_t)(l->burn + 1) * l->last_B * kHid;
+  *rows = (l->T - l->burn) * l->last_B;
+  return RELA_OK;
+}
+
+extern "C" int rela_r2d2_learner_debug_trunk(rela_r2d2_learner* l, float** a1, float** a2, float** d_a3, int* rows) {
+  RELA_CHECK(l && a1 && a2 && d_a3 && rows, RELA_EINVAL, "rela_r2d2_learner_debug_trunk: bad arguments");
+  RELA_CHECK(l->last_B > 0, RELA_ESTATE, "rela_r2d2_learner_debug_trunk: no rela_r2d2_learner_loss yet");
+  const size_t tr0 = (size_t)l->burn * l->last_B;  // first training row
+  *a1 = l->a1 + tr0 * kA1, *a2 = l->a2 + tr0 * kA2, *d_a3 = l->d_a3;
   *rows = (l->T - l->burn) * l->last_B;
   return RELA_OK;
 }

@@ -206,6 +206,12 @@ class _HipLearner:
         accuracy) in whatever precision mode is set; False (default): the mode's own kernels.  rela_*_learner_set_dgrad_x3."""
         self._call("set_dgrad_x3", int(bool(on)))
 
+    def set_wgrad_x3(self, on):
+        """conv1's and conv2's weight gradients of the backward pass on three-part bf16 operands (csrc/wgrad_conv_x3.h, f32
+        accuracy) in whatever precision mode is set; conv3's stays on the mode's own kernel.  False (default): the mode's own
+        kernels.  rela_*_learner_set_wgrad_x3."""
+        self._call("set_wgrad_x3", int(bool(on)))
+
     def grad(self):
         self._call("grad", self._stream())
 
@@ -400,6 +406,16 @@ class HipR2D2Learner(_HipLearner):
         self._call("debug_heads", *[C.byref(x) for x in p], C.byref(rows))
         n, A = rows.value, self.num_action
         return [self._view(x.value, sh) for x, sh in zip(p, [(n, A), (n, A), (n, 32), (n, 512), (n, 512)])]
+
+    def debug_trunk(self):
+        """f32 views of what the conv trunk's backward pass of the last grad() read, over the time-major training rows: the
+        online net's a1 [rows,400,32], a2 [rows,81,64] and the masked d_a3 [rows,49,64]; valid until the next loss()."""
+        C = self._C
+        p = [C.c_void_p() for _ in range(3)]
+        rows = C.c_int()
+        self._call("debug_trunk", *[C.byref(x) for x in p], C.byref(rows))
+        n = rows.value
+        return [self._view(x.value, sh) for x, sh in zip(p, [(n, 400, 32), (n, 81, 64), (n, 49, 64)])]
 
     def backward(self, batch, weight):
         """batch: RNNTransition-shaped (time-major [T, B, ...] cuda tensors: obs{s, eps, legal_move}, h0{h0, c0},

@@ -32,6 +32,7 @@ rela = create_env.rela
 
 LEARNER_PRECISIONS = ("f32", "bf16x2", "f32x3", "f32x3_bwd")
 LEARNER_DGRADS = ("mode", "x3")  # --learner_dgrad
+LEARNER_WGRADS = ("mode", "x3")  # --learner_wgrad
 LEARNER_LSTM_INS = ("mode", "rec3")  # --learner_lstm_in
 
 
@@ -91,6 +92,9 @@ def parse_args(argv=None):
     p.add_argument("--learner_lstm_in", type=str, default="mode", choices=LEARNER_LSTM_INS,
                    help="the LSTM's input-side backward GEMMs of the HIP R2D2 learner step: mode = what --learner_precision "
                         "runs; rec3 = three-part record GEMMs, f32 accuracy (set_lstm_in_rec3 of rela_amd/learner.py)")
+    p.add_argument("--learner_wgrad", type=str, default="mode", choices=LEARNER_WGRADS,
+                   help="conv1 / conv2 weight gradients of the HIP learner step: mode = what --learner_precision runs; x3 = "
+                        "three-part bf16 space-to-depth kernels, f32 accuracy (set_wgrad_x3 of rela_amd/learner.py)")
     # update rules beyond the reference's (torch's defaults, a fixed lr, the whole target copy); the defaults give its runs
     p.add_argument("--rmsprop_alpha", type=float, default=0.99, help="RMSprop's decay (apex; Ape-X as published: 0.95)")
     p.add_argument("--rmsprop_centered", type=int, default=0, help="1: centred RMSprop (apex; Ape-X as published)")
@@ -188,6 +192,17 @@ def learner_dgrad_x3(args):
     return choice == "x3"
 
 
+def learner_wgrad_x3(args):
+    """--learner_wgrad as the learners' set_wgrad_x3 argument, checked against --hip_learner (without it: mode)."""
+    choice = getattr(args, "learner_wgrad", "mode")
+    if choice not in LEARNER_WGRADS:
+        raise SystemExit("--learner_wgrad must be one of %s" % ", ".join(LEARNER_WGRADS))
+    if choice == "x3" and not getattr(args, "hip_learner", 1):
+        raise SystemExit("--learner_wgrad x3 needs the HIP learner step (--hip_learner 1): the PyTorch autograd step has no "
+                         "such kernels")
+    return choice == "x3"
+
+
 def learner_lstm_in_rec3(args):
     """--learner_lstm_in as the R2D2 learner's set_lstm_in_rec3 argument, checked against --algo and --hip_learner."""
     choice = getattr(args, "learner_lstm_in", "mode")
@@ -206,6 +221,7 @@ def train(args, on_epoch=None):
         raise SystemExit("--algo must be apex or r2d2")
     precision = learner_precision(args)
     dgrad_x3 = learner_dgrad_x3(args)
+    wgrad_x3 = learner_wgrad_x3(args)
     lstm_in_rec3 = learner_lstm_in_rec3(args)
     rules = UpdateRules(args)
     torch.manual_seed(args.seed + 2)
@@ -235,6 +251,8 @@ def train(args, on_epoch=None):
             learner.set_precision(precision)
         if dgrad_x3:
             learner.set_dgrad_x3(True)
+        if wgrad_x3:
+            learner.set_wgrad_x3(True)
         if lstm_in_rec3:
             learner.set_lstm_in_rec3(True)
 
@@ -433,6 +451,8 @@ def _multi_worker(rank, world, args, port, results):
             learner.set_precision(learner_precision(args))
         if learner_dgrad_x3(args):
             learner.set_dgrad_x3(True)
+        if learner_wgrad_x3(args):
+            learner.set_wgrad_x3(True)
         if learner_lstm_in_rec3(args):
             learner.set_lstm_in_rec3(True)
         # scheduled exchange: command words (a host synchronisation on every rank) only with the weight publish every
@@ -590,6 +610,7 @@ def train_multi(args):
         raise SystemExit("--algo must be apex or r2d2")
     learner_precision(args)  # (refused here, before any process is spawned)
     learner_dgrad_x3(args)
+    learner_wgrad_x3(args)
     learner_lstm_in_rec3(args)
     UpdateRules(args, quiet=True)  # (likewise; the learner's rank builds and announces its own)
     if args.algo == "r2d2" and os.environ.get("RELA_REPLAY_DEDUP"):

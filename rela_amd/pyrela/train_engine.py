@@ -58,6 +58,7 @@ def parse_args(argv=None):
                    help="target net copy every so many updates (main.py: 2500; this loop's default run is 20,000 updates)")
     p.add_argument("--learner_precision", type=str, default="f32", choices=_main.LEARNER_PRECISIONS)
     p.add_argument("--learner_dgrad", type=str, default="mode", choices=_main.LEARNER_DGRADS)
+    p.add_argument("--learner_wgrad", type=str, default="mode", choices=_main.LEARNER_WGRADS)
     p.add_argument("--rmsprop_alpha", type=float, default=0.99)
     p.add_argument("--rmsprop_centered", type=int, default=0)
     p.add_argument("--adam_beta1", type=float, default=0.9)
@@ -141,6 +142,8 @@ def train(args, on_epoch=None):
         learner.set_precision(precision)
     if _main.learner_dgrad_x3(args):
         learner.set_dgrad_x3(True)
+    if _main.learner_wgrad_x3(args):
+        learner.set_wgrad_x3(True)
     online, target = FFNetHandle(A, device), FFNetHandle(A, device)
     online.load_state_dict(agent.online_net.state_dict())
     target.load_state_dict(agent.target_net.state_dict())

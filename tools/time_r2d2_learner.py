@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel HIP-event timings of the isolated R2D2 learner step at C4's shape (B = 64, seq 80 / burn 40 / n 3).
 
-  ITERS=10 [PRECISION=bf16x2] [DGRAD=x3] [LSTM_IN=rec3] python tools/time_r2d2_learner.py   -> one line: kernel -> ms per step
+  ITERS=10 [PRECISION=bf16x2] [DGRAD=x3] [WGRAD=x3] [LSTM_IN=rec3] python tools/time_r2d2_learner.py   -> one line: kernel -> ms per step
   LSTM_IN_AB=5 ITERS=20 PRECISION=f32x3_bwd DGRAD=x3 python tools/time_r2d2_learner.py
       -> lstm_in_rec3 off and on alternated in this one process, LSTM_IN_AB pairs: per leg the whole step (device events,
          profiler off) and, from a second window with the profiler on, the LSTM input backward's scopes; then
@@ -31,6 +31,8 @@ learner = HipR2D2Learner.from_agent(agent, B)
 learner.set_precision(os.environ.get("PRECISION", "f32"))
 if os.environ.get("DGRAD") == "x3":
     learner.set_dgrad_x3(True)
+if os.environ.get("WGRAD") == "x3":
+    learner.set_wgrad_x3(True)
 if os.environ.get("LSTM_IN") == "rec3":
     learner.set_lstm_in_rec3(True)
 
