@@ -684,7 +684,7 @@ int rela_apex_learner_set_adam_betas(rela_apex_learner* l, float b1, float b2);
  * 512 rows) and the weight-gradient / fc / head GEMMs with three-part bf16 operands (csrc/gemm_bf16x3.h, PARTS = 3) --
  * f32 accuracy, mode 0's tolerances (tests/test_learner_gpu.py); conv1, the conv data gradients, loss, clip and
  * optimiser exactly as in mode 0.  In every mode rela_apex_learner_set_dgrad_x3 moves the conv data gradients alone, and
- * rela_apex_learner_set_wgrad_x3 conv1's / conv2's weight gradients alone (conv3's stays on the mode's own kernel). */
+ * rela_apex_learner_set_wgrad_x3 conv1's / conv2's weight gradients alone (conv3's: rela_apex_learner_set_wgrad3_x3). */
 int rela_apex_learner_set_precision(rela_apex_learner* l, int mode);
 /* on = 1: the conv2 / conv3 data gradients of the backward pass on the bf16 MFMA with every operand in three bf16 parts
  * (csrc/dgrad_conv_x3.h: transposed convolutions, f32 accuracy), whatever the precision mode chose for them; 0 (default):
@@ -693,9 +693,15 @@ int rela_apex_learner_set_dgrad_x3(rela_apex_learner* l, int on);
 /* on = 1: conv1's and conv2's weight gradients of the backward pass on the bf16 MFMA with three-part operands
  * (csrc/wgrad_conv_x3.h: space-to-depth kernels as the bf16x2 mode's, the u8 frame in one exact part, every f32 operand in
  * three, f32 accuracy; partial tiles summed in a fixed order), whatever the precision mode chose for them; conv3's weight
- * gradient stays on the mode's own kernel (in f32x3: the three-part GEMM).  0 (default): the mode's own kernels, bit for
+ * gradient has a setter of its own, rela_apex_learner_set_wgrad3_x3.  0 (default): the mode's own kernels, bit for
  * bit.  Before or after _load; from the next _loss / _backward.  Other values: RELA_EINVAL. */
 int rela_apex_learner_set_wgrad_x3(rela_apex_learner* l, int on);
+/* on = 1: conv3's weight gradient of the backward pass on the bf16 MFMA with three-part operands (csrc/wgrad_conv3_x3.h:
+ * contraction over pixels as the bf16x2 mode's kernel, both operands in three exact bf16 parts, six products, f32 accuracy;
+ * one partial tile per block, summed in a fixed order), whatever the precision mode chose for it (in f32x3: the three-part
+ * GEMM) and independent of the other two options.  0 (default): the mode's own kernel, bit for bit.  Before or after _load;
+ * from the next _loss / _backward.  Other values: RELA_EINVAL. */
+int rela_apex_learner_set_wgrad3_x3(rela_apex_learner* l, int on);
 /* as rela_apex_actor_set_value_rescale, for the target of td_err (apex.py:43-44).  The target carries no gradient, so the
  * backward pass keeps its formula with the new error.  Before the first rela_apex_learner_loss / _backward only (later:
  * RELA_ESTATE); eps <= 0 (default): off. */
@@ -758,6 +764,13 @@ int rela_debug_trunk_backward_opts(int frames, int mode, int lanes, int fast_wgr
 /* as rela_debug_trunk_backward_opts, with the option of rela_*_learner_set_wgrad_x3 (0 or 1) as well: with 1 conv1's and
  * conv2's weight gradients run on csrc/wgrad_conv_x3.h in every mode, on the lanes of the kernels they replace */
 int rela_debug_trunk_backward_opts2(int frames, int mode, int lanes, int fast_wgrad_min_frames, int dgrad_x3, int wgrad_x3,
+                                    const uint8_t* obs, const float* a1, const float* a2, const float* d_a3,
+                                    const float* conv2_w, const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w,
+                                    float* g_c2b, float* g_c3w, float* g_c3b, float* d_a2, float* d_a1, void* stream);
+/* as rela_debug_trunk_backward_opts2, with the options as a bit mask: opts bit 0 = dgrad_x3, bit 1 = wgrad_x3, bit 2 = the
+ * option of rela_*_learner_set_wgrad3_x3 (conv3's weight gradient on csrc/wgrad_conv3_x3.h in every mode, on the lane of the
+ * kernel it replaces).  Any other bit: RELA_EINVAL. */
+int rela_debug_trunk_backward_opts3(int frames, int mode, int lanes, int fast_wgrad_min_frames, unsigned opts,
                                     const uint8_t* obs, const float* a1, const float* a2, const float* d_a3,
                                     const float* conv2_w, const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w,
                                     float* g_c2b, float* g_c3w, float* g_c3b, float* d_a2, float* d_a1, void* stream);
@@ -955,12 +968,14 @@ int rela_r2d2_learner_check(rela_r2d2_learner* l, void* stream);
  * recurrent chains and per-step recurrent GEMMs, the cell kernels, the conv data gradients, column sums, loss, clip and
  * optimiser.  Every split-K sum is reduced in a fixed order: a step gives the same bits every time.
  * Other values: RELA_EINVAL.  In every mode rela_r2d2_learner_set_dgrad_x3 moves the conv data gradients alone, and
- * rela_r2d2_learner_set_wgrad_x3 conv1's / conv2's weight gradients alone (conv3's stays on the mode's own kernel). */
+ * rela_r2d2_learner_set_wgrad_x3 conv1's / conv2's weight gradients alone (conv3's: rela_r2d2_learner_set_wgrad3_x3). */
 int rela_r2d2_learner_set_precision(rela_r2d2_learner* l, int mode);
 /* as rela_apex_learner_set_dgrad_x3 (this learner packs the weight fragments per call, into its scratch) */
 int rela_r2d2_learner_set_dgrad_x3(rela_r2d2_learner* l, int on);
 /* as rela_apex_learner_set_wgrad_x3 (one lane: both kernels on the caller's stream) */
 int rela_r2d2_learner_set_wgrad_x3(rela_r2d2_learner* l, int on);
+/* as rela_apex_learner_set_wgrad3_x3 (one lane: the kernel on the caller's stream) */
+int rela_r2d2_learner_set_wgrad3_x3(rela_r2d2_learner* l, int on);
 /* on = 1: the three large GEMMs of the LSTM's input-side backward (dW_ih, dW_hh, d_a3 with its ReLU mask) on three-part
  * record GEMMs (csrc/gemm_rec3.h: every operand split once per step into records of three exact bf16 parts, six part
  * products per product, f32 accuracy) in whatever precision mode is set; 0 (default): the mode's own kernels.  Before or

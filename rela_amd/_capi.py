@@ -248,6 +248,7 @@ _sig("rela_apex_learner_sync_target", i32, [vp, vp])
 _sig("rela_apex_learner_set_precision", i32, [vp, i32])
 _sig("rela_apex_learner_set_dgrad_x3", i32, [vp, i32])
 _sig("rela_apex_learner_set_wgrad_x3", i32, [vp, i32])
+_sig("rela_apex_learner_set_wgrad3_x3", i32, [vp, i32])
 _sig("rela_apex_learner_set_value_rescale", i32, [vp, f32])
 _sig("rela_apex_learner_backward", i32, [vp, i32, P(vp), vp, vp, vp, vp])
 _sig("rela_apex_learner_loss", i32, [vp, i32, P(vp), vp, vp, vp, vp])
@@ -261,6 +262,7 @@ _sig("rela_apex_learner_debug_activations", i32, [vp, P(vp), P(vp), P(vp), P(vp)
 _sig("rela_debug_trunk_backward", i32, [i32, i32, i32, i32] + [vp] * 15)
 _sig("rela_debug_trunk_backward_opts", i32, [i32, i32, i32, i32, i32] + [vp] * 15)
 _sig("rela_debug_trunk_backward_opts2", i32, [i32, i32, i32, i32, i32, i32] + [vp] * 15)
+_sig("rela_debug_trunk_backward_opts3", i32, [i32, i32, i32, i32, C.c_uint] + [vp] * 15)
 _sig("rela_debug_loss_grad", i32, [i32, i32, i32] + [vp] * 7 + [f32, f32] + [vp] * 7)
 _sig("rela_debug_head_fc_backward", i32, [i32, i32, i32, i32] + [vp] * 15)
 _sig("rela_debug_lstm_input_backward", i32, [i32, i32] + [vp] * 10)
@@ -296,6 +298,7 @@ _sig("rela_r2d2_learner_check", i32, [vp, vp])
 _sig("rela_r2d2_learner_set_precision", i32, [vp, i32])
 _sig("rela_r2d2_learner_set_dgrad_x3", i32, [vp, i32])
 _sig("rela_r2d2_learner_set_wgrad_x3", i32, [vp, i32])
+_sig("rela_r2d2_learner_set_wgrad3_x3", i32, [vp, i32])
 _sig("rela_r2d2_learner_set_lstm_in_rec3", i32, [vp, i32])
 _sig("rela_r2d2_learner_set_value_rescale", i32, [vp, f32])
 _sig("rela_r2d2_learner_debug_heads", i32, [vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(i32)])

@@ -207,6 +207,7 @@ struct rela_apex_learner : LearnerCore {
   uint8_t *frag2_x3 = nullptr, *frag3_x3 = nullptr;  // ... and the three-part ones, while dgrad_x3 is on
   bool dgrad_x3 = false;  // rela_apex_learner_set_dgrad_x3
   bool wgrad_x3 = false;  // rela_apex_learner_set_wgrad_x3
+  bool wgrad3_x3 = false;  // rela_apex_learner_set_wgrad3_x3
 };
 
 namespace {
@@ -429,6 +430,12 @@ extern "C" int rela_apex_learner_set_wgrad_x3(rela_apex_learner* l, int on) {
   return RELA_OK;
 }
 
+extern "C" int rela_apex_learner_set_wgrad3_x3(rela_apex_learner* l, int on) {
+  RELA_CHECK(l && (on == 0 || on == 1), RELA_EINVAL, "rela_apex_learner_set_wgrad3_x3: needs a learner and on = 0 or 1");
+  l->wgrad3_x3 = on != 0;  // (the kernel reads the activations itself: nothing to pack)
+  return RELA_OK;
+}
+
 extern "C" int rela_apex_learner_sync_target(rela_apex_learner* l, void* stream_) {
   RELA_CHECK(l && l->loaded, RELA_ESTATE, "rela_apex_learner_sync_target: parameters were never loaded");
   hipStream_t s = (hipStream_t)stream_;
@@ -609,7 +616,7 @@ extern "C" int rela_apex_learner_grad(rela_apex_learner* l, void* stream_) {
 
   ColsumJobs sums;  // the five bias gradients: queued here, one launch pair at the end of trunk_backward
   const bool lanes = l->side != nullptr;
-  const ApexBwdPlan plan = plan_apex_backward(rela_ffnet_precision(l->online), lanes, l->dgrad_x3, l->wgrad_x3);
+  const ApexBwdPlan plan = plan_apex_backward(rela_ffnet_precision(l->online), lanes, l->dgrad_x3, l->wgrad_x3, l->wgrad3_x3);
   hipStream_t sw = lanes ? l->side : s;  // the weight-gradient lane
   if (lanes) lane_dep(l->ev[2], s, sw);  // d_ha and the forward's activations are ready
 

@@ -128,6 +128,9 @@ int lstm_rec3_row_tile(bool small);
 // `blocks` partial tiles part[block][32][256] / part[block][64][512] for reduce_splits (kRedConv1 / kRedConv2)
 int launch_wgrad_conv1_x3(const uint8_t* obs, const float* d_a1, int frames, float* part, int blocks, hipStream_t s);
 int launch_wgrad_conv2_x3(const float* a1, const float* d_a2, int frames, float* part, int blocks, hipStream_t s);
+// the three-part conv3 weight gradient (wgrad_conv3_x3.h, compiled in wgrad_conv3_x3.hip; TrunkBwdPlan::wgrad3_x3):
+// `blocks` partial tiles part[block][64][576] for reduce_splits (kRedConv3)
+int launch_wgrad_conv3_x3(const float* a2, const float* d_a3, int frames, float* part, int blocks, hipStream_t s);
 
 // the most frames of one trunk_backward call: the data gradients put frames * 100 / 64 (conv2) and frames * 81 / 64
 // (conv3) tiles on the grid's y axis
@@ -147,7 +150,8 @@ struct TrunkBwd {
   // GEMMs (contraction over batch x positions) on the bf16 MFMA with three-part operands, f32 accuracy (r4 at 512 frames, us
   // f32 -> three-part: conv3 49 -> 35, conv2 63 -> 52, conv1 110 -> 102).  plan.dgrad_x3 (an option beside the mode): the two
   // data gradients on dgrad_conv_x3.h whatever the mode's own choice was.  plan.wgrad_x3 (likewise): conv1's / conv2's weight
-  // gradients on wgrad_conv_x3.h, on the lanes and into the `part` buffers of the kernels they replace.
+  // gradients on wgrad_conv_x3.h, on the lanes and into the `part` buffers of the kernels they replace.  plan.wgrad3_x3
+  // (likewise): conv3's weight gradient on wgrad_conv3_x3.h.
   TrunkBwdPlan plan;
   // Two-lane form (the Ape-X learner): conv3's and conv2's weight gradients, and the column sums of every tensor that
   // exists by then (the caller's pending jobs, d_a3, d_a2), run on `side` next to the data-gradient chain on the

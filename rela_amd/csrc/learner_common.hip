@@ -465,7 +465,7 @@ int conv_wgrad(const WgradPlan& w, const P& p, Fast fast, int red, float* out, h
   return RELA_OK;
 }
 
-// conv1's / conv2's weight gradient of the wgrad_x3 option: `launch` (wgrad_conv_x3.hip) leaves `blocks` partial tiles in
+// a conv weight gradient of the wgrad_x3 / wgrad3_x3 options: `launch` (wgrad_conv_x3.hip, wgrad_conv3_x3.hip) leaves `blocks` partial tiles in
 // `part`, reduce_splits finishes them as it does for the kernels above
 template <class Launch>
 int conv_wgrad_x3(Launch launch, const float* part, int blocks, int M, int N, int red, float* out, hipStream_t s, const char* name) {
@@ -524,7 +524,10 @@ int trunk_backward(const TrunkBwd& t, hipStream_t s, ColsumJobs* pending) {
   hipStream_t sw = lanes ? t.side : s;  // the lane of conv3's / conv2's weight gradients
   float* partw = lanes ? t.part_side : t.part;
   if (lanes) lane_dep(t.ev_da3, s, sw);  // d_a3 (and everything the pending jobs read) is ready
-  {  // conv3: dW3, db3, d_a2
+  if (plan.wgrad3_x3) {  // conv3: dW3 on wgrad_conv3_x3.h
+    auto x3 = [&]() { return launch_wgrad_conv3_x3(t.a2, t.d_a3, Bn, partw, plan.w3_x3_blocks, sw); };
+    if (int rc = conv_wgrad_x3(x3, partw, plan.w3_x3_blocks, 64, 576, kRedConv3, t.g_c3w, sw, "learner_wgrad_conv3")) return rc;
+  } else {  // conv3: dW3, db3, d_a2
     ProbW3 p{};
     p.M = 64, p.N = 576, p.K = Bn * 49;
     p.d_out = t.d_a3, p.in = t.a2, p.part = partw;
@@ -629,15 +632,16 @@ using namespace rela_amd;
 
 // Test tap: trunk_backward on its own, with the activations and the masked d_a3 as inputs of the call.
 // Everything the learners keep across steps (scratch, the permuted weight copies, the side lane) lives for this one call.
-// (`who`: rela_debug_trunk_backward, or rela_debug_trunk_backward_opts / _opts2 with the learners' dgrad_x3 / wgrad_x3 options)
+// (`who`: rela_debug_trunk_backward, or rela_debug_trunk_backward_opts / _opts2 / _opts3 with the learners' dgrad_x3 /
+// wgrad_x3 / wgrad3_x3 options)
 static int debug_trunk_backward(const char* who, int frames, int mode, int lanes, int fast_wgrad_min_frames, int dgrad_x3,
-                                int wgrad_x3, const uint8_t* obs, const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
+                                int wgrad_x3, int wgrad3_x3, const uint8_t* obs, const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
                                 const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b, float* g_c3w,
                                 float* g_c3b, float* d_a2, float* d_a1, void* stream_) {
   RELA_CHECK(frames >= 1 && frames <= kTrunkMaxFrames && mode >= 0 && mode <= 2 && (lanes == 0 || lanes == 1) &&
-                 (dgrad_x3 == 0 || dgrad_x3 == 1) && (wgrad_x3 == 0 || wgrad_x3 == 1),
-             RELA_EINVAL, "%s: bad arguments (frames %d, mode %d, lanes %d, dgrad_x3 %d, wgrad_x3 %d)", who, frames, mode, lanes,
-             dgrad_x3, wgrad_x3);
+                 (dgrad_x3 == 0 || dgrad_x3 == 1) && (wgrad_x3 == 0 || wgrad_x3 == 1) && (wgrad3_x3 == 0 || wgrad3_x3 == 1),
+             RELA_EINVAL, "%s: bad arguments (frames %d, mode %d, lanes %d, dgrad_x3 %d, wgrad_x3 %d, wgrad3_x3 %d)", who, frames,
+             mode, lanes, dgrad_x3, wgrad_x3, wgrad3_x3);
   RELA_CHECK(obs && a1 && a2 && d_a3 && conv2_w && conv3_w && g_c1w && g_c1b && g_c2w && g_c2b && g_c3w && g_c3b && d_a2 &&
                  d_a1,
              RELA_EINVAL, "%s: a pointer is NULL", who);
@@ -653,7 +657,7 @@ static int debug_trunk_backward(const char* who, int frames, int mode, int lanes
   t.Bn = frames, t.obs = obs, t.a1 = a1, t.a2 = a2, t.d_a3 = d_a3, t.d_a2 = d_a2, t.d_a1 = d_a1;
   t.w2p = w2p, t.w3p = w3p;
   t.g_c1w = g_c1w, t.g_c1b = g_c1b, t.g_c2w = g_c2w, t.g_c2b = g_c2b, t.g_c3w = g_c3w, t.g_c3b = g_c3b;
-  t.plan = plan_apex_backward(mode, lanes != 0, dgrad_x3 != 0, wgrad_x3 != 0)
+  t.plan = plan_apex_backward(mode, lanes != 0, dgrad_x3 != 0, wgrad_x3 != 0, wgrad3_x3 != 0)
                .trunk.plan(frames, fast_wgrad_min_frames > 0 ? fast_wgrad_min_frames : kFastWgradMinFrames);
   if (int rc = sc.mem.alloc(&t.part, kTrunkPartFloats, false)) return rc;
   if (int rc = sc.mem.alloc(&t.cpart, cpart_floats, false)) return rc;
@@ -693,7 +697,7 @@ extern "C" int rela_debug_trunk_backward(int frames, int mode, int lanes, int fa
                                          const float* a1, const float* a2, const float* d_a3, const float* conv2_w,
                                          const float* conv3_w, float* g_c1w, float* g_c1b, float* g_c2w, float* g_c2b,
                                          float* g_c3w, float* g_c3b, float* d_a2, float* d_a1, void* stream_) {
-  return debug_trunk_backward("rela_debug_trunk_backward", frames, mode, lanes, fast_wgrad_min_frames, 0, 0, obs, a1, a2, d_a3,
+  return debug_trunk_backward("rela_debug_trunk_backward", frames, mode, lanes, fast_wgrad_min_frames, 0, 0, 0, obs, a1, a2, d_a3,
                               conv2_w, conv3_w, g_c1w, g_c1b, g_c2w, g_c2b, g_c3w, g_c3b, d_a2, d_a1, stream_);
 }
 
@@ -703,7 +707,7 @@ extern "C" int rela_debug_trunk_backward_opts(int frames, int mode, int lanes, i
                                               const float* conv2_w, const float* conv3_w, float* g_c1w, float* g_c1b,
                                               float* g_c2w, float* g_c2b, float* g_c3w, float* g_c3b, float* d_a2, float* d_a1,
                                               void* stream_) {
-  return debug_trunk_backward("rela_debug_trunk_backward_opts", frames, mode, lanes, fast_wgrad_min_frames, dgrad_x3, 0, obs, a1,
+  return debug_trunk_backward("rela_debug_trunk_backward_opts", frames, mode, lanes, fast_wgrad_min_frames, dgrad_x3, 0, 0, obs, a1,
                               a2, d_a3, conv2_w, conv3_w, g_c1w, g_c1b, g_c2w, g_c2b, g_c3w, g_c3b, d_a2, d_a1, stream_);
 }
 
@@ -713,8 +717,21 @@ extern "C" int rela_debug_trunk_backward_opts2(int frames, int mode, int lanes, 
                                                const float* d_a3, const float* conv2_w, const float* conv3_w, float* g_c1w,
                                                float* g_c1b, float* g_c2w, float* g_c2b, float* g_c3w, float* g_c3b, float* d_a2,
                                                float* d_a1, void* stream_) {
-  return debug_trunk_backward("rela_debug_trunk_backward_opts2", frames, mode, lanes, fast_wgrad_min_frames, dgrad_x3, wgrad_x3,
+  return debug_trunk_backward("rela_debug_trunk_backward_opts2", frames, mode, lanes, fast_wgrad_min_frames, dgrad_x3, wgrad_x3, 0,
                               obs, a1, a2, d_a3, conv2_w, conv3_w, g_c1w, g_c1b, g_c2w, g_c2b, g_c3w, g_c3b, d_a2, d_a1, stream_);
+}
+
+// Test tap: as rela_debug_trunk_backward_opts2, with every option of the trunk's backward as a bit of `opts`
+extern "C" int rela_debug_trunk_backward_opts3(int frames, int mode, int lanes, int fast_wgrad_min_frames, unsigned opts,
+                                               const uint8_t* obs, const float* a1, const float* a2, const float* d_a3,
+                                               const float* conv2_w, const float* conv3_w, float* g_c1w, float* g_c1b,
+                                               float* g_c2w, float* g_c2b, float* g_c3w, float* g_c3b, float* d_a2, float* d_a1,
+                                               void* stream_) {
+  RELA_CHECK((opts & ~7u) == 0, RELA_EINVAL,
+             "rela_debug_trunk_backward_opts3: opts 0x%x has a bit beyond dgrad_x3 (1), wgrad_x3 (2) and wgrad3_x3 (4)", opts);
+  return debug_trunk_backward("rela_debug_trunk_backward_opts3", frames, mode, lanes, fast_wgrad_min_frames, opts & 1,
+                              (opts >> 1) & 1, (opts >> 2) & 1, obs, a1, a2, d_a3, conv2_w, conv3_w, g_c1w, g_c1b, g_c2w, g_c2b,
+                              g_c3w, g_c3b, d_a2, d_a1, stream_);
 }
 
 // Test tap: optimizer_apply itself on the caller's flat buffers: the norm, the clip coefficient and one

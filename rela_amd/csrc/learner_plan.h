@@ -45,6 +45,10 @@ inline int plan_wgrad1_x3_blocks(int frames, bool two_lanes) {
 // measured 114 / 62 / 42 us on one lane and 152 / 99 / 78 us on two (profiles/wgrad_x3_ab.md), so fewer blocks for few
 // frames were tried and dropped.
 inline int plan_wgrad2_x3_blocks(int frames) { return frames < kWgradX3MaxBlocks ? frames : kWgradX3MaxBlocks; }
+// ---- the wgrad3_x3 option: conv3's weight gradient on wgrad_conv3_x3.h.  A frame per block up to one block per CU (its
+// tile is 144 KB: kTrunkPartFloats is exactly 256 of them); the result's bits depend on `frames` through this function only.
+constexpr int kWgrad3X3MaxBlocks = 256;
+inline int plan_wgrad3_x3_blocks(int frames) { return frames < kWgrad3X3MaxBlocks ? frames : kWgrad3X3MaxBlocks; }
 
 struct WgradPlan {
   bool bf16_kernel;  // wgrad_conv{1,2,3}_bf16.h (one partial tile per block), else a split-K GEMM:
@@ -57,9 +61,12 @@ struct TrunkBwdPlan {
   bool dgrad_bf16;    // the data gradients on dgrad_conv_bf16.h, else the f32 GEMM (f32x3 too: exact f32, one launch)
   bool dgrad_x3;      // ... unless this is set: both on dgrad_conv_x3.h (three-part bf16 operands, f32 accuracy), in every mode
   // conv1's / conv2's weight gradients on wgrad_conv_x3.h (three-part operands, f32 accuracy) with this many blocks,
-  // whatever w1 / w2 say, in every mode; conv3 keeps w3
+  // whatever w1 / w2 say, in every mode
   bool wgrad_x3;
   int w1_x3_blocks, w2_x3_blocks;
+  // conv3's weight gradient on wgrad_conv3_x3.h (likewise) with this many blocks, whatever w3 says, in every mode
+  bool wgrad3_x3;
+  int w3_x3_blocks;
 };
 
 // conv3 / conv2: `base` slices, tripled for few frames; above, times the multiplier of the three-part GEMM
@@ -75,8 +82,9 @@ inline WgradPlan plan_wgrad23(GemmArith arith, int frames, int fast_wgrad_min_fr
 // rela_debug_trunk_backward lowers it so that small ragged frame counts reach wgrad_conv{2,3}_bf16.
 // dgrad_x3: the learners' option of that name (rela_*_learner_set_dgrad_x3); it changes nothing but the plan's member.
 // wgrad_x3: likewise (rela_*_learner_set_wgrad_x3); it sets its member and the two block counts and nothing else.
+// wgrad3_x3: likewise (rela_*_learner_set_wgrad3_x3); its member and its block count.
 inline TrunkBwdPlan plan_trunk_backward(GemmArith arith, int frames, int fast_wgrad_min_frames, const int split_mul[3],
-                                        bool two_lanes, bool dgrad_x3 = false, bool wgrad_x3 = false) {
+                                        bool two_lanes, bool dgrad_x3 = false, bool wgrad_x3 = false, bool wgrad3_x3 = false) {
   TrunkBwdPlan p{};
   p.w3 = plan_wgrad23(arith, frames, fast_wgrad_min_frames, kSplitW3, split_mul[2]);
   p.w2 = plan_wgrad23(arith, frames, fast_wgrad_min_frames, kSplitW2, split_mul[1]);
@@ -88,6 +96,8 @@ inline TrunkBwdPlan plan_trunk_backward(GemmArith arith, int frames, int fast_wg
   p.wgrad_x3 = wgrad_x3;
   p.w1_x3_blocks = wgrad_x3 ? plan_wgrad1_x3_blocks(frames, two_lanes) : 0;
   p.w2_x3_blocks = wgrad_x3 ? plan_wgrad2_x3_blocks(frames) : 0;
+  p.wgrad3_x3 = wgrad3_x3;
+  p.w3_x3_blocks = wgrad3_x3 ? plan_wgrad3_x3_blocks(frames) : 0;
   return p;
 }
 
@@ -98,8 +108,9 @@ struct TrunkArith {
   bool two_lanes;
   bool dgrad_x3 = false;
   bool wgrad_x3 = false;
+  bool wgrad3_x3 = false;
   TrunkBwdPlan plan(int frames, int fast_wgrad_min_frames = kFastWgradMinFrames) const {
-    return plan_trunk_backward(arith, frames, fast_wgrad_min_frames, split_mul, two_lanes, dgrad_x3, wgrad_x3);
+    return plan_trunk_backward(arith, frames, fast_wgrad_min_frames, split_mul, two_lanes, dgrad_x3, wgrad_x3, wgrad3_x3);
   }
 };
 
@@ -108,9 +119,10 @@ struct ApexBwdPlan {
   GemmArith heads_fc;  // the four GEMMs of head_fc_backward
   TrunkArith trunk;
 };
-inline ApexBwdPlan plan_apex_backward(int precision, bool two_lanes, bool dgrad_x3 = false, bool wgrad_x3 = false) {
+inline ApexBwdPlan plan_apex_backward(int precision, bool two_lanes, bool dgrad_x3 = false, bool wgrad_x3 = false,
+                                      bool wgrad3_x3 = false) {
   const GemmArith arith = precision == 1 ? kArithBf16x2 : precision == 2 ? kArithF32x3 : kArithF32;
-  return {arith, {arith, {1, 1, 1}, two_lanes, dgrad_x3, wgrad_x3}};
+  return {arith, {arith, {1, 1, 1}, two_lanes, dgrad_x3, wgrad_x3, wgrad3_x3}};
 }
 
 // ---- R2D2 (rela_r2d2_learner_set_precision: 0 f32 | 1 bf16x2 | 2 f32x3 | 3 f32x3_bwd) -------------------------------
@@ -118,7 +130,7 @@ inline ApexBwdPlan plan_apex_backward(int precision, bool two_lanes, bool dgrad_
 // dW_ih, d_a3, the conv weight gradients) to three-part operands; the heads' GEMMs (K = 32, M = 32: 11 / 10 us in three
 // parts against 10 / 8 us), the recurrence, the cell kernels and the conv data gradients stay what they are in mode 0
 // (the data gradients unless dgrad_x3 moves them to dgrad_conv_x3.h, in any mode; wgrad_x3 moves conv1's / conv2's weight
-// gradients to wgrad_conv_x3.h, in any mode).
+// gradients to wgrad_conv_x3.h and wgrad3_x3 conv3's to wgrad_conv3_x3.h, in any mode).
 constexpr int kSplitHeads = 32;
 constexpr int kSeqHeadSplitRows = 1024;  // from here the head weight gradient is split-K: 256 blocks instead of 8
 // twice the splits in mode 3: conv1 0.35 -> 0.28 ms, conv2 0.31 -> 0.25, conv3 0.28 -> 0.15 at 5,312 rows (four times: the same)
@@ -135,7 +147,7 @@ struct R2d2BwdPlan {
 };
 // lstm_in_rec3: the learner's option of that name (rela_r2d2_learner_set_lstm_in_rec3); it changes nothing but the plan's member.
 inline R2d2BwdPlan plan_r2d2_backward(int precision, int rows, bool dgrad_x3 = false, bool lstm_in_rec3 = false,
-                                      bool wgrad_x3 = false) {
+                                      bool wgrad_x3 = false, bool wgrad3_x3 = false) {
   R2d2BwdPlan p{};
   p.heads = kArithF32;
   p.head_wgrad_splits = rows >= kSeqHeadSplitRows ? kSplitHeads : 1;
@@ -147,6 +159,7 @@ inline R2d2BwdPlan plan_r2d2_backward(int precision, int rows, bool dgrad_x3 = f
   else p.trunk = {kArithF32, {1, 1, 1}, false};
   p.trunk.dgrad_x3 = dgrad_x3;
   p.trunk.wgrad_x3 = wgrad_x3;
+  p.trunk.wgrad3_x3 = wgrad3_x3;
   return p;
 }
 

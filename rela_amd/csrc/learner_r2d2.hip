@@ -667,6 +667,7 @@ struct rela_r2d2_learner : LearnerCore {
   int precision = 0;
   bool dgrad_x3 = false;  // rela_r2d2_learner_set_dgrad_x3
   bool wgrad_x3 = false;  // rela_r2d2_learner_set_wgrad_x3
+  bool wgrad3_x3 = false;  // rela_r2d2_learner_set_wgrad3_x3
   // rec64 operands of those GEMMs (hi | lo bf16 records, 4 bytes per element)
   uint8_t* wrec[2] = {nullptr, nullptr};  // W_ih [2048][49 chunks], k = pos * 64 + c       (gate GEMM, per net)
   uint8_t* wTrec = nullptr;               // W_ih^T [3136][32 chunks], online                 (data gradient)
@@ -1225,6 +1226,12 @@ extern "C" int rela_r2d2_learner_set_wgrad_x3(rela_r2d2_learner* l, int on) {
   return RELA_OK;
 }
 
+extern "C" int rela_r2d2_learner_set_wgrad3_x3(rela_r2d2_learner* l, int on) {
+  RELA_CHECK(l && (on == 0 || on == 1), RELA_EINVAL, "rela_r2d2_learner_set_wgrad3_x3: needs a learner and on = 0 or 1");
+  l->wgrad3_x3 = on != 0;
+  return RELA_OK;
+}
+
 extern "C" int rela_r2d2_learner_set_dgrad_x3(rela_r2d2_learner* l, int on) {
   RELA_CHECK(l && (on == 0 || on == 1), RELA_EINVAL, "rela_r2d2_learner_set_dgrad_x3: needs a learner and on = 0 or 1");
   l->dgrad_x3 = on != 0;  // (the weight fragments are packed per call, into the trunk's scratch)
@@ -1396,7 +1403,7 @@ extern "C" int rela_r2d2_learner_grad(rela_r2d2_learner* l, void* stream_) {
   const size_t blk = (size_t)Bn * kHid;
   float *H = l->Hs[0], *Cc = l->Cs[0];
   const float* o_tr = H + (size_t)(burn + 1) * blk;  // LSTM outputs of the training steps
-  const R2d2BwdPlan plan = plan_r2d2_backward(l->precision, rowsTr, l->dgrad_x3, l->lstm_in_rec3, l->wgrad_x3);
+  const R2d2BwdPlan plan = plan_r2d2_backward(l->precision, rowsTr, l->dgrad_x3, l->lstm_in_rec3, l->wgrad_x3, l->wgrad3_x3);
   // heads: d_o, dW, db
   if (int rc = seq_head_backward(plan, rowsTr, A, l->d_ha, o_tr, P.a_w, P.v_w, l->d_o, Gm[12], Gm[13], Gm[10], Gm[11], l->part,
                                  l->cpart, l->s32, false, s))

@@ -208,9 +208,15 @@ class _HipLearner:
 
     def set_wgrad_x3(self, on):
         """conv1's and conv2's weight gradients of the backward pass on three-part bf16 operands (csrc/wgrad_conv_x3.h, f32
-        accuracy) in whatever precision mode is set; conv3's stays on the mode's own kernel.  False (default): the mode's own
+        accuracy) in whatever precision mode is set; conv3's has set_wgrad3_x3.  False (default): the mode's own
         kernels.  rela_*_learner_set_wgrad_x3."""
         self._call("set_wgrad_x3", int(bool(on)))
+
+    def set_wgrad3_x3(self, on):
+        """conv3's weight gradient of the backward pass on three-part bf16 operands (csrc/wgrad_conv3_x3.h, f32 accuracy) in
+        whatever precision mode is set, independent of the other options.  False (default): the mode's own kernel.
+        rela_*_learner_set_wgrad3_x3."""
+        self._call("set_wgrad3_x3", int(bool(on)))
 
     def grad(self):
         self._call("grad", self._stream())

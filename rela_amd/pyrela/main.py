@@ -32,7 +32,7 @@ rela = create_env.rela
 
 LEARNER_PRECISIONS = ("f32", "bf16x2", "f32x3", "f32x3_bwd")
 LEARNER_DGRADS = ("mode", "x3")  # --learner_dgrad
-LEARNER_WGRADS = ("mode", "x3")  # --learner_wgrad
+LEARNER_WGRADS = ("mode", "x3", "x3_all")  # --learner_wgrad
 LEARNER_LSTM_INS = ("mode", "rec3")  # --learner_lstm_in
 
 
@@ -94,7 +94,8 @@ def parse_args(argv=None):
                         "runs; rec3 = three-part record GEMMs, f32 accuracy (set_lstm_in_rec3 of rela_amd/learner.py)")
     p.add_argument("--learner_wgrad", type=str, default="mode", choices=LEARNER_WGRADS,
                    help="conv1 / conv2 weight gradients of the HIP learner step: mode = what --learner_precision runs; x3 = "
-                        "three-part bf16 space-to-depth kernels, f32 accuracy (set_wgrad_x3 of rela_amd/learner.py)")
+                        "three-part bf16 space-to-depth kernels, f32 accuracy (set_wgrad_x3 of rela_amd/learner.py); x3_all = "
+                        "x3 and conv3's weight gradient in three parts as well (set_wgrad3_x3)")
     # update rules beyond the reference's (torch's defaults, a fixed lr, the whole target copy); the defaults give its runs
     p.add_argument("--rmsprop_alpha", type=float, default=0.99, help="RMSprop's decay (apex; Ape-X as published: 0.95)")
     p.add_argument("--rmsprop_centered", type=int, default=0, help="1: centred RMSprop (apex; Ape-X as published)")
@@ -197,10 +198,15 @@ def learner_wgrad_x3(args):
     choice = getattr(args, "learner_wgrad", "mode")
     if choice not in LEARNER_WGRADS:
         raise SystemExit("--learner_wgrad must be one of %s" % ", ".join(LEARNER_WGRADS))
-    if choice == "x3" and not getattr(args, "hip_learner", 1):
-        raise SystemExit("--learner_wgrad x3 needs the HIP learner step (--hip_learner 1): the PyTorch autograd step has no "
-                         "such kernels")
-    return choice == "x3"
+    if choice != "mode" and not getattr(args, "hip_learner", 1):
+        raise SystemExit("--learner_wgrad %s needs the HIP learner step (--hip_learner 1): the PyTorch autograd step has no "
+                         "such kernels" % choice)
+    return choice != "mode"
+
+
+def learner_wgrad3_x3(args):
+    """--learner_wgrad as the learners' set_wgrad3_x3 argument (x3_all; learner_wgrad_x3 has checked the choice)."""
+    return getattr(args, "learner_wgrad", "mode") == "x3_all"
 
 
 def learner_lstm_in_rec3(args):
@@ -253,6 +259,8 @@ def train(args, on_epoch=None):
             learner.set_dgrad_x3(True)
         if wgrad_x3:
             learner.set_wgrad_x3(True)
+        if learner_wgrad3_x3(args):
+            learner.set_wgrad3_x3(True)
         if lstm_in_rec3:
             learner.set_lstm_in_rec3(True)
 
@@ -453,6 +461,8 @@ def _multi_worker(rank, world, args, port, results):
             learner.set_dgrad_x3(True)
         if learner_wgrad_x3(args):
             learner.set_wgrad_x3(True)
+        if learner_wgrad3_x3(args):
+            learner.set_wgrad3_x3(True)
         if learner_lstm_in_rec3(args):
             learner.set_lstm_in_rec3(True)
         # scheduled exchange: command words (a host synchronisation on every rank) only with the weight publish every

@@ -144,6 +144,8 @@ def train(args, on_epoch=None):
         learner.set_dgrad_x3(True)
     if _main.learner_wgrad_x3(args):
         learner.set_wgrad_x3(True)
+    if _main.learner_wgrad3_x3(args):
+        learner.set_wgrad3_x3(True)
     online, target = FFNetHandle(A, device), FFNetHandle(A, device)
     online.load_state_dict(agent.online_net.state_dict())
     target.load_state_dict(agent.target_net.state_dict())

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Per-kernel HIP-event timings of the isolated R2D2 learner step at C4's shape (B = 64, seq 80 / burn 40 / n 3).
 
-  ITERS=10 [PRECISION=bf16x2] [DGRAD=x3] [WGRAD=x3] [LSTM_IN=rec3] python tools/time_r2d2_learner.py   -> one line: kernel -> ms per step
+  ITERS=10 [PRECISION=bf16x2] [DGRAD=x3] [WGRAD=x3|x3_all] [LSTM_IN=rec3] python tools/time_r2d2_learner.py   -> one line: kernel -> ms per step
   LSTM_IN_AB=5 ITERS=20 PRECISION=f32x3_bwd DGRAD=x3 python tools/time_r2d2_learner.py
       -> lstm_in_rec3 off and on alternated in this one process, LSTM_IN_AB pairs: per leg the whole step (device events,
          profiler off) and, from a second window with the profiler on, the LSTM input backward's scopes; then
          median [min .. max] of both per leg (profiles/lstm_in_rec3_ab.md)
+  WGRAD3_AB=7 ITERS=4 PRECISION=f32x3_bwd DGRAD=x3 WGRAD=x3 LSTM_IN=rec3 python tools/time_r2d2_learner.py
+      -> the same for wgrad3_x3 and the learner_wgrad_conv3 scope (profiles/wgrad3_x3_ab.md)
 """
 import ctypes as C
 import json
@@ -31,8 +33,10 @@ learner = HipR2D2Learner.from_agent(agent, B)
 learner.set_precision(os.environ.get("PRECISION", "f32"))
 if os.environ.get("DGRAD") == "x3":
     learner.set_dgrad_x3(True)
-if os.environ.get("WGRAD") == "x3":
+if os.environ.get("WGRAD") in ("x3", "x3_all"):
     learner.set_wgrad_x3(True)
+if os.environ.get("WGRAD") == "x3_all":
+    learner.set_wgrad3_x3(True)
 if os.environ.get("LSTM_IN") == "rec3":
     learner.set_lstm_in_rec3(True)
 
@@ -56,25 +60,32 @@ def window(profile):
     return t0.elapsed_time(t1) / ITERS, {k: v["total_ms"] / ITERS for k, v in json.loads(buf.value.decode()).items()}
 
 
-if os.environ.get("LSTM_IN_AB"):
+def alternate(pairs, name, setter, scopes, what):
+    """`name` off and on alternated, `pairs` pairs: per leg the whole step and the sum of `scopes`, then the medians"""
     legs = {0: [], 1: []}
-    for pair in range(int(os.environ["LSTM_IN_AB"])):
+    for pair in range(pairs):
         for on in (0, 1):
-            learner.set_lstm_in_rec3(bool(on))
+            setter(bool(on))
             for _ in range(3):
                 learner.step(batch, weight)
             learner.check()
             step_ms, _ = window(False)
             _, prof = window(True)
-            scopes = {k: round(prof.get(k, 0.0), 4) for k in LSTM_IN_SCOPES}
-            legs[on].append((step_ms, sum(scopes.values())))
-            print("pair %d lstm_in_rec3 %d step %.3f ms  lstm_in %.3f ms  %s" % (pair, on, step_ms, sum(scopes.values()), scopes),
+            picked = {k: round(prof.get(k, 0.0), 4) for k in scopes}
+            legs[on].append((step_ms, sum(picked.values())))
+            print("pair %d %s %d step %.3f ms  %s %.3f ms  %s" % (pair, name, on, step_ms, what, sum(picked.values()), picked),
                   flush=True)
     for on in (0, 1):
-        for what, col in (("whole step", 0), ("lstm input backward scopes", 1)):
+        for label, col in (("whole step", 0), (what + " scopes", 1)):
             v = sorted(x[col] for x in legs[on])
-            print("lstm_in_rec3 %d %-27s median %.3f [%.3f .. %.3f] ms" % (on, what, v[len(v) // 2], v[0], v[-1]), flush=True)
+            print("%s %d %-27s median %.3f [%.3f .. %.3f] ms" % (name, on, label, v[len(v) // 2], v[0], v[-1]), flush=True)
     sys.exit(0)
+
+
+if os.environ.get("LSTM_IN_AB"):
+    alternate(int(os.environ["LSTM_IN_AB"]), "lstm_in_rec3", learner.set_lstm_in_rec3, LSTM_IN_SCOPES, "lstm input backward")
+if os.environ.get("WGRAD3_AB"):
+    alternate(int(os.environ["WGRAD3_AB"]), "wgrad3_x3", learner.set_wgrad3_x3, ("learner_wgrad_conv3",), "conv3 weight gradient")
 
 for _ in range(2):
     learner.step(batch, weight)
