@@ -982,6 +982,14 @@ int rela_r2d2_learner_set_wgrad3_x3(rela_r2d2_learner* l, int on);
  * after load; takes effect from the next rela_r2d2_learner_loss.  The first on = 1 allocates the records (W_ih^T and the
  * row / column scratch of a full batch): RELA_ENOMEM if that fails.  Other values: RELA_EINVAL. */
 int rela_r2d2_learner_set_lstm_in_rec3(rela_r2d2_learner* l, int on);
+/* on = 1: a batch of 65 .. 128 rows runs the forward recurrence of both nets as ONE persistent launch, lstm_rec_chain32
+ * (csrc/learner_r2d2.hip: lstm_rec_chain's chains with 32 batch rows each, two 16-row sub-tiles per B fragment, the same
+ * bounded hand-off and timeout word, so rela_r2d2_learner_check covers it), instead of a split-K GEMM and a cell launch
+ * per net and time step; a row's sums keep lstm_rec_chain's order.  0 (default): the per-step launches.  Batches of up
+ * to 64 rows (lstm_rec_chain) and over 128 rows (per-step) are not affected, nor is a learner created with
+ * RELA_R2D2_REC=steps or on a device whose CUs cannot hold the grid.  Before or after load; takes effect from the next
+ * rela_r2d2_learner_loss / _backward.  NULL learner or other values: RELA_EINVAL. */
+int rela_r2d2_learner_set_rec_wide(rela_r2d2_learner* l, int on);
 /* as rela_apex_learner_set_value_rescale, for the per-timestep target of td_err (r2d2.py:172-176):
  * h(reward[i] + bootstrap[i] * gamma ** n * h_inv(target_qa[i + n])).  Padding, the eta-mixed priority and the gradient
  * keep their logic.  Before the first rela_r2d2_learner_loss / _backward only (later: RELA_ESTATE). */

@@ -377,6 +377,146 @@ __global__ __launch_bounds__(kRecThreads) void lstm_rec_chain(ChainArgs2 a) {
   }
 }
 
+// ---- persistent recurrent forward, wide chains (batches of 65 .. 128 rows; rela_r2d2_learner_set_rec_wide) ------
+// lstm_rec_chain with 32 batch rows per chain: a CHAIN is one net x one tile of 32 rows (2 x 4 chains = 128 rows),
+// run by the 32 blocks whose ids are equal mod 8; block j owns hidden units 16 j .. 16 j + 15 and holds the same 64
+// B-fragment registers of W_hh^T per lane, which now serve two 16-row sub-tiles: per step wave w loads its k-slice
+// [64 w, 64 w + 64) of h_{t-1} for both sub-tiles (8 sc1 loads of 16 bytes in flight), then runs 2 x 4 x 16
+// v_mfma_f32_16x16x4_f32, each B register feeding both sub-tiles.  A tile whose rows end in sub-tile 0 (one row of a
+// batch of 65 or 97) skips sub-tile 1.  ORDER OF SUMMATION per (row, gate column): as in lstm_rec_chain -- within
+// wave w the 16 MFMAs in k-step order ks = 0 .. 15 (k-step ks adds k = 64 w + 16 g + ks, g = 0 .. 3, inside one
+// MFMA), then x-part + partial of wave 0 + ... + wave 7 -- so a row's h_t has the bits lstm_rec_chain gives it.  The
+// partial tiles [8][32][65] f32 are 66,560 B: dynamic LDS, the limit raised at the launch.  The cell runs on one
+// thread per (row, unit), 32 x 16 = all 512 threads, c_t in a register.  Hand-off: lstm_rec_chain's, unchanged (one
+// counter per chain and step, 32 arrivals, every storing wave drained, one lane polling with bounded spins, the
+// timeout word, sc1 loads of h_{t-1}).  154 VGPRs, no scratch, one block per CU.  B = 128, T = 123: 1.05 ms (8.6 us per
+// step) against 4.57 ms of device time in 492 per-step launches (profiles/rec_wide_ab.md).
+constexpr int kWideRows = 32;
+constexpr size_t kWideLdsBytes = sizeof(float) * 8 * kWideRows * 65;
+__global__ __launch_bounds__(kRecThreads) void lstm_rec_chain32(ChainArgs2 a) {
+  extern __shared__ __attribute__((aligned(16))) float wide_red[];  // [8 waves][32 rows][65]
+  __shared__ int alive;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int li = lane & 15, g = lane >> 4;
+  const int chain = blockIdx.x & 7, j = blockIdx.x >> 3;  // chain = (net, row tile); j = unit block
+  const RecNet nt = a.net[chain >> 2];
+  const int row0 = (chain & 3) * kWideRows;
+  if (row0 >= a.Bn) return;  // (the whole chain leaves: its counters are its own)
+  const int nrow = min(kWideRows, a.Bn - row0);
+  const bool two = nrow > 16;  // (block-uniform) rows in sub-tile 1
+  // B fragments: column tile c = gate c, column li = unit 16 j + li; wave w: k in [64 w, 64 w + 64)
+  float bfr[4][16];
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) bfr[c][ks] = nt.whhT[(size_t)(wave * 64 + 16 * g + ks) * kGates + c * kHid + 16 * j + li];
+  const size_t blk = (size_t)a.Bn * kHid;
+  const __amdgpu_buffer_rsrc_t rsH = sc1_rsrc(nt.H, (size_t)(a.T + 1) * blk * 4);
+  // the cell's thread: unit u = tid & 15, row r = tid >> 4
+  const int cu = tid & 15, cr = tid >> 4;
+  const bool cell = cr < nrow;
+  const int crow = row0 + cr;
+  float c_reg = 0.f;
+  if (cell) c_reg = nt.C[(size_t)crow * kHid + 16 * j + cu];  // slot 0 = the initial state
+  float gpre[4];
+  auto gx_fetch = [&](int t) {
+    const float* grow = nt.gx + ((size_t)t * a.Bn + crow) * kGates + 16 * j + cu;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) gpre[q] = grow[q * kHid];
+  };
+  if (cell) gx_fetch(0);
+  float* red = wide_red + (size_t)wave * kWideRows * 65;
+  unsigned* bar = a.bar + (size_t)chain * a.Tpad;
+  for (int t = 0; t < a.T; ++t) {
+    // h_{t-1} of the chain's rows (rows past the batch re-read its last row; their results are never read)
+    float4 hv[2][4];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      if (s == 1 && !two) break;
+      const int arow = row0 + min(16 * s + li, nrow - 1);
+      const size_t hoff = (size_t)t * blk + (size_t)arow * kHid + wave * 64 + 16 * g;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) hv[s][q] = ld4_shared<true>(rsH, nt.H, hoff + 4 * q);
+    }
+    f32x4 acc[2][4];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[s][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float a0[16] = {hv[0][0].x, hv[0][0].y, hv[0][0].z, hv[0][0].w, hv[0][1].x, hv[0][1].y, hv[0][1].z, hv[0][1].w,
+                          hv[0][2].x, hv[0][2].y, hv[0][2].z, hv[0][2].w, hv[0][3].x, hv[0][3].y, hv[0][3].z, hv[0][3].w};
+    if (two) {
+      const float a1[16] = {hv[1][0].x, hv[1][0].y, hv[1][0].z, hv[1][0].w, hv[1][1].x, hv[1][1].y, hv[1][1].z, hv[1][1].w,
+                            hv[1][2].x, hv[1][2].y, hv[1][2].z, hv[1][2].w, hv[1][3].x, hv[1][3].y, hv[1][3].z, hv[1][3].w};
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) {  // (two independent accumulators per B register)
+          acc[0][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[ks], bfr[c][ks], acc[0][c], 0, 0, 0);
+          acc[1][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[ks], bfr[c][ks], acc[1][c], 0, 0, 0);
+        }
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) acc[0][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[ks], bfr[c][ks], acc[0][c], 0, 0, 0);
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      if (s == 1 && !two) break;
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[(16 * s + 4 * g + r) * 65 + c * 16 + li] = acc[s][c][r];
+    }
+    __syncthreads();
+    if (cell) {
+      float pre[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        pre[q] = gpre[q];
+#pragma unroll
+        for (int w = 0; w < 8; ++w) pre[q] += wide_red[((size_t)w * kWideRows + cr) * 65 + q * 16 + cu];
+      }
+      // the state that ENTERS the first training step is zeroed where the burn-in was a dummy (r2d2.py:149-154)
+      const bool zero = a.burn > 0 && t + 1 == a.burn && a.term[(size_t)(a.burn - 1) * a.Bn + crow] != 0;
+      const float gi = sigm(pre[0]), gf = sigm(pre[1]), gg = tanhf(pre[2]), go = sigm(pre[3]);
+      float c = gf * c_reg + gi * gg;
+      float h = go * tanhf(c);
+      if (zero) c = 0.f, h = 0.f;
+      c_reg = c;
+      const size_t o = (size_t)(t + 1) * blk + (size_t)crow * kHid + 16 * j + cu;
+      __hip_atomic_store((gu32*)(nt.H + o), __float_as_uint(h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // write-through
+      nt.C[o] = c;
+      if (nt.save && t >= a.burn) {
+        float* grow = nt.gx + ((size_t)t * a.Bn + crow) * kGates + 16 * j + cu;
+        grow[0] = gi, grow[kHid] = gf, grow[2 * kHid] = gg, grow[3 * kHid] = go;
+      }
+    }
+    if (t + 1 == a.T) break;
+    // grid barrier of the chain: every storing wave drains its stores, then ONE lane signals and polls
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (cell) gx_fetch(t + 1);  // in flight across the wait
+    if (tid == 0) {
+      gu32* cnt = (gu32*)(bar + t);
+      __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      bool ok = true;
+      for (unsigned spins = 0; __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)kChainBlocks;) {
+        __builtin_amdgcn_s_sleep(1);
+        if (++spins > kRecSpinLimit || __hip_atomic_load((gu32*)a.tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+          __hip_atomic_store((gu32*)a.tmo, (unsigned)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          ok = false;
+          break;
+        }
+      }
+      alive = ok ? 1 : 0;
+    }
+    __syncthreads();
+    if (!alive) return;
+  }
+}
+
 // ---- persistent BPTT: XCD-local chains (batches of up to 128 rows) ---------------------------------------------
 // The seq_len + n backward steps of the online net in ONE launch (2 launches per step before r2: a split-K GEMM for
 // dh = dgates_{t+1} x W_hh and the cell kernel; launch gaps alone cost ~1 ms per learner step).  chain = tile of 16
@@ -662,6 +802,9 @@ struct rela_r2d2_learner : LearnerCore {
   unsigned* rec_chain_bar = nullptr;                                  // lstm_rec_chain: [8 chains][Tpad]
   bool rec_chains_fit = true;                                         // its 256 blocks are resident at once (checked at create)
   bool rec_persist = true;
+  // rela_r2d2_learner_set_rec_wide: batches of 65 .. 128 rows run the forward recurrence on lstm_rec_chain32;
+  // rec_wide_fit: its 256 blocks (66,560 B of dynamic LDS each) are resident at once (checked at create)
+  bool rec_wide = false, rec_wide_fit = false;
   // 1: the target net's conv trunk (no gradient, activations never read back) and the three large GEMMs of the LSTM's
   //    input side (gate GEMM of both nets, its data and weight gradients) on split-bf16 MFMA (gemm_bf16s.h)
   int precision = 0;
@@ -982,7 +1125,8 @@ int forward_both(rela_r2d2_learner* l, int Bn, const uint8_t* obs, const float* 
   if (rc != RELA_OK) return rc;
   rc = forward_pre(l, 0, Bn, obs, h0, c0, s);
   if (rc != RELA_OK) return rc;
-  if (l->rec_persist && l->rec_chains_fit && Bn <= 64) {
+  const bool wide = l->rec_persist && l->rec_wide && l->rec_wide_fit && Bn > 64 && Bn <= 4 * kWideRows;
+  if ((l->rec_persist && l->rec_chains_fit && Bn <= 64) || wide) {
     // arrival counters of this launch: [8 chains][Tpad] (the timeout word rec_bar[0] is sticky until ..._check)
     const int Tpad = (T + 3) / 4 * 4;
     RELA_HIP(hipMemsetAsync(l->rec_chain_bar, 0, sizeof(unsigned) * (size_t)(8 * Tpad), s));
@@ -992,9 +1136,15 @@ int forward_both(rela_r2d2_learner* l, int Bn, const uint8_t* obs, const float* 
       ca.net[w].bar = nullptr, ca.net[w].save = w == 0 ? 1 : 0;
     }
     ca.term = term, ca.tmo = l->rec_bar, ca.bar = l->rec_chain_bar, ca.T = T, ca.Tpad = Tpad, ca.Bn = Bn, ca.burn = burn;
-    ProfScope prof("learner_lstm_rec_persist", s);
-    note_launch("lstm_rec_chain");
-    hipLaunchKernelGGL(lstm_rec_chain<true>, dim3(8 * kChainBlocks), dim3(kRecThreads), 0, s, ca);
+    if (wide) {  // 32 rows per chain: the same grid, arguments and counters
+      ProfScope prof("learner_lstm_rec_wide", s);
+      note_launch("lstm_rec_chain32");
+      hipLaunchKernelGGL(lstm_rec_chain32, dim3(8 * kChainBlocks), dim3(kRecThreads), kWideLdsBytes, s, ca);
+    } else {
+      ProfScope prof("learner_lstm_rec_persist", s);
+      note_launch("lstm_rec_chain");
+      hipLaunchKernelGGL(lstm_rec_chain<true>, dim3(8 * kChainBlocks), dim3(kRecThreads), 0, s, ca);
+    }
     RELA_LAUNCH_CHECK();
   } else {
     rc = forward_rec_steps(l, 1, Bn, term, false, s);
@@ -1077,6 +1227,14 @@ int build_learner(rela_r2d2_learner* l, int num_action, int max_batch, int multi
                       "grids (%d, %d): using the per-step launches\n", cus, occ_c, occ_d, 8 * kChainBlocks, 8 * kBpttBlocks);
       l->rec_chains_fit = false;
     }
+    // lstm_rec_chain32 (set_rec_wide): the same grid with 66,560 B of dynamic LDS per block, over the static limit, so
+    // the limit is raised first; where that fails or the grid would not be resident the option has no effect
+    int occ_w = 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_rec_chain32), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)kWideLdsBytes) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_w, lstm_rec_chain32, kRecThreads, kWideLdsBytes) != hipSuccess)
+      occ_w = 0, (void)hipGetLastError();
+    l->rec_wide_fit = room(occ_w) >= 8 * kChainBlocks;
   }
   if (int rc = m.alloc(&l->ha, rowsTr * 32, false)) return rc;
   if (int rc = m.alloc(&l->q_on, rowsTr * A, false)) return rc;
@@ -1248,6 +1406,12 @@ extern "C" int rela_r2d2_learner_set_lstm_in_rec3(rela_r2d2_learner* l, int on) 
     if (int rc = l->mem.alloc(&l->wTrec3, (size_t)kFeat * (kGates / 64) * kLstmRec3Bytes, false)) return rc;
   }
   l->lstm_in_rec3 = on != 0;  // (the weight records are made by the next rela_r2d2_learner_loss)
+  return RELA_OK;
+}
+
+extern "C" int rela_r2d2_learner_set_rec_wide(rela_r2d2_learner* l, int on) {
+  RELA_CHECK(l && (on == 0 || on == 1), RELA_EINVAL, "rela_r2d2_learner_set_rec_wide: needs a learner and on = 0 or 1");
+  l->rec_wide = on != 0;  // (forward_both: lstm_rec_chain32 for 65 .. 128 rows where its grid fits)
   return RELA_OK;
 }
 

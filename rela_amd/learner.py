@@ -398,6 +398,13 @@ class HipR2D2Learner(_HipLearner):
         (default): the mode's own kernels.  From the next step on.  rela_r2d2_learner_set_lstm_in_rec3."""
         self._call("set_lstm_in_rec3", int(bool(on)))
 
+    def set_rec_wide(self, on):
+        """True: a batch of 65 .. 128 rows runs the forward recurrence of both nets as one persistent launch
+        (lstm_rec_chain32, csrc/learner_r2d2.hip: chains of 32 batch rows) instead of per-step launches; False (default):
+        the per-step launches.  Other batch sizes are not affected.  From the next step on.
+        rela_r2d2_learner_set_rec_wide."""
+        self._call("set_rec_wide", int(bool(on)))
+
     def check(self):
         """Synchronises and raises if a grid barrier of the persistent recurrent kernels gave up since the last check."""
         self._call("check", self._stream())

@@ -34,6 +34,7 @@ LEARNER_PRECISIONS = ("f32", "bf16x2", "f32x3", "f32x3_bwd")
 LEARNER_DGRADS = ("mode", "x3")  # --learner_dgrad
 LEARNER_WGRADS = ("mode", "x3", "x3_all")  # --learner_wgrad
 LEARNER_LSTM_INS = ("mode", "rec3")  # --learner_lstm_in
+LEARNER_RECS = ("mode", "wide")  # --learner_rec
 
 
 def parse_args(argv=None):
@@ -92,6 +93,9 @@ def parse_args(argv=None):
     p.add_argument("--learner_lstm_in", type=str, default="mode", choices=LEARNER_LSTM_INS,
                    help="the LSTM's input-side backward GEMMs of the HIP R2D2 learner step: mode = what --learner_precision "
                         "runs; rec3 = three-part record GEMMs, f32 accuracy (set_lstm_in_rec3 of rela_amd/learner.py)")
+    p.add_argument("--learner_rec", type=str, default="mode", choices=LEARNER_RECS,
+                   help="the forward recurrence of the HIP R2D2 learner step at 65 .. 128 batch rows: mode = per-step "
+                        "launches; wide = one persistent launch, lstm_rec_chain32 (set_rec_wide of rela_amd/learner.py)")
     p.add_argument("--learner_wgrad", type=str, default="mode", choices=LEARNER_WGRADS,
                    help="conv1 / conv2 weight gradients of the HIP learner step: mode = what --learner_precision runs; x3 = "
                         "three-part bf16 space-to-depth kernels, f32 accuracy (set_wgrad_x3 of rela_amd/learner.py); x3_all = "
@@ -222,6 +226,19 @@ def learner_lstm_in_rec3(args):
     return choice == "rec3"
 
 
+def learner_rec_wide(args):
+    """--learner_rec as the R2D2 learner's set_rec_wide argument, checked against --algo and --hip_learner."""
+    choice = getattr(args, "learner_rec", "mode")
+    if choice not in LEARNER_RECS:
+        raise SystemExit("--learner_rec must be one of %s" % ", ".join(LEARNER_RECS))
+    if choice == "wide" and not getattr(args, "hip_learner", 1):
+        raise SystemExit("--learner_rec wide needs the HIP learner step (--hip_learner 1): the PyTorch autograd step has "
+                         "no such kernel")
+    if choice == "wide" and args.algo != "r2d2":
+        raise SystemExit("--learner_rec wide is the R2D2 learner's option (--algo r2d2): the Ape-X net has no LSTM")
+    return choice == "wide"
+
+
 def train(args, on_epoch=None):
     if args.algo not in ("apex", "r2d2"):
         raise SystemExit("--algo must be apex or r2d2")
@@ -229,6 +246,7 @@ def train(args, on_epoch=None):
     dgrad_x3 = learner_dgrad_x3(args)
     wgrad_x3 = learner_wgrad_x3(args)
     lstm_in_rec3 = learner_lstm_in_rec3(args)
+    rec_wide = learner_rec_wide(args)
     rules = UpdateRules(args)
     torch.manual_seed(args.seed + 2)
     torch.cuda.manual_seed(args.seed + 3)
@@ -263,6 +281,8 @@ def train(args, on_epoch=None):
             learner.set_wgrad3_x3(True)
         if lstm_in_rec3:
             learner.set_lstm_in_rec3(True)
+        if rec_wide:
+            learner.set_rec_wide(True)
 
     # create eval locker here, as upstream (main.py:115-116): replicas on the host, device string "cpu"
     eval_locker = rela.ModelLocker([type(agent).clone(agent, "cpu")], "cpu")
@@ -465,6 +485,8 @@ def _multi_worker(rank, world, args, port, results):
             learner.set_wgrad3_x3(True)
         if learner_lstm_in_rec3(args):
             learner.set_lstm_in_rec3(True)
+        if learner_rec_wide(args):
+            learner.set_rec_wide(True)
         # scheduled exchange: command words (a host synchronisation on every rank) only with the weight publish every
         # actor_sync_freq steps; the sample / update_priority pairs in between follow the announced cycle
         if native:  # partitions and flat buffers mapped through HIP IPC: rows and weights never enter a collective
@@ -622,6 +644,7 @@ def train_multi(args):
     learner_dgrad_x3(args)
     learner_wgrad_x3(args)
     learner_lstm_in_rec3(args)
+    learner_rec_wide(args)
     UpdateRules(args, quiet=True)  # (likewise; the learner's rank builds and announces its own)
     if args.algo == "r2d2" and os.environ.get("RELA_REPLAY_DEDUP"):
         # the learner process would read the partitions' rows through IPC, and a sequence partition with de-duplicated

@@ -8,6 +8,10 @@
          median [min .. max] of both per leg (profiles/lstm_in_rec3_ab.md)
   WGRAD3_AB=7 ITERS=4 PRECISION=f32x3_bwd DGRAD=x3 WGRAD=x3 LSTM_IN=rec3 python tools/time_r2d2_learner.py
       -> the same for wgrad3_x3 and the learner_wgrad_conv3 scope (profiles/wgrad3_x3_ab.md)
+  REC_WIDE_AB=5 ITERS=10 B=128 python tools/time_r2d2_learner.py
+      -> the same for rec_wide and the forward recurrence's scopes (per-step: learner_lstm_rec_fwd + learner_lstm_cell, the
+         two zeroing launches have no scope; wide: learner_lstm_rec_wide), after three legs of the same learner at B = 64
+         on lstm_rec_chain (profiles/rec_wide_ab.md)
 """
 import ctypes as C
 import json
@@ -86,6 +90,22 @@ if os.environ.get("LSTM_IN_AB"):
     alternate(int(os.environ["LSTM_IN_AB"]), "lstm_in_rec3", learner.set_lstm_in_rec3, LSTM_IN_SCOPES, "lstm input backward")
 if os.environ.get("WGRAD3_AB"):
     alternate(int(os.environ["WGRAD3_AB"]), "wgrad3_x3", learner.set_wgrad3_x3, ("learner_wgrad_conv3",), "conv3 weight gradient")
+
+if os.environ.get("REC_WIDE_AB"):  # (B=128: the option concerns 65 .. 128 rows)
+    if B > 64:  # for comparison, the same learner's step at 64 rows on lstm_rec_chain
+        wide_batch = (batch, weight)
+        batch, weight = _random_batch(np.random.default_rng(6), A, 64, SEQ, BURN, N, "cuda:0")
+        for _ in range(3):
+            learner.step(batch, weight)
+        learner.check()
+        for leg in range(3):
+            step_ms, _ = window(False)
+            _, prof = window(True)
+            print("B 64 leg %d step %.3f ms  learner_lstm_rec_persist %.3f ms" % (leg, step_ms, prof.get("learner_lstm_rec_persist", 0.0)),
+                  flush=True)
+        batch, weight = wide_batch
+    alternate(int(os.environ["REC_WIDE_AB"]), "rec_wide", learner.set_rec_wide,
+              ("learner_lstm_rec_fwd", "learner_lstm_cell", "learner_lstm_rec_wide"), "forward recurrence")
 
 for _ in range(2):
     learner.step(batch, weight)
