@@ -183,6 +183,14 @@ int rela_replay_write_rows_gather(rela_replay* r, int first_slot, int count,
  * rela_replay_write_rows; the commit on the same stream orders the rows before the block becomes visible.        */
 int rela_replay_direct_rows(rela_replay* r, int first_slot, int count, int field, void** base_dev, int* ring,
                             int64_t* row_bytes, void* stream);
+/* The same for the block's small fields and its weights, for a producer whose own kernel on `stream` has the priorities
+ * and finishes the block in the same launch: base_dev[k] / row_bytes[k] of fields[k] (plain fields of at most 256 bytes
+ * per row), the ring length, the weight ring (slot sh at weights_dev[sh]) and alpha; `stream` gets the same waits.  The
+ * producer stores pow(priority, alpha) as the append does -- into the ring and, in row order, into a buffer of its own
+ * -- and commits with rela_replay_commit_add_weighted.  A replay in the decoupled insert form sets *weights_dev = NULL
+ * and does nothing else: the caller then inserts with write_rows / commit_add.                                      */
+int rela_replay_direct_small(rela_replay* r, int first_slot, int count, const int* fields, int nfields, void** base_dev,
+                             int64_t* row_bytes, int* ring, float** weights_dev, float* alpha, void* stream);
 int rela_replay_commit_add(rela_replay* r, int first_slot, int n, const float* priority_dev,
                            void* stream);
 /* The same commit for n = G*group_rows slots that stand for G consecutive reference blocks of
@@ -190,6 +198,12 @@ int rela_replay_commit_add(rela_replay* r, int first_slot, int n, const float* p
  * `sum_ +=` of :58-66,73 are taken per group, in order, exactly as G separate appends would.   */
 int rela_replay_commit_add_grouped(rela_replay* r, int first_slot, int n, int group_rows,
                                    const float* priority_dev, void* stream);
+/* The grouped commit of a block whose weights the producer has written (rela_replay_direct_small): weights_dev holds
+ * them in row order, and only the ordered sums are left, on the replay's stream behind an event of `stream`.
+ * done_event (a hipEvent_t, may be NULL) is recorded behind the read of weights_dev: the producer waits for it before
+ * it writes that buffer again; NULL: `stream` waits for the read here.  In-order insert form only (RELA_ESTATE).   */
+int rela_replay_commit_add_weighted(rela_replay* r, int first_slot, int n, int group_rows, const float* weights_dev,
+                                    void* done_event, void* stream);
 
 /* Releases a reservation whose producer failed between begin and commit (no reference counterpart:
  * there an exception on an actor thread ends the process, rela/context.h:39-46).  The n slots are
@@ -273,6 +287,9 @@ int rela_replay_debug_state(rela_replay* r, rela_replay_state* out, int32_t* ids
 int rela_replay_debug_weights(rela_replay* r, float* weights_host, uint8_t* evicted_host);
 /* raw rows [slot, slot+count) of one field (physical slots, no wrap) -> host; synchronises */
 int rela_replay_debug_read_rows(rela_replay* r, int field, int slot, int count, void* rows_host);
+/* the eviction list: entries whose sample may still read the slots it evicted, events parked for reuse, and the
+ * waits the last writer of rows was given (write_rows, direct_rows, direct_small); any pointer may be NULL */
+int rela_replay_debug_evictions(rela_replay* r, int* pending, int* pooled, int* last_waits);
 
 /* The scan primitive on its own: for nt targets (f64, host, ascending not required) over the
  * logical range [head, head+size) of a device weight ring, the first index whose
@@ -559,12 +576,14 @@ int64_t rela_apex_actor_num_act(const rela_apex_actor* a); /* numAct()  dqn_acto
  * on = 1 (default): reuse both; 2: only the one of next_obs; 0: always recompute, i.e. the reference's
  * 4 forwards per step */
 int rela_apex_actor_set_reuse(rela_apex_actor* a, int on);
-/* on = 1 (default): where the target net's forward of post_step runs conv12_s3 (f32x3, 512 rows and up) and the
+/* on = 1: where the target net's forward of post_step runs conv12_s3 (f32x3, 512 rows and up) and the
  * shard enters the replay as one block of plain rows, that forward stores next_obs into the block's rows itself
  * (rela_replay_direct_rows) and the insert copies one field less; 2: under the same conditions that forward also
  * passes obs, the frames acted on n ticks ago, through to the block's obs rows (conv12_s3_copy2), and the insert
- * copies no frame rows at all; 0: every field is copied by the insert.  The replay's contents are the same bytes in
- * every mode.                                                                                                   */
+ * copies no frame rows at all; 3 (default): as 2, and where that forward stored both fields the TD kernel stores the
+ * block's eight small fields and its weights (rela_replay_direct_small), so that the insert is one launch on the
+ * replay's stream (rela_replay_commit_add_weighted) for which the actor's stream does not wait; 0: every field is
+ * copied by the insert.  The replay's contents are the same bytes in every mode.                                */
 int rela_apex_actor_set_fused_insert(rela_apex_actor* a, int on);
 /* Invertible value rescaling of the priority's TD target (R2D2 as published, Kapturowski et al. 2019; the reference
  * leaves it out and clips rewards in its env instead, so ApexAgent.td_err apex.py:30-45 has no such step):

@@ -150,6 +150,8 @@ _sig("rela_replay_begin_add", i32, [vp, i32, i32, P(i32)])
 _sig("rela_replay_write_rows", i32, [vp, i32, i32, i32, P(vp), vp])
 _sig("rela_replay_write_rows_gather", i32, [vp, i32, i32, vp, P(vp), P(vp), vp])
 _sig("rela_replay_direct_rows", i32, [vp, i32, i32, i32, P(vp), P(i32), P(i64), vp])
+_sig("rela_replay_direct_small", i32, [vp, i32, i32, P(i32), i32, P(vp), P(i64), P(i32), P(vp), P(f32), vp])
+_sig("rela_replay_commit_add_weighted", i32, [vp, i32, i32, i32, vp, vp, vp])
 _sig("rela_replay_commit_add", i32, [vp, i32, i32, vp, vp])
 _sig("rela_replay_commit_add_grouped", i32, [vp, i32, i32, i32, vp, vp])
 _sig("rela_replay_abort_add", i32, [vp, i32, i32])
@@ -167,6 +169,7 @@ _sig("rela_replay_num_add", i64, [vp])
 _sig("rela_replay_debug_state", i32, [vp, P(ReplayState), vp, vp, vp])
 _sig("rela_replay_debug_weights", i32, [vp, vp, vp])
 _sig("rela_replay_debug_read_rows", i32, [vp, i32, i32, i32, vp])
+_sig("rela_replay_debug_evictions", i32, [vp, P(i32), P(i32), P(i32)])
 _sig("rela_seqscan_search", i32, [vp, i64, i64, i64, vp, i32, vp, vp, vp, P(f64), vp])
 _sig("rela_debug_pow", i32, [vp, i32, f32, vp, vp])
 _sig("rela_debug_value_rescale", i32, [i32, vp, f32, vp, vp, vp])

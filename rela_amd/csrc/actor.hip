@@ -23,11 +23,53 @@ struct rela_apex_actor : ActorShardBase {
   void* ws = nullptr;
   int64_t ws_bytes = 0;
   int64_t key_tick = -1;  // de-duplication: tick of the last keyframe (all planes stored)
+  // fused insert, mode 3: the block's weights in row order, written by td_kernel_insert on the actor's stream and added up
+  // by the replay's replay_append_sums on ITS stream.  Two buffers taken in turn, each with the event the commit records
+  // behind that read: the tick that writes a buffer again waits for the event of two ticks ago, which has long
+  // completed, so the actor's stream never stalls on the replay stream.  Nothing else reads these buffers: their only
+  // other holder is the one replay_append_sums launch rela_replay_commit_add_weighted is given the pointer for.
+  float* wtmp[2] = {nullptr, nullptr};  // [R] each; a shard with a replay has both buffers and both events from create on
+  hipEvent_t wtmp_done[2] = {nullptr, nullptr};
+  bool wtmp_used[2] = {false, false};
+  int wtmp_next = 0;
 };
 
 namespace {
 constexpr int kTickWin = 64;  // de-duplication: ticks tick_seq remembers
+
+// Fused insert, mode 3: the priorities of post_step from the TD kernel that also stores the eight small fields of the
+// reserved block [slot, slot + R) and its weights (td_kernel_insert; rela_replay_direct_small).  small[f]: the source rows
+// of replay fields 2..9.  *wk = the weight buffer the launch writes, for the commit -- set as soon as the kernel may have
+// been queued, also where an error is returned; -1 with RELA_OK = the replay does not offer the path (decoupled insert
+// form) and nothing was launched: the caller runs td_from_q and inserts as usual.
+int td_with_insert(rela_apex_actor* a, int slot, const float* q_online_t, const float* q_online_n, const float* q_target,
+                   const float* legal_n, const int64_t* act_t, const void* const small[kTdInsertFields], hipStream_t s,
+                   int* wk) {
+  *wk = -1;
+  static const int fields[kTdInsertFields] = {2, 3, 4, 5, 6, 7, 8, 9};
+  const int64_t want[kTdInsertFields] = {4, 4, 4 * a->A, 4 * a->A, 8, 4, 1, 4};
+  TdInsert ins{};
+  void* bases[kTdInsertFields] = {};
+  int64_t rb[kTdInsertFields] = {};
+  int rc = rela_replay_direct_small(a->replay, slot, a->R, fields, kTdInsertFields, bases, rb, &ins.ring, &ins.w, &ins.alpha, s);
+  if (rc != RELA_OK || !ins.w) return rc;
+  for (int f = 0; f < kTdInsertFields; ++f) {
+    RELA_CHECK(rb[f] == want[f], RELA_EINVAL, "rela_apex_actor_post_step: the replay's field %d has rows of %lld bytes, the shard's %lld",
+               fields[f], (long long)rb[f], (long long)want[f]);
+    ins.src[f] = static_cast<const uint8_t*>(small[f]);
+    ins.dst[f] = static_cast<uint8_t*>(bases[f]);
+    ins.row_bytes[f] = (int32_t)rb[f];
+  }
+  ins.nfields = kTdInsertFields;
+  ins.first_slot = slot;
+  const int k = a->wtmp_next;
+  if (a->wtmp_used[k]) RELA_HIP(hipStreamWaitEvent(s, a->wtmp_done[k], 0));  // the sums of two inserts ago read it
+  ins.wtmp = a->wtmp[k];
+  *wk = k;  // from here on the kernel may be queued, whatever is returned
+  return td_from_q_insert(a->R, a->A, a->K, q_online_t, q_online_n, q_target, legal_n, act_t, a->out_r, a->out_b, a->gamma_n,
+                          a->vr_eps, a->prio, ins, s);
 }
+}  // namespace
 
 extern "C" int rela_apex_actor_create(rela_apex_actor** out, int rows, int group_rows, int num_action, int multi_step,
                                       float gamma, rela_replay* replay, uint64_t seed, int device) {
@@ -51,6 +93,10 @@ extern "C" int rela_apex_actor_create(rela_apex_actor** out, int rows, int group
   rc = shard_alloc_ring(a);
   if (rc != RELA_OK) return rc;
   RELA_ALLOC(a->prio, (size_t)rows * sizeof(float));
+  for (int k = 0; k < 2 && replay; ++k) {
+    RELA_ALLOC(a->wtmp[k], (size_t)rows * sizeof(float));
+    RELA_HIP(hipEventCreateWithFlags(&a->wtmp_done[k], hipEventDisableTiming));
+  }
   a->ws_bytes = rela_ffnet_workspace_bytes(nullptr, rows);
   RELA_HIP(hipMalloc(&a->ws, (size_t)a->ws_bytes));
   *out = a;
@@ -64,6 +110,10 @@ extern "C" void rela_apex_actor_destroy(rela_apex_actor* a) {
   shard_free(a);
   (void)hipFree(a->prio);
   (void)hipFree(a->ws);
+  for (int k = 0; k < 2; ++k) {
+    (void)hipFree(a->wtmp[k]);
+    if (a->wtmp_done[k]) (void)hipEventDestroy(a->wtmp_done[k]);
+  }
   delete a;
 }
 
@@ -87,7 +137,8 @@ extern "C" int rela_apex_actor_set_reuse(rela_apex_actor* a, int on) {
   return shard_set_reuse(a, on, "rela_apex_actor_set_reuse");
 }
 extern "C" int rela_apex_actor_set_fused_insert(rela_apex_actor* a, int on) {
-  RELA_CHECK(a && on >= 0 && on <= 2, RELA_EINVAL, "rela_apex_actor_set_fused_insert: 0 (off), 1 (next_obs) or 2 (next_obs and obs)");
+  RELA_CHECK(a && on >= 0 && on <= 3, RELA_EINVAL,
+             "rela_apex_actor_set_fused_insert: 0 (off), 1 (next_obs), 2 (next_obs and obs) or 3 (those, small fields and weights)");
   a->fused_insert = on;
   return RELA_OK;
 }
@@ -237,7 +288,7 @@ extern "C" int rela_apex_actor_post_step(rela_apex_actor* a, const float* reward
       rc = RELA_EINVAL;
     }
     FrameRows fr{static_cast<uint8_t*>(base), fused_slot, rows_ring};
-    if (rc == RELA_OK && a->fused_insert == 2) {
+    if (rc == RELA_OK && a->fused_insert >= 2) {
       void* base0 = nullptr;
       int ring0 = 0;
       rc = rela_replay_direct_rows(a->replay, fused_slot, a->R, 0, &base0, &ring0, &row_bytes, s);
@@ -256,15 +307,28 @@ extern "C" int rela_apex_actor_post_step(rela_apex_actor* a, const float* reward
     rc = rela_ffnet_forward(target, a->R, obs_n, legal_n, a->q + 3 * QA, a->ws, a->ws_bytes, s);  // :42
   }
   const int64_t* act_t = a->act + (size_t)first * a->R;
-  if (rc == RELA_OK)
+  // FFTransition rows (types.h:18-51): obs{s,eps,legal_move}, next_obs{...}, action{a}, reward, terminal, bootstrap
+  const void* rows[10] = {obs_t, obs_n, eps_t, eps_n, legal_t, legal_n, act_t, a->out_r, a->out_t, a->out_b};
+  // fused_insert == 3, where the forward above stored both frame fields (fused_copied == 2): the TD kernel finishes the
+  // block.  It has every row's priority in a register and the eight small fields are a few bytes per row from buffers
+  // already on `s`, so it stores those into the block's rows and the row's weight pow(priority, alpha) into the replay's
+  // weight ring (td_kernel_insert, the arithmetic and stores of replay_append_pow); the insert is then no copy stream
+  // hand-over, no replay_scatter_small and no replay_append_pow, and the commit is replay_append_sums alone behind one
+  // event -- for which `s` does not wait (wtmp, above).  The replay in its decoupled form does not offer this (wk < 0).
+  int wk = -1;
+  if (rc == RELA_OK && a->fused_insert == 3 && fused_copied == 2)
+    rc = td_with_insert(a, fused_slot, q_online_t, q_online_n, a->q + 3 * QA, legal_n, act_t, rows + 2, s, &wk);
+  if (rc == RELA_OK && wk < 0)
     rc = td_from_q(a->R, a->A, a->K, q_online_t, q_online_n, a->q + 3 * QA, legal_n, act_t, a->out_r, a->out_b, a->gamma_n,
                    a->vr_eps, nullptr, a->prio, s);
   if (rc != RELA_OK) {
-    if (fused_slot >= 0) (void)rela_replay_abort_add(a->replay, fused_slot, a->R);
+    if (fused_slot >= 0) {
+      // (abort_add zeroes the block's weights on the replay's stream: not while td_kernel_insert may still store them)
+      if (wk >= 0) (void)hipStreamSynchronize(s);
+      (void)rela_replay_abort_add(a->replay, fused_slot, a->R);
+    }
     return rc;
   }
-  // FFTransition rows (types.h:18-51): obs{s,eps,legal_move}, next_obs{...}, action{a}, reward, terminal, bootstrap
-  const void* rows[10] = {obs_t, obs_n, eps_t, eps_n, legal_t, legal_n, act_t, a->out_r, a->out_t, a->out_b};
   if (a->dd_ups > 0) {
     rows[0] = a->ref_hist + (size_t)first * a->R * a->dd_ups;
     rows[1] = a->ref_hist + (size_t)last * a->R * a->dd_ups;
@@ -290,8 +354,18 @@ extern "C" int rela_apex_actor_post_step(rela_apex_actor* a, const float* reward
       if (rc != RELA_OK) break;
     }
     if (a->dd_ups > 0) (void)rela_replay_set_block_min_unit(a->replay, slot, cnt, dd_min_seq);
-    rc = rela_replay_write_rows(a->replay, slot, 0, cnt, prow, s);
-    if (rc == RELA_OK) rc = rela_replay_commit_add_grouped(a->replay, slot, cnt, a->K, a->prio + off, s);
+    if (wk >= 0) {  // (mode 3: the rows and the weights are written; cnt == R)
+      rc = rela_replay_commit_add_weighted(a->replay, slot, cnt, a->K, a->wtmp[wk], a->wtmp_done[wk], s);
+      if (rc == RELA_OK) {
+        a->wtmp_used[wk] = true;
+        a->wtmp_next = wk ^ 1;
+      } else {
+        (void)hipStreamSynchronize(s);  // (as above: abort_add zeroes weights td_kernel_insert may still be storing)
+      }
+    } else {
+      rc = rela_replay_write_rows(a->replay, slot, 0, cnt, prow, s);
+      if (rc == RELA_OK) rc = rela_replay_commit_add_grouped(a->replay, slot, cnt, a->K, a->prio + off, s);
+    }
     if (rc != RELA_OK) {  // release the reservation so later blocks of other producers can still commit
       (void)rela_replay_abort_add(a->replay, slot, cnt);
       break;

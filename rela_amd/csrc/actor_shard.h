@@ -41,8 +41,8 @@ struct ActorShardBase {
   int q_slot = -1;     // slot of the last act()
   int reuse_mode = 1;  // 0: recompute everything, 1: reuse both act() forwards, 2: only the one of s_t+n
   // Ape-X shard (*_set_fused_insert): the target forward stores into the reserved replay rows itself: 1 next_obs, 2 next_obs
-  // and obs, 0 neither
-  int fused_insert = 2;
+  // and obs, 0 neither; 3 as 2, and the TD kernel stores the block's small fields and weights (td_kernel_insert)
+  int fused_insert = 3;
   float vr_eps = 0.f;  // value rescaling of the priority's TD target (*_set_value_rescale; value_rescale.h), 0 = off
   // sliding-stack and screen input of the observation slot
   uint8_t* restart = nullptr;       // [R] *_slide_stacks / *_screens_to_stacks: 1 = the row's stack restarts with its new plane

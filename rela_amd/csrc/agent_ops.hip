@@ -8,7 +8,10 @@
 // All three are tiny (K <= a few thousand rows of <= 18 floats): one workgroup each, so the
 // batch-global q.min() of greedy_act (apex.py:51) needs no second launch.
 // HBM-bound in principle, launch-latency-bound in practice.
+#include <type_traits>
+
 #include "common.h"
+#include "pow_aten.h"
 #include "prof.h"
 #include "value_rescale.h"
 
@@ -141,12 +144,22 @@ __global__ __launch_bounds__(kT) void act_kernel(int n, int A, int group, const 
   }
 }
 
+// kInsert: the launch is for a producer that has reserved the rows' block in a replay (TdInsert, common.h; the Ape-X
+// shard's fused insert, mode 3; census name td_kernel_insert).  The priorities are the same arithmetic in the same order
+// -- there is one copy of it -- and for row i, slot sh = (first_slot + i) mod ring, the kernel stores besides
+//   * the row's small fields into the replay's rows (replay.hip: what replay_scatter_small copies), and
+//   * the row's weight: replay_append_pow's arithmetic and stores -- a workgroup is one reference block here as there
+//     (g = group, gi = blockIdx.x, the block's length r1 - r0 = min(g, n - gi * g)), so pow_aten gets the same arguments.
+// What stays for the replay's stream is replay_append_sums over wtmp.  td_kernel<false> takes an empty argument in its place.
+struct TdNoInsert {};
+template <bool kInsert>
 __global__ __launch_bounds__(kT) void td_kernel(int n, int A, int group, const float* __restrict__ q,
                                                 const float* __restrict__ qno, const float* __restrict__ qnt,
                                                 const float* __restrict__ nlegal, const int64_t* __restrict__ action,
                                                 const float* __restrict__ reward, const float* __restrict__ bootstrap,
                                                 float gamma_n, float vr_eps, float* __restrict__ td,
-                                                float* __restrict__ prio) {
+                                                float* __restrict__ prio,
+                                                std::conditional_t<kInsert, TdInsert, TdNoInsert> ins) {
   __shared__ float red[kT];
   const int r0 = blockIdx.x * group;
   const int r1 = min(n, r0 + group);
@@ -164,6 +177,14 @@ __global__ __launch_bounds__(kT) void td_kernel(int n, int A, int group, const f
     const float e = __fsub_rn(tgt, qa);                    // :45
     if (td) td[i] = e;
     if (prio) prio[i] = fabsf(e);                          // :78
+    if constexpr (kInsert) {
+      const float v = pow_aten(fabsf(e), ins.alpha, i - r0, r1 - r0);  // prioritized_replay.h:188
+      const int64_t sh = ((int64_t)ins.first_slot + i) % ins.ring;
+      ins.wtmp[i] = v;
+      ins.w[sh] = v;
+      for (int f = 0; f < ins.nfields; ++f)
+        copy_small(ins.dst[f] + sh * ins.row_bytes[f], ins.src[f] + (int64_t)i * ins.row_bytes[f], ins.row_bytes[f]);
+    }
   }
 }
 
@@ -211,10 +232,35 @@ int rela_amd::td_from_q(int n, int num_action, int group_rows, const float* q_de
   const int group = group_rows > 0 ? group_rows : n;
   const int threads = group >= 512 ? kT : 256;
   ProfScope prof("td_kernel", stream);
-  hipLaunchKernelGGL(td_kernel, dim3(ceil_div(n, group)), dim3(threads), 0, stream, n, num_action, group,
+  hipLaunchKernelGGL(td_kernel<false>, dim3(ceil_div(n, group)), dim3(threads), 0, stream, n, num_action, group,
                      q_dev, q_next_online_dev,
                      q_next_target_dev, next_legal_dev, action_dev, reward_dev, bootstrap_dev, gamma_n, vr_eps, td_err_dev,
-                     priority_dev);
+                     priority_dev, TdNoInsert{});
+  RELA_LAUNCH_CHECK();
+  return RELA_OK;
+}
+
+// td_from_q where the same launch inserts (td_kernel<true>; TdInsert, common.h)
+int rela_amd::td_from_q_insert(int n, int num_action, int group_rows, const float* q_dev, const float* q_next_online_dev,
+                               const float* q_next_target_dev, const float* next_legal_dev, const int64_t* action_dev,
+                               const float* reward_dev, const float* bootstrap_dev, float gamma_n, float vr_eps,
+                               float* priority_dev, const TdInsert& ins, hipStream_t stream) {
+  RELA_CHECK(n >= 1 && num_action >= 1 && group_rows >= 0 && q_dev && q_next_online_dev && q_next_target_dev &&
+                 next_legal_dev && action_dev && reward_dev && bootstrap_dev && priority_dev,
+             RELA_EINVAL, "td_from_q_insert: bad arguments");
+  RELA_CHECK(ins.nfields >= 0 && ins.nfields <= kTdInsertFields && ins.ring >= n && ins.first_slot >= 0 &&
+                 ins.first_slot < ins.ring && ins.w && ins.wtmp,
+             RELA_EINVAL, "td_from_q_insert: bad block (%d rows from slot %d in a ring of %d, %d fields)", n, ins.first_slot,
+             ins.ring, ins.nfields);
+  for (int f = 0; f < ins.nfields; ++f)
+    RELA_CHECK(ins.src[f] && ins.dst[f] && ins.row_bytes[f] > 0, RELA_EINVAL, "td_from_q_insert: field %d of the block", f);
+  const int group = group_rows > 0 ? group_rows : n;
+  const int threads = group >= 512 ? kT : 256;
+  ProfScope prof("td_kernel_insert", stream);
+  note_launch("td_kernel_insert");
+  hipLaunchKernelGGL(td_kernel<true>, dim3(ceil_div(n, group)), dim3(threads), 0, stream, n, num_action, group, q_dev,
+                     q_next_online_dev, q_next_target_dev, next_legal_dev, action_dev, reward_dev, bootstrap_dev, gamma_n,
+                     vr_eps, (float*)nullptr, priority_dev, ins);
   RELA_LAUNCH_CHECK();
   return RELA_OK;
 }

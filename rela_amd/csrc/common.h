@@ -164,6 +164,16 @@ inline hipError_t dev_copy2(void* d0, const void* s0, size_t n0, void* d1, const
   return hipGetLastError();
 }
 
+// One row of a small replay field (4..72 bytes), by the thread that owns the row: replay.hip's replay_scatter_small and
+// agent_ops.hip's inserting TD kernel store the same bytes with it.
+__device__ __forceinline__ void copy_small(uint8_t* __restrict__ d, const uint8_t* __restrict__ s, int nbytes) {
+  if (((nbytes | (int)(uintptr_t)d | (int)(uintptr_t)s) & 3) == 0) {
+    for (int i = 0; i < nbytes; i += 4) *reinterpret_cast<uint32_t*>(d + i) = *reinterpret_cast<const uint32_t*>(s + i);
+  } else {
+    for (int i = 0; i < nbytes; ++i) d[i] = s[i];
+  }
+}
+
 // agent_ops.hip: completes sliding frame stacks of an observation slot from the previous slot (see there)
 int slide_stacks(uint8_t* cur_slot, const uint8_t* prev_slot, const uint8_t* fresh_planes, const uint8_t* restart_dev, int rows,
                  hipStream_t s);
@@ -174,6 +184,27 @@ int td_from_q(int n, int num_action, int group_rows, const float* q_dev, const f
               const float* q_next_target_dev, const float* next_legal_dev, const int64_t* action_dev,
               const float* reward_dev, const float* bootstrap_dev, float gamma_n, float vr_eps, float* td_err_dev,
               float* priority_dev, hipStream_t stream);
+
+// agent_ops.hip: the same priorities from a kernel that also inserts (td_kernel_insert; the Ape-X shard's fused insert,
+// mode 3).  Row i of the launch is slot sh = (first_slot + i) mod ring of a block the caller has reserved in a replay
+// (rela_replay_direct_small fills the replay's half of this table): the kernel stores the row's small fields into the
+// replay's rows -- the bytes replay_scatter_small copies -- and the row's weight pow(priority, alpha) into w[sh] and
+// wtmp[i], exactly what replay_append_pow stores (pow_aten.h; group_rows = the reference block, as there).
+constexpr int kTdInsertFields = 8;
+struct TdInsert {
+  const uint8_t* src[kTdInsertFields];  // the producer's rows: row i at src[f] + i * row_bytes[f]
+  uint8_t* dst[kTdInsertFields];        // the replay's field bases: slot sh at dst[f] + sh * row_bytes[f]
+  int32_t row_bytes[kTdInsertFields];
+  int32_t nfields;
+  int32_t first_slot, ring;
+  float alpha;
+  float* w;     // [ring] the replay's weights
+  float* wtmp;  // [n] the block's weights in row order (the producer's buffer; replay_append_sums adds them up)
+};
+int td_from_q_insert(int n, int num_action, int group_rows, const float* q_dev, const float* q_next_online_dev,
+                     const float* q_next_target_dev, const float* next_legal_dev, const int64_t* action_dev,
+                     const float* reward_dev, const float* bootstrap_dev, float gamma_n, float vr_eps,
+                     float* priority_dev, const TdInsert& ins, hipStream_t stream);
 
 // atari_screen.hip: 84x84 features of staged screen pairs, and the shards' screens_to_stacks (features into
 // fresh_planes, then slide_stacks with the host restart flags; `first`: the shard's first act, every row must restart;

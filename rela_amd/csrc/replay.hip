@@ -28,7 +28,7 @@
 #include "common.h"
 #include "prof.h"
 #include "seqsum_dev.h"
-#include "sleef_powf_core.h"
+#include "pow_aten.h"
 #include "vmm_field.h"
 
 namespace rela_amd {
@@ -46,25 +46,7 @@ namespace {
 constexpr int kMaxBatch = 4096;
 constexpr int kThreads = 256;
 
-// torch::pow(tensor, exponent) as ATen's CPU kernel evaluates it for a float tensor of n elements and a
-// float exponent held in a double Scalar (rela/prioritized_replay.h:188,239,321): the vectorised loop takes
-// 2 * Vec::size() = 32 floats per iteration through SLEEF's powf (u10) with the exponent as float; the
-// remaining n % 32 elements go through the scalar lambda, std::pow(float, double) -> double pow, rounded to
-// float.  Exponent 1 is a copy.  pos = index inside that tensor, n_ref = its length.
-__device__ __forceinline__ float pow_aten(float p, float ex, int pos, int n_ref) {
-  if (ex == 1.0f) return p;
-  // exponents ATen evaluates without pow (pow_tensor_scalar_optimized_kernel); beta = 1 gives the reciprocal.
-  // (+-0.5 go through ATen's vectorised sqrt, which is not the IEEE square root in the last bit on every input:
-  // the device uses the IEEE one; no BASELINE config uses those exponents and they are not pinned.)
-  if (ex == -1.0f) return __fdiv_rn(1.0f, p);
-  if (ex == 0.5f) return __fsqrt_rn(p);
-  if (ex == 2.0f) return __fmul_rn(p, p);
-  if (ex == 3.0f) return __fmul_rn(__fmul_rn(p, p), p);
-  if (ex == -0.5f) return __fdiv_rn(1.0f, __fsqrt_rn(p));
-  if (ex == -2.0f) return __fdiv_rn(1.0f, __fmul_rn(p, p));
-  if (pos < n_ref - (n_ref & 31)) return sleef::powf_u10(p, ex);
-  return (float)pow((double)p, (double)ex);
-}
+// (torch::pow as ATen's CPU kernel evaluates it: pow_aten, pow_aten.h)
 
 // ---- add ------------------------------------------------------------------------------
 // blockAppend :57-66,73.  One workgroup: weights in parallel, then lane 0 accumulates the
@@ -213,13 +195,7 @@ struct SmallFields {
   int32_t row_bytes[kMaxSmallFields];
   int32_t n;
 };
-__device__ __forceinline__ void copy_small(uint8_t* __restrict__ d, const uint8_t* __restrict__ s, int nbytes) {
-  if (((nbytes | (int)(uintptr_t)d | (int)(uintptr_t)s) & 3) == 0) {
-    for (int i = 0; i < nbytes; i += 4) *reinterpret_cast<uint32_t*>(d + i) = *reinterpret_cast<const uint32_t*>(s + i);
-  } else {
-    for (int i = 0; i < nbytes; ++i) d[i] = s[i];
-  }
-}
+// (a row of a small field: copy_small, common.h)
 __global__ void replay_scatter_small(SmallFields t, int n, int ring, int start) {
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
@@ -614,6 +590,7 @@ struct rela_replay {
     hipEvent_t done;
   };
   std::deque<Eviction> evictions;
+  int last_eviction_waits = 0;  // waits the last writer was given (eviction_waits; rela_replay_debug_evictions)
   // slots popped by a sample that gathered NOTHING itself (out_rows_dev = NULL: the owner's half of the native
   // exchange; the learner's rela_replay_remote_gather reads the rows later, from another process, where no event of
   // this one can order it): they stay reserved -- begin_add counts them as occupied -- until the update_priority that
@@ -1004,9 +981,18 @@ static void launch_gather_dedup(const ReplaySchema& sc, const uint8_t* refs, con
 
 // (caller holds r->m) Opens a row copy of `count` slots from `start` on the copy stream: ordered after the producer's
 // queued work and after the gathers of every sample that evicted one of these slots and may still be reading it.
+static int eviction_waits(rela_replay* r, hipStream_t writer, int start, int count);
 static int copy_begin(rela_replay* r, hipStream_t producer, int start, int count) {
   RELA_HIP(hipEventRecord(r->ev_cin, producer));
   RELA_HIP(hipStreamWaitEvent(r->copy_stream, r->ev_cin, 0));
+  return eviction_waits(r, r->copy_stream, start, count);
+}
+// (caller holds r->m) Puts onto `writer`, the stream that is about to write slots [start, start + count), a wait for the
+// gathers of every sample that evicted one of them and may still be reading it -- after retiring the entries whose
+// gathers have finished (their events go back to ev_pool).  Every writer comes through here, the copy stream of
+// write_rows and a producer's own stream (rela_replay_direct_rows / _direct_small) alike, so the list stays as long as the
+// samples still in flight whichever way the inserts go.
+static int eviction_waits(rela_replay* r, hipStream_t writer, int start, int count) {
   while (!r->evictions.empty() && hipEventQuery(r->evictions.front().done) == hipSuccess) {
     r->ev_pool.push_back(r->evictions.front().done);
     r->evictions.pop_front();
@@ -1015,8 +1001,12 @@ static int copy_begin(rela_replay* r, hipStream_t producer, int start, int count
     const int d = ((b0 - a0) % r->ring + r->ring) % r->ring;  // b0 relative to a0
     return d < an || d + bn > r->ring;
   };
+  r->last_eviction_waits = 0;
   for (auto& e : r->evictions)
-    if (overlaps(start, count, e.start, e.count)) RELA_HIP(hipStreamWaitEvent(r->copy_stream, e.done, 0));
+    if (overlaps(start, count, e.start, e.count)) {
+      RELA_HIP(hipStreamWaitEvent(writer, e.done, 0));
+      r->last_eviction_waits += 1;
+    }
   return RELA_OK;
 }
 // ... and closes it: the producer may reuse its source rows once the copies ran
@@ -1076,6 +1066,7 @@ extern "C" int rela_replay_write_rows(rela_replay* r, int first_slot, int offset
   }
   if (small.n > 0) {
     ProfScope prof("replay_scatter_small", r->copy_stream);
+    note_launch("replay_scatter_small");
     hipLaunchKernelGGL(replay_scatter_small, dim3(ceil_div(count, 256)), dim3(256), 0, r->copy_stream, small, count, r->ring,
                        start);
   }
@@ -1136,15 +1127,54 @@ extern "C" int rela_replay_direct_rows(rela_replay* r, int first_slot, int count
   hipStream_t producer = (hipStream_t)stream_;
   DeviceGuard g(r->device);
   std::lock_guard<std::mutex> lk(r->m);
-  auto overlaps = [&](int a0, int an, int b0, int bn) {  // ring intervals [a0, a0 + an) and [b0, b0 + bn)
-    const int d = ((b0 - a0) % r->ring + r->ring) % r->ring;
-    return d < an || d + bn > r->ring;
-  };
-  for (auto& e : r->evictions)
-    if (overlaps(first_slot, count, e.start, e.count)) RELA_HIP(hipStreamWaitEvent(producer, e.done, 0));
+  if (int rc = eviction_waits(r, producer, first_slot, count)) return rc;
   *base_dev = r->fields[(size_t)field].base;
   *ring = r->ring;
   if (row_bytes) *row_bytes = r->sc.row_bytes[(size_t)field];
+  return RELA_OK;
+}
+
+// The same for the block's SMALL fields and its WEIGHTS, for a producer whose own kernel computes the priorities and can
+// finish the rows in the same launch (the Ape-X shard's td_kernel_insert): the bases and row sizes of the listed fields
+// (plain fields of at most kSmallRowBytes, the ones write_rows moves with replay_scatter_small), the weight ring, alpha
+// and the ring length, and on the producer's stream the same eviction waits.  The producer stores w[sh] =
+// pow(priority, alpha) as replay_append_pow does, keeps the block's weights in row order in a buffer of its own and
+// commits with rela_replay_commit_add_weighted.
+// Why the weight ring may be written from the producer's stream: (1) sample's scan reads d_w through ring_load /
+// SeqRingAt (seqsum.hip, seqsum_dev.h) for k < size = safe_size only, i.e. inside [head, head + safe_size), and
+// replay_update writes the ids of such a scan; the reserved block lies outside that range until publish_block, and the
+// scan of every later sample runs on the replay stream behind the commit's wait for the producer's event.  (2) The last
+// readers of these slots' OLD weights are the scans of the samples that evicted them; their events (recorded behind those
+// samples' gathers, hence behind their scans) are the waits placed here.  (3) rela_replay_abort_add zeroes the block's
+// weights on the replay stream with no order against the producer: a producer that aborts after its kernel was queued
+// synchronises its stream first (actor.hip does).
+// Decoupled insert form: *weights_dev = NULL and nothing else is done -- the caller inserts as usual.
+extern "C" int rela_replay_direct_small(rela_replay* r, int first_slot, int count, const int* fields, int nfields,
+                                        void** base_dev, int64_t* row_bytes, int* ring, float** weights_dev, float* alpha,
+                                        void* stream_) {
+  RELA_CHECK(r && count > 0 && first_slot >= 0 && first_slot < r->ring && count <= r->ring && nfields >= 0 &&
+                 (nfields == 0 || (fields && base_dev && row_bytes)) && ring && weights_dev && alpha,
+             RELA_EINVAL, "rela_replay_direct_small: bad arguments");
+  for (int k = 0; k < nfields; ++k) {
+    const int f = fields[k];
+    RELA_CHECK(f >= 0 && f < (int)r->fields.size() && r->sc.steps[(size_t)f] == 1 && !r->sc.is_stack(f) &&
+                   r->sc.row_bytes[(size_t)f] <= kSmallRowBytes,
+               RELA_EINVAL, "rela_replay_direct_small: field %d is not a plain field of at most %d bytes per row", f,
+               kSmallRowBytes);
+  }
+  hipStream_t producer = (hipStream_t)stream_;
+  DeviceGuard g(r->device);
+  std::lock_guard<std::mutex> lk(r->m);
+  *weights_dev = nullptr;
+  if (r->decoupled_insert) return RELA_OK;
+  if (int rc = eviction_waits(r, producer, first_slot, count)) return rc;
+  for (int k = 0; k < nfields; ++k) {
+    base_dev[k] = r->fields[(size_t)fields[k]].base;
+    row_bytes[k] = r->sc.row_bytes[(size_t)fields[k]];
+  }
+  *ring = r->ring;
+  *weights_dev = r->d_w;
+  *alpha = r->alpha;
   return RELA_OK;
 }
 
@@ -1163,12 +1193,15 @@ static int launch_append(rela_replay* r, const float* prio, int n, int first_slo
       r->tmpw_cap = n;
     }
     ProfScope prof("replay_append_weights", r->stream);
+    note_launch("replay_append_pow");
     hipLaunchKernelGGL(replay_append_pow, dim3((n + 255) / 256), dim3(256), 0, r->stream, prio, n, r->alpha, r->d_w,
                        r->ring, first_slot, group_rows, r->d_tmpw);
+    note_launch("replay_append_sums");
     hipLaunchKernelGGL(replay_append_sums, dim3(1), dim3(kThreads), 0, r->stream, (const float*)r->d_tmpw, n, group_rows,
                        r->d_state);
   } else {
     ProfScope prof("replay_append_weights", r->stream);
+    note_launch("replay_append_weights");
     hipLaunchKernelGGL(replay_append_weights, dim3(1), dim3(kThreads), 0, r->stream, prio, n, r->alpha, r->d_w, r->ring,
                        first_slot, group_rows, r->d_state);
   }
@@ -1233,6 +1266,40 @@ extern "C" int rela_replay_commit_add_grouped(rela_replay* r, int first_slot, in
   if (int rc = launch_append(r, r->d_pstage[k], n, first_slot, group_rows)) return rc;
   RELA_HIP(hipEventRecord(r->ev_done[k], r->stream));
   r->pstage_used[k] = true;
+  publish_block(r, lk, first_slot, n, true);
+  return RELA_OK;
+}
+
+// The commit of a block whose producer has written the weights itself (rela_replay_direct_small): d_w holds them, and
+// weights_dev -- the producer's buffer -- holds them in row order.  In-order form only.  What is left of blockAppend is
+// the ordered sums: the replay stream waits for the producer's event and runs replay_append_sums alone, the arithmetic of
+// replay_append_weights / replay_append_pow + replay_append_sums on the same numbers.  weights_dev is read on the replay
+// stream: done_event (a hipEvent_t of the producer's) is recorded behind that read, and the producer waits for it before
+// it writes the buffer again -- a producer with two buffers and two events never stalls on the replay stream; NULL: the
+// producer's stream waits here, as after rela_replay_commit_add.
+extern "C" int rela_replay_commit_add_weighted(rela_replay* r, int first_slot, int n, int group_rows,
+                                               const float* weights_dev, void* done_event, void* stream_) {
+  RELA_CHECK(r && n > 0 && weights_dev && group_rows >= 0, RELA_EINVAL, "rela_replay_commit_add_weighted: bad arguments");
+  hipStream_t producer = (hipStream_t)stream_;
+  DeviceGuard g(r->device);
+  std::unique_lock<std::mutex> lk(r->m);
+  RELA_CHECK(!r->decoupled_insert, RELA_ESTATE, "rela_replay_commit_add_weighted: not in the decoupled insert form");
+  r->cv_tail.wait(lk, [&] { return r->shut || r->safe_tail == first_slot; });  // in-order commit :69
+  if (r->safe_tail != first_slot) return RELA_EWOULDBLOCK;  // shut down while an earlier block never committed
+  RELA_HIP(hipEventRecord(r->ev_in, producer));
+  RELA_HIP(hipStreamWaitEvent(r->stream, r->ev_in, 0));
+  {
+    ProfScope prof("replay_append_sums", r->stream);  // (its own scope: not the cost of a whole replay_append_weights)
+    note_launch("replay_append_sums");
+    hipLaunchKernelGGL(replay_append_sums, dim3(1), dim3(kThreads), 0, r->stream, weights_dev, n, group_rows, r->d_state);
+  }
+  RELA_LAUNCH_CHECK();
+  if (done_event) {
+    RELA_HIP(hipEventRecord((hipEvent_t)done_event, r->stream));
+  } else {
+    RELA_HIP(hipEventRecord(r->ev_out, r->stream));
+    RELA_HIP(hipStreamWaitEvent(producer, r->ev_out, 0));
+  }
   publish_block(r, lk, first_slot, n, true);
   return RELA_OK;
 }
@@ -1521,6 +1588,17 @@ extern "C" int rela_replay_debug_weights(rela_replay* r, float* weights_host, ui
   if (evicted_host)
     RELA_HIP(hipMemcpyAsync(evicted_host, r->d_evicted, (size_t)r->ring, hipMemcpyDeviceToHost, r->stream));
   RELA_HIP(hipStreamSynchronize(r->stream));
+  return RELA_OK;
+}
+
+// Test tap: the eviction list -- entries whose sample may still be reading the slots it evicted, events parked in the
+// pool, and the waits the last writer of rows was given (write_rows, direct_rows, direct_small).
+extern "C" int rela_replay_debug_evictions(rela_replay* r, int* pending, int* pooled, int* last_waits) {
+  RELA_CHECK(r, RELA_EINVAL, "rela_replay_debug_evictions: bad arguments");
+  std::lock_guard<std::mutex> lk(r->m);
+  if (pending) *pending = (int)r->evictions.size();
+  if (pooled) *pooled = (int)r->ev_pool.size();
+  if (last_waits) *last_waits = r->last_eviction_waits;
   return RELA_OK;
 }
 

@@ -149,8 +149,9 @@ class ApexActorEngine:
 
     def set_fused_insert(self, on):
         """1 / True: the target forward of post_step stores next_obs into the replay's rows itself where it can (f32x3,
-        512 rows and up, the shard as one block); 2 (default): obs as well, so the insert copies no frame rows;
-        0 / False: the insert copies every field."""
+        512 rows and up, the shard as one block); 2: obs as well, so the insert copies no frame rows; 3 (default): as 2,
+        and the TD kernel stores the block's small fields and weights, so the insert is one launch on the replay's
+        stream; 0 / False: the insert copies every field."""
         capi.check(capi.lib.rela_apex_actor_set_fused_insert(self.h, int(on)), "rela_apex_actor_set_fused_insert")
 
     def next_obs_slot(self):
