@@ -1009,6 +1009,15 @@ int rela_r2d2_learner_set_lstm_in_rec3(rela_r2d2_learner* l, int on);
  * RELA_R2D2_REC=steps or on a device whose CUs cannot hold the grid.  Before or after load; takes effect from the next
  * rela_r2d2_learner_loss / _backward.  NULL learner or other values: RELA_EINVAL. */
 int rela_r2d2_learner_set_rec_wide(rela_r2d2_learner* l, int on);
+/* on = 1: a batch of 129 .. 256 rows runs the forward recurrence of both nets as ONE persistent launch, lstm_rec_chain64
+ * (csrc/learner_r2d2.hip: lstm_rec_chain's chains with 64 batch rows each, four 16-row sub-tiles per B fragment, partial
+ * tiles in 133,120 B of dynamic LDS, the same bounded hand-off and timeout word, so rela_r2d2_learner_check covers it),
+ * instead of a split-K GEMM and a cell launch per net and time step; a row's sums keep lstm_rec_chain's order.  0
+ * (default): the per-step launches.  Independent of rela_r2d2_learner_set_rec_wide: batches of up to 128 rows and over
+ * 256 rows are not affected, nor is the BPTT (per-step above 128 rows), nor a learner created with RELA_R2D2_REC=steps
+ * or on a device without 256 CUs that hold one such block each.  Before or after load; takes effect from the next
+ * rela_r2d2_learner_loss / _backward.  NULL learner or other values: RELA_EINVAL. */
+int rela_r2d2_learner_set_rec_wide256(rela_r2d2_learner* l, int on);
 /* as rela_apex_learner_set_value_rescale, for the per-timestep target of td_err (r2d2.py:172-176):
  * h(reward[i] + bootstrap[i] * gamma ** n * h_inv(target_qa[i + n])).  Padding, the eta-mixed priority and the gradient
  * keep their logic.  Before the first rela_r2d2_learner_loss / _backward only (later: RELA_ESTATE). */

@@ -304,6 +304,7 @@ _sig("rela_r2d2_learner_set_wgrad_x3", i32, [vp, i32])
 _sig("rela_r2d2_learner_set_wgrad3_x3", i32, [vp, i32])
 _sig("rela_r2d2_learner_set_lstm_in_rec3", i32, [vp, i32])
 _sig("rela_r2d2_learner_set_rec_wide", i32, [vp, i32])
+_sig("rela_r2d2_learner_set_rec_wide256", i32, [vp, i32])
 _sig("rela_r2d2_learner_set_value_rescale", i32, [vp, f32])
 _sig("rela_r2d2_learner_debug_heads", i32, [vp, P(vp), P(vp), P(vp), P(vp), P(vp), P(i32)])
 _sig("rela_r2d2_learner_debug_trunk", i32, [vp, P(vp), P(vp), P(vp), P(i32)])

@@ -517,6 +517,157 @@ __global__ __launch_bounds__(kRecThreads) void lstm_rec_chain32(ChainArgs2 a) {
   }
 }
 
+// ---- persistent recurrent forward, 64-row chains (batches of 129 .. 256 rows; ..._set_rec_wide256) --------------
+// lstm_rec_chain32 with 64 batch rows per chain: a CHAIN is one net x one tile of 64 rows (2 x 4 chains = 256 rows) on
+// the 32 blocks whose ids are equal mod 8; block j owns hidden units 16 j .. 16 j + 15 and holds the same 64 B-fragment
+// registers of W_hh^T per lane, each now feeding FOUR 16-row sub-tiles: per step wave w loads its k-slice [64 w, 64 w +
+// 64) of h_{t-1} for the tile's sub-tiles (16 sc1 loads of 16 bytes in flight), then runs 4 x 4 x 16
+// v_mfma_f32_16x16x4_f32 with four independent accumulators per B register.  The number of sub-tiles that hold rows,
+// NS = 1 .. 4, is block-uniform and picks one of four unrolled bodies (rec64_partials<NS>), so a ragged tile issues no
+// load, MFMA or LDS store for an empty sub-tile; rows past the batch inside the last used sub-tile re-read the tile's
+// last row and are never read back.  ORDER OF SUMMATION per (row, gate column): lstm_rec_chain's -- within wave w the
+// 16 MFMAs in k-step order, then x-part + partial of wave 0 + ... + wave 7 -- so a row's h_t has the same bits whatever
+// rows share its chain.  The partial tiles [8][64][65] f32 are 133,120 B of dynamic LDS (of a CU's 160 KB; the limit is
+// raised at create).  The cell covers 64 x 16 (row, unit) pairs on 512 threads: thread (r, u) owns rows r and r + 32 of
+// unit u, both c_t in registers, the gx of step t + 1 of both in flight across the hand-off wait.  Hand-off:
+// lstm_rec_chain's, unchanged (one counter per chain and step, 32 arrivals, every storing wave drained, one lane polling
+// with bounded spins, the timeout word, sc1 loads of h_{t-1}).  Resources and timings: profiles/rec_wide256_ab.md.
+constexpr int kWide64Rows = 64;
+constexpr size_t kWide64LdsBytes = sizeof(float) * 8 * kWide64Rows * 65;
+// one wave's partial tiles of one step: h_{t-1} (float index hoff0 + row * kHid of the buffer) x its k-slice of the B
+// fragments -> red[64 rows][65], sub-tiles 0 .. NS - 1
+template <int NS>
+__device__ __forceinline__ void rec64_partials(const __amdgpu_buffer_rsrc_t rsH, const float* H, size_t hoff0, int nrow,
+                                               int li, int g, const float (&bfr)[4][16], float* red) {
+  float4 hv[NS][4];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const size_t hoff = hoff0 + (size_t)min(16 * s + li, nrow - 1) * kHid;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) hv[s][q] = ld4_shared<true>(rsH, H, hoff + 4 * q);
+  }
+  f32x4 acc[NS][4];
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[s][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) {  // (NS independent accumulators per B register)
+      const int q = ks >> 2, e = ks & 3;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const float av = e == 0 ? hv[s][q].x : e == 1 ? hv[s][q].y : e == 2 ? hv[s][q].z : hv[s][q].w;
+        acc[s][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bfr[c][ks], acc[s][c], 0, 0, 0);
+      }
+    }
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[(16 * s + 4 * g + r) * 65 + c * 16 + li] = acc[s][c][r];
+}
+
+__global__ __launch_bounds__(kRecThreads) void lstm_rec_chain64(ChainArgs2 a) {
+  extern __shared__ __attribute__((aligned(16))) float wide64_red[];  // [8 waves][64 rows][65]
+  __shared__ int alive;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int li = lane & 15, g = lane >> 4;
+  const int chain = blockIdx.x & 7, j = blockIdx.x >> 3;  // chain = (net, row tile); j = unit block
+  const RecNet nt = a.net[chain >> 2];
+  const int row0 = (chain & 3) * kWide64Rows;
+  if (row0 >= a.Bn) return;  // (the whole chain leaves: its counters are its own)
+  const int nrow = min(kWide64Rows, a.Bn - row0);
+  const int nsub = (nrow + 15) >> 4;  // (block-uniform) sub-tiles that hold rows
+  // B fragments: column tile c = gate c, column li = unit 16 j + li; wave w: k in [64 w, 64 w + 64)
+  float bfr[4][16];
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) bfr[c][ks] = nt.whhT[(size_t)(wave * 64 + 16 * g + ks) * kGates + c * kHid + 16 * j + li];
+  const size_t blk = (size_t)a.Bn * kHid;
+  const __amdgpu_buffer_rsrc_t rsH = sc1_rsrc(nt.H, (size_t)(a.T + 1) * blk * 4);
+  // the cell's thread: unit u = tid & 15, rows cr and cr + 32, cr = tid >> 4
+  const int cu = tid & 15, cr = tid >> 4;
+  const bool cell[2] = {cr < nrow, cr + 32 < nrow};
+  const int crow[2] = {row0 + cr, row0 + cr + 32};
+  float c_reg[2] = {0.f, 0.f};
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+    if (cell[p]) c_reg[p] = nt.C[(size_t)crow[p] * kHid + 16 * j + cu];  // slot 0 = the initial state
+  float gpre[2][4];
+  auto gx_fetch = [&](int t) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      if (!cell[p]) continue;
+      const float* grow = nt.gx + ((size_t)t * a.Bn + crow[p]) * kGates + 16 * j + cu;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) gpre[p][q] = grow[q * kHid];
+    }
+  };
+  gx_fetch(0);
+  float* red = wide64_red + (size_t)wave * kWide64Rows * 65;
+  unsigned* bar = a.bar + (size_t)chain * a.Tpad;
+  for (int t = 0; t < a.T; ++t) {
+    const size_t hoff0 = (size_t)t * blk + (size_t)row0 * kHid + wave * 64 + 16 * g;
+    switch (nsub) {
+      case 1: rec64_partials<1>(rsH, nt.H, hoff0, nrow, li, g, bfr, red); break;
+      case 2: rec64_partials<2>(rsH, nt.H, hoff0, nrow, li, g, bfr, red); break;
+      case 3: rec64_partials<3>(rsH, nt.H, hoff0, nrow, li, g, bfr, red); break;
+      default: rec64_partials<4>(rsH, nt.H, hoff0, nrow, li, g, bfr, red); break;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      if (!cell[p]) continue;
+      float pre[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        pre[q] = gpre[p][q];
+#pragma unroll
+        for (int w = 0; w < 8; ++w) pre[q] += wide64_red[((size_t)w * kWide64Rows + cr + 32 * p) * 65 + q * 16 + cu];
+      }
+      // the state that ENTERS the first training step is zeroed where the burn-in was a dummy (r2d2.py:149-154)
+      const bool zero = a.burn > 0 && t + 1 == a.burn && a.term[(size_t)(a.burn - 1) * a.Bn + crow[p]] != 0;
+      const float gi = sigm(pre[0]), gf = sigm(pre[1]), gg = tanhf(pre[2]), go = sigm(pre[3]);
+      float c = gf * c_reg[p] + gi * gg;
+      float h = go * tanhf(c);
+      if (zero) c = 0.f, h = 0.f;
+      c_reg[p] = c;
+      const size_t o = (size_t)(t + 1) * blk + (size_t)crow[p] * kHid + 16 * j + cu;
+      __hip_atomic_store((gu32*)(nt.H + o), __float_as_uint(h), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // write-through
+      nt.C[o] = c;
+      if (nt.save && t >= a.burn) {
+        float* grow = nt.gx + ((size_t)t * a.Bn + crow[p]) * kGates + 16 * j + cu;
+        grow[0] = gi, grow[kHid] = gf, grow[2 * kHid] = gg, grow[3 * kHid] = go;
+      }
+    }
+    if (t + 1 == a.T) break;
+    // grid barrier of the chain: every storing wave drains its stores, then ONE lane signals and polls
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    gx_fetch(t + 1);  // in flight across the wait
+    if (tid == 0) {
+      gu32* cnt = (gu32*)(bar + t);
+      __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      bool ok = true;
+      for (unsigned spins = 0; __hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)kChainBlocks;) {
+        __builtin_amdgcn_s_sleep(1);
+        if (++spins > kRecSpinLimit || __hip_atomic_load((gu32*)a.tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+          __hip_atomic_store((gu32*)a.tmo, (unsigned)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          ok = false;
+          break;
+        }
+      }
+      alive = ok ? 1 : 0;
+    }
+    __syncthreads();
+    if (!alive) return;
+  }
+}
+
 // ---- persistent BPTT: XCD-local chains (batches of up to 128 rows) ---------------------------------------------
 // The seq_len + n backward steps of the online net in ONE launch (2 launches per step before r2: a split-K GEMM for
 // dh = dgates_{t+1} x W_hh and the cell kernel; launch gaps alone cost ~1 ms per learner step).  chain = tile of 16
@@ -805,6 +956,9 @@ struct rela_r2d2_learner : LearnerCore {
   // rela_r2d2_learner_set_rec_wide: batches of 65 .. 128 rows run the forward recurrence on lstm_rec_chain32;
   // rec_wide_fit: its 256 blocks (66,560 B of dynamic LDS each) are resident at once (checked at create)
   bool rec_wide = false, rec_wide_fit = false;
+  // rela_r2d2_learner_set_rec_wide256: batches of 129 .. 256 rows run it on lstm_rec_chain64; rec_wide256_fit: its 256
+  // blocks (133,120 B of dynamic LDS each) are resident at once (checked at create)
+  bool rec_wide256 = false, rec_wide256_fit = false;
   // 1: the target net's conv trunk (no gradient, activations never read back) and the three large GEMMs of the LSTM's
   //    input side (gate GEMM of both nets, its data and weight gradients) on split-bf16 MFMA (gemm_bf16s.h)
   int precision = 0;
@@ -1126,7 +1280,9 @@ int forward_both(rela_r2d2_learner* l, int Bn, const uint8_t* obs, const float* 
   rc = forward_pre(l, 0, Bn, obs, h0, c0, s);
   if (rc != RELA_OK) return rc;
   const bool wide = l->rec_persist && l->rec_wide && l->rec_wide_fit && Bn > 64 && Bn <= 4 * kWideRows;
-  if ((l->rec_persist && l->rec_chains_fit && Bn <= 64) || wide) {
+  const bool wide64 =
+      l->rec_persist && l->rec_wide256 && l->rec_wide256_fit && Bn > 4 * kWideRows && Bn <= 4 * kWide64Rows;
+  if ((l->rec_persist && l->rec_chains_fit && Bn <= 64) || wide || wide64) {
     // arrival counters of this launch: [8 chains][Tpad] (the timeout word rec_bar[0] is sticky until ..._check)
     const int Tpad = (T + 3) / 4 * 4;
     RELA_HIP(hipMemsetAsync(l->rec_chain_bar, 0, sizeof(unsigned) * (size_t)(8 * Tpad), s));
@@ -1136,7 +1292,11 @@ int forward_both(rela_r2d2_learner* l, int Bn, const uint8_t* obs, const float* 
       ca.net[w].bar = nullptr, ca.net[w].save = w == 0 ? 1 : 0;
     }
     ca.term = term, ca.tmo = l->rec_bar, ca.bar = l->rec_chain_bar, ca.T = T, ca.Tpad = Tpad, ca.Bn = Bn, ca.burn = burn;
-    if (wide) {  // 32 rows per chain: the same grid, arguments and counters
+    if (wide64) {  // 64 rows per chain: the same grid, arguments and counters
+      ProfScope prof("learner_lstm_rec_wide256", s);
+      note_launch("lstm_rec_chain64");
+      hipLaunchKernelGGL(lstm_rec_chain64, dim3(8 * kChainBlocks), dim3(kRecThreads), kWide64LdsBytes, s, ca);
+    } else if (wide) {  // 32 rows per chain: the same grid, arguments and counters
       ProfScope prof("learner_lstm_rec_wide", s);
       note_launch("lstm_rec_chain32");
       hipLaunchKernelGGL(lstm_rec_chain32, dim3(8 * kChainBlocks), dim3(kRecThreads), kWideLdsBytes, s, ca);
@@ -1235,6 +1395,14 @@ int build_learner(rela_r2d2_learner* l, int num_action, int max_batch, int multi
         hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_w, lstm_rec_chain32, kRecThreads, kWideLdsBytes) != hipSuccess)
       occ_w = 0, (void)hipGetLastError();
     l->rec_wide_fit = room(occ_w) >= 8 * kChainBlocks;
+    // lstm_rec_chain64 (set_rec_wide256): 133,120 B of dynamic LDS per block, so one block per CU at the most and the
+    // grid needs 256 CUs; the same two steps, the same consequence
+    int occ_w64 = 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_rec_chain64), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)kWide64LdsBytes) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_w64, lstm_rec_chain64, kRecThreads, kWide64LdsBytes) != hipSuccess)
+      occ_w64 = 0, (void)hipGetLastError();
+    l->rec_wide256_fit = room(occ_w64) >= 8 * kChainBlocks;
   }
   if (int rc = m.alloc(&l->ha, rowsTr * 32, false)) return rc;
   if (int rc = m.alloc(&l->q_on, rowsTr * A, false)) return rc;
@@ -1412,6 +1580,12 @@ extern "C" int rela_r2d2_learner_set_lstm_in_rec3(rela_r2d2_learner* l, int on) 
 extern "C" int rela_r2d2_learner_set_rec_wide(rela_r2d2_learner* l, int on) {
   RELA_CHECK(l && (on == 0 || on == 1), RELA_EINVAL, "rela_r2d2_learner_set_rec_wide: needs a learner and on = 0 or 1");
   l->rec_wide = on != 0;  // (forward_both: lstm_rec_chain32 for 65 .. 128 rows where its grid fits)
+  return RELA_OK;
+}
+
+extern "C" int rela_r2d2_learner_set_rec_wide256(rela_r2d2_learner* l, int on) {
+  RELA_CHECK(l && (on == 0 || on == 1), RELA_EINVAL, "rela_r2d2_learner_set_rec_wide256: needs a learner and on = 0 or 1");
+  l->rec_wide256 = on != 0;  // (forward_both: lstm_rec_chain64 for 129 .. 256 rows where its grid fits)
   return RELA_OK;
 }
 

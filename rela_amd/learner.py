@@ -405,6 +405,13 @@ class HipR2D2Learner(_HipLearner):
         rela_r2d2_learner_set_rec_wide."""
         self._call("set_rec_wide", int(bool(on)))
 
+    def set_rec_wide256(self, on):
+        """True: a batch of 129 .. 256 rows runs the forward recurrence of both nets as one persistent launch
+        (lstm_rec_chain64, csrc/learner_r2d2.hip: chains of 64 batch rows) instead of per-step launches; False (default):
+        the per-step launches.  Independent of set_rec_wide; other batch sizes and the BPTT are not affected.  From the
+        next step on.  rela_r2d2_learner_set_rec_wide256."""
+        self._call("set_rec_wide256", int(bool(on)))
+
     def check(self):
         """Synchronises and raises if a grid barrier of the persistent recurrent kernels gave up since the last check."""
         self._call("check", self._stream())

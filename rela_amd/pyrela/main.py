@@ -34,7 +34,7 @@ LEARNER_PRECISIONS = ("f32", "bf16x2", "f32x3", "f32x3_bwd")
 LEARNER_DGRADS = ("mode", "x3")  # --learner_dgrad
 LEARNER_WGRADS = ("mode", "x3", "x3_all")  # --learner_wgrad
 LEARNER_LSTM_INS = ("mode", "rec3")  # --learner_lstm_in
-LEARNER_RECS = ("mode", "wide")  # --learner_rec
+LEARNER_RECS = ("mode", "wide", "wide256")  # --learner_rec
 
 
 def parse_args(argv=None):
@@ -94,8 +94,10 @@ def parse_args(argv=None):
                    help="the LSTM's input-side backward GEMMs of the HIP R2D2 learner step: mode = what --learner_precision "
                         "runs; rec3 = three-part record GEMMs, f32 accuracy (set_lstm_in_rec3 of rela_amd/learner.py)")
     p.add_argument("--learner_rec", type=str, default="mode", choices=LEARNER_RECS,
-                   help="the forward recurrence of the HIP R2D2 learner step at 65 .. 128 batch rows: mode = per-step "
-                        "launches; wide = one persistent launch, lstm_rec_chain32 (set_rec_wide of rela_amd/learner.py)")
+                   help="the forward recurrence of the HIP R2D2 learner step above 64 batch rows: mode = per-step launches; "
+                        "wide = one persistent launch at 65 .. 128 rows, lstm_rec_chain32 (set_rec_wide of "
+                        "rela_amd/learner.py); wide256 = wide, and one persistent launch at 129 .. 256 rows as well, "
+                        "lstm_rec_chain64 (set_rec_wide256)")
     p.add_argument("--learner_wgrad", type=str, default="mode", choices=LEARNER_WGRADS,
                    help="conv1 / conv2 weight gradients of the HIP learner step: mode = what --learner_precision runs; x3 = "
                         "three-part bf16 space-to-depth kernels, f32 accuracy (set_wgrad_x3 of rela_amd/learner.py); x3_all = "
@@ -227,16 +229,22 @@ def learner_lstm_in_rec3(args):
 
 
 def learner_rec_wide(args):
-    """--learner_rec as the R2D2 learner's set_rec_wide argument, checked against --algo and --hip_learner."""
+    """--learner_rec as the R2D2 learner's set_rec_wide argument (wide and wide256), checked against --algo and
+    --hip_learner."""
     choice = getattr(args, "learner_rec", "mode")
     if choice not in LEARNER_RECS:
         raise SystemExit("--learner_rec must be one of %s" % ", ".join(LEARNER_RECS))
-    if choice == "wide" and not getattr(args, "hip_learner", 1):
-        raise SystemExit("--learner_rec wide needs the HIP learner step (--hip_learner 1): the PyTorch autograd step has "
+    if choice != "mode" and not getattr(args, "hip_learner", 1):
+        raise SystemExit("--learner_rec wide / wide256 needs the HIP learner step (--hip_learner 1): the PyTorch autograd step has "
                          "no such kernel")
-    if choice == "wide" and args.algo != "r2d2":
-        raise SystemExit("--learner_rec wide is the R2D2 learner's option (--algo r2d2): the Ape-X net has no LSTM")
-    return choice == "wide"
+    if choice != "mode" and args.algo != "r2d2":
+        raise SystemExit("--learner_rec wide / wide256 is the R2D2 learner's option (--algo r2d2): the Ape-X net has no LSTM")
+    return choice != "mode"
+
+
+def learner_rec_wide256(args):
+    """--learner_rec as the R2D2 learner's set_rec_wide256 argument, after learner_rec_wide's checks."""
+    return learner_rec_wide(args) and args.learner_rec == "wide256"
 
 
 def train(args, on_epoch=None):
@@ -283,6 +291,8 @@ def train(args, on_epoch=None):
             learner.set_lstm_in_rec3(True)
         if rec_wide:
             learner.set_rec_wide(True)
+        if learner_rec_wide256(args):
+            learner.set_rec_wide256(True)
 
     # create eval locker here, as upstream (main.py:115-116): replicas on the host, device string "cpu"
     eval_locker = rela.ModelLocker([type(agent).clone(agent, "cpu")], "cpu")
@@ -487,6 +497,8 @@ def _multi_worker(rank, world, args, port, results):
             learner.set_lstm_in_rec3(True)
         if learner_rec_wide(args):
             learner.set_rec_wide(True)
+        if learner_rec_wide256(args):
+            learner.set_rec_wide256(True)
         # scheduled exchange: command words (a host synchronisation on every rank) only with the weight publish every
         # actor_sync_freq steps; the sample / update_priority pairs in between follow the announced cycle
         if native:  # partitions and flat buffers mapped through HIP IPC: rows and weights never enter a collective

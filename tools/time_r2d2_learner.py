@@ -12,6 +12,8 @@
       -> the same for rec_wide and the forward recurrence's scopes (per-step: learner_lstm_rec_fwd + learner_lstm_cell, the
          two zeroing launches have no scope; wide: learner_lstm_rec_wide), after three legs of the same learner at B = 64
          on lstm_rec_chain (profiles/rec_wide_ab.md)
+  REC_WIDE256_AB=7 ITERS=10 B=256 python tools/time_r2d2_learner.py
+      -> the same for rec_wide256 (on: learner_lstm_rec_wide256), without the legs at B = 64 (profiles/rec_wide256_ab.md)
 """
 import ctypes as C
 import json
@@ -106,6 +108,9 @@ if os.environ.get("REC_WIDE_AB"):  # (B=128: the option concerns 65 .. 128 rows)
         batch, weight = wide_batch
     alternate(int(os.environ["REC_WIDE_AB"]), "rec_wide", learner.set_rec_wide,
               ("learner_lstm_rec_fwd", "learner_lstm_cell", "learner_lstm_rec_wide"), "forward recurrence")
+if os.environ.get("REC_WIDE256_AB"):  # (B=256: the option concerns 129 .. 256 rows)
+    alternate(int(os.environ["REC_WIDE256_AB"]), "rec_wide256", learner.set_rec_wide256,
+              ("learner_lstm_rec_fwd", "learner_lstm_cell", "learner_lstm_rec_wide256"), "forward recurrence")
 
 for _ in range(2):
     learner.step(batch, weight)
